@@ -14,10 +14,12 @@ inside ONE launch of the fused sampler (qiddm_dense_sample: four wavefronts per 
 registers between steps and every intermediate image is written out, as Diffusion.sample records it):
 15 per launch (the reference's n_iters per Diffusion.sample call, src/mnist_exm.py:211), a remainder of K rides in
 the last launch.  Synthetic random-noise images (``rand*0.75+0.5``, src/mnist_exm.py:396), random-init weights
-under ``torch.manual_seed(42)``.  The K steps are recorded into hipGraphs and replayed; the timed region repeats
-the K steps until it is >= 50 ms long (``repeats``), bracketed by barrier + synchronize, max over ranks.
+under ``torch.manual_seed(42)``.  The K steps are recorded into hipGraphs and replayed; the timed region is exactly
+the K steps, bracketed by barrier + synchronize, max over ranks.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  A plain run times the headline only;
+``--full`` adds everything else the line can carry (kernel roofline, the reference's precision, training, secondary
+nets, CPU baseline).  ``--dump-outputs DIR`` writes the images of the last timed step as ``DIR/denoised_images.npy``.
 """
 from __future__ import annotations
 
@@ -46,6 +48,11 @@ def parse(argv=None):
     ap.add_argument("--steps-per-graph", type=int, default=15,
                     help="consecutive denoise steps of the sampling loop per launch of the fused sampler "
                          "(15 = the reference's n_iters per Diffusion.sample call)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: kernel roofline, the reference's precision, training, secondary nets and "
+                         "the CPU baseline (the --no-* options below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the images of the last timed step to DIR/denoised_images.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary (non-headline) timings")
     ap.add_argument("--no-train", action="store_true", help="skip the data-parallel training-step timing")
@@ -56,7 +63,10 @@ def parse(argv=None):
                          "group is gloo (RCCL refuses two ranks on one device); timings are meaningless")
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="print the command `--gpus N` would start (JSON) and exit; touches no GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port() -> int:
@@ -229,6 +239,12 @@ class Runner:
             for chunk in set(self._chunks(k)):
                 self._graph(chunk)
 
+    def warm(self, k):
+        """Replay each graph of the k-step plan once, untimed and uncounted (the first replay of a fresh graph is slow)."""
+        if self.use_graph:
+            for chunk in set(self._chunks(k)):
+                self._graph(chunk).replay()
+
     def run(self, k):
         if not self.use_graph:
             for _ in range(k):
@@ -259,6 +275,25 @@ class Runner:
 
 
 def timed_region(runner, steps, warmup, world, dev):
+    """W untimed steps, then exactly K steps between barrier + synchronize, max over ranks; returns seconds."""
+    runner.prepare(steps)
+    runner.prepare(warmup)
+    runner.warm(steps)
+    runner.run(warmup)
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    runner.run(steps)
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    return _max_over_ranks(time.perf_counter() - t0, dev)
+
+
+def repeated_timed_region(runner, steps, warmup, world, dev):
     """W untimed steps, then `repeats` x exactly K steps between barrier + synchronize; returns (seconds, repeats)."""
     runner.prepare(steps)
     runner.prepare(warmup)
@@ -367,7 +402,7 @@ def f64_timed(dev, x0, args, spl, world):
     try:
         diff = build_model(dev)
         runner = Runner(diff, x0.to(dev), use_graph=not args.no_graph, spl=spl)
-        elapsed, repeats = timed_region(runner, args.steps, args.warmup, world, dev)
+        elapsed, repeats = repeated_timed_region(runner, args.steps, args.warmup, world, dev)
         plan = launch_plan(args.steps, spl)
         kspl = max(set(plan), key=plan.count) if plan else spl
         us = time_dominant_kernel(diff, x0.to(dev), kspl, launches=20)
@@ -790,6 +825,23 @@ def cpu_baseline(diff, x0_cpu, budget_s):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, name, t, budget):
+    """`t` as `out_dir/<name>.npy`, float64 kept, any other dtype as float32; an array over `budget` bytes is cut to a
+    fixed, seeded sample of its rows (the same rows on every run)."""
+    import numpy as np
+    a = t.detach().cpu().numpy()
+    if a.dtype != np.float64:
+        a = a.astype(np.float32)
+    if a.nbytes > budget:
+        keep = budget // (a.nbytes // a.shape[0])
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main(argv=None):
     args = parse(argv)
     world, rank, local = init_dist(args)
@@ -802,18 +854,21 @@ def main(argv=None):
     x0 = (torch.rand(args.batch, 1, IMG, IMG, dtype=torch.double) * 0.75 + 0.5)
     spl = 1 if args.no_graph else args.steps_per_graph
     runner = Runner(diff, x0.to(dev), use_graph=not args.no_graph, spl=spl)
-    elapsed, repeats = timed_region(runner, args.steps, args.warmup, world, dev)
+    elapsed = timed_region(runner, args.steps, args.warmup, world, dev)
+    value = world * args.batch * args.steps / elapsed
+    if args.dump_outputs:
+        # the resident batch after the last timed step: the image Diffusion.sample's caller gets from that step
+        dump_outputs(args.dump_outputs, "denoised_images" if world == 1 else f"denoised_images_rank{rank}",
+                     runner.x, DUMP_LIMIT_BYTES // world)
 
-    total_steps = args.steps * repeats
-    value = world * args.batch * total_steps / elapsed
     f64 = None
-    if not args.no_f64:
+    if args.full and not args.no_f64:
         try:
             f64 = f64_timed(dev, x0, args, spl, world)           # every rank: the region has barriers
         except Exception as e:  # pragma: no cover
             f64 = {"error": repr(e)}
     train = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         try:
             train = dp_train_measurement(dev, args.batch, world, rank)
         except Exception as e:  # pragma: no cover - must not cost the headline line
@@ -822,17 +877,8 @@ def main(argv=None):
     if rank == 0:
         try:
             plan = launch_plan(args.steps, spl)
-            kspl = max(set(plan), key=plan.count) if plan else spl     # the launch shape the timed region is made of
-            kern_us = time_dominant_kernel(diff, x0.to(dev), kspl)
             circ = diff.net._circuit_descriptor()
             g_per_sample = circ.gate_count()
-            alg_bytes = circ.algorithmic_bytes_per_sample("f32") * args.batch * kspl   # per launch
-            hbm_eq = alg_bytes / (kern_us * 1e-6) / 1e9
-            flop = lean_flop(N_QUBITS, QDEPTH, 1, IMG * IMG, False)   # what the kernel executes (tangent-form layers)
-            std_flop = dense_flop(N_QUBITS, QDEPTH, 1, IMG * IMG)     # the same circuit in the (c, s) form of round 2
-            valu_tf = flop * args.batch * kspl / (kern_us * 1e-6) / 1e12
-            io_bytes = kspl * args.batch * IMG * IMG * 8              # one image out per step (exact); the input image is not read:
-                                                                      # linear_down's output is a global phase of this circuit
             result = {
                 "metric": "denoise-step images/sec, 8-qubit MNIST-28",
                 "value": value,
@@ -840,9 +886,8 @@ def main(argv=None):
                 "n_gpus": world,
                 "steps": args.steps,
                 "warmup": args.warmup,
-                "repeats": repeats,
                 "timed_region_s": elapsed,
-                "ms_per_step": elapsed / total_steps * 1e3,
+                "ms_per_step": elapsed / args.steps * 1e3,
                 "higher_is_better": True,
                 "scaling": "weak",
                 "vs_baseline": None,
@@ -853,13 +898,23 @@ def main(argv=None):
                            "batch_per_gpu": args.batch, "global_batch": world * args.batch,
                            "n_qubits": N_QUBITS, "gates_per_sample": g_per_sample,
                            "launch": "eager" if args.no_graph else
-                           f"hipGraph replay; launches of the fused sampler hold {plan} steps for K={args.steps}; the K steps "
-                           f"are repeated {repeats}x inside the timed region"
-                           + (f", {Runner.GROUP} consecutive K-step launches per graph replay" if len(plan) == 1 else ""),
+                           f"hipGraph replay; launches of the fused sampler hold {plan} steps for K={args.steps}, up to "
+                           f"{runner.lpg} launches per graph replay; the timed region is the K steps once",
                            "backend": ("gloo (one-GPU rehearsal)" if args.rehearse_on_one_gpu else "nccl (RCCL)") if world > 1 else "none",
                            "parallelism": f"shard{world}"},
                 "gate_apps_per_s": value * g_per_sample,
-                "roofline": {
+            }
+            if args.full:
+                kspl = max(set(plan), key=plan.count) if plan else spl     # the launch shape the timed region is made of
+                kern_us = time_dominant_kernel(diff, x0.to(dev), kspl)
+                alg_bytes = circ.algorithmic_bytes_per_sample("f32") * args.batch * kspl   # per launch
+                hbm_eq = alg_bytes / (kern_us * 1e-6) / 1e9
+                flop = lean_flop(N_QUBITS, QDEPTH, 1, IMG * IMG, False)   # what the kernel executes (tangent-form layers)
+                std_flop = dense_flop(N_QUBITS, QDEPTH, 1, IMG * IMG)     # the same circuit in the (c, s) form of round 2
+                valu_tf = flop * args.batch * kspl / (kern_us * 1e-6) / 1e12
+                io_bytes = kspl * args.batch * IMG * IMG * 8              # one image out per step (exact); the input image is
+                                                                          # not read: linear_down's output is a global phase
+                result["roofline"] = {
                     # The statevector of an 8-qubit sample (2 KiB) lives in the registers of four wavefronts: the kernel
                     # is bounded by instruction issue / latency on the vector ALU, not by HBM.  frac = executed VALU flop
                     # / f32 vector peak; the counters behind "latency-bound" are in profiles/ (SQ_* passes).
@@ -884,20 +939,19 @@ def main(argv=None):
                                                "HBM simulator would move. Not a roofline fraction: the slab never leaves "
                                                "the registers"},
                     "note": HEADLINE_NOTE,
-                },
-            }
+                }
             if train:
                 result.update(train)
             if f64 is not None:
                 result["f64"] = f64
-            if world == 1:
+            if args.full and world == 1:
                 try:
                     result["roofline_c5"] = c5_roofline(dev)
                 except Exception as e:  # pragma: no cover
                     result["roofline_c5"] = {"error": repr(e)}
-            if not args.no_secondary and world == 1:
+            if args.full and not args.no_secondary and world == 1:
                 result["secondary"] = secondary_measurements(dev, args.batch)
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 cb = cpu_baseline(diff, x0, args.cpu_seconds)
                 v, sample = cb["batched"]
                 vl, sample_l = cb["per_sample_loop"]

@@ -1,11 +1,12 @@
 """CPU tests of bench.py's own machinery: the launch plan / Runner bookkeeping (the round-2 driver line lost two
 secondaries to `prepare(75); run(150)`), the N-rank self-launch command, and the line checker that turns any
-`error_*` key into a non-zero exit."""
+`error_*` key into a non-zero exit; one GPU test runs a plain benchmark end to end."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -114,6 +115,66 @@ def test_run_repeated_groups_eight_single_launch_blocks_per_replay():
     r.prepare_repeated(2000)
     assert all(len(set(k)) <= 2 for k in r.graphs)
     assert tuple(bench.launch_plan(2000, 15)) * bench.Runner.GROUP not in r.graphs
+
+
+@pytest.mark.parametrize("k,w", [(20, 5), (75, 0), (2000, 200)])
+def test_timed_region_is_exactly_k_steps_after_w_warmup(monkeypatch, k, w):
+    """`--steps K` is the number of timed steps: the region runs K once, and every graph it replays is recorded and
+    replayed before it starts."""
+    monkeypatch.setattr(bench.torch.cuda, "synchronize", lambda: None)
+    _, r = make_runner()
+    calls = []
+
+    def run(n, _run=r.run):
+        calls.append((n, {c: g.replays for c, g in r.graphs.items()}))     # the graphs as the run finds them
+        _run(n)
+    monkeypatch.setattr(r, "run", run)
+    elapsed = bench.timed_region(r, k, w, 1, "cpu")
+    assert elapsed > 0
+    assert [n for n, _ in calls] == [w, k] and r.steps_done == w + k
+    replays = calls[-1][1]
+    assert set(replays) == set(r.graphs) and r.lazy_records == 0
+    assert all(replays[c] >= 1 for c in r._chunks(k))
+
+
+def test_parse_full_and_dump_outputs():
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 20
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    t = torch.arange(40 * 6, dtype=torch.float64).reshape(40, 6)
+    bench.dump_outputs(str(tmp_path / "all"), "x", t, 1 << 20)
+    assert np.array_equal(np.load(tmp_path / "all" / "x.npy"), t.numpy())
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), "x", t, 10 * 6 * 8)
+    a, b = np.load(tmp_path / "s1" / "x.npy"), np.load(tmp_path / "s2" / "x.npy")
+    assert a.shape == (10, 6) and a.dtype == np.float64 and np.array_equal(a, b)    # a fixed sample of whole rows
+    assert all(any(np.array_equal(row, full) for full in t.numpy()) for row in a)
+    bench.dump_outputs(str(tmp_path / "half"), "x", t.half(), 1 << 20)
+    assert np.load(tmp_path / "half" / "x.npy").dtype == np.float32
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run prints the headline only; with the same arguments it computes the same images."""
+    outs = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup",
+                            "5", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=300,
+                           cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-4000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 30 and line["warmup"] == 5 and line["unit"] == "images/s"
+        assert line["value"] == pytest.approx(256 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+        assert not {"roofline", "f64", "secondary", "cpu_baseline", "train_images_per_s"} & set(line)
+        outs.append(np.load(tmp_path / d / "denoised_images.npy"))
+    assert outs[0].shape == (256, 1, 28, 28) and outs[0].dtype == np.float64 and np.isfinite(outs[0]).all()
+    np.testing.assert_allclose(outs[0], outs[1], rtol=0, atol=1e-6)
 
 
 def test_eager_runner_steps_one_at_a_time():

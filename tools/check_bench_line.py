@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Gate on a bench.py JSON line:  python bench.py ... | python tools/check_bench_line.py [--require KEY ...]
+"""Gate on a bench.py JSON line:  python bench.py --full ... | python tools/check_bench_line.py [--require KEY ...]
 
 Exits non-zero when the input holds no JSON line, when a contract field is missing, or when ANY key anywhere in
 the line contains "error" (every part of bench.py catches its own failure into such a key so that one broken secondary

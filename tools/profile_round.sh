@@ -16,7 +16,7 @@ S=$OUT/summary
 mkdir -p $S
 cd /tmp && export TMPDIR=/tmp
 BARGS=${*:---steps 20 --warmup 5 --no-secondary --no-cpu-baseline --no-train}
-BENCH="python3 $ROOT/bench.py $BARGS"
+BENCH="python3 $ROOT/bench.py --full $BARGS"
 WIDE="python3 $ROOT/tools/profile_wide.py"
 run() { # name, then the rocprofv3 args..., then -- cmd
   local name=$1; shift
