@@ -58,7 +58,8 @@ qiddm::KScalars params_of(const qiddm_circuit_t* c) {
 template <typename T, int N, int PPT, bool REUP, int LPR, bool POST>
 int launch_lean(const double* x, const double* wd, const double* bd, const double* wu, const double* bu, double* y,
                 const void* tables, const qiddm::QuadScalars& d, const qiddm::KScalars& p, int layers, hipStream_t st) {
-  const size_t smem = qiddm::LeanTables<T, N>::lds_bytes(layers, p.n_rounds);
+  const size_t smem = qiddm::LeanTables<T, N>::lds_bytes(layers, p.n_rounds,
+                                                         !qiddm::lean_tables_in_registers<REUP, LPR>());
   auto kern = qiddm::dense_lean_kernel<T, N, PPT, REUP, LPR, POST>;
   static qiddm_capi::DeviceFlags big_lds_enabled;
   if (smem > 48 * 1024 && !big_lds_enabled.get()) {
@@ -93,7 +94,8 @@ int dispatch_lean_n(const double* x, const double* wd, const double* bd, const d
       return launch_lean<T, N, 4, true, kReupLpr, POST>(x, wd, bd, wu, bu, y, tables, d, p, layers, st);
     return launch_lean<T, N, 4, true, 0, POST>(x, wd, bd, wu, bu, y, tables, d, p, layers, st);
   }
-  if (lpr == 14) return launch_lean<T, N, 4, false, 14, POST>(x, wd, bd, wu, bu, y, tables, d, p, layers, st);
+  // (the compiled-in count keeps the tables in registers for one round: qsim_lean.h)
+  if (lpr == 14 && p.n_rounds == 1) return launch_lean<T, N, 4, false, 14, POST>(x, wd, bd, wu, bu, y, tables, d, p, layers, st);
   return launch_lean<T, N, 4, false, 0, POST>(x, wd, bd, wu, bu, y, tables, d, p, layers, st);
 }
 template <typename T>
