@@ -186,3 +186,31 @@ def qconv2d_forward(x, weights, out_channels, kernel_size=(3, 3), padding=(1, 1)
     p = run_round(spec, feats, qw_map_tanh(weights.to(sv.RDT)).unsqueeze(0))
     p = torch.clamp(p * p.shape[-1] * 0.5, 0.0, 1.0)[:, ::2][:, :out_channels]
     return p.reshape(b, h_out, w_out, -1).permute(0, 3, 1, 2).contiguous()
+
+
+def qconv2d_forward_unitary(x, weights, out_channels, kernel_size=(3, 3), padding=(1, 1), clamp=True):
+    """``qconv2d_forward`` through the circuit's unitary: one statevector simulation of the ``2**n`` basis states
+    instead of one per output pixel, so it stays fast at training sizes (tens of thousands of pixels).
+
+    ``U`` comes from ``sv.strongly_entangling_layers`` applied to the identity's columns (row ``j`` of the result is
+    ``U|j>``, i.e. the result is ``U^T``); each unfolded patch is embedded by ``sv.amplitude_embedding`` (offset 0.1,
+    pad 0.5, normalised), and the probabilities are ``|v U^T|^2`` followed by the same clamp and even-index slice.
+    The embedded state is real, so the product is taken on the real and imaginary parts of ``U^T`` separately.
+    ``clamp=False`` returns the scaled probabilities before the [0, 1] clamp.
+    CPU torch float64 / complex128, differentiable through ``weights`` and ``x``."""
+    b, c, h_in, w_in = x.shape
+    kh, kw = kernel_size
+    n = qconv_wires(c, out_channels, kernel_size)
+    d = 2 ** n
+    h_out = h_in + 2 * padding[0] - kh + 1
+    w_out = w_in + 2 * padding[1] - kw + 1
+    ut = sv.strongly_entangling_layers(torch.eye(d, dtype=sv.CDT), qw_map_tanh(weights.to(sv.RDT)), n, "CNOT")
+    ut = ut[:, ::2][:, :out_channels]                 # only the read-out columns: U^T[:, 2k] = <2k|U|.>
+    cols = torch.nn.functional.unfold(x.to(sv.RDT), kernel_size=kernel_size, padding=padding)
+    feats = cols.permute(0, 2, 1).reshape(b * h_out * w_out, c * kh * kw)
+    v = sv.amplitude_embedding(feats + 0.1, n, pad_with=0.5, normalize=True).real
+    p = (v @ ut.real) ** 2 + (v @ ut.imag) ** 2
+    p = p * d * 0.5
+    if clamp:
+        p = torch.clamp(p, 0.0, 1.0)
+    return p.reshape(b, h_out, w_out, -1).permute(0, 3, 1, 2).contiguous()

@@ -47,15 +47,17 @@ def _bn(x, sd, prefix, training, eps=1e-5):
     return xn * w[None, :, None, None] + b[None, :, None, None]
 
 
-def unet_simple_forward(x, sd, depth=3, start_channels=8, training=False):
+def unet_simple_forward(x, sd, depth=3, start_channels=8, training=False, unitary=False):
     """``UNetUndirected.forward`` (``nn/unet.py:162-174``) over ``DownBlockS`` / ``UpBlockS``
-    (``nn/unet_simple.py:6-49``; block forwards ``nn/unet.py:70-75, 111-116``)."""
+    (``nn/unet_simple.py:6-49``; block forwards ``nn/unet.py:70-75, 111-116``).  ``unitary=True`` takes the quantum
+    convolutions through ``oc.qconv2d_forward_unitary`` (same values, fast enough for training-sized batches)."""
+    qconv = oc.qconv2d_forward_unitary if unitary else oc.qconv2d_forward
     x = x.double()
     skips = []
     out_ch = -1
     for i in range(depth):
         out_ch = start_channels * 2 ** i
-        x = oc.qconv2d_forward(x, sd[f"down_blocks.{i}.net.0.weights"], out_ch, (3, 3), (1, 1))
+        x = qconv(x, sd[f"down_blocks.{i}.net.0.weights"], out_ch, (3, 3), (1, 1))
         x = _bn(x, sd, f"down_blocks.{i}.net.1", training)
         skips.append(x)
         if i < depth - 1:                                       # no pooling in the last block (nn/unet.py:142)
@@ -64,9 +66,9 @@ def unet_simple_forward(x, sd, depth=3, start_channels=8, training=False):
         out_ch //= 2
         skip = skips[-(i + 2)]
         up = F.interpolate(x, scale_factor=2, mode="bilinear")   # torch.nn.Upsample(scale_factor=2, mode="bilinear")
-        up = oc.qconv2d_forward(up, sd[f"up_blocks.{i}.up_conv.1.weights"], out_ch, (1, 1), (0, 0))
+        up = qconv(up, sd[f"up_blocks.{i}.up_conv.1.weights"], out_ch, (1, 1), (0, 0))
         skip, up = autopad(skip, up)
         x = torch.cat([up, skip], dim=1)
-        x = oc.qconv2d_forward(x, sd[f"up_blocks.{i}.net.0.weights"], out_ch, (3, 3), (1, 1))
+        x = qconv(x, sd[f"up_blocks.{i}.net.0.weights"], out_ch, (3, 3), (1, 1))
         x = _bn(x, sd, f"up_blocks.{i}.net.1", training)
     return F.conv2d(x, sd["final_conv.weight"].double(), sd["final_conv.bias"].double())

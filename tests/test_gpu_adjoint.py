@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import circuits as oc
+from oracle.training import circuit_grads as _oracle_grads
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +24,6 @@ def _case(n, enc, imp, meas, L, S, batch, seed, feat=None, pad=0.0, offset=0.0, 
     cols = 2 ** n if meas == "probs" else n
     gout = torch.randn(batch, cols, generator=g, dtype=torch.float64)
     return circ, spec, x, w, gout
-
-
-def _oracle_grads(spec, x, w, gout):
-    w = w.clone().requires_grad_(True)
-    x = x.clone().requires_grad_(True)
-    loss = (oc.run_circuit(spec, x, w) * gout).sum()
-    return torch.autograd.grad(loss, [w, x])
 
 
 CASES = [

@@ -4,35 +4,11 @@
 import pytest
 import torch
 
+from oracle.training import dense_step as _oracle_step
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-
-
-def _oracle_step(kind, sd, x, noise, T, shape, goal, detach):
-    """loss and gradients by autograd through the oracle (CPU, float64)."""
-    from oracle import circuits as oc
-    from oracle import diffusion as odf
-    prm = {k: v.detach().cpu().double().clone().requires_grad_(True) for k, v in sd.items()}
-
-    def net(t):
-        if kind == "qnn":
-            w = prm["weights"]
-            xr = t.reshape(t.shape[0], -1) @ prm["linear_down.weight"].T + prm["linear_down.bias"]
-            ev = oc.run_round(oc.Spec(n=w.shape[1], encoding="rz", imprimitive="CZ", measure="expz"), xr,
-                              w.unsqueeze(0))
-        else:
-            w = prm["weights1"]
-            xr = t.reshape(t.shape[0], -1) @ prm["linear_down.weight"].T + prm["linear_down.bias"]
-            ev = oc.run_circuit(oc.Spec(n=w.shape[3], encoding="rz", imprimitive="CZ", measure="expz"), xr, w)
-        if detach:
-            ev = ev.detach()
-        out = ev @ prm["linear_up.weight"].T + prm["linear_up.bias"]
-        return out.reshape(t.shape)
-
-    loss, recon = odf.training_loss(net, x.cpu(), T, shape, goal, noise=noise.cpu())
-    loss.backward()
-    return loss.item(), {k: v.grad for k, v in prm.items()}, recon.detach()
 
 
 def _build(kind, detach, goal, side, n, seed=5):

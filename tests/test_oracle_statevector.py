@@ -227,3 +227,35 @@ def test_gate_counts_match_survey():
     assert oc.gate_count(oc.Spec(10, "rz"), 2, 9, 2) == 900
     assert oc.gate_count(oc.Spec(10, "amplitude"), 1, 1, 60) == 1201
     assert oc.gate_count(oc.Spec(4, "rz"), 1, 1, 2) == 20
+
+
+@pytest.mark.parametrize("c_in,c_out,k,pad,hw,depth,scale", [
+    (1, 1, 1, 0, (3, 4), 1, 0.8),        # n = 1: a single even-index probability
+    (3, 5, 3, 1, (5, 7), 2, 0.8),        # n = 5, ragged image
+    (16, 8, 1, 0, (4, 6), 2, 0.8),       # 1 x 1 kernel (the UNet's up_conv), n = 4
+    (8, 16, 3, 1, (5, 5), 3, 0.8),       # n = 7
+    (16, 16, 3, 1, (3, 4), 2, 0.8),      # n = 8
+    (1, 8, 3, 1, (6, 5), 1, 0.05),       # near-identity circuit: p * D / 2 > 1 on |0>, the [0, 1] clamp is active
+])
+def test_qconv2d_forward_unitary_matches_per_pixel_oracle(c_in, c_out, k, pad, hw, depth, scale):
+    """The unitary-product restatement of the quantum convolution equals the per-pixel statevector one on values and
+    on both autograd gradients (weights and input)."""
+    g = torch.Generator().manual_seed(c_in * 7 + c_out)
+    n = oc.qconv_wires(c_in, c_out, (k, k))
+    x = torch.rand(2, c_in, *hw, generator=g, dtype=torch.float64)
+    w = torch.randn(depth, n, 3, generator=g, dtype=torch.float64) * scale
+    ho, wo = hw[0] + 2 * pad - k + 1, hw[1] + 2 * pad - k + 1
+    gy = torch.randn(2, c_out, ho, wo, generator=g, dtype=torch.float64)
+    res = []
+    for f in (oc.qconv2d_forward, oc.qconv2d_forward_unitary):
+        xi, wi = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        y = f(xi, wi, c_out, (k, k), (pad, pad))
+        gw, gx = torch.autograd.grad((y * gy).sum(), [wi, xi])
+        res.append((y.detach(), gw, gx))
+    (y0, gw0, gx0), (y1, gw1, gx1) = res
+    assert y1.shape == y0.shape == (2, c_out, ho, wo)
+    assert (y1 - y0).abs().max().item() <= 1e-12
+    assert (gw1 - gw0).abs().max().item() <= 1e-12
+    assert (gx1 - gx0).abs().max().item() <= 1e-12
+    if scale < 0.1:
+        assert (y0 == 1.0).any()                       # the clamp really cut a value
