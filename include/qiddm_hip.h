@@ -556,7 +556,8 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  * Replaces PennyLane's `default.mixed` for the circuits the `*_noise.py` drivers run at sampling time
  * (src/mnist_noise.py:214-229; channels at nn/qdense.py:98-104, 255-261, 1410-1417).  The circuit is handed over
  * as a program of single-wire / two-wire ops (the caller expands templates and entangler rings); one workgroup
- * keeps one sample's rho (2^n x 2^n) in LDS or in `workspace`.  Forward only, n_qubits <= 8.
+ * keeps one sample's rho (2^n x 2^n) in LDS or in `workspace`.  n_qubits <= 8.  qiddm_mixed_backward gives the exact
+ * gradient of sum(grad_out * out) by a reverse sweep over the same program (PennyLane differentiates such QNodes).
  *   QIDDM_MIX_ZERO            rho = |0..0><0..0|                      (a program starts with ZERO or AMP_EMBED)
  *   QIDDM_MIX_AMP_EMBED       AmplitudeEmbedding(features + enc_offset, pad_with, normalize)
  *   QIDDM_MIX_PHASE           RZ / PhaseShift on `wire`: angle = p + scale * angle_rows[a][sample] (a < 0: p only)
@@ -581,6 +582,26 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t 
                         int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with,
                         const double *gates, int32_t n_gates, int32_t measure, int64_t batch, double *out,
                         int64_t out_ld, void *workspace, int64_t workspace_bytes, void *stream);
+/* Reverse sweep (vector-Jacobian product) of qiddm_mixed_forward: the same program and inputs, plus
+ *   grad_out       (batch, gout_ld >= 2^n | n) float64 DEVICE: dL/d out
+ *   grad_rows      (n_rows, batch) float64 DEVICE: dL/d angle_rows (required when n_rows > 0)
+ *   grad_gates     (batch, n_gates, 8) float64 DEVICE: per-sample dL/d gates (the caller sums over the batch;
+ *                  required when n_gates > 0)
+ *   grad_features  (batch, n_features) float64 DEVICE: dL/d features (required when the program has AMP_EMBED)
+ *   max_blocks     grid cap (0: the default of 256 workgroups); samples beyond the grid loop
+ * The kernel replays the forward, keeping a copy of rho in front of every channel (and every state preparation
+ * after op 0) in `workspace`, then walks the program backwards.  No atomics: reruns are bit-identical.  The
+ * workspace holds the program, the snapshots and, when rho and the adjoint do not both fit in 128 KiB of LDS
+ * (n >= 7), those two as well -- qiddm_mixed_backward_workspace_bytes(program) bytes.                    */
+int64_t qiddm_mixed_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch,
+                                             const qiddm_mixed_op_t *program, int32_t n_ops, int32_t max_blocks);
+int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t *program, int32_t n_ops,
+                         const double *angle_rows, int64_t rows_ld, int32_t n_rows, const double *features,
+                         int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with,
+                         const double *gates, int32_t n_gates, int32_t measure, int64_t batch,
+                         const double *grad_out, int64_t gout_ld, double *grad_rows, double *grad_gates,
+                         double *grad_features, int32_t max_blocks, void *workspace, int64_t workspace_bytes,
+                         void *stream);
 
 #ifdef __cplusplus
 }

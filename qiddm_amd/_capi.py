@@ -91,6 +91,8 @@ EXPORTS = (
     "qiddm_upsample2x_backward",
     "qiddm_mixed_workspace_bytes",
     "qiddm_mixed_forward",
+    "qiddm_mixed_backward_workspace_bytes",
+    "qiddm_mixed_backward",
 )
 
 
@@ -247,6 +249,14 @@ def _declare(lib):
     lib.qiddm_mixed_forward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MixedOp), ctypes.c_int32, vp, i64,
                                         ctypes.c_int32, vp, i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp,
                                         ctypes.c_int32, ctypes.c_int32, i64, vp, i64, vp, i64, vp]
+    lib.qiddm_mixed_backward_workspace_bytes.restype = i64
+    lib.qiddm_mixed_backward_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, i64, ctypes.POINTER(MixedOp),
+                                                         ctypes.c_int32, ctypes.c_int32]
+    lib.qiddm_mixed_backward.restype = ctypes.c_int
+    lib.qiddm_mixed_backward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MixedOp), ctypes.c_int32, vp, i64,
+                                         ctypes.c_int32, vp, i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp,
+                                         ctypes.c_int32, ctypes.c_int32, i64, vp, i64, vp, vp, vp, ctypes.c_int32, vp,
+                                         i64, vp]
     lib.qiddm_amp_embed_rows.restype = ctypes.c_int
     lib.qiddm_amp_embed_rows.argtypes = [vp, i64, i64, i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp, vp]
     lib.qiddm_prob_post.restype = ctypes.c_int

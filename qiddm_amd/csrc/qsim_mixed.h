@@ -16,7 +16,8 @@
 //     Depolarizing(p):      M00, M11 <- (1-2p/3) own + (2p/3) other;  M01, M10 *= 1-4p/3
 // (the Kraus sums of PennyLane's channel definitions, written out).  Diagonal gates multiply by u_i conj(u_j); CZ by
 // sign(i) sign(j); CNOT permutes rows and columns (an involution: swapped in place).  Read-out: the diagonal.
-// Forward only -- the reference differentiates nothing on default.mixed.  n <= 8.
+// mixed_backward_kernel (below) differentiates the same programs: PennyLane trains QNodes on default.mixed with
+// backprop or parameter-shift.  n <= 8.
 #pragma once
 #include "qsim_fused.h"
 
@@ -66,6 +67,173 @@ __device__ __forceinline__ uint32_t insert_two_bits(uint32_t t, int qlo, int qhi
   return lo | (mid << (qlo + 1)) | (hi << (qhi + 1));
 }
 
+__device__ __forceinline__ double mixed_angle(const MixedOp& op, const double* __restrict__ angle_rows,
+                                              const MixedScalars& m, int64_t sample) {
+  return op.p + (op.a >= 0 ? op.scale * angle_rows[(size_t)op.a * m.rows_ld + sample] : 0.0);
+}
+
+// the sum of every thread's v, in a fixed order, handed to every thread (s_red is free again on return)
+__device__ __forceinline__ double mixed_block_sum(double v, double* s_red) {
+  const int tid = threadIdx.x;
+  s_red[tid] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) s_red[tid] += s_red[tid + s];
+    __syncthreads();
+  }
+  const double total = s_red[0];
+  __syncthreads();
+  return total;
+}
+
+__device__ __forceinline__ bool mixed_needs_snapshot(int kind, int oi) {
+  return kind == kMixPhaseDamp || kind == kMixAmpDamp || kind == kMixDepol ||
+         (oi > 0 && (kind == kMixZero || kind == kMixAmpEmbed));
+}
+
+// Op `op` of the program on one sample's rho.  `snap` (NULL in the forward): where the backward's replay keeps rho as
+// it was before a channel or a state preparation.  The caller puts a barrier after every op.
+template <typename T>
+__device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restrict__ rho, V2<T>* __restrict__ snap,
+                                               const double* __restrict__ angle_rows, const double* __restrict__ feats,
+                                               const double* __restrict__ gates, double* s_red, const MixedScalars& m,
+                                               int64_t sample) {
+  using C = V2<T>;
+  const int n = m.n, tid = threadIdx.x;
+  const uint32_t D = 1u << n, DD = 1u << (2 * n);
+  const int q = n - 1 - op.wire;  // bit of the column half; the row half's is q + n
+  if (snap && (op.kind == kMixZero || op.kind == kMixAmpEmbed))
+    for (uint32_t k = tid; k < DD; k += 256) snap[k] = rho[k];  // the same thread then overwrites rho[k]
+  switch (op.kind) {
+    case kMixZero: {
+      for (uint32_t k = tid; k < DD; k += 256) rho[k] = C{k == 0 ? (T)1 : (T)0, (T)0};
+      break;
+    }
+    case kMixAmpEmbed: {
+      const double* __restrict__ row = feats + sample * m.feat_ld;
+      double part = 0.0;
+      for (uint32_t k = tid; k < D; k += 256) {
+        const double v = k < (uint32_t)m.n_features ? row[k] + m.enc_offset : m.pad_with;
+        part += v * v;
+      }
+      s_red[tid] = part;
+      __syncthreads();
+      for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) s_red[tid] += s_red[tid + s];
+        __syncthreads();
+      }
+      const double inv = 1.0 / s_red[0];
+      for (uint32_t k = tid; k < DD; k += 256) {
+        const uint32_t i = k >> n, j = k & (D - 1);
+        const double vi = i < (uint32_t)m.n_features ? row[i] + m.enc_offset : m.pad_with;
+        const double vj = j < (uint32_t)m.n_features ? row[j] + m.enc_offset : m.pad_with;
+        rho[k] = C{(T)(vi * vj * inv), (T)0};
+      }
+      break;
+    }
+    case kMixPhase: {
+      const double phi = mixed_angle(op, angle_rows, m, sample);
+      double sn, cs;
+      sincos(phi, &sn, &cs);
+      const C up{(T)cs, (T)sn}, dn{(T)cs, (T)-sn};
+      for (uint32_t k = tid; k < DD; k += 256) {
+        const int bi = (k >> (q + n)) & 1, bj = (k >> q) & 1;
+        if (bi != bj) rho[k] = cmul<T>(rho[k], bi ? up : dn);
+      }
+      break;
+    }
+    case kMixRY:
+    case kMixGate: {
+      C u00, u01, u10, u11;
+      if (op.kind == kMixRY) {
+        const double th = mixed_angle(op, angle_rows, m, sample);
+        double sn, cs;
+        sincos(0.5 * th, &sn, &cs);
+        u00 = C{(T)cs, 0};
+        u01 = C{(T)-sn, 0};
+        u10 = C{(T)sn, 0};
+        u11 = C{(T)cs, 0};
+      } else {
+        const double* __restrict__ g = gates + (size_t)op.a * 8;
+        u00 = C{(T)g[0], (T)g[1]};
+        u01 = C{(T)g[2], (T)g[3]};
+        u10 = C{(T)g[4], (T)g[5]};
+        u11 = C{(T)g[6], (T)g[7]};
+      }
+      for (uint32_t t = tid; t < DD / 4; t += 256) {
+        const uint32_t base = insert_two_bits(t, q, q + n);
+        const uint32_t cj = 1u << q, ci = 1u << (q + n);
+        const C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
+        // A = U M
+        const C a00 = V2<T>{0, 0} + cmul<T>(u00, m00) + cmul<T>(u01, m10);
+        const C a01 = cmul<T>(u00, m01) + cmul<T>(u01, m11);
+        const C a10 = cmul<T>(u10, m00) + cmul<T>(u11, m10);
+        const C a11 = cmul<T>(u10, m01) + cmul<T>(u11, m11);
+        // M' = A U^dagger:  M'_{xy} = sum_k A_{xk} conj(U_{yk})
+        rho[base] = cmulc<T>(a00, u00) + cmulc<T>(a01, u01);
+        rho[base | cj] = cmulc<T>(a00, u10) + cmulc<T>(a01, u11);
+        rho[base | ci] = cmulc<T>(a10, u00) + cmulc<T>(a11, u01);
+        rho[base | ci | cj] = cmulc<T>(a10, u10) + cmulc<T>(a11, u11);
+      }
+      break;
+    }
+    case kMixCZ: {
+      const int qt = n - 1 - op.a;
+      for (uint32_t k = tid; k < DD; k += 256) {
+        const uint32_t i = k >> n, j = k & (D - 1);
+        const int si = ((i >> q) & (i >> qt) & 1), sj = ((j >> q) & (j >> qt) & 1);
+        if (si != sj) rho[k] = C{-rho[k].x, -rho[k].y};
+      }
+      break;
+    }
+    case kMixCNOT: {
+      const int qt = n - 1 - op.a;
+      for (uint32_t k = tid; k < DD; k += 256) {
+        const uint32_t i = k >> n, j = k & (D - 1);
+        const uint32_t pi = i ^ (((i >> q) & 1u) << qt), pj = j ^ (((j >> q) & 1u) << qt);
+        const uint32_t pk = (pi << n) | pj;
+        if (k < pk) {
+          const C tmp = rho[k];
+          rho[k] = rho[pk];
+          rho[pk] = tmp;
+        }
+      }
+      break;
+    }
+    case kMixPhaseDamp:
+    case kMixAmpDamp:
+    case kMixDepol: {
+      T off, d_own, d_other_to_0, d_other_to_1, d11;
+      if (op.kind == kMixPhaseDamp) {
+        off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = 1; d_other_to_0 = 0; d_other_to_1 = 0;
+      } else if (op.kind == kMixAmpDamp) {
+        off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = (T)(1.0 - op.p); d_other_to_0 = (T)op.p; d_other_to_1 = 0;
+      } else {
+        off = (T)(1.0 - 4.0 * op.p / 3.0); d_own = (T)(1.0 - 2.0 * op.p / 3.0); d11 = d_own;
+        d_other_to_0 = (T)(2.0 * op.p / 3.0); d_other_to_1 = d_other_to_0;
+      }
+      for (uint32_t t = tid; t < DD / 4; t += 256) {
+        const uint32_t base = insert_two_bits(t, q, q + n);
+        const uint32_t cj = 1u << q, ci = 1u << (q + n);
+        const C m00 = rho[base], m11 = rho[base | ci | cj];
+        if (snap) {
+          snap[base] = m00;
+          snap[base | ci | cj] = m11;
+          snap[base | cj] = rho[base | cj];
+          snap[base | ci] = rho[base | ci];
+        }
+        rho[base] = C{d_own * m00.x + d_other_to_0 * m11.x, d_own * m00.y + d_other_to_0 * m11.y};
+        rho[base | ci | cj] = C{d11 * m11.x + d_other_to_1 * m00.x, d11 * m11.y + d_other_to_1 * m00.y};
+        const C m01 = rho[base | cj], m10 = rho[base | ci];
+        rho[base | cj] = C{off * m01.x, off * m01.y};
+        rho[base | ci] = C{off * m10.x, off * m10.y};
+      }
+      break;
+    }
+    default: break;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ prog,
                                                     const double* __restrict__ angle_rows,
@@ -82,129 +250,7 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
   for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
     for (int oi = 0; oi < m.n_ops; ++oi) {
       const MixedOp op = prog[oi];
-      const int q = n - 1 - op.wire;  // bit of the column half; the row half's is q + n
-      switch (op.kind) {
-        case kMixZero: {
-          for (uint32_t k = tid; k < DD; k += 256) rho[k] = C{k == 0 ? (T)1 : (T)0, (T)0};
-          break;
-        }
-        case kMixAmpEmbed: {
-          const double* __restrict__ row = feats + sample * m.feat_ld;
-          double part = 0.0;
-          for (uint32_t k = tid; k < D; k += 256) {
-            const double v = k < (uint32_t)m.n_features ? row[k] + m.enc_offset : m.pad_with;
-            part += v * v;
-          }
-          s_red[tid] = part;
-          __syncthreads();
-          for (int s = 128; s > 0; s >>= 1) {
-            if (tid < s) s_red[tid] += s_red[tid + s];
-            __syncthreads();
-          }
-          const double inv = 1.0 / s_red[0];
-          for (uint32_t k = tid; k < DD; k += 256) {
-            const uint32_t i = k >> n, j = k & (D - 1);
-            const double vi = i < (uint32_t)m.n_features ? row[i] + m.enc_offset : m.pad_with;
-            const double vj = j < (uint32_t)m.n_features ? row[j] + m.enc_offset : m.pad_with;
-            rho[k] = C{(T)(vi * vj * inv), (T)0};
-          }
-          break;
-        }
-        case kMixPhase: {
-          const double phi = op.p + (op.a >= 0 ? op.scale * angle_rows[(size_t)op.a * m.rows_ld + sample] : 0.0);
-          double sn, cs;
-          sincos(phi, &sn, &cs);
-          const C up{(T)cs, (T)sn}, dn{(T)cs, (T)-sn};
-          for (uint32_t k = tid; k < DD; k += 256) {
-            const int bi = (k >> (q + n)) & 1, bj = (k >> q) & 1;
-            if (bi != bj) rho[k] = cmul<T>(rho[k], bi ? up : dn);
-          }
-          break;
-        }
-        case kMixRY:
-        case kMixGate: {
-          C u00, u01, u10, u11;
-          if (op.kind == kMixRY) {
-            const double th = op.p + (op.a >= 0 ? op.scale * angle_rows[(size_t)op.a * m.rows_ld + sample] : 0.0);
-            double sn, cs;
-            sincos(0.5 * th, &sn, &cs);
-            u00 = C{(T)cs, 0};
-            u01 = C{(T)-sn, 0};
-            u10 = C{(T)sn, 0};
-            u11 = C{(T)cs, 0};
-          } else {
-            const double* __restrict__ g = gates + (size_t)op.a * 8;
-            u00 = C{(T)g[0], (T)g[1]};
-            u01 = C{(T)g[2], (T)g[3]};
-            u10 = C{(T)g[4], (T)g[5]};
-            u11 = C{(T)g[6], (T)g[7]};
-          }
-          for (uint32_t t = tid; t < DD / 4; t += 256) {
-            const uint32_t base = insert_two_bits(t, q, q + n);
-            const uint32_t cj = 1u << q, ci = 1u << (q + n);
-            const C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
-            // A = U M
-            const C a00 = V2<T>{0, 0} + cmul<T>(u00, m00) + cmul<T>(u01, m10);
-            const C a01 = cmul<T>(u00, m01) + cmul<T>(u01, m11);
-            const C a10 = cmul<T>(u10, m00) + cmul<T>(u11, m10);
-            const C a11 = cmul<T>(u10, m01) + cmul<T>(u11, m11);
-            // M' = A U^dagger:  M'_{xy} = sum_k A_{xk} conj(U_{yk})
-            rho[base] = cmulc<T>(a00, u00) + cmulc<T>(a01, u01);
-            rho[base | cj] = cmulc<T>(a00, u10) + cmulc<T>(a01, u11);
-            rho[base | ci] = cmulc<T>(a10, u00) + cmulc<T>(a11, u01);
-            rho[base | ci | cj] = cmulc<T>(a10, u10) + cmulc<T>(a11, u11);
-          }
-          break;
-        }
-        case kMixCZ: {
-          const int qt = n - 1 - op.a;
-          for (uint32_t k = tid; k < DD; k += 256) {
-            const uint32_t i = k >> n, j = k & (D - 1);
-            const int si = ((i >> q) & (i >> qt) & 1), sj = ((j >> q) & (j >> qt) & 1);
-            if (si != sj) rho[k] = C{-rho[k].x, -rho[k].y};
-          }
-          break;
-        }
-        case kMixCNOT: {
-          const int qt = n - 1 - op.a;
-          for (uint32_t k = tid; k < DD; k += 256) {
-            const uint32_t i = k >> n, j = k & (D - 1);
-            const uint32_t pi = i ^ (((i >> q) & 1u) << qt), pj = j ^ (((j >> q) & 1u) << qt);
-            const uint32_t pk = (pi << n) | pj;
-            if (k < pk) {
-              const C tmp = rho[k];
-              rho[k] = rho[pk];
-              rho[pk] = tmp;
-            }
-          }
-          break;
-        }
-        case kMixPhaseDamp:
-        case kMixAmpDamp:
-        case kMixDepol: {
-          T off, d_own, d_other_to_0, d_other_to_1, d11;
-          if (op.kind == kMixPhaseDamp) {
-            off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = 1; d_other_to_0 = 0; d_other_to_1 = 0;
-          } else if (op.kind == kMixAmpDamp) {
-            off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = (T)(1.0 - op.p); d_other_to_0 = (T)op.p; d_other_to_1 = 0;
-          } else {
-            off = (T)(1.0 - 4.0 * op.p / 3.0); d_own = (T)(1.0 - 2.0 * op.p / 3.0); d11 = d_own;
-            d_other_to_0 = (T)(2.0 * op.p / 3.0); d_other_to_1 = d_other_to_0;
-          }
-          for (uint32_t t = tid; t < DD / 4; t += 256) {
-            const uint32_t base = insert_two_bits(t, q, q + n);
-            const uint32_t cj = 1u << q, ci = 1u << (q + n);
-            const C m00 = rho[base], m11 = rho[base | ci | cj];
-            rho[base] = C{d_own * m00.x + d_other_to_0 * m11.x, d_own * m00.y + d_other_to_0 * m11.y};
-            rho[base | ci | cj] = C{d11 * m11.x + d_other_to_1 * m00.x, d11 * m11.y + d_other_to_1 * m00.y};
-            const C m01 = rho[base | cj], m10 = rho[base | ci];
-            rho[base | cj] = C{off * m01.x, off * m01.y};
-            rho[base | ci] = C{off * m10.x, off * m10.y};
-          }
-          break;
-        }
-        default: break;
-      }
+      mixed_apply_op<T>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
       __syncthreads();
     }
     // ---- read-out: the diagonal ------------------------------------------------------------------------
@@ -225,6 +271,276 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
         }
         if (tid == 0) out[sample * m.out_ld + w] = s_red[0];
         __syncthreads();
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- reverse sweep ------------------------------------------------------------------------------------------------
+// Per sample: replay the forward to rho_N (copying rho to a snapshot in front of every channel and every later state
+// preparation), seed the adjoint Lambda_N = dL/drho_N (diagonal: diag(g) for probs, sum_w g_w (1 - 2 bit_w) for <Z>),
+// then walk the program backwards with rho_k and Lambda_k side by side:
+//     single-wire unitary U (generator G for RY: Y, PHASE: Z):
+//         N = sum over the wire's 2 x 2 blocks of B_rho B_Lambda^dagger  (= Tr_other rho_k Lambda_k)
+//         dL/dtheta = Im Tr(G N);  GATE: R = U^dagger N, dL/dRe U_ab = 2 Re R_ba, dL/dIm U_ab = -2 Im R_ba
+//         rho, Lambda <- U^dagger B U  (one pass over both)
+//     CZ / CNOT: applied to both (involutions)
+//     channel E: Lambda <- E^dagger(Lambda), rho <- snapshot (a channel is not inverted: Depolarizing(0.9) has
+//         condition number 5 per wire)
+//     AMP_EMBED: rho_0 = v v^T / |v|^2, dL/dv = 2 (Re(Lambda) v - (v^T Re(Lambda) v / |v|^2) v) / |v|^2
+// Gradients go to per-sample double outputs (no atomics): every reduction runs in a fixed order, so reruns are
+// bit-identical.  Thread 0 adds each parameter's reduced value after the op's barrier.
+struct MixedBwdScalars {
+  int64_t gout_ld;
+  int32_t n_rows, n_gates, n_snaps, pad_;
+};
+
+__device__ __forceinline__ double mixed_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// U^dagger B U for the 2 x 2 block (b00, b01, b10, b11), in place
+template <typename T>
+__device__ __forceinline__ void mixed_udag_b_u(V2<T>& b00, V2<T>& b01, V2<T>& b10, V2<T>& b11, V2<T> u00, V2<T> u01,
+                                               V2<T> u10, V2<T> u11) {
+  // A = U^dagger B:  A_xl = sum_k conj(U_kx) B_kl
+  const V2<T> a00 = cmulc<T>(b00, u00) + cmulc<T>(b10, u10), a01 = cmulc<T>(b01, u00) + cmulc<T>(b11, u10);
+  const V2<T> a10 = cmulc<T>(b00, u01) + cmulc<T>(b10, u11), a11 = cmulc<T>(b01, u01) + cmulc<T>(b11, u11);
+  // B' = A U
+  b00 = cmul<T>(a00, u00) + cmul<T>(a01, u10);
+  b01 = cmul<T>(a00, u01) + cmul<T>(a01, u11);
+  b10 = cmul<T>(a10, u00) + cmul<T>(a11, u10);
+  b11 = cmul<T>(a10, u01) + cmul<T>(a11, u11);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_backward_kernel(
+    const MixedOp* __restrict__ prog, const double* __restrict__ angle_rows, const double* __restrict__ feats,
+    const double* __restrict__ gates, const double* __restrict__ grad_out, double* __restrict__ grad_rows,
+    double* __restrict__ grad_gates, double* __restrict__ grad_feats, V2<T>* __restrict__ workspace,
+    const MixedScalars m, const MixedBwdScalars b) {
+  using C = V2<T>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ double s_red[256];
+  __shared__ double s_v[256];
+  __shared__ double s_part[2][4][8];
+  const int n = m.n, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t D = 1u << n, DD = 1u << (2 * n);
+  // workspace per workgroup: [rho, Lambda unless in LDS] then n_snaps snapshots
+  const size_t per_block = (size_t)(m.slab_in_lds ? 0 : 2) + (size_t)b.n_snaps;
+  C* const slabs = workspace + (size_t)blockIdx.x * per_block * DD;
+  C* const rho = m.slab_in_lds ? reinterpret_cast<C*>(smem_raw) : slabs;
+  C* const lam = rho + DD;
+  C* const snaps = m.slab_in_lds ? slabs : slabs + 2 * (size_t)DD;
+  int buf = 0;
+
+  for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
+    for (int r = tid; r < b.n_rows; r += 256) grad_rows[(size_t)r * m.batch + sample] = 0.0;
+    for (int i = tid; i < b.n_gates * 8; i += 256) grad_gates[(size_t)sample * b.n_gates * 8 + i] = 0.0;
+    if (grad_feats)  // thread k owns feature k (n_features <= 2^n <= 256) here and in AMP_EMBED below
+      for (int k = tid; k < m.n_features; k += 256) grad_feats[sample * m.n_features + k] = 0.0;
+
+    // ---- replay -------------------------------------------------------------------------------------------------
+    int si = 0;
+    for (int oi = 0; oi < m.n_ops; ++oi) {
+      const MixedOp op = prog[oi];
+      C* snap = mixed_needs_snapshot(op.kind, oi) ? snaps + (size_t)(si++) * DD : nullptr;
+      mixed_apply_op<T>(op, rho, snap, angle_rows, feats, gates, s_red, m, sample);
+      __syncthreads();
+    }
+
+    // ---- seed Lambda_N --------------------------------------------------------------------------------------------
+    const double* __restrict__ g = grad_out + sample * b.gout_ld;
+    for (uint32_t k = tid; k < DD; k += 256) {
+      const uint32_t i = k >> n, j = k & (D - 1);
+      double v = 0.0;
+      if (i == j) {
+        if (m.measure == 0) {
+          v = g[i];
+        } else {
+          for (int w = 0; w < n; ++w) v += ((i >> (n - 1 - w)) & 1u) ? -g[w] : g[w];
+        }
+      }
+      lam[k] = C{(T)v, (T)0};
+    }
+    __syncthreads();
+
+    // ---- reverse sweep --------------------------------------------------------------------------------------------
+    for (int oi = m.n_ops - 1; oi >= 0; --oi) {
+      const MixedOp op = prog[oi];
+      const int q = n - 1 - op.wire;
+      const bool param = op.kind == kMixPhase || op.kind == kMixRY || op.kind == kMixGate;
+      switch (op.kind) {
+        case kMixPhase:
+        case kMixRY:
+        case kMixGate: {
+          C u00, u01, u10, u11;
+          if (op.kind == kMixGate) {
+            const double* __restrict__ gu = gates + (size_t)op.a * 8;
+            u00 = C{(T)gu[0], (T)gu[1]};
+            u01 = C{(T)gu[2], (T)gu[3]};
+            u10 = C{(T)gu[4], (T)gu[5]};
+            u11 = C{(T)gu[6], (T)gu[7]};
+          } else {
+            const double th = mixed_angle(op, angle_rows, m, sample);
+            double sn, cs;
+            if (op.kind == kMixRY) {
+              sincos(0.5 * th, &sn, &cs);
+              u00 = C{(T)cs, 0};
+              u01 = C{(T)-sn, 0};
+              u10 = C{(T)sn, 0};
+              u11 = C{(T)cs, 0};
+            } else {  // diag(1, e^{i phi}), as the forward applies it
+              sincos(th, &sn, &cs);
+              u00 = C{(T)1, 0};
+              u01 = C{0, 0};
+              u10 = C{0, 0};
+              u11 = C{(T)cs, (T)sn};
+            }
+          }
+          // N_ab = sum over blocks, c of rho_ac conj(Lambda_bc): (re, im) of N00, N01, N10, N11
+          double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+          for (uint32_t t = tid; t < DD / 4; t += 256) {
+            const uint32_t base = insert_two_bits(t, q, q + n);
+            const uint32_t cj = 1u << q, ci = 1u << (q + n);
+            C r00 = rho[base], r01 = rho[base | cj], r10 = rho[base | ci], r11 = rho[base | ci | cj];
+            C l00 = lam[base], l01 = lam[base | cj], l10 = lam[base | ci], l11 = lam[base | ci | cj];
+            const C n00 = cmulc<T>(r00, l00) + cmulc<T>(r01, l01), n01 = cmulc<T>(r00, l10) + cmulc<T>(r01, l11);
+            const C n10 = cmulc<T>(r10, l00) + cmulc<T>(r11, l01), n11 = cmulc<T>(r10, l10) + cmulc<T>(r11, l11);
+            acc[0] += (double)n00.x; acc[1] += (double)n00.y;
+            acc[2] += (double)n01.x; acc[3] += (double)n01.y;
+            acc[4] += (double)n10.x; acc[5] += (double)n10.y;
+            acc[6] += (double)n11.x; acc[7] += (double)n11.y;
+            mixed_udag_b_u<T>(r00, r01, r10, r11, u00, u01, u10, u11);
+            mixed_udag_b_u<T>(l00, l01, l10, l11, u00, u01, u10, u11);
+            rho[base] = r00; rho[base | cj] = r01; rho[base | ci] = r10; rho[base | ci | cj] = r11;
+            lam[base] = l00; lam[base | cj] = l01; lam[base | ci] = l10; lam[base | ci | cj] = l11;
+          }
+          if (op.kind == kMixGate) {
+            for (int k = 0; k < 8; ++k) {
+              const double s = mixed_wave_sum(acc[k]);
+              if (lane == 0) s_part[buf][wave][k] = s;
+            }
+          } else {
+            // Im Tr(G N): Y -> Re N01 - Re N10, Z -> Im N00 - Im N11
+            const double v = op.kind == kMixRY ? acc[2] - acc[4] : acc[1] - acc[7];
+            const double s = mixed_wave_sum(v);
+            if (lane == 0) s_part[buf][wave][0] = s;
+          }
+          break;
+        }
+        case kMixCZ: {
+          const int qt = n - 1 - op.a;
+          for (uint32_t k = tid; k < DD; k += 256) {
+            const uint32_t i = k >> n, j = k & (D - 1);
+            const int si_ = ((i >> q) & (i >> qt) & 1), sj = ((j >> q) & (j >> qt) & 1);
+            if (si_ != sj) {
+              rho[k] = C{-rho[k].x, -rho[k].y};
+              lam[k] = C{-lam[k].x, -lam[k].y};
+            }
+          }
+          break;
+        }
+        case kMixCNOT: {
+          const int qt = n - 1 - op.a;
+          for (uint32_t k = tid; k < DD; k += 256) {
+            const uint32_t i = k >> n, j = k & (D - 1);
+            const uint32_t pi = i ^ (((i >> q) & 1u) << qt), pj = j ^ (((j >> q) & 1u) << qt);
+            const uint32_t pk = (pi << n) | pj;
+            if (k < pk) {
+              const C tr = rho[k], tl = lam[k];
+              rho[k] = rho[pk];
+              rho[pk] = tr;
+              lam[k] = lam[pk];
+              lam[pk] = tl;
+            }
+          }
+          break;
+        }
+        case kMixPhaseDamp:
+        case kMixAmpDamp:
+        case kMixDepol: {
+          // E^dagger on the diagonal is the transpose of E's 2 x 2 mixing; off-diagonals scale alike
+          T off, d_own, d_other_to_0, d_other_to_1, d11;
+          if (op.kind == kMixPhaseDamp) {
+            off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = 1; d_other_to_0 = 0; d_other_to_1 = 0;
+          } else if (op.kind == kMixAmpDamp) {
+            off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = (T)(1.0 - op.p); d_other_to_0 = (T)op.p; d_other_to_1 = 0;
+          } else {
+            off = (T)(1.0 - 4.0 * op.p / 3.0); d_own = (T)(1.0 - 2.0 * op.p / 3.0); d11 = d_own;
+            d_other_to_0 = (T)(2.0 * op.p / 3.0); d_other_to_1 = d_other_to_0;
+          }
+          const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
+          for (uint32_t t = tid; t < DD / 4; t += 256) {
+            const uint32_t base = insert_two_bits(t, q, q + n);
+            const uint32_t cj = 1u << q, ci = 1u << (q + n);
+            const C l00 = lam[base], l01 = lam[base | cj], l10 = lam[base | ci], l11 = lam[base | ci | cj];
+            lam[base] = C{d_own * l00.x + d_other_to_1 * l11.x, d_own * l00.y + d_other_to_1 * l11.y};
+            lam[base | ci | cj] = C{d11 * l11.x + d_other_to_0 * l00.x, d11 * l11.y + d_other_to_0 * l00.y};
+            lam[base | cj] = C{off * l01.x, off * l01.y};
+            lam[base | ci] = C{off * l10.x, off * l10.y};
+            rho[base] = sp[base];
+            rho[base | cj] = sp[base | cj];
+            rho[base | ci] = sp[base | ci];
+            rho[base | ci | cj] = sp[base | ci | cj];
+          }
+          break;
+        }
+        case kMixAmpEmbed: {
+          const double* __restrict__ row = feats + sample * m.feat_ld;
+          if (tid < (int)D) s_v[tid] = tid < m.n_features ? row[tid] + m.enc_offset : m.pad_with;
+          __syncthreads();
+          double v = 0.0, lv = 0.0;  // v_i and (Re(Lambda) v)_i for i = tid
+          if (tid < (int)D) {
+            v = s_v[tid];
+            for (uint32_t j = 0; j < D; ++j) lv += (double)lam[((uint32_t)tid << n) | j].x * s_v[j];
+          }
+          const double inv = 1.0 / mixed_block_sum(v * v, s_red);
+          const double quad = mixed_block_sum(v * lv, s_red) * inv;
+          if (grad_feats && tid < m.n_features) grad_feats[sample * m.n_features + tid] += 2.0 * (lv - quad * v) * inv;
+        }
+          [[fallthrough]];
+        case kMixZero: {
+          if (oi > 0) {  // a later preparation: nothing before it reaches the output
+            const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
+            for (uint32_t k = tid; k < DD; k += 256) {
+              lam[k] = C{0, 0};
+              rho[k] = sp[k];
+            }
+          }
+          break;
+        }
+        default: break;
+      }
+      __syncthreads();
+      if (param) {
+        if (tid == 0) {
+          if (op.kind == kMixGate) {
+            double s[8];
+            for (int k = 0; k < 8; ++k) s[k] = s_part[buf][0][k] + s_part[buf][1][k] + s_part[buf][2][k] + s_part[buf][3][k];
+            const double* __restrict__ gu = gates + (size_t)op.a * 8;
+            double* __restrict__ go = grad_gates + ((size_t)sample * b.n_gates + op.a) * 8;
+            // R_ba = sum_c conj(U_cb) N_ca;  dL/dRe U_ab = 2 Re R_ba, dL/dIm U_ab = -2 Im R_ba
+            for (int a = 0; a < 2; ++a)
+              for (int bb = 0; bb < 2; ++bb) {
+                double re = 0.0, im = 0.0;
+                for (int c = 0; c < 2; ++c) {
+                  const double ur = gu[(c * 2 + bb) * 2], ui = gu[(c * 2 + bb) * 2 + 1];
+                  const double nr = s[(c * 2 + a) * 2], ni = s[(c * 2 + a) * 2 + 1];
+                  re += ur * nr + ui * ni;
+                  im += ur * ni - ui * nr;
+                }
+                go[(a * 2 + bb) * 2] += 2.0 * re;
+                go[(a * 2 + bb) * 2 + 1] += -2.0 * im;
+              }
+          } else if (op.a >= 0) {
+            const double s = s_part[buf][0][0] + s_part[buf][1][0] + s_part[buf][2][0] + s_part[buf][3][0];
+            grad_rows[(size_t)op.a * m.batch + sample] += op.scale * s;
+          }
+        }
+        buf ^= 1;
       }
     }
     __syncthreads();

@@ -3,8 +3,13 @@
 bodies insert PhaseDamping / AmplitudeDamping / DepolarizingChannel, nn/qdense.py:98-104, 255-261, 1410-1417).
 
 The tape is lowered, in order, to the op program of ``qiddm_mixed_forward`` (templates and entangler rings expanded
-here; see include/qiddm_hip.h) and executed in one launch, one workgroup per sample.  Forward only -- the reference
-never differentiates on ``default.mixed`` -- and n <= 8.  No CPU path.
+here; see include/qiddm_hip.h) and executed in one launch, one workgroup per sample.  n <= 8.  No CPU path.
+
+With grad mode on and an input that requires grad, the launch is one ``torch.autograd.Function`` whose backward is
+``qiddm_mixed_backward``: a reverse sweep over the same program that gives the exact gradient with respect to the
+angle rows, the SEL rotation matrices and the amplitude-embedding features (PennyLane trains such QNodes with backprop
+or parameter-shift; both give this gradient).  Autograd carries it on through the stacked rows, ``rot_matrices`` and
+whatever weight map the circuit applied.  Channel strengths get no gradient.
 """
 from __future__ import annotations
 
@@ -20,8 +25,9 @@ CHANNELS = {"PhaseDamping": _capi.MIX_PHASE_DAMP, "AmplitudeDamping": _capi.MIX_
 
 
 def rot_matrices(weights: torch.Tensor) -> torch.Tensor:
-    """(..., 3) Rot angles -> (G, 8) float64 rows (u00, u01, u10, u11) as (re, im); Rot = RZ(omega) RY(theta) RZ(phi)."""
-    w = weights.detach().to(torch.float64).reshape(-1, 3)
+    """(..., 3) Rot angles -> (G, 8) float64 rows (u00, u01, u10, u11) as (re, im); Rot = RZ(omega) RY(theta) RZ(phi).
+    Differentiable."""
+    w = weights.to(torch.float64).reshape(-1, 3)
     phi, theta, omega = w[:, 0], w[:, 1], w[:, 2]
     c, s = torch.cos(theta / 2), torch.sin(theta / 2)
     a, b = (phi + omega) / 2, (phi - omega) / 2
@@ -55,10 +61,10 @@ class _Lowering:
         self._see(value)
         if value.dim() == 0:
             self._note_batch(1, False)
-            self.rows.append(value.detach().reshape(1))
+            self.rows.append(value.reshape(1))
         elif value.dim() == 1:
             self._note_batch(value.shape[0], True)
-            self.rows.append(value.detach())
+            self.rows.append(value)
         else:
             raise NotImplementedError("gate parameters must be scalars or 1-D (batched) tensors")
         return len(self.rows) - 1, 0.0
@@ -101,7 +107,7 @@ def lower(tape, ret, n):
                 raise ValueError(f"Features must be of length {1 << n}; got length {feat}. "
                                  "Use the 'pad_with' argument for automated padding.")
             low._note_batch(1 if f.dim() == 1 else f.shape[0], f.dim() > 1)
-            low.features = f.detach().reshape(-1, feat)
+            low.features = f.reshape(-1, feat)
             low.pad_with = float(t.hyper["pad_with"] or 0.0)
             low.op(_capi.MIX_AMP_EMBED)
         else:
@@ -142,9 +148,90 @@ def lower(tape, ret, n):
     return low, measure
 
 
+class _Launch:
+    """One lowered circuit with its device operands (float64, contiguous, batch-expanded)."""
+
+    def __init__(self, low, measure, n, prec, device, batch):
+        self.n, self.prec, self.measure, self.batch, self.device = n, prec, measure, batch, device
+        self.pad_with, self.n_rows = low.pad_with, len(low.rows)
+        self.prog = (_capi.MixedOp * len(low.ops))()
+        for dst, (kind, wire, a, p, scale) in zip(self.prog, low.ops):
+            dst.kind, dst.wire, dst.a, dst.reserved, dst.p, dst.scale = kind, wire, a, 0, p, scale
+
+    def stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def forward(self, rows, gates, feats):
+        n, batch = self.n, self.batch
+        out = torch.empty(batch, (1 << n) if self.measure == _capi.MEAS_PROBS else n, dtype=torch.float64,
+                          device=self.device)
+        lib = _capi.lib()
+        need = lib.qiddm_mixed_workspace_bytes(n, self.prec, batch, len(self.prog))
+        if need < 0:
+            _capi.check(int(need))
+        key = (self.device.type, self.device.index, self.stream())
+        ws = _workspaces.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _workspaces[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        _capi.check(lib.qiddm_mixed_forward(
+            n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0), self.n_rows,
+            _ptr(feats), 0 if feats is None else feats.stride(0), 0 if feats is None else feats.shape[1], 0.0,
+            self.pad_with, _ptr(gates), 0 if gates is None else gates.shape[0], self.measure, batch, out.data_ptr(),
+            out.stride(0), ws.data_ptr(), ws.numel(), ctypes.c_void_p(self.stream())))
+        return out
+
+    def backward(self, rows, gates, feats, grad_out, max_blocks=0):
+        """-> (dL/d rows, dL/d gates summed over the batch, dL/d feats); None where there is no operand."""
+        n, batch = self.n, self.batch
+        grad_out = grad_out.to(torch.float64).contiguous()
+        f64 = dict(dtype=torch.float64, device=self.device)
+        g_rows = torch.empty(self.n_rows, batch, **f64) if rows is not None else None
+        g_gates = torch.empty(batch, gates.shape[0], 8, **f64) if gates is not None else None
+        g_feats = torch.empty(batch, feats.shape[1], **f64) if feats is not None else None
+        lib = _capi.lib()
+        need = lib.qiddm_mixed_backward_workspace_bytes(n, self.prec, batch, self.prog, len(self.prog), max_blocks)
+        if need < 0:
+            _capi.check(int(need))
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        _capi.check(lib.qiddm_mixed_backward(
+            n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0), self.n_rows,
+            _ptr(feats), 0 if feats is None else feats.stride(0), 0 if feats is None else feats.shape[1], 0.0,
+            self.pad_with, _ptr(gates), 0 if gates is None else gates.shape[0], self.measure, batch,
+            grad_out.data_ptr(), grad_out.shape[1], _ptr(g_rows), _ptr(g_gates), _ptr(g_feats), max_blocks,
+            ws.data_ptr(), ws.numel(), ctypes.c_void_p(self.stream())))
+        return g_rows, None if g_gates is None else g_gates.sum(dim=0), g_feats
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+class _MixedFunction(torch.autograd.Function):
+    """``qiddm_mixed_forward`` as an autograd node; its backward is ``qiddm_mixed_backward``."""
+
+    @staticmethod
+    def forward(ctx, launch, rows, gates, feats):
+        ctx.launch = launch
+        ctx.save_for_backward(rows, gates, feats)
+        return launch.forward(rows, gates, feats)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        rows, gates, feats = ctx.saved_tensors
+        g_rows, g_gates, g_feats = ctx.launch.backward(rows, gates, feats, grad_out, backward_max_blocks)
+        return (None, g_rows if ctx.needs_input_grad[1] else None, g_gates if ctx.needs_input_grad[2] else None,
+                g_feats if ctx.needs_input_grad[3] else None)
+
+
+# grid cap of the backward launch (0: the library's default); tests lower it to force the sample loop
+backward_max_blocks = 0
+
+
 def execute(tape, ret, n, precision=None):
     """Run the recorded function on the density-matrix kernel.  Returns float64 ``(B, 2^n)`` / ``(B, n)``
-    (or the unbatched row), as ``default.mixed`` does."""
+    (or the unbatched row), as ``default.mixed`` does.  Differentiable when grad mode is on and an input requires
+    grad; otherwise a plain launch whose result has no ``grad_fn``."""
     from . import circuit as _c
     low, measure = lower(tape, ret, n)
     if low.device is None:
@@ -152,31 +239,15 @@ def execute(tape, ret, n, precision=None):
     device = low.device
     batch = low.batch or 1
     prec = _capi.F64 if (precision or _c._default_precision) == "f64" else _capi.F32
-    prog = (_capi.MixedOp * len(low.ops))()
-    for dst, (kind, wire, a, p, scale) in zip(prog, low.ops):
-        dst.kind, dst.wire, dst.a, dst.reserved, dst.p, dst.scale = kind, wire, a, 0, p, scale
+    launch = _Launch(low, measure, n, prec, device, batch)
     f64 = dict(dtype=torch.float64, device=device)
     rows = torch.stack([r.to(**f64).expand(batch) for r in low.rows]).contiguous() if low.rows else None
     gates = torch.cat(low.gates).to(device).contiguous() if low.gates else None
     feats = low.features.to(**f64).contiguous() if low.features is not None else None
     if feats is not None and feats.shape[0] != batch:
         feats = feats.expand(batch, -1).contiguous()
-    out = torch.empty(batch, (1 << n) if measure == _capi.MEAS_PROBS else n, **f64)
-    lib = _capi.lib()
-    need = lib.qiddm_mixed_workspace_bytes(n, prec, batch, len(low.ops))
-    if need < 0:
-        _capi.check(int(need))
-    key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _workspaces[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-
-    def ptr(t):
-        return 0 if t is None else t.data_ptr()
-
-    _capi.check(lib.qiddm_mixed_forward(
-        n, prec, prog, len(low.ops), ptr(rows), 0 if rows is None else rows.stride(0), len(low.rows), ptr(feats),
-        0 if feats is None else feats.stride(0), 0 if feats is None else feats.shape[1], 0.0, low.pad_with, ptr(gates),
-        0 if gates is None else gates.shape[0], measure, batch, out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(),
-        ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (rows, gates, feats)):
+        out = _MixedFunction.apply(launch, rows, gates, feats)
+    else:
+        out = launch.forward(rows, gates, feats)
     return out if low.batched else out[0]

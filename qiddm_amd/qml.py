@@ -175,7 +175,7 @@ class Device:
 def device(name, wires=1, **kwargs):
     """``qml.device(name, wires=n)``.  Every pure-state device name the reference uses maps
     to the HIP statevector engine; ``default.mixed`` (the noise scripts create it,
-    src/mnist_noise.py:223) maps to the density-matrix kernel (``qiddm_amd.mixed``: forward only, n <= 8)."""
+    src/mnist_noise.py:223) maps to the density-matrix kernel (``qiddm_amd.mixed``: n <= 8, differentiable by a reverse sweep)."""
     return Device(name, wires, **kwargs)
 
 
@@ -209,11 +209,11 @@ class QNode:
         tape, ret = self._trace(args, kwargs)
         n = self.device.num_wires
         if self.device.mixed:
-            # density-matrix execution (forward only; the reference samples, never trains, on default.mixed)
+            # density-matrix execution; differentiable (reverse sweep, whatever diff_method says) when grad mode is
+            # on and an input requires grad
             from . import mixed as _mixed
             self.circuit = None
-            with torch.no_grad():
-                return _mixed.execute(tape, ret, n, self.precision)
+            return _mixed.execute(tape, ret, n, self.precision)
         circ, x, angles, batched, as_list = _compile(tape, ret, n, self.device)
         self.circuit = circ
         out = _c.execute(circ, x, angles, self.precision, self.diff_method or "backprop")
