@@ -556,8 +556,9 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  * Replaces PennyLane's `default.mixed` for the circuits the `*_noise.py` drivers run at sampling time
  * (src/mnist_noise.py:214-229; channels at nn/qdense.py:98-104, 255-261, 1410-1417).  The circuit is handed over
  * as a program of single-wire / two-wire ops (the caller expands templates and entangler rings); one workgroup
- * keeps one sample's rho (2^n x 2^n) in LDS or in `workspace`.  n_qubits <= 8.  qiddm_mixed_backward gives the exact
- * gradient of sum(grad_out * out) by a reverse sweep over the same program (PennyLane differentiates such QNodes).
+ * keeps one sample's rho (2^n x 2^n) in LDS or in `workspace`.  qiddm_mixed_forward / _backward take n_qubits <= 8;
+ * qiddm_mixed_wide_forward (below) runs the same programs forward at 7 <= n_qubits <= 10.  qiddm_mixed_backward gives the
+ * exact gradient of sum(grad_out * out) by a reverse sweep over the same program (PennyLane differentiates such QNodes).
  *   QIDDM_MIX_ZERO            rho = |0..0><0..0|                      (a program starts with ZERO or AMP_EMBED)
  *   QIDDM_MIX_AMP_EMBED       AmplitudeEmbedding(features + enc_offset, pad_with, normalize)
  *   QIDDM_MIX_PHASE           RZ / PhaseShift on `wire`: angle = p + scale * angle_rows[a][sample] (a < 0: p only)
@@ -602,6 +603,32 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
                          const double *grad_out, int64_t gout_ld, double *grad_rows, double *grad_gates,
                          double *grad_features, int32_t max_blocks, void *workspace, int64_t workspace_bytes,
                          void *stream);
+
+/* Tile-fused density-matrix engine, forward only, 7 <= n_qubits <= 10 (else QIDDM_ERR_UNSUPPORTED): the 10-wire models
+ * of the reference's 28 x 28 noise study (src/fashion_noise.py:42-44).  rho of a sample (index (i << n) | j) lives in a
+ * slab of `workspace`; the program is cut into SEGMENTS, each run by one sweep -- one launch over (tile, sample) in which
+ * a workgroup holds the 2^12 elements spanned by the index-bit pairs of six wires in LDS and applies the whole segment.
+ * A segment takes PHASE / CZ / PHASE_DAMP on any wires (diagonal on vec(rho)), GATE / RY / AMP_DAMP / DEPOL on its six
+ * wires, CNOT between two of them, and ZERO / AMP_EMBED as its first op.  Ops keep program order except where they
+ * commute (no shared wire, or both diagonal).  Same arguments and results as qiddm_mixed_forward; float64 read-out with
+ * fixed-order sums, no atomics: reruns are bit-identical.
+ *   qiddm_mixed_wide_plan             host only (no device is touched): the number of sweeps, the number of ops that are
+ *                                     not diagonal (state preparations included) and, if op_segment is not NULL, the
+ *                                     segment of every op.  Any of the three outputs may be NULL.
+ *   qiddm_mixed_wide_workspace_bytes  program head + one float64 per resident sample + the resident slabs.  At most
+ *                                     1 GiB of slabs is resident (64 samples at n = 10 in float64); larger batches run
+ *                                     in chunks inside qiddm_mixed_wide_forward.  `program` may be NULL.
+ *   qiddm_mixed_wide_forward          also accepts a smaller workspace, down to one slab: fewer samples are resident
+ *                                     per chunk; the results do not depend on the chunking.                          */
+int64_t qiddm_mixed_wide_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch,
+                                         const qiddm_mixed_op_t *program, int32_t n_ops);
+int qiddm_mixed_wide_plan(int32_t n_qubits, const qiddm_mixed_op_t *program, int32_t n_ops, int32_t *n_sweeps,
+                          int32_t *n_nondiag_ops, int32_t *op_segment);
+int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t *program, int32_t n_ops,
+                             const double *angle_rows, int64_t rows_ld, int32_t n_rows, const double *features,
+                             int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with,
+                             const double *gates, int32_t n_gates, int32_t measure, int64_t batch, double *out,
+                             int64_t out_ld, void *workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

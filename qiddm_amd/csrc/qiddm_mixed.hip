@@ -1,10 +1,14 @@
 // qiddm_mixed.hip -- extern "C" entry points of the density-matrix executor (include/qiddm_hip.h,
-// "hardware-noise study"); device code in qsim_mixed.h.
+// "hardware-noise study"); device code in qsim_mixed.h (n <= 8, one workgroup per sample) and qsim_mixed_wide.h
+// (n = 7..10, tile-fused sweeps, forward only) with the planner that cuts a program into sweeps.
 #include "capi_common.h"
 
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "qsim_mixed.h"
+#include "qsim_mixed_wide.h"
 
 namespace {
 
@@ -92,6 +96,164 @@ int mixed_backward_geometry(int32_t n, int32_t dtype, int64_t batch, const qiddm
   g->in_lds = (size_t)(2 * g->slab_bytes) <= kMixedLdsSlab;
   if (max_blocks > 0 && g->blocks > max_blocks) g->blocks = max_blocks;
   g->total = g->off_slabs + g->blocks * ((g->in_lds ? 0 : 2) + (int64_t)snaps) * g->slab_bytes;
+  return QIDDM_OK;
+}
+
+// ---- tile-fused engine (qsim_mixed_wide.h): geometry and planner ------------------------------------------------------
+constexpr int kWideMinQubits = 7, kWideMaxQubits = 10;
+constexpr int64_t kWideSlabBudget = (int64_t)1 << 30;  // resident slabs per launch: at most 1 GiB
+
+struct WideGeometry {
+  int64_t slab_bytes, resident, off_norms, off_slabs, total;
+};
+
+int wide_geometry(int32_t n, int32_t dtype, int64_t batch, int32_t n_ops, WideGeometry* g) {
+  if (n < kWideMinQubits || n > kWideMaxQubits)
+    return fail(QIDDM_ERR_UNSUPPORTED, "tile-fused density-matrix execution needs %d <= n_qubits <= %d (got %d)",
+                kWideMinQubits, kWideMaxQubits, n);
+  if (dtype != QIDDM_F32 && dtype != QIDDM_F64) return fail(QIDDM_ERR_INVALID, "unknown dtype %d", dtype);
+  if (batch < 0 || n_ops < 0) return fail(QIDDM_ERR_INVALID, "negative batch / n_ops");
+  g->slab_bytes = ((int64_t)1 << (2 * n)) * (dtype == QIDDM_F32 ? 8 : 16);
+  const int64_t cap = kWideSlabBudget / g->slab_bytes;
+  g->resident = batch < cap ? batch : cap;
+  if (g->resident < 1) g->resident = 1;
+  g->off_norms = ((int64_t)n_ops * (int64_t)sizeof(qiddm::MixedOp) + 255) / 256 * 256;
+  g->off_slabs = g->off_norms + (g->resident * 8 + 255) / 256 * 256;
+  g->total = g->off_slabs + g->resident * g->slab_bytes;
+  return QIDDM_OK;
+}
+
+struct WidePlan {
+  std::vector<int32_t> order;       // program indices, segment after segment
+  std::vector<int32_t> op_segment;  // segment of every op
+  std::vector<qiddm::WideSegment> segments;
+  int32_t n_nondiag = 0;
+};
+
+inline bool wide_is_prep(int kind) { return kind == qiddm::kMixZero || kind == qiddm::kMixAmpEmbed; }
+inline bool wide_is_diag(int kind) {
+  return kind == qiddm::kMixPhase || kind == qiddm::kMixCZ || kind == qiddm::kMixPhaseDamp;
+}
+
+// Cuts a program into segments, each executable by one sweep over tiles of six wires.  Two ops commute when they share
+// no wire or both act diagonally on vec(rho); an op joins the open segment only if every earlier op that does not
+// commute with it is placed (so executing segment after segment, each in program order, is a reordering of commuting
+// neighbours only), and a non-diagonal op only if its wires fit the segment's wire set.  Wires n-1 and n-2 are in every
+// set (the two lowest column bits stay local: 16-byte accesses).  ZERO / AMP_EMBED open a segment.  The first unplaced
+// op always fits an empty segment, so every segment places at least one op, and at least one that is not diagonal.
+int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WidePlan* plan) {
+  if (n < kWideMinQubits || n > kWideMaxQubits)
+    return fail(QIDDM_ERR_UNSUPPORTED, "tile-fused density-matrix execution needs %d <= n_qubits <= %d (got %d)",
+                kWideMinQubits, kWideMaxQubits, n);
+  if (n_ops < 1 || !program) return fail(QIDDM_ERR_INVALID, "empty program");
+  if (!wide_is_prep(program[0].kind)) return fail(QIDDM_ERR_INVALID, "the program must start by preparing the state");
+  const uint32_t all = (1u << n) - 1u;
+  std::vector<uint32_t> wires(n_ops);
+  plan->n_nondiag = 0;
+  for (int i = 0; i < n_ops; ++i) {
+    const qiddm_mixed_op_t& op = program[i];
+    if (op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
+    if (wide_is_prep(op.kind)) {
+      wires[i] = all;
+    } else {
+      if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
+      wires[i] = 1u << op.wire;
+      if (op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) {
+        if (op.a < 0 || op.a >= n || op.a == op.wire) return fail(QIDDM_ERR_INVALID, "op %d: bad target wire %d", i, op.a);
+        wires[i] |= 1u << op.a;
+      }
+    }
+    plan->n_nondiag += wide_is_diag(op.kind) ? 0 : 1;
+  }
+  plan->order.clear();
+  plan->order.reserve(n_ops);
+  plan->op_segment.assign(n_ops, -1);
+  plan->segments.clear();
+  std::vector<char> placed(n_ops, 0);
+  int first = 0;
+  while (first < n_ops) {
+    uint32_t set = (1u << (n - 1)) | (1u << (n - 2));
+    int count = 2;
+    uint32_t blocked_nondiag = 0, blocked_any = 0;  // wires with an earlier unplaced (non-diagonal / any) op
+    qiddm::WideSegment sg{};
+    sg.op_begin = (int32_t)plan->order.size();
+    bool empty = true;
+    for (int i = first; i < n_ops && blocked_nondiag != all; ++i) {
+      if (placed[i]) continue;
+      const int kind = program[i].kind;
+      const uint32_t w = wires[i];
+      bool ok;
+      int extra = 0;
+      if (wide_is_diag(kind)) {
+        ok = !(w & blocked_nondiag);
+      } else if (wide_is_prep(kind)) {
+        ok = !blocked_any && empty;
+      } else {
+        extra = __builtin_popcount(w & ~set);
+        ok = !(w & blocked_any) && count + extra <= qiddm::kWideTileWires;
+      }
+      if (ok) {
+        placed[i] = 1;
+        plan->order.push_back(i);
+        plan->op_segment[i] = (int32_t)plan->segments.size();
+        if (extra) {
+          set |= w;
+          count += extra;
+        }
+        empty = false;
+      } else {
+        blocked_any |= w;
+        if (!wide_is_diag(kind)) blocked_nondiag |= w;
+      }
+    }
+    while (first < n_ops && placed[first]) ++first;
+    sg.op_end = (int32_t)plan->order.size();
+    if (sg.op_end == sg.op_begin) return fail(QIDDM_ERR_INVALID, "planner made no progress at op %d", first);
+    for (int w = n - 1; w >= 0 && count < qiddm::kWideTileWires; --w)  // fill the tile: lowest index bits first
+      if (!(set >> w & 1u)) {
+        set |= 1u << w;
+        ++count;
+      }
+    sg.n_tile_bits = 2 * n - qiddm::kWideLocalBits;
+    int nl = 0, ng = 0;
+    for (int bit = 0; bit < 2 * n; ++bit) {
+      const int q = bit % n;
+      if (set >> (n - 1 - q) & 1u) sg.lpos[nl++] = (uint8_t)bit;
+      else sg.gpos[ng++] = (uint8_t)bit;
+    }
+    if (nl != qiddm::kWideLocalBits || ng != sg.n_tile_bits || sg.lpos[0] != 0 || sg.lpos[1] != 1)
+      return fail(QIDDM_ERR_INVALID, "planner built a malformed tile (%d local, %d tile bits)", nl, ng);
+    plan->segments.push_back(sg);
+  }
+  return QIDDM_OK;
+}
+
+template <typename T>
+int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resident, unsigned char* ws,
+                      const double* angle_rows, const double* features, const double* gates, double* out,
+                      qiddm::MixedScalars m, bool embeds, hipStream_t st) {
+  const size_t smem = (size_t)qiddm::kWideTile * sizeof(qiddm::V2<T>);
+  auto sweep = qiddm::mixed_wide_sweep<T>;
+  static qiddm_capi::DeviceFlags big;
+  if (smem > 48 * 1024 && !big.get()) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sweep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(e));
+    big.set();
+  }
+  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
+  double* norms = reinterpret_cast<double*>(ws + g.off_norms);
+  qiddm::V2<T>* slabs = reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs);
+  const unsigned tiles = 1u << (2 * m.n - qiddm::kWideLocalBits);
+  for (int64_t s0 = 0; s0 < m.batch; s0 += resident) {
+    const unsigned chunk = (unsigned)(m.batch - s0 < resident ? m.batch - s0 : resident);
+    if (embeds) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, features, norms, m, s0);
+    for (const qiddm::WideSegment& sg : plan.segments)
+      hipLaunchKernelGGL(sweep, dim3(tiles, chunk), dim3(256), smem, st, prog, angle_rows, features, gates, norms, slabs, m,
+                         sg, s0);
+    hipLaunchKernelGGL(qiddm::mixed_wide_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "mixed_wide launch failed: %s", hipGetErrorString(e));
+  }
   return QIDDM_OK;
 }
 
@@ -257,6 +419,83 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   e = hipGetLastError();
   if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "mixed_backward_kernel launch failed: %s", hipGetErrorString(e));
   return QIDDM_OK;
+}
+
+int64_t qiddm_mixed_wide_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, const qiddm_mixed_op_t* program,
+                                         int32_t n_ops) {
+  (void)program;  // the workspace does not depend on the plan: program head, |v|^2 per resident sample, resident slabs
+  WideGeometry g;
+  const int rc = wide_geometry(n_qubits, dtype, batch, n_ops, &g);
+  if (rc != QIDDM_OK) return rc;
+  return g.total;
+}
+
+int qiddm_mixed_wide_plan(int32_t n_qubits, const qiddm_mixed_op_t* program, int32_t n_ops, int32_t* n_sweeps,
+                          int32_t* n_nondiag_ops, int32_t* op_segment) {
+  WidePlan plan;
+  const int rc = plan_mixed_wide(n_qubits, program, n_ops, &plan);
+  if (rc != QIDDM_OK) return rc;
+  if (n_sweeps) *n_sweeps = (int32_t)plan.segments.size();
+  if (n_nondiag_ops) *n_nondiag_ops = plan.n_nondiag;
+  if (op_segment)
+    for (int i = 0; i < n_ops; ++i) op_segment[i] = plan.op_segment[i];
+  return QIDDM_OK;
+}
+
+int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t* program, int32_t n_ops,
+                             const double* angle_rows, int64_t rows_ld, int32_t n_rows, const double* features,
+                             int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with, const double* gates,
+                             int32_t n_gates, int32_t measure, int64_t batch, double* out, int64_t out_ld, void* workspace,
+                             int64_t workspace_bytes, void* stream) {
+  WideGeometry g;
+  int rc = wide_geometry(n_qubits, dtype, batch, n_ops, &g);
+  if (rc != QIDDM_OK) return rc;
+  if (measure != QIDDM_MEAS_PROBS && measure != QIDDM_MEAS_EXPZ) return fail(QIDDM_ERR_INVALID, "unknown measure %d", measure);
+  if (batch == 0) return QIDDM_OK;
+  if (!program || n_ops < 1) return fail(QIDDM_ERR_INVALID, "empty program");
+  if (!out) return fail(QIDDM_ERR_INVALID, "out is NULL");
+  const int64_t width = measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits;
+  if (out_ld < width) return fail(QIDDM_ERR_INVALID, "out_ld %lld < %lld", (long long)out_ld, (long long)width);
+  if (n_rows < 0 || n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
+  if (n_rows > 0 && (!angle_rows || rows_ld < batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
+  if (n_gates > 0 && !gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");
+  rc = check_program(n_qubits, program, n_ops, n_rows, features, feat_ld, n_features, n_gates);
+  if (rc != QIDDM_OK) return rc;
+  WidePlan plan;
+  rc = plan_mixed_wide(n_qubits, program, n_ops, &plan);
+  if (rc != QIDDM_OK) return rc;
+  // a smaller workspace than qiddm_mixed_wide_workspace_bytes() is accepted down to one slab: fewer samples are resident
+  int64_t resident = workspace ? (workspace_bytes - g.off_slabs) / g.slab_bytes : 0;
+  if (resident > g.resident) resident = g.resident;
+  if (resident < 1)
+    return fail(QIDDM_ERR_INVALID, "workspace of at least %lld B needed (qiddm_mixed_wide_workspace_bytes: %lld), got %lld",
+                (long long)(g.off_slabs + g.slab_bytes), (long long)g.total, (long long)workspace_bytes);
+  bool embeds = false;
+  std::vector<qiddm_mixed_op_t> sorted(n_ops);
+  for (int i = 0; i < n_ops; ++i) {
+    sorted[i] = program[plan.order[i]];
+    embeds = embeds || sorted[i].kind == qiddm::kMixAmpEmbed;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  // pageable source: the copy is staged before the call returns, so `sorted` may go out of scope
+  hipError_t e = hipMemcpyAsync(ws, sorted.data(), (size_t)n_ops * sizeof(qiddm_mixed_op_t), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "program upload failed: %s", hipGetErrorString(e));
+  qiddm::MixedScalars m{};
+  m.n = n_qubits;
+  m.n_ops = n_ops;
+  m.measure = measure;
+  m.n_features = n_features;
+  m.batch = batch;
+  m.rows_ld = rows_ld;
+  m.feat_ld = feat_ld;
+  m.out_ld = out_ld;
+  m.enc_offset = enc_offset;
+  m.pad_with = pad_with;
+  m.slab_in_lds = 0;
+  if (dtype == QIDDM_F32)
+    return launch_mixed_wide<float>(plan, g, resident, ws, angle_rows, features, gates, out, m, embeds, st);
+  return launch_mixed_wide<double>(plan, g, resident, ws, angle_rows, features, gates, out, m, embeds, st);
 }
 
 }  // extern "C"

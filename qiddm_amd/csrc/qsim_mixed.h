@@ -91,6 +91,164 @@ __device__ __forceinline__ bool mixed_needs_snapshot(int kind, int oi) {
          (oi > 0 && (kind == kMixZero || kind == kMixAmpEmbed));
 }
 
+// ---- per-element / per-block arithmetic, shared by mixed_apply_op and the tiled engine (qsim_mixed_wide.h) ----------
+template <typename T>
+__device__ __forceinline__ void mixed_phase_factors(double phi, V2<T>& up, V2<T>& dn) {
+  double sn, cs;
+  sincos(phi, &sn, &cs);
+  up = V2<T>{(T)cs, (T)sn};
+  dn = V2<T>{(T)cs, (T)-sn};
+}
+// PHASE on bit q of the column half (q + n of the row half) of element k
+template <typename T>
+__device__ __forceinline__ V2<T> mixed_phase_elem(V2<T> v, uint32_t k, int q, int n, V2<T> up, V2<T> dn) {
+  const int bi = (k >> (q + n)) & 1, bj = (k >> q) & 1;
+  return bi != bj ? cmul<T>(v, bi ? up : dn) : v;
+}
+template <typename T>
+__device__ __forceinline__ V2<T> mixed_cz_elem(V2<T> v, uint32_t k, int q, int qt, int n) {
+  const uint32_t i = k >> n, j = k & ((1u << n) - 1u);
+  const int si = ((i >> q) & (i >> qt) & 1), sj = ((j >> q) & (j >> qt) & 1);
+  return si != sj ? V2<T>{-v.x, -v.y} : v;
+}
+// where CNOT(control bit q, target bit qt) sends element k (an involution)
+__device__ __forceinline__ uint32_t mixed_cnot_index(uint32_t k, int q, int qt, int n) {
+  const uint32_t i = k >> n, j = k & ((1u << n) - 1u);
+  const uint32_t pi = i ^ (((i >> q) & 1u) << qt), pj = j ^ (((j >> q) & 1u) << qt);
+  return (pi << n) | pj;
+}
+
+template <typename T>
+struct MixedU {
+  V2<T> u00, u01, u10, u11;
+};
+// the 2 x 2 unitary of an RY / GATE op, evaluated in float64 and rounded once
+template <typename T>
+__device__ __forceinline__ MixedU<T> mixed_unitary(const MixedOp& op, const double* __restrict__ angle_rows,
+                                                   const double* __restrict__ gates, const MixedScalars& m,
+                                                   int64_t sample) {
+  using C = V2<T>;
+  MixedU<T> u;
+  if (op.kind == kMixRY) {
+    const double th = mixed_angle(op, angle_rows, m, sample);
+    double sn, cs;
+    sincos(0.5 * th, &sn, &cs);
+    u.u00 = C{(T)cs, 0};
+    u.u01 = C{(T)-sn, 0};
+    u.u10 = C{(T)sn, 0};
+    u.u11 = C{(T)cs, 0};
+  } else {
+    const double* __restrict__ g = gates + (size_t)op.a * 8;
+    u.u00 = C{(T)g[0], (T)g[1]};
+    u.u01 = C{(T)g[2], (T)g[3]};
+    u.u10 = C{(T)g[4], (T)g[5]};
+    u.u11 = C{(T)g[6], (T)g[7]};
+  }
+  return u;
+}
+// M <- U M U^dagger on one block
+template <typename T>
+__device__ __forceinline__ void mixed_block_unitary(const MixedU<T>& u, V2<T>& m00, V2<T>& m01, V2<T>& m10, V2<T>& m11) {
+  using C = V2<T>;
+  // A = U M
+  const C a00 = V2<T>{0, 0} + cmul<T>(u.u00, m00) + cmul<T>(u.u01, m10);
+  const C a01 = cmul<T>(u.u00, m01) + cmul<T>(u.u01, m11);
+  const C a10 = cmul<T>(u.u10, m00) + cmul<T>(u.u11, m10);
+  const C a11 = cmul<T>(u.u10, m01) + cmul<T>(u.u11, m11);
+  // M' = A U^dagger:  M'_{xy} = sum_k A_{xk} conj(U_{yk})
+  m00 = cmulc<T>(a00, u.u00) + cmulc<T>(a01, u.u01);
+  m01 = cmulc<T>(a00, u.u10) + cmulc<T>(a01, u.u11);
+  m10 = cmulc<T>(a10, u.u00) + cmulc<T>(a11, u.u01);
+  m11 = cmulc<T>(a10, u.u10) + cmulc<T>(a11, u.u11);
+}
+
+template <typename T>
+struct MixedChannel {
+  T off, d_own, d_other_to_0, d_other_to_1, d11;
+};
+template <typename T>
+__device__ __forceinline__ MixedChannel<T> mixed_channel(const MixedOp& op) {
+  MixedChannel<T> c;
+  if (op.kind == kMixPhaseDamp) {
+    c.off = (T)sqrt(1.0 - op.p); c.d_own = 1; c.d11 = 1; c.d_other_to_0 = 0; c.d_other_to_1 = 0;
+  } else if (op.kind == kMixAmpDamp) {
+    c.off = (T)sqrt(1.0 - op.p); c.d_own = 1; c.d11 = (T)(1.0 - op.p); c.d_other_to_0 = (T)op.p; c.d_other_to_1 = 0;
+  } else {
+    c.off = (T)(1.0 - 4.0 * op.p / 3.0); c.d_own = (T)(1.0 - 2.0 * op.p / 3.0); c.d11 = c.d_own;
+    c.d_other_to_0 = (T)(2.0 * op.p / 3.0); c.d_other_to_1 = c.d_other_to_0;
+  }
+  return c;
+}
+template <typename T>
+__device__ __forceinline__ void mixed_block_channel(const MixedChannel<T>& c, V2<T>& m00, V2<T>& m01, V2<T>& m10, V2<T>& m11) {
+  using C = V2<T>;
+  const C n00 = C{c.d_own * m00.x + c.d_other_to_0 * m11.x, c.d_own * m00.y + c.d_other_to_0 * m11.y};
+  const C n11 = C{c.d11 * m11.x + c.d_other_to_1 * m00.x, c.d11 * m11.y + c.d_other_to_1 * m00.y};
+  m00 = n00;
+  m11 = n11;
+  m01 = C{c.off * m01.x, c.off * m01.y};
+  m10 = C{c.off * m10.x, c.off * m10.y};
+}
+// an off-diagonal element of a wire's blocks under PhaseDamping (the diagonal ones stay)
+template <typename T>
+__device__ __forceinline__ V2<T> mixed_phase_damp_elem(V2<T> v, uint32_t k, int q, int n, T off) {
+  const int bi = (k >> (q + n)) & 1, bj = (k >> q) & 1;
+  return bi != bj ? V2<T>{off * v.x, off * v.y} : v;
+}
+
+// |v|^2 of a sample's padded feature row, summed in a fixed order and handed to every thread
+__device__ __forceinline__ double mixed_embed_norm2(const double* __restrict__ row, double* s_red, const MixedScalars& m) {
+  const int tid = threadIdx.x;
+  const uint32_t D = 1u << m.n;
+  double part = 0.0;
+  for (uint32_t k = tid; k < D; k += 256) {
+    const double v = k < (uint32_t)m.n_features ? row[k] + m.enc_offset : m.pad_with;
+    part += v * v;
+  }
+  s_red[tid] = part;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) s_red[tid] += s_red[tid + s];
+    __syncthreads();
+  }
+  return s_red[0];
+}
+// element k of v v^T / |v|^2
+template <typename T>
+__device__ __forceinline__ V2<T> mixed_embed_elem(const double* __restrict__ row, uint32_t k, double inv, const MixedScalars& m) {
+  const uint32_t i = k >> m.n, j = k & ((1u << m.n) - 1u);
+  const double vi = i < (uint32_t)m.n_features ? row[i] + m.enc_offset : m.pad_with;
+  const double vj = j < (uint32_t)m.n_features ? row[j] + m.enc_offset : m.pad_with;
+  return V2<T>{(T)(vi * vj * inv), (T)0};
+}
+
+// the diagonal of one sample's rho -> probs / <Z_w>, float64, fixed-order sums
+template <typename T>
+__device__ __forceinline__ void mixed_read_out(const V2<T>* __restrict__ rho, double* __restrict__ out, double* s_red,
+                                               const MixedScalars& m, int64_t sample) {
+  const int n = m.n, tid = threadIdx.x;
+  const uint32_t D = 1u << n;
+  if (m.measure == 0) {
+    for (uint32_t k = tid; k < D; k += 256) out[sample * m.out_ld + k] = (double)rho[((size_t)k << n) | k].x;
+  } else {
+    for (int w = 0; w < n; ++w) {
+      double part = 0.0;
+      for (uint32_t k = tid; k < D; k += 256) {
+        const double pk = (double)rho[((size_t)k << n) | k].x;
+        part += ((k >> (n - 1 - w)) & 1u) ? -pk : pk;
+      }
+      s_red[tid] = part;
+      __syncthreads();
+      for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) s_red[tid] += s_red[tid + s];
+        __syncthreads();
+      }
+      if (tid == 0) out[sample * m.out_ld + w] = s_red[0];
+      __syncthreads();
+    }
+  }
+}
+
 // Op `op` of the program on one sample's rho.  `snap` (NULL in the forward): where the backward's replay keeps rho as
 // it was before a channel or a state preparation.  The caller puts a barrier after every op.
 template <typename T>
@@ -111,31 +269,13 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
     }
     case kMixAmpEmbed: {
       const double* __restrict__ row = feats + sample * m.feat_ld;
-      double part = 0.0;
-      for (uint32_t k = tid; k < D; k += 256) {
-        const double v = k < (uint32_t)m.n_features ? row[k] + m.enc_offset : m.pad_with;
-        part += v * v;
-      }
-      s_red[tid] = part;
-      __syncthreads();
-      for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) s_red[tid] += s_red[tid + s];
-        __syncthreads();
-      }
-      const double inv = 1.0 / s_red[0];
-      for (uint32_t k = tid; k < DD; k += 256) {
-        const uint32_t i = k >> n, j = k & (D - 1);
-        const double vi = i < (uint32_t)m.n_features ? row[i] + m.enc_offset : m.pad_with;
-        const double vj = j < (uint32_t)m.n_features ? row[j] + m.enc_offset : m.pad_with;
-        rho[k] = C{(T)(vi * vj * inv), (T)0};
-      }
+      const double inv = 1.0 / mixed_embed_norm2(row, s_red, m);
+      for (uint32_t k = tid; k < DD; k += 256) rho[k] = mixed_embed_elem<T>(row, k, inv, m);
       break;
     }
     case kMixPhase: {
-      const double phi = mixed_angle(op, angle_rows, m, sample);
-      double sn, cs;
-      sincos(phi, &sn, &cs);
-      const C up{(T)cs, (T)sn}, dn{(T)cs, (T)-sn};
+      C up, dn;
+      mixed_phase_factors<T>(mixed_angle(op, angle_rows, m, sample), up, dn);
       for (uint32_t k = tid; k < DD; k += 256) {
         const int bi = (k >> (q + n)) & 1, bj = (k >> q) & 1;
         if (bi != bj) rho[k] = cmul<T>(rho[k], bi ? up : dn);
@@ -144,36 +284,16 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
     }
     case kMixRY:
     case kMixGate: {
-      C u00, u01, u10, u11;
-      if (op.kind == kMixRY) {
-        const double th = mixed_angle(op, angle_rows, m, sample);
-        double sn, cs;
-        sincos(0.5 * th, &sn, &cs);
-        u00 = C{(T)cs, 0};
-        u01 = C{(T)-sn, 0};
-        u10 = C{(T)sn, 0};
-        u11 = C{(T)cs, 0};
-      } else {
-        const double* __restrict__ g = gates + (size_t)op.a * 8;
-        u00 = C{(T)g[0], (T)g[1]};
-        u01 = C{(T)g[2], (T)g[3]};
-        u10 = C{(T)g[4], (T)g[5]};
-        u11 = C{(T)g[6], (T)g[7]};
-      }
+      const MixedU<T> u = mixed_unitary<T>(op, angle_rows, gates, m, sample);
       for (uint32_t t = tid; t < DD / 4; t += 256) {
         const uint32_t base = insert_two_bits(t, q, q + n);
         const uint32_t cj = 1u << q, ci = 1u << (q + n);
-        const C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
-        // A = U M
-        const C a00 = V2<T>{0, 0} + cmul<T>(u00, m00) + cmul<T>(u01, m10);
-        const C a01 = cmul<T>(u00, m01) + cmul<T>(u01, m11);
-        const C a10 = cmul<T>(u10, m00) + cmul<T>(u11, m10);
-        const C a11 = cmul<T>(u10, m01) + cmul<T>(u11, m11);
-        // M' = A U^dagger:  M'_{xy} = sum_k A_{xk} conj(U_{yk})
-        rho[base] = cmulc<T>(a00, u00) + cmulc<T>(a01, u01);
-        rho[base | cj] = cmulc<T>(a00, u10) + cmulc<T>(a01, u11);
-        rho[base | ci] = cmulc<T>(a10, u00) + cmulc<T>(a11, u01);
-        rho[base | ci | cj] = cmulc<T>(a10, u10) + cmulc<T>(a11, u11);
+        C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
+        mixed_block_unitary<T>(u, m00, m01, m10, m11);
+        rho[base] = m00;
+        rho[base | cj] = m01;
+        rho[base | ci] = m10;
+        rho[base | ci | cj] = m11;
       }
       break;
     }
@@ -189,9 +309,7 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
     case kMixCNOT: {
       const int qt = n - 1 - op.a;
       for (uint32_t k = tid; k < DD; k += 256) {
-        const uint32_t i = k >> n, j = k & (D - 1);
-        const uint32_t pi = i ^ (((i >> q) & 1u) << qt), pj = j ^ (((j >> q) & 1u) << qt);
-        const uint32_t pk = (pi << n) | pj;
+        const uint32_t pk = mixed_cnot_index(k, q, qt, n);
         if (k < pk) {
           const C tmp = rho[k];
           rho[k] = rho[pk];
@@ -203,30 +321,22 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
     case kMixPhaseDamp:
     case kMixAmpDamp:
     case kMixDepol: {
-      T off, d_own, d_other_to_0, d_other_to_1, d11;
-      if (op.kind == kMixPhaseDamp) {
-        off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = 1; d_other_to_0 = 0; d_other_to_1 = 0;
-      } else if (op.kind == kMixAmpDamp) {
-        off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = (T)(1.0 - op.p); d_other_to_0 = (T)op.p; d_other_to_1 = 0;
-      } else {
-        off = (T)(1.0 - 4.0 * op.p / 3.0); d_own = (T)(1.0 - 2.0 * op.p / 3.0); d11 = d_own;
-        d_other_to_0 = (T)(2.0 * op.p / 3.0); d_other_to_1 = d_other_to_0;
-      }
+      const MixedChannel<T> ch = mixed_channel<T>(op);
       for (uint32_t t = tid; t < DD / 4; t += 256) {
         const uint32_t base = insert_two_bits(t, q, q + n);
         const uint32_t cj = 1u << q, ci = 1u << (q + n);
-        const C m00 = rho[base], m11 = rho[base | ci | cj];
+        C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
         if (snap) {
           snap[base] = m00;
           snap[base | ci | cj] = m11;
-          snap[base | cj] = rho[base | cj];
-          snap[base | ci] = rho[base | ci];
+          snap[base | cj] = m01;
+          snap[base | ci] = m10;
         }
-        rho[base] = C{d_own * m00.x + d_other_to_0 * m11.x, d_own * m00.y + d_other_to_0 * m11.y};
-        rho[base | ci | cj] = C{d11 * m11.x + d_other_to_1 * m00.x, d11 * m11.y + d_other_to_1 * m00.y};
-        const C m01 = rho[base | cj], m10 = rho[base | ci];
-        rho[base | cj] = C{off * m01.x, off * m01.y};
-        rho[base | ci] = C{off * m10.x, off * m10.y};
+        mixed_block_channel<T>(ch, m00, m01, m10, m11);
+        rho[base] = m00;
+        rho[base | ci | cj] = m11;
+        rho[base | cj] = m01;
+        rho[base | ci] = m10;
       }
       break;
     }
@@ -253,26 +363,7 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
       mixed_apply_op<T>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
       __syncthreads();
     }
-    // ---- read-out: the diagonal ------------------------------------------------------------------------
-    if (m.measure == 0) {
-      for (uint32_t k = tid; k < D; k += 256) out[sample * m.out_ld + k] = (double)rho[((size_t)k << n) | k].x;
-    } else {
-      for (int w = 0; w < n; ++w) {
-        double part = 0.0;
-        for (uint32_t k = tid; k < D; k += 256) {
-          const double pk = (double)rho[((size_t)k << n) | k].x;
-          part += ((k >> (n - 1 - w)) & 1u) ? -pk : pk;
-        }
-        s_red[tid] = part;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-          if (tid < s) s_red[tid] += s_red[tid + s];
-          __syncthreads();
-        }
-        if (tid == 0) out[sample * m.out_ld + w] = s_red[0];
-        __syncthreads();
-      }
-    }
+    mixed_read_out<T>(rho, out, s_red, m, sample);  // the diagonal
     __syncthreads();
   }
 }

@@ -3,7 +3,11 @@
 bodies insert PhaseDamping / AmplitudeDamping / DepolarizingChannel, nn/qdense.py:98-104, 255-261, 1410-1417).
 
 The tape is lowered, in order, to the op program of ``qiddm_mixed_forward`` (templates and entangler rings expanded
-here; see include/qiddm_hip.h) and executed in one launch, one workgroup per sample.  n <= 8.  No CPU path.
+here; see include/qiddm_hip.h).  Up to 8 wires it runs in one launch, one workgroup per sample.  9 and 10 wires -- the
+reference's 28 x 28 noise study samples 10-wire models (src/fashion_noise.py:42-44) -- run on the tile-fused engine
+(``qiddm_mixed_wide_forward``: rho in a workspace slab, the program cut into sweeps over six-wire tiles), forward only, once
+the wire limit has been raised: ``set_max_wires(10)`` or ``with max_wires(10):``.  The limit is 8 by default (a 10-wire
+batch takes up to 1 GiB of workspace); the engine is always chosen by the number of wires.  No CPU path.
 
 With grad mode on and an input that requires grad, the launch is one ``torch.autograd.Function`` whose backward is
 ``qiddm_mixed_backward``: a reverse sweep over the same program that gives the exact gradient with respect to the
@@ -13,6 +17,7 @@ whatever weight map the circuit applied.  Channel strengths get no gradient.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
@@ -22,6 +27,32 @@ from . import _capi
 _workspaces = {}
 CHANNELS = {"PhaseDamping": _capi.MIX_PHASE_DAMP, "AmplitudeDamping": _capi.MIX_AMP_DAMP,
             "DepolarizingChannel": _capi.MIX_DEPOL}
+
+
+# wires up to which ``execute`` runs a circuit (8: the one-workgroup kernel only; 9, 10: the tile-fused engine as well)
+_max_wires = 8
+# resident samples per chunk of the tile-fused engine (0: the library's cap of 1 GiB of slabs); tests lower it to force
+# the chunk loop
+wide_resident_samples = 0
+
+
+def set_max_wires(k: int) -> None:
+    """Largest ``default.mixed`` device that executes: 8 (default), 9 or 10.  Beyond 8 wires execution is forward only."""
+    global _max_wires
+    if not isinstance(k, int) or not 8 <= k <= 10:
+        raise ValueError(f"the default.mixed wire limit must be 8, 9 or 10 (got {k!r})")
+    _max_wires = k
+
+
+@contextlib.contextmanager
+def max_wires(k: int):
+    """``with mixed.max_wires(10): ...`` -- ``set_max_wires`` for the duration of a block."""
+    before = _max_wires
+    set_max_wires(k)
+    try:
+        yield
+    finally:
+        set_max_wires(before)
 
 
 def rot_matrices(weights: torch.Tensor) -> torch.Tensor:
@@ -161,19 +192,27 @@ class _Launch:
     def stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def forward(self, rows, gates, feats):
+    def forward(self, rows, gates, feats, wide=False):
         n, batch = self.n, self.batch
         out = torch.empty(batch, (1 << n) if self.measure == _capi.MEAS_PROBS else n, dtype=torch.float64,
                           device=self.device)
         lib = _capi.lib()
-        need = lib.qiddm_mixed_workspace_bytes(n, self.prec, batch, len(self.prog))
+        if wide:
+            resident = min(batch, wide_resident_samples) if wide_resident_samples > 0 else batch
+            need = lib.qiddm_mixed_wide_workspace_bytes(n, self.prec, resident, self.prog, len(self.prog))
+        else:
+            need = lib.qiddm_mixed_workspace_bytes(n, self.prec, batch, len(self.prog))
         if need < 0:
             _capi.check(int(need))
-        key = (self.device.type, self.device.index, self.stream())
-        ws = _workspaces.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _workspaces[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        _capi.check(lib.qiddm_mixed_forward(
+        if wide:  # up to 1 GiB: handed back to the caching allocator after the call instead of being kept
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        else:
+            key = (self.device.type, self.device.index, self.stream())
+            ws = _workspaces.get(key)
+            if ws is None or ws.numel() < need:
+                ws = _workspaces[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        entry = lib.qiddm_mixed_wide_forward if wide else lib.qiddm_mixed_forward
+        _capi.check(entry(
             n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0), self.n_rows,
             _ptr(feats), 0 if feats is None else feats.stride(0), 0 if feats is None else feats.shape[1], 0.0,
             self.pad_with, _ptr(gates), 0 if gates is None else gates.shape[0], self.measure, batch, out.data_ptr(),
@@ -228,11 +267,18 @@ class _MixedFunction(torch.autograd.Function):
 backward_max_blocks = 0
 
 
-def execute(tape, ret, n, precision=None):
-    """Run the recorded function on the density-matrix kernel.  Returns float64 ``(B, 2^n)`` / ``(B, n)``
-    (or the unbatched row), as ``default.mixed`` does.  Differentiable when grad mode is on and an input requires
-    grad; otherwise a plain launch whose result has no ``grad_fn``."""
+def execute(tape, ret, n, precision=None, _engine=None):
+    """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)``
+    (or the unbatched row), as ``default.mixed`` does.  Up to 8 wires: differentiable when grad mode is on and an input
+    requires grad; otherwise a plain launch whose result has no ``grad_fn``.  9 and 10 wires (within the wire limit, see
+    ``set_max_wires``): forward only."""
     from . import circuit as _c
+    # the engine follows the number of wires; `_engine="wide"` (tests, A/B tools) forces the tile-fused one at 7, 8 wires
+    wide = _engine == "wide" or 8 < n <= _max_wires
+    if wide and torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params):
+        raise NotImplementedError(
+            f"default.mixed on {n} wires executes forward only: gradients stop at 8 wires (the tile-fused engine has no "
+            "reverse sweep).  Sample under torch.no_grad(), or train on a pure-state device.")
     low, measure = lower(tape, ret, n)
     if low.device is None:
         raise RuntimeError("default.mixed runs on the GPU only: no tensor argument lives on a HIP device (no CPU path)")
@@ -246,7 +292,9 @@ def execute(tape, ret, n, precision=None):
     feats = low.features.to(**f64).contiguous() if low.features is not None else None
     if feats is not None and feats.shape[0] != batch:
         feats = feats.expand(batch, -1).contiguous()
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (rows, gates, feats)):
+    if wide:
+        out = launch.forward(rows, gates, feats, wide=True)
+    elif torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (rows, gates, feats)):
         out = _MixedFunction.apply(launch, rows, gates, feats)
     else:
         out = launch.forward(rows, gates, feats)
