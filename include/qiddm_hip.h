@@ -557,7 +557,7 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  * (src/mnist_noise.py:214-229; channels at nn/qdense.py:98-104, 255-261, 1410-1417).  The circuit is handed over
  * as a program of single-wire / two-wire ops (the caller expands templates and entangler rings); one workgroup
  * keeps one sample's rho (2^n x 2^n) in LDS or in `workspace`.  qiddm_mixed_forward / _backward take n_qubits <= 8;
- * qiddm_mixed_wide_forward (below) runs the same programs forward at 7 <= n_qubits <= 10.  qiddm_mixed_backward gives the
+ * qiddm_mixed_wide_forward / _backward (below) run the same programs at 7 <= n_qubits <= 10.  qiddm_mixed_backward gives the
  * exact gradient of sum(grad_out * out) by a reverse sweep over the same program (PennyLane differentiates such QNodes).
  *   QIDDM_MIX_ZERO            rho = |0..0><0..0|                      (a program starts with ZERO or AMP_EMBED)
  *   QIDDM_MIX_AMP_EMBED       AmplitudeEmbedding(features + enc_offset, pad_with, normalize)
@@ -604,7 +604,7 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
                          double *grad_features, int32_t max_blocks, void *workspace, int64_t workspace_bytes,
                          void *stream);
 
-/* Tile-fused density-matrix engine, forward only, 7 <= n_qubits <= 10 (else QIDDM_ERR_UNSUPPORTED): the 10-wire models
+/* Tile-fused density-matrix engine, 7 <= n_qubits <= 10 (else QIDDM_ERR_UNSUPPORTED): the 10-wire models
  * of the reference's 28 x 28 noise study (src/fashion_noise.py:42-44).  rho of a sample (index (i << n) | j) lives in a
  * slab of `workspace`; the program is cut into SEGMENTS, each run by one sweep -- one launch over (tile, sample) in which
  * a workgroup holds the 2^12 elements spanned by the index-bit pairs of six wires in LDS and applies the whole segment.
@@ -629,6 +629,39 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
                              int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with,
                              const double *gates, int32_t n_gates, int32_t measure, int64_t batch, double *out,
                              int64_t out_ld, void *workspace, int64_t workspace_bytes, void *stream);
+/* Reverse sweep of the tile-fused engine: the exact vector-Jacobian product of qiddm_mixed_wide_forward, with the
+ * arguments and gradient layouts of qiddm_mixed_backward (no max_blocks) and its argument checks; 7 <= n_qubits <= 10
+ * (else QIDDM_ERR_UNSUPPORTED).  Channel strengths get no gradient.  Ops in front of the last state preparation reach
+ * no output: only the ops from there on (the LIVE ops) are planned and run, other parameters get a zero gradient.  The
+ * live ops are cut into segments that hold either channels only or no channel.  The call
+ *   replays     the forward sweeps; a channel segment writes rho to a further slab, so the state in front of it stays
+ *               behind as a snapshot (a channel is not inverted).  Channel segments behind the last unitary one are
+ *               not replayed.
+ *   walks back  one launch over (tile, sample) per segment, the rho tile and the adjoint's tile side by side in LDS;
+ *               the first one generates the adjoint from grad_out.  A unitary un-computes both tiles and writes its
+ *               tile partial per (op, tile, sample); a channel segment applies E^dagger to the adjoint and rho steps
+ *               back to the snapshot.  AMP_EMBED: a matrix-vector pass over the adjoint's slab.
+ *   finalizes   the tile partials, summed in a fixed order per parameter and sample.
+ * No atomics: reruns are bit-identical and the gradients do not depend on the chunking.
+ *   qiddm_mixed_wide_backward_plan             host only: sweeps of the replay, launches of the walk back, snapshots.
+ *                                              Any output may be NULL.
+ *   qiddm_mixed_wide_backward_workspace_bytes  head + resident * per_sample, every term rounded up to 256 B:
+ *                                              head = live ops * 32 + live ops * 4 + gradient ops * 24 + (parameter
+ *                                              groups + 1) * 4; per_sample = 8 (1 + 2^n) + 8 * slots * 2^(2n-12) +
+ *                                              (2 + snapshots) slabs, slots = 8 per live GATE + 1 per live PHASE / RY
+ *                                              with a >= 0.  resident = min(batch, 1 GiB / per_sample), at least 1;
+ *                                              larger batches run in chunks inside the call.  `program` is required.
+ *   qiddm_mixed_wide_backward                  also accepts a smaller workspace, down to head + per_sample.          */
+int64_t qiddm_mixed_wide_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch,
+                                                  const qiddm_mixed_op_t *program, int32_t n_ops);
+int qiddm_mixed_wide_backward_plan(int32_t n_qubits, const qiddm_mixed_op_t *program, int32_t n_ops,
+                                   int32_t *n_replay_sweeps, int32_t *n_reverse_sweeps, int32_t *n_snapshots);
+int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t *program, int32_t n_ops,
+                              const double *angle_rows, int64_t rows_ld, int32_t n_rows, const double *features,
+                              int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with,
+                              const double *gates, int32_t n_gates, int32_t measure, int64_t batch,
+                              const double *grad_out, int64_t gout_ld, double *grad_rows, double *grad_gates,
+                              double *grad_features, void *workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

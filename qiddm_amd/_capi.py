@@ -96,6 +96,9 @@ EXPORTS = (
     "qiddm_mixed_wide_workspace_bytes",
     "qiddm_mixed_wide_plan",
     "qiddm_mixed_wide_forward",
+    "qiddm_mixed_wide_backward_workspace_bytes",
+    "qiddm_mixed_wide_backward_plan",
+    "qiddm_mixed_wide_backward",
 )
 
 
@@ -268,6 +271,15 @@ def _declare(lib):
     lib.qiddm_mixed_wide_plan.argtypes = [ctypes.c_int32, ctypes.POINTER(MixedOp), ctypes.c_int32, i32p, i32p, i32p]
     lib.qiddm_mixed_wide_forward.restype = ctypes.c_int
     lib.qiddm_mixed_wide_forward.argtypes = lib.qiddm_mixed_forward.argtypes
+    lib.qiddm_mixed_wide_backward_workspace_bytes.restype = i64
+    lib.qiddm_mixed_wide_backward_workspace_bytes.argtypes = lib.qiddm_mixed_wide_workspace_bytes.argtypes
+    lib.qiddm_mixed_wide_backward_plan.restype = ctypes.c_int
+    lib.qiddm_mixed_wide_backward_plan.argtypes = lib.qiddm_mixed_wide_plan.argtypes
+    lib.qiddm_mixed_wide_backward.restype = ctypes.c_int
+    lib.qiddm_mixed_wide_backward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MixedOp), ctypes.c_int32, vp,
+                                              i64, ctypes.c_int32, vp, i64, ctypes.c_int32, ctypes.c_double,
+                                              ctypes.c_double, vp, ctypes.c_int32, ctypes.c_int32, i64, vp, i64, vp, vp,
+                                              vp, vp, i64, vp]
     lib.qiddm_amp_embed_rows.restype = ctypes.c_int
     lib.qiddm_amp_embed_rows.argtypes = [vp, i64, i64, i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp, vp]
     lib.qiddm_prob_post.restype = ctypes.c_int

@@ -1,14 +1,19 @@
 // qiddm_mixed.hip -- extern "C" entry points of the density-matrix executor (include/qiddm_hip.h,
 // "hardware-noise study"); device code in qsim_mixed.h (n <= 8, one workgroup per sample) and qsim_mixed_wide.h
-// (n = 7..10, tile-fused sweeps, forward only) with the planner that cuts a program into sweeps.
+// (n = 7..10, tile-fused sweeps) and qsim_mixed_wide_adjoint.h (their reverse sweep), with the planner that cuts a
+// program into sweeps.
 #include "capi_common.h"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstring>
+#include <utility>
 #include <vector>
 
 #include "qsim_mixed.h"
 #include "qsim_mixed_wide.h"
+#include "qsim_mixed_wide_adjoint.h"
 
 namespace {
 
@@ -127,12 +132,16 @@ struct WidePlan {
   std::vector<int32_t> order;       // program indices, segment after segment
   std::vector<int32_t> op_segment;  // segment of every op
   std::vector<qiddm::WideSegment> segments;
+  std::vector<char> seg_channel;    // split_channels: the segment holds channels only
   int32_t n_nondiag = 0;
 };
 
 inline bool wide_is_prep(int kind) { return kind == qiddm::kMixZero || kind == qiddm::kMixAmpEmbed; }
 inline bool wide_is_diag(int kind) {
   return kind == qiddm::kMixPhase || kind == qiddm::kMixCZ || kind == qiddm::kMixPhaseDamp;
+}
+inline bool wide_is_channel(int kind) {
+  return kind == qiddm::kMixPhaseDamp || kind == qiddm::kMixAmpDamp || kind == qiddm::kMixDepol;
 }
 
 // Cuts a program into segments, each executable by one sweep over tiles of six wires.  Two ops commute when they share
@@ -141,7 +150,10 @@ inline bool wide_is_diag(int kind) {
 // neighbours only), and a non-diagonal op only if its wires fit the segment's wire set.  Wires n-1 and n-2 are in every
 // set (the two lowest column bits stay local: 16-byte accesses).  ZERO / AMP_EMBED open a segment.  The first unplaced
 // op always fits an empty segment, so every segment places at least one op, and at least one that is not diagonal.
-int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WidePlan* plan) {
+// `split_channels` (the reverse sweep's plan): a segment takes channels only or no channel at all -- an op of the other
+// sort waits like one whose wires do not fit -- so that the state in front of a channel is a whole slab.
+int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WidePlan* plan,
+                    bool split_channels = false) {
   if (n < kWideMinQubits || n > kWideMaxQubits)
     return fail(QIDDM_ERR_UNSUPPORTED, "tile-fused density-matrix execution needs %d <= n_qubits <= %d (got %d)",
                 kWideMinQubits, kWideMaxQubits, n);
@@ -169,6 +181,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
   plan->order.reserve(n_ops);
   plan->op_segment.assign(n_ops, -1);
   plan->segments.clear();
+  plan->seg_channel.clear();
   std::vector<char> placed(n_ops, 0);
   int first = 0;
   while (first < n_ops) {
@@ -177,7 +190,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
     uint32_t blocked_nondiag = 0, blocked_any = 0;  // wires with an earlier unplaced (non-diagonal / any) op
     qiddm::WideSegment sg{};
     sg.op_begin = (int32_t)plan->order.size();
-    bool empty = true;
+    bool empty = true, channels = false;
     for (int i = first; i < n_ops && blocked_nondiag != all; ++i) {
       if (placed[i]) continue;
       const int kind = program[i].kind;
@@ -192,7 +205,9 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
         extra = __builtin_popcount(w & ~set);
         ok = !(w & blocked_any) && count + extra <= qiddm::kWideTileWires;
       }
+      if (split_channels && !empty && wide_is_channel(kind) != channels) ok = false;
       if (ok) {
+        if (empty) channels = wide_is_channel(kind);
         placed[i] = 1;
         plan->order.push_back(i);
         plan->op_segment[i] = (int32_t)plan->segments.size();
@@ -224,6 +239,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
     if (nl != qiddm::kWideLocalBits || ng != sg.n_tile_bits || sg.lpos[0] != 0 || sg.lpos[1] != 1)
       return fail(QIDDM_ERR_INVALID, "planner built a malformed tile (%d local, %d tile bits)", nl, ng);
     plan->segments.push_back(sg);
+    plan->seg_channel.push_back(channels ? 1 : 0);
   }
   return QIDDM_OK;
 }
@@ -249,10 +265,175 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
     if (embeds) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, features, norms, m, s0);
     for (const qiddm::WideSegment& sg : plan.segments)
       hipLaunchKernelGGL(sweep, dim3(tiles, chunk), dim3(256), smem, st, prog, angle_rows, features, gates, norms, slabs, m,
-                         sg, s0);
+                         sg, s0, (int64_t)0);
     hipLaunchKernelGGL(qiddm::mixed_wide_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "mixed_wide launch failed: %s", hipGetErrorString(e));
+  }
+  return QIDDM_OK;
+}
+
+// ---- reverse sweep of the tile-fused engine (qsim_mixed_wide_adjoint.h) ------------------------------------------------
+// Ops in front of the last state preparation reach no output: the backward plans and runs program[live_begin ..) only,
+// and their parameters keep a zero gradient.
+struct WideBwdPlan {
+  WidePlan plan;                          // of the live ops, channels split off into segments of their own
+  int32_t live_begin = 0, n_live = 0;
+  int32_t replay_end = 0;                 // segments [0, replay_end) are replayed: up to the last unitary one
+  int32_t n_snaps = 0;                    // channel segments among them
+  int32_t n_slots = 0;                    // tile partials per (tile, sample)
+  bool embed_live = false;
+  std::vector<int32_t> slot;              // per sorted live op, -1: no gradient
+  std::vector<qiddm::WideParam> params;   // grouped by the parameter they feed, program order within a group
+  std::vector<int32_t> group_begin;       // n_groups + 1
+};
+
+int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WideBwdPlan* bp) {
+  if (n < kWideMinQubits || n > kWideMaxQubits)
+    return fail(QIDDM_ERR_UNSUPPORTED, "tile-fused density-matrix execution needs %d <= n_qubits <= %d (got %d)",
+                kWideMinQubits, kWideMaxQubits, n);
+  if (n_ops < 1 || !program) return fail(QIDDM_ERR_INVALID, "empty program");
+  if (!wide_is_prep(program[0].kind)) return fail(QIDDM_ERR_INVALID, "the program must start by preparing the state");
+  bp->live_begin = 0;
+  for (int i = 0; i < n_ops; ++i)
+    if (wide_is_prep(program[i].kind)) bp->live_begin = i;
+  bp->n_live = n_ops - bp->live_begin;
+  const qiddm_mixed_op_t* live = program + bp->live_begin;
+  const int rc = plan_mixed_wide(n, live, bp->n_live, &bp->plan, true);
+  if (rc != QIDDM_OK) return rc;
+  const int n_seg = (int)bp->plan.segments.size();
+  bp->replay_end = n_seg;
+  while (bp->replay_end > 0 && bp->plan.seg_channel[bp->replay_end - 1]) --bp->replay_end;
+  bp->n_snaps = 0;
+  for (int s = 0; s < bp->replay_end; ++s) bp->n_snaps += bp->plan.seg_channel[s];
+  bp->embed_live = live[0].kind == qiddm::kMixAmpEmbed;
+  bp->slot.assign(bp->n_live, -1);
+  bp->n_slots = 0;
+  std::vector<std::pair<int64_t, int32_t>> keyed;  // (parameter, sorted position)
+  for (int i = 0; i < bp->n_live; ++i) {
+    const qiddm_mixed_op_t& op = live[bp->plan.order[i]];
+    const bool gate = op.kind == qiddm::kMixGate;
+    if (!gate && !((op.kind == qiddm::kMixPhase || op.kind == qiddm::kMixRY) && op.a >= 0)) continue;
+    bp->slot[i] = bp->n_slots;
+    bp->n_slots += gate ? 8 : 1;
+    keyed.push_back({((int64_t)(gate ? 1 : 0) << 32) | (uint32_t)op.a, i});
+  }
+  std::stable_sort(keyed.begin(), keyed.end(),
+                   [](const std::pair<int64_t, int32_t>& x, const std::pair<int64_t, int32_t>& y) { return x.first < y.first; });
+  bp->params.clear();
+  bp->group_begin.clear();
+  for (size_t k = 0; k < keyed.size(); ++k) {
+    const qiddm_mixed_op_t& op = live[bp->plan.order[keyed[k].second]];
+    if (k == 0 || keyed[k].first != keyed[k - 1].first) bp->group_begin.push_back((int32_t)k);
+    qiddm::WideParam p{};
+    p.kind = op.kind == qiddm::kMixGate ? qiddm::kMixGate : qiddm::kMixPhase;  // the finalize tells gates from angles
+    p.a = op.a;
+    p.slot = bp->slot[keyed[k].second];
+    p.scale = op.scale;
+    bp->params.push_back(p);
+  }
+  bp->group_begin.push_back((int32_t)keyed.size());
+  return QIDDM_OK;
+}
+
+inline int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
+
+// Workspace: [sorted live program | slot per op | params | group_begin] then, per resident sample, |v|^2 and
+// Re(Lambda_0) v (AMP_EMBED), the tile partials, and 2 + n_snaps slabs.
+struct WideBwdGeometry {
+  int64_t slab_bytes, aux_bytes, part_bytes, per_sample, resident;
+  int64_t off_slot, off_params, off_groups, head, total;
+};
+
+int wide_backward_geometry(int32_t n, int32_t dtype, int64_t batch, const WideBwdPlan& bp, WideBwdGeometry* g) {
+  if (dtype != QIDDM_F32 && dtype != QIDDM_F64) return fail(QIDDM_ERR_INVALID, "unknown dtype %d", dtype);
+  if (batch < 0) return fail(QIDDM_ERR_INVALID, "negative batch");
+  g->slab_bytes = ((int64_t)1 << (2 * n)) * (dtype == QIDDM_F32 ? 8 : 16);
+  g->aux_bytes = round256(8 * (1 + ((int64_t)1 << n)));
+  g->part_bytes = round256((int64_t)bp.n_slots * ((int64_t)1 << (2 * n - qiddm::kWideLocalBits)) * 8);
+  g->per_sample = g->aux_bytes + g->part_bytes + (2 + (int64_t)bp.n_snaps) * g->slab_bytes;
+  const int64_t cap = kWideSlabBudget / g->per_sample;
+  g->resident = batch < cap ? batch : cap;
+  if (g->resident < 1) g->resident = 1;
+  g->off_slot = round256((int64_t)bp.n_live * (int64_t)sizeof(qiddm::MixedOp));
+  g->off_params = g->off_slot + round256((int64_t)bp.n_live * 4);
+  g->off_groups = g->off_params + round256((int64_t)bp.params.size() * (int64_t)sizeof(qiddm::WideParam));
+  g->head = g->off_groups + round256((int64_t)bp.group_begin.size() * 4);
+  g->total = g->head + g->resident * g->per_sample;
+  return QIDDM_OK;
+}
+
+template <typename T>
+int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, int64_t resident, unsigned char* ws,
+                               const double* angle_rows, const double* features, const double* gates,
+                               const double* grad_out, double* grad_rows, double* grad_gates, double* grad_features,
+                               qiddm::MixedScalars m, qiddm::WideBwdScalars b, int32_t n_gates, hipStream_t st) {
+  using C = qiddm::V2<T>;
+  const size_t tile_bytes = (size_t)qiddm::kWideTile * sizeof(C);
+  auto sweep = qiddm::mixed_wide_sweep<T>;
+  auto reverse = qiddm::mixed_wide_reverse_sweep<T>;
+  auto channels = qiddm::mixed_wide_adjoint_channels<T>;
+  static qiddm_capi::DeviceFlags big;
+  if (!big.get()) {
+    const void* kernels[3] = {reinterpret_cast<const void*>(sweep), reinterpret_cast<const void*>(reverse),
+                              reinterpret_cast<const void*>(channels)};
+    const size_t sizes[3] = {tile_bytes, 2 * tile_bytes, tile_bytes};
+    for (int k = 0; k < 3; ++k) {
+      if (sizes[k] <= 48 * 1024) continue;
+      hipError_t e = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizes[k]);
+      if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(e));
+    }
+    big.set();
+  }
+  const int n = m.n;
+  const size_t DD = (size_t)1 << (2 * n);
+  const unsigned D = 1u << n, tiles = 1u << (2 * n - qiddm::kWideLocalBits);
+  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
+  const int32_t* slot = reinterpret_cast<const int32_t*>(ws + g.off_slot);
+  const qiddm::WideParam* params = reinterpret_cast<const qiddm::WideParam*>(ws + g.off_params);
+  const int32_t* group_begin = reinterpret_cast<const int32_t*>(ws + g.off_groups);
+  // the per-sample regions, laid out for `resident` samples
+  double* norms = reinterpret_cast<double*>(ws + g.head);
+  double* lv = norms + resident;
+  double* partials = reinterpret_cast<double*>(ws + g.head + resident * g.aux_bytes);
+  C* slabs = reinterpret_cast<C*>(ws + g.head + resident * (g.aux_bytes + g.part_bytes));
+  const size_t set_stride = (size_t)resident * DD;  // rho sets 0 .. n_snaps, then Lambda
+  C* lam = slabs + (size_t)(bp.n_snaps + 1) * set_stride;
+  const int n_seg = (int)bp.plan.segments.size();
+  const int n_groups = (int)bp.group_begin.size() - 1;
+  for (int64_t s0 = 0; s0 < m.batch; s0 += resident) {
+    const unsigned chunk = (unsigned)(m.batch - s0 < resident ? m.batch - s0 : resident);
+    if (bp.embed_live) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, features, norms, m, s0);
+    int cur = 0;
+    for (int s = 0; s < bp.replay_end; ++s) {
+      const bool ch = bp.plan.seg_channel[s] != 0;
+      hipLaunchKernelGGL(sweep, dim3(tiles, chunk), dim3(256), tile_bytes, st, prog, angle_rows, features, gates, norms,
+                         slabs + (size_t)cur * set_stride, m, bp.plan.segments[s], s0, (int64_t)(ch ? set_stride : 0));
+      cur += ch ? 1 : 0;
+    }
+    qiddm::WideBwdScalars bs = b;
+    bs.seed = 1;
+    for (int s = n_seg - 1; s >= 0; --s) {
+      if (bp.plan.seg_channel[s]) {
+        hipLaunchKernelGGL(channels, dim3(tiles, chunk), dim3(256), tile_bytes, st, prog, grad_out, lam, m,
+                           bp.plan.segments[s], bs, s0);
+        if (s < bp.replay_end) --cur;
+      } else {
+        hipLaunchKernelGGL(reverse, dim3(tiles, chunk), dim3(256), 2 * tile_bytes, st, prog, slot, angle_rows, gates,
+                           grad_out, slabs + (size_t)cur * set_stride, lam, partials, m, bp.plan.segments[s], bs, s0);
+      }
+      bs.seed = 0;
+    }
+    if (bp.embed_live) {
+      hipLaunchKernelGGL(qiddm::mixed_wide_embed_matvec<T>, dim3(D / 4, chunk), dim3(256), 0, st, lam, features, lv, m, s0);
+      hipLaunchKernelGGL(qiddm::mixed_wide_embed_grad, dim3(chunk), dim3(256), 0, st, features, lv, grad_features, m, s0);
+    }
+    if (n_groups > 0)
+      hipLaunchKernelGGL(qiddm::mixed_wide_grad_finalize, dim3((n_groups + 3) / 4, chunk), dim3(256), 0, st, params,
+                         group_begin, n_groups, gates, partials, grad_rows, grad_gates, bp.n_slots, n_gates, tiles,
+                         m.batch, s0);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "mixed_wide backward launch failed: %s", hipGetErrorString(e));
   }
   return QIDDM_OK;
 }
@@ -496,6 +677,106 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
   if (dtype == QIDDM_F32)
     return launch_mixed_wide<float>(plan, g, resident, ws, angle_rows, features, gates, out, m, embeds, st);
   return launch_mixed_wide<double>(plan, g, resident, ws, angle_rows, features, gates, out, m, embeds, st);
+}
+
+int64_t qiddm_mixed_wide_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch,
+                                                  const qiddm_mixed_op_t* program, int32_t n_ops) {
+  WideBwdPlan bp;
+  int rc = plan_mixed_wide_backward(n_qubits, program, n_ops, &bp);
+  if (rc != QIDDM_OK) return rc;
+  WideBwdGeometry g;
+  rc = wide_backward_geometry(n_qubits, dtype, batch, bp, &g);
+  if (rc != QIDDM_OK) return rc;
+  return g.total;
+}
+
+int qiddm_mixed_wide_backward_plan(int32_t n_qubits, const qiddm_mixed_op_t* program, int32_t n_ops,
+                                   int32_t* n_replay_sweeps, int32_t* n_reverse_sweeps, int32_t* n_snapshots) {
+  WideBwdPlan bp;
+  const int rc = plan_mixed_wide_backward(n_qubits, program, n_ops, &bp);
+  if (rc != QIDDM_OK) return rc;
+  if (n_replay_sweeps) *n_replay_sweeps = bp.replay_end;
+  if (n_reverse_sweeps) *n_reverse_sweeps = (int32_t)bp.plan.segments.size();
+  if (n_snapshots) *n_snapshots = bp.n_snaps;
+  return QIDDM_OK;
+}
+
+int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t* program, int32_t n_ops,
+                              const double* angle_rows, int64_t rows_ld, int32_t n_rows, const double* features,
+                              int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with,
+                              const double* gates, int32_t n_gates, int32_t measure, int64_t batch,
+                              const double* grad_out, int64_t gout_ld, double* grad_rows, double* grad_gates,
+                              double* grad_features, void* workspace, int64_t workspace_bytes, void* stream) {
+  WideGeometry fg;
+  int rc = wide_geometry(n_qubits, dtype, batch, n_ops, &fg);  // wires, dtype, batch, n_ops
+  if (rc != QIDDM_OK) return rc;
+  if (measure != QIDDM_MEAS_PROBS && measure != QIDDM_MEAS_EXPZ) return fail(QIDDM_ERR_INVALID, "unknown measure %d", measure);
+  if (batch == 0) return QIDDM_OK;
+  if (!program || n_ops < 1) return fail(QIDDM_ERR_INVALID, "empty program");
+  if (n_rows < 0 || n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
+  if (n_rows > 0 && (!angle_rows || rows_ld < batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
+  if (n_gates > 0 && !gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");
+  rc = check_program(n_qubits, program, n_ops, n_rows, features, feat_ld, n_features, n_gates);
+  if (rc != QIDDM_OK) return rc;
+  const int64_t width = measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits;
+  if (!grad_out || gout_ld < width)
+    return fail(QIDDM_ERR_INVALID, "grad_out missing or gout_ld < %lld", (long long)width);
+  bool embeds = false;
+  for (int i = 0; i < n_ops; ++i) embeds = embeds || program[i].kind == qiddm::kMixAmpEmbed;
+  if (n_rows > 0 && !grad_rows) return fail(QIDDM_ERR_INVALID, "grad_rows is NULL");
+  if (n_gates > 0 && !grad_gates) return fail(QIDDM_ERR_INVALID, "grad_gates is NULL");
+  if (embeds && !grad_features) return fail(QIDDM_ERR_INVALID, "grad_features is NULL");
+  WideBwdPlan bp;
+  rc = plan_mixed_wide_backward(n_qubits, program, n_ops, &bp);
+  if (rc != QIDDM_OK) return rc;
+  WideBwdGeometry g;
+  rc = wide_backward_geometry(n_qubits, dtype, batch, bp, &g);
+  if (rc != QIDDM_OK) return rc;
+  // a smaller workspace than qiddm_mixed_wide_backward_workspace_bytes() is accepted down to one sample's worth
+  int64_t resident = workspace ? (workspace_bytes - g.head) / g.per_sample : 0;
+  if (resident > g.resident) resident = g.resident;
+  if (resident < 1)
+    return fail(QIDDM_ERR_INVALID,
+                "workspace of at least %lld B needed (qiddm_mixed_wide_backward_workspace_bytes: %lld), got %lld",
+                (long long)(g.head + g.per_sample), (long long)g.total, (long long)workspace_bytes);
+  // the head in one upload: sorted live program, slots, params, groups
+  std::vector<unsigned char> head((size_t)g.head, 0);
+  qiddm_mixed_op_t* sorted = reinterpret_cast<qiddm_mixed_op_t*>(head.data());
+  for (int i = 0; i < bp.n_live; ++i) sorted[i] = program[bp.live_begin + bp.plan.order[i]];
+  memcpy(head.data() + g.off_slot, bp.slot.data(), bp.slot.size() * 4);
+  if (!bp.params.empty()) memcpy(head.data() + g.off_params, bp.params.data(), bp.params.size() * sizeof(qiddm::WideParam));
+  memcpy(head.data() + g.off_groups, bp.group_begin.data(), bp.group_begin.size() * 4);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  // pageable source: the copy is staged before the call returns, so `head` may go out of scope
+  hipError_t e = hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "program upload failed: %s", hipGetErrorString(e));
+  // parameters no live op feeds keep a zero gradient
+  if (n_rows > 0) e = hipMemsetAsync(grad_rows, 0, (size_t)n_rows * (size_t)batch * 8, st);
+  if (e == hipSuccess && n_gates > 0) e = hipMemsetAsync(grad_gates, 0, (size_t)batch * (size_t)n_gates * 64, st);
+  if (e == hipSuccess && embeds && !bp.embed_live)
+    e = hipMemsetAsync(grad_features, 0, (size_t)batch * (size_t)n_features * 8, st);
+  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "gradient reset failed: %s", hipGetErrorString(e));
+  qiddm::MixedScalars m{};
+  m.n = n_qubits;
+  m.n_ops = bp.n_live;
+  m.measure = measure;
+  m.n_features = embeds ? n_features : 0;
+  m.batch = batch;
+  m.rows_ld = rows_ld;
+  m.feat_ld = feat_ld;
+  m.out_ld = 0;
+  m.enc_offset = enc_offset;
+  m.pad_with = pad_with;
+  m.slab_in_lds = 0;
+  qiddm::WideBwdScalars b{};
+  b.gout_ld = gout_ld;
+  b.n_slots = bp.n_slots;
+  if (dtype == QIDDM_F32)
+    return launch_mixed_wide_backward<float>(bp, g, resident, ws, angle_rows, features, gates, grad_out, grad_rows,
+                                             grad_gates, grad_features, m, b, n_gates, st);
+  return launch_mixed_wide_backward<double>(bp, g, resident, ws, angle_rows, features, gates, grad_out, grad_rows,
+                                            grad_gates, grad_features, m, b, n_gates, st);
 }
 
 }  // extern "C"

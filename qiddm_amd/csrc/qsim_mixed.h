@@ -189,6 +189,46 @@ __device__ __forceinline__ void mixed_block_channel(const MixedChannel<T>& c, V2
   m01 = C{c.off * m01.x, c.off * m01.y};
   m10 = C{c.off * m10.x, c.off * m10.y};
 }
+// E^dagger on one block (the reverse sweeps): the transpose of E's 2 x 2 mixing of the diagonal; off-diagonals scale alike
+template <typename T>
+__device__ __forceinline__ void mixed_block_channel_adjoint(const MixedChannel<T>& c, V2<T>& m00, V2<T>& m01, V2<T>& m10,
+                                                            V2<T>& m11) {
+  using C = V2<T>;
+  const C n00 = C{c.d_own * m00.x + c.d_other_to_1 * m11.x, c.d_own * m00.y + c.d_other_to_1 * m11.y};
+  const C n11 = C{c.d11 * m11.x + c.d_other_to_0 * m00.x, c.d11 * m11.y + c.d_other_to_0 * m00.y};
+  m00 = n00;
+  m11 = n11;
+  m01 = C{c.off * m01.x, c.off * m01.y};
+  m10 = C{c.off * m10.x, c.off * m10.y};
+}
+// acc += B_rho B_Lambda^dagger of one block: N_ab = sum_c rho_ac conj(Lambda_bc), (re, im) of N00, N01, N10, N11
+template <typename T>
+__device__ __forceinline__ void mixed_block_n_accumulate(double (&acc)[8], V2<T> r00, V2<T> r01, V2<T> r10, V2<T> r11,
+                                                         V2<T> l00, V2<T> l01, V2<T> l10, V2<T> l11) {
+  using C = V2<T>;
+  const C n00 = cmulc<T>(r00, l00) + cmulc<T>(r01, l01), n01 = cmulc<T>(r00, l10) + cmulc<T>(r01, l11);
+  const C n10 = cmulc<T>(r10, l00) + cmulc<T>(r11, l01), n11 = cmulc<T>(r10, l10) + cmulc<T>(r11, l11);
+  acc[0] += (double)n00.x; acc[1] += (double)n00.y;
+  acc[2] += (double)n01.x; acc[3] += (double)n01.y;
+  acc[4] += (double)n10.x; acc[5] += (double)n10.y;
+  acc[6] += (double)n11.x; acc[7] += (double)n11.y;
+}
+// GATE: go += dL/dU from the reduced N `s` and the gate `gu` (both as (re, im) of the 00, 01, 10, 11 entries):
+// R_ba = sum_c conj(U_cb) N_ca;  dL/dRe U_ab = 2 Re R_ba, dL/dIm U_ab = -2 Im R_ba
+__device__ __forceinline__ void mixed_gate_grad_accumulate(const double* s, const double* __restrict__ gu, double* go) {
+  for (int a = 0; a < 2; ++a)
+    for (int bb = 0; bb < 2; ++bb) {
+      double re = 0.0, im = 0.0;
+      for (int c = 0; c < 2; ++c) {
+        const double ur = gu[(c * 2 + bb) * 2], ui = gu[(c * 2 + bb) * 2 + 1];
+        const double nr = s[(c * 2 + a) * 2], ni = s[(c * 2 + a) * 2 + 1];
+        re += ur * nr + ui * ni;
+        im += ur * ni - ui * nr;
+      }
+      go[(a * 2 + bb) * 2] += 2.0 * re;
+      go[(a * 2 + bb) * 2 + 1] += -2.0 * im;
+    }
+}
 // an off-diagonal element of a wire's blocks under PhaseDamping (the diagonal ones stay)
 template <typename T>
 __device__ __forceinline__ V2<T> mixed_phase_damp_elem(V2<T> v, uint32_t k, int q, int n, T off) {
@@ -498,12 +538,7 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
             const uint32_t cj = 1u << q, ci = 1u << (q + n);
             C r00 = rho[base], r01 = rho[base | cj], r10 = rho[base | ci], r11 = rho[base | ci | cj];
             C l00 = lam[base], l01 = lam[base | cj], l10 = lam[base | ci], l11 = lam[base | ci | cj];
-            const C n00 = cmulc<T>(r00, l00) + cmulc<T>(r01, l01), n01 = cmulc<T>(r00, l10) + cmulc<T>(r01, l11);
-            const C n10 = cmulc<T>(r10, l00) + cmulc<T>(r11, l01), n11 = cmulc<T>(r10, l10) + cmulc<T>(r11, l11);
-            acc[0] += (double)n00.x; acc[1] += (double)n00.y;
-            acc[2] += (double)n01.x; acc[3] += (double)n01.y;
-            acc[4] += (double)n10.x; acc[5] += (double)n10.y;
-            acc[6] += (double)n11.x; acc[7] += (double)n11.y;
+            mixed_block_n_accumulate<T>(acc, r00, r01, r10, r11, l00, l01, l10, l11);
             mixed_udag_b_u<T>(r00, r01, r10, r11, u00, u01, u10, u11);
             mixed_udag_b_u<T>(l00, l01, l10, l11, u00, u01, u10, u11);
             rho[base] = r00; rho[base | cj] = r01; rho[base | ci] = r10; rho[base | ci | cj] = r11;
@@ -553,25 +588,17 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
         case kMixPhaseDamp:
         case kMixAmpDamp:
         case kMixDepol: {
-          // E^dagger on the diagonal is the transpose of E's 2 x 2 mixing; off-diagonals scale alike
-          T off, d_own, d_other_to_0, d_other_to_1, d11;
-          if (op.kind == kMixPhaseDamp) {
-            off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = 1; d_other_to_0 = 0; d_other_to_1 = 0;
-          } else if (op.kind == kMixAmpDamp) {
-            off = (T)sqrt(1.0 - op.p); d_own = 1; d11 = (T)(1.0 - op.p); d_other_to_0 = (T)op.p; d_other_to_1 = 0;
-          } else {
-            off = (T)(1.0 - 4.0 * op.p / 3.0); d_own = (T)(1.0 - 2.0 * op.p / 3.0); d11 = d_own;
-            d_other_to_0 = (T)(2.0 * op.p / 3.0); d_other_to_1 = d_other_to_0;
-          }
+          const MixedChannel<T> ch = mixed_channel<T>(op);
           const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
           for (uint32_t t = tid; t < DD / 4; t += 256) {
             const uint32_t base = insert_two_bits(t, q, q + n);
             const uint32_t cj = 1u << q, ci = 1u << (q + n);
-            const C l00 = lam[base], l01 = lam[base | cj], l10 = lam[base | ci], l11 = lam[base | ci | cj];
-            lam[base] = C{d_own * l00.x + d_other_to_1 * l11.x, d_own * l00.y + d_other_to_1 * l11.y};
-            lam[base | ci | cj] = C{d11 * l11.x + d_other_to_0 * l00.x, d11 * l11.y + d_other_to_0 * l00.y};
-            lam[base | cj] = C{off * l01.x, off * l01.y};
-            lam[base | ci] = C{off * l10.x, off * l10.y};
+            C l00 = lam[base], l01 = lam[base | cj], l10 = lam[base | ci], l11 = lam[base | ci | cj];
+            mixed_block_channel_adjoint<T>(ch, l00, l01, l10, l11);
+            lam[base] = l00;
+            lam[base | ci | cj] = l11;
+            lam[base | cj] = l01;
+            lam[base | ci] = l10;
             rho[base] = sp[base];
             rho[base | cj] = sp[base | cj];
             rho[base | ci] = sp[base | ci];
@@ -611,21 +638,7 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
           if (op.kind == kMixGate) {
             double s[8];
             for (int k = 0; k < 8; ++k) s[k] = s_part[buf][0][k] + s_part[buf][1][k] + s_part[buf][2][k] + s_part[buf][3][k];
-            const double* __restrict__ gu = gates + (size_t)op.a * 8;
-            double* __restrict__ go = grad_gates + ((size_t)sample * b.n_gates + op.a) * 8;
-            // R_ba = sum_c conj(U_cb) N_ca;  dL/dRe U_ab = 2 Re R_ba, dL/dIm U_ab = -2 Im R_ba
-            for (int a = 0; a < 2; ++a)
-              for (int bb = 0; bb < 2; ++bb) {
-                double re = 0.0, im = 0.0;
-                for (int c = 0; c < 2; ++c) {
-                  const double ur = gu[(c * 2 + bb) * 2], ui = gu[(c * 2 + bb) * 2 + 1];
-                  const double nr = s[(c * 2 + a) * 2], ni = s[(c * 2 + a) * 2 + 1];
-                  re += ur * nr + ui * ni;
-                  im += ur * ni - ui * nr;
-                }
-                go[(a * 2 + bb) * 2] += 2.0 * re;
-                go[(a * 2 + bb) * 2 + 1] += -2.0 * im;
-              }
+            mixed_gate_grad_accumulate(s, gates + (size_t)op.a * 8, grad_gates + ((size_t)sample * b.n_gates + op.a) * 8);
           } else if (op.a >= 0) {
             const double s = s_part[buf][0][0] + s_part[buf][1][0] + s_part[buf][2][0] + s_part[buf][3][0];
             grad_rows[(size_t)op.a * m.batch + sample] += op.scale * s;

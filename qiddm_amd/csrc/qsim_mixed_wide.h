@@ -15,20 +15,33 @@
 // Wires n-1 and n-2 (q = 0, 1) belong to every tile: the two lowest column bits are local, so a lane moves two
 // consecutive elements (16 bytes in float32) and four lanes cover 64 contiguous bytes.
 // Per 2 x 2 block and per element the arithmetic is that of mixed_apply_op (shared helpers in qsim_mixed.h).
+// `dst_delta` (elements; 0 in the forward) moves the write-back to another set of slabs: the reverse sweep's replay
+// (qsim_mixed_wide_adjoint.h) leaves the state in front of a channel segment behind as its snapshot.
 #pragma once
 #include "qsim_mixed.h"
 
 namespace qiddm {
 
-constexpr int kWideLocalBits = 12;
-constexpr int kWideTileWires = 6;
+// Tile width: six wires.  -DQIDDM_WIDE_TILE_WIRES=5 builds the five-wire variant (2^10 elements a tile) for A/B runs;
+// the loops below take their trip counts from it.
+#ifndef QIDDM_WIDE_TILE_WIRES
+#define QIDDM_WIDE_TILE_WIRES 6
+#endif
+constexpr int kWideTileWires = QIDDM_WIDE_TILE_WIRES;
+constexpr int kWideLocalBits = 2 * kWideTileWires;
 constexpr uint32_t kWideTile = 1u << kWideLocalBits;
+constexpr int kWideMaxTileBits = 20 - kWideLocalBits;  // tile-number bits at 10 wires
+constexpr int kWideHiBits = kWideLocalBits - 6;        // local bits above the low six
+constexpr int kWidePairs = kWideTile / 512;            // element pairs per thread
+constexpr int kWideBlocks = kWideTile / 1024;          // 2 x 2 blocks per thread
+constexpr int kWideElems = kWideTile / 256;            // elements per thread
+static_assert(kWideTileWires == 5 || kWideTileWires == 6, "tile width");
 
 struct WideSegment {
   int32_t op_begin, op_end;   // into the uploaded (segment-sorted) program
-  int32_t n_tile_bits, pad_;  // 2n - 12
+  int32_t n_tile_bits, pad_;  // 2n - kWideLocalBits
   uint8_t lpos[12];           // global bit of local bit r, ascending; lpos[0] = 0, lpos[1] = 1
-  uint8_t gpos[8];            // global bit of tile-number bit r, ascending
+  uint8_t gpos[kWideMaxTileBits];  // global bit of tile-number bit r, ascending
 };
 
 template <typename T>
@@ -64,7 +77,8 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
                                                         const double* __restrict__ feats,
                                                         const double* __restrict__ gates,
                                                         const double* __restrict__ norms, V2<T>* __restrict__ slabs,
-                                                        const MixedScalars m, const WideSegment sg, int64_t sample0) {
+                                                        const MixedScalars m, const WideSegment sg, int64_t sample0,
+                                                        int64_t dst_delta) {
   using C = V2<T>;
   extern __shared__ __attribute__((aligned(32))) unsigned char smem_raw[];
   __shared__ uint32_t s_lo[64], s_hi[64];
@@ -72,16 +86,16 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
   const int n = m.n, tid = threadIdx.x;
   const int64_t resident = blockIdx.y, sample = sample0 + resident;
   C* __restrict__ rho = slabs + ((size_t)resident << (2 * n));
-  const uint32_t base = wide_deposit<8>(blockIdx.x, sg.gpos);  // the tile number has n_tile_bits bits
+  const uint32_t base = wide_deposit<kWideMaxTileBits>(blockIdx.x, sg.gpos);  // the tile number has n_tile_bits bits
   if (tid < 64) {
     s_lo[tid] = wide_deposit<6>(tid, sg.lpos);
-    s_hi[tid] = wide_deposit<6>(tid, sg.lpos + 6);
+    s_hi[tid] = wide_deposit<kWideHiBits>(tid, sg.lpos + 6);
   }
   __syncthreads();
   // a thread owns the element pairs l = 2 (tid + 256 i), l + 1: global k, k + 1 (lpos[0] = 0)
-  uint32_t kown[8];
+  uint32_t kown[kWidePairs];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < kWidePairs; ++i) {
     const uint32_t l = 2u * (tid + 256u * i);
     kown[i] = base | s_lo[l & 63u] | s_hi[l >> 6];
   }
@@ -90,7 +104,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
   const int first_kind = prog[oi].kind;
   if (first_kind == kMixZero) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < kWidePairs; ++i) {
       const uint32_t l = 2u * (tid + 256u * i);
       tile[l] = C{kown[i] == 0 ? (T)1 : (T)0, (T)0};
       tile[l + 1] = C{(T)0, (T)0};
@@ -100,7 +114,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
     const double* __restrict__ row = feats + sample * m.feat_ld;
     const double inv = 1.0 / norms[resident];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < kWidePairs; ++i) {
       const uint32_t l = 2u * (tid + 256u * i);
       tile[l] = mixed_embed_elem<T>(row, kown[i], inv, m);
       tile[l + 1] = mixed_embed_elem<T>(row, kown[i] + 1u, inv, m);
@@ -108,7 +122,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
     ++oi;
   } else {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < kWidePairs; ++i) {
       const uint32_t l = 2u * (tid + 256u * i);
       const V4<T> v = *reinterpret_cast<const V4<T>*>(rho + kown[i]);
       *reinterpret_cast<V4<T>*>(tile + l) = v;
@@ -128,7 +142,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         C up, dn;
         mixed_phase_factors<T>(mixed_angle(op, angle_rows, m, sample), up, dn);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < kWidePairs; ++i) {
           const uint32_t l = 2u * (tid + 256u * i);
           tile[l] = mixed_phase_elem<T>(tile[l], kown[i], q, n, up, dn);
           tile[l + 1] = mixed_phase_elem<T>(tile[l + 1], kown[i] + 1u, q, n, up, dn);
@@ -138,7 +152,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
       case kMixCZ: {
         const int qt = n - 1 - op.a;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < kWidePairs; ++i) {
           const uint32_t l = 2u * (tid + 256u * i);
           tile[l] = mixed_cz_elem<T>(tile[l], kown[i], q, qt, n);
           tile[l + 1] = mixed_cz_elem<T>(tile[l + 1], kown[i] + 1u, q, qt, n);
@@ -148,7 +162,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
       case kMixPhaseDamp: {
         const T off = mixed_channel<T>(op).off;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < kWidePairs; ++i) {
           const uint32_t l = 2u * (tid + 256u * i);
           tile[l] = mixed_phase_damp_elem<T>(tile[l], kown[i], q, n, off);
           tile[l + 1] = mixed_phase_damp_elem<T>(tile[l + 1], kown[i] + 1u, q, n, off);
@@ -167,7 +181,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         if (unitary) u = mixed_unitary<T>(op, angle_rows, gates, m, sample);
         else ch = mixed_channel<T>(op);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < kWideBlocks; ++i) {
           const uint32_t l = insert_two_bits(tid + 256u * i, a, b);
           C m00 = tile[l], m01 = tile[l | cj], m10 = tile[l | ci], m11 = tile[l | ci | cj];
           if (unitary) mixed_block_unitary<T>(u, m00, m01, m10, m11);
@@ -185,7 +199,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         const int ac = wide_local_rank(sg, q), at = wide_local_rank(sg, qt);
         const int bc = wide_local_rank(sg, q + n), bt = wide_local_rank(sg, qt + n);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
+        for (int i = 0; i < kWideElems; ++i) {
           const uint32_t l = tid + 256u * i;
           const uint32_t pl = l ^ (((l >> ac) & 1u) << at) ^ (((l >> bc) & 1u) << bt);
           if (l < pl) {
@@ -201,9 +215,9 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
   }
   if (!owned) __syncthreads();
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < kWidePairs; ++i) {
     const uint32_t l = 2u * (tid + 256u * i);
-    *reinterpret_cast<V4<T>*>(rho + kown[i]) = *reinterpret_cast<const V4<T>*>(tile + l);
+    *reinterpret_cast<V4<T>*>(rho + dst_delta + kown[i]) = *reinterpret_cast<const V4<T>*>(tile + l);
   }
 }
 

@@ -1,0 +1,375 @@
+// qsim_mixed_wide_adjoint.h -- reverse sweep of the tile-fused density-matrix engine (qsim_mixed_wide.h): the exact
+// vector-Jacobian product of qiddm_mixed_wide_forward at n = 7..10, with the mathematics of mixed_backward_kernel
+// (qsim_mixed.h).  The reference trains such layers with backprop on default.mixed (nn/qdense.py:71-105,
+// src/fashion_noise.py:210-225).
+//
+// The host plans the program a second time (plan_mixed_wide with split_channels): a segment holds either channels only
+// or no channel.  A sample owns 2 + n_snaps slabs: rho sets 0..n_snaps and Lambda.
+//   replay    the forward sweeps; a channel segment reads rho set c and writes set c + 1, so set c stays behind as the
+//             snapshot (a channel is not inverted).  Channel segments after the last unitary one are not replayed:
+//             nothing reads the state behind them.
+//   reverse   segments backwards, one launch over (tile, sample) each.
+//             unitary segment: mixed_wide_reverse_sweep holds the rho tile and the Lambda tile in LDS and walks the ops
+//               backwards: U^dagger . U on both, N = sum B_rho B_Lambda^dagger of the tile in double -> one partial per
+//               (slot, tile, sample).  PHASE is element-wise on any wire.
+//             channel segment: mixed_wide_adjoint_channels applies E^dagger to the Lambda tile; rho steps back one set.
+//             The first reverse launch generates Lambda_N from grad_out instead of reading it.
+//   AMP_EMBED dL/dv from Re(Lambda_0) v: a matrix-vector pass over Lambda's slab, then one workgroup per sample.
+//   finalize  a wave per parameter (angle row / gate) and sample sums the tile partials in a fixed order: no atomics,
+//             reruns are bit-identical and the result does not depend on how the batch is chunked.
+#pragma once
+#include "qsim_mixed_wide.h"
+
+namespace qiddm {
+
+struct WideBwdScalars {
+  int64_t gout_ld;
+  int32_t n_slots, seed;  // seed: generate Lambda_N from grad_out instead of reading the slab
+};
+
+// a gradient-carrying op of the (segment-sorted) program, grouped by the parameter it feeds
+struct WideParam {
+  int32_t kind, a, slot, pad_;
+  double scale;
+};
+
+// the global indices of the element pairs a thread owns: l = 2 (tid + 256 i) -> k, k + 1 (as in mixed_wide_sweep)
+__device__ __forceinline__ void wide_owned_indices(const WideSegment& sg, uint32_t* s_lo, uint32_t* s_hi,
+                                                   uint32_t (&kown)[kWidePairs]) {
+  const int tid = threadIdx.x;
+  const uint32_t base = wide_deposit<kWideMaxTileBits>(blockIdx.x, sg.gpos);
+  if (tid < 64) {
+    s_lo[tid] = wide_deposit<6>(tid, sg.lpos);
+    s_hi[tid] = wide_deposit<kWideHiBits>(tid, sg.lpos + 6);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i) {
+    const uint32_t l = 2u * (tid + 256u * i);
+    kown[i] = base | s_lo[l & 63u] | s_hi[l >> 6];
+  }
+}
+
+// element k of Lambda_N = dL/drho_N: diag(g) for probs, sum_w g_w (1 - 2 bit_w) for <Z> (the seed of
+// mixed_backward_kernel)
+template <typename T>
+__device__ __forceinline__ V2<T> wide_seed_elem(const double* __restrict__ g, uint32_t k, const MixedScalars& m) {
+  const int n = m.n;
+  const uint32_t i = k >> n, j = k & ((1u << n) - 1u);
+  double v = 0.0;
+  if (i == j) {
+    if (m.measure == 0) {
+      v = g[i];
+    } else {
+      for (int w = 0; w < n; ++w) v += ((i >> (n - 1 - w)) & 1u) ? -g[w] : g[w];
+    }
+  }
+  return V2<T>{(T)v, (T)0};
+}
+
+template <typename T>
+__device__ __forceinline__ void wide_load_lambda(V2<T>* tile, const V2<T>* __restrict__ lam, const uint32_t (&kown)[kWidePairs],
+                                                 const double* __restrict__ g, const MixedScalars& m, bool seed) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i) {
+    const uint32_t l = 2u * (tid + 256u * i);
+    if (seed) {
+      tile[l] = wide_seed_elem<T>(g, kown[i], m);
+      tile[l + 1] = wide_seed_elem<T>(g, kown[i] + 1u, m);
+    } else {
+      *reinterpret_cast<V4<T>*>(tile + l) = *reinterpret_cast<const V4<T>*>(lam + kown[i]);
+    }
+  }
+}
+
+// One unitary segment backwards on the rho tile and the Lambda tile of (tile, sample).  slot[oi] >= 0: the op feeds a
+// parameter and writes its tile partial(s) to partials[(resident * n_slots + slot + c) * tiles + tile].
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_reverse_sweep(
+    const MixedOp* __restrict__ prog, const int32_t* __restrict__ slot, const double* __restrict__ angle_rows,
+    const double* __restrict__ gates, const double* __restrict__ grad_out, V2<T>* __restrict__ rho_slabs,
+    V2<T>* __restrict__ lam_slabs, double* __restrict__ partials, const MixedScalars m, const WideSegment sg,
+    const WideBwdScalars b, int64_t sample0) {
+  using C = V2<T>;
+  extern __shared__ __attribute__((aligned(32))) unsigned char smem_raw[];
+  __shared__ uint32_t s_lo[64], s_hi[64];
+  __shared__ double s_part[2][4][8];
+  C* rt = reinterpret_cast<C*>(smem_raw);
+  C* lt = rt + kWideTile;
+  const int n = m.n, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t resident = blockIdx.y, sample = sample0 + resident;
+  C* __restrict__ rho = rho_slabs + ((size_t)resident << (2 * n));
+  C* __restrict__ lam = lam_slabs + ((size_t)resident << (2 * n));
+  uint32_t kown[kWidePairs];
+  wide_owned_indices(sg, s_lo, s_hi, kown);
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i) {
+    const uint32_t l = 2u * (tid + 256u * i);
+    *reinterpret_cast<V4<T>*>(rt + l) = *reinterpret_cast<const V4<T>*>(rho + kown[i]);
+  }
+  wide_load_lambda<T>(lt, lam, kown, grad_out + sample * b.gout_ld, m, b.seed != 0);
+  __syncthreads();
+
+  double* __restrict__ part = partials + (size_t)resident * b.n_slots * gridDim.x + blockIdx.x;
+  int buf = 0, prep = -1;
+  for (int oi = sg.op_end - 1; oi >= sg.op_begin; --oi) {
+    const MixedOp op = prog[oi];
+    if (op.kind == kMixZero || op.kind == kMixAmpEmbed) {  // the segment's first op: rho_0 needs no un-computing
+      prep = op.kind;
+      break;
+    }
+    const int q = n - 1 - op.wire;
+    const int sl = slot[oi];
+    int n_vals = 0;
+    switch (op.kind) {
+      case kMixPhase: {
+        // Im Tr(Z N) = Im N00 - Im N11 = sum_k (1 - 2 rowbit_k) Im(rho_k conj(Lambda_k)); the same before and after
+        C up, dn;
+        mixed_phase_factors<T>(mixed_angle(op, angle_rows, m, sample), up, dn);
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < kWidePairs; ++i) {
+          const uint32_t l = 2u * (tid + 256u * i);
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const uint32_t k = kown[i] + e;
+            const C r = rt[l + e], lm = lt[l + e];
+            const double im = (double)cmulc<T>(r, lm).y;
+            acc += ((k >> (q + n)) & 1u) ? -im : im;
+            rt[l + e] = mixed_phase_elem<T>(r, k, q, n, dn, up);  // the conjugate factors
+            lt[l + e] = mixed_phase_elem<T>(lm, k, q, n, dn, up);
+          }
+        }
+        if (sl >= 0) {
+          const double s = mixed_wave_sum(acc);
+          if (lane == 0) s_part[buf][wave][0] = s;
+          n_vals = 1;
+        }
+        break;
+      }
+      case kMixRY:
+      case kMixGate: {
+        const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
+        const uint32_t cj = 1u << a, ci = 1u << bb;
+        const MixedU<T> u = mixed_unitary<T>(op, angle_rows, gates, m, sample);
+        double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < kWideBlocks; ++i) {
+          const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
+          C r00 = rt[l], r01 = rt[l | cj], r10 = rt[l | ci], r11 = rt[l | ci | cj];
+          C l00 = lt[l], l01 = lt[l | cj], l10 = lt[l | ci], l11 = lt[l | ci | cj];
+          mixed_block_n_accumulate<T>(acc, r00, r01, r10, r11, l00, l01, l10, l11);
+          mixed_udag_b_u<T>(r00, r01, r10, r11, u.u00, u.u01, u.u10, u.u11);
+          mixed_udag_b_u<T>(l00, l01, l10, l11, u.u00, u.u01, u.u10, u.u11);
+          rt[l] = r00; rt[l | cj] = r01; rt[l | ci] = r10; rt[l | ci | cj] = r11;
+          lt[l] = l00; lt[l | cj] = l01; lt[l | ci] = l10; lt[l | ci | cj] = l11;
+        }
+        if (op.kind == kMixGate) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const double s = mixed_wave_sum(acc[k]);
+            if (lane == 0) s_part[buf][wave][k] = s;
+          }
+          n_vals = 8;
+        } else if (sl >= 0) {  // Im Tr(Y N) = Re N01 - Re N10
+          const double s = mixed_wave_sum(acc[2] - acc[4]);
+          if (lane == 0) s_part[buf][wave][0] = s;
+          n_vals = 1;
+        }
+        break;
+      }
+      case kMixCZ: {
+        const int qt = n - 1 - op.a;
+#pragma unroll
+        for (int i = 0; i < kWidePairs; ++i) {
+          const uint32_t l = 2u * (tid + 256u * i);
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            rt[l + e] = mixed_cz_elem<T>(rt[l + e], kown[i] + e, q, qt, n);
+            lt[l + e] = mixed_cz_elem<T>(lt[l + e], kown[i] + e, q, qt, n);
+          }
+        }
+        break;
+      }
+      case kMixCNOT: {
+        const int qt = n - 1 - op.a;
+        const int ac = wide_local_rank(sg, q), at = wide_local_rank(sg, qt);
+        const int bc = wide_local_rank(sg, q + n), bt = wide_local_rank(sg, qt + n);
+#pragma unroll
+        for (int i = 0; i < kWideElems; ++i) {
+          const uint32_t l = tid + 256u * i;
+          const uint32_t pl = l ^ (((l >> ac) & 1u) << at) ^ (((l >> bc) & 1u) << bt);
+          if (l < pl) {
+            const C tr = rt[l], tl = lt[l];
+            rt[l] = rt[pl];
+            rt[pl] = tr;
+            lt[l] = lt[pl];
+            lt[pl] = tl;
+          }
+        }
+        break;
+      }
+      default: break;
+    }
+    __syncthreads();
+    if (n_vals) {  // uniform over the workgroup; s_part is double-buffered, so the next op may already fill the other half
+      if (tid < n_vals)
+        part[(size_t)(sl + tid) * gridDim.x] = s_part[buf][0][tid] + s_part[buf][1][tid] + s_part[buf][2][tid] + s_part[buf][3][tid];
+      buf ^= 1;
+    }
+  }
+  // rho_0 is not read again, and Lambda_0 only by the AMP_EMBED gradient
+  if (prep < 0) {
+#pragma unroll
+    for (int i = 0; i < kWidePairs; ++i) {
+      const uint32_t l = 2u * (tid + 256u * i);
+      *reinterpret_cast<V4<T>*>(rho + kown[i]) = *reinterpret_cast<const V4<T>*>(rt + l);
+    }
+  }
+  if (prep != kMixZero) {
+#pragma unroll
+    for (int i = 0; i < kWidePairs; ++i) {
+      const uint32_t l = 2u * (tid + 256u * i);
+      *reinterpret_cast<V4<T>*>(lam + kown[i]) = *reinterpret_cast<const V4<T>*>(lt + l);
+    }
+  }
+}
+
+// One channel segment backwards: E^dagger on the Lambda tile of (tile, sample), ops in reverse
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp* __restrict__ prog,
+                                                                   const double* __restrict__ grad_out,
+                                                                   V2<T>* __restrict__ lam_slabs, const MixedScalars m,
+                                                                   const WideSegment sg, const WideBwdScalars b,
+                                                                   int64_t sample0) {
+  using C = V2<T>;
+  extern __shared__ __attribute__((aligned(32))) unsigned char smem_raw[];
+  __shared__ uint32_t s_lo[64], s_hi[64];
+  C* lt = reinterpret_cast<C*>(smem_raw);
+  const int n = m.n, tid = threadIdx.x;
+  const int64_t resident = blockIdx.y, sample = sample0 + resident;
+  C* __restrict__ lam = lam_slabs + ((size_t)resident << (2 * n));
+  uint32_t kown[kWidePairs];
+  wide_owned_indices(sg, s_lo, s_hi, kown);
+  wide_load_lambda<T>(lt, lam, kown, grad_out + sample * b.gout_ld, m, b.seed != 0);
+  bool owned = true;  // PhaseDamping works on the elements its thread owns: no barrier between two of them
+  for (int oi = sg.op_end - 1; oi >= sg.op_begin; --oi) {
+    const MixedOp op = prog[oi];
+    const int q = n - 1 - op.wire;
+    const bool diag = op.kind == kMixPhaseDamp;
+    if (!(diag && owned)) __syncthreads();
+    owned = diag;
+    const MixedChannel<T> ch = mixed_channel<T>(op);
+    if (diag) {
+#pragma unroll
+      for (int i = 0; i < kWidePairs; ++i) {
+        const uint32_t l = 2u * (tid + 256u * i);
+        lt[l] = mixed_phase_damp_elem<T>(lt[l], kown[i], q, n, ch.off);
+        lt[l + 1] = mixed_phase_damp_elem<T>(lt[l + 1], kown[i] + 1u, q, n, ch.off);
+      }
+    } else {
+      const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
+      const uint32_t cj = 1u << a, ci = 1u << bb;
+#pragma unroll
+      for (int i = 0; i < kWideBlocks; ++i) {
+        const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
+        C l00 = lt[l], l01 = lt[l | cj], l10 = lt[l | ci], l11 = lt[l | ci | cj];
+        mixed_block_channel_adjoint<T>(ch, l00, l01, l10, l11);
+        lt[l] = l00;
+        lt[l | cj] = l01;
+        lt[l | ci] = l10;
+        lt[l | ci | cj] = l11;
+      }
+    }
+  }
+  if (!owned) __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i) {
+    const uint32_t l = 2u * (tid + 256u * i);
+    *reinterpret_cast<V4<T>*>(lam + kown[i]) = *reinterpret_cast<const V4<T>*>(lt + l);
+  }
+}
+
+// (Re(Lambda_0) v)_i, one wave per row i of every resident sample's Lambda: lv[resident * 2^n + i]
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_embed_matvec(const V2<T>* __restrict__ lam_slabs,
+                                                               const double* __restrict__ feats, double* __restrict__ lv,
+                                                               const MixedScalars m, int64_t sample0) {
+  const int n = m.n, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t D = 1u << n, i = blockIdx.x * 4u + wave;
+  const int64_t resident = blockIdx.y;
+  const double* __restrict__ row = feats + (sample0 + resident) * m.feat_ld;
+  const V2<T>* __restrict__ lam = lam_slabs + ((size_t)resident << (2 * n)) + ((size_t)i << n);
+  double acc = 0.0;
+  for (uint32_t j = lane; j < D; j += 64) {
+    const double vj = j < (uint32_t)m.n_features ? row[j] + m.enc_offset : m.pad_with;
+    acc += (double)lam[j].x * vj;
+  }
+  acc = mixed_wave_sum(acc);
+  if (lane == 0) lv[(size_t)resident * D + i] = acc;
+}
+
+// dL/dv = 2 (Re(Lambda) v - (v^T Re(Lambda) v / |v|^2) v) / |v|^2 of one sample (the AMP_EMBED step of
+// mixed_backward_kernel)
+__global__ __launch_bounds__(256) void mixed_wide_embed_grad(const double* __restrict__ feats, const double* __restrict__ lv,
+                                                             double* __restrict__ grad_feats, const MixedScalars m,
+                                                             int64_t sample0) {
+  __shared__ double s_red[256];
+  const int tid = threadIdx.x;
+  const uint32_t D = 1u << m.n;
+  const int64_t sample = sample0 + blockIdx.x;
+  const double* __restrict__ row = feats + sample * m.feat_ld;
+  const double* __restrict__ l = lv + (size_t)blockIdx.x * D;
+  double vv = 0.0, vl = 0.0;
+  for (uint32_t k = tid; k < D; k += 256) {
+    const double v = k < (uint32_t)m.n_features ? row[k] + m.enc_offset : m.pad_with;
+    vv += v * v;
+    vl += v * l[k];
+  }
+  const double inv = 1.0 / mixed_block_sum(vv, s_red);
+  const double quad = mixed_block_sum(vl, s_red) * inv;
+  for (uint32_t k = tid; k < (uint32_t)m.n_features; k += 256)
+    grad_feats[sample * m.n_features + k] = 2.0 * (l[k] - quad * (row[k] + m.enc_offset)) * inv;
+}
+
+// One wave per (parameter group, sample): the tile partials of every op of the group, summed lane-strided and then
+// across the wave, in program order.  group_begin[g] .. group_begin[g + 1] index `params`; a group's ops share kind and a.
+__global__ __launch_bounds__(256) void mixed_wide_grad_finalize(const WideParam* __restrict__ params,
+                                                                const int32_t* __restrict__ group_begin, int32_t n_groups,
+                                                                const double* __restrict__ gates,
+                                                                const double* __restrict__ partials,
+                                                                double* __restrict__ grad_rows, double* __restrict__ grad_gates,
+                                                                int32_t n_slots, int32_t n_gates, uint32_t tiles,
+                                                                int64_t batch, int64_t sample0) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + wave;
+  if (g >= n_groups) return;
+  const int64_t resident = blockIdx.y, sample = sample0 + resident;
+  const double* __restrict__ part = partials + (size_t)resident * n_slots * tiles;
+  const int begin = group_begin[g], end = group_begin[g + 1];
+  const WideParam head = params[begin];
+  double go[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int pi = begin; pi < end; ++pi) {
+    const WideParam p = params[pi];
+    const int n_vals = p.kind == kMixGate ? 8 : 1;
+    double s[8];
+    for (int c = 0; c < n_vals; ++c) {
+      const double* __restrict__ src = part + (size_t)(p.slot + c) * tiles;
+      double v = 0.0;
+      for (uint32_t t = lane; t < tiles; t += 64) v += src[t];
+      s[c] = mixed_wave_sum(v);
+    }
+    if (p.kind == kMixGate) mixed_gate_grad_accumulate(s, gates + (size_t)p.a * 8, go);
+    else go[0] += p.scale * s[0];
+  }
+  if (lane != 0) return;
+  if (head.kind == kMixGate) {
+    double* __restrict__ dst = grad_gates + ((size_t)sample * n_gates + head.a) * 8;
+    for (int k = 0; k < 8; ++k) dst[k] = go[k];
+  } else {
+    grad_rows[(size_t)head.a * batch + sample] = go[0];
+  }
+}
+
+}  // namespace qiddm

@@ -5,15 +5,21 @@ bodies insert PhaseDamping / AmplitudeDamping / DepolarizingChannel, nn/qdense.p
 The tape is lowered, in order, to the op program of ``qiddm_mixed_forward`` (templates and entangler rings expanded
 here; see include/qiddm_hip.h).  Up to 8 wires it runs in one launch, one workgroup per sample.  9 and 10 wires -- the
 reference's 28 x 28 noise study samples 10-wire models (src/fashion_noise.py:42-44) -- run on the tile-fused engine
-(``qiddm_mixed_wide_forward``: rho in a workspace slab, the program cut into sweeps over six-wire tiles), forward only, once
-the wire limit has been raised: ``set_max_wires(10)`` or ``with max_wires(10):``.  The limit is 8 by default (a 10-wire
-batch takes up to 1 GiB of workspace); the engine is always chosen by the number of wires.  No CPU path.
+(``qiddm_mixed_wide_forward``: rho in a workspace slab, the program cut into sweeps over six-wire tiles) once the wire
+limit has been raised: ``set_max_wires(10)`` or ``with max_wires(10):``.  The limit is 8 by default (a 10-wire batch
+takes up to 1 GiB of workspace); the engine is always chosen by the number of wires.  No CPU path.
 
 With grad mode on and an input that requires grad, the launch is one ``torch.autograd.Function`` whose backward is
 ``qiddm_mixed_backward``: a reverse sweep over the same program that gives the exact gradient with respect to the
 angle rows, the SEL rotation matrices and the amplitude-embedding features (PennyLane trains such QNodes with backprop
 or parameter-shift; both give this gradient).  Autograd carries it on through the stacked rows, ``rot_matrices`` and
 whatever weight map the circuit applied.  Channel strengths get no gradient.
+
+Beyond 8 wires gradients are a second opt-in, ``set_max_grad_wires(10)`` or ``with max_grad_wires(10):`` -- the reverse
+sweep of the tile-fused engine (``qiddm_mixed_wide_backward``) keeps rho, its adjoint and one snapshot per group of
+channels per sample, several slabs where the forward keeps one.  With both limits raised a 9- or 10-wire launch is the
+same kind of autograd node: the forward is the tile-fused forward (bit-identical to the no-grad call), the backward the
+tile-fused reverse sweep.
 """
 from __future__ import annotations
 
@@ -37,7 +43,8 @@ wide_resident_samples = 0
 
 
 def set_max_wires(k: int) -> None:
-    """Largest ``default.mixed`` device that executes: 8 (default), 9 or 10.  Beyond 8 wires execution is forward only."""
+    """Largest ``default.mixed`` device that executes: 8 (default), 9 or 10.  Beyond 8 wires gradients need
+    ``set_max_grad_wires`` as well."""
     global _max_wires
     if not isinstance(k, int) or not 8 <= k <= 10:
         raise ValueError(f"the default.mixed wire limit must be 8, 9 or 10 (got {k!r})")
@@ -53,6 +60,30 @@ def max_wires(k: int):
         yield
     finally:
         set_max_wires(before)
+
+
+# wires up to which ``execute`` differentiates (8: the one-workgroup reverse sweep only; 9, 10: the tile-fused one too)
+_max_grad_wires = 8
+
+
+def set_max_grad_wires(k: int) -> None:
+    """Largest ``default.mixed`` device that is differentiable: 8 (default), 9 or 10.  Separate from ``set_max_wires``
+    (which must admit the device as well): the reverse sweep's working set is several slabs per sample."""
+    global _max_grad_wires
+    if not isinstance(k, int) or isinstance(k, bool) or not 8 <= k <= 10:
+        raise ValueError(f"the default.mixed gradient wire limit must be 8, 9 or 10 (got {k!r})")
+    _max_grad_wires = k
+
+
+@contextlib.contextmanager
+def max_grad_wires(k: int):
+    """``with mixed.max_grad_wires(10): ...`` -- ``set_max_grad_wires`` for the duration of a block."""
+    before = _max_grad_wires
+    set_max_grad_wires(k)
+    try:
+        yield
+    finally:
+        set_max_grad_wires(before)
 
 
 def rot_matrices(weights: torch.Tensor) -> torch.Tensor:
@@ -219,7 +250,7 @@ class _Launch:
             out.stride(0), ws.data_ptr(), ws.numel(), ctypes.c_void_p(self.stream())))
         return out
 
-    def backward(self, rows, gates, feats, grad_out, max_blocks=0):
+    def backward(self, rows, gates, feats, grad_out, max_blocks=0, wide=False):
         """-> (dL/d rows, dL/d gates summed over the batch, dL/d feats); None where there is no operand."""
         n, batch = self.n, self.batch
         grad_out = grad_out.to(torch.float64).contiguous()
@@ -228,6 +259,19 @@ class _Launch:
         g_gates = torch.empty(batch, gates.shape[0], 8, **f64) if gates is not None else None
         g_feats = torch.empty(batch, feats.shape[1], **f64) if feats is not None else None
         lib = _capi.lib()
+        if wide:
+            resident = min(batch, wide_resident_samples) if wide_resident_samples > 0 else batch
+            need = lib.qiddm_mixed_wide_backward_workspace_bytes(n, self.prec, resident, self.prog, len(self.prog))
+            if need < 0:
+                _capi.check(int(need))
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)  # handed back after the call, as the forward's
+            _capi.check(lib.qiddm_mixed_wide_backward(
+                n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0), self.n_rows,
+                _ptr(feats), 0 if feats is None else feats.stride(0), 0 if feats is None else feats.shape[1], 0.0,
+                self.pad_with, _ptr(gates), 0 if gates is None else gates.shape[0], self.measure, batch,
+                grad_out.data_ptr(), grad_out.shape[1], _ptr(g_rows), _ptr(g_gates), _ptr(g_feats),
+                ws.data_ptr(), ws.numel(), ctypes.c_void_p(self.stream())))
+            return g_rows, None if g_gates is None else g_gates.sum(dim=0), g_feats
         need = lib.qiddm_mixed_backward_workspace_bytes(n, self.prec, batch, self.prog, len(self.prog), max_blocks)
         if need < 0:
             _capi.check(int(need))
@@ -246,21 +290,22 @@ def _ptr(t):
 
 
 class _MixedFunction(torch.autograd.Function):
-    """``qiddm_mixed_forward`` as an autograd node; its backward is ``qiddm_mixed_backward``."""
+    """``qiddm_mixed_forward`` as an autograd node; its backward is ``qiddm_mixed_backward`` (``wide``: the tile-fused
+    pair ``qiddm_mixed_wide_forward`` / ``qiddm_mixed_wide_backward``)."""
 
     @staticmethod
-    def forward(ctx, launch, rows, gates, feats):
-        ctx.launch = launch
+    def forward(ctx, launch, rows, gates, feats, wide=False):
+        ctx.launch, ctx.wide = launch, wide
         ctx.save_for_backward(rows, gates, feats)
-        return launch.forward(rows, gates, feats)
+        return launch.forward(rows, gates, feats, wide=wide)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         rows, gates, feats = ctx.saved_tensors
-        g_rows, g_gates, g_feats = ctx.launch.backward(rows, gates, feats, grad_out, backward_max_blocks)
+        g_rows, g_gates, g_feats = ctx.launch.backward(rows, gates, feats, grad_out, backward_max_blocks, wide=ctx.wide)
         return (None, g_rows if ctx.needs_input_grad[1] else None, g_gates if ctx.needs_input_grad[2] else None,
-                g_feats if ctx.needs_input_grad[3] else None)
+                g_feats if ctx.needs_input_grad[3] else None, None)
 
 
 # grid cap of the backward launch (0: the library's default); tests lower it to force the sample loop
@@ -271,11 +316,17 @@ def execute(tape, ret, n, precision=None, _engine=None):
     """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)``
     (or the unbatched row), as ``default.mixed`` does.  Up to 8 wires: differentiable when grad mode is on and an input
     requires grad; otherwise a plain launch whose result has no ``grad_fn``.  9 and 10 wires (within the wire limit, see
-    ``set_max_wires``): forward only."""
+    ``set_max_wires``): forward only unless ``set_max_grad_wires`` admits them too."""
     from . import circuit as _c
     # the engine follows the number of wires; `_engine="wide"` (tests, A/B tools) forces the tile-fused one at 7, 8 wires
     wide = _engine == "wide" or 8 < n <= _max_wires
-    if wide and torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params):
+    if wide and n > _max_grad_wires and torch.is_grad_enabled() and \
+            any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params):
+        if _max_grad_wires > 8:
+            raise NotImplementedError(
+                f"default.mixed on {n} wires executes forward only: gradients stop at {_max_grad_wires} wires (the "
+                f"limit of set_max_grad_wires).  Raise it to {n}, sample under torch.no_grad(), or train on a pure-state "
+                "device.")
         raise NotImplementedError(
             f"default.mixed on {n} wires executes forward only: gradients stop at 8 wires (the tile-fused engine has no "
             "reverse sweep).  Sample under torch.no_grad(), or train on a pure-state device.")
@@ -292,10 +343,8 @@ def execute(tape, ret, n, precision=None, _engine=None):
     feats = low.features.to(**f64).contiguous() if low.features is not None else None
     if feats is not None and feats.shape[0] != batch:
         feats = feats.expand(batch, -1).contiguous()
-    if wide:
-        out = launch.forward(rows, gates, feats, wide=True)
-    elif torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (rows, gates, feats)):
-        out = _MixedFunction.apply(launch, rows, gates, feats)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (rows, gates, feats)):
+        out = _MixedFunction.apply(launch, rows, gates, feats, wide)
     else:
-        out = launch.forward(rows, gates, feats)
+        out = launch.forward(rows, gates, feats, wide=wide)
     return out if low.batched else out[0]

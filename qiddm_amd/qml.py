@@ -176,7 +176,7 @@ def device(name, wires=1, **kwargs):
     """``qml.device(name, wires=n)``.  Every pure-state device name the reference uses maps
     to the HIP statevector engine; ``default.mixed`` (the noise scripts create it,
     src/mnist_noise.py:223) maps to the density-matrix kernels (``qiddm_amd.mixed``: n <= 8 differentiable by a reverse sweep;
-    n = 9, 10 forward only, after ``mixed.set_max_wires``)."""
+    n = 9, 10 after ``mixed.set_max_wires``, differentiable after ``mixed.set_max_grad_wires``)."""
     return Device(name, wires, **kwargs)
 
 
