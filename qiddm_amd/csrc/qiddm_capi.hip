@@ -108,8 +108,19 @@ namespace {
 
 using qiddm_capi::check_circuit;
 using qiddm_capi::fail;
+using qiddm_capi::for_dtype;
+using qiddm_capi::for_qubits;
 using qiddm_capi::g_err;
 using qiddm_capi::kMaxLds;
+using qiddm_capi::launched;
+
+constexpr int kFused = QIDDM_MAX_QUBITS_FUSED;
+
+// Rot gates of the whole circuit, and of one QNode round
+int64_t rot_gates(const qiddm_circuit_t* c) { return (int64_t)c->n_rounds * c->n_blocks * c->sel_layers * c->n_qubits; }
+int64_t round_rot_gates(const qiddm_circuit_t* c) { return (int64_t)c->n_blocks * c->sel_layers * c->n_qubits; }
+int64_t rot_gates(const qiddm::KScalars& p, int n) { return (int64_t)p.n_rounds * p.n_blocks * p.sel_layers * n; }
+int64_t round_rot_gates(const qiddm::KScalars& p, int n) { return (int64_t)p.n_blocks * p.sel_layers * n; }
 
 struct Ptrs {
   const void* inputs = nullptr;
@@ -120,7 +131,7 @@ struct Ptrs {
 };
 
 template <typename T, int N, bool SHIFT>
-int launch(const Ptrs& ptr, const qiddm::KScalars& p, int64_t n_replicas, hipStream_t stream) {
+int launch_circuit(const Ptrs& ptr, const qiddm::KScalars& p, int64_t n_replicas, hipStream_t stream) {
   using L = qiddm::Layout<N>;
   using S = qiddm::Smem<T, N>;
   const int64_t groups = (p.batch + L::SPW - 1) / L::SPW;
@@ -131,7 +142,7 @@ int launch(const Ptrs& ptr, const qiddm::KScalars& p, int64_t n_replicas, hipStr
   const int64_t cap = SHIFT ? 1024 : 4096;
   if (bx > cap) bx = cap;
   dim3 grid((unsigned)bx, SHIFT ? (unsigned)n_replicas : 1u, 1u);
-  const int64_t n_rot = (int64_t)p.n_rounds * p.n_blocks * p.sel_layers * N;
+  const int64_t n_rot = rot_gates(p, N);
   const size_t smem = S::bytes(n_rot, p.imprimitive == QIDDM_IMP_CNOT, waves);
   if (smem > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED,
@@ -149,79 +160,35 @@ int launch(const Ptrs& ptr, const qiddm::KScalars& p, int64_t n_replicas, hipStr
     // batch (B = 1024: 64.9 vs 69.5 us; tools/ab_lean_threshold.py, gpurun_out/ab_lean_*.log).  QIDDM_LEAN_ABOVE: A/B.
     static const int64_t lean_above_env = std::getenv("QIDDM_LEAN_ABOVE") ? std::atoll(std::getenv("QIDDM_LEAN_ABOVE")) : -1;
     const int64_t lean_above = lean_above_env >= 0 ? lean_above_env : (N == 10 ? 0 : 1024);
-    if (p.fold && p.encoding != QIDDM_ENC_AMPLITUDE && !all_paths && groups > lean_above) {
-      auto kf = qiddm::circuit_folded_kernel<T, N>;
-      static qiddm_capi::DeviceFlags big_lds_folded;
-      if (smem > 48 * 1024 && !big_lds_folded.get()) {
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kf),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-        if (ea != hipSuccess)
-          return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-        big_lds_folded.set();
-      }
-      hipLaunchKernelGGL(kf, grid, dim3(waves * qiddm::kWave), smem, stream, static_cast<const T*>(ptr.inputs),
-                         static_cast<const T*>(ptr.table), static_cast<T*>(ptr.out), p);
-      const hipError_t ef = hipGetLastError();
-      if (ef != hipSuccess)
-        return fail(QIDDM_ERR_LAUNCH, "circuit_folded_kernel<n=%d> launch failed: %s", N, hipGetErrorString(ef));
-      return QIDDM_OK;
-    }
+    if (p.fold && p.encoding != QIDDM_ENC_AMPLITUDE && !all_paths && groups > lean_above)
+      return qiddm_capi::launch<qiddm::circuit_folded_kernel<T, N>>(
+          kMaxLds, grid, dim3(waves * qiddm::kWave), smem, stream, "circuit_folded_kernel",
+          static_cast<const T*>(ptr.inputs), static_cast<const T*>(ptr.table), static_cast<T*>(ptr.out), p);
   }
-  auto kern = qiddm::circuit_kernel<T, N, SHIFT>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;  // benign race: the attribute call is idempotent
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess)
-      return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(waves * qiddm::kWave), smem, stream, static_cast<const T*>(ptr.inputs),
-                     static_cast<const T*>(ptr.table), static_cast<T*>(ptr.out),
-                     static_cast<const T*>(ptr.gout), static_cast<T*>(ptr.dots), p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "circuit_kernel<n=%d> launch failed: %s", N, hipGetErrorString(e));
-  return QIDDM_OK;
+  return qiddm_capi::launch<qiddm::circuit_kernel<T, N, SHIFT>>(
+      kMaxLds, grid, dim3(waves * qiddm::kWave), smem, stream, "circuit_kernel", static_cast<const T*>(ptr.inputs),
+      static_cast<const T*>(ptr.table), static_cast<T*>(ptr.out), static_cast<const T*>(ptr.gout),
+      static_cast<T*>(ptr.dots), p);
 }
 
-template <typename T, bool SHIFT>
-int dispatch_n(int n, const Ptrs& ptr, const qiddm::KScalars& p, int64_t n_replicas, hipStream_t stream) {
-  switch (n) {
-    case 1: return launch<T, 1, SHIFT>(ptr, p, n_replicas, stream);
-    case 2: return launch<T, 2, SHIFT>(ptr, p, n_replicas, stream);
-    case 3: return launch<T, 3, SHIFT>(ptr, p, n_replicas, stream);
-    case 4: return launch<T, 4, SHIFT>(ptr, p, n_replicas, stream);
-    case 5: return launch<T, 5, SHIFT>(ptr, p, n_replicas, stream);
-    case 6: return launch<T, 6, SHIFT>(ptr, p, n_replicas, stream);
-    case 7: return launch<T, 7, SHIFT>(ptr, p, n_replicas, stream);
-    case 8: return launch<T, 8, SHIFT>(ptr, p, n_replicas, stream);
-    case 9: return launch<T, 9, SHIFT>(ptr, p, n_replicas, stream);
-    case 10: return launch<T, 10, SHIFT>(ptr, p, n_replicas, stream);
-    default: return fail(QIDDM_ERR_UNSUPPORTED, "n_qubits=%d not instantiated", n);
-  }
+// the register-resident circuit of the descriptor's width and dtype (n <= 10)
+template <bool SHIFT>
+int dispatch_circuit(const qiddm_circuit_t* c, const Ptrs& ptr, const qiddm::KScalars& p, int64_t n_replicas,
+                     hipStream_t stream) {
+  return for_dtype(c->dtype, [&](auto t) {
+    return for_qubits<1, kFused>(c->n_qubits, "fused circuit", [&](auto N) {
+      return launch_circuit<decltype(t), N(), SHIFT>(ptr, p, n_replicas, stream);
+    });
+  });
 }
 
 template <typename T, int N, bool LDSW, int WPB>
 int launch_dense_impl(const double* x, const double* wd, const double* bd, const double* angles,
                       const double* wu, const double* bu, double* y, const qiddm::DenseScalars& d,
                       const qiddm::KScalars& p, size_t smem, unsigned blocks, hipStream_t stream) {
-  constexpr int waves = WPB;
-  auto kern = qiddm::dense_forward_kernel<T, N, LDSW, WPB>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess)
-      return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(waves * qiddm::kWave), smem, stream, x, wd, bd, angles, wu,
-                     bu, y, d, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "dense_forward_kernel<n=%d> launch failed: %s", N, hipGetErrorString(e));
-  return QIDDM_OK;
+  return qiddm_capi::launch<qiddm::dense_forward_kernel<T, N, LDSW, WPB>>(
+      kMaxLds, dim3(blocks), dim3(WPB * qiddm::kWave), smem, stream, "dense_forward_kernel", x, wd, bd, angles, wu, bu,
+      y, d, p);
 }
 
 template <typename T, int N>
@@ -239,7 +206,7 @@ int launch_dense(const double* x, const double* wd, const double* bd, const doub
   const int waves = groups <= 1024 ? 1 : ((kCanUse8 && groups > 2048) ? 8 : 4);
   int64_t bx = (groups + waves - 1) / waves;
   if (bx > 4096) bx = 4096;
-  const int64_t n_rot = (int64_t)p.n_rounds * p.n_blocks * p.sel_layers * N;
+  const int64_t n_rot = rot_gates(p, N);
   const size_t base = S::bytes(n_rot, p.imprimitive == QIDDM_IMP_CNOT, waves);
   if (base > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "circuit with %lld Rot gates needs %zu B of LDS (limit %zu)",
@@ -261,25 +228,6 @@ int launch_dense(const double* x, const double* wd, const double* bd, const doub
               : launch_dense_impl<T, N, false, 4>(x, wd, bd, angles, wu, bu, y, d, p, smem, blocks, stream);
 }
 
-template <typename T>
-int dispatch_dense(int n, const double* x, const double* wd, const double* bd, const double* angles,
-                   const double* wu, const double* bu, double* y, const qiddm::DenseScalars& d,
-                   const qiddm::KScalars& p, hipStream_t st) {
-  switch (n) {
-    case 1: return launch_dense<T, 1>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 2: return launch_dense<T, 2>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 3: return launch_dense<T, 3>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 4: return launch_dense<T, 4>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 5: return launch_dense<T, 5>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 6: return launch_dense<T, 6>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 7: return launch_dense<T, 7>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 8: return launch_dense<T, 8>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 9: return launch_dense<T, 9>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    case 10: return launch_dense<T, 10>(x, wd, bd, angles, wu, bu, y, d, p, st);
-    default: return fail(QIDDM_ERR_UNSUPPORTED, "n_qubits=%d not instantiated", n);
-  }
-}
-
 template <typename T, int N>
 int launch_qconv(const double* x, const double* angles, double* y, const qiddm::ConvScalars& cv,
                  const qiddm::KScalars& p, hipStream_t stream) {
@@ -295,54 +243,14 @@ int launch_qconv(const double* x, const double* angles, double* y, const qiddm::
   if (smem > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "circuit with %lld Rot gates needs %zu B of LDS (limit %zu)",
                 (long long)n_rot, smem, kMaxLds);
-  auto kern = qiddm::qconv_forward_kernel<T, N>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess)
-      return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)bx), dim3(waves * qiddm::kWave), smem, stream, x, angles, y, cv, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "qconv_forward_kernel<n=%d> launch failed: %s", N, hipGetErrorString(e));
-  return QIDDM_OK;
-}
-
-template <typename T>
-int dispatch_qconv(int n, const double* x, const double* angles, double* y, const qiddm::ConvScalars& cv,
-                   const qiddm::KScalars& p, hipStream_t st) {
-  switch (n) {
-    case 1: return launch_qconv<T, 1>(x, angles, y, cv, p, st);
-    case 2: return launch_qconv<T, 2>(x, angles, y, cv, p, st);
-    case 3: return launch_qconv<T, 3>(x, angles, y, cv, p, st);
-    case 4: return launch_qconv<T, 4>(x, angles, y, cv, p, st);
-    case 5: return launch_qconv<T, 5>(x, angles, y, cv, p, st);
-    case 6: return launch_qconv<T, 6>(x, angles, y, cv, p, st);
-    case 7: return launch_qconv<T, 7>(x, angles, y, cv, p, st);
-    case 8: return launch_qconv<T, 8>(x, angles, y, cv, p, st);
-    case 9: return launch_qconv<T, 9>(x, angles, y, cv, p, st);
-    case 10: return launch_qconv<T, 10>(x, angles, y, cv, p, st);
-    default: return fail(QIDDM_ERR_UNSUPPORTED, "fused QConv2d needs n_qubits <= 10 (got %d)", n);
-  }
+  return qiddm_capi::launch<qiddm::qconv_forward_kernel<T, N>>(kMaxLds, dim3((unsigned)bx), dim3(waves * qiddm::kWave),
+                                                               smem, stream, "qconv_forward_kernel", x, angles, y, cv, p);
 }
 
 // ---- quad layout (4 waves per sample) dense sampler ---------------------------------------------------
 template <typename T>
 size_t quad_lds_bytes(int n, int64_t n_rot) {
-  switch (n) {
-    case 2: return qiddm::QuadSmem<T, 2>::bytes(n_rot);
-    case 3: return qiddm::QuadSmem<T, 3>::bytes(n_rot);
-    case 4: return qiddm::QuadSmem<T, 4>::bytes(n_rot);
-    case 5: return qiddm::QuadSmem<T, 5>::bytes(n_rot);
-    case 6: return qiddm::QuadSmem<T, 6>::bytes(n_rot);
-    case 7: return qiddm::QuadSmem<T, 7>::bytes(n_rot);
-    case 8: return qiddm::QuadSmem<T, 8>::bytes(n_rot);
-    case 9: return qiddm::QuadSmem<T, 9>::bytes(n_rot);
-    default: return qiddm::QuadSmem<T, 10>::bytes(n_rot);
-  }
+  return for_qubits<2, kFused>(n, "fused sampler", [&](auto N) { return qiddm::QuadSmem<T, N()>::bytes(n_rot); });
 }
 
 bool quad_supported(const qiddm_circuit_t* c, int64_t in_features, int64_t out_features) {
@@ -350,10 +258,7 @@ bool quad_supported(const qiddm_circuit_t* c, int64_t in_features, int64_t out_f
         c->encoding == QIDDM_ENC_RZ && c->measure == QIDDM_MEAS_EXPZ && in_features <= 2048 && out_features <= 2048))
     return false;
   // its per-layer phase tables must fit in LDS (deep float64 circuits at n = 10 do not)
-  const int64_t n_rot = (int64_t)c->n_rounds * c->n_blocks * c->sel_layers * c->n_qubits;
-  const size_t lds = c->dtype == QIDDM_F32 ? quad_lds_bytes<float>(c->n_qubits, n_rot)
-                                           : quad_lds_bytes<double>(c->n_qubits, n_rot);
-  return lds <= kMaxLds;
+  return for_dtype(c->dtype, [&](auto t) { return quad_lds_bytes<decltype(t)>(c->n_qubits, rot_gates(c)); }) <= kMaxLds;
 }
 
 template <typename T, int N>
@@ -361,28 +266,17 @@ int launch_quad(const double* x, const double* wd, const double* bd, const doubl
                 const double* bu, double* y, const void* tables, const qiddm::QuadScalars& d,
                 const qiddm::KScalars& p, hipStream_t stream) {
   if (p.batch == 0 || d.n_steps == 0) return QIDDM_OK;
-  const int64_t n_rot = (int64_t)p.n_rounds * p.n_blocks * p.sel_layers * N;
+  const int64_t n_rot = rot_gates(p, N);
   const size_t smem = qiddm::QuadSmem<T, N>::bytes(n_rot);
   if (smem > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "circuit with %lld Rot gates needs %zu B of LDS (limit %zu)",
                 (long long)n_rot, smem, kMaxLds);
   const bool small = d.in_features <= 1024 && d.out_features <= 1024;
   auto kern = small ? qiddm::dense_quad_kernel<T, N, 4> : qiddm::dense_quad_kernel<T, N, 8>;
-  static qiddm_capi::DeviceFlags big_lds_enabled[2];
-  if (smem > 48 * 1024 && !big_lds_enabled[small].get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess)
-      return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled[small].set();
-  }
+  static qiddm_capi::DeviceFlags big_lds_enabled[2];   // the kernel is chosen at run time: one per choice
   const unsigned blocks = (unsigned)(p.batch < 2048 ? p.batch : 2048);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), smem, stream, x, wd, bd, angles, wu, bu, y,
-                     static_cast<const T*>(tables), d, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "dense_quad_kernel<n=%d> launch failed: %s", N, hipGetErrorString(e));
-  return QIDDM_OK;
+  return qiddm_capi::launch_with(kern, big_lds_enabled[small], kMaxLds, dim3(blocks), dim3(256), smem, stream,
+                                 "dense_quad_kernel", x, wd, bd, angles, wu, bu, y, static_cast<const T*>(tables), d, p);
 }
 
 template <typename T, int N>
@@ -392,44 +286,14 @@ size_t quad_tables_bytes_n(int64_t n_rot) {
 }
 template <typename T>
 size_t quad_tables_bytes(int n, int64_t n_rot) {
-  switch (n) {
-    case 2: return quad_tables_bytes_n<T, 2>(n_rot);
-    case 3: return quad_tables_bytes_n<T, 3>(n_rot);
-    case 4: return quad_tables_bytes_n<T, 4>(n_rot);
-    case 5: return quad_tables_bytes_n<T, 5>(n_rot);
-    case 6: return quad_tables_bytes_n<T, 6>(n_rot);
-    case 7: return quad_tables_bytes_n<T, 7>(n_rot);
-    case 8: return quad_tables_bytes_n<T, 8>(n_rot);
-    case 9: return quad_tables_bytes_n<T, 9>(n_rot);
-    default: return quad_tables_bytes_n<T, 10>(n_rot);
-  }
+  return for_qubits<2, kFused>(n, "fused sampler", [&](auto N) { return quad_tables_bytes_n<T, N()>(n_rot); });
 }
 template <typename T, int N>
 int launch_quad_tables(const double* angles, void* tables, const qiddm::KScalars& p, int64_t n_rot, hipStream_t st) {
   const size_t smem = (size_t)n_rot * sizeof(double);
   if (smem > 48 * 1024) return fail(QIDDM_ERR_UNSUPPORTED, "too many Rot gates (%lld) for the table builder", (long long)n_rot);
   hipLaunchKernelGGL((qiddm::quad_tables_kernel<T, N>), dim3(1), dim3(256), smem, st, angles, static_cast<T*>(tables), p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "quad_tables_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
-}
-
-template <typename T>
-int dispatch_quad(int n, const double* x, const double* wd, const double* bd, const double* angles,
-                  const double* wu, const double* bu, double* y, const void* tables, const qiddm::QuadScalars& d,
-                  const qiddm::KScalars& p, hipStream_t st) {
-  switch (n) {
-    case 2: return launch_quad<T, 2>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    case 3: return launch_quad<T, 3>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    case 4: return launch_quad<T, 4>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    case 5: return launch_quad<T, 5>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    case 6: return launch_quad<T, 6>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    case 7: return launch_quad<T, 7>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    case 8: return launch_quad<T, 8>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    case 9: return launch_quad<T, 9>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    case 10: return launch_quad<T, 10>(x, wd, bd, angles, wu, bu, y, tables, d, p, st);
-    default: return fail(QIDDM_ERR_UNSUPPORTED, "quad layout needs 8 <= n <= 10 (got %d)", n);
-  }
+  return launched("quad_tables_kernel");
 }
 
 // ---- adjoint backward (n <= 10) -------------------------------------------------------------------------
@@ -442,14 +306,7 @@ int64_t adjoint_blocks(int64_t batch) {
   return bx < 1 ? 1 : bx;
 }
 int64_t adjoint_blocks_n(int n, int64_t batch) {
-  switch (n) {
-    case 1: return adjoint_blocks<1>(batch);
-    case 2: return adjoint_blocks<2>(batch);
-    case 3: return adjoint_blocks<3>(batch);
-    case 4: return adjoint_blocks<4>(batch);
-    case 5: return adjoint_blocks<5>(batch);
-    default: return adjoint_blocks<6>(batch);  // SPW == 1 from n = 6 on
-  }
+  return for_qubits<1, kFused>(n, "adjoint backward", [&](auto N) { return adjoint_blocks<N()>(batch); });
 }
 
 struct ConvPtrs {  // quantum-convolution backward: image, dL/dy and geometry (unused otherwise)
@@ -463,48 +320,27 @@ int launch_adjoint(const Ptrs& ptr, T* k_partials, T* grad_inputs, const qiddm::
                    const qiddm::AdjointScalars& ad, const ConvPtrs& conv, hipStream_t stream) {
   using S = qiddm::Smem<T, N>;
   const int waves = 4;
-  const int64_t n_rot = (int64_t)p.n_blocks * p.sel_layers * N;
+  const int64_t n_rot = round_rot_gates(p, N);
   const size_t smem = S::bytes(n_rot, p.imprimitive == QIDDM_IMP_CNOT, waves) +
                       (size_t)n_rot * qiddm::kLdsGateReals * sizeof(T) + (size_t)waves * n_rot * 8 * sizeof(T);
   if (smem > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "circuit with %lld Rot gates needs %zu B of LDS for the adjoint pass",
                 (long long)n_rot, smem);
-  auto kern = qiddm::adjoint_kernel<T, N, CONV>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess)
-      return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)adjoint_blocks<N>(p.batch)), dim3(waves * qiddm::kWave), smem, stream,
-                     static_cast<const T*>(ptr.inputs), static_cast<const T*>(ptr.table),
-                     static_cast<const T*>(ptr.gout), k_partials, grad_inputs, p, ad, conv.img, conv.gy, conv.cv);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "adjoint_kernel<n=%d> launch failed: %s", N, hipGetErrorString(e));
-  return QIDDM_OK;
+  return qiddm_capi::launch<qiddm::adjoint_kernel<T, N, CONV>>(
+      kMaxLds, dim3((unsigned)adjoint_blocks<N>(p.batch)), dim3(waves * qiddm::kWave), smem, stream, "adjoint_kernel",
+      static_cast<const T*>(ptr.inputs), static_cast<const T*>(ptr.table), static_cast<const T*>(ptr.gout), k_partials,
+      grad_inputs, p, ad, conv.img, conv.gy, conv.cv);
 }
 
-template <typename T, bool CONV>
-int dispatch_adjoint(int n, const Ptrs& ptr, void* kp, void* gi, const qiddm::KScalars& p,
+template <bool CONV>
+int dispatch_adjoint(const qiddm_circuit_t* c, const Ptrs& ptr, void* kp, void* gi, const qiddm::KScalars& p,
                      const qiddm::AdjointScalars& ad, const ConvPtrs& conv, hipStream_t st) {
-  T* k = static_cast<T*>(kp);
-  T* g = static_cast<T*>(gi);
-  switch (n) {
-    case 1: return launch_adjoint<T, 1, CONV>(ptr, k, g, p, ad, conv, st);
-    case 2: return launch_adjoint<T, 2, CONV>(ptr, k, g, p, ad, conv, st);
-    case 3: return launch_adjoint<T, 3, CONV>(ptr, k, g, p, ad, conv, st);
-    case 4: return launch_adjoint<T, 4, CONV>(ptr, k, g, p, ad, conv, st);
-    case 5: return launch_adjoint<T, 5, CONV>(ptr, k, g, p, ad, conv, st);
-    case 6: return launch_adjoint<T, 6, CONV>(ptr, k, g, p, ad, conv, st);
-    case 7: return launch_adjoint<T, 7, CONV>(ptr, k, g, p, ad, conv, st);
-    case 8: return launch_adjoint<T, 8, CONV>(ptr, k, g, p, ad, conv, st);
-    case 9: return launch_adjoint<T, 9, CONV>(ptr, k, g, p, ad, conv, st);
-    case 10: return launch_adjoint<T, 10, CONV>(ptr, k, g, p, ad, conv, st);
-    default: return fail(QIDDM_ERR_UNSUPPORTED, "adjoint backward needs n_qubits <= 10 (got %d)", n);
-  }
+  return for_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    return for_qubits<1, kFused>(c->n_qubits, "adjoint backward", [&](auto N) {
+      return launch_adjoint<T, N(), CONV>(ptr, static_cast<T*>(kp), static_cast<T*>(gi), p, ad, conv, st);
+    });
+  });
 }
 
 // ---- n = 11..16: tiled kernel -----------------------------------------------------------------------
@@ -526,7 +362,7 @@ template <typename T, bool SHIFT>
 int launch_tiled(int n, const Ptrs& ptr, const qiddm::KScalars& p, int64_t n_replicas, void* ws,
                  hipStream_t stream) {
   if (p.batch == 0 || (SHIFT && n_replicas == 0)) return QIDDM_OK;
-  const int64_t n_rot = (int64_t)p.n_rounds * p.n_blocks * p.sel_layers * n;
+  const int64_t n_rot = rot_gates(p, n);
   const int64_t layers = (int64_t)p.n_blocks * p.sel_layers;
   if (n_rot + 2 * layers + p.n_blocks + 2 * n > qiddm::kTiledMaxOps ||
       2 * layers + 4 > qiddm::kTiledMaxPasses)
@@ -536,27 +372,14 @@ int launch_tiled(int n, const Ptrs& ptr, const qiddm::KScalars& p, int64_t n_rep
   if (smem > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "circuit with %lld Rot gates needs %zu B of LDS (limit %zu)",
                 (long long)n_rot, smem, kMaxLds);
-  auto kern = qiddm::tiled_circuit_kernel<T, SHIFT>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess)
-      return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
   dim3 grid((unsigned)tiled_blocks_x(p.batch, SHIFT ? n_replicas : 0), SHIFT ? (unsigned)n_replicas : 1u, 1u);
   qiddm::TiledScalars tp;
   tp.n = n;
   tp.pad_ = 0;
-  hipLaunchKernelGGL(kern, grid, dim3(qiddm::kTiledWaves * qiddm::kWave), smem, stream,
-                     static_cast<const T*>(ptr.inputs), static_cast<const T*>(ptr.table),
-                     static_cast<T*>(ptr.out), static_cast<const T*>(ptr.gout), static_cast<T*>(ptr.dots),
-                     static_cast<qiddm::V2<T>*>(ws), p, tp);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "tiled_circuit_kernel<n=%d> launch failed: %s", n, hipGetErrorString(e));
-  return QIDDM_OK;
+  return qiddm_capi::launch<qiddm::tiled_circuit_kernel<T, SHIFT>>(
+      kMaxLds, grid, dim3(qiddm::kTiledWaves * qiddm::kWave), smem, stream, "tiled_circuit_kernel",
+      static_cast<const T*>(ptr.inputs), static_cast<const T*>(ptr.table), static_cast<T*>(ptr.out),
+      static_cast<const T*>(ptr.gout), static_cast<T*>(ptr.dots), static_cast<qiddm::V2<T>*>(ws), p, tp);
 }
 
 int check_workspace(const qiddm_circuit_t* c, int64_t batch, int64_t n_replicas, const void* ws,
@@ -598,31 +421,57 @@ template <typename T>
 int launch_wide_adjoint(const qiddm_circuit_t* c, const void* inputs, const void* table, const void* gout,
                                void* k_partials, void* grad_inputs, void* ws, const qiddm::KScalars& p,
                                int64_t gin_ld, hipStream_t st, bool raw = false) {
-  const int64_t n_rot = (int64_t)c->n_blocks * c->sel_layers * c->n_qubits;
+  const int64_t n_rot = round_rot_gates(c);
   const size_t smem = ((size_t)n_rot * 8 + 64 + 48) * sizeof(T);
   if (smem > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "circuit with %lld Rot gates needs %zu B of LDS for the adjoint pass",
                 (long long)n_rot, smem);
-  auto kern = qiddm::wide_adjoint_kernel<T>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
   qiddm::WideAdjointScalars ad;
   ad.gin_ld = gin_ld;
   ad.n = c->n_qubits;
   ad.want_inputs = (!raw && grad_inputs != nullptr && c->encoding != QIDDM_ENC_NONE) ? 1 : 0;
   ad.raw = raw ? 1 : 0;
   ad.pad_ = 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)wide_adjoint_blocks(p.batch)), dim3(qiddm::kWideThreads), smem, st,
-                     static_cast<const T*>(inputs), static_cast<const T*>(table), static_cast<const T*>(gout),
-                     static_cast<T*>(k_partials), static_cast<T*>(grad_inputs), static_cast<qiddm::V2<T>*>(ws), p, ad);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "wide_adjoint_kernel launch failed: %s", hipGetErrorString(e));
+  return qiddm_capi::launch<qiddm::wide_adjoint_kernel<T>>(
+      kMaxLds, dim3((unsigned)wide_adjoint_blocks(p.batch)), dim3(qiddm::kWideThreads), smem, st, "wide_adjoint_kernel",
+      static_cast<const T*>(inputs), static_cast<const T*>(table), static_cast<const T*>(gout),
+      static_cast<T*>(k_partials), static_cast<T*>(grad_inputs), static_cast<qiddm::V2<T>*>(ws), p, ad);
+}
+
+// the encodings other than "none" read `inputs`, n_features values per row
+int check_inputs(const qiddm_circuit_t* c, const void* inputs, int64_t in_ld) {
+  if (c->encoding == QIDDM_ENC_NONE) return QIDDM_OK;
+  if (!inputs) return fail(QIDDM_ERR_INVALID, "inputs is NULL but the encoding reads them");
+  if (in_ld < c->n_features)
+    return fail(QIDDM_ERR_INVALID, "in_ld=%lld < n_features=%d", (long long)in_ld, c->n_features);
   return QIDDM_OK;
+}
+
+// what lies behind the gate variants in the circuit's gate table, `extra_reals` further elements in
+const void* table_tail(const qiddm_circuit_t* c, const void* gate_table, int64_t extra_reals) {
+  const size_t esz = c->dtype == QIDDM_F32 ? 4 : 8;
+  return static_cast<const char*>(gate_table) +
+         ((size_t)rot_gates(c) * qiddm::kVariants * qiddm::kGateReals + (size_t)extra_reals) * esz;
+}
+
+// geometry of a stride-1 quantum convolution; the read-out is scaled by half the state dimension `d`
+qiddm::ConvScalars make_conv_scalars(int64_t in_channels, int64_t height, int64_t width, int64_t kh, int64_t kw,
+                                     int64_t pad_h, int64_t pad_w, int64_t ho, int64_t wo, int64_t out_channels,
+                                     int64_t d) {
+  qiddm::ConvScalars cv;
+  std::memset(&cv, 0, sizeof(cv));
+  cv.C = (int32_t)in_channels;
+  cv.H = (int32_t)height;
+  cv.W = (int32_t)width;
+  cv.kh = (int32_t)kh;
+  cv.kw = (int32_t)kw;
+  cv.ph = (int32_t)pad_h;
+  cv.pw = (int32_t)pad_w;
+  cv.Ho = (int32_t)ho;
+  cv.Wo = (int32_t)wo;
+  cv.C_out = (int32_t)out_channels;
+  cv.post_scale = 0.5 * (double)d;
+  return cv;
 }
 
 }  // namespace
@@ -643,7 +492,7 @@ const char* qiddm_last_error(void) { return g_err; }
 
 int64_t qiddm_num_rot_gates(const qiddm_circuit_t* c) {
   if (check_circuit(c) != QIDDM_OK) return -1;
-  return (int64_t)c->n_rounds * c->n_blocks * c->sel_layers * c->n_qubits;
+  return rot_gates(c);
 }
 
 int64_t qiddm_gate_count(const qiddm_circuit_t* c) {
@@ -687,22 +536,18 @@ int qiddm_prepare_gates(const qiddm_circuit_t* c, const double* angles, void* ga
   int rc = check_circuit(c);
   if (rc != QIDDM_OK) return rc;
   if (!angles || !gate_table) return fail(QIDDM_ERR_INVALID, "angles/gate_table is NULL");
-  const int64_t n_rot = (int64_t)c->n_rounds * c->n_blocks * c->sel_layers * c->n_qubits;
+  const int64_t n_rot = rot_gates(c);
   const int64_t fe = fold_entries(c, n_rot);
   const int64_t total = n_rot * qiddm::kVariants + fe;
   const unsigned blocks = (unsigned)((total + 255) / 256);
   const int lpr = c->n_blocks * c->sel_layers;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (c->dtype == QIDDM_F32)
-    hipLaunchKernelGGL(qiddm::prepare_gates_kernel<float>, dim3(blocks), dim3(256), 0, st, angles,
-                       static_cast<float*>(gate_table), n_rot, c->n_qubits, lpr, fe);
-  else
-    hipLaunchKernelGGL(qiddm::prepare_gates_kernel<double>, dim3(blocks), dim3(256), 0, st, angles,
-                       static_cast<double*>(gate_table), n_rot, c->n_qubits, lpr, fe);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "prepare_gates launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return for_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(qiddm::prepare_gates_kernel<T>, dim3(blocks), dim3(256), 0, st, angles,
+                       static_cast<T*>(gate_table), n_rot, c->n_qubits, lpr, fe);
+    return launched("prepare_gates");
+  });
 }
 
 int qiddm_forward_post(const qiddm_circuit_t* c, const void* inputs, int64_t batch, int64_t in_ld,
@@ -718,11 +563,8 @@ int qiddm_forward_post(const qiddm_circuit_t* c, const void* inputs, int64_t bat
   if (out_ld < post_cols) return fail(QIDDM_ERR_INVALID, "out_ld=%lld < post_cols=%d", (long long)out_ld, post_cols);
   if (batch == 0) return QIDDM_OK;
   if (!gate_table || !out) return fail(QIDDM_ERR_INVALID, "gate_table/out is NULL");
-  if (c->encoding != QIDDM_ENC_NONE) {
-    if (!inputs) return fail(QIDDM_ERR_INVALID, "inputs is NULL but the encoding reads them");
-    if (in_ld < c->n_features)
-      return fail(QIDDM_ERR_INVALID, "in_ld=%lld < n_features=%d", (long long)in_ld, c->n_features);
-  }
+  rc = check_inputs(c, inputs, in_ld);
+  if (rc != QIDDM_OK) return rc;
   qiddm::KScalars p = make_params(c);
   Ptrs ptr;
   ptr.inputs = inputs;
@@ -734,8 +576,7 @@ int qiddm_forward_post(const qiddm_circuit_t* c, const void* inputs, int64_t bat
   p.post_cols = post_cols;
   p.post_scale = post_scale;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return c->dtype == QIDDM_F32 ? dispatch_n<float, false>(c->n_qubits, ptr, p, 0, st)
-                               : dispatch_n<double, false>(c->n_qubits, ptr, p, 0, st);
+  return dispatch_circuit<false>(c, ptr, p, 0, st);
 }
 
 int qiddm_forward(const qiddm_circuit_t* c, const void* inputs, int64_t batch, int64_t in_ld,
@@ -746,11 +587,8 @@ int qiddm_forward(const qiddm_circuit_t* c, const void* inputs, int64_t batch, i
   if (batch < 0) return fail(QIDDM_ERR_INVALID, "batch=%lld < 0", (long long)batch);
   if (batch == 0) return QIDDM_OK;
   if (!gate_table || !out) return fail(QIDDM_ERR_INVALID, "gate_table/out is NULL");
-  if (c->encoding != QIDDM_ENC_NONE) {
-    if (!inputs) return fail(QIDDM_ERR_INVALID, "inputs is NULL but the encoding reads them");
-    if (in_ld < c->n_features)
-      return fail(QIDDM_ERR_INVALID, "in_ld=%lld < n_features=%d", (long long)in_ld, c->n_features);
-  }
+  rc = check_inputs(c, inputs, in_ld);
+  if (rc != QIDDM_OK) return rc;
   if (out_ld < out_cols(c))
     return fail(QIDDM_ERR_INVALID, "out_ld=%lld < %lld output columns", (long long)out_ld,
                 (long long)out_cols(c));
@@ -767,17 +605,14 @@ int qiddm_forward(const qiddm_circuit_t* c, const void* inputs, int64_t batch, i
     rc = check_workspace(c, batch, 0, workspace, workspace_bytes);
     if (rc != QIDDM_OK) return rc;
     static const bool force_tiled = std::getenv("QIDDM_WIDE_TILED") != nullptr;   // kernel experiments: A/B
-    if (qiddm_capi::wide_cz_eligible(c) && !force_tiled) {
-      const int64_t n_rot = (int64_t)c->n_rounds * c->n_blocks * c->sel_layers * c->n_qubits;
-      const size_t esz = c->dtype == QIDDM_F32 ? 4 : 8;
-      const char* tail = static_cast<const char*>(gate_table) + (size_t)n_rot * qiddm::kVariants * qiddm::kGateReals * esz;
-      return qiddm_capi::launch_wide_cz(c->dtype, c->n_qubits, inputs, tail, out, workspace, p, 2 * tiled_blocks_x(batch, 0), stream);
-    }
-    return c->dtype == QIDDM_F32 ? launch_tiled<float, false>(c->n_qubits, ptr, p, 0, workspace, st)
-                                 : launch_tiled<double, false>(c->n_qubits, ptr, p, 0, workspace, st);
+    if (qiddm_capi::wide_cz_eligible(c) && !force_tiled)
+      return qiddm_capi::launch_wide_cz(c->dtype, c->n_qubits, inputs, table_tail(c, gate_table, 0), out,
+                                        workspace, p, 2 * tiled_blocks_x(batch, 0), stream);
+    return for_dtype(c->dtype, [&](auto t) {
+      return launch_tiled<decltype(t), false>(c->n_qubits, ptr, p, 0, workspace, st);
+    });
   }
-  return c->dtype == QIDDM_F32 ? dispatch_n<float, false>(c->n_qubits, ptr, p, 0, st)
-                               : dispatch_n<double, false>(c->n_qubits, ptr, p, 0, st);
+  return dispatch_circuit<false>(c, ptr, p, 0, st);
 }
 
 int qiddm_forward_shifted(const qiddm_circuit_t* c, const void* inputs, int64_t batch, int64_t in_ld,
@@ -800,11 +635,8 @@ int qiddm_forward_shifted(const qiddm_circuit_t* c, const void* inputs, int64_t 
   if (batch == 0 || n_replicas == 0) return QIDDM_OK;
   if (!gate_table || !grad_out || !dots)
     return fail(QIDDM_ERR_INVALID, "gate_table/grad_out/dots is NULL");
-  if (c->encoding != QIDDM_ENC_NONE) {
-    if (!inputs) return fail(QIDDM_ERR_INVALID, "inputs is NULL but the encoding reads them");
-    if (in_ld < c->n_features)
-      return fail(QIDDM_ERR_INVALID, "in_ld=%lld < n_features=%d", (long long)in_ld, c->n_features);
-  }
+  rc = check_inputs(c, inputs, in_ld);
+  if (rc != QIDDM_OK) return rc;
   if (g_ld < out_cols(c))
     return fail(QIDDM_ERR_INVALID, "g_ld=%lld < %lld output columns", (long long)g_ld,
                 (long long)out_cols(c));
@@ -822,12 +654,11 @@ int qiddm_forward_shifted(const qiddm_circuit_t* c, const void* inputs, int64_t 
   if (c->n_qubits > QIDDM_MAX_QUBITS_FUSED) {
     rc = check_workspace(c, batch, n_replicas, workspace, workspace_bytes);
     if (rc != QIDDM_OK) return rc;
-    return c->dtype == QIDDM_F32
-               ? launch_tiled<float, true>(c->n_qubits, ptr, p, n_replicas, workspace, st)
-               : launch_tiled<double, true>(c->n_qubits, ptr, p, n_replicas, workspace, st);
+    return for_dtype(c->dtype, [&](auto t) {
+      return launch_tiled<decltype(t), true>(c->n_qubits, ptr, p, n_replicas, workspace, st);
+    });
   }
-  return c->dtype == QIDDM_F32 ? dispatch_n<float, true>(c->n_qubits, ptr, p, n_replicas, st)
-                               : dispatch_n<double, true>(c->n_qubits, ptr, p, n_replicas, st);
+  return dispatch_circuit<true>(c, ptr, p, n_replicas, st);
 }
 
 int64_t qiddm_adjoint_partials(const qiddm_circuit_t* c, int64_t batch) {
@@ -867,15 +698,15 @@ int qiddm_backward_adjoint_wide(const qiddm_circuit_t* c, const void* inputs, in
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (batch > 0 && qiddm_capi::wide_cz_adjoint_eligible(c)) {
     // pass-structured reverse sweep; the slabs then hold per-layer angle-gradient sums (qiddm_adjoint_finalize knows)
-    const int64_t n_rot = (int64_t)c->n_blocks * c->sel_layers * c->n_qubits;
-    const size_t esz = c->dtype == QIDDM_F32 ? 4 : 8;
-    const char* tail = static_cast<const char*>(gate_table) + (size_t)n_rot * qiddm::kVariants * qiddm::kGateReals * esz;
-    return qiddm_capi::launch_wide_cz_adjoint(c->dtype, c->n_qubits, inputs, tail, grad_out, k_partials, n_rot * 8,
-                                              grad_inputs, gin_ld, workspace, p, wide_adjoint_blocks(batch), stream);
+    const int64_t n_rot = round_rot_gates(c);
+    return qiddm_capi::launch_wide_cz_adjoint(c->dtype, c->n_qubits, inputs, table_tail(c, gate_table, 0),
+                                              grad_out, k_partials, n_rot * 8, grad_inputs, gin_ld, workspace, p,
+                                              wide_adjoint_blocks(batch), stream);
   }
-  return c->dtype == QIDDM_F32
-             ? launch_wide_adjoint<float>(c, inputs, gate_table, grad_out, k_partials, grad_inputs, workspace, p, gin_ld, st)
-             : launch_wide_adjoint<double>(c, inputs, gate_table, grad_out, k_partials, grad_inputs, workspace, p, gin_ld, st);
+  return for_dtype(c->dtype, [&](auto t) {
+    return launch_wide_adjoint<decltype(t)>(c, inputs, gate_table, grad_out, k_partials, grad_inputs, workspace, p,
+                                            gin_ld, st);
+  });
 }
 
 int64_t qiddm_matrix_adjoint_partials(int64_t count) { return count < 0 ? -1 : wide_adjoint_blocks(count); }
@@ -938,11 +769,8 @@ int qiddm_backward_adjoint(const qiddm_circuit_t* c, const void* inputs, int64_t
                 "parameter-shift sweep", QIDDM_MAX_QUBITS_FUSED, c->n_qubits);
   if (batch < 0) return fail(QIDDM_ERR_INVALID, "batch < 0");
   if (!gate_table || !grad_out || !k_partials) return fail(QIDDM_ERR_INVALID, "gate_table/grad_out/k_partials is NULL");
-  if (c->encoding != QIDDM_ENC_NONE) {
-    if (!inputs) return fail(QIDDM_ERR_INVALID, "inputs is NULL but the encoding reads them");
-    if (in_ld < c->n_features)
-      return fail(QIDDM_ERR_INVALID, "in_ld=%lld < n_features=%d", (long long)in_ld, c->n_features);
-  }
+  rc = check_inputs(c, inputs, in_ld);
+  if (rc != QIDDM_OK) return rc;
   if (g_ld < out_cols(c)) return fail(QIDDM_ERR_INVALID, "g_ld smaller than the output width");
   const int64_t gin_cols = c->encoding == QIDDM_ENC_AMPLITUDE ? c->n_features : c->n_qubits;
   if (grad_inputs && gin_ld < gin_cols) return fail(QIDDM_ERR_INVALID, "gin_ld=%lld < %lld", (long long)gin_ld, (long long)gin_cols);
@@ -961,21 +789,17 @@ int qiddm_backward_adjoint(const qiddm_circuit_t* c, const void* inputs, int64_t
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (batch > 0 && qiddm_capi::cz10_adjoint_eligible(c)) {
     // register-resident folded reverse sweep; the slabs then hold per-layer angle-gradient sums (finalize knows)
-    const int64_t n_rot = (int64_t)c->n_blocks * c->sel_layers * c->n_qubits;
+    const int64_t n_rot = round_rot_gates(c);
     const int64_t layers = n_rot / c->n_qubits;
-    const size_t esz = c->dtype == QIDDM_F32 ? 4 : 8;
     const int64_t fold_reals = 2 * layers * (10 + 64 + 16);
-    const char* tail = static_cast<const char*>(gate_table) +
-                       ((size_t)n_rot * qiddm::kVariants * qiddm::kGateReals + (size_t)fold_reals) * esz;
-    return qiddm_capi::launch_cz10_adjoint(c->dtype, inputs, tail, grad_out, k_partials, n_rot * 8,
+    return qiddm_capi::launch_cz10_adjoint(c->dtype, inputs, table_tail(c, gate_table, fold_reals), grad_out,
+                                           k_partials, n_rot * 8,
                                            ad.want_inputs ? grad_inputs : nullptr, gin_ld, p, adjoint_blocks_n(10, batch),
                                            stream);
   }
   // batch == 0 still has to zero the (single) partial slab: launch with no samples
   const ConvPtrs none;
-  return c->dtype == QIDDM_F32
-             ? dispatch_adjoint<float, false>(c->n_qubits, ptr, k_partials, grad_inputs, p, ad, none, st)
-             : dispatch_adjoint<double, false>(c->n_qubits, ptr, k_partials, grad_inputs, p, ad, none, st);
+  return dispatch_adjoint<false>(c, ptr, k_partials, grad_inputs, p, ad, none, st);
 }
 
 int qiddm_qconv_backward(const qiddm_circuit_t* c, const double* x, int64_t batch, int64_t in_channels,
@@ -1014,18 +838,7 @@ int qiddm_qconv_backward(const qiddm_circuit_t* c, const double* x, int64_t batc
   ConvPtrs conv;
   conv.img = x;
   conv.gy = grad_y;
-  std::memset(&conv.cv, 0, sizeof(conv.cv));
-  conv.cv.C = (int32_t)in_channels;
-  conv.cv.H = (int32_t)height;
-  conv.cv.W = (int32_t)width;
-  conv.cv.kh = (int32_t)kh;
-  conv.cv.kw = (int32_t)kw;
-  conv.cv.ph = (int32_t)pad_h;
-  conv.cv.pw = (int32_t)pad_w;
-  conv.cv.Ho = (int32_t)ho;
-  conv.cv.Wo = (int32_t)wo;
-  conv.cv.C_out = (int32_t)out_channels;
-  conv.cv.post_scale = 0.5 * (double)d;
+  conv.cv = make_conv_scalars(in_channels, height, width, kh, kw, pad_h, pad_w, ho, wo, out_channels, d);
   qiddm::AdjointScalars ad;
   ad.gin_ld = c->n_features;
   ad.want_inputs = grad_x != nullptr ? 1 : 0;
@@ -1033,21 +846,16 @@ int qiddm_qconv_backward(const qiddm_circuit_t* c, const double* x, int64_t batc
   Ptrs ptr;
   ptr.table = gate_table;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = c->dtype == QIDDM_F32
-           ? dispatch_adjoint<float, true>(c->n_qubits, ptr, k_partials, grad_features, p, ad, conv, st)
-           : dispatch_adjoint<double, true>(c->n_qubits, ptr, k_partials, grad_features, p, ad, conv, st);
+  rc = dispatch_adjoint<true>(c, ptr, k_partials, grad_features, p, ad, conv, st);
   if (rc != QIDDM_OK || grad_x == nullptr || batch == 0) return rc;
   const int64_t total = batch * in_channels * height * width;
   const unsigned blocks = (unsigned)((total + 255) / 256);
-  if (c->dtype == QIDDM_F32)
-    hipLaunchKernelGGL(qiddm::qconv_fold_kernel<float>, dim3(blocks), dim3(256), 0, st,
-                       static_cast<const float*>(grad_features), grad_x, total, conv.cv);
-  else
-    hipLaunchKernelGGL(qiddm::qconv_fold_kernel<double>, dim3(blocks), dim3(256), 0, st,
-                       static_cast<const double*>(grad_features), grad_x, total, conv.cv);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_fold launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return for_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(qiddm::qconv_fold_kernel<T>, dim3(blocks), dim3(256), 0, st,
+                       static_cast<const T*>(grad_features), grad_x, total, conv.cv);
+    return launched("qconv_fold");
+  });
 }
 
 int qiddm_adjoint_finalize(const qiddm_circuit_t* c, const double* angles, const void* k_partials,
@@ -1056,33 +864,26 @@ int qiddm_adjoint_finalize(const qiddm_circuit_t* c, const double* angles, const
   if (rc != QIDDM_OK) return rc;
   if (!angles || !k_partials || !grad_angles) return fail(QIDDM_ERR_INVALID, "angles/k_partials/grad_angles is NULL");
   if (n_partials < 0) return fail(QIDDM_ERR_INVALID, "n_partials < 0");
-  const int64_t n_rot = (int64_t)c->n_rounds * c->n_blocks * c->sel_layers * c->n_qubits;
+  const int64_t n_rot = rot_gates(c);
   const unsigned blocks = (unsigned)n_rot;  // one wavefront per gate
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (finalize_reads_folded_slabs(c)) {
     // the slabs hold per-layer angle-gradient sums (folded reverse sweep), not K
     const int slots = c->n_qubits <= 8 ? 8 : 16;
-    if (c->dtype == QIDDM_F32)
-      hipLaunchKernelGGL(qiddm::adjoint_finalize_folded_kernel<float>, dim3(blocks), dim3(qiddm::kWave), 0, st,
-                         static_cast<const float*>(k_partials), n_partials, n_rot * 8, c->n_qubits,
+    return for_dtype(c->dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(qiddm::adjoint_finalize_folded_kernel<T>, dim3(blocks), dim3(qiddm::kWave), 0, st,
+                         static_cast<const T*>(k_partials), n_partials, n_rot * 8, c->n_qubits,
                          c->n_blocks * c->sel_layers, slots, n_rot, grad_angles);
-    else
-      hipLaunchKernelGGL(qiddm::adjoint_finalize_folded_kernel<double>, dim3(blocks), dim3(qiddm::kWave), 0, st,
-                         static_cast<const double*>(k_partials), n_partials, n_rot * 8, c->n_qubits,
-                         c->n_blocks * c->sel_layers, slots, n_rot, grad_angles);
-    const hipError_t ef = hipGetLastError();
-    if (ef != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "adjoint_finalize launch failed: %s", hipGetErrorString(ef));
-    return QIDDM_OK;
+      return launched("adjoint_finalize");
+    });
   }
-  if (c->dtype == QIDDM_F32)
-    hipLaunchKernelGGL(qiddm::adjoint_finalize_kernel<float>, dim3(blocks), dim3(qiddm::kWave), 0, st,
-                       static_cast<const float*>(k_partials), n_partials, n_rot, angles, grad_angles);
-  else
-    hipLaunchKernelGGL(qiddm::adjoint_finalize_kernel<double>, dim3(blocks), dim3(qiddm::kWave), 0, st,
-                       static_cast<const double*>(k_partials), n_partials, n_rot, angles, grad_angles);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "adjoint_finalize launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return for_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(qiddm::adjoint_finalize_kernel<T>, dim3(blocks), dim3(qiddm::kWave), 0, st,
+                       static_cast<const T*>(k_partials), n_partials, n_rot, angles, grad_angles);
+    return launched("adjoint_finalize");
+  });
 }
 
 int qiddm_dense_forward(const qiddm_circuit_t* c, const double* x, int64_t batch, int64_t x_ld,
@@ -1126,9 +927,11 @@ int qiddm_dense_forward(const qiddm_circuit_t* c, const double* x, int64_t batch
   d.noise_factor = noise_factor;
   d.stamps = qiddm_capi::stamp_buffer(8);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return c->dtype == QIDDM_F32
-             ? dispatch_dense<float>(c->n_qubits, x, w_down, b_down, angles, w_up, b_up, y, d, p, st)
-             : dispatch_dense<double>(c->n_qubits, x, w_down, b_down, angles, w_up, b_up, y, d, p, st);
+  return for_dtype(c->dtype, [&](auto t) {
+    return for_qubits<1, kFused>(c->n_qubits, "dense forward", [&](auto N) {
+      return launch_dense<decltype(t), N()>(x, w_down, b_down, angles, w_up, b_up, y, d, p, st);
+    });
+  });
 }
 
 int qiddm_qconv_forward(const qiddm_circuit_t* c, const double* x, int64_t batch, int64_t in_channels,
@@ -1157,22 +960,13 @@ int qiddm_qconv_forward(const qiddm_circuit_t* c, const double* x, int64_t batch
   if (!x || !angles || !y) return fail(QIDDM_ERR_INVALID, "x/angles/y is NULL");
   qiddm::KScalars p = make_params(c);
   p.batch = batch * ho * wo;  // one circuit per output pixel
-  qiddm::ConvScalars cv;
-  std::memset(&cv, 0, sizeof(cv));
-  cv.C = (int32_t)in_channels;
-  cv.H = (int32_t)height;
-  cv.W = (int32_t)width;
-  cv.kh = (int32_t)kh;
-  cv.kw = (int32_t)kw;
-  cv.ph = (int32_t)pad_h;
-  cv.pw = (int32_t)pad_w;
-  cv.Ho = (int32_t)ho;
-  cv.Wo = (int32_t)wo;
-  cv.C_out = (int32_t)out_channels;
-  cv.post_scale = 0.5 * (double)d;
+  const qiddm::ConvScalars cv = make_conv_scalars(in_channels, height, width, kh, kw, pad_h, pad_w, ho, wo, out_channels, d);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return c->dtype == QIDDM_F32 ? dispatch_qconv<float>(c->n_qubits, x, angles, y, cv, p, st)
-                               : dispatch_qconv<double>(c->n_qubits, x, angles, y, cv, p, st);
+  return for_dtype(c->dtype, [&](auto t) {
+    return for_qubits<1, kFused>(c->n_qubits, "fused QConv2d", [&](auto N) {
+      return launch_qconv<decltype(t), N()>(x, angles, y, cv, p, st);
+    });
+  });
 }
 
 int qiddm_dense_sample(const qiddm_circuit_t* c, const double* x, int64_t batch, int64_t x_ld,
@@ -1209,20 +1003,20 @@ int qiddm_dense_sample(const qiddm_circuit_t* c, const double* x, int64_t batch,
   d.noise_factor = noise_factor;
   d.stamps = qiddm_capi::stamp_buffer(8);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return c->dtype == QIDDM_F32
-             ? dispatch_quad<float>(c->n_qubits, x, w_down, b_down, angles, w_up, b_up, y, tables, d, p, st)
-             : dispatch_quad<double>(c->n_qubits, x, w_down, b_down, angles, w_up, b_up, y, tables, d, p, st);
+  return for_dtype(c->dtype, [&](auto t) {
+    return for_qubits<2, kFused>(c->n_qubits, "fused sampler", [&](auto N) {
+      return launch_quad<decltype(t), N()>(x, w_down, b_down, angles, w_up, b_up, y, tables, d, p, st);
+    });
+  });
 }
 
 int64_t qiddm_dense_sample_tables_bytes(const qiddm_circuit_t* c) {
   if (check_circuit(c) != QIDDM_OK) return -1;
   if (!quad_supported(c, 1, 1)) {
-    fail(QIDDM_ERR_UNSUPPORTED, "fused sampling loop: needs 8 <= n <= 10, CZ, RZ encoding, <Z>");
+    fail(QIDDM_ERR_UNSUPPORTED, "fused sampling loop: needs 2 <= n <= 10, CZ, RZ encoding, <Z>");
     return QIDDM_ERR_UNSUPPORTED;
   }
-  const int64_t n_rot = (int64_t)c->n_rounds * c->n_blocks * c->sel_layers * c->n_qubits;
-  return (int64_t)(c->dtype == QIDDM_F32 ? quad_tables_bytes<float>(c->n_qubits, n_rot)
-                                         : quad_tables_bytes<double>(c->n_qubits, n_rot));
+  return (int64_t)for_dtype(c->dtype, [&](auto t) { return quad_tables_bytes<decltype(t)>(c->n_qubits, rot_gates(c)); });
 }
 
 int qiddm_dense_sample_prepare(const qiddm_circuit_t* c, const double* angles, void* tables, void* stream) {
@@ -1230,20 +1024,12 @@ int qiddm_dense_sample_prepare(const qiddm_circuit_t* c, const double* angles, v
   if (need < 0) return (int)need;
   if (!angles || !tables) return fail(QIDDM_ERR_INVALID, "angles/tables is NULL");
   const qiddm::KScalars p = make_params(c);
-  const int64_t n_rot = (int64_t)c->n_rounds * c->n_blocks * c->sel_layers * c->n_qubits;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool f32 = c->dtype == QIDDM_F32;
-  switch (c->n_qubits) {
-    case 2: return f32 ? launch_quad_tables<float, 2>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 2>(angles, tables, p, n_rot, st);
-    case 3: return f32 ? launch_quad_tables<float, 3>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 3>(angles, tables, p, n_rot, st);
-    case 4: return f32 ? launch_quad_tables<float, 4>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 4>(angles, tables, p, n_rot, st);
-    case 5: return f32 ? launch_quad_tables<float, 5>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 5>(angles, tables, p, n_rot, st);
-    case 6: return f32 ? launch_quad_tables<float, 6>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 6>(angles, tables, p, n_rot, st);
-    case 7: return f32 ? launch_quad_tables<float, 7>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 7>(angles, tables, p, n_rot, st);
-    case 8: return f32 ? launch_quad_tables<float, 8>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 8>(angles, tables, p, n_rot, st);
-    case 9: return f32 ? launch_quad_tables<float, 9>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 9>(angles, tables, p, n_rot, st);
-    default: return f32 ? launch_quad_tables<float, 10>(angles, tables, p, n_rot, st) : launch_quad_tables<double, 10>(angles, tables, p, n_rot, st);
-  }
+  return for_qubits<2, kFused>(c->n_qubits, "fused sampler", [&](auto N) {
+    return for_dtype(c->dtype, [&](auto t) {
+      return launch_quad_tables<decltype(t), N()>(angles, tables, p, rot_gates(c), st);
+    });
+  });
 }
 
 }  // extern "C"

@@ -26,20 +26,10 @@ int launch_t(const void* inputs, const void* tail, const void* gout, void* parti
   if (smem > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "circuit with %lld layers needs %zu B of LDS for the reverse sweep (limit %zu)",
                 (long long)layers, smem, kMaxLds);
-  auto kern = qiddm::cz10_adjoint_kernel<T>;
-  static DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(qiddm::kCz10Waves * qiddm::kWave), smem, st,
-                     static_cast<const T*>(inputs), static_cast<const T*>(tail), static_cast<const T*>(gout),
-                     static_cast<T*>(partials), slab_stride, static_cast<T*>(grad_inputs), gin_ld, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "cz10_adjoint_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return launch<qiddm::cz10_adjoint_kernel<T>>(
+      kMaxLds, dim3((unsigned)grid), dim3(qiddm::kCz10Waves * qiddm::kWave), smem, st, "cz10_adjoint_kernel",
+      static_cast<const T*>(inputs), static_cast<const T*>(tail), static_cast<const T*>(gout),
+      static_cast<T*>(partials), slab_stride, static_cast<T*>(grad_inputs), gin_ld, p);
 }
 }  // namespace
 
@@ -47,8 +37,9 @@ int launch_cz10_adjoint(int dtype, const void* inputs, const void* tail, const v
                         int64_t slab_stride, void* grad_inputs, int64_t gin_ld, const qiddm::KScalars& p, int64_t grid,
                         void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == QIDDM_F32 ? launch_t<float>(inputs, tail, gout, partials, slab_stride, grad_inputs, gin_ld, p, grid, st)
-                            : launch_t<double>(inputs, tail, gout, partials, slab_stride, grad_inputs, gin_ld, p, grid, st);
+  return for_dtype(dtype, [&](auto t) {
+    return launch_t<decltype(t)>(inputs, tail, gout, partials, slab_stride, grad_inputs, gin_ld, p, grid, st);
+  });
 }
 
 }  // namespace qiddm_capi

@@ -12,6 +12,7 @@
 namespace {
 
 using qiddm_capi::fail;
+using qiddm_capi::for_dtype;
 using qiddm_capi::kMaxLds;
 
 template <typename T>
@@ -31,8 +32,7 @@ int lean_layers(const qiddm_circuit_t* c) {
   const int64_t layers = (int64_t)c->n_rounds * c->n_blocks * c->sel_layers;
   if (layers > 128)
     return fail(QIDDM_ERR_UNSUPPORTED, "lean sampling loop: %lld layers (limit 128)", (long long)layers);
-  const size_t lds = c->dtype == QIDDM_F32 ? lean_lds<float>(c->n_qubits, (int)layers, c->n_rounds)
-                                           : lean_lds<double>(c->n_qubits, (int)layers, c->n_rounds);
+  const size_t lds = for_dtype(c->dtype, [&](auto t) { return lean_lds<decltype(t)>(c->n_qubits, (int)layers, c->n_rounds); });
   if (lds > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "lean sampling loop: %lld layers need %zu B of LDS (limit %zu)",
                 (long long)layers, lds, kMaxLds);
@@ -60,20 +60,10 @@ int launch_lean(const double* x, const double* wd, const double* bd, const doubl
                 const void* tables, const qiddm::QuadScalars& d, const qiddm::KScalars& p, int layers, hipStream_t st) {
   const size_t smem = qiddm::LeanTables<T, N>::lds_bytes(layers, p.n_rounds,
                                                          !qiddm::lean_tables_in_registers<REUP, LPR>());
-  auto kern = qiddm::dense_lean_kernel<T, N, PPT, REUP, LPR, POST>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
   const unsigned blocks = (unsigned)(p.batch < 2048 ? p.batch : 2048);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), smem, st, x, wd, bd, wu, bu, y,
-                     static_cast<const unsigned char*>(tables), d, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "dense_lean_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return qiddm_capi::launch<qiddm::dense_lean_kernel<T, N, PPT, REUP, LPR, POST>>(
+      kMaxLds, dim3(blocks), dim3(256), smem, st, "dense_lean_kernel", x, wd, bd, wu, bu, y,
+      static_cast<const unsigned char*>(tables), d, p);
 }
 
 // the instantiation for this circuit: re-upload or not; layers per round compiled in for the shapes the reference's
@@ -117,8 +107,7 @@ int64_t qiddm_dense_sample_lean_tables_bytes(const qiddm_circuit_t* c) {
   if (rc != QIDDM_OK) return rc;
   const int layers = lean_layers(c);
   if (layers < 0) return layers;
-  return (int64_t)(c->dtype == QIDDM_F32 ? lean_bytes<float>(c->n_qubits, layers, c->n_rounds)
-                                         : lean_bytes<double>(c->n_qubits, layers, c->n_rounds));
+  return (int64_t)for_dtype(c->dtype, [&](auto t) { return lean_bytes<decltype(t)>(c->n_qubits, layers, c->n_rounds); });
 }
 
 int qiddm_dense_sample_lean_prepare(const qiddm_circuit_t* c, const double* angles, const double* w_down,
@@ -132,20 +121,14 @@ int qiddm_dense_sample_lean_prepare(const qiddm_circuit_t* c, const double* angl
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* tb = static_cast<unsigned char*>(tables);
   const int f = (int)features;
-  if (c->n_qubits == 8) {
-    if (c->dtype == QIDDM_F32)
-      hipLaunchKernelGGL((qiddm::lean_tables_kernel<float, 8>), dim3(1), dim3(256), 0, st, angles, w_down, b_down, w_up, b_up, f, tb, p);
-    else
-      hipLaunchKernelGGL((qiddm::lean_tables_kernel<double, 8>), dim3(1), dim3(256), 0, st, angles, w_down, b_down, w_up, b_up, f, tb, p);
-  } else {
-    if (c->dtype == QIDDM_F32)
-      hipLaunchKernelGGL((qiddm::lean_tables_kernel<float, 6>), dim3(1), dim3(256), 0, st, angles, w_down, b_down, w_up, b_up, f, tb, p);
-    else
-      hipLaunchKernelGGL((qiddm::lean_tables_kernel<double, 6>), dim3(1), dim3(256), 0, st, angles, w_down, b_down, w_up, b_up, f, tb, p);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "lean_tables_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  auto prepare = [&](auto N) {
+    return for_dtype(c->dtype, [&](auto t) {
+      hipLaunchKernelGGL((qiddm::lean_tables_kernel<decltype(t), N()>), dim3(1), dim3(256), 0, st, angles, w_down, b_down,
+                         w_up, b_up, f, tb, p);
+      return qiddm_capi::launched("lean_tables_kernel");
+    });
+  };
+  return c->n_qubits == 8 ? prepare(std::integral_constant<int, 8>{}) : prepare(std::integral_constant<int, 6>{});
 }
 
 int qiddm_dense_sample_lean_check(const qiddm_circuit_t* c, const void* tables, void* stream) {
@@ -190,9 +173,9 @@ int qiddm_dense_sample_lean(const qiddm_circuit_t* c, const double* x, int64_t b
   d.noise_factor = noise_factor;
   d.stamps = qiddm_capi::stamp_buffer(8);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return c->dtype == QIDDM_F32
-             ? dispatch_lean<float>(c->n_qubits, x, w_down, b_down, w_up, b_up, y, tables, d, p, layers, st)
-             : dispatch_lean<double>(c->n_qubits, x, w_down, b_down, w_up, b_up, y, tables, d, p, layers, st);
+  return for_dtype(c->dtype, [&](auto t) {
+    return dispatch_lean<decltype(t)>(c->n_qubits, x, w_down, b_down, w_up, b_up, y, tables, d, p, layers, st);
+  });
 }
 
 }  // extern "C"

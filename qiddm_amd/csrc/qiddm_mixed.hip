@@ -18,7 +18,10 @@
 namespace {
 
 using qiddm_capi::fail;
+using qiddm_capi::for_dtype;
 using qiddm_capi::kMaxLds;
+using qiddm_capi::launch;
+using qiddm_capi::launched;
 
 constexpr int kMixedMaxQubits = 8;
 constexpr int64_t kMixedMaxBlocks = 256;
@@ -249,13 +252,6 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
                       const double* angle_rows, const double* features, const double* gates, double* out,
                       qiddm::MixedScalars m, bool embeds, hipStream_t st) {
   const size_t smem = (size_t)qiddm::kWideTile * sizeof(qiddm::V2<T>);
-  auto sweep = qiddm::mixed_wide_sweep<T>;
-  static qiddm_capi::DeviceFlags big;
-  if (smem > 48 * 1024 && !big.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sweep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(e));
-    big.set();
-  }
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
   double* norms = reinterpret_cast<double*>(ws + g.off_norms);
   qiddm::V2<T>* slabs = reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs);
@@ -263,12 +259,14 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
   for (int64_t s0 = 0; s0 < m.batch; s0 += resident) {
     const unsigned chunk = (unsigned)(m.batch - s0 < resident ? m.batch - s0 : resident);
     if (embeds) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, features, norms, m, s0);
-    for (const qiddm::WideSegment& sg : plan.segments)
-      hipLaunchKernelGGL(sweep, dim3(tiles, chunk), dim3(256), smem, st, prog, angle_rows, features, gates, norms, slabs, m,
-                         sg, s0, (int64_t)0);
+    for (const qiddm::WideSegment& sg : plan.segments) {   // (the sweeps ask for the LDS they use, no more)
+      const int rc = launch<qiddm::mixed_wide_sweep<T>>(smem, dim3(tiles, chunk), dim3(256), smem, st, "mixed_wide_sweep",
+                                                       prog, angle_rows, features, gates, norms, slabs, m, sg, s0,
+                                                       (int64_t)0);
+      if (rc != QIDDM_OK) return rc;
+    }
     hipLaunchKernelGGL(qiddm::mixed_wide_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "mixed_wide launch failed: %s", hipGetErrorString(e));
+    if (const int rc = launched("mixed_wide"); rc != QIDDM_OK) return rc;
   }
   return QIDDM_OK;
 }
@@ -370,21 +368,8 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
                                qiddm::MixedScalars m, qiddm::WideBwdScalars b, int32_t n_gates, hipStream_t st) {
   using C = qiddm::V2<T>;
   const size_t tile_bytes = (size_t)qiddm::kWideTile * sizeof(C);
-  auto sweep = qiddm::mixed_wide_sweep<T>;
-  auto reverse = qiddm::mixed_wide_reverse_sweep<T>;
-  auto channels = qiddm::mixed_wide_adjoint_channels<T>;
-  static qiddm_capi::DeviceFlags big;
-  if (!big.get()) {
-    const void* kernels[3] = {reinterpret_cast<const void*>(sweep), reinterpret_cast<const void*>(reverse),
-                              reinterpret_cast<const void*>(channels)};
-    const size_t sizes[3] = {tile_bytes, 2 * tile_bytes, tile_bytes};
-    for (int k = 0; k < 3; ++k) {
-      if (sizes[k] <= 48 * 1024) continue;
-      hipError_t e = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizes[k]);
-      if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(e));
-    }
-    big.set();
-  }
+  const dim3 block(256);
+  int rc;
   const int n = m.n;
   const size_t DD = (size_t)1 << (2 * n);
   const unsigned D = 1u << n, tiles = 1u << (2 * n - qiddm::kWideLocalBits);
@@ -407,21 +392,27 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
     int cur = 0;
     for (int s = 0; s < bp.replay_end; ++s) {
       const bool ch = bp.plan.seg_channel[s] != 0;
-      hipLaunchKernelGGL(sweep, dim3(tiles, chunk), dim3(256), tile_bytes, st, prog, angle_rows, features, gates, norms,
-                         slabs + (size_t)cur * set_stride, m, bp.plan.segments[s], s0, (int64_t)(ch ? set_stride : 0));
+      rc = launch<qiddm::mixed_wide_sweep<T>>(tile_bytes, dim3(tiles, chunk), block, tile_bytes, st, "mixed_wide_sweep", prog,
+                                              angle_rows, features, gates, norms, slabs + (size_t)cur * set_stride, m,
+                                              bp.plan.segments[s], s0, (int64_t)(ch ? set_stride : 0));
+      if (rc != QIDDM_OK) return rc;
       cur += ch ? 1 : 0;
     }
     qiddm::WideBwdScalars bs = b;
     bs.seed = 1;
     for (int s = n_seg - 1; s >= 0; --s) {
-      if (bp.plan.seg_channel[s]) {
-        hipLaunchKernelGGL(channels, dim3(tiles, chunk), dim3(256), tile_bytes, st, prog, grad_out, lam, m,
-                           bp.plan.segments[s], bs, s0);
-        if (s < bp.replay_end) --cur;
+      if (!bp.plan.seg_channel[s]) {
+        rc = launch<qiddm::mixed_wide_reverse_sweep<T>>(2 * tile_bytes, dim3(tiles, chunk), block, 2 * tile_bytes, st,
+                                                        "mixed_wide_reverse_sweep", prog, slot, angle_rows, gates, grad_out,
+                                                        slabs + (size_t)cur * set_stride, lam, partials, m,
+                                                        bp.plan.segments[s], bs, s0);
       } else {
-        hipLaunchKernelGGL(reverse, dim3(tiles, chunk), dim3(256), 2 * tile_bytes, st, prog, slot, angle_rows, gates,
-                           grad_out, slabs + (size_t)cur * set_stride, lam, partials, m, bp.plan.segments[s], bs, s0);
+        rc = launch<qiddm::mixed_wide_adjoint_channels<T>>(tile_bytes, dim3(tiles, chunk), block, tile_bytes, st,
+                                                           "mixed_wide_adjoint_channels", prog, grad_out, lam, m,
+                                                           bp.plan.segments[s], bs, s0);
+        if (s < bp.replay_end) --cur;
       }
+      if (rc != QIDDM_OK) return rc;
       bs.seed = 0;
     }
     if (bp.embed_live) {
@@ -432,8 +423,7 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
       hipLaunchKernelGGL(qiddm::mixed_wide_grad_finalize, dim3((n_groups + 3) / 4, chunk), dim3(256), 0, st, params,
                          group_begin, n_groups, gates, partials, grad_rows, grad_gates, bp.n_slots, n_gates, tiles,
                          m.batch, s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "mixed_wide backward launch failed: %s", hipGetErrorString(e));
+    if (rc = launched("mixed_wide backward"); rc != QIDDM_OK) return rc;
   }
   return QIDDM_OK;
 }
@@ -487,30 +477,12 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
   m.slab_in_lds = g.in_lds ? 1 : 0;
   const size_t smem = g.in_lds ? (size_t)g.slab_bytes : 0;
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws + g.off_prog);
-  if (dtype == QIDDM_F32) {
-    auto kern = qiddm::mixed_kernel<float>;
-    static qiddm_capi::DeviceFlags big;
-    if (smem > 48 * 1024 && !big.get()) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMaxLds - 4096));  // the kernel also has 2 KiB of static LDS
-      if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(e));
-      big.set();
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)g.blocks), dim3(256), smem, st, prog, angle_rows, features, gates, out,
-                       reinterpret_cast<qiddm::V2<float>*>(ws + g.off_slabs), m);
-  } else {
-    auto kern = qiddm::mixed_kernel<double>;
-    static qiddm_capi::DeviceFlags big;
-    if (smem > 48 * 1024 && !big.get()) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMaxLds - 4096));  // the kernel also has 2 KiB of static LDS
-      if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(e));
-      big.set();
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)g.blocks), dim3(256), smem, st, prog, angle_rows, features, gates, out,
-                       reinterpret_cast<qiddm::V2<double>*>(ws + g.off_slabs), m);
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "mixed_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch<qiddm::mixed_kernel<T>>(kMaxLds - 4096 /* the kernel also has 2 KiB of static LDS */,
+                                          dim3((unsigned)g.blocks), dim3(256), smem, st, "mixed_kernel", prog, angle_rows,
+                                          features, gates, out, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m);
+  });
 }
 
 int64_t qiddm_mixed_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch,
@@ -574,32 +546,14 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   b.n_snaps = n_snaps;
   const size_t smem = g.in_lds ? 2 * (size_t)g.slab_bytes : 0;
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws + g.off_prog);
-  if (dtype == QIDDM_F32) {
-    auto kern = qiddm::mixed_backward_kernel<float>;
-    static qiddm_capi::DeviceFlags big;
-    if (smem > 48 * 1024 && !big.get()) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMaxLds - 8192));  // the kernel also has 4.5 KiB of static LDS
-      if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(e));
-      big.set();
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)g.blocks), dim3(256), smem, st, prog, angle_rows, features, gates, grad_out,
-                       grad_rows, grad_gates, embeds ? grad_features : nullptr,
-                       reinterpret_cast<qiddm::V2<float>*>(ws + g.off_slabs), m, b);
-  } else {
-    auto kern = qiddm::mixed_backward_kernel<double>;
-    static qiddm_capi::DeviceFlags big;
-    if (smem > 48 * 1024 && !big.get()) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMaxLds - 8192));  // the kernel also has 4.5 KiB of static LDS
-      if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(e));
-      big.set();
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)g.blocks), dim3(256), smem, st, prog, angle_rows, features, gates, grad_out,
-                       grad_rows, grad_gates, embeds ? grad_features : nullptr,
-                       reinterpret_cast<qiddm::V2<double>*>(ws + g.off_slabs), m, b);
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "mixed_backward_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch<qiddm::mixed_backward_kernel<T>>(kMaxLds - 8192 /* the kernel also has 4.5 KiB of static LDS */,
+                                                   dim3((unsigned)g.blocks), dim3(256), smem, st, "mixed_backward_kernel",
+                                                   prog, angle_rows, features, gates, grad_out, grad_rows, grad_gates,
+                                                   embeds ? grad_features : nullptr,
+                                                   reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m, b);
+  });
 }
 
 int64_t qiddm_mixed_wide_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, const qiddm_mixed_op_t* program,
@@ -674,9 +628,9 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
   m.enc_offset = enc_offset;
   m.pad_with = pad_with;
   m.slab_in_lds = 0;
-  if (dtype == QIDDM_F32)
-    return launch_mixed_wide<float>(plan, g, resident, ws, angle_rows, features, gates, out, m, embeds, st);
-  return launch_mixed_wide<double>(plan, g, resident, ws, angle_rows, features, gates, out, m, embeds, st);
+  return for_dtype(dtype, [&](auto t) {
+    return launch_mixed_wide<decltype(t)>(plan, g, resident, ws, angle_rows, features, gates, out, m, embeds, st);
+  });
 }
 
 int64_t qiddm_mixed_wide_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch,
@@ -772,11 +726,10 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
   qiddm::WideBwdScalars b{};
   b.gout_ld = gout_ld;
   b.n_slots = bp.n_slots;
-  if (dtype == QIDDM_F32)
-    return launch_mixed_wide_backward<float>(bp, g, resident, ws, angle_rows, features, gates, grad_out, grad_rows,
-                                             grad_gates, grad_features, m, b, n_gates, st);
-  return launch_mixed_wide_backward<double>(bp, g, resident, ws, angle_rows, features, gates, grad_out, grad_rows,
-                                            grad_gates, grad_features, m, b, n_gates, st);
+  return for_dtype(dtype, [&](auto t) {
+    return launch_mixed_wide_backward<decltype(t)>(bp, g, resident, ws, angle_rows, features, gates, grad_out, grad_rows,
+                                                   grad_gates, grad_features, m, b, n_gates, st);
+  });
 }
 
 }  // extern "C"

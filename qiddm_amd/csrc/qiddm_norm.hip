@@ -13,6 +13,7 @@
 #include <cstdint>
 
 using qiddm_capi::fail;
+using qiddm_capi::launched;
 
 namespace qiddm {
 
@@ -501,12 +502,6 @@ int make_geom(int64_t batch, int64_t channels, int64_t hw, qiddm::NormGeom* g) {
   g->hw = hw;
   g->channels = (int32_t)channels;
   g->slices = (int32_t)(batch < qiddm::kNormMaxSlices ? batch : qiddm::kNormMaxSlices);
-  return QIDDM_OK;
-}
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "%s launch failed: %s", what, hipGetErrorString(e));
   return QIDDM_OK;
 }
 

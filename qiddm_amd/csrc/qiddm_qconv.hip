@@ -19,6 +19,8 @@ namespace {
 using qiddm_capi::check_circuit;
 using qiddm_capi::fail;
 using qiddm_capi::kMaxLds;
+using qiddm_capi::launch_status;
+using qiddm_capi::launched;
 
 int check_unitary_circuit(const qiddm_circuit_t* c) {
   int rc = check_circuit(c);
@@ -52,36 +54,18 @@ int launch_unitary(const qiddm_circuit_t* c, const double* angles, double* u, hi
   const size_t smem = S::bytes(n_rot, c->imprimitive == QIDDM_IMP_CNOT, waves);
   if (smem > kMaxLds)
     return fail(QIDDM_ERR_UNSUPPORTED, "circuit with %lld Rot gates needs %zu B of LDS", (long long)n_rot, smem);
-  auto kern = qiddm::unitary_kernel<T, N>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
   const int groups = (L::D + L::SPW - 1) / L::SPW;
   const int blocks = (groups + waves - 1) / waves;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(waves * qiddm::kWave), smem, st, angles, u, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "unitary_kernel<n=%d> launch failed: %s", N, hipGetErrorString(e));
-  return QIDDM_OK;
+  return qiddm_capi::launch<qiddm::unitary_kernel<T, N>>(kMaxLds, dim3((unsigned)blocks), dim3(waves * qiddm::kWave), smem,
+                                                         st, "unitary_kernel", angles, u, p);
 }
 
-template <typename T>
 int dispatch_unitary(const qiddm_circuit_t* c, const double* angles, double* u, hipStream_t st) {
-  switch (c->n_qubits) {
-    case 1: return launch_unitary<T, 1>(c, angles, u, st);
-    case 2: return launch_unitary<T, 2>(c, angles, u, st);
-    case 3: return launch_unitary<T, 3>(c, angles, u, st);
-    case 4: return launch_unitary<T, 4>(c, angles, u, st);
-    case 5: return launch_unitary<T, 5>(c, angles, u, st);
-    case 6: return launch_unitary<T, 6>(c, angles, u, st);
-    case 7: return launch_unitary<T, 7>(c, angles, u, st);
-    case 8: return launch_unitary<T, 8>(c, angles, u, st);
-    case 9: return launch_unitary<T, 9>(c, angles, u, st);
-    default: return launch_unitary<T, 10>(c, angles, u, st);
-  }
+  return qiddm_capi::for_dtype(c->dtype, [&](auto t) {
+    return qiddm_capi::for_qubits<1, QIDDM_MAX_QUBITS_FUSED>(c->n_qubits, "circuit unitary", [&](auto N) {
+      return launch_unitary<decltype(t), N()>(c, angles, u, st);
+    });
+  });
 }
 
 struct ConvGeometry {
@@ -129,9 +113,7 @@ int qiddm_circuit_unitary(const qiddm_circuit_t* circ, const double* angles, dou
   int rc = check_unitary_circuit(circ);
   if (rc != QIDDM_OK) return rc;
   if (!angles || !u) return fail(QIDDM_ERR_INVALID, "angles/u is NULL");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return circ->dtype == QIDDM_F32 ? dispatch_unitary<float>(circ, angles, u, st)
-                                  : dispatch_unitary<double>(circ, angles, u, st);
+  return dispatch_unitary(circ, angles, u, static_cast<hipStream_t>(stream));
 }
 
 int qiddm_circuit_unitary_wide(const qiddm_circuit_t* circ, const double* angles, double* ut, void* stream) {
@@ -146,9 +128,7 @@ int qiddm_circuit_unitary_wide(const qiddm_circuit_t* circ, const double* angles
   hipLaunchKernelGGL(qiddm::wide_unitary_kernel<0>, dim3(d < 2048 ? d : 2048), dim3(qiddm::kWideThreads), 0,
                      static_cast<hipStream_t>(stream), angles, reinterpret_cast<qiddm::V2<double>*>(ut), circ->n_qubits,
                      circ->sel_layers, circ->imprimitive == QIDDM_IMP_CNOT ? 1 : 0);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "wide_unitary_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return launched("wide_unitary_kernel");
 }
 
 int64_t qiddm_qconv_unitary_workspace_bytes(int32_t n_qubits, int64_t in_channels, int64_t kh, int64_t kw,
@@ -190,8 +170,8 @@ int qiddm_qconv_unitary_forward(int32_t n_qubits, const double* u, const double*
                        (int)out_channels, (int)g.k_pad, (int)g.n_pad, g.packed == 3 ? 0 : g.packed, w, padv,
                        bn ? bn->weight : nullptr, bn ? bn->bias : nullptr, bn ? bn->running_mean : nullptr,
                        bn ? bn->running_var : nullptr, bn ? bn->eps : 0.0, bnv, (int)(g.n_pad / 2));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_pack_kernel launch failed: %s", hipGetErrorString(e));
+  rc = launched("qconv_pack_kernel");
+  if (rc != QIDDM_OK) return rc;
   qiddm::GemmConv gc{};
   gc.C = (int32_t)in_channels;
   gc.H = (int32_t)h_eff;
@@ -255,9 +235,7 @@ int qiddm_qconv_unitary_forward(int32_t n_qubits, const double* u, const double*
       const float* pc = padv;
       const double* bc = bnv;
       void* args[] = {(void*)&x, (void*)&wc, (void*)&pc, (void*)&bc, (void*)&y, (void*)&gc};
-      e = hipLaunchKernel(kern, dim3(grid), dim3(qiddm::kFwdThreads), args, smem, st);
-      if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_fwd_halo_kernel launch failed: %s", hipGetErrorString(e));
-      return QIDDM_OK;
+      return launch_status("qconv_fwd_halo_kernel", hipLaunchKernel(kern, dim3(grid), dim3(qiddm::kFwdThreads), args, smem, st));
     }
   }
   const int64_t mblocks = (g.m + qiddm::kGemmM - 1) / qiddm::kGemmM;
@@ -280,9 +258,7 @@ int qiddm_qconv_unitary_forward(int32_t n_qubits, const double* u, const double*
   else
     QIDDM_GEMM_LAUNCH(g.n_pad / 64, qconv_gemm_kernel<0,);
 #undef QIDDM_GEMM_LAUNCH
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_gemm_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return launched("qconv_gemm_kernel");
 }
 
 namespace {
@@ -616,8 +592,8 @@ int train_backward(int32_t n_qubits, const void* x, bool x32, int64_t batch, int
     tc.wpix = pixel_rows;
   }
   void* args[] = {(void*)&x, (void*)&grad_y, (void*)&rows, (void*)&grad_features_t, (void*)&h_partials, (void*)&tc};
-  hipError_t e = hipLaunchKernel(kern, dim3(grid), dim3(threads), args, smem, st);
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_train_backward_kernel launch failed: %s", hipGetErrorString(e));
+  int rc = launch_status("qconv_train_backward_kernel", hipLaunchKernel(kern, dim3(grid), dim3(threads), args, smem, st));
+  if (rc != QIDDM_OK) return rc;
   if (pixel_rows) {
     if (dx.smem > 48 * 1024) {
       const hipError_t ea = hipFuncSetAttribute(dx.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
@@ -631,14 +607,9 @@ int train_backward(int32_t n_qubits, const void* x, bool x32, int64_t batch, int
     const double* xd = static_cast<const double*>(x);
     const float* wp = pixel_rows;
     void* dargs[] = {(void*)&xd, (void*)&wp, (void*)&rows, (void*)&grad_x, (void*)&tc};
-    e = hipLaunchKernel(dx.kern, dim3(dgrid), dim3(qiddm::kDxThreads), dargs, dx.smem, st);
-    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_dx_kernel launch failed: %s", hipGetErrorString(e));
-    return QIDDM_OK;
+    return launch_status("qconv_dx_kernel", hipLaunchKernel(dx.kern, dim3(dgrid), dim3(qiddm::kDxThreads), dargs, dx.smem, st));
   }
-  if (grad_x) {
-    e = qiddm::launch_fold_t(grad_features_t, grad_x, batch, tc, st);
-    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_fold_t_kernel launch failed: %s", hipGetErrorString(e));
-  }
+  if (grad_x) return launch_status("qconv_fold_t_kernel", qiddm::launch_fold_t(grad_features_t, grad_x, batch, tc, st));
   return QIDDM_OK;
 }
 }  // namespace
@@ -666,9 +637,8 @@ int qiddm_qconv_fold_features(const float* grad_features_t, int64_t batch, int64
   tc.Wo = (int32_t)wo;
   tc.F = (int32_t)(in_channels * kh * kw);
   tc.M = batch * ho * wo;
-  const hipError_t e = qiddm::launch_fold_t(grad_features_t, grad_x, batch, tc, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_fold_t_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return launch_status("qconv_fold_t_kernel",
+                       qiddm::launch_fold_t(grad_features_t, grad_x, batch, tc, static_cast<hipStream_t>(stream)));
 }
 
 int qiddm_qconv_train_rows(int32_t n_qubits, const double* u, int32_t u_transposed, int64_t features,
@@ -681,9 +651,7 @@ int qiddm_qconv_train_rows(int32_t n_qubits, const double* u, int32_t u_transpos
   hipLaunchKernelGGL(qiddm::qconv_rows_kernel, dim3((unsigned)row_channels), dim3(256), 0,
                      static_cast<hipStream_t>(stream), u, (int)u_transposed, (int)d, (int)features, (int)out_channels,
                      (int)row_channels, rows);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_rows_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return launched("qconv_rows_kernel");
 }
 
 int qiddm_qconv_train_vectors(int32_t n_qubits, const float* h_partials, int64_t n_partials, int64_t features,
@@ -698,9 +666,7 @@ int qiddm_qconv_train_vectors(int32_t n_qubits, const float* h_partials, int64_t
                      dim3(256), 0,
                      static_cast<hipStream_t>(stream), h_partials, (int)n_partials, (int)d, (int)features,
                      (int)out_channels, (int)row_channels, psi0, lambda);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "qconv_vectors_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return launched("qconv_vectors_kernel");
 }
 
 int qiddm_conv1x1_forward(const double* x, const double* weight, const double* bias, int64_t batch,
@@ -715,9 +681,7 @@ int qiddm_conv1x1_forward(const double* x, const double* weight, const double* b
   if (blocks > 0x7fffffff) return fail(QIDDM_ERR_UNSUPPORTED, "too many pixels for one launch");
   hipLaunchKernelGGL(qiddm::conv1x1_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
                      weight, bias, y, total, hw, (int)in_channels, (int)out_channels);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "conv1x1_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return launched("conv1x1_kernel");
 }
 
 int64_t qiddm_conv1x1_head_partials(int64_t batch, int64_t hw) {
@@ -747,9 +711,7 @@ int qiddm_conv1x1_head_backward(const double* x, const double* weight, const dou
                        grad_y, total, hw, (int)in_channels, grad_x, partials);
   hipLaunchKernelGGL(qiddm::conv1x1_head_finalize_kernel, dim3(1), dim3(256), 0, st, partials, (int)grid,
                      (int)in_channels, grad_weight, grad_bias);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "conv1x1_head_backward launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
+  return launched("conv1x1_head_backward");
 }
 
 }  // extern "C"

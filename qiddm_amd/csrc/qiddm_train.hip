@@ -14,6 +14,7 @@ namespace {
 using qiddm_capi::check_circuit;
 using qiddm_capi::fail;
 using qiddm_capi::kMaxLds;
+using qiddm_capi::launched;
 
 constexpr int64_t kMaxRowBlocks = 1024;
 
@@ -50,23 +51,10 @@ Geometry geometry(const qiddm_circuit_t* c, int64_t batch, int32_t pixels, int32
 template <typename T, int N, bool QUANTUM, int WPB, bool FOLD>
 int launch_rows(const qiddm_train_args_t* a, const Geometry& g, unsigned char* ws, const qiddm::TrainScalars& d,
                 const qiddm::KScalars& p, size_t smem, int64_t blocks, hipStream_t st) {
-  auto kern = qiddm::train_rows_kernel<T, N, QUANTUM, WPB, FOLD>;
-  static qiddm_capi::DeviceFlags big_lds_enabled;
-  if (smem > 48 * 1024 && !big_lds_enabled.get()) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (ea != hipSuccess)
-      return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
-    big_lds_enabled.set();
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WPB * qiddm::kWave), smem, st,
-                     reinterpret_cast<const double*>(ws + g.off_proj), a->b_down, a->angles,
-                     reinterpret_cast<double*>(ws + g.off_ev), reinterpret_cast<double*>(ws + g.off_gxr),
-                     reinterpret_cast<T*>(ws + g.off_k), a->batch, d, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "train_rows_kernel<n=%d> launch failed: %s", N, hipGetErrorString(e));
-  return QIDDM_OK;
+  return qiddm_capi::launch<qiddm::train_rows_kernel<T, N, QUANTUM, WPB, FOLD>>(
+      kMaxLds, dim3((unsigned)blocks), dim3(WPB * qiddm::kWave), smem, st, "train_rows_kernel",
+      reinterpret_cast<const double*>(ws + g.off_proj), a->b_down, a->angles, reinterpret_cast<double*>(ws + g.off_ev),
+      reinterpret_cast<double*>(ws + g.off_gxr), reinterpret_cast<T*>(ws + g.off_k), a->batch, d, p);
 }
 
 template <typename T, int N>
@@ -104,7 +92,6 @@ int run_step(const qiddm_circuit_t* c, const qiddm_train_args_t* a, const Geomet
             N <= qiddm::kFoldedAdjointMaxQubits) ? 1 : 0;   // (the forward-only step folds too)
   d.layers_per_round = c->n_blocks * c->sel_layers;
   p.fold = d.fold;
-  hipError_t e;
 
   // ---- 1a. projections (only the reverse sweep and linear_down consume them) ---------------------------------
   {
@@ -112,9 +99,7 @@ int run_step(const qiddm_circuit_t* c, const qiddm_train_args_t* a, const Geomet
     hipLaunchKernelGGL(qiddm::train_project_kernel<N>, dim3((unsigned)units), dim3(qiddm::kProjWaves * qiddm::kWave), 0,
                        st, a->x, a->noise, a->rng_state, a->schedule, a->w_down, a->w_up, a->b_up,
                        reinterpret_cast<double*>(ws + g.off_proj), a->batch, d);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return fail(QIDDM_ERR_LAUNCH, "train_project_kernel launch failed: %s", hipGetErrorString(e));
+    if (const int rc = launched("train_project_kernel"); rc != QIDDM_OK) return rc;
   }
 
   // ---- 1b. rows ---------------------------------------------------------------------------------------------
@@ -151,9 +136,7 @@ int run_step(const qiddm_circuit_t* c, const qiddm_train_args_t* a, const Geomet
                      reinterpret_cast<const double*>(ws + g.off_ev), reinterpret_cast<const double*>(ws + g.off_gxr),
                      reinterpret_cast<double*>(ws + g.off_partials), reinterpret_cast<double*>(ws + g.off_loss),
                      a->recon, a->elem_loss, a->batch, d);
-  e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(QIDDM_ERR_LAUNCH, "train_weight_grads_kernel launch failed: %s", hipGetErrorString(e));
+  if (rc = launched("train_weight_grads_kernel"); rc != QIDDM_OK) return rc;
 
   // ---- 3. finalize -----------------------------------------------------------------------------------------
   const int rows_out = q ? 2 * N + 1 : N + 1;
@@ -165,27 +148,7 @@ int run_step(const qiddm_circuit_t* c, const qiddm_train_args_t* a, const Geomet
                      reinterpret_cast<const double*>(ws + g.off_gxr), reinterpret_cast<const T*>(ws + g.off_k),
                      k_blocks, a->angles, N, g.n_rot_all, wblocks, a->loss, a->g_w_down, a->g_b_down, a->g_angles,
                      a->g_w_up, a->g_b_up, a->rng_state, d);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "train_finalize_kernel launch failed: %s", hipGetErrorString(e));
-  return QIDDM_OK;
-}
-
-template <typename T>
-int dispatch(const qiddm_circuit_t* c, const qiddm_train_args_t* a, const Geometry& g, unsigned char* ws,
-             hipStream_t st) {
-  switch (c->n_qubits) {
-    case 1: return run_step<T, 1>(c, a, g, ws, st);
-    case 2: return run_step<T, 2>(c, a, g, ws, st);
-    case 3: return run_step<T, 3>(c, a, g, ws, st);
-    case 4: return run_step<T, 4>(c, a, g, ws, st);
-    case 5: return run_step<T, 5>(c, a, g, ws, st);
-    case 6: return run_step<T, 6>(c, a, g, ws, st);
-    case 7: return run_step<T, 7>(c, a, g, ws, st);
-    case 8: return run_step<T, 8>(c, a, g, ws, st);
-    case 9: return run_step<T, 9>(c, a, g, ws, st);
-    case 10: return run_step<T, 10>(c, a, g, ws, st);
-    default: return fail(QIDDM_ERR_UNSUPPORTED, "the fused training step needs n_qubits <= 10 (got %d)", c->n_qubits);
-  }
+  return launched("train_finalize_kernel");
 }
 
 int check_args(const qiddm_circuit_t* c, int64_t batch, int32_t pixels, int32_t tau) {
@@ -233,7 +196,11 @@ int qiddm_train_step(const qiddm_circuit_t* circ, const qiddm_train_args_t* a, v
                 (long long)g.total, (long long)workspace_bytes);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return circ->dtype == QIDDM_F32 ? dispatch<float>(circ, a, g, ws, st) : dispatch<double>(circ, a, g, ws, st);
+  return qiddm_capi::for_dtype(circ->dtype, [&](auto t) {
+    return qiddm_capi::for_qubits<1, QIDDM_MAX_QUBITS_FUSED>(circ->n_qubits, "fused training step", [&](auto N) {
+      return run_step<decltype(t), N()>(circ, a, g, ws, st);
+    });
+  });
 }
 
 int qiddm_adam_step(const qiddm_adam_tensor_t* tensors, int32_t n_tensors, double lr, double beta1, double beta2,
@@ -278,8 +245,7 @@ int qiddm_adam_step(const qiddm_adam_tensor_t* tensors, int32_t n_tensors, doubl
     a.weight_decay = weight_decay;
     if (blocks > 0x7fffffff) return fail(QIDDM_ERR_UNSUPPORTED, "too many elements for one Adam launch");
     hipLaunchKernelGGL(qiddm::adam_step_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, sync);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "adam_step_kernel launch failed: %s", hipGetErrorString(e));
+    if (const int rc = launched("adam_step_kernel"); rc != QIDDM_OK) return rc;
   }
   return QIDDM_OK;
 }

@@ -58,7 +58,16 @@ rejected(lib.qiddm_dense_sample(P(ok), None, 4, 784, 784, None, None, None, None
                                 4 * 784, None, None), b"post_mode")
 rejected(lib.qiddm_dense_sample_prepare(P(ok), None, None, None))
 wide = Circuit(16, "rz", "CZ", "expz", 2, 6, 2).c_struct("f32")
-rejected(lib.qiddm_dense_sample_tables_bytes(P(wide)))
+rejected(lib.qiddm_dense_sample_tables_bytes(P(wide)), b"2 <= n <= 10")
+rejected(lib.qiddm_dense_sample(P(wide), None, 4, 784, 784, None, None, None, None, None, 784, 0, 1.0, 2, None, 784,
+                                4 * 784, None, None), b"2 <= n <= 10")
+# ---- a wire count just outside a width dispatcher's range ----------------------------------------------------------
+# Every entry point but one bounds n before it dispatches (the fused ones refuse n > 10 by name, qiddm_forward routes
+# 11..16 to the wide kernels, check_circuit stops at 16); qiddm_qconv_forward leaves n = 11 to its dispatcher, which
+# refuses before any launch -- the buffers are never read.
+conv11 = Circuit(11, "amplitude", "CNOT", "probs", 1, 1, 2, n_features=9).c_struct("f32")
+host = (ctypes.c_double * 64)()
+rejected(lib.qiddm_qconv_forward(P(conv11), host, 1, 1, 4, 4, 3, 3, 0, 0, host, 2, host, None), b"n_qubits=11 outside 1..10")
 # a 16-qubit forward without its workspace
 rejected(lib.qiddm_forward(P(wide), None, 8, 16, None, None, 16, None, 0, None))
 cnot = Circuit(10, "amplitude", "CNOT", "probs", 1, 1, 60, n_features=784, pad_with=0.1).c_struct("f32")

@@ -97,6 +97,14 @@ def test_qconv_stack_trains_through_the_adjoint():
     (8, 12, 3, 1, (6, 6), 2, "f32", 2e-4),      # 12 channels in the 16-channel kernel: zero channel columns
     (4, 20, 3, 1, (5, 5), 2, "f32", 2e-4),      # 20 channels in the 32-channel kernel, 36 features
     (28, 8, 3, 1, (4, 4), 2, "f32", 2e-4),      # 252 features on 8 wires: almost no pad columns, 16 column blocks
+    # the remaining widths of the per-pixel sweep, smallest layer of each: 1, 2, 3, 6, 8, 9, 10 wires
+    (1, 1, 1, 0, (3, 2), 1, "f64", 1e-9),
+    (3, 2, 1, 0, (3, 2), 1, "f64", 1e-9),
+    (5, 4, 1, 0, (3, 2), 1, "f64", 1e-9),
+    (4, 4, 3, 1, (3, 2), 1, "f64", 1e-9),
+    (16, 4, 3, 1, (3, 2), 1, "f64", 1e-9),
+    (32, 4, 3, 1, (3, 2), 1, "f64", 1e-9),
+    (60, 4, 3, 1, (3, 2), 1, "f64", 1e-9),
 ])
 def test_fused_qconv_backward_vs_oracle_autograd(c_in, c_out, k, pad, hw, qdepth, precision, tol):
     """qiddm_qconv_backward (adjoint sweep with the patch and dL/dy read in place, then the fold): d/dweights and
@@ -289,7 +297,7 @@ def test_wide_qconv_trains_through_the_unitary_gemm_route(c_in, c_out, hw, batch
 # ---- the pass-structured reverse sweep of the wide CZ family (qsim_wide_cz_adjoint.h) --------------------------------
 @pytest.mark.parametrize("n,L,S,meas,B", [(11, 1, 2, "expz", 3), (11, 3, 1, "probs", 2), (12, 2, 2, "probs", 3),
                                           (13, 1, 3, "expz", 2), (13, 5, 1, "expz", 2), (14, 2, 2, "expz", 2),
-                                          (16, 1, 2, "expz", 2), (16, 2, 2, "expz", 1)])
+                                          (16, 1, 2, "expz", 2), (16, 2, 2, "expz", 1), (15, 1, 2, "expz", 2)])
 @pytest.mark.parametrize("precision,tol", [("f64", 1e-9), ("f32", 2e-4)])
 def test_wide_cz_adjoint_vs_oracle_autograd(n, L, S, meas, B, precision, tol):
     """Weights and angle inputs against autograd through the oracle: even / odd layer counts (the turnaround runs on

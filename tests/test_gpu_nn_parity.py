@@ -280,7 +280,10 @@ def test_c4_style_12_qubit_qconv():
 
 
 @pytest.mark.parametrize("cin,cout,k,pad,hw", [(1, 8, 3, 1, 9), (8, 16, 3, 1, 6), (32, 16, 1, 0, 7), (16, 8, 3, 1, 11),
-                                               (2, 2, (2, 3), (1, 0), 6)])
+                                               (2, 2, (2, 3), (1, 0), 6),
+                                               # the remaining widths, smallest layer of each: 1, 2, 3, 6, 9, 10 wires
+                                               (1, 1, 1, 0, 3), (3, 2, 1, 0, 3), (5, 4, 1, 0, 3), (4, 4, 3, 1, 3),
+                                               (32, 4, 3, 1, 3), (60, 4, 3, 1, 3)])
 def test_qconv2d_fused_equals_traced_path(cin, cout, k, pad, hw):
     """qiddm_qconv_forward (unfold fused, inference) == unfold + QNode path == oracle."""
     from qiddm_amd import nn
@@ -329,11 +332,12 @@ def test_dense_sample_quad_kernel(n, N, L, S, P, precision, tol):
         assert torch.allclose(got, ref, atol=tol, rtol=tol), (post, (got - ref).abs().max())
 
 
-def test_dense_forward_large_batch_uses_wave_kernel():
-    """Above 1024 samples qiddm_dense_forward runs the one-wave-per-sample kernel (LDS-staged weights)."""
+@pytest.mark.parametrize("n,P,B", [(8, 784, 2100)] + [(k, 16, 1030) for k in (1, 2, 3, 4, 5, 6, 7, 9, 10)])
+def test_dense_forward_large_batch_uses_wave_kernel(n, P, B):
+    """Above 1024 samples qiddm_dense_forward runs the one-wave-per-sample kernel (LDS-staged weights); below, the
+    four-wave sampler takes these circuits, so this is where every width of the dense forward itself is launched."""
     from qiddm_amd.circuit import Circuit, dense_forward
     g = torch.Generator().manual_seed(3)
-    n, P, B = 8, 784, 2100
     x = torch.rand(B, P, generator=g, dtype=torch.float64)
     wd = torch.randn(n, P, generator=g, dtype=torch.float64) * 0.1
     wu = torch.randn(P, n, generator=g, dtype=torch.float64)

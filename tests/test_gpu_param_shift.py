@@ -44,6 +44,8 @@ def _oracle_grads(spec, x, w, gout, wrt_x):
     (7, "ry", "CNOT", "probs", 1, 3),
     (5, "amplitude", "CNOT", "probs", 1, 3),
     (9, "rz", "CZ", "probs", 1, 2),
+    (2, "rz", "CNOT", "probs", 1, 2),     # with these two the sweep runs at every register-resident width
+    (10, "rz", "CZ", "expz", 1, 2),
 ])
 def test_shift_sweep_matches_autograd(n, enc, imp, meas, L, S, precision, tol):
     from qiddm_amd.circuit import run_shift_sweep

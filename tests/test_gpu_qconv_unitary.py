@@ -10,7 +10,7 @@ DEV = "cuda"
 
 
 @pytest.mark.parametrize("n,imp", [(1, "CNOT"), (2, "CNOT"), (3, "CZ"), (5, "CNOT"), (6, "CNOT"), (8, "CNOT"),
-                                   (10, "CNOT"), (7, "CZ")])
+                                   (10, "CNOT"), (7, "CZ"), (4, "CZ"), (9, "CNOT")])
 def test_circuit_unitary_vs_oracle(n, imp):
     from oracle import statevector as sv
     from qiddm_amd import circuit as qc

@@ -120,7 +120,7 @@ def test_elementwise_loss_variant_and_fallbacks():
 
 
 @pytest.mark.parametrize("kind,n,B,T", [("qnn", 1, 3, 2), ("qnn", 2, 1, 1), ("ll", 2, 2, 3), ("qnn", 9, 3, 2), ("ll", 9, 2, 2),
-                                        ("qnn", 10, 2, 2), ("ll", 10, 2, 1), ("qnn", 5, 70, 3)])
+                                        ("qnn", 10, 2, 2), ("ll", 10, 2, 1), ("qnn", 5, 70, 3), ("qnn", 6, 3, 2)])
 def test_fused_step_edge_shapes_vs_oracle_autograd(kind, n, B, T):
     """Smallest / largest register-resident circuits (general reverse sweep at n = 10, folded below), single rows,
     more rows than one workgroup wave."""
