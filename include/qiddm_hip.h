@@ -24,6 +24,12 @@
  *     reason is available from qiddm_last_error() (thread local).
  *   - wire w is bit (n-1-w) of the amplitude index (wire 0 = most significant),
  *     the order qml.probs(wires=range(n)) reports.
+ *   - every `*_ld` (and `y_step_stride`) is a leading dimension counted in ELEMENTS of the operand's own
+ *     type: row r of the operand starts `r * ld` elements behind its pointer.  `in_ld`, `g_ld`, `gin_ld` and
+ *     `out_ld` of qiddm_forward count elements of circ->dtype; `out_ld` of qiddm_forward_post counts float64
+ *     elements (its output is float64 whatever the circuit's dtype).  A leading dimension below the operand's
+ *     width is refused with QIDDM_ERR_INVALID.  Rows need no alignment beyond that of one element, and the
+ *     elements between the end of a row and the start of the next (the padding) are never read or written.
  *
  * Circuit family (covers every `_circuit` of reference nn/qdense.py and the
  * exported QConv2d of nn/qconv.py):

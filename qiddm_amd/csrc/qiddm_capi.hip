@@ -685,8 +685,13 @@ int qiddm_backward_adjoint_wide(const qiddm_circuit_t* c, const void* inputs, in
     return fail(QIDDM_ERR_UNSUPPORTED, "n_qubits=%d: use qiddm_backward_adjoint (register-resident)", c->n_qubits);
   if (batch < 0) return fail(QIDDM_ERR_INVALID, "batch < 0");
   if (!gate_table || !grad_out || !k_partials) return fail(QIDDM_ERR_INVALID, "gate_table/grad_out/k_partials is NULL");
-  if (c->encoding != QIDDM_ENC_NONE && batch > 0 && !inputs) return fail(QIDDM_ERR_INVALID, "inputs is NULL");
+  if (batch > 0) {
+    rc = check_inputs(c, inputs, in_ld);
+    if (rc != QIDDM_OK) return rc;
+  }
   if (g_ld < out_cols(c)) return fail(QIDDM_ERR_INVALID, "g_ld smaller than the output row");
+  const int64_t gin_cols = c->encoding == QIDDM_ENC_AMPLITUDE ? c->n_features : c->n_qubits;
+  if (grad_inputs && gin_ld < gin_cols) return fail(QIDDM_ERR_INVALID, "gin_ld=%lld < %lld", (long long)gin_ld, (long long)gin_cols);
   const int64_t need = qiddm_adjoint_workspace_bytes(c, batch);
   if (!workspace || workspace_bytes < need)
     return fail(QIDDM_ERR_INVALID, "workspace of %lld B needed (qiddm_adjoint_workspace_bytes), got %lld",
@@ -909,8 +914,8 @@ int qiddm_dense_forward(const qiddm_circuit_t* c, const double* x, int64_t batch
   if (!x || !w_down || !angles || !w_up || !y)
     return fail(QIDDM_ERR_INVALID, "x/w_down/angles/w_up/y is NULL");
   if (x == y) return fail(QIDDM_ERR_INVALID, "y must not alias x");
-  if (x_ld < in_features || y_ld < out_features)
-    return fail(QIDDM_ERR_INVALID, "row strides smaller than the feature counts");
+  if (x_ld < in_features) return fail(QIDDM_ERR_INVALID, "x_ld=%lld < in_features=%lld", (long long)x_ld, (long long)in_features);
+  if (y_ld < out_features) return fail(QIDDM_ERR_INVALID, "y_ld=%lld < out_features=%lld", (long long)y_ld, (long long)out_features);
   static const bool no_quad = std::getenv("QIDDM_NO_QUAD") != nullptr;  // tuning switch
   if (!no_quad && batch <= 1024 && quad_supported(c, in_features, out_features))
     return qiddm_dense_sample(c, x, batch, x_ld, in_features, w_down, b_down, angles, w_up, b_up, out_features,
@@ -987,8 +992,11 @@ int qiddm_dense_sample(const qiddm_circuit_t* c, const double* x, int64_t batch,
   if (batch == 0 || n_steps == 0) return QIDDM_OK;
   if (!x || !w_down || !angles || !w_up || !y) return fail(QIDDM_ERR_INVALID, "x/w_down/angles/w_up/y is NULL");
   if (x == y) return fail(QIDDM_ERR_INVALID, "y must not alias x");
-  if (x_ld < in_features || y_ld < out_features || y_step_stride < batch * y_ld - (y_ld - out_features))
-    return fail(QIDDM_ERR_INVALID, "strides smaller than the tensor extents");
+  if (x_ld < in_features) return fail(QIDDM_ERR_INVALID, "x_ld=%lld < in_features=%lld", (long long)x_ld, (long long)in_features);
+  if (y_ld < out_features) return fail(QIDDM_ERR_INVALID, "y_ld=%lld < out_features=%lld", (long long)y_ld, (long long)out_features);
+  if (y_step_stride < batch * y_ld - (y_ld - out_features))
+    return fail(QIDDM_ERR_INVALID, "y_step_stride=%lld < the %lld elements of one step", (long long)y_step_stride,
+                (long long)(batch * y_ld - (y_ld - out_features)));
   qiddm::KScalars p = make_params(c);
   p.batch = batch;
   qiddm::QuadScalars d;

@@ -157,8 +157,11 @@ int qiddm_dense_sample_lean(const qiddm_circuit_t* c, const double* x, int64_t b
   if (batch == 0 || n_steps == 0) return QIDDM_OK;
   if (!x || !w_down || !w_up || !y || !tables) return fail(QIDDM_ERR_INVALID, "x/w_down/w_up/y/tables is NULL");
   if (x == y) return fail(QIDDM_ERR_INVALID, "y must not alias x");
-  if (x_ld < features || y_ld < features || y_step_stride < batch * y_ld - (y_ld - features))
-    return fail(QIDDM_ERR_INVALID, "strides smaller than the tensor extents");
+  if (x_ld < features) return fail(QIDDM_ERR_INVALID, "x_ld=%lld < features=%lld", (long long)x_ld, (long long)features);
+  if (y_ld < features) return fail(QIDDM_ERR_INVALID, "y_ld=%lld < features=%lld", (long long)y_ld, (long long)features);
+  if (y_step_stride < batch * y_ld - (y_ld - features))
+    return fail(QIDDM_ERR_INVALID, "y_step_stride=%lld < the %lld elements of one step", (long long)y_step_stride,
+                (long long)(batch * y_ld - (y_ld - features)));
   qiddm::KScalars p = params_of(c);
   p.batch = batch;
   qiddm::QuadScalars d;

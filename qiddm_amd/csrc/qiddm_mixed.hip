@@ -60,8 +60,9 @@ int check_program(int32_t n_qubits, const qiddm_mixed_op_t* program, int32_t n_o
     if (op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
     if (op.kind == qiddm::kMixZero) continue;
     if (op.kind == qiddm::kMixAmpEmbed) {
-      if (!features || n_features < 1 || n_features > d || feat_ld < n_features)
+      if (!features || n_features < 1 || n_features > d)
         return fail(QIDDM_ERR_INVALID, "Features must be of length %lld or smaller; got length %d.", (long long)d, n_features);
+      if (feat_ld < n_features) return fail(QIDDM_ERR_INVALID, "feat_ld %lld < n_features %d", (long long)feat_ld, n_features);
       continue;
     }
     if (op.wire < 0 || op.wire >= n_qubits) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
@@ -451,6 +452,8 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
   if (batch == 0) return QIDDM_OK;
   if (!program || n_ops < 1) return fail(QIDDM_ERR_INVALID, "empty program");
   if (!out) return fail(QIDDM_ERR_INVALID, "out is NULL");
+  const int64_t width = measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits;
+  if (out_ld < width) return fail(QIDDM_ERR_INVALID, "out_ld %lld < %lld", (long long)out_ld, (long long)width);
   if (n_rows < 0 || n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
   if (n_rows > 0 && (!angle_rows || rows_ld < batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
   if (n_gates > 0 && !gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");

@@ -643,8 +643,9 @@ int qiddm_maxpool2_backward(const double* x, const double* grad_y, int64_t plane
 
 int qiddm_amp_embed_rows(const double* x, int64_t batch, int64_t x_ld, int64_t features, int32_t n_qubits, double pad_with,
                          double offset, float* v, void* stream) {
-  if (batch < 0 || features < 1 || n_qubits < 1 || n_qubits > 14 || features > ((int64_t)1 << n_qubits) || x_ld < features)
+  if (batch < 0 || features < 1 || n_qubits < 1 || n_qubits > 14 || features > ((int64_t)1 << n_qubits))
     return fail(QIDDM_ERR_INVALID, "bad amplitude-embedding geometry");
+  if (x_ld < features) return fail(QIDDM_ERR_INVALID, "x_ld=%lld < features=%lld", (long long)x_ld, (long long)features);
   if (batch == 0) return QIDDM_OK;
   if (!x || !v) return fail(QIDDM_ERR_INVALID, "x/v is NULL");
   if (batch > 0x7fffffff) return fail(QIDDM_ERR_UNSUPPORTED, "too many rows for one launch");

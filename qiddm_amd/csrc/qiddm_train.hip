@@ -188,8 +188,8 @@ int qiddm_train_step(const qiddm_circuit_t* circ, const qiddm_train_args_t* a, v
   if (!a->loss || !a->g_w_up || !a->g_b_up) return fail(QIDDM_ERR_INVALID, "loss/g_w_up/g_b_up must not be NULL");
   if (a->train_quantum && (!a->g_w_down || !a->g_b_down || !a->g_angles))
     return fail(QIDDM_ERR_INVALID, "train_quantum needs g_w_down/g_b_down/g_angles");
-  if (a->x_ld < a->pixels || a->noise_ld < a->pixels)
-    return fail(QIDDM_ERR_INVALID, "x_ld/noise_ld smaller than pixels");
+  if (a->x_ld < a->pixels) return fail(QIDDM_ERR_INVALID, "x_ld=%lld < pixels=%d", (long long)a->x_ld, a->pixels);
+  if (a->noise_ld < a->pixels) return fail(QIDDM_ERR_INVALID, "noise_ld=%lld < pixels=%d", (long long)a->noise_ld, a->pixels);
   const Geometry g = geometry(circ, a->batch, a->pixels, a->tau);
   if (!workspace || workspace_bytes < g.total)
     return fail(QIDDM_ERR_INVALID, "workspace of %lld B needed (qiddm_train_workspace_bytes), got %lld",

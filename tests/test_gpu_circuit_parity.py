@@ -159,7 +159,9 @@ def test_deep_circuit_f32_drift():
 
 
 def test_noncontiguous_and_wide_inputs():
-    """Only the first n columns are read (nn/qdense.py:427); row stride honoured."""
+    """Only the first n columns of a wider input are read (nn/qdense.py:427): in_ld = 64 > n.  The wrapper copies its
+    input to a dense tensor, so no kernel sees a padded row here; tests/test_gpu_capi_strides.py hands the kernels real
+    row strides."""
     circ, spec, x, w = _mk(6, "rz", "CZ", "probs", N=1, L=2, S=2, batch=10, seed=1, feat=64)
     got = _run(circ, x, w, "f64")
     ref = _oracle(spec, x[:, :6], w)
