@@ -574,7 +574,13 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *   QIDDM_MIX_PHASE_DAMP / _AMP_DAMP / _DEPOL   PennyLane's PhaseDamping / AmplitudeDamping /
  *                             DepolarizingChannel with probability p on `wire`
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
- * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n) float64 DEVICE arrays.            */
+ * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n) float64 DEVICE arrays.
+ * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
+ * batch / n_ops, measure (batch == 0 then returns QIDDM_OK with no pointer looked at), program (not empty, starts with a
+ * state preparation), negative n_rows / n_gates, angle_rows / rows_ld, gates, the ops one by one (kind, wire, target wire,
+ * then the operand they index: features / feat_ld / n_features, angle row, gate, probability), max_blocks (negative:
+ * refused for an empty batch as well), the outputs
+ * (out, out_ld | grad_out / gout_ld, grad_rows, grad_gates, grad_features), workspace.                   */
 enum {
   QIDDM_MIX_ZERO = 0, QIDDM_MIX_AMP_EMBED, QIDDM_MIX_PHASE, QIDDM_MIX_RY, QIDDM_MIX_GATE, QIDDM_MIX_CZ,
   QIDDM_MIX_CNOT, QIDDM_MIX_PHASE_DAMP, QIDDM_MIX_AMP_DAMP, QIDDM_MIX_DEPOL

@@ -249,37 +249,23 @@ def _declare(lib):
     lib.qiddm_qconv_unitary_forward.argtypes = [ctypes.c_int32, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
                                                 i64, ctypes.c_int32, ctypes.POINTER(BatchNormStruct), ctypes.c_int32, vp, vp,
                                                 i64, vp]
-    lib.qiddm_mixed_workspace_bytes.restype = i64
-    lib.qiddm_mixed_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, i64, ctypes.c_int32]
-    lib.qiddm_mixed_forward.restype = ctypes.c_int
-    lib.qiddm_mixed_forward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MixedOp), ctypes.c_int32, vp, i64,
-                                        ctypes.c_int32, vp, i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp,
-                                        ctypes.c_int32, ctypes.c_int32, i64, vp, i64, vp, i64, vp]
-    lib.qiddm_mixed_backward_workspace_bytes.restype = i64
-    lib.qiddm_mixed_backward_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, i64, ctypes.POINTER(MixedOp),
-                                                         ctypes.c_int32, ctypes.c_int32]
-    lib.qiddm_mixed_backward.restype = ctypes.c_int
-    lib.qiddm_mixed_backward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MixedOp), ctypes.c_int32, vp, i64,
-                                         ctypes.c_int32, vp, i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp,
-                                         ctypes.c_int32, ctypes.c_int32, i64, vp, i64, vp, vp, vp, ctypes.c_int32, vp,
-                                         i64, vp]
-    lib.qiddm_mixed_wide_workspace_bytes.restype = i64
-    lib.qiddm_mixed_wide_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, i64, ctypes.POINTER(MixedOp),
-                                                     ctypes.c_int32]
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    lib.qiddm_mixed_wide_plan.restype = ctypes.c_int
-    lib.qiddm_mixed_wide_plan.argtypes = [ctypes.c_int32, ctypes.POINTER(MixedOp), ctypes.c_int32, i32p, i32p, i32p]
-    lib.qiddm_mixed_wide_forward.restype = ctypes.c_int
-    lib.qiddm_mixed_wide_forward.argtypes = lib.qiddm_mixed_forward.argtypes
-    lib.qiddm_mixed_wide_backward_workspace_bytes.restype = i64
-    lib.qiddm_mixed_wide_backward_workspace_bytes.argtypes = lib.qiddm_mixed_wide_workspace_bytes.argtypes
-    lib.qiddm_mixed_wide_backward_plan.restype = ctypes.c_int
-    lib.qiddm_mixed_wide_backward_plan.argtypes = lib.qiddm_mixed_wide_plan.argtypes
-    lib.qiddm_mixed_wide_backward.restype = ctypes.c_int
-    lib.qiddm_mixed_wide_backward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MixedOp), ctypes.c_int32, vp,
-                                              i64, ctypes.c_int32, vp, i64, ctypes.c_int32, ctypes.c_double,
-                                              ctypes.c_double, vp, ctypes.c_int32, ctypes.c_int32, i64, vp, i64, vp, vp,
-                                              vp, vp, i64, vp]
+    i32, dbl, ops, i32p = ctypes.c_int32, ctypes.c_double, ctypes.POINTER(MixedOp), ctypes.POINTER(ctypes.c_int32)
+    # what the four compute entry points of the density-matrix executor share: n_qubits .. batch
+    mixed_call = [i32, i32, ops, i32, vp, i64, i32, vp, i64, i32, dbl, dbl, vp, i32, i32, i64]
+    tail = [vp, i64, vp]                                   # workspace, workspace_bytes, stream
+    for name, restype, argtypes in (
+            ("qiddm_mixed_workspace_bytes", i64, [i32, i32, i64, i32]),
+            ("qiddm_mixed_forward", ctypes.c_int, mixed_call + [vp, i64] + tail),
+            ("qiddm_mixed_backward_workspace_bytes", i64, [i32, i32, i64, ops, i32, i32]),
+            ("qiddm_mixed_backward", ctypes.c_int, mixed_call + [vp, i64, vp, vp, vp, i32] + tail),
+            ("qiddm_mixed_wide_workspace_bytes", i64, [i32, i32, i64, ops, i32]),
+            ("qiddm_mixed_wide_plan", ctypes.c_int, [i32, ops, i32, i32p, i32p, i32p]),
+            ("qiddm_mixed_wide_forward", ctypes.c_int, mixed_call + [vp, i64] + tail),
+            ("qiddm_mixed_wide_backward_workspace_bytes", i64, [i32, i32, i64, ops, i32]),
+            ("qiddm_mixed_wide_backward_plan", ctypes.c_int, [i32, ops, i32, i32p, i32p, i32p]),
+            ("qiddm_mixed_wide_backward", ctypes.c_int, mixed_call + [vp, i64, vp, vp, vp] + tail)):
+        getattr(lib, name).restype = restype
+        getattr(lib, name).argtypes = argtypes
     lib.qiddm_amp_embed_rows.restype = ctypes.c_int
     lib.qiddm_amp_embed_rows.argtypes = [vp, i64, i64, i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp, vp]
     lib.qiddm_prob_post.restype = ctypes.c_int

@@ -2,6 +2,10 @@
 // "hardware-noise study"); device code in qsim_mixed.h (n <= 8, one workgroup per sample) and qsim_mixed_wide.h
 // (n = 7..10, tile-fused sweeps) and qsim_mixed_wide_adjoint.h (their reverse sweep), with the planner that cuts a
 // program into sweeps.
+// Host side: the four compute entry points share their arguments from n_qubits to batch.  Each puts them into a
+// MixedCall, has check_call() validate them (one order for all four, stated in the header), and then reads as a list of
+// steps: outputs, geometry (and plan), workspace, upload(), make_scalars(), for_dtype launch.  The *_workspace_bytes
+// functions check sizes with check_sizes() and the two *_plan functions validate through the planner alone.
 #include "capi_common.h"
 
 #include <hip/hip_runtime.h>
@@ -23,84 +27,198 @@ using qiddm_capi::kMaxLds;
 using qiddm_capi::launch;
 using qiddm_capi::launched;
 
-constexpr int kMixedMaxQubits = 8;
+static_assert(sizeof(qiddm::MixedOp) == sizeof(qiddm_mixed_op_t), "program layout");
+
+inline int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
+inline int64_t slab_bytes(int32_t n, int32_t dtype) { return ((int64_t)1 << (2 * n)) * (dtype == QIDDM_F32 ? 8 : 16); }
+inline int64_t program_bytes(int32_t n_ops) { return round256((int64_t)n_ops * (int64_t)sizeof(qiddm::MixedOp)); }
+
+inline bool is_prep(int kind) { return kind == qiddm::kMixZero || kind == qiddm::kMixAmpEmbed; }
+inline bool is_diag(int kind) {
+  return kind == qiddm::kMixPhase || kind == qiddm::kMixCZ || kind == qiddm::kMixPhaseDamp;
+}
+inline bool is_channel(int kind) {
+  return kind == qiddm::kMixPhaseDamp || kind == qiddm::kMixAmpDamp || kind == qiddm::kMixDepol;
+}
+
+// ---- argument checks ---------------------------------------------------------------------------------------------------
+struct Engine {
+  const char* name;
+  int min_qubits, max_qubits;
+};
+constexpr Engine kOneWorkgroup{"", 1, 8}, kTileFused{"tile-fused ", 7, 10};
+
+int check_wires(int32_t n, const Engine& e) {
+  if (n < e.min_qubits || n > e.max_qubits)
+    return fail(QIDDM_ERR_UNSUPPORTED, "%sdensity-matrix execution needs %d <= n_qubits <= %d (got %d)", e.name,
+                e.min_qubits, e.max_qubits, n);
+  return QIDDM_OK;
+}
+
+// what a workspace size depends on: checked by the *_workspace_bytes functions and, first of all, by check_call
+int check_sizes(int32_t n, int32_t dtype, int64_t batch, int32_t n_ops, const Engine& e) {
+  if (const int rc = check_wires(n, e); rc != QIDDM_OK) return rc;
+  if (dtype != QIDDM_F32 && dtype != QIDDM_F64) return fail(QIDDM_ERR_INVALID, "unknown dtype %d", dtype);
+  if (batch < 0 || n_ops < 0) return fail(QIDDM_ERR_INVALID, "negative batch / n_ops");
+  return QIDDM_OK;
+}
+
+int check_max_blocks(int32_t max_blocks) {
+  if (max_blocks < 0) return fail(QIDDM_ERR_INVALID, "negative max_blocks %d", max_blocks);
+  return QIDDM_OK;
+}
+
+// a program has ops and starts by preparing the state (validator and planners)
+int check_program_start(const qiddm_mixed_op_t* program, int32_t n_ops) {
+  if (n_ops < 1 || !program) return fail(QIDDM_ERR_INVALID, "empty program");
+  if (!is_prep(program[0].kind)) return fail(QIDDM_ERR_INVALID, "the program must start by preparing the state");
+  return QIDDM_OK;
+}
+
+// kind, wire and target wire of op i: all the planner reads of an op, and the first thing the validator checks of it
+int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i) {
+  if (op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
+  if (is_prep(op.kind)) return QIDDM_OK;
+  if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
+  if ((op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) && (op.a < 0 || op.a >= n || op.a == op.wire))
+    return fail(QIDDM_ERR_INVALID, "op %d: bad target wire %d", i, op.a);
+  return QIDDM_OK;
+}
+
+// the arguments the four compute entry points share
+struct MixedCall {
+  int32_t n_qubits, dtype;
+  const qiddm_mixed_op_t* program;
+  int32_t n_ops;
+  const double* angle_rows;
+  int64_t rows_ld;
+  int32_t n_rows;
+  const double* features;
+  int64_t feat_ld;
+  int32_t n_features;
+  double enc_offset, pad_with;
+  const double* gates;
+  int32_t n_gates, measure;
+  int64_t batch;
+  int64_t width() const { return measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits; }  // of out / grad_out
+};
+
+// Everything the compute entry points check about a MixedCall, in the order include/qiddm_hip.h states: wires, dtype,
+// negative batch / n_ops, measure; [an empty batch is QIDDM_OK here: nothing further is looked at, the caller returns];
+// program, n_rows / n_gates, angle_rows / rows_ld, gates, then op by op against the arguments it indexes.
+// *embeds: the program has an AMP_EMBED.
+int check_call(const MixedCall& c, const Engine& e, bool* embeds) {
+  int rc = check_sizes(c.n_qubits, c.dtype, c.batch, c.n_ops, e);
+  if (rc != QIDDM_OK) return rc;
+  if (c.measure != QIDDM_MEAS_PROBS && c.measure != QIDDM_MEAS_EXPZ) return fail(QIDDM_ERR_INVALID, "unknown measure %d", c.measure);
+  if (c.batch == 0) return QIDDM_OK;
+  if ((rc = check_program_start(c.program, c.n_ops)) != QIDDM_OK) return rc;
+  if (c.n_rows < 0 || c.n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
+  if (c.n_rows > 0 && (!c.angle_rows || c.rows_ld < c.batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
+  if (c.n_gates > 0 && !c.gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");
+  const int64_t d = (int64_t)1 << c.n_qubits;
+  *embeds = false;
+  for (int i = 0; i < c.n_ops; ++i) {
+    const qiddm_mixed_op_t& op = c.program[i];
+    if ((rc = check_op_wires(c.n_qubits, op, i)) != QIDDM_OK) return rc;
+    switch (op.kind) {
+      case qiddm::kMixAmpEmbed:
+        if (!c.features || c.n_features < 1 || c.n_features > d)
+          return fail(QIDDM_ERR_INVALID, "Features must be of length %lld or smaller; got length %d.", (long long)d, c.n_features);
+        if (c.feat_ld < c.n_features) return fail(QIDDM_ERR_INVALID, "feat_ld %lld < n_features %d", (long long)c.feat_ld, c.n_features);
+        *embeds = true;
+        break;
+      case qiddm::kMixPhase:
+      case qiddm::kMixRY:
+        if (op.a >= c.n_rows) return fail(QIDDM_ERR_INVALID, "op %d: angle row %d out of range", i, op.a);
+        break;
+      case qiddm::kMixGate:
+        if (op.a < 0 || op.a >= c.n_gates) return fail(QIDDM_ERR_INVALID, "op %d: gate %d out of range", i, op.a);
+        break;
+      case qiddm::kMixPhaseDamp:
+      case qiddm::kMixAmpDamp:
+      case qiddm::kMixDepol:
+        if (!(op.p >= 0.0 && op.p <= 1.0))
+          return fail(QIDDM_ERR_INVALID, "op %d: channel probability %g outside [0, 1]", i, op.p);
+        break;
+      default:
+        break;
+    }
+  }
+  return QIDDM_OK;
+}
+
+int check_forward_outputs(const MixedCall& c, const double* out, int64_t out_ld) {
+  if (!out) return fail(QIDDM_ERR_INVALID, "out is NULL");
+  if (out_ld < c.width()) return fail(QIDDM_ERR_INVALID, "out_ld %lld < %lld", (long long)out_ld, (long long)c.width());
+  return QIDDM_OK;
+}
+
+int check_backward_outputs(const MixedCall& c, bool embeds, const double* grad_out, int64_t gout_ld,
+                           const double* grad_rows, const double* grad_gates, const double* grad_features) {
+  if (!grad_out || gout_ld < c.width())
+    return fail(QIDDM_ERR_INVALID, "grad_out missing or gout_ld < %lld", (long long)c.width());
+  if (c.n_rows > 0 && !grad_rows) return fail(QIDDM_ERR_INVALID, "grad_rows is NULL");
+  if (c.n_gates > 0 && !grad_gates) return fail(QIDDM_ERR_INVALID, "grad_gates is NULL");
+  if (embeds && !grad_features) return fail(QIDDM_ERR_INVALID, "grad_features is NULL");
+  return QIDDM_OK;
+}
+
+// ---- what the entry points share after the checks ----------------------------------------------------------------------
+// `n_ops`, `n_features`: as the kernels see them (the tile-fused backward runs the live ops only; a backward without
+// AMP_EMBED has no features)
+qiddm::MixedScalars make_scalars(const MixedCall& c, int32_t n_ops, int32_t n_features, int64_t out_ld, bool in_lds) {
+  qiddm::MixedScalars m{};
+  m.n = c.n_qubits;
+  m.n_ops = n_ops;
+  m.measure = c.measure;
+  m.n_features = n_features;
+  m.batch = c.batch;
+  m.rows_ld = c.rows_ld;
+  m.feat_ld = c.feat_ld;
+  m.out_ld = out_ld;
+  m.enc_offset = c.enc_offset;
+  m.pad_with = c.pad_with;
+  m.slab_in_lds = in_lds ? 1 : 0;
+  return m;
+}
+
+// the program (or the whole head) to the front of the workspace.  `src` is pageable: the copy is staged before the call
+// returns, so it may go out of scope
+int upload(unsigned char* ws, const void* src, size_t bytes, hipStream_t st) {
+  const hipError_t e = hipMemcpyAsync(ws, src, bytes, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "program upload failed: %s", hipGetErrorString(e));
+  return QIDDM_OK;
+}
+
+// ---- one-workgroup engine (qsim_mixed.h): geometry; the arguments have been checked --------------------------------------
 constexpr int64_t kMixedMaxBlocks = 256;
 constexpr size_t kMixedLdsSlab = 128 * 1024;
 
 struct MixedGeometry {
-  int64_t blocks, slab_bytes, off_prog, off_slabs, total;
+  int64_t blocks, slab_bytes, off_slabs, total;  // the program sits at offset 0
   bool in_lds;
 };
 
-int mixed_geometry(int32_t n, int32_t dtype, int64_t batch, int32_t n_ops, MixedGeometry* g) {
-  if (n < 1 || n > kMixedMaxQubits)
-    return fail(QIDDM_ERR_UNSUPPORTED, "density-matrix execution needs 1 <= n_qubits <= %d (got %d)", kMixedMaxQubits, n);
-  if (dtype != QIDDM_F32 && dtype != QIDDM_F64) return fail(QIDDM_ERR_INVALID, "unknown dtype %d", dtype);
-  if (batch < 0 || n_ops < 0) return fail(QIDDM_ERR_INVALID, "negative batch / n_ops");
-  g->slab_bytes = ((int64_t)1 << (2 * n)) * (dtype == QIDDM_F32 ? 8 : 16);
-  g->in_lds = (size_t)g->slab_bytes <= kMixedLdsSlab;
-  g->blocks = batch < kMixedMaxBlocks ? batch : kMixedMaxBlocks;
-  if (g->blocks < 1) g->blocks = 1;
-  g->off_prog = 0;
-  g->off_slabs = ((int64_t)n_ops * (int64_t)sizeof(qiddm::MixedOp) + 255) / 256 * 256;
-  g->total = g->off_slabs + (g->in_lds ? 0 : g->blocks * g->slab_bytes);
-  return QIDDM_OK;
-}
-
-static_assert(sizeof(qiddm::MixedOp) == sizeof(qiddm_mixed_op_t), "program layout");
-
-// the ops of a program, checked against the arguments they index (forward and backward)
-int check_program(int32_t n_qubits, const qiddm_mixed_op_t* program, int32_t n_ops, int32_t n_rows,
-                  const double* features, int64_t feat_ld, int32_t n_features, int32_t n_gates) {
-  if (program[0].kind != qiddm::kMixZero && program[0].kind != qiddm::kMixAmpEmbed)
-    return fail(QIDDM_ERR_INVALID, "the program must start by preparing the state");
-  const int64_t d = (int64_t)1 << n_qubits;
-  for (int i = 0; i < n_ops; ++i) {
-    const qiddm_mixed_op_t& op = program[i];
-    if (op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
-    if (op.kind == qiddm::kMixZero) continue;
-    if (op.kind == qiddm::kMixAmpEmbed) {
-      if (!features || n_features < 1 || n_features > d)
-        return fail(QIDDM_ERR_INVALID, "Features must be of length %lld or smaller; got length %d.", (long long)d, n_features);
-      if (feat_ld < n_features) return fail(QIDDM_ERR_INVALID, "feat_ld %lld < n_features %d", (long long)feat_ld, n_features);
-      continue;
-    }
-    if (op.wire < 0 || op.wire >= n_qubits) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
-    switch (op.kind) {
-      case qiddm::kMixPhase:
-      case qiddm::kMixRY:
-        if (op.a >= n_rows) return fail(QIDDM_ERR_INVALID, "op %d: angle row %d out of range", i, op.a);
-        break;
-      case qiddm::kMixGate:
-        if (op.a < 0 || op.a >= n_gates) return fail(QIDDM_ERR_INVALID, "op %d: gate %d out of range", i, op.a);
-        break;
-      case qiddm::kMixCZ:
-      case qiddm::kMixCNOT:
-        if (op.a < 0 || op.a >= n_qubits || op.a == op.wire)
-          return fail(QIDDM_ERR_INVALID, "op %d: bad target wire %d", i, op.a);
-        break;
-      default:
-        if (!(op.p >= 0.0 && op.p <= 1.0))
-          return fail(QIDDM_ERR_INVALID, "op %d: channel probability %g outside [0, 1]", i, op.p);
-    }
-  }
-  return QIDDM_OK;
+MixedGeometry mixed_geometry(int32_t n, int32_t dtype, int64_t batch, int32_t n_ops) {
+  MixedGeometry g;
+  g.slab_bytes = slab_bytes(n, dtype);
+  g.in_lds = (size_t)g.slab_bytes <= kMixedLdsSlab;
+  g.blocks = batch < kMixedMaxBlocks ? batch : kMixedMaxBlocks;
+  if (g.blocks < 1) g.blocks = 1;
+  g.off_slabs = program_bytes(n_ops);
+  g.total = g.off_slabs + (g.in_lds ? 0 : g.blocks * g.slab_bytes);
+  return g;
 }
 
 // The backward's workspace per workgroup: rho and Lambda unless both fit in LDS, then one snapshot of rho for every
 // channel and every state preparation after the first op.
 int mixed_backward_geometry(int32_t n, int32_t dtype, int64_t batch, const qiddm_mixed_op_t* program, int32_t n_ops,
                             int32_t max_blocks, MixedGeometry* g, int32_t* n_snaps) {
-  int rc = mixed_geometry(n, dtype, batch, n_ops, g);
-  if (rc != QIDDM_OK) return rc;
-  if (max_blocks < 0) return fail(QIDDM_ERR_INVALID, "negative max_blocks %d", max_blocks);
   if (n_ops > 0 && !program) return fail(QIDDM_ERR_INVALID, "program is NULL");
+  *g = mixed_geometry(n, dtype, batch, n_ops);
   int32_t snaps = 0;
-  for (int i = 0; i < n_ops; ++i) {
-    const int k = program[i].kind;
-    snaps += (k == qiddm::kMixPhaseDamp || k == qiddm::kMixAmpDamp || k == qiddm::kMixDepol ||
-              (i > 0 && (k == qiddm::kMixZero || k == qiddm::kMixAmpEmbed))) ? 1 : 0;
-  }
+  for (int i = 0; i < n_ops; ++i) snaps += (is_channel(program[i].kind) || (i > 0 && is_prep(program[i].kind))) ? 1 : 0;
   *n_snaps = snaps;
   g->in_lds = (size_t)(2 * g->slab_bytes) <= kMixedLdsSlab;
   if (max_blocks > 0 && g->blocks > max_blocks) g->blocks = max_blocks;
@@ -108,28 +226,47 @@ int mixed_backward_geometry(int32_t n, int32_t dtype, int64_t batch, const qiddm
   return QIDDM_OK;
 }
 
+int check_workspace(const void* workspace, int64_t workspace_bytes, int64_t need, const char* sizer) {
+  if (!workspace || workspace_bytes < need)
+    return fail(QIDDM_ERR_INVALID, "workspace of %lld B needed (%s), got %lld", (long long)need, sizer, (long long)workspace_bytes);
+  return QIDDM_OK;
+}
+
 // ---- tile-fused engine (qsim_mixed_wide.h): geometry and planner ------------------------------------------------------
-constexpr int kWideMinQubits = 7, kWideMaxQubits = 10;
 constexpr int64_t kWideSlabBudget = (int64_t)1 << 30;  // resident slabs per launch: at most 1 GiB
 
 struct WideGeometry {
   int64_t slab_bytes, resident, off_norms, off_slabs, total;
 };
 
-int wide_geometry(int32_t n, int32_t dtype, int64_t batch, int32_t n_ops, WideGeometry* g) {
-  if (n < kWideMinQubits || n > kWideMaxQubits)
-    return fail(QIDDM_ERR_UNSUPPORTED, "tile-fused density-matrix execution needs %d <= n_qubits <= %d (got %d)",
-                kWideMinQubits, kWideMaxQubits, n);
-  if (dtype != QIDDM_F32 && dtype != QIDDM_F64) return fail(QIDDM_ERR_INVALID, "unknown dtype %d", dtype);
-  if (batch < 0 || n_ops < 0) return fail(QIDDM_ERR_INVALID, "negative batch / n_ops");
-  g->slab_bytes = ((int64_t)1 << (2 * n)) * (dtype == QIDDM_F32 ? 8 : 16);
-  const int64_t cap = kWideSlabBudget / g->slab_bytes;
-  g->resident = batch < cap ? batch : cap;
-  if (g->resident < 1) g->resident = 1;
-  g->off_norms = ((int64_t)n_ops * (int64_t)sizeof(qiddm::MixedOp) + 255) / 256 * 256;
-  g->off_slabs = g->off_norms + (g->resident * 8 + 255) / 256 * 256;
-  g->total = g->off_slabs + g->resident * g->slab_bytes;
+WideGeometry wide_geometry(int32_t n, int32_t dtype, int64_t batch, int32_t n_ops) {
+  WideGeometry g;
+  g.slab_bytes = slab_bytes(n, dtype);
+  const int64_t cap = kWideSlabBudget / g.slab_bytes;
+  g.resident = batch < cap ? batch : cap;
+  if (g.resident < 1) g.resident = 1;
+  g.off_norms = program_bytes(n_ops);
+  g.off_slabs = g.off_norms + round256(g.resident * 8);
+  g.total = g.off_slabs + g.resident * g.slab_bytes;
+  return g;
+}
+
+// The samples resident in the caller's workspace: a smaller one than `total` (what `sizer` returns) is accepted down to
+// one sample's worth, fewer samples are then resident per chunk.
+int wide_resident(const void* workspace, int64_t workspace_bytes, int64_t head, int64_t per_sample, int64_t cap,
+                  int64_t total, const char* sizer, int64_t* resident) {
+  *resident = workspace ? (workspace_bytes - head) / per_sample : 0;
+  if (*resident > cap) *resident = cap;
+  if (*resident < 1)
+    return fail(QIDDM_ERR_INVALID, "workspace of at least %lld B needed (%s: %lld), got %lld", (long long)(head + per_sample),
+                sizer, (long long)total, (long long)workspace_bytes);
   return QIDDM_OK;
+}
+
+// what the planners check before they read an op
+int check_plan_input(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops) {
+  const int rc = check_wires(n, kTileFused);
+  return rc != QIDDM_OK ? rc : check_program_start(program, n_ops);
 }
 
 struct WidePlan {
@@ -140,14 +277,6 @@ struct WidePlan {
   int32_t n_nondiag = 0;
 };
 
-inline bool wide_is_prep(int kind) { return kind == qiddm::kMixZero || kind == qiddm::kMixAmpEmbed; }
-inline bool wide_is_diag(int kind) {
-  return kind == qiddm::kMixPhase || kind == qiddm::kMixCZ || kind == qiddm::kMixPhaseDamp;
-}
-inline bool wide_is_channel(int kind) {
-  return kind == qiddm::kMixPhaseDamp || kind == qiddm::kMixAmpDamp || kind == qiddm::kMixDepol;
-}
-
 // Cuts a program into segments, each executable by one sweep over tiles of six wires.  Two ops commute when they share
 // no wire or both act diagonally on vec(rho); an op joins the open segment only if every earlier op that does not
 // commute with it is placed (so executing segment after segment, each in program order, is a reordering of commuting
@@ -156,30 +285,20 @@ inline bool wide_is_channel(int kind) {
 // op always fits an empty segment, so every segment places at least one op, and at least one that is not diagonal.
 // `split_channels` (the reverse sweep's plan): a segment takes channels only or no channel at all -- an op of the other
 // sort waits like one whose wires do not fit -- so that the state in front of a channel is a whole slab.
+// Validates what it reads (wires, program start, kind and wires of every op): the *_plan functions come here directly.
 int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WidePlan* plan,
                     bool split_channels = false) {
-  if (n < kWideMinQubits || n > kWideMaxQubits)
-    return fail(QIDDM_ERR_UNSUPPORTED, "tile-fused density-matrix execution needs %d <= n_qubits <= %d (got %d)",
-                kWideMinQubits, kWideMaxQubits, n);
-  if (n_ops < 1 || !program) return fail(QIDDM_ERR_INVALID, "empty program");
-  if (!wide_is_prep(program[0].kind)) return fail(QIDDM_ERR_INVALID, "the program must start by preparing the state");
+  int rc = check_plan_input(n, program, n_ops);
+  if (rc != QIDDM_OK) return rc;
   const uint32_t all = (1u << n) - 1u;
   std::vector<uint32_t> wires(n_ops);
   plan->n_nondiag = 0;
   for (int i = 0; i < n_ops; ++i) {
     const qiddm_mixed_op_t& op = program[i];
-    if (op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
-    if (wide_is_prep(op.kind)) {
-      wires[i] = all;
-    } else {
-      if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
-      wires[i] = 1u << op.wire;
-      if (op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) {
-        if (op.a < 0 || op.a >= n || op.a == op.wire) return fail(QIDDM_ERR_INVALID, "op %d: bad target wire %d", i, op.a);
-        wires[i] |= 1u << op.a;
-      }
-    }
-    plan->n_nondiag += wide_is_diag(op.kind) ? 0 : 1;
+    if ((rc = check_op_wires(n, op, i)) != QIDDM_OK) return rc;
+    wires[i] = is_prep(op.kind) ? all : 1u << op.wire;
+    if (op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) wires[i] |= 1u << op.a;
+    plan->n_nondiag += is_diag(op.kind) ? 0 : 1;
   }
   plan->order.clear();
   plan->order.reserve(n_ops);
@@ -201,17 +320,17 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
       const uint32_t w = wires[i];
       bool ok;
       int extra = 0;
-      if (wide_is_diag(kind)) {
+      if (is_diag(kind)) {
         ok = !(w & blocked_nondiag);
-      } else if (wide_is_prep(kind)) {
+      } else if (is_prep(kind)) {
         ok = !blocked_any && empty;
       } else {
         extra = __builtin_popcount(w & ~set);
         ok = !(w & blocked_any) && count + extra <= qiddm::kWideTileWires;
       }
-      if (split_channels && !empty && wide_is_channel(kind) != channels) ok = false;
+      if (split_channels && !empty && is_channel(kind) != channels) ok = false;
       if (ok) {
-        if (empty) channels = wide_is_channel(kind);
+        if (empty) channels = is_channel(kind);
         placed[i] = 1;
         plan->order.push_back(i);
         plan->op_segment[i] = (int32_t)plan->segments.size();
@@ -222,7 +341,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
         empty = false;
       } else {
         blocked_any |= w;
-        if (!wide_is_diag(kind)) blocked_nondiag |= w;
+        if (!is_diag(kind)) blocked_nondiag |= w;
       }
     }
     while (first < n_ops && placed[first]) ++first;
@@ -249,9 +368,8 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
 }
 
 template <typename T>
-int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resident, unsigned char* ws,
-                      const double* angle_rows, const double* features, const double* gates, double* out,
-                      qiddm::MixedScalars m, bool embeds, hipStream_t st) {
+int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resident, unsigned char* ws, const MixedCall& c,
+                      double* out, qiddm::MixedScalars m, bool embeds, hipStream_t st) {
   const size_t smem = (size_t)qiddm::kWideTile * sizeof(qiddm::V2<T>);
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
   double* norms = reinterpret_cast<double*>(ws + g.off_norms);
@@ -259,10 +377,10 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
   const unsigned tiles = 1u << (2 * m.n - qiddm::kWideLocalBits);
   for (int64_t s0 = 0; s0 < m.batch; s0 += resident) {
     const unsigned chunk = (unsigned)(m.batch - s0 < resident ? m.batch - s0 : resident);
-    if (embeds) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, features, norms, m, s0);
+    if (embeds) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, c.features, norms, m, s0);
     for (const qiddm::WideSegment& sg : plan.segments) {   // (the sweeps ask for the LDS they use, no more)
       const int rc = launch<qiddm::mixed_wide_sweep<T>>(smem, dim3(tiles, chunk), dim3(256), smem, st, "mixed_wide_sweep",
-                                                       prog, angle_rows, features, gates, norms, slabs, m, sg, s0,
+                                                       prog, c.angle_rows, c.features, c.gates, norms, slabs, m, sg, s0,
                                                        (int64_t)0);
       if (rc != QIDDM_OK) return rc;
     }
@@ -288,18 +406,14 @@ struct WideBwdPlan {
 };
 
 int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WideBwdPlan* bp) {
-  if (n < kWideMinQubits || n > kWideMaxQubits)
-    return fail(QIDDM_ERR_UNSUPPORTED, "tile-fused density-matrix execution needs %d <= n_qubits <= %d (got %d)",
-                kWideMinQubits, kWideMaxQubits, n);
-  if (n_ops < 1 || !program) return fail(QIDDM_ERR_INVALID, "empty program");
-  if (!wide_is_prep(program[0].kind)) return fail(QIDDM_ERR_INVALID, "the program must start by preparing the state");
+  int rc = check_plan_input(n, program, n_ops);
+  if (rc != QIDDM_OK) return rc;
   bp->live_begin = 0;
   for (int i = 0; i < n_ops; ++i)
-    if (wide_is_prep(program[i].kind)) bp->live_begin = i;
+    if (is_prep(program[i].kind)) bp->live_begin = i;
   bp->n_live = n_ops - bp->live_begin;
   const qiddm_mixed_op_t* live = program + bp->live_begin;
-  const int rc = plan_mixed_wide(n, live, bp->n_live, &bp->plan, true);
-  if (rc != QIDDM_OK) return rc;
+  if ((rc = plan_mixed_wide(n, live, bp->n_live, &bp->plan, true)) != QIDDM_OK) return rc;
   const int n_seg = (int)bp->plan.segments.size();
   bp->replay_end = n_seg;
   while (bp->replay_end > 0 && bp->plan.seg_channel[bp->replay_end - 1]) --bp->replay_end;
@@ -335,8 +449,6 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
   return QIDDM_OK;
 }
 
-inline int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
-
 // Workspace: [sorted live program | slot per op | params | group_begin] then, per resident sample, |v|^2 and
 // Re(Lambda_0) v (AMP_EMBED), the tile partials, and 2 + n_snaps slabs.
 struct WideBwdGeometry {
@@ -344,29 +456,27 @@ struct WideBwdGeometry {
   int64_t off_slot, off_params, off_groups, head, total;
 };
 
-int wide_backward_geometry(int32_t n, int32_t dtype, int64_t batch, const WideBwdPlan& bp, WideBwdGeometry* g) {
-  if (dtype != QIDDM_F32 && dtype != QIDDM_F64) return fail(QIDDM_ERR_INVALID, "unknown dtype %d", dtype);
-  if (batch < 0) return fail(QIDDM_ERR_INVALID, "negative batch");
-  g->slab_bytes = ((int64_t)1 << (2 * n)) * (dtype == QIDDM_F32 ? 8 : 16);
-  g->aux_bytes = round256(8 * (1 + ((int64_t)1 << n)));
-  g->part_bytes = round256((int64_t)bp.n_slots * ((int64_t)1 << (2 * n - qiddm::kWideLocalBits)) * 8);
-  g->per_sample = g->aux_bytes + g->part_bytes + (2 + (int64_t)bp.n_snaps) * g->slab_bytes;
-  const int64_t cap = kWideSlabBudget / g->per_sample;
-  g->resident = batch < cap ? batch : cap;
-  if (g->resident < 1) g->resident = 1;
-  g->off_slot = round256((int64_t)bp.n_live * (int64_t)sizeof(qiddm::MixedOp));
-  g->off_params = g->off_slot + round256((int64_t)bp.n_live * 4);
-  g->off_groups = g->off_params + round256((int64_t)bp.params.size() * (int64_t)sizeof(qiddm::WideParam));
-  g->head = g->off_groups + round256((int64_t)bp.group_begin.size() * 4);
-  g->total = g->head + g->resident * g->per_sample;
-  return QIDDM_OK;
+WideBwdGeometry wide_backward_geometry(int32_t n, int32_t dtype, int64_t batch, const WideBwdPlan& bp) {
+  WideBwdGeometry g;
+  g.slab_bytes = slab_bytes(n, dtype);
+  g.aux_bytes = round256(8 * (1 + ((int64_t)1 << n)));
+  g.part_bytes = round256((int64_t)bp.n_slots * ((int64_t)1 << (2 * n - qiddm::kWideLocalBits)) * 8);
+  g.per_sample = g.aux_bytes + g.part_bytes + (2 + (int64_t)bp.n_snaps) * g.slab_bytes;
+  const int64_t cap = kWideSlabBudget / g.per_sample;
+  g.resident = batch < cap ? batch : cap;
+  if (g.resident < 1) g.resident = 1;
+  g.off_slot = program_bytes(bp.n_live);
+  g.off_params = g.off_slot + round256((int64_t)bp.n_live * 4);
+  g.off_groups = g.off_params + round256((int64_t)bp.params.size() * (int64_t)sizeof(qiddm::WideParam));
+  g.head = g.off_groups + round256((int64_t)bp.group_begin.size() * 4);
+  g.total = g.head + g.resident * g.per_sample;
+  return g;
 }
 
 template <typename T>
 int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, int64_t resident, unsigned char* ws,
-                               const double* angle_rows, const double* features, const double* gates,
-                               const double* grad_out, double* grad_rows, double* grad_gates, double* grad_features,
-                               qiddm::MixedScalars m, qiddm::WideBwdScalars b, int32_t n_gates, hipStream_t st) {
+                               const MixedCall& c, const double* grad_out, double* grad_rows, double* grad_gates,
+                               double* grad_features, qiddm::MixedScalars m, qiddm::WideBwdScalars b, hipStream_t st) {
   using C = qiddm::V2<T>;
   const size_t tile_bytes = (size_t)qiddm::kWideTile * sizeof(C);
   const dim3 block(256);
@@ -389,12 +499,12 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
   const int n_groups = (int)bp.group_begin.size() - 1;
   for (int64_t s0 = 0; s0 < m.batch; s0 += resident) {
     const unsigned chunk = (unsigned)(m.batch - s0 < resident ? m.batch - s0 : resident);
-    if (bp.embed_live) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, features, norms, m, s0);
+    if (bp.embed_live) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, c.features, norms, m, s0);
     int cur = 0;
     for (int s = 0; s < bp.replay_end; ++s) {
       const bool ch = bp.plan.seg_channel[s] != 0;
       rc = launch<qiddm::mixed_wide_sweep<T>>(tile_bytes, dim3(tiles, chunk), block, tile_bytes, st, "mixed_wide_sweep", prog,
-                                              angle_rows, features, gates, norms, slabs + (size_t)cur * set_stride, m,
+                                              c.angle_rows, c.features, c.gates, norms, slabs + (size_t)cur * set_stride, m,
                                               bp.plan.segments[s], s0, (int64_t)(ch ? set_stride : 0));
       if (rc != QIDDM_OK) return rc;
       cur += ch ? 1 : 0;
@@ -404,7 +514,7 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
     for (int s = n_seg - 1; s >= 0; --s) {
       if (!bp.plan.seg_channel[s]) {
         rc = launch<qiddm::mixed_wide_reverse_sweep<T>>(2 * tile_bytes, dim3(tiles, chunk), block, 2 * tile_bytes, st,
-                                                        "mixed_wide_reverse_sweep", prog, slot, angle_rows, gates, grad_out,
+                                                        "mixed_wide_reverse_sweep", prog, slot, c.angle_rows, c.gates, grad_out,
                                                         slabs + (size_t)cur * set_stride, lam, partials, m,
                                                         bp.plan.segments[s], bs, s0);
       } else {
@@ -417,12 +527,12 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
       bs.seed = 0;
     }
     if (bp.embed_live) {
-      hipLaunchKernelGGL(qiddm::mixed_wide_embed_matvec<T>, dim3(D / 4, chunk), dim3(256), 0, st, lam, features, lv, m, s0);
-      hipLaunchKernelGGL(qiddm::mixed_wide_embed_grad, dim3(chunk), dim3(256), 0, st, features, lv, grad_features, m, s0);
+      hipLaunchKernelGGL(qiddm::mixed_wide_embed_matvec<T>, dim3(D / 4, chunk), dim3(256), 0, st, lam, c.features, lv, m, s0);
+      hipLaunchKernelGGL(qiddm::mixed_wide_embed_grad, dim3(chunk), dim3(256), 0, st, c.features, lv, grad_features, m, s0);
     }
     if (n_groups > 0)
       hipLaunchKernelGGL(qiddm::mixed_wide_grad_finalize, dim3((n_groups + 3) / 4, chunk), dim3(256), 0, st, params,
-                         group_begin, n_groups, gates, partials, grad_rows, grad_gates, bp.n_slots, n_gates, tiles,
+                         group_begin, n_groups, c.gates, partials, grad_rows, grad_gates, bp.n_slots, c.n_gates, tiles,
                          m.batch, s0);
     if (rc = launched("mixed_wide backward"); rc != QIDDM_OK) return rc;
   }
@@ -434,10 +544,9 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
 extern "C" {
 
 int64_t qiddm_mixed_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, int32_t n_ops) {
-  MixedGeometry g;
-  const int rc = mixed_geometry(n_qubits, dtype, batch, n_ops, &g);
+  const int rc = check_sizes(n_qubits, dtype, batch, n_ops, kOneWorkgroup);
   if (rc != QIDDM_OK) return rc;
-  return g.total;
+  return mixed_geometry(n_qubits, dtype, batch, n_ops).total;
 }
 
 int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t* program, int32_t n_ops,
@@ -445,41 +554,20 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
                         int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with, const double* gates,
                         int32_t n_gates, int32_t measure, int64_t batch, double* out, int64_t out_ld, void* workspace,
                         int64_t workspace_bytes, void* stream) {
-  MixedGeometry g;
-  int rc = mixed_geometry(n_qubits, dtype, batch, n_ops, &g);
-  if (rc != QIDDM_OK) return rc;
-  if (measure != QIDDM_MEAS_PROBS && measure != QIDDM_MEAS_EXPZ) return fail(QIDDM_ERR_INVALID, "unknown measure %d", measure);
-  if (batch == 0) return QIDDM_OK;
-  if (!program || n_ops < 1) return fail(QIDDM_ERR_INVALID, "empty program");
-  if (!out) return fail(QIDDM_ERR_INVALID, "out is NULL");
-  const int64_t width = measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits;
-  if (out_ld < width) return fail(QIDDM_ERR_INVALID, "out_ld %lld < %lld", (long long)out_ld, (long long)width);
-  if (n_rows < 0 || n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
-  if (n_rows > 0 && (!angle_rows || rows_ld < batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
-  if (n_gates > 0 && !gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");
-  rc = check_program(n_qubits, program, n_ops, n_rows, features, feat_ld, n_features, n_gates);
-  if (rc != QIDDM_OK) return rc;
-  if (!workspace || workspace_bytes < g.total)
-    return fail(QIDDM_ERR_INVALID, "workspace of %lld B needed (qiddm_mixed_workspace_bytes), got %lld",
-                (long long)g.total, (long long)workspace_bytes);
+  const MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+                    enc_offset, pad_with, gates, n_gates, measure, batch};
+  bool embeds = false;
+  int rc = check_call(c, kOneWorkgroup, &embeds);
+  if (rc != QIDDM_OK || batch == 0) return rc;
+  if ((rc = check_forward_outputs(c, out, out_ld)) != QIDDM_OK) return rc;
+  const MixedGeometry g = mixed_geometry(n_qubits, dtype, batch, n_ops);
+  if ((rc = check_workspace(workspace, workspace_bytes, g.total, "qiddm_mixed_workspace_bytes")) != QIDDM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  hipError_t e = hipMemcpyAsync(ws + g.off_prog, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "program upload failed: %s", hipGetErrorString(e));
-  qiddm::MixedScalars m{};
-  m.n = n_qubits;
-  m.n_ops = n_ops;
-  m.measure = measure;
-  m.n_features = n_features;
-  m.batch = batch;
-  m.rows_ld = rows_ld;
-  m.feat_ld = feat_ld;
-  m.out_ld = out_ld;
-  m.enc_offset = enc_offset;
-  m.pad_with = pad_with;
-  m.slab_in_lds = g.in_lds ? 1 : 0;
+  if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  const qiddm::MixedScalars m = make_scalars(c, n_ops, n_features, out_ld, g.in_lds);
   const size_t smem = g.in_lds ? (size_t)g.slab_bytes : 0;
-  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws + g.off_prog);
+  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     return launch<qiddm::mixed_kernel<T>>(kMaxLds - 4096 /* the kernel also has 2 KiB of static LDS */,
@@ -492,7 +580,9 @@ int64_t qiddm_mixed_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, in
                                              const qiddm_mixed_op_t* program, int32_t n_ops, int32_t max_blocks) {
   MixedGeometry g;
   int32_t n_snaps = 0;
-  const int rc = mixed_backward_geometry(n_qubits, dtype, batch, program, n_ops, max_blocks, &g, &n_snaps);
+  int rc = check_sizes(n_qubits, dtype, batch, n_ops, kOneWorkgroup);
+  if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc == QIDDM_OK) rc = mixed_backward_geometry(n_qubits, dtype, batch, program, n_ops, max_blocks, &g, &n_snaps);
   if (rc != QIDDM_OK) return rc;
   return g.total;
 }
@@ -503,52 +593,28 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
                          int32_t n_gates, int32_t measure, int64_t batch, const double* grad_out, int64_t gout_ld,
                          double* grad_rows, double* grad_gates, double* grad_features, int32_t max_blocks,
                          void* workspace, int64_t workspace_bytes, void* stream) {
+  const MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+                    enc_offset, pad_with, gates, n_gates, measure, batch};
+  bool embeds = false;
+  int rc = check_call(c, kOneWorkgroup, &embeds);
+  if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);  // refused for an empty batch as well
+  if (rc != QIDDM_OK || batch == 0) return rc;
+  if ((rc = check_backward_outputs(c, embeds, grad_out, gout_ld, grad_rows, grad_gates, grad_features)) != QIDDM_OK) return rc;
   MixedGeometry g;
   int32_t n_snaps = 0;
-  int rc = mixed_backward_geometry(n_qubits, dtype, batch, program, n_ops, max_blocks, &g, &n_snaps);
-  if (rc != QIDDM_OK) return rc;
-  if (measure != QIDDM_MEAS_PROBS && measure != QIDDM_MEAS_EXPZ) return fail(QIDDM_ERR_INVALID, "unknown measure %d", measure);
-  if (batch == 0) return QIDDM_OK;
-  if (!program || n_ops < 1) return fail(QIDDM_ERR_INVALID, "empty program");
-  if (n_rows < 0 || n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
-  if (n_rows > 0 && (!angle_rows || rows_ld < batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
-  if (n_gates > 0 && !gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");
-  rc = check_program(n_qubits, program, n_ops, n_rows, features, feat_ld, n_features, n_gates);
-  if (rc != QIDDM_OK) return rc;
-  const int64_t width = measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits;
-  if (!grad_out || gout_ld < width)
-    return fail(QIDDM_ERR_INVALID, "grad_out missing or gout_ld < %lld", (long long)width);
-  bool embeds = false;
-  for (int i = 0; i < n_ops; ++i) embeds = embeds || program[i].kind == qiddm::kMixAmpEmbed;
-  if (n_rows > 0 && !grad_rows) return fail(QIDDM_ERR_INVALID, "grad_rows is NULL");
-  if (n_gates > 0 && !grad_gates) return fail(QIDDM_ERR_INVALID, "grad_gates is NULL");
-  if (embeds && !grad_features) return fail(QIDDM_ERR_INVALID, "grad_features is NULL");
-  if (!workspace || workspace_bytes < g.total)
-    return fail(QIDDM_ERR_INVALID, "workspace of %lld B needed (qiddm_mixed_backward_workspace_bytes), got %lld",
-                (long long)g.total, (long long)workspace_bytes);
+  if ((rc = mixed_backward_geometry(n_qubits, dtype, batch, program, n_ops, max_blocks, &g, &n_snaps)) != QIDDM_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, g.total, "qiddm_mixed_backward_workspace_bytes")) != QIDDM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  hipError_t e = hipMemcpyAsync(ws + g.off_prog, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "program upload failed: %s", hipGetErrorString(e));
-  qiddm::MixedScalars m{};
-  m.n = n_qubits;
-  m.n_ops = n_ops;
-  m.measure = measure;
-  m.n_features = embeds ? n_features : 0;
-  m.batch = batch;
-  m.rows_ld = rows_ld;
-  m.feat_ld = feat_ld;
-  m.out_ld = 0;
-  m.enc_offset = enc_offset;
-  m.pad_with = pad_with;
-  m.slab_in_lds = g.in_lds ? 1 : 0;
+  if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  const qiddm::MixedScalars m = make_scalars(c, n_ops, embeds ? n_features : 0, 0, g.in_lds);
   qiddm::MixedBwdScalars b{};
   b.gout_ld = gout_ld;
   b.n_rows = n_rows;
   b.n_gates = n_gates;
   b.n_snaps = n_snaps;
   const size_t smem = g.in_lds ? 2 * (size_t)g.slab_bytes : 0;
-  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws + g.off_prog);
+  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     return launch<qiddm::mixed_backward_kernel<T>>(kMaxLds - 8192 /* the kernel also has 4.5 KiB of static LDS */,
@@ -562,10 +628,9 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
 int64_t qiddm_mixed_wide_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, const qiddm_mixed_op_t* program,
                                          int32_t n_ops) {
   (void)program;  // the workspace does not depend on the plan: program head, |v|^2 per resident sample, resident slabs
-  WideGeometry g;
-  const int rc = wide_geometry(n_qubits, dtype, batch, n_ops, &g);
+  const int rc = check_sizes(n_qubits, dtype, batch, n_ops, kTileFused);
   if (rc != QIDDM_OK) return rc;
-  return g.total;
+  return wide_geometry(n_qubits, dtype, batch, n_ops).total;
 }
 
 int qiddm_mixed_wide_plan(int32_t n_qubits, const qiddm_mixed_op_t* program, int32_t n_ops, int32_t* n_sweeps,
@@ -585,54 +650,27 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
                              int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with, const double* gates,
                              int32_t n_gates, int32_t measure, int64_t batch, double* out, int64_t out_ld, void* workspace,
                              int64_t workspace_bytes, void* stream) {
-  WideGeometry g;
-  int rc = wide_geometry(n_qubits, dtype, batch, n_ops, &g);
-  if (rc != QIDDM_OK) return rc;
-  if (measure != QIDDM_MEAS_PROBS && measure != QIDDM_MEAS_EXPZ) return fail(QIDDM_ERR_INVALID, "unknown measure %d", measure);
-  if (batch == 0) return QIDDM_OK;
-  if (!program || n_ops < 1) return fail(QIDDM_ERR_INVALID, "empty program");
-  if (!out) return fail(QIDDM_ERR_INVALID, "out is NULL");
-  const int64_t width = measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits;
-  if (out_ld < width) return fail(QIDDM_ERR_INVALID, "out_ld %lld < %lld", (long long)out_ld, (long long)width);
-  if (n_rows < 0 || n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
-  if (n_rows > 0 && (!angle_rows || rows_ld < batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
-  if (n_gates > 0 && !gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");
-  rc = check_program(n_qubits, program, n_ops, n_rows, features, feat_ld, n_features, n_gates);
-  if (rc != QIDDM_OK) return rc;
-  WidePlan plan;
-  rc = plan_mixed_wide(n_qubits, program, n_ops, &plan);
-  if (rc != QIDDM_OK) return rc;
-  // a smaller workspace than qiddm_mixed_wide_workspace_bytes() is accepted down to one slab: fewer samples are resident
-  int64_t resident = workspace ? (workspace_bytes - g.off_slabs) / g.slab_bytes : 0;
-  if (resident > g.resident) resident = g.resident;
-  if (resident < 1)
-    return fail(QIDDM_ERR_INVALID, "workspace of at least %lld B needed (qiddm_mixed_wide_workspace_bytes: %lld), got %lld",
-                (long long)(g.off_slabs + g.slab_bytes), (long long)g.total, (long long)workspace_bytes);
+  const MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+                    enc_offset, pad_with, gates, n_gates, measure, batch};
   bool embeds = false;
+  int rc = check_call(c, kTileFused, &embeds);
+  if (rc != QIDDM_OK || batch == 0) return rc;
+  if ((rc = check_forward_outputs(c, out, out_ld)) != QIDDM_OK) return rc;
+  const WideGeometry g = wide_geometry(n_qubits, dtype, batch, n_ops);
+  WidePlan plan;
+  if ((rc = plan_mixed_wide(n_qubits, program, n_ops, &plan)) != QIDDM_OK) return rc;
+  int64_t resident;
+  rc = wide_resident(workspace, workspace_bytes, g.off_slabs, g.slab_bytes, g.resident, g.total,
+                     "qiddm_mixed_wide_workspace_bytes", &resident);
+  if (rc != QIDDM_OK) return rc;
   std::vector<qiddm_mixed_op_t> sorted(n_ops);
-  for (int i = 0; i < n_ops; ++i) {
-    sorted[i] = program[plan.order[i]];
-    embeds = embeds || sorted[i].kind == qiddm::kMixAmpEmbed;
-  }
+  for (int i = 0; i < n_ops; ++i) sorted[i] = program[plan.order[i]];
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  // pageable source: the copy is staged before the call returns, so `sorted` may go out of scope
-  hipError_t e = hipMemcpyAsync(ws, sorted.data(), (size_t)n_ops * sizeof(qiddm_mixed_op_t), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "program upload failed: %s", hipGetErrorString(e));
-  qiddm::MixedScalars m{};
-  m.n = n_qubits;
-  m.n_ops = n_ops;
-  m.measure = measure;
-  m.n_features = n_features;
-  m.batch = batch;
-  m.rows_ld = rows_ld;
-  m.feat_ld = feat_ld;
-  m.out_ld = out_ld;
-  m.enc_offset = enc_offset;
-  m.pad_with = pad_with;
-  m.slab_in_lds = 0;
+  if ((rc = upload(ws, sorted.data(), (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  const qiddm::MixedScalars m = make_scalars(c, n_ops, n_features, out_ld, false);
   return for_dtype(dtype, [&](auto t) {
-    return launch_mixed_wide<decltype(t)>(plan, g, resident, ws, angle_rows, features, gates, out, m, embeds, st);
+    return launch_mixed_wide<decltype(t)>(plan, g, resident, ws, c, out, m, embeds, st);
   });
 }
 
@@ -640,11 +678,9 @@ int64_t qiddm_mixed_wide_backward_workspace_bytes(int32_t n_qubits, int32_t dtyp
                                                   const qiddm_mixed_op_t* program, int32_t n_ops) {
   WideBwdPlan bp;
   int rc = plan_mixed_wide_backward(n_qubits, program, n_ops, &bp);
+  if (rc == QIDDM_OK) rc = check_sizes(n_qubits, dtype, batch, n_ops, kTileFused);
   if (rc != QIDDM_OK) return rc;
-  WideBwdGeometry g;
-  rc = wide_backward_geometry(n_qubits, dtype, batch, bp, &g);
-  if (rc != QIDDM_OK) return rc;
-  return g.total;
+  return wide_backward_geometry(n_qubits, dtype, batch, bp).total;
 }
 
 int qiddm_mixed_wide_backward_plan(int32_t n_qubits, const qiddm_mixed_op_t* program, int32_t n_ops,
@@ -664,38 +700,19 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
                               const double* gates, int32_t n_gates, int32_t measure, int64_t batch,
                               const double* grad_out, int64_t gout_ld, double* grad_rows, double* grad_gates,
                               double* grad_features, void* workspace, int64_t workspace_bytes, void* stream) {
-  WideGeometry fg;
-  int rc = wide_geometry(n_qubits, dtype, batch, n_ops, &fg);  // wires, dtype, batch, n_ops
-  if (rc != QIDDM_OK) return rc;
-  if (measure != QIDDM_MEAS_PROBS && measure != QIDDM_MEAS_EXPZ) return fail(QIDDM_ERR_INVALID, "unknown measure %d", measure);
-  if (batch == 0) return QIDDM_OK;
-  if (!program || n_ops < 1) return fail(QIDDM_ERR_INVALID, "empty program");
-  if (n_rows < 0 || n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
-  if (n_rows > 0 && (!angle_rows || rows_ld < batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
-  if (n_gates > 0 && !gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");
-  rc = check_program(n_qubits, program, n_ops, n_rows, features, feat_ld, n_features, n_gates);
-  if (rc != QIDDM_OK) return rc;
-  const int64_t width = measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits;
-  if (!grad_out || gout_ld < width)
-    return fail(QIDDM_ERR_INVALID, "grad_out missing or gout_ld < %lld", (long long)width);
+  const MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+                    enc_offset, pad_with, gates, n_gates, measure, batch};
   bool embeds = false;
-  for (int i = 0; i < n_ops; ++i) embeds = embeds || program[i].kind == qiddm::kMixAmpEmbed;
-  if (n_rows > 0 && !grad_rows) return fail(QIDDM_ERR_INVALID, "grad_rows is NULL");
-  if (n_gates > 0 && !grad_gates) return fail(QIDDM_ERR_INVALID, "grad_gates is NULL");
-  if (embeds && !grad_features) return fail(QIDDM_ERR_INVALID, "grad_features is NULL");
+  int rc = check_call(c, kTileFused, &embeds);
+  if (rc != QIDDM_OK || batch == 0) return rc;
+  if ((rc = check_backward_outputs(c, embeds, grad_out, gout_ld, grad_rows, grad_gates, grad_features)) != QIDDM_OK) return rc;
   WideBwdPlan bp;
-  rc = plan_mixed_wide_backward(n_qubits, program, n_ops, &bp);
+  if ((rc = plan_mixed_wide_backward(n_qubits, program, n_ops, &bp)) != QIDDM_OK) return rc;
+  const WideBwdGeometry g = wide_backward_geometry(n_qubits, dtype, batch, bp);
+  int64_t resident;
+  rc = wide_resident(workspace, workspace_bytes, g.head, g.per_sample, g.resident, g.total,
+                     "qiddm_mixed_wide_backward_workspace_bytes", &resident);
   if (rc != QIDDM_OK) return rc;
-  WideBwdGeometry g;
-  rc = wide_backward_geometry(n_qubits, dtype, batch, bp, &g);
-  if (rc != QIDDM_OK) return rc;
-  // a smaller workspace than qiddm_mixed_wide_backward_workspace_bytes() is accepted down to one sample's worth
-  int64_t resident = workspace ? (workspace_bytes - g.head) / g.per_sample : 0;
-  if (resident > g.resident) resident = g.resident;
-  if (resident < 1)
-    return fail(QIDDM_ERR_INVALID,
-                "workspace of at least %lld B needed (qiddm_mixed_wide_backward_workspace_bytes: %lld), got %lld",
-                (long long)(g.head + g.per_sample), (long long)g.total, (long long)workspace_bytes);
   // the head in one upload: sorted live program, slots, params, groups
   std::vector<unsigned char> head((size_t)g.head, 0);
   qiddm_mixed_op_t* sorted = reinterpret_cast<qiddm_mixed_op_t*>(head.data());
@@ -705,33 +722,21 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
   memcpy(head.data() + g.off_groups, bp.group_begin.data(), bp.group_begin.size() * 4);
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  // pageable source: the copy is staged before the call returns, so `head` may go out of scope
-  hipError_t e = hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "program upload failed: %s", hipGetErrorString(e));
+  if ((rc = upload(ws, head.data(), head.size(), st)) != QIDDM_OK) return rc;
   // parameters no live op feeds keep a zero gradient
+  hipError_t e = hipSuccess;
   if (n_rows > 0) e = hipMemsetAsync(grad_rows, 0, (size_t)n_rows * (size_t)batch * 8, st);
   if (e == hipSuccess && n_gates > 0) e = hipMemsetAsync(grad_gates, 0, (size_t)batch * (size_t)n_gates * 64, st);
   if (e == hipSuccess && embeds && !bp.embed_live)
     e = hipMemsetAsync(grad_features, 0, (size_t)batch * (size_t)n_features * 8, st);
   if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "gradient reset failed: %s", hipGetErrorString(e));
-  qiddm::MixedScalars m{};
-  m.n = n_qubits;
-  m.n_ops = bp.n_live;
-  m.measure = measure;
-  m.n_features = embeds ? n_features : 0;
-  m.batch = batch;
-  m.rows_ld = rows_ld;
-  m.feat_ld = feat_ld;
-  m.out_ld = 0;
-  m.enc_offset = enc_offset;
-  m.pad_with = pad_with;
-  m.slab_in_lds = 0;
+  const qiddm::MixedScalars m = make_scalars(c, bp.n_live, embeds ? n_features : 0, 0, false);
   qiddm::WideBwdScalars b{};
   b.gout_ld = gout_ld;
   b.n_slots = bp.n_slots;
   return for_dtype(dtype, [&](auto t) {
-    return launch_mixed_wide_backward<decltype(t)>(bp, g, resident, ws, angle_rows, features, gates, grad_out, grad_rows,
-                                                   grad_gates, grad_features, m, b, n_gates, st);
+    return launch_mixed_wide_backward<decltype(t)>(bp, g, resident, ws, c, grad_out, grad_rows, grad_gates, grad_features,
+                                                   m, b, st);
   });
 }
 

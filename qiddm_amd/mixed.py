@@ -29,8 +29,8 @@ import ctypes
 import torch
 
 from . import _capi
+from . import circuit as _c
 
-_workspaces = {}
 CHANNELS = {"PhaseDamping": _capi.MIX_PHASE_DAMP, "AmplitudeDamping": _capi.MIX_AMP_DAMP,
             "DepolarizingChannel": _capi.MIX_DEPOL}
 
@@ -223,31 +223,42 @@ class _Launch:
     def stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def _prefix(self, rows, gates, feats):
+        """The arguments every compute entry point starts with: ``n_qubits`` .. ``batch``."""
+        return (self.n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0),
+                self.n_rows, _ptr(feats), 0 if feats is None else feats.stride(0),
+                0 if feats is None else feats.shape[1], 0.0, self.pad_with, _ptr(gates),
+                0 if gates is None else gates.shape[0], self.measure, self.batch)
+
+    def _resident(self):
+        """Samples per chunk of the tile-fused engine."""
+        return min(self.batch, wide_resident_samples) if wide_resident_samples > 0 else self.batch
+
+    @staticmethod
+    def _checked(need):
+        """The result of a ``*_workspace_bytes`` call, or the library's refusal."""
+        if need < 0:
+            _capi.check(int(need))
+        return need
+
+    def _fresh(self, need):
+        """A workspace for this call alone.  The tile-fused engine and the backward take up to 1 GiB: handed back to the
+        caching allocator after the call instead of being kept."""
+        return torch.empty(max(self._checked(need), 256), dtype=torch.uint8, device=self.device)
+
     def forward(self, rows, gates, feats, wide=False):
         n, batch = self.n, self.batch
         out = torch.empty(batch, (1 << n) if self.measure == _capi.MEAS_PROBS else n, dtype=torch.float64,
                           device=self.device)
         lib = _capi.lib()
         if wide:
-            resident = min(batch, wide_resident_samples) if wide_resident_samples > 0 else batch
-            need = lib.qiddm_mixed_wide_workspace_bytes(n, self.prec, resident, self.prog, len(self.prog))
+            ws = self._fresh(lib.qiddm_mixed_wide_workspace_bytes(n, self.prec, self._resident(), self.prog, len(self.prog)))
         else:
-            need = lib.qiddm_mixed_workspace_bytes(n, self.prec, batch, len(self.prog))
-        if need < 0:
-            _capi.check(int(need))
-        if wide:  # up to 1 GiB: handed back to the caching allocator after the call instead of being kept
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        else:
-            key = (self.device.type, self.device.index, self.stream())
-            ws = _workspaces.get(key)
-            if ws is None or ws.numel() < need:
-                ws = _workspaces[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            need = self._checked(lib.qiddm_mixed_workspace_bytes(n, self.prec, batch, len(self.prog)))
+            ws = _c._scratch(_c._workspaces, "mixed", need, self.device, floor=256)  # eager: cached per stream
         entry = lib.qiddm_mixed_wide_forward if wide else lib.qiddm_mixed_forward
-        _capi.check(entry(
-            n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0), self.n_rows,
-            _ptr(feats), 0 if feats is None else feats.stride(0), 0 if feats is None else feats.shape[1], 0.0,
-            self.pad_with, _ptr(gates), 0 if gates is None else gates.shape[0], self.measure, batch, out.data_ptr(),
-            out.stride(0), ws.data_ptr(), ws.numel(), ctypes.c_void_p(self.stream())))
+        _capi.check(entry(*self._prefix(rows, gates, feats), out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(),
+                          ctypes.c_void_p(self.stream())))
         return out
 
     def backward(self, rows, gates, feats, grad_out, max_blocks=0, wide=False):
@@ -259,29 +270,17 @@ class _Launch:
         g_gates = torch.empty(batch, gates.shape[0], 8, **f64) if gates is not None else None
         g_feats = torch.empty(batch, feats.shape[1], **f64) if feats is not None else None
         lib = _capi.lib()
+        grads = (grad_out.data_ptr(), grad_out.shape[1], _ptr(g_rows), _ptr(g_gates), _ptr(g_feats))
         if wide:
-            resident = min(batch, wide_resident_samples) if wide_resident_samples > 0 else batch
-            need = lib.qiddm_mixed_wide_backward_workspace_bytes(n, self.prec, resident, self.prog, len(self.prog))
-            if need < 0:
-                _capi.check(int(need))
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)  # handed back after the call, as the forward's
-            _capi.check(lib.qiddm_mixed_wide_backward(
-                n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0), self.n_rows,
-                _ptr(feats), 0 if feats is None else feats.stride(0), 0 if feats is None else feats.shape[1], 0.0,
-                self.pad_with, _ptr(gates), 0 if gates is None else gates.shape[0], self.measure, batch,
-                grad_out.data_ptr(), grad_out.shape[1], _ptr(g_rows), _ptr(g_gates), _ptr(g_feats),
-                ws.data_ptr(), ws.numel(), ctypes.c_void_p(self.stream())))
-            return g_rows, None if g_gates is None else g_gates.sum(dim=0), g_feats
-        need = lib.qiddm_mixed_backward_workspace_bytes(n, self.prec, batch, self.prog, len(self.prog), max_blocks)
-        if need < 0:
-            _capi.check(int(need))
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        _capi.check(lib.qiddm_mixed_backward(
-            n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0), self.n_rows,
-            _ptr(feats), 0 if feats is None else feats.stride(0), 0 if feats is None else feats.shape[1], 0.0,
-            self.pad_with, _ptr(gates), 0 if gates is None else gates.shape[0], self.measure, batch,
-            grad_out.data_ptr(), grad_out.shape[1], _ptr(g_rows), _ptr(g_gates), _ptr(g_feats), max_blocks,
-            ws.data_ptr(), ws.numel(), ctypes.c_void_p(self.stream())))
+            ws = self._fresh(lib.qiddm_mixed_wide_backward_workspace_bytes(n, self.prec, self._resident(), self.prog,
+                                                                           len(self.prog)))
+            entry = lib.qiddm_mixed_wide_backward
+        else:
+            ws = self._fresh(lib.qiddm_mixed_backward_workspace_bytes(n, self.prec, batch, self.prog, len(self.prog),
+                                                                      max_blocks))
+            entry, grads = lib.qiddm_mixed_backward, grads + (max_blocks,)
+        _capi.check(entry(*self._prefix(rows, gates, feats), *grads, ws.data_ptr(), ws.numel(),
+                          ctypes.c_void_p(self.stream())))
         return g_rows, None if g_gates is None else g_gates.sum(dim=0), g_feats
 
 
@@ -317,7 +316,6 @@ def execute(tape, ret, n, precision=None, _engine=None):
     (or the unbatched row), as ``default.mixed`` does.  Up to 8 wires: differentiable when grad mode is on and an input
     requires grad; otherwise a plain launch whose result has no ``grad_fn``.  9 and 10 wires (within the wire limit, see
     ``set_max_wires``): forward only unless ``set_max_grad_wires`` admits them too."""
-    from . import circuit as _c
     # the engine follows the number of wires; `_engine="wide"` (tests, A/B tools) forces the tile-fused one at 7, 8 wires
     wide = _engine == "wide" or 8 < n <= _max_wires
     if wide and n > _max_grad_wires and torch.is_grad_enabled() and \
@@ -335,7 +333,7 @@ def execute(tape, ret, n, precision=None, _engine=None):
         raise RuntimeError("default.mixed runs on the GPU only: no tensor argument lives on a HIP device (no CPU path)")
     device = low.device
     batch = low.batch or 1
-    prec = _capi.F64 if (precision or _c._default_precision) == "f64" else _capi.F32
+    prec = _capi.F64 if (precision or _c.get_default_precision()) == "f64" else _capi.F32
     launch = _Launch(low, measure, n, prec, device, batch)
     f64 = dict(dtype=torch.float64, device=device)
     rows = torch.stack([r.to(**f64).expand(batch) for r in low.rows]).contiguous() if low.rows else None
