@@ -124,3 +124,49 @@ def zero_rho(b, n):
     rho = torch.zeros(b, 1 << n, 1 << n, dtype=CDT)
     rho[:, 0, 0] = 1
     return rho
+
+
+# ---- op programs (include/qiddm_hip.h: QIDDM_MIX_*) --------------------------------------------------------------------
+ZERO, AMP_EMBED, PHASE, RY, GATE, CZ, CNOT, PHASE_DAMP, AMP_DAMP, DEPOL = range(10)
+CHANNEL_NAMES = {PHASE_DAMP: "PhaseDamping", AMP_DAMP: "AmplitudeDamping", DEPOL: "DepolarizingChannel"}
+
+
+def run_program(ops, n, rows, gates, feats, enc_offset, pad_with, measure):
+    """An op program as the header defines it, op by op in program order, from the functions above.
+
+    ops      list of (kind, wire, a, p, scale), kinds numbered as QIDDM_MIX_*
+    rows     (n_rows, B) angle rows: the angle of PHASE / RY is ``p + scale * rows[a]`` (``a < 0``: ``p`` alone)
+    gates    (n_gates, 8) shared or (B, n_gates, 8) per sample: (u00, u01, u10, u11) as (re, im)
+    feats    (B, F) or None: AMP_EMBED prepares AmplitudeEmbedding(feats + enc_offset, pad_with, normalize)
+    measure  "probs" -> (B, 2^n), "expz" -> (B, n)
+    PHASE is RZ (a global phase away from PhaseShift, which rho does not see); CZ / CNOT: control ``wire``, target ``a``.
+    Differentiable in rows, gates and feats."""
+    if measure not in ("probs", "expz"):
+        raise ValueError(measure)
+    b = rows.shape[1] if rows is not None else feats.shape[0] if feats is not None else \
+        gates.shape[0] if gates is not None and gates.dim() == 3 else 1
+    if not ops or ops[0][0] not in (ZERO, AMP_EMBED):
+        raise ValueError("a program starts with ZERO or AMP_EMBED")
+    rho = None
+    for kind, wire, a, p, scale in ops:
+        if kind == ZERO:
+            rho = zero_rho(b, n)
+        elif kind == AMP_EMBED:
+            rho = from_state(sv.amplitude_embedding(feats + enc_offset, n, pad_with=pad_with, normalize=True), n)
+        elif kind in (PHASE, RY):
+            angle = torch.full((b,), float(p), dtype=sv.RDT) if a < 0 else p + scale * rows[a].to(sv.RDT)
+            if kind == PHASE:
+                rho = rz_batched(rho, angle, wire, n)
+            else:
+                cs, sn = torch.cos(0.5 * angle), torch.sin(0.5 * angle)
+                rho = apply_unitary(rho, torch.stack([torch.stack([cs, -sn], 1), torch.stack([sn, cs], 1)], 1), wire, n)
+        elif kind == GATE:
+            g = gates[a] if gates.dim() == 2 else gates[:, a]
+            rho = apply_unitary(rho, torch.complex(g[..., 0::2], g[..., 1::2]).reshape(g.shape[:-1] + (2, 2)), wire, n)
+        elif kind in (CZ, CNOT):
+            rho = apply_diag_pair(rho, wire, a, n, "CZ" if kind == CZ else "CNOT")
+        elif kind in CHANNEL_NAMES:
+            rho = apply_kraus(rho, channel_kraus(CHANNEL_NAMES[kind], p), wire, n)
+        else:
+            raise ValueError(f"unknown op kind {kind}")
+    return probs(rho) if measure == "probs" else expval_z(rho, n)

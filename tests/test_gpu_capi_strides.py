@@ -561,30 +561,6 @@ def _mixed_program(n):
     return prog
 
 
-def _mixed_oracle(n, rows, gates, feats, offset, pad, measure):
-    """rows (2, B), gates (B, 2, 8) per sample, feats (B, F) -> out (B, 2^n | n), differentiable."""
-    from qiddm_amd import _capi as c
-    b = feats.shape[0]
-    rho = None
-    for kind, wire, a, p, scale in _mixed_ops(n):
-        if kind == c.MIX_AMP_EMBED:
-            rho = od.from_state(sv.amplitude_embedding(feats + offset, n, pad_with=pad, normalize=True), n)
-        elif kind == c.MIX_PHASE:
-            rho = od.rz_batched(rho, p + scale * rows[a], wire, n)
-        elif kind == c.MIX_RY:
-            half = 0.5 * (p + scale * rows[a])
-            cs, sn = torch.cos(half), torch.sin(half)
-            rho = od.apply_unitary(rho, torch.stack([torch.stack([cs, -sn], 1), torch.stack([sn, cs], 1)], 1), wire, n)
-        elif kind == c.MIX_GATE:
-            u = torch.complex(gates[:, a, 0::2], gates[:, a, 1::2]).reshape(b, 2, 2)
-            rho = od.apply_unitary(rho, u, wire, n)
-        elif kind == c.MIX_CZ:
-            rho = od.apply_diag_pair(rho, wire, a, n, "CZ")
-        else:
-            rho = od.apply_kraus(rho, od.channel_kraus("DepolarizingChannel", p), wire, n)
-    return od.probs(rho) if measure == "probs" else od.expval_z(rho, n)
-
-
 @functools.lru_cache(maxsize=None)
 def _mixed_case(n, measure):
     batch, nf, offset, pad = 3, MIX_FEATURES[n], 0.1, 0.1
@@ -598,7 +574,7 @@ def _mixed_case(n, measure):
     gout = torch.randn(batch, width, generator=g, dtype=torch.float64)
     r, f = rows.clone().requires_grad_(True), feats.clone().requires_grad_(True)
     gb = gates.unsqueeze(0).expand(batch, 2, 8).clone().requires_grad_(True)
-    out = _mixed_oracle(n, r, gb, f, offset, pad, measure)
+    out = od.run_program(_mixed_ops(n), n, r, gb, f, offset, pad, measure)
     g_rows, g_gates, g_feats = torch.autograd.grad((out * gout).sum(), [r, gb, f])
     return dict(batch=batch, nf=nf, offset=offset, pad=pad, rows=rows, feats=feats, gates=gates, gout=gout, width=width,
                 out=out.detach(), g_rows=g_rows, g_gates=g_gates, g_feats=g_feats)
