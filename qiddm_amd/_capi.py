@@ -25,82 +25,6 @@ IMP_CNOT, IMP_CZ = 0, 1
 MEAS_PROBS, MEAS_EXPZ = 0, 1
 F32, F64 = 0, 1
 
-# every symbol include/qiddm_hip.h declares (checked by tests/test_capi_symbols.py)
-EXPORTS = (
-    "qiddm_abi_version",
-    "qiddm_max_qubits",
-    "qiddm_last_error",
-    "qiddm_set_stamp_buffer",
-    "qiddm_num_rot_gates",
-    "qiddm_gate_count",
-    "qiddm_gate_table_elems",
-    "qiddm_num_shift_replicas",
-    "qiddm_workspace_bytes",
-    "qiddm_prepare_gates",
-    "qiddm_forward",
-    "qiddm_forward_post",
-    "qiddm_forward_shifted",
-    "qiddm_adjoint_partials",
-    "qiddm_backward_adjoint",
-    "qiddm_adjoint_finalize",
-    "qiddm_adjoint_workspace_bytes",
-    "qiddm_backward_adjoint_wide",
-    "qiddm_dense_forward",
-    "qiddm_dense_sample",
-    "qiddm_dense_sample_tables_bytes",
-    "qiddm_dense_sample_prepare",
-    "qiddm_dense_sample_lean_tables_bytes",
-    "qiddm_dense_sample_lean_prepare",
-    "qiddm_dense_sample_lean_check",
-    "qiddm_dense_sample_lean",
-    "qiddm_qconv_forward",
-    "qiddm_qconv_backward",
-    "qiddm_train_workspace_bytes",
-    "qiddm_train_step",
-    "qiddm_adam_step",
-    "qiddm_circuit_unitary",
-    "qiddm_circuit_unitary_wide",
-    "qiddm_qconv_unitary_workspace_bytes",
-    "qiddm_qconv_unitary_forward",
-    "qiddm_amp_embed_rows",
-    "qiddm_prob_post",
-    "qiddm_maxpool2_forward",
-    "qiddm_maxpool2_backward",
-    "qiddm_conv1x1_forward",
-    "qiddm_conv1x1_head_partials",
-    "qiddm_conv1x1_head_backward",
-    "qiddm_qconv_fold_features",
-    "qiddm_qconv_train_rows",
-    "qiddm_qconv_train_vectors",
-    "qiddm_qconv_train_partials",
-    "qiddm_qconv_train_backward",
-    "qiddm_qconv_train_x32_ok",
-    "qiddm_qconv_train_backward_x32",
-    "qiddm_qconv_train_dx_elems",
-    "qiddm_qconv_train_backward_dx",
-    "qiddm_matrix_adjoint_partials",
-    "qiddm_matrix_adjoint_workspace_bytes",
-    "qiddm_matrix_adjoint",
-    "qiddm_batchnorm_workspace_bytes",
-    "qiddm_batchnorm_train_forward",
-    "qiddm_batchnorm_backward",
-    "qiddm_batchnorm_backward_stats",
-    "qiddm_qconv_train_backward_bn",
-    "qiddm_qconv_train_bn_ok",
-    "qiddm_upsample2x_forward",
-    "qiddm_upsample2x_backward",
-    "qiddm_mixed_workspace_bytes",
-    "qiddm_mixed_forward",
-    "qiddm_mixed_backward_workspace_bytes",
-    "qiddm_mixed_backward",
-    "qiddm_mixed_wide_workspace_bytes",
-    "qiddm_mixed_wide_plan",
-    "qiddm_mixed_wide_forward",
-    "qiddm_mixed_wide_backward_workspace_bytes",
-    "qiddm_mixed_wide_backward_plan",
-    "qiddm_mixed_wide_backward",
-)
-
 
 class CircuitStruct(ctypes.Structure):
     """``qiddm_circuit_t``."""
@@ -126,163 +50,6 @@ class QiddmError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libqiddm_hip: {msg} (status {code})")
         self.code = code
-
-
-_lock = threading.Lock()
-_lib = None
-
-
-def _declare(lib):
-    P = ctypes.POINTER(CircuitStruct)
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    lib.qiddm_abi_version.restype = ctypes.c_int
-    lib.qiddm_abi_version.argtypes = []
-    lib.qiddm_max_qubits.restype = ctypes.c_int
-    lib.qiddm_max_qubits.argtypes = []
-    lib.qiddm_last_error.restype = ctypes.c_char_p
-    lib.qiddm_last_error.argtypes = []
-    lib.qiddm_set_stamp_buffer.restype = ctypes.c_int
-    lib.qiddm_set_stamp_buffer.argtypes = [vp, i64]
-    for name in ("qiddm_num_rot_gates", "qiddm_gate_count", "qiddm_gate_table_elems"):
-        getattr(lib, name).restype = i64
-        getattr(lib, name).argtypes = [P]
-    lib.qiddm_num_shift_replicas.restype = i64
-    lib.qiddm_num_shift_replicas.argtypes = [P, ctypes.c_int]
-    lib.qiddm_prepare_gates.restype = ctypes.c_int
-    lib.qiddm_prepare_gates.argtypes = [P, vp, vp, vp]
-    lib.qiddm_forward.restype = ctypes.c_int
-    lib.qiddm_forward.argtypes = [P, vp, i64, i64, vp, vp, i64, vp, i64, vp]
-    lib.qiddm_forward_post.restype = ctypes.c_int
-    lib.qiddm_forward_post.argtypes = [P, vp, i64, i64, vp, vp, i64, ctypes.c_int32, ctypes.c_double, vp]
-    lib.qiddm_forward_shifted.restype = ctypes.c_int
-    lib.qiddm_forward_shifted.argtypes = [P, vp, i64, i64, vp, vp, i64, i64, i64, vp, vp, i64, vp]
-    lib.qiddm_workspace_bytes.restype = i64
-    lib.qiddm_workspace_bytes.argtypes = [P, i64, i64]
-    lib.qiddm_dense_forward.restype = ctypes.c_int
-    lib.qiddm_dense_forward.argtypes = [P, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.c_int32,
-                                        ctypes.c_double, vp, i64, vp]
-    lib.qiddm_dense_sample.restype = ctypes.c_int
-    lib.qiddm_dense_sample.argtypes = [P, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.c_int32,
-                                       ctypes.c_double, ctypes.c_int32, vp, i64, i64, vp, vp]
-    lib.qiddm_dense_sample_tables_bytes.restype = i64
-    lib.qiddm_dense_sample_tables_bytes.argtypes = [P]
-    lib.qiddm_dense_sample_prepare.restype = ctypes.c_int
-    lib.qiddm_dense_sample_prepare.argtypes = [P, vp, vp, vp]
-    lib.qiddm_dense_sample_lean_tables_bytes.restype = i64
-    lib.qiddm_dense_sample_lean_tables_bytes.argtypes = [P]
-    lib.qiddm_dense_sample_lean_prepare.restype = ctypes.c_int
-    lib.qiddm_dense_sample_lean_prepare.argtypes = [P, vp, vp, vp, vp, vp, i64, vp, vp]
-    lib.qiddm_dense_sample_lean_check.restype = ctypes.c_int
-    lib.qiddm_dense_sample_lean_check.argtypes = [P, vp, vp]
-    lib.qiddm_dense_sample_lean.restype = ctypes.c_int
-    lib.qiddm_dense_sample_lean.argtypes = [P, vp, i64, i64, i64, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_double,
-                                            ctypes.c_int32, vp, i64, i64, vp, vp]
-    lib.qiddm_adjoint_partials.restype = i64
-    lib.qiddm_adjoint_partials.argtypes = [P, i64]
-    lib.qiddm_backward_adjoint.restype = ctypes.c_int
-    lib.qiddm_backward_adjoint.argtypes = [P, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp]
-    lib.qiddm_adjoint_workspace_bytes.restype = i64
-    lib.qiddm_adjoint_workspace_bytes.argtypes = [P, i64]
-    lib.qiddm_backward_adjoint_wide.restype = ctypes.c_int
-    lib.qiddm_backward_adjoint_wide.argtypes = [P, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp]
-    lib.qiddm_adjoint_finalize.restype = ctypes.c_int
-    lib.qiddm_adjoint_finalize.argtypes = [P, vp, vp, i64, vp, vp]
-    lib.qiddm_qconv_forward.restype = ctypes.c_int
-    lib.qiddm_qconv_forward.argtypes = [P, vp, i64, i64, i64, i64, i64, i64, i64, i64, vp, i64, vp, vp]
-    lib.qiddm_qconv_backward.restype = ctypes.c_int
-    lib.qiddm_qconv_backward.argtypes = [P, vp, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, i64, vp, vp, vp, vp]
-    dbl = ctypes.c_double
-    lib.qiddm_upsample2x_forward.restype = ctypes.c_int
-    lib.qiddm_upsample2x_forward.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp]
-    lib.qiddm_upsample2x_backward.restype = ctypes.c_int
-    lib.qiddm_upsample2x_backward.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp]
-    lib.qiddm_qconv_fold_features.restype = ctypes.c_int
-    lib.qiddm_qconv_fold_features.argtypes = [vp, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp]
-    lib.qiddm_qconv_train_rows.restype = ctypes.c_int
-    lib.qiddm_qconv_train_rows.argtypes = [ctypes.c_int32, vp, ctypes.c_int32, i64, i64, ctypes.c_int32, vp, vp]
-    lib.qiddm_qconv_train_vectors.restype = ctypes.c_int
-    lib.qiddm_qconv_train_vectors.argtypes = [ctypes.c_int32, vp, i64, i64, i64, ctypes.c_int32, vp, vp, vp]
-    lib.qiddm_qconv_train_partials.restype = ctypes.c_int64
-    lib.qiddm_qconv_train_partials.argtypes = [i64, i64, i64, i64]
-    lib.qiddm_qconv_train_backward.restype = ctypes.c_int
-    lib.qiddm_qconv_train_backward.argtypes = [ctypes.c_int32, vp, i64, i64, i64, i64, i64, i64, i64, i64, vp, i64, vp,
-                                               ctypes.c_int32, vp, vp, vp, vp]
-    lib.qiddm_qconv_train_x32_ok.restype = ctypes.c_int32
-    lib.qiddm_qconv_train_x32_ok.argtypes = [i64, i64, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int32]
-    lib.qiddm_qconv_train_backward_x32.restype = ctypes.c_int
-    lib.qiddm_qconv_train_backward_x32.argtypes = lib.qiddm_qconv_train_backward.argtypes
-    lib.qiddm_qconv_train_dx_elems.restype = ctypes.c_int64
-    lib.qiddm_qconv_train_dx_elems.argtypes = [ctypes.c_int32, i64, i64, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int32]
-    lib.qiddm_qconv_train_backward_dx.restype = ctypes.c_int
-    lib.qiddm_qconv_train_backward_dx.argtypes = [ctypes.c_int32, vp, i64, i64, i64, i64, i64, i64, i64, i64, vp, i64, i64,
-                                                  vp, ctypes.c_int32, vp, vp, vp, vp]
-    lib.qiddm_matrix_adjoint_partials.restype = ctypes.c_int64
-    lib.qiddm_matrix_adjoint_partials.argtypes = [i64]
-    lib.qiddm_matrix_adjoint_workspace_bytes.restype = ctypes.c_int64
-    lib.qiddm_matrix_adjoint_workspace_bytes.argtypes = [P, i64]
-    lib.qiddm_matrix_adjoint.restype = ctypes.c_int
-    lib.qiddm_matrix_adjoint.argtypes = [P, vp, vp, i64, vp, vp, vp, i64, vp]
-    lib.qiddm_batchnorm_workspace_bytes.restype = ctypes.c_int64
-    lib.qiddm_batchnorm_workspace_bytes.argtypes = [i64, i64, i64]
-    lib.qiddm_batchnorm_train_forward.restype = ctypes.c_int
-    lib.qiddm_batchnorm_train_forward.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, dbl, dbl, vp, vp, vp, vp, i64, vp]
-    lib.qiddm_batchnorm_backward_stats.restype = ctypes.c_int
-    lib.qiddm_batchnorm_backward_stats.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.qiddm_qconv_train_bn_ok.restype = ctypes.c_int32
-    lib.qiddm_qconv_train_bn_ok.argtypes = [i64, i64, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int32]
-    lib.qiddm_qconv_train_backward_bn.restype = ctypes.c_int
-    lib.qiddm_qconv_train_backward_bn.argtypes = [ctypes.c_int32, vp, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp,
-                                                  i64, vp, ctypes.c_int32, vp, vp, vp, vp, vp]
-    lib.qiddm_batchnorm_backward.restype = ctypes.c_int
-    lib.qiddm_batchnorm_backward.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.qiddm_train_workspace_bytes.restype = ctypes.c_int64
-    lib.qiddm_train_workspace_bytes.argtypes = [P, i64, ctypes.c_int32, ctypes.c_int32]
-    lib.qiddm_train_step.restype = ctypes.c_int
-    lib.qiddm_train_step.argtypes = [P, ctypes.POINTER(TrainArgs), vp, i64, vp]
-    lib.qiddm_circuit_unitary.restype = ctypes.c_int
-    lib.qiddm_circuit_unitary.argtypes = [P, vp, vp, vp]
-    lib.qiddm_circuit_unitary_wide.restype = ctypes.c_int
-    lib.qiddm_circuit_unitary_wide.argtypes = [P, vp, vp, vp]
-    lib.qiddm_qconv_unitary_workspace_bytes.restype = i64
-    lib.qiddm_qconv_unitary_workspace_bytes.argtypes = [ctypes.c_int32, i64, i64, i64, i64]
-    lib.qiddm_qconv_unitary_forward.restype = ctypes.c_int
-    lib.qiddm_qconv_unitary_forward.argtypes = [ctypes.c_int32, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
-                                                i64, ctypes.c_int32, ctypes.POINTER(BatchNormStruct), ctypes.c_int32, vp, vp,
-                                                i64, vp]
-    i32, dbl, ops, i32p = ctypes.c_int32, ctypes.c_double, ctypes.POINTER(MixedOp), ctypes.POINTER(ctypes.c_int32)
-    # what the four compute entry points of the density-matrix executor share: n_qubits .. batch
-    mixed_call = [i32, i32, ops, i32, vp, i64, i32, vp, i64, i32, dbl, dbl, vp, i32, i32, i64]
-    tail = [vp, i64, vp]                                   # workspace, workspace_bytes, stream
-    for name, restype, argtypes in (
-            ("qiddm_mixed_workspace_bytes", i64, [i32, i32, i64, i32]),
-            ("qiddm_mixed_forward", ctypes.c_int, mixed_call + [vp, i64] + tail),
-            ("qiddm_mixed_backward_workspace_bytes", i64, [i32, i32, i64, ops, i32, i32]),
-            ("qiddm_mixed_backward", ctypes.c_int, mixed_call + [vp, i64, vp, vp, vp, i32] + tail),
-            ("qiddm_mixed_wide_workspace_bytes", i64, [i32, i32, i64, ops, i32]),
-            ("qiddm_mixed_wide_plan", ctypes.c_int, [i32, ops, i32, i32p, i32p, i32p]),
-            ("qiddm_mixed_wide_forward", ctypes.c_int, mixed_call + [vp, i64] + tail),
-            ("qiddm_mixed_wide_backward_workspace_bytes", i64, [i32, i32, i64, ops, i32]),
-            ("qiddm_mixed_wide_backward_plan", ctypes.c_int, [i32, ops, i32, i32p, i32p, i32p]),
-            ("qiddm_mixed_wide_backward", ctypes.c_int, mixed_call + [vp, i64, vp, vp, vp] + tail)):
-        getattr(lib, name).restype = restype
-        getattr(lib, name).argtypes = argtypes
-    lib.qiddm_amp_embed_rows.restype = ctypes.c_int
-    lib.qiddm_amp_embed_rows.argtypes = [vp, i64, i64, i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp, vp]
-    lib.qiddm_prob_post.restype = ctypes.c_int
-    lib.qiddm_prob_post.argtypes = [vp, i64, i64, ctypes.c_double, vp, vp]
-    lib.qiddm_maxpool2_forward.restype = ctypes.c_int
-    lib.qiddm_maxpool2_forward.argtypes = [vp, i64, i64, i64, vp, vp]
-    lib.qiddm_maxpool2_backward.restype = ctypes.c_int
-    lib.qiddm_maxpool2_backward.argtypes = [vp, vp, i64, i64, i64, vp, vp]
-    lib.qiddm_conv1x1_forward.restype = ctypes.c_int
-    lib.qiddm_conv1x1_forward.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp]
-    lib.qiddm_conv1x1_head_partials.restype = ctypes.c_int64
-    lib.qiddm_conv1x1_head_partials.argtypes = [i64, i64]
-    lib.qiddm_conv1x1_head_backward.restype = ctypes.c_int
-    lib.qiddm_conv1x1_head_backward.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]
-    lib.qiddm_adam_step.restype = ctypes.c_int
-    lib.qiddm_adam_step.argtypes = [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_double, ctypes.c_double,
-                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, vp]
 
 
 class TrainArgs(ctypes.Structure):
@@ -327,6 +94,128 @@ class AdamTensor(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+_P = ctypes.POINTER(CircuitStruct)
+_int, _i32, _i64, _dbl, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
+_ops, _i32p = ctypes.POINTER(MixedOp), ctypes.POINTER(ctypes.c_int32)
+# argument runs that several entry points share, in the header's order
+_stream = [_vp]
+_ws = [_vp, _i64]                                          # workspace, workspace_bytes
+_image = [_i64] * 8                                        # batch, in_channels, height, width, kh, kw, pad_h, pad_w
+_table_of = [_P, _vp, _vp] + _stream                       # circ, angles -> one device table
+_dense = [_P, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _dbl]     # circ, x .. noise_factor
+_adjoint = [_P, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64]                    # circ, inputs .. gin_ld
+_thin = [_i32, _vp] + _image + [_vp, _i64, _vp, _i32, _vp, _vp, _vp] + _stream      # qiddm_qconv_train_backward[_x32]
+_layer_ok = _image + [_i64, _i32]                          # the geometry, out_channels, row_channels
+_norm_back = [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp] + _ws + _stream
+_planes = [_vp, _i64, _i64, _i64]                          # x, planes, height, width
+# what the four compute entry points of the density-matrix executor share: n_qubits .. batch
+_mixed = [_i32, _i32, _ops, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _dbl, _dbl, _vp, _i32, _i32, _i64]
+_mixed_plan = [_i32, _ops, _i32, _i32p, _i32p, _i32p]
+
+# The one Python copy of include/qiddm_hip.h: name -> (restype, argtypes), in the header's order.
+# tests/test_capi_symbols.py checks the names against the header, tests/test_capi_binding.py every parameter list.
+SIGNATURES = {
+    "qiddm_abi_version": (_int, []),
+    "qiddm_max_qubits": (_int, []),
+    "qiddm_last_error": (ctypes.c_char_p, []),
+    "qiddm_set_stamp_buffer": (_int, [_vp, _i64]),
+    "qiddm_num_rot_gates": (_i64, [_P]),
+    "qiddm_gate_count": (_i64, [_P]),
+    "qiddm_gate_table_elems": (_i64, [_P]),
+    "qiddm_num_shift_replicas": (_i64, [_P, _int]),
+    "qiddm_workspace_bytes": (_i64, [_P, _i64, _i64]),
+    "qiddm_prepare_gates": (_int, _table_of),
+    "qiddm_forward": (_int, [_P, _vp, _i64, _i64, _vp, _vp, _i64] + _ws + _stream),
+    "qiddm_forward_post": (_int, [_P, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _dbl] + _stream),
+    "qiddm_forward_shifted": (_int, [_P, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp] + _ws + _stream),
+    "qiddm_adjoint_partials": (_i64, [_P, _i64]),
+    "qiddm_backward_adjoint": (_int, _adjoint + _stream),
+    "qiddm_adjoint_workspace_bytes": (_i64, [_P, _i64]),
+    "qiddm_backward_adjoint_wide": (_int, _adjoint + _ws + _stream),
+    "qiddm_adjoint_finalize": (_int, [_P, _vp, _vp, _i64, _vp] + _stream),
+    "qiddm_dense_forward": (_int, _dense + [_vp, _i64] + _stream),
+    "qiddm_dense_sample": (_int, _dense + [_i32, _vp, _i64, _i64, _vp] + _stream),
+    "qiddm_dense_sample_tables_bytes": (_i64, [_P]),
+    "qiddm_dense_sample_prepare": (_int, _table_of),
+    "qiddm_dense_sample_lean_tables_bytes": (_i64, [_P]),
+    "qiddm_dense_sample_lean_prepare": (_int, [_P, _vp, _vp, _vp, _vp, _vp, _i64, _vp] + _stream),
+    "qiddm_dense_sample_lean_check": (_int, [_P, _vp] + _stream),
+    "qiddm_dense_sample_lean": (_int, [_P, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _vp, _i64, _i64, _vp]
+                                + _stream),
+    "qiddm_qconv_forward": (_int, [_P, _vp] + _image + [_vp, _i64, _vp] + _stream),
+    "qiddm_qconv_backward": (_int, [_P, _vp] + _image + [_vp, _vp, _i64, _vp, _vp, _vp] + _stream),
+    "qiddm_train_workspace_bytes": (_i64, [_P, _i64, _i32, _i32]),
+    "qiddm_train_step": (_int, [_P, ctypes.POINTER(TrainArgs)] + _ws + _stream),
+    "qiddm_adam_step": (_int, [ctypes.POINTER(AdamTensor), _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _vp] + _stream),
+    "qiddm_circuit_unitary": (_int, _table_of),
+    "qiddm_circuit_unitary_wide": (_int, _table_of),
+    "qiddm_qconv_unitary_workspace_bytes": (_i64, [_i32, _i64, _i64, _i64, _i64]),
+    "qiddm_qconv_unitary_forward": (_int, [_i32, _vp, _vp] + _image + [_i64, _i32, ctypes.POINTER(BatchNormStruct), _i32, _vp]
+                                    + _ws + _stream),
+    "qiddm_batchnorm_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "qiddm_batchnorm_train_forward": (_int, _planes + [_vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp] + _ws + _stream),
+    "qiddm_batchnorm_backward_stats": (_int, _norm_back),
+    "qiddm_batchnorm_backward": (_int, _norm_back),
+    "qiddm_upsample2x_forward": (_int, _planes + [_vp, _vp, _vp] + _stream),
+    "qiddm_upsample2x_backward": (_int, _planes + [_vp, _vp, _vp] + _stream),
+    "qiddm_amp_embed_rows": (_int, [_vp, _i64, _i64, _i64, _i32, _dbl, _dbl, _vp] + _stream),
+    "qiddm_prob_post": (_int, [_vp, _i64, _i64, _dbl, _vp] + _stream),
+    "qiddm_maxpool2_forward": (_int, _planes + [_vp] + _stream),
+    "qiddm_maxpool2_backward": (_int, [_vp] + _planes + [_vp] + _stream),
+    "qiddm_qconv_train_rows": (_int, [_i32, _vp, _i32, _i64, _i64, _i32, _vp] + _stream),
+    "qiddm_qconv_train_vectors": (_int, [_i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp] + _stream),
+    "qiddm_qconv_fold_features": (_int, [_vp] + _image + [_vp] + _stream),
+    "qiddm_qconv_train_partials": (_i64, [_i64, _i64, _i64, _i64]),
+    "qiddm_qconv_train_backward": (_int, _thin),
+    "qiddm_qconv_train_x32_ok": (_i32, _layer_ok),
+    "qiddm_qconv_train_backward_x32": (_int, _thin),
+    "qiddm_qconv_train_dx_elems": (_i64, [_i32] + _layer_ok),
+    "qiddm_qconv_train_backward_dx": (_int, [_i32, _vp] + _image + [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp] + _stream),
+    "qiddm_qconv_train_bn_ok": (_i32, _layer_ok),
+    "qiddm_qconv_train_backward_bn": (_int, [_i32, _vp] + _image + [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]
+                                      + _stream),
+    "qiddm_matrix_adjoint_partials": (_i64, [_i64]),
+    "qiddm_matrix_adjoint_workspace_bytes": (_i64, [_P, _i64]),
+    "qiddm_matrix_adjoint": (_int, [_P, _vp, _vp, _i64, _vp, _vp] + _ws + _stream),
+    "qiddm_conv1x1_forward": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp] + _stream),
+    "qiddm_conv1x1_head_partials": (_i64, [_i64, _i64]),
+    "qiddm_conv1x1_head_backward": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp] + _stream),
+    "qiddm_mixed_workspace_bytes": (_i64, [_i32, _i32, _i64, _i32]),
+    "qiddm_mixed_forward": (_int, _mixed + [_vp, _i64] + _ws + _stream),
+    "qiddm_mixed_backward_workspace_bytes": (_i64, [_i32, _i32, _i64, _ops, _i32, _i32]),
+    "qiddm_mixed_backward": (_int, _mixed + [_vp, _i64, _vp, _vp, _vp, _i32] + _ws + _stream),
+    "qiddm_mixed_wide_workspace_bytes": (_i64, [_i32, _i32, _i64, _ops, _i32]),
+    "qiddm_mixed_wide_plan": (_int, _mixed_plan),
+    "qiddm_mixed_wide_forward": (_int, _mixed + [_vp, _i64] + _ws + _stream),
+    "qiddm_mixed_wide_backward_workspace_bytes": (_i64, [_i32, _i32, _i64, _ops, _i32]),
+    "qiddm_mixed_wide_backward_plan": (_int, _mixed_plan),
+    "qiddm_mixed_wide_backward": (_int, _mixed + [_vp, _i64, _vp, _vp, _vp] + _ws + _stream),
+}
+# every symbol include/qiddm_hip.h declares
+EXPORTS = tuple(SIGNATURES)
+
+
+_lock = threading.Lock()
+_lib = None
+
+
+def _declare(handle):
+    """Check the ABI version of ``handle``, then set ``restype`` / ``argtypes`` of every entry of ``SIGNATURES``.  A
+    library of another version, or one that lacks a symbol, is a stale build: both say so."""
+    def bind(name):
+        try:
+            fn = getattr(handle, name)
+        except AttributeError:
+            raise RuntimeError(f"libqiddm_hip.so has no symbol {name}: ABI mismatch; rebuild it") from None
+        fn.restype, fn.argtypes = SIGNATURES[name]
+        return fn
+
+    if bind("qiddm_abi_version")() != 1:
+        raise RuntimeError("libqiddm_hip.so ABI version mismatch; rebuild it")
+    for name in SIGNATURES:
+        bind(name)
+
+
 def _preload_torch_hip_runtime():
     cand = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
     if os.path.exists(cand):
@@ -350,8 +239,6 @@ def lib():
             _preload_torch_hip_runtime()
             handle = ctypes.CDLL(LIB_PATH)
             _declare(handle)
-            if handle.qiddm_abi_version() != 1:
-                raise RuntimeError("libqiddm_hip.so ABI version mismatch; rebuild it")
             _lib = handle
     return _lib
 
@@ -359,3 +246,37 @@ def lib():
 def check(status: int):
     if status != QIDDM_OK:
         raise QiddmError(status, lib().qiddm_last_error().decode("utf-8", "replace"))
+
+
+def _addresses(name: str, args) -> list:
+    """``args`` as ctypes takes them: every tensor as its device address (an int, which the entry's ``c_void_p`` argtype
+    widens to a pointer), everything else as it is -- None is NULL, and a structure or array instance goes by reference
+    where the argtype is a ``POINTER``.  A tensor outside the device would be a wild address inside a kernel."""
+    args = list(args)
+    for i, a in enumerate(args):
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                raise TypeError(f"{name}: argument {i} is a tensor on {a.device}, not on a HIP device")
+            args[i] = a.data_ptr()
+    return args
+
+
+def launch(name: str, device, *args) -> None:
+    """Call the status-returning entry ``name`` with ``args`` and, last, the current stream of ``device``; raise
+    ``QiddmError`` unless it returns QIDDM_OK.  ``device=None`` appends nothing: ``args`` is the whole argument list."""
+    args = _addresses(name, args)
+    if device is not None:
+        args.append(torch.cuda.current_stream(device).cuda_stream)
+    check(getattr(lib(), name)(*args))
+
+
+def query(name: str, *args, device=None) -> int:
+    """The value of a size / count / predicate entry; a negative one is the library's status and raises ``QiddmError``
+    with that code.  ``device``: as for ``launch`` (``qiddm_dense_sample_lean_check`` reads back on a stream)."""
+    args = _addresses(name, args)
+    if device is not None:
+        args.append(torch.cuda.current_stream(device).cuda_stream)
+    value = getattr(lib(), name)(*args)
+    if value < 0:
+        check(int(value))
+    return value

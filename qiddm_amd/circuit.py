@@ -10,7 +10,6 @@ be built, otherwise the call raises.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from dataclasses import dataclass, replace
 
@@ -128,10 +127,6 @@ def wide_sweeps_per_sample(circ: "Circuit", precision: str = "f32"):
     return circ.n_rounds * (passes - 1), f"qiddm::tiled_circuit_kernel<{t}, false>"
 
 
-def _stream_ptr(device) -> int:
-    return int(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _require_device(t: torch.Tensor, what: str):
     if not t.is_cuda:
         raise RuntimeError(
@@ -184,17 +179,12 @@ def _scratch(cache: dict, tag, need: int, device, floor: int = 0) -> torch.Tenso
 
 def _workspace(circ: Circuit, precision: str, batch: int, n_replicas: int, device):
     """Per-device scratch for the n > 10 tiled kernel (slabs of concurrently resident workgroups).
-    Returns (tensor, ptr, nbytes); (None, 0, 0) when the circuit is register-resident.  The caller keeps the TENSOR
+    Returns (tensor, nbytes); (None, 0) when the circuit is register-resident.  The caller keeps the TENSOR
     alive across its launch: during a graph capture it is a fresh allocation that nothing else references."""
-    lib = _capi.lib()
-    cs = circ.c_struct(precision)
-    need = lib.qiddm_workspace_bytes(ctypes.byref(cs), batch, n_replicas)
-    if need < 0:
-        _capi.check(-1)
+    need = _capi.query("qiddm_workspace_bytes", circ.c_struct(precision), batch, n_replicas)
     if need == 0:
-        return None, 0, 0
-    buf = _scratch(_workspaces, "tiled", need, device)
-    return buf, buf.data_ptr(), need
+        return None, 0
+    return _scratch(_workspaces, "tiled", need, device), need
 
 
 def prepare_gates(circ: Circuit, angles: torch.Tensor, precision: str) -> torch.Tensor:
@@ -202,15 +192,10 @@ def prepare_gates(circ: Circuit, angles: torch.Tensor, precision: str) -> torch.
     _require_device(angles, "the circuit weights")
     if tuple(angles.shape) != circ.angles_shape:
         raise ValueError(f"angles must have shape {circ.angles_shape}; got {tuple(angles.shape)}")
-    lib = _capi.lib()
     cs = circ.c_struct(precision)
     a64 = angles.detach().to(torch.float64).contiguous()
-    n_elems = lib.qiddm_gate_table_elems(ctypes.byref(cs))
-    if n_elems < 0:
-        _capi.check(-1)
-    table = torch.empty(n_elems, dtype=_DT[precision][1], device=angles.device)
-    _capi.check(lib.qiddm_prepare_gates(ctypes.byref(cs), a64.data_ptr(), table.data_ptr(),
-                                        _stream_ptr(angles.device)))
+    table = torch.empty(_capi.query("qiddm_gate_table_elems", cs), dtype=_DT[precision][1], device=angles.device)
+    _capi.launch("qiddm_prepare_gates", angles.device, cs, a64, table)
     return table
 
 
@@ -227,14 +212,11 @@ def run_forward(circ: Circuit, inputs, angles: torch.Tensor, precision: str | No
     if x is None and batch is None:
         raise ValueError("run_forward needs inputs (or batch=) to know the batch size")
     batch = x.shape[0] if x is not None else int(batch)
-    lib = _capi.lib()
     if table is None:
         table = prepare_gates(circ, angles, precision)
     out = torch.empty(batch, circ.out_cols, dtype=dtype, device=device)
-    cs = circ.c_struct(precision)
-    ws_buf, ws_ptr, ws_bytes = _workspace(circ, precision, batch, 0, device)
-    _capi.check(lib.qiddm_forward(ctypes.byref(cs), 0 if x is None else x.data_ptr(), batch, ld, table.data_ptr(),
-                                  out.data_ptr(), circ.out_cols, ws_ptr, ws_bytes, _stream_ptr(device)))
+    ws, ws_bytes = _workspace(circ, precision, batch, 0, device)
+    _capi.launch("qiddm_forward", device, circ.c_struct(precision), x, batch, ld, table, out, circ.out_cols, ws, ws_bytes)
     return out
 
 
@@ -255,10 +237,8 @@ def run_forward_post(circ: Circuit, inputs, angles: torch.Tensor, post_cols: int
     if table is None:
         table = prepare_gates(circ, angles, precision)
     out = torch.empty(x.shape[0], post_cols, dtype=torch.float64, device=device)
-    cs = circ.c_struct(precision)
-    _capi.check(_capi.lib().qiddm_forward_post(ctypes.byref(cs), x.data_ptr(), x.shape[0], ld, table.data_ptr(),
-                                               out.data_ptr(), out.stride(0), int(post_cols), float(post_scale),
-                                               _stream_ptr(device)))
+    _capi.launch("qiddm_forward_post", device, circ.c_struct(precision), x, x.shape[0], ld, table, out, out.stride(0),
+                 int(post_cols), float(post_scale))
     return out
 
 
@@ -286,12 +266,8 @@ def dense_forward(circ: Circuit, x: torch.Tensor, w_down, b_down, angles, w_up, 
         raise ValueError(f"linear shapes {tuple(wd.shape)} / {tuple(wu.shape)} do not match n={n}, "
                          f"in_features={xx.shape[1]}")
     y = torch.empty(xx.shape[0], wu.shape[0], dtype=torch.float64, device=device)
-    cs = circ.c_struct(precision)
-    _capi.check(_capi.lib().qiddm_dense_forward(
-        ctypes.byref(cs), xx.data_ptr(), xx.shape[0], xx.stride(0), xx.shape[1], wd.data_ptr(),
-        0 if bd is None else bd.data_ptr(), ang.data_ptr(), wu.data_ptr(),
-        0 if bu is None else bu.data_ptr(), wu.shape[0], int(post_mode), float(noise_factor),
-        y.data_ptr(), y.stride(0), _stream_ptr(device)))
+    _capi.launch("qiddm_dense_forward", device, circ.c_struct(precision), xx, xx.shape[0], xx.stride(0), xx.shape[1], wd,
+                 bd, ang, wu, bu, wu.shape[0], int(post_mode), float(noise_factor), y, y.stride(0))
     return y
 
 
@@ -304,14 +280,9 @@ def dense_sample_tables(circ: Circuit, angles: torch.Tensor, precision: str | No
     ang = _as_f64(angles.detach(), device)
     if tuple(ang.shape) != circ.angles_shape:
         raise ValueError(f"angles must have shape {circ.angles_shape}; got {tuple(ang.shape)}")
-    lib = _capi.lib()
     cs = circ.c_struct(precision)
-    need = lib.qiddm_dense_sample_tables_bytes(ctypes.byref(cs))
-    if need < 0:
-        _capi.check(int(need))
-    tables = torch.empty(need, dtype=torch.uint8, device=device)
-    _capi.check(lib.qiddm_dense_sample_prepare(ctypes.byref(cs), ang.data_ptr(), tables.data_ptr(),
-                                               _stream_ptr(device)))
+    tables = torch.empty(_capi.query("qiddm_dense_sample_tables_bytes", cs), dtype=torch.uint8, device=device)
+    _capi.launch("qiddm_dense_sample_prepare", device, cs, ang, tables)
     return tables
 
 
@@ -330,12 +301,9 @@ def dense_sample(circ: Circuit, x: torch.Tensor, w_down, b_down, angles, w_up, b
     if tuple(ang.shape) != circ.angles_shape:
         raise ValueError(f"angles must have shape {circ.angles_shape}; got {tuple(ang.shape)}")
     y = torch.empty(n_steps, xx.shape[0], wu.shape[0], dtype=torch.float64, device=device)
-    cs = circ.c_struct(precision)
-    _capi.check(_capi.lib().qiddm_dense_sample(
-        ctypes.byref(cs), xx.data_ptr(), xx.shape[0], xx.stride(0), xx.shape[1], wd.data_ptr(),
-        0 if bd is None else bd.data_ptr(), ang.data_ptr(), wu.data_ptr(), 0 if bu is None else bu.data_ptr(),
-        wu.shape[0], int(post_mode), float(noise_factor), int(n_steps), y.data_ptr(), y.stride(1),
-        y.stride(0), 0 if tables is None else tables.data_ptr(), _stream_ptr(device)))
+    _capi.launch("qiddm_dense_sample", device, circ.c_struct(precision), xx, xx.shape[0], xx.stride(0), xx.shape[1], wd,
+                 bd, ang, wu, bu, wu.shape[0], int(post_mode), float(noise_factor), int(n_steps), y, y.stride(1),
+                 y.stride(0), tables)
     return y
 
 
@@ -358,20 +326,14 @@ def dense_sample_lean_tables(circ: Circuit, angles, w_down, b_down, w_up, b_up, 
     wd, bd, wu, bu = (_as_f64(t, device) for t in (w_down, b_down, w_up, b_up))
     if tuple(ang.shape) != circ.angles_shape or wd.shape[0] != n or wu.shape != (wd.shape[1], n) or wd.shape[1] > 2048:
         return None
-    lib = _capi.lib()
     cs = circ.c_struct(precision)
-    need = lib.qiddm_dense_sample_lean_tables_bytes(ctypes.byref(cs))
-    if need < 0:
+    try:
+        need = _capi.query("qiddm_dense_sample_lean_tables_bytes", cs)
+    except _capi.QiddmError:
         return None                                  # e.g. deep float64 circuits whose tables do not fit in LDS
     tables = torch.empty(need, dtype=torch.uint8, device=device)
-    st = _stream_ptr(device)
-    _capi.check(lib.qiddm_dense_sample_lean_prepare(ctypes.byref(cs), ang.data_ptr(), wd.data_ptr(),
-                                                    0 if bd is None else bd.data_ptr(), wu.data_ptr(),
-                                                    0 if bu is None else bu.data_ptr(), wd.shape[1], tables.data_ptr(), st))
-    ok = lib.qiddm_dense_sample_lean_check(ctypes.byref(cs), tables.data_ptr(), st)
-    if ok < 0:
-        _capi.check(ok)
-    return tables if ok == 1 else None
+    _capi.launch("qiddm_dense_sample_lean_prepare", device, cs, ang, wd, bd, wu, bu, wd.shape[1], tables)
+    return tables if _capi.query("qiddm_dense_sample_lean_check", cs, tables, device=device) == 1 else None
 
 
 def dense_sample_lean(circ: Circuit, x: torch.Tensor, w_down, b_down, w_up, b_up, n_steps: int, tables: torch.Tensor,
@@ -384,13 +346,15 @@ def dense_sample_lean(circ: Circuit, x: torch.Tensor, w_down, b_down, w_up, b_up
     xx = _as_f64(x, device)
     wd, bd, wu, bu = (_as_f64(t, device) for t in (w_down, b_down, w_up, b_up))
     y = torch.empty(n_steps, xx.shape[0], wu.shape[0], dtype=torch.float64, device=device)
-    cs = circ.c_struct(precision)
-    _capi.check(_capi.lib().qiddm_dense_sample_lean(
-        ctypes.byref(cs), xx.data_ptr(), xx.shape[0], xx.stride(0), xx.shape[1], wd.data_ptr(),
-        0 if bd is None else bd.data_ptr(), wu.data_ptr(), 0 if bu is None else bu.data_ptr(), int(post_mode),
-        float(noise_factor), int(n_steps), y.data_ptr(), y.stride(1), y.stride(0), tables.data_ptr(),
-        _stream_ptr(device)))
+    _capi.launch("qiddm_dense_sample_lean", device, circ.c_struct(precision), xx, xx.shape[0], xx.stride(0), xx.shape[1],
+                 wd, bd, wu, bu, int(post_mode), float(noise_factor), int(n_steps), y, y.stride(1), y.stride(0), tables)
     return y
+
+
+def _weights_only_circuit(n_qubits: int, sel_layers: int, imprimitive: str = "CNOT") -> Circuit:
+    """``StronglyEntanglingLayers`` on its own: no data encoding, one round, one block."""
+    return Circuit(n_qubits=n_qubits, encoding="none", imprimitive=imprimitive, measure="probs", n_rounds=1,
+                   n_blocks=1, sel_layers=sel_layers)
 
 
 def circuit_unitary(angles: torch.Tensor, n_qubits: int, imprimitive: str = "CNOT",
@@ -401,8 +365,7 @@ def circuit_unitary(angles: torch.Tensor, n_qubits: int, imprimitive: str = "CNO
     _require_device(angles, "the circuit weights")
     device = angles.device
     ang = _as_f64(angles, device)
-    circ = Circuit(n_qubits=n_qubits, encoding="none", imprimitive=imprimitive, measure="probs", n_rounds=1,
-                   n_blocks=1, sel_layers=ang.shape[0])
+    circ = _weights_only_circuit(n_qubits, ang.shape[0], imprimitive)
     if tuple(ang.reshape(circ.angles_shape).shape) != circ.angles_shape:
         raise ValueError(f"angles must have shape (S, {n_qubits}, 3); got {tuple(angles.shape)}")
     d = 1 << n_qubits
@@ -411,11 +374,9 @@ def circuit_unitary(angles: torch.Tensor, n_qubits: int, imprimitive: str = "CNO
     if n_qubits > 10:
         # the wide kernel writes U^T (columns contiguous); hand back the transposed view: indexing is <k|U|j> as
         # below, and qconv_unitary_forward recognises the layout
-        _capi.check(_capi.lib().qiddm_circuit_unitary_wide(ctypes.byref(cs), ang.data_ptr(), u.data_ptr(),
-                                                           _stream_ptr(device)))
+        _capi.launch("qiddm_circuit_unitary_wide", device, cs, ang, u)
         return torch.view_as_complex(u).transpose(0, 1)
-    _capi.check(_capi.lib().qiddm_circuit_unitary(ctypes.byref(cs), ang.data_ptr(), u.data_ptr(),
-                                                  _stream_ptr(device)))
+    _capi.launch("qiddm_circuit_unitary", device, cs, ang, u)
     return torch.view_as_complex(u)
 
 
@@ -438,17 +399,27 @@ def dense_unitary_forward(x: torch.Tensor, operand: torch.Tensor, n_qubits: int,
         xx = xx.contiguous()
     b, f = xx.shape
     d = 1 << n_qubits
-    lib = _capi.lib()
-    st = _stream_ptr(device)
     v = torch.empty(b, d, dtype=torch.float32, device=device)
-    _capi.check(lib.qiddm_amp_embed_rows(xx.data_ptr(), b, xx.stride(0), f, n_qubits, float(pad_with), 0.0, v.data_ptr(), st))
+    _capi.launch("qiddm_amp_embed_rows", device, xx, b, xx.stride(0), f, n_qubits, float(pad_with), 0.0, v)
     amps = torch.mm(v, operand)                              # (B, 2 cols): the plain library GEMM
     out = torch.empty(b, cols, dtype=torch.float64, device=device)
-    _capi.check(lib.qiddm_prob_post(amps.data_ptr(), b, cols, float(post_scale), out.data_ptr(), st))
+    _capi.launch("qiddm_prob_post", device, amps, b, cols, float(post_scale), out)
     return out
 
 
 _qconv_workspaces = {}
+
+
+def _conv_out(h: int, w: int, kernel_size, padding):
+    """(H_out, W_out) of a stride-1 convolution."""
+    return h + 2 * padding[0] - kernel_size[0] + 1, w + 2 * padding[1] - kernel_size[1] + 1
+
+
+def _unitary_real(u: torch.Tensor):
+    """(the (D, D, 2) float64 view of ``u`` the library reads, whether that view holds U^T): the transposed view
+    ``circuit_unitary`` returns for n > 10 goes in as it is."""
+    transposed = (not u.is_contiguous()) and u.transpose(0, 1).is_contiguous()
+    return torch.view_as_real(u.transpose(0, 1) if transposed else u.contiguous()), transposed
 
 
 def qconv_unitary_forward(x: torch.Tensor, unitary: torch.Tensor, n_qubits: int, out_channels: int, kernel_size,
@@ -474,12 +445,8 @@ def qconv_unitary_forward(x: torch.Tensor, unitary: torch.Tensor, n_qubits: int,
     if tuple(unitary.shape) != (d, d) or unitary.dtype != torch.complex128:
         raise ValueError(f"unitary must be ({d}, {d}) complex128; got {tuple(unitary.shape)} {unitary.dtype}")
     xx = _as_f64(x, device).contiguous()
-    transposed = (not unitary.is_contiguous()) and unitary.transpose(0, 1).is_contiguous()
-    ur = torch.view_as_real(unitary.transpose(0, 1) if transposed else unitary.contiguous())
-    lib = _capi.lib()
-    need = lib.qiddm_qconv_unitary_workspace_bytes(n_qubits, c, kh, kw, out_channels)
-    if need < 0:
-        _capi.check(int(need))
+    ur, transposed = _unitary_real(unitary)
+    need = _capi.query("qiddm_qconv_unitary_workspace_bytes", n_qubits, c, kh, kw, out_channels)
     reuse = False
     if packed is not None and packed_key is not None and not torch.cuda.is_current_stream_capturing():
         bn_key = None if batch_norm is None else tuple(
@@ -495,9 +462,9 @@ def qconv_unitary_forward(x: torch.Tensor, unitary: torch.Tensor, n_qubits: int,
     else:
         ws = _scratch(_qconv_workspaces, "qconv", need, device)
     he, we = (2 * h, 2 * w) if upsample2x else (h, w)
-    ho, wo = he + 2 * ph - kh + 1, we + 2 * pw - kw + 1
+    ho, wo = _conv_out(he, we, kernel_size, padding)
     y = torch.empty(b, out_channels, max(ho, 0), max(wo, 0), dtype=torch.float64, device=device)
-    bn_ref, keep = None, []
+    bn_struct, keep = None, []
     if batch_norm is not None:
         if batch_norm.running_mean is None or batch_norm.running_var is None:
             raise ValueError("the fused BatchNorm epilogue needs running statistics (eval mode)")
@@ -512,10 +479,9 @@ def qconv_unitary_forward(x: torch.Tensor, unitary: torch.Tensor, n_qubits: int,
         bn_struct = _capi.BatchNormStruct(weight=f64(batch_norm.weight), bias=f64(batch_norm.bias),
                                           running_mean=f64(batch_norm.running_mean),
                                           running_var=f64(batch_norm.running_var), eps=float(batch_norm.eps))
-        bn_ref = ctypes.byref(bn_struct)
-    _capi.check(lib.qiddm_qconv_unitary_forward(n_qubits, 0 if reuse else ur.data_ptr(), xx.data_ptr(), b, c, h, w, kh, kw, ph, pw,
-                                                out_channels, int(bool(upsample2x)), bn_ref, int(transposed), y.data_ptr(),
-                                                ws.data_ptr(), ws.numel(), _stream_ptr(device)))
+    # u = 0 (NULL): `ws` still holds the packing of an earlier call, the pack launch is skipped
+    _capi.launch("qiddm_qconv_unitary_forward", device, n_qubits, 0 if reuse else ur, xx, b, c, h, w, kh, kw, ph, pw,
+                 out_channels, int(bool(upsample2x)), bn_struct, int(transposed), y, ws, ws.numel())
     return y
 
 
@@ -530,8 +496,7 @@ def conv1x1_forward(x: torch.Tensor, weight: torch.Tensor, bias) -> torch.Tensor
         raise ValueError(f"weight expects {wt.shape[1]} input channels, x has {c}")
     bs = None if bias is None else _as_f64(bias.detach(), device).contiguous()
     y = torch.empty(b, wt.shape[0], h, w, dtype=torch.float64, device=device)
-    _capi.check(_capi.lib().qiddm_conv1x1_forward(xx.data_ptr(), wt.data_ptr(), 0 if bs is None else bs.data_ptr(), b,
-                                                  c, wt.shape[0], h * w, y.data_ptr(), _stream_ptr(device)))
+    _capi.launch("qiddm_conv1x1_forward", device, xx, wt, bs, b, c, wt.shape[0], h * w, y)
     return y
 
 
@@ -554,17 +519,11 @@ class _Conv1x1HeadFunction(torch.autograd.Function):
         b, c, h, w = xx.shape
         g = _as_f64(gy, device).contiguous()
         wt = _as_f64(weight.detach(), device).reshape(-1).contiguous()
-        lib = _capi.lib()
         gx = torch.empty_like(xx) if ctx.needs_input_grad[0] else None
         gw = torch.empty(c, dtype=torch.float64, device=device) if ctx.needs_input_grad[1] else None
         gb = torch.empty(1, dtype=torch.float64, device=device) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        part = torch.empty(lib.qiddm_conv1x1_head_partials(b, h * w), c + 1, dtype=torch.float64, device=device)
-
-        def ptr(t):
-            return 0 if t is None else t.data_ptr()
-
-        _capi.check(lib.qiddm_conv1x1_head_backward(xx.data_ptr(), wt.data_ptr(), g.data_ptr(), b, c, h * w, ptr(gx),
-                                                    ptr(gw), ptr(gb), part.data_ptr(), _stream_ptr(device)))
+        part = torch.empty(_capi.query("qiddm_conv1x1_head_partials", b, h * w), c + 1, dtype=torch.float64, device=device)
+        _capi.launch("qiddm_conv1x1_head_backward", device, xx, wt, g, b, c, h * w, gx, gw, gb, part)
         return (None if gx is None else gx.to(x.dtype)), (None if gw is None else gw.reshape(weight.shape).to(weight.dtype)), \
             (None if gb is None else gb)
 
@@ -633,12 +592,8 @@ def train_step(circ: Circuit, x: torch.Tensor, noise: torch.Tensor, schedule: to
         raise ValueError(f"noise must have shape {(batch, pixels)}; got {tuple(nz.shape)}")
     if tuple(wd.shape) != (circ.n_qubits, pixels) or tuple(wu.shape) != (pixels, circ.n_qubits):
         raise ValueError("linear_down / linear_up must map pixels -> n_qubits -> pixels")
-    lib = _capi.lib()
     cs = circ.c_struct(precision)
-    need = lib.qiddm_train_workspace_bytes(ctypes.byref(cs), batch, pixels, tau)
-    if need < 0:
-        _capi.check(int(need))
-    ws = _scratch(_train_workspaces, "train", need, device)
+    ws = _scratch(_train_workspaces, "train", _capi.query("qiddm_train_workspace_bytes", cs, batch, pixels, tau), device)
     f64 = dict(dtype=torch.float64, device=device)
     out = {"loss": torch.empty((), **f64), "w_up": torch.empty_like(wu), "b_up": torch.empty(pixels, **f64)}
     if train_quantum:
@@ -649,7 +604,7 @@ def train_step(circ: Circuit, x: torch.Tensor, noise: torch.Tensor, schedule: to
     if want_elem_loss:
         out["elem_loss"] = torch.empty(batch * tau, pixels, **f64)
 
-    def ptr(t):
+    def ptr(t):                          # addresses stored into the struct's fields
         return 0 if t is None else t.data_ptr()
 
     args = _capi.TrainArgs(
@@ -659,9 +614,22 @@ def train_step(circ: Circuit, x: torch.Tensor, noise: torch.Tensor, schedule: to
         g_w_down=ptr(out.get("w_down")), g_b_down=ptr(out.get("b_down")), g_angles=ptr(out.get("angles")),
         g_w_up=ptr(out["w_up"]), g_b_up=ptr(out["b_up"]), recon=ptr(out.get("recon")),
         elem_loss=ptr(out.get("elem_loss")), rng_state=ptr(rng_state))
-    _capi.check(lib.qiddm_train_step(ctypes.byref(cs), ctypes.byref(args), ws.data_ptr(), ws.numel(),
-                                     _stream_ptr(device)))
+    _capi.launch("qiddm_train_step", device, cs, args, ws, ws.numel())
     return out
+
+
+def _qconv_circuit(n_qubits, sel_layers, features):
+    return Circuit(n_qubits=n_qubits, encoding="amplitude", imprimitive="CNOT", measure="probs",
+                   n_rounds=1, n_blocks=1, sel_layers=sel_layers, n_features=features,
+                   enc_offset=0.1, pad_with=0.5)
+
+
+def _adjoint_finalize(cs, angles64: torch.Tensor, kp: torch.Tensor, device) -> torch.Tensor:
+    """dL/dangles (n_rot, 3) float64 from the (n_partials, n_rot, 8) slabs an adjoint sweep of ``cs`` left
+    (``qiddm_adjoint_finalize``); ``angles64``: the float64 contiguous angles of the gate table."""
+    ga = torch.empty(kp.shape[1], 3, dtype=torch.float64, device=device)
+    _capi.launch("qiddm_adjoint_finalize", device, cs, angles64, kp, kp.shape[0], ga)
+    return ga
 
 
 def qconv_forward(x: torch.Tensor, angles: torch.Tensor, n_qubits: int, out_channels: int, kernel_size,
@@ -676,24 +644,13 @@ def qconv_forward(x: torch.Tensor, angles: torch.Tensor, n_qubits: int, out_chan
     b, c, h, w = x.shape
     kh, kw = kernel_size
     ph, pw = padding
-    circ = Circuit(n_qubits=n_qubits, encoding="amplitude", imprimitive="CNOT", measure="probs",
-                   n_rounds=1, n_blocks=1, sel_layers=angles.shape[0], n_features=c * kh * kw,
-                   enc_offset=0.1, pad_with=0.5)
+    circ = _qconv_circuit(n_qubits, angles.shape[0], c * kh * kw)
     xx = _as_f64(x, device)
     ang = _as_f64(angles, device)
-    ho, wo = h + 2 * ph - kh + 1, w + 2 * pw - kw + 1
-    y = torch.empty(b, out_channels, ho, wo, dtype=torch.float64, device=device)
-    cs = circ.c_struct(precision)
-    _capi.check(_capi.lib().qiddm_qconv_forward(ctypes.byref(cs), xx.data_ptr(), b, c, h, w, kh, kw, ph, pw,
-                                                ang.data_ptr(), out_channels, y.data_ptr(),
-                                                _stream_ptr(device)))
+    y = torch.empty(b, out_channels, *_conv_out(h, w, kernel_size, padding), dtype=torch.float64, device=device)
+    _capi.launch("qiddm_qconv_forward", device, circ.c_struct(precision), xx, b, c, h, w, kh, kw, ph, pw, ang,
+                 out_channels, y)
     return y
-
-
-def _qconv_circuit(n_qubits, sel_layers, features):
-    return Circuit(n_qubits=n_qubits, encoding="amplitude", imprimitive="CNOT", measure="probs",
-                   n_rounds=1, n_blocks=1, sel_layers=sel_layers, n_features=features,
-                   enc_offset=0.1, pad_with=0.5)
 
 
 def qconv_backward(x: torch.Tensor, angles: torch.Tensor, grad_y: torch.Tensor, n_qubits: int, kernel_size, padding,
@@ -711,28 +668,18 @@ def qconv_backward(x: torch.Tensor, angles: torch.Tensor, grad_y: torch.Tensor, 
     xx = _as_f64(x, device)
     gy = _as_f64(grad_y, device)
     ang = _as_f64(angles, device)
-    ho, wo = h + 2 * ph - kh + 1, w + 2 * pw - kw + 1
+    ho, wo = _conv_out(h, w, kernel_size, padding)
     m = b * ho * wo
-    lib = _capi.lib()
     cs = circ.c_struct(precision)
     table = prepare_gates(circ, ang.reshape(circ.angles_shape), precision)
-    n_rot = lib.qiddm_num_rot_gates(ctypes.byref(cs))
-    n_part = lib.qiddm_adjoint_partials(ctypes.byref(cs), m)
-    if n_part < 0:
-        _capi.check(-2)
-    kp = torch.empty(n_part, n_rot, 8, dtype=dtype, device=device)
+    kp = torch.empty(_capi.query("qiddm_adjoint_partials", cs, m), _capi.query("qiddm_num_rot_gates", cs), 8,
+                     dtype=dtype, device=device)
     gfeat = gx = None
     if with_input:
         gfeat = torch.empty(m, c * kh * kw, dtype=dtype, device=device)
         gx = torch.empty(b, c, h, w, dtype=torch.float64, device=device)
-    _capi.check(lib.qiddm_qconv_backward(ctypes.byref(cs), xx.data_ptr(), b, c, h, w, kh, kw, ph, pw,
-                                         table.data_ptr(), gy.data_ptr(), out_channels, kp.data_ptr(),
-                                         0 if gfeat is None else gfeat.data_ptr(),
-                                         0 if gx is None else gx.data_ptr(), _stream_ptr(device)))
-    ga = torch.empty(n_rot, 3, dtype=torch.float64, device=device)
-    _capi.check(lib.qiddm_adjoint_finalize(ctypes.byref(cs), ang.data_ptr(), kp.data_ptr(), n_part,
-                                           ga.data_ptr(), _stream_ptr(device)))
-    return ga.reshape(angles.shape), gx
+    _capi.launch("qiddm_qconv_backward", device, cs, xx, b, c, h, w, kh, kw, ph, pw, table, gy, out_channels, kp, gfeat, gx)
+    return _adjoint_finalize(cs, ang, kp, device).reshape(angles.shape), gx
 
 
 class _QConvFunction(torch.autograd.Function):
@@ -845,39 +792,28 @@ def _angle_grads_off_stream(hpart, n_part, angles, n_qubits, f, c_out, co, devic
 
 def _unitary_rows(u, n_qubits, f, c_out, co, device):
     """(F + 1, 2 co) float32 rows table of the backward (``qiddm_qconv_train_rows``)."""
-    transposed = (not u.is_contiguous()) and u.transpose(0, 1).is_contiguous()
-    ur = torch.view_as_real(u.transpose(0, 1) if transposed else u.contiguous())
+    ur, transposed = _unitary_real(u)
     rt = torch.empty(f + 1, 2 * co, dtype=torch.float32, device=device)
-    _capi.check(_capi.lib().qiddm_qconv_train_rows(n_qubits, ur.data_ptr(), int(transposed), f, c_out, co,
-                                                   rt.data_ptr(), _stream_ptr(device)))
+    _capi.launch("qiddm_qconv_train_rows", device, n_qubits, ur, int(transposed), f, c_out, co, rt)
     return rt
 
 
 def _angle_grads_from_h(hpart, n_part, angles, n_qubits, f, c_out, co, device):
     """dL/dangles = 2 Re sum_c <e_2c| dU/dangle |h_c> from the h partial slabs: start vectors
     (``qiddm_qconv_train_vectors``), one adjoint sweep per channel (``qiddm_matrix_adjoint``), finalize."""
-    lib = _capi.lib()
-    st = _stream_ptr(device)
     d = 1 << n_qubits
     psi0 = torch.empty(c_out, d, 2, dtype=torch.float64, device=device)
     lam = torch.empty(c_out, d, 2, dtype=torch.float64, device=device)
-    _capi.check(lib.qiddm_qconv_train_vectors(n_qubits, hpart.data_ptr(), n_part, f, c_out, co, psi0.data_ptr(),
-                                              lam.data_ptr(), st))
+    _capi.launch("qiddm_qconv_train_vectors", device, n_qubits, hpart, n_part, f, c_out, co, psi0, lam)
     ang = _as_f64(angles.detach(), device).contiguous()
-    circ = Circuit(n_qubits=n_qubits, encoding="none", imprimitive="CNOT", measure="probs", n_rounds=1,
-                   n_blocks=1, sel_layers=ang.shape[0])
+    circ = _weights_only_circuit(n_qubits, ang.shape[0])
     cs = circ.c_struct("f64")
     table = prepare_gates(circ, ang.reshape(circ.angles_shape), "f64")
-    n_rot = lib.qiddm_num_rot_gates(ctypes.byref(cs))
-    kparts = lib.qiddm_matrix_adjoint_partials(c_out)
-    kp = torch.empty(kparts, n_rot, 8, dtype=torch.float64, device=device)
-    need = lib.qiddm_matrix_adjoint_workspace_bytes(ctypes.byref(cs), c_out)
-    ws = _scratch(_workspaces, "matrix-adjoint", need, device)
-    _capi.check(lib.qiddm_matrix_adjoint(ctypes.byref(cs), psi0.data_ptr(), lam.data_ptr(), c_out, table.data_ptr(),
-                                         kp.data_ptr(), ws.data_ptr(), ws.numel(), st))
-    ga = torch.empty(n_rot, 3, dtype=torch.float64, device=device)
-    _capi.check(lib.qiddm_adjoint_finalize(ctypes.byref(cs), ang.data_ptr(), kp.data_ptr(), kparts, ga.data_ptr(), st))
-    return ga.reshape(angles.shape)
+    kp = torch.empty(_capi.query("qiddm_matrix_adjoint_partials", c_out), _capi.query("qiddm_num_rot_gates", cs), 8,
+                     dtype=torch.float64, device=device)
+    ws = _scratch(_workspaces, "matrix-adjoint", _capi.query("qiddm_matrix_adjoint_workspace_bytes", cs, c_out), device)
+    _capi.launch("qiddm_matrix_adjoint", device, cs, psi0, lam, c_out, table, kp, ws, ws.numel())
+    return _adjoint_finalize(cs, ang, kp, device).reshape(angles.shape)
 
 
 # QIDDM_QCONV_X32=1: hand the thin-product backward a float32 copy of the activations (qiddm_qconv_train_backward_x32).
@@ -903,14 +839,13 @@ def _qconv_unitary_backward_gemm(x, grad_y, u, n_qubits, c_out, kernel_size, pad
     kh, kw = kernel_size
     ph, pw = padding
     f, d = c * kh * kw, 1 << n_qubits
-    ho, wo = h + 2 * ph - kh + 1, w + 2 * pw - kw + 1
+    ho, wo = _conv_out(h, w, kernel_size, padding)
     rt = _unitary_rows(u, n_qubits, f, c_out, c_out, device)
     r, rp = rt[:f], rt[f]                                   # (F, 2C), (2C)
     post = 0.5 * d
     hsum = torch.zeros(2 * c_out, f + 1, dtype=torch.float64, device=device)
     gx = torch.empty(b, c, h, w, dtype=torch.float64, device=device) if need_gx else None
     chunk = max(1, min(b, _GEMM_CHUNK_BYTES // max(ho * wo * f * 4, 1)))
-    lib = _capi.lib()
     for b0 in range(0, b, chunk):
         xb = x[b0:b0 + chunk]
         cb = xb.shape[0]
@@ -928,8 +863,7 @@ def _qconv_unitary_backward_gemm(x, grad_y, u, n_qubits, c_out, kernel_size, pad
         if need_gx:
             gft = (2.0 * (r @ w2.t()) - v.t() * dot.t()) * inv.t()                     # (F, Mc), transposed gradients
             gft = gft.contiguous()
-            _capi.check(lib.qiddm_qconv_fold_features(gft.data_ptr(), cb, c, h, w, kh, kw, ph, pw,
-                                                      gx[b0:b0 + cb].data_ptr(), _stream_ptr(device)))
+            _capi.launch("qiddm_qconv_fold_features", device, gft, cb, c, h, w, kh, kw, ph, pw, gx[b0:b0 + cb])
     return hsum.to(torch.float32).unsqueeze(0).contiguous(), gx
 
 
@@ -961,7 +895,7 @@ def _qconv_unitary_backward(x, angles, u, cfg, grad_y, need_gx, need_ga, bn=None
     device = x.device
     b, c, h, w = x.shape
     f = c * kh * kw
-    ho, wo = h + 2 * ph - kh + 1, w + 2 * pw - kw + 1
+    ho, wo = _conv_out(h, w, (kh, kw), (ph, pw))
     if qconv_unitary_route(n_qubits, c, (kh, kw), c_out) == "gemm":
         if bn is not None:      # library-GEMM route: apply the BatchNorm coefficients with torch
             conv_y, coef = bn
@@ -971,49 +905,30 @@ def _qconv_unitary_backward(x, angles, u, cfg, grad_y, need_gx, need_ga, bn=None
         ga = _angle_grads_off_stream(hpart, 1, angles, n_qubits, f, c_out, c_out, device) if need_ga else None
         return (None if gx is None else gx.to(x.dtype)), ga
     co = _row_channels(c_out)
-    lib = _capi.lib()
-    st = _stream_ptr(device)
     rt = _unitary_rows(u, n_qubits, f, c_out, co, device)
     # the matrix-core kernel converts every patch element to float32 anyway: hand it a float32 copy (one elementwise
     # pass; its gather then holds half the bytes in flight)
-    x32 = bn is None and _QCONV_X32 and bool(lib.qiddm_qconv_train_x32_ok(b, c, h, w, kh, kw, ph, pw, c_out, co))
+    x32 = bn is None and _QCONV_X32 and bool(_capi.query("qiddm_qconv_train_x32_ok", b, c, h, w, kh, kw, ph, pw, c_out, co))
     xx = x.detach().to(device=device, dtype=torch.float32).contiguous() if x32 else _as_f64(x, device).contiguous()
-    n_part = lib.qiddm_qconv_train_partials(b, ho, wo, f)
+    n_part = _capi.query("qiddm_qconv_train_partials", b, ho, wo, f)
     hpart = torch.empty(n_part, 2 * co, f + 1, dtype=torch.float32, device=device)
     gx = torch.empty(b, c, h, w, dtype=torch.float64, device=device) if need_gx else None
     # dL/dx from 2 co + 1 floats per pixel where the layer allows it (same-size convolution on the matrix-core
     # kernel), instead of the (F, M) feature gradients and their fold
     dx_elems = 0 if (gx is None or x32 or not _QCONV_DX) else \
-        lib.qiddm_qconv_train_dx_elems(n_qubits, b, c, h, w, kh, kw, ph, pw, c_out, co)
+        _capi.query("qiddm_qconv_train_dx_elems", n_qubits, b, c, h, w, kh, kw, ph, pw, c_out, co)
     wpix = torch.empty(dx_elems, dtype=torch.float32, device=device) if dx_elems > 0 else None
     gfeat_t = torch.empty(f, b * ho * wo, dtype=torch.float32, device=device) if wpix is None else None
-    # a channel slice of a wider contiguous gradient (one half of torch.cat's backward) is read in place by the
-    # per-pixel-row entry point; anything else is made dense first
-    gy = _as_f64(grad_y, device)
-    gy_bstride = 0
-    if wpix is not None and bn is None and not gy.is_contiguous() and gy.dim() == 4 and b > 1 \
-            and gy.stride()[1:] == (ho * wo, wo, 1) and gy.stride(0) >= c_out * ho * wo \
-            and b * gy.stride(0) < (1 << 32):
-        gy_bstride = gy.stride(0)
-    else:
-        gy = gy.contiguous()
-
-    def ptr(t):
-        return 0 if t is None else t.data_ptr()
-
+    gy = _as_f64(grad_y, device)            # dense: grad_y_batch_stride below is always 0
+    geom = (n_qubits, xx, b, c, h, w, kh, kw, ph, pw)
     if bn is not None:
         conv_y, coef = bn
-        _capi.check(lib.qiddm_qconv_train_backward_bn(n_qubits, xx.data_ptr(), b, c, h, w, kh, kw, ph, pw, gy.data_ptr(),
-                                                      conv_y.data_ptr(), coef.data_ptr(), c_out, rt.data_ptr(), co,
-                                                      ptr(gfeat_t), ptr(wpix), hpart.data_ptr(), ptr(gx), st))
+        _capi.launch("qiddm_qconv_train_backward_bn", device, *geom, gy, conv_y, coef, c_out, rt, co, gfeat_t, wpix, hpart, gx)
     elif wpix is not None:
-        _capi.check(lib.qiddm_qconv_train_backward_dx(n_qubits, xx.data_ptr(), b, c, h, w, kh, kw, ph, pw,
-                                                      gy.data_ptr(), gy_bstride, c_out, rt.data_ptr(), co,
-                                                      wpix.data_ptr(), hpart.data_ptr(), gx.data_ptr(), st))
+        _capi.launch("qiddm_qconv_train_backward_dx", device, *geom, gy, 0, c_out, rt, co, wpix, hpart, gx)
     else:
-        entry = lib.qiddm_qconv_train_backward_x32 if x32 else lib.qiddm_qconv_train_backward
-        _capi.check(entry(n_qubits, xx.data_ptr(), b, c, h, w, kh, kw, ph, pw, gy.data_ptr(), c_out, rt.data_ptr(),
-                          co, gfeat_t.data_ptr(), hpart.data_ptr(), ptr(gx), st))
+        _capi.launch("qiddm_qconv_train_backward_x32" if x32 else "qiddm_qconv_train_backward", device, *geom, gy, c_out,
+                     rt, co, gfeat_t, hpart, gx)
     ga = _angle_grads_off_stream(hpart, n_part, angles, n_qubits, f, c_out, co, device) if need_ga else None
     return (None if gx is None else gx.to(x.dtype)), ga
 
@@ -1025,10 +940,31 @@ def qconv_unitary_execute(x: torch.Tensor, angles: torch.Tensor, n_qubits: int, 
 
 
 def _norm_workspace(batch, channels, hw, device):
-    need = _capi.lib().qiddm_batchnorm_workspace_bytes(batch, channels, hw)
-    if need < 0:
-        _capi.check(-1)
+    need = _capi.query("qiddm_batchnorm_workspace_bytes", batch, channels, hw)
     return _scratch(_workspaces, "norm", need, device, floor=1 << 16)
+
+
+def _batch_norm_forward(x, weight, bias, running_mean, running_var, momentum, eps):
+    """Training-mode BatchNorm2d of a contiguous float64 (B, C, ...) tensor (``qiddm_batchnorm_train_forward``; moves the
+    running statistics in place): (y, mean, invstd), the last two (C) as the backward reads them."""
+    b, c = x.shape[:2]
+    hw = x.numel() // max(b * c, 1)
+    y = torch.empty_like(x)
+    mean = torch.empty(c, dtype=torch.float64, device=x.device)
+    invstd = torch.empty_like(mean)
+    ws = _norm_workspace(b, c, hw, x.device)
+    _capi.launch("qiddm_batchnorm_train_forward", x.device, x, b, c, hw, weight, bias, running_mean, running_var,
+                 float(momentum), float(eps), y, mean, invstd, ws, ws.numel())
+    return y, mean, invstd
+
+
+def _running_stats(bn: torch.nn.BatchNorm2d):
+    """Count this training batch as the torch module does; (running_mean, running_var) to move, or (None, None)."""
+    if not bn.track_running_stats:
+        return None, None
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return bn.running_mean, bn.running_var
 
 
 class _BatchNormTrainFunction(torch.autograd.Function):
@@ -1037,21 +973,8 @@ class _BatchNormTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps):
-        b, c = x.shape[:2]
-        hw = x.numel() // max(b * c, 1)
         x = x.contiguous()
-        y = torch.empty_like(x)
-        mean = torch.empty(c, dtype=torch.float64, device=x.device)
-        invstd = torch.empty_like(mean)
-        ws = _norm_workspace(b, c, hw, x.device)
-
-        def ptr(t):
-            return 0 if t is None else t.data_ptr()
-
-        _capi.check(_capi.lib().qiddm_batchnorm_train_forward(
-            x.data_ptr(), b, c, hw, ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var), float(momentum),
-            float(eps), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ws.numel(),
-            _stream_ptr(x.device)))
+        y, mean, invstd = _batch_norm_forward(x, weight, bias, running_mean, running_var, momentum, eps)
         ctx.save_for_backward(x, weight, mean, invstd)
         ctx.has_bias = bias is not None
         return y
@@ -1066,30 +989,24 @@ class _BatchNormTrainFunction(torch.autograd.Function):
         gw = torch.empty(c, dtype=torch.float64, device=x.device) if weight is not None else None
         gb = torch.empty(c, dtype=torch.float64, device=x.device) if ctx.has_bias else None
         ws = _norm_workspace(b, c, hw, x.device)
-
-        def ptr(t):
-            return 0 if t is None else t.data_ptr()
-
-        _capi.check(_capi.lib().qiddm_batchnorm_backward(
-            x.data_ptr(), gy.data_ptr(), b, c, hw, ptr(weight), mean.data_ptr(), invstd.data_ptr(), ptr(gx), ptr(gw),
-            ptr(gb), ws.data_ptr(), ws.numel(), _stream_ptr(x.device)))
+        _capi.launch("qiddm_batchnorm_backward", x.device, x, gy, b, c, hw, weight, mean, invstd, gx, gw, gb, ws, ws.numel())
         return gx, gw, gb, None, None, None, None
+
+
+def _batch_norm_module_ok(bn) -> bool:
+    """What ``batch_norm_train`` and ``batch_norm_eligible`` both ask of the module: training mode, a momentum, float64."""
+    return bool(bn.training and bn.momentum is not None and (bn.weight is None or bn.weight.dtype == torch.float64)
+                and (bn.running_mean is None or bn.running_mean.dtype == torch.float64))
 
 
 def batch_norm_train(bn: torch.nn.BatchNorm2d, x: torch.Tensor) -> torch.Tensor:
     """``bn(x)`` for a float64 ``BatchNorm2d`` in training mode on the device, through the HIP kernels; anything else
     (eval mode, cumulative-average momentum, other dtypes, empty batches, CPU) goes to the torch module."""
-    if not (bn.training and x.is_cuda and x.dtype == torch.float64 and x.dim() == 4 and x.numel() > 0
-            and bn.momentum is not None and (bn.weight is None or bn.weight.dtype == torch.float64)
-            and (bn.running_mean is None or bn.running_mean.dtype == torch.float64)):
+    if not (_batch_norm_module_ok(bn) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 4 and x.numel() > 0):
         return bn(x)
     if x.shape[1] != bn.num_features:
         return bn(x)       # torch raises its own message
-    if bn.track_running_stats and bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
-    rm = bn.running_mean if bn.track_running_stats else None
-    rv = bn.running_var if bn.track_running_stats else None
-    return _BatchNormTrainFunction.apply(x, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps)
+    return _BatchNormTrainFunction.apply(x, bn.weight, bn.bias, *_running_stats(bn), bn.momentum, bn.eps)
 
 
 class _QConvBNTrainFunction(torch.autograd.Function):
@@ -1105,20 +1022,7 @@ class _QConvBNTrainFunction(torch.autograd.Function):
                 kernel_size, padding):
         u = circuit_unitary(angles.detach(), n_qubits, "CNOT")
         y = qconv_unitary_forward(x, u, n_qubits, out_channels, kernel_size, padding)
-        b, c = y.shape[:2]
-        hw = y.numel() // max(b * c, 1)
-        out = torch.empty_like(y)
-        mean = torch.empty(c, dtype=torch.float64, device=y.device)
-        invstd = torch.empty_like(mean)
-        ws = _norm_workspace(b, c, hw, y.device)
-
-        def ptr(t):
-            return 0 if t is None else t.data_ptr()
-
-        _capi.check(_capi.lib().qiddm_batchnorm_train_forward(
-            y.data_ptr(), b, c, hw, ptr(bn_weight), ptr(bn_bias), ptr(running_mean), ptr(running_var), float(momentum),
-            float(eps), out.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ws.numel(),
-            _stream_ptr(y.device)))
+        out, mean, invstd = _batch_norm_forward(y, bn_weight, bn_bias, running_mean, running_var, momentum, eps)
         ctx.save_for_backward(x, angles, u, y, bn_weight, mean, invstd)
         ctx.cfg = (n_qubits, out_channels, kernel_size, padding)
         ctx.has_bias = bn_bias is not None
@@ -1135,13 +1039,8 @@ class _QConvBNTrainFunction(torch.autograd.Function):
         gb = torch.empty(c, dtype=torch.float64, device=device) if ctx.has_bias else None
         coef = torch.empty(3, c, dtype=torch.float64, device=device)
         ws = _norm_workspace(b, c, hw, device)
-
-        def ptr(t):
-            return 0 if t is None else t.data_ptr()
-
-        _capi.check(_capi.lib().qiddm_batchnorm_backward_stats(
-            y.data_ptr(), g.data_ptr(), b, c, hw, ptr(bn_weight), mean.data_ptr(), invstd.data_ptr(), ptr(gw), ptr(gb),
-            coef.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(device)))
+        _capi.launch("qiddm_batchnorm_backward_stats", device, y, g, b, c, hw, bn_weight, mean, invstd, gw, gb, coef, ws,
+                     ws.numel())
         gx, ga = _qconv_unitary_backward(x, angles, u, ctx.cfg, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                          bn=(y, coef))
         return (gx, ga, gw, gb) + (None,) * 8
@@ -1155,27 +1054,20 @@ def qconv_bn_foldable(x_shape, n_qubits: int, out_channels: int, kernel_size, pa
     route = qconv_unitary_route(n_qubits, c, (kh, kw), out_channels)
     if route != "thin":
         return route == "gemm"
-    return bool(_capi.lib().qiddm_qconv_train_bn_ok(b, c, h, w, kh, kw, ph, pw, out_channels, _row_channels(out_channels)))
+    return bool(_capi.query("qiddm_qconv_train_bn_ok", b, c, h, w, kh, kw, ph, pw, out_channels, _row_channels(out_channels)))
 
 
 def batch_norm_eligible(bn: torch.nn.BatchNorm2d, channels: int) -> bool:
     """Whether a float64 training-mode ``BatchNorm2d`` runs on the HIP kernels (the module-side half of
     ``batch_norm_train``'s test)."""
-    return bool(type(bn) is torch.nn.BatchNorm2d and bn.training and bn.momentum is not None
-                and bn.num_features == channels
-                and (bn.weight is None or bn.weight.dtype == torch.float64)
-                and (bn.running_mean is None or bn.running_mean.dtype == torch.float64))
+    return type(bn) is torch.nn.BatchNorm2d and bn.num_features == channels and _batch_norm_module_ok(bn)
 
 
 def qconv_bn_train(x: torch.Tensor, angles: torch.Tensor, bn: torch.nn.BatchNorm2d, n_qubits: int, out_channels: int,
                    kernel_size, padding) -> torch.Tensor:
     """``bn(QConv2d(x))`` through the circuit unitary with the BatchNorm backward folded into the convolution's
     (``_QConvBNTrainFunction``).  The caller has checked ``qconv_unitary_trainable`` and ``batch_norm_eligible``."""
-    if bn.track_running_stats and bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
-    rm = bn.running_mean if bn.track_running_stats else None
-    rv = bn.running_var if bn.track_running_stats else None
-    return _QConvBNTrainFunction.apply(x, angles, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps, n_qubits,
+    return _QConvBNTrainFunction.apply(x, angles, bn.weight, bn.bias, *_running_stats(bn), bn.momentum, bn.eps, n_qubits,
                                        out_channels, tuple(kernel_size), tuple(padding))
 
 
@@ -1188,8 +1080,7 @@ class _Upsample2xFunction(torch.autograd.Function):
         x = x.contiguous()
         b, c, h, w = x.shape
         y = torch.empty(b, c, 2 * h, 2 * w, dtype=torch.float64, device=x.device)
-        _capi.check(_capi.lib().qiddm_upsample2x_forward(x.data_ptr(), b * c, h, w, a_h.data_ptr(), a_w.data_ptr(),
-                                                         y.data_ptr(), _stream_ptr(x.device)))
+        _capi.launch("qiddm_upsample2x_forward", x.device, x, b * c, h, w, a_h, a_w, y)
         ctx.save_for_backward(a_h, a_w)
         ctx.shape = (b, c, h, w)
         return y
@@ -1200,8 +1091,7 @@ class _Upsample2xFunction(torch.autograd.Function):
         b, c, h, w = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty(b, c, h, w, dtype=torch.float64, device=gy.device)
-        _capi.check(_capi.lib().qiddm_upsample2x_backward(gy.data_ptr(), b * c, h, w, a_h.data_ptr(), a_w.data_ptr(),
-                                                          gx.data_ptr(), _stream_ptr(gy.device)))
+        _capi.launch("qiddm_upsample2x_backward", gy.device, gy, b * c, h, w, a_h, a_w, gx)
         return gx, None, None
 
 
@@ -1214,7 +1104,7 @@ class _MaxPool2Function(torch.autograd.Function):
         x = x.contiguous()
         b, c, h, w = x.shape
         y = torch.empty(b, c, h // 2, w // 2, dtype=torch.float64, device=x.device)
-        _capi.check(_capi.lib().qiddm_maxpool2_forward(x.data_ptr(), b * c, h, w, y.data_ptr(), _stream_ptr(x.device)))
+        _capi.launch("qiddm_maxpool2_forward", x.device, x, b * c, h, w, y)
         ctx.save_for_backward(x)
         return y
 
@@ -1224,8 +1114,7 @@ class _MaxPool2Function(torch.autograd.Function):
         b, c, h, w = x.shape
         gy = gy.contiguous()
         gx = torch.empty_like(x)
-        _capi.check(_capi.lib().qiddm_maxpool2_backward(x.data_ptr(), gy.data_ptr(), b * c, h, w, gx.data_ptr(),
-                                                        _stream_ptr(x.device)))
+        _capi.launch("qiddm_maxpool2_backward", x.device, x, gy, b * c, h, w, gx)
         return gx
 
 
@@ -1257,13 +1146,12 @@ def run_shift_sweep(circ: Circuit, inputs, angles: torch.Tensor, grad_out: torch
     x, ld, circ2 = _prep_inputs(circ, inputs, dtype, device)
     circ = circ2 or circ
     batch = x.shape[0] if x is not None else grad_out.shape[0]      # encoding "none": one row of grad_out per sample
-    lib = _capi.lib()
     cs = circ.c_struct(precision)
     table = prepare_gates(circ, angles, precision)
     g = grad_out.to(device=device, dtype=dtype).contiguous()
     want_inputs = with_inputs and circ.encoding in ("rz", "ry", "ry_blocks")
-    total = lib.qiddm_num_shift_replicas(ctypes.byref(cs), 1 if want_inputs else 0)
-    n_rot = lib.qiddm_num_rot_gates(ctypes.byref(cs))
+    total = _capi.query("qiddm_num_shift_replicas", cs, 1 if want_inputs else 0)
+    n_rot = _capi.query("qiddm_num_rot_gates", cs)
     chunk = max(2, min(65534, (max_dots_elems // max(batch, 1)) // 2 * 2, total))
     if circ.n_qubits > 10:
         chunk = min(chunk, 256)   # bounds the tiled kernel's workspace (one slab per replica x block)
@@ -1273,10 +1161,8 @@ def run_shift_sweep(circ: Circuit, inputs, angles: torch.Tensor, grad_out: torch
     while first < total:
         cnt = min(chunk, total - first)
         dots = torch.empty(cnt, batch, dtype=dtype, device=device)
-        ws_buf, ws_ptr, ws_bytes = _workspace(circ, precision, batch, cnt, device)
-        _capi.check(lib.qiddm_forward_shifted(ctypes.byref(cs), x.data_ptr(), batch, ld,
-                                              table.data_ptr(), g.data_ptr(), g.shape[1], first, cnt,
-                                              dots.data_ptr(), ws_ptr, ws_bytes, _stream_ptr(device)))
+        ws, ws_bytes = _workspace(circ, precision, batch, cnt, device)
+        _capi.launch("qiddm_forward_shifted", device, cs, x, batch, ld, table, g, g.shape[1], first, cnt, dots, ws, ws_bytes)
         w_hi = min(first + cnt, 6 * n_rot)
         if first < w_hi:
             w_sum[first:w_hi] = dots[: w_hi - first].to(torch.float64).sum(dim=1)
@@ -1304,35 +1190,22 @@ def run_adjoint(circ: Circuit, inputs, angles: torch.Tensor, grad_out: torch.Ten
     x, ld, circ2 = _prep_inputs(circ, inputs, dtype, device)
     circ = circ2 or circ
     batch = x.shape[0] if x is not None else grad_out.shape[0]      # encoding "none": one row of grad_out per sample
-    lib = _capi.lib()
     cs = circ.c_struct(precision)
     table = prepare_gates(circ, angles, precision)
     g = grad_out.to(device=device, dtype=dtype).contiguous()
-    n_rot = lib.qiddm_num_rot_gates(ctypes.byref(cs))
-    n_part = lib.qiddm_adjoint_partials(ctypes.byref(cs), batch)
-    if n_part < 0:
-        _capi.check(-2)
-    kp = torch.empty(n_part, n_rot, 8, dtype=dtype, device=device)
+    kp = torch.empty(_capi.query("qiddm_adjoint_partials", cs, batch), _capi.query("qiddm_num_rot_gates", cs), 8,
+                     dtype=dtype, device=device)
     gin = None
     gin_cols = circ.features if circ.encoding == "amplitude" else circ.n_qubits
     if with_inputs and circ.encoding != "none":
         gin = torch.empty(batch, gin_cols, dtype=dtype, device=device)
-    x_ptr = 0 if x is None else x.data_ptr()
+    sweep = (cs, x, batch, ld, table, g, g.shape[1], kp, gin, gin_cols)
     if circ.n_qubits > 10:
-        need = lib.qiddm_adjoint_workspace_bytes(ctypes.byref(cs), batch)
-        ws = _scratch(_workspaces, "adjoint", need, device)
-        _capi.check(lib.qiddm_backward_adjoint_wide(ctypes.byref(cs), x_ptr, batch, ld, table.data_ptr(),
-                                                    g.data_ptr(), g.shape[1], kp.data_ptr(),
-                                                    0 if gin is None else gin.data_ptr(), gin_cols, ws.data_ptr(),
-                                                    ws.numel(), _stream_ptr(device)))
+        ws = _scratch(_workspaces, "adjoint", _capi.query("qiddm_adjoint_workspace_bytes", cs, batch), device)
+        _capi.launch("qiddm_backward_adjoint_wide", device, *sweep, ws, ws.numel())
     else:
-        _capi.check(lib.qiddm_backward_adjoint(ctypes.byref(cs), x_ptr, batch, ld, table.data_ptr(),
-                                               g.data_ptr(), g.shape[1], kp.data_ptr(),
-                                               0 if gin is None else gin.data_ptr(), gin_cols, _stream_ptr(device)))
-    a64 = angles.detach().to(torch.float64).contiguous()
-    ga = torch.empty(n_rot, 3, dtype=torch.float64, device=device)
-    _capi.check(lib.qiddm_adjoint_finalize(ctypes.byref(cs), a64.data_ptr(), kp.data_ptr(), n_part,
-                                           ga.data_ptr(), _stream_ptr(device)))
+        _capi.launch("qiddm_backward_adjoint", device, *sweep)
+    ga = _adjoint_finalize(cs, angles.detach().to(torch.float64).contiguous(), kp, device)
     return ga.reshape(circ.angles_shape), (None if gin is None else gin.to(torch.float64))
 
 

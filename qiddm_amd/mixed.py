@@ -24,7 +24,6 @@ tile-fused reverse sweep.
 from __future__ import annotations
 
 import contextlib
-import ctypes
 
 import torch
 
@@ -220,45 +219,34 @@ class _Launch:
         for dst, (kind, wire, a, p, scale) in zip(self.prog, low.ops):
             dst.kind, dst.wire, dst.a, dst.reserved, dst.p, dst.scale = kind, wire, a, 0, p, scale
 
-    def stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _prefix(self, rows, gates, feats):
         """The arguments every compute entry point starts with: ``n_qubits`` .. ``batch``."""
-        return (self.n, self.prec, self.prog, len(self.prog), _ptr(rows), 0 if rows is None else rows.stride(0),
-                self.n_rows, _ptr(feats), 0 if feats is None else feats.stride(0),
-                0 if feats is None else feats.shape[1], 0.0, self.pad_with, _ptr(gates),
+        return (self.n, self.prec, self.prog, len(self.prog), rows, 0 if rows is None else rows.stride(0),
+                self.n_rows, feats, 0 if feats is None else feats.stride(0),
+                0 if feats is None else feats.shape[1], 0.0, self.pad_with, gates,
                 0 if gates is None else gates.shape[0], self.measure, self.batch)
 
     def _resident(self):
         """Samples per chunk of the tile-fused engine."""
         return min(self.batch, wide_resident_samples) if wide_resident_samples > 0 else self.batch
 
-    @staticmethod
-    def _checked(need):
-        """The result of a ``*_workspace_bytes`` call, or the library's refusal."""
-        if need < 0:
-            _capi.check(int(need))
-        return need
-
     def _fresh(self, need):
         """A workspace for this call alone.  The tile-fused engine and the backward take up to 1 GiB: handed back to the
         caching allocator after the call instead of being kept."""
-        return torch.empty(max(self._checked(need), 256), dtype=torch.uint8, device=self.device)
+        return torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
 
     def forward(self, rows, gates, feats, wide=False):
         n, batch = self.n, self.batch
         out = torch.empty(batch, (1 << n) if self.measure == _capi.MEAS_PROBS else n, dtype=torch.float64,
                           device=self.device)
-        lib = _capi.lib()
         if wide:
-            ws = self._fresh(lib.qiddm_mixed_wide_workspace_bytes(n, self.prec, self._resident(), self.prog, len(self.prog)))
+            ws = self._fresh(_capi.query("qiddm_mixed_wide_workspace_bytes", n, self.prec, self._resident(), self.prog,
+                                         len(self.prog)))
         else:
-            need = self._checked(lib.qiddm_mixed_workspace_bytes(n, self.prec, batch, len(self.prog)))
+            need = _capi.query("qiddm_mixed_workspace_bytes", n, self.prec, batch, len(self.prog))
             ws = _c._scratch(_c._workspaces, "mixed", need, self.device, floor=256)  # eager: cached per stream
-        entry = lib.qiddm_mixed_wide_forward if wide else lib.qiddm_mixed_forward
-        _capi.check(entry(*self._prefix(rows, gates, feats), out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(),
-                          ctypes.c_void_p(self.stream())))
+        _capi.launch("qiddm_mixed_wide_forward" if wide else "qiddm_mixed_forward", self.device,
+                     *self._prefix(rows, gates, feats), out, out.stride(0), ws, ws.numel())
         return out
 
     def backward(self, rows, gates, feats, grad_out, max_blocks=0, wide=False):
@@ -269,23 +257,17 @@ class _Launch:
         g_rows = torch.empty(self.n_rows, batch, **f64) if rows is not None else None
         g_gates = torch.empty(batch, gates.shape[0], 8, **f64) if gates is not None else None
         g_feats = torch.empty(batch, feats.shape[1], **f64) if feats is not None else None
-        lib = _capi.lib()
-        grads = (grad_out.data_ptr(), grad_out.shape[1], _ptr(g_rows), _ptr(g_gates), _ptr(g_feats))
+        grads = (grad_out, grad_out.shape[1], g_rows, g_gates, g_feats)
         if wide:
-            ws = self._fresh(lib.qiddm_mixed_wide_backward_workspace_bytes(n, self.prec, self._resident(), self.prog,
-                                                                           len(self.prog)))
-            entry = lib.qiddm_mixed_wide_backward
+            ws = self._fresh(_capi.query("qiddm_mixed_wide_backward_workspace_bytes", n, self.prec, self._resident(),
+                                         self.prog, len(self.prog)))
+            entry = "qiddm_mixed_wide_backward"
         else:
-            ws = self._fresh(lib.qiddm_mixed_backward_workspace_bytes(n, self.prec, batch, self.prog, len(self.prog),
-                                                                      max_blocks))
-            entry, grads = lib.qiddm_mixed_backward, grads + (max_blocks,)
-        _capi.check(entry(*self._prefix(rows, gates, feats), *grads, ws.data_ptr(), ws.numel(),
-                          ctypes.c_void_p(self.stream())))
+            ws = self._fresh(_capi.query("qiddm_mixed_backward_workspace_bytes", n, self.prec, batch, self.prog,
+                                         len(self.prog), max_blocks))
+            entry, grads = "qiddm_mixed_backward", grads + (max_blocks,)
+        _capi.launch(entry, self.device, *self._prefix(rows, gates, feats), *grads, ws, ws.numel())
         return g_rows, None if g_gates is None else g_gates.sum(dim=0), g_feats
-
-
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
 
 
 class _MixedFunction(torch.autograd.Function):

@@ -8,8 +8,6 @@ State keys (``step``, ``exp_avg``, ``exp_avg_sq``) match torch's (``step`` is an
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _capi
@@ -35,7 +33,6 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _capi.lib()
         for group in self.param_groups:
             entries, device = [], None
             for p in group["params"]:
@@ -68,10 +65,8 @@ class FusedAdam(torch.optim.Optimizer):
                 a.numel = p.numel()
                 a.dtype = _capi.F64 if p.dtype == torch.float64 else _capi.F32
             b1, b2 = group["betas"]
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _capi.check(lib.qiddm_adam_step(arr, len(entries), float(group["lr"]), float(b1), float(b2),
-                                            float(group["eps"]), float(group["weight_decay"]),
-                                            self._sync(device).data_ptr(), ctypes.c_void_p(stream)))
+            _capi.launch("qiddm_adam_step", device, arr, len(entries), float(group["lr"]), float(b1), float(b2),
+                         float(group["eps"]), float(group["weight_decay"]), self._sync(device))
             self._keepalive = entries      # until the stream has consumed them
             for p, *_ in entries:          # the launch wrote the parameters behind autograd's back
                 torch.autograd.graph.increment_version(p)
