@@ -573,17 +573,30 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *   QIDDM_MIX_CZ / _CNOT      control `wire`, target `a`
  *   QIDDM_MIX_PHASE_DAMP / _AMP_DAMP / _DEPOL   PennyLane's PhaseDamping / AmplitudeDamping /
  *                             DepolarizingChannel with probability p on `wire`
+ *   QIDDM_MIX_CHANNEL (= 16)  a general one-wire channel on `wire`: `a` is the first of FOUR consecutive rows of `gates`,
+ *                             rows a .. a+3 hold the superoperator S (4 x 4 complex, row-major; row r = S[r][0..3] as
+ *                             (re, im)).  On every 2 x 2 block M of the wire vec(M') = S vec(M), vec(M) = (M00, M01,
+ *                             M10, M11); for Kraus operators S = sum_k K_k (x) conj(K_k).  `p` and `scale` are not read.
+ *                             `gates` is device memory the library does not look into: that S is completely positive
+ *                             and trace preserving is the caller's responsibility.  The planner and every workspace
+ *                             size treat it as AMP_DAMP on the same wire.  In the reverse sweeps the adjoint takes S^H
+ *                             per block and the op's four rows of grad_gates are zeros for every sample (channel
+ *                             operands get no gradient).  PennyLane's BitFlip, PhaseFlip, PauliError,
+ *                             GeneralizedAmplitudeDamping, ResetError, ThermalRelaxationError and QubitChannel on one
+ *                             wire are this op.
+ * Kinds 10..15 and kinds above 16 are no ops: refused as `op %d: unknown kind %d` (16 leaves the next native kinds room).
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
  * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
  * batch / n_ops, measure (batch == 0 then returns QIDDM_OK with no pointer looked at), program (not empty, starts with a
  * state preparation), negative n_rows / n_gates, angle_rows / rows_ld, gates, the ops one by one (kind, wire, target wire,
- * then the operand they index: features / feat_ld / n_features, angle row, gate, probability), max_blocks (negative:
+ * then the operand they index: features / feat_ld / n_features, angle row, gate, probability, channel rows), max_blocks (negative:
  * refused for an empty batch as well), the outputs
  * (out, out_ld | grad_out / gout_ld, grad_rows, grad_gates, grad_features), workspace.                   */
 enum {
   QIDDM_MIX_ZERO = 0, QIDDM_MIX_AMP_EMBED, QIDDM_MIX_PHASE, QIDDM_MIX_RY, QIDDM_MIX_GATE, QIDDM_MIX_CZ,
-  QIDDM_MIX_CNOT, QIDDM_MIX_PHASE_DAMP, QIDDM_MIX_AMP_DAMP, QIDDM_MIX_DEPOL
+  QIDDM_MIX_CNOT, QIDDM_MIX_PHASE_DAMP, QIDDM_MIX_AMP_DAMP, QIDDM_MIX_DEPOL,
+  QIDDM_MIX_CHANNEL = 16
 };
 typedef struct qiddm_mixed_op {
   int32_t kind, wire, a, reserved;
@@ -620,7 +633,7 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
  * of the reference's 28 x 28 noise study (src/fashion_noise.py:42-44).  rho of a sample (index (i << n) | j) lives in a
  * slab of `workspace`; the program is cut into SEGMENTS, each run by one sweep -- one launch over (tile, sample) in which
  * a workgroup holds the 2^12 elements spanned by the index-bit pairs of six wires in LDS and applies the whole segment.
- * A segment takes PHASE / CZ / PHASE_DAMP on any wires (diagonal on vec(rho)), GATE / RY / AMP_DAMP / DEPOL on its six
+ * A segment takes PHASE / CZ / PHASE_DAMP on any wires (diagonal on vec(rho)), GATE / RY / AMP_DAMP / DEPOL / CHANNEL on its six
  * wires, CNOT between two of them, and ZERO / AMP_EMBED as its first op.  Ops keep program order except where they
  * commute (no shared wire, or both diagonal).  Same arguments and results as qiddm_mixed_forward; float64 read-out with
  * fixed-order sums, no atomics: reruns are bit-identical.

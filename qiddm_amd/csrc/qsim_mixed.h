@@ -14,7 +14,9 @@
 //     PhaseDamping(g):      M01, M10 *= sqrt(1-g)
 //     AmplitudeDamping(g):  M00 += g M11;  M11 *= 1-g;  M01, M10 *= sqrt(1-g)
 //     Depolarizing(p):      M00, M11 <- (1-2p/3) own + (2p/3) other;  M01, M10 *= 1-4p/3
-// (the Kraus sums of PennyLane's channel definitions, written out).  Diagonal gates multiply by u_i conj(u_j); CZ by
+//     general channel S:    vec(M) <- S vec(M), vec(M) = (M00, M01, M10, M11), S = sum_k K_k (x) conj(K_k) (4 x 4 complex)
+// (the Kraus sums of PennyLane's channel definitions, written out; the general one carries BitFlip, PhaseFlip,
+// PauliError, GeneralizedAmplitudeDamping, ResetError, ThermalRelaxationError and QubitChannel).  Diagonal gates multiply by u_i conj(u_j); CZ by
 // sign(i) sign(j); CNOT permutes rows and columns (an involution: swapped in place).  Read-out: the diagonal.
 // mixed_backward_kernel (below) differentiates the same programs: PennyLane trains QNodes on default.mixed with
 // backprop or parameter-shift.  n <= 8.
@@ -34,6 +36,7 @@ enum MixedKind : int32_t {
   kMixPhaseDamp,    // p = gamma
   kMixAmpDamp,      // p = gamma
   kMixDepol,        // p
+  kMixChannel = 16, // general one-wire channel: gates[a .. a+3] are the rows of the 4 x 4 superoperator S (10..15: no kind)
 };
 
 struct MixedOp {
@@ -87,7 +90,7 @@ __device__ __forceinline__ double mixed_block_sum(double v, double* s_red) {
 }
 
 __device__ __forceinline__ bool mixed_needs_snapshot(int kind, int oi) {
-  return kind == kMixPhaseDamp || kind == kMixAmpDamp || kind == kMixDepol ||
+  return kind == kMixPhaseDamp || kind == kMixAmpDamp || kind == kMixDepol || kind == kMixChannel ||
          (oi > 0 && (kind == kMixZero || kind == kMixAmpEmbed));
 }
 
@@ -201,6 +204,63 @@ __device__ __forceinline__ void mixed_block_channel_adjoint(const MixedChannel<T
   m01 = C{c.off * m01.x, c.off * m01.y};
   m10 = C{c.off * m10.x, c.off * m10.y};
 }
+
+// The general one-wire channel: S (4 x 4 complex, row-major in gates[a .. a+3]) on vec(M) = (M00, M01, M10, M11).
+// The coefficients are the same for every thread of the workgroup: mixed_uniform pins each one to scalar registers, so
+// the 16 complex numbers cost no vector registers in the block loops.  Its case still costs the kernels that carry it
+// vector registers (a resident wave per SIMD in mixed_kernel, mixed_wide_sweep<float> and mixed_wide_adjoint_channels),
+// so those kernels have a GENERAL instantiation with the case and a lean one without; the host launches GENERAL only
+// for a program (tile-fused engine: a segment) that holds such an op.
+__device__ __forceinline__ float mixed_uniform(float v) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+__device__ __forceinline__ double mixed_uniform(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                          __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+template <typename T>
+struct MixedSuper {
+  V2<T> s[4][4];
+};
+// evaluated like mixed_unitary: read in float64 and rounded once
+template <typename T>
+__device__ __forceinline__ MixedSuper<T> mixed_super(const MixedOp& op, const double* __restrict__ gates) {
+  const double* __restrict__ g = gates + (size_t)op.a * 8;
+  MixedSuper<T> su;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      su.s[r][c] = V2<T>{mixed_uniform((T)g[(r * 4 + c) * 2]), mixed_uniform((T)g[(r * 4 + c) * 2 + 1])};
+  return su;
+}
+// vec(M) <- S vec(M) on one block
+template <typename T>
+__device__ __forceinline__ void mixed_block_super(const MixedSuper<T>& su, V2<T>& m00, V2<T>& m01, V2<T>& m10, V2<T>& m11) {
+  const V2<T> v[4] = {m00, m01, m10, m11};
+  V2<T> o[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    o[r] = cmul<T>(su.s[r][0], v[0]) + cmul<T>(su.s[r][1], v[1]) + cmul<T>(su.s[r][2], v[2]) + cmul<T>(su.s[r][3], v[3]);
+  m00 = o[0];
+  m01 = o[1];
+  m10 = o[2];
+  m11 = o[3];
+}
+// E^dagger of the general channel for the pairing Tr(Lambda^dagger rho) of the reverse sweeps: vec(M) <- S^H vec(M)
+template <typename T>
+__device__ __forceinline__ void mixed_block_super_adjoint(const MixedSuper<T>& su, V2<T>& m00, V2<T>& m01, V2<T>& m10,
+                                                          V2<T>& m11) {
+  const V2<T> v[4] = {m00, m01, m10, m11};
+  V2<T> o[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    o[c] = cmulc<T>(v[0], su.s[0][c]) + cmulc<T>(v[1], su.s[1][c]) + cmulc<T>(v[2], su.s[2][c]) + cmulc<T>(v[3], su.s[3][c]);
+  m00 = o[0];
+  m01 = o[1];
+  m10 = o[2];
+  m11 = o[3];
+}
 // acc += B_rho B_Lambda^dagger of one block: N_ab = sum_c rho_ac conj(Lambda_bc), (re, im) of N00, N01, N10, N11
 template <typename T>
 __device__ __forceinline__ void mixed_block_n_accumulate(double (&acc)[8], V2<T> r00, V2<T> r01, V2<T> r10, V2<T> r11,
@@ -291,7 +351,7 @@ __device__ __forceinline__ void mixed_read_out(const V2<T>* __restrict__ rho, do
 
 // Op `op` of the program on one sample's rho.  `snap` (NULL in the forward): where the backward's replay keeps rho as
 // it was before a channel or a state preparation.  The caller puts a barrier after every op.
-template <typename T>
+template <typename T, bool GENERAL>
 __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restrict__ rho, V2<T>* __restrict__ snap,
                                                const double* __restrict__ angle_rows, const double* __restrict__ feats,
                                                const double* __restrict__ gates, double* s_red, const MixedScalars& m,
@@ -380,11 +440,33 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
       }
       break;
     }
+    case kMixChannel: {
+      if constexpr (GENERAL) {
+        const MixedSuper<T> su = mixed_super<T>(op, gates);
+        for (uint32_t t = tid; t < DD / 4; t += 256) {
+          const uint32_t base = insert_two_bits(t, q, q + n);
+          const uint32_t cj = 1u << q, ci = 1u << (q + n);
+          C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
+          if (snap) {
+            snap[base] = m00;
+            snap[base | cj] = m01;
+            snap[base | ci] = m10;
+            snap[base | ci | cj] = m11;
+          }
+          mixed_block_super<T>(su, m00, m01, m10, m11);
+          rho[base] = m00;
+          rho[base | cj] = m01;
+          rho[base | ci] = m10;
+          rho[base | ci | cj] = m11;
+        }
+      }
+      break;
+    }
     default: break;
   }
 }
 
-template <typename T>
+template <typename T, bool GENERAL>
 __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ prog,
                                                     const double* __restrict__ angle_rows,
                                                     const double* __restrict__ feats,
@@ -400,7 +482,7 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
   for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
     for (int oi = 0; oi < m.n_ops; ++oi) {
       const MixedOp op = prog[oi];
-      mixed_apply_op<T>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
+      mixed_apply_op<T, GENERAL>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
       __syncthreads();
     }
     mixed_read_out<T>(rho, out, s_red, m, sample);  // the diagonal
@@ -417,7 +499,7 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
 //         dL/dtheta = Im Tr(G N);  GATE: R = U^dagger N, dL/dRe U_ab = 2 Re R_ba, dL/dIm U_ab = -2 Im R_ba
 //         rho, Lambda <- U^dagger B U  (one pass over both)
 //     CZ / CNOT: applied to both (involutions)
-//     channel E: Lambda <- E^dagger(Lambda), rho <- snapshot (a channel is not inverted: Depolarizing(0.9) has
+//     channel E: Lambda <- E^dagger(Lambda) (the general channel: S^H on vec of each block), rho <- snapshot (a channel is not inverted: Depolarizing(0.9) has
 //         condition number 5 per wire)
 //     AMP_EMBED: rho_0 = v v^T / |v|^2, dL/dv = 2 (Re(Lambda) v - (v^T Re(Lambda) v / |v|^2) v) / |v|^2
 // Gradients go to per-sample double outputs (no atomics): every reduction runs in a fixed order, so reruns are
@@ -446,7 +528,7 @@ __device__ __forceinline__ void mixed_udag_b_u(V2<T>& b00, V2<T>& b01, V2<T>& b1
   b11 = cmul<T>(a10, u01) + cmul<T>(a11, u11);
 }
 
-template <typename T>
+template <typename T, bool GENERAL>
 __global__ __launch_bounds__(256) void mixed_backward_kernel(
     const MixedOp* __restrict__ prog, const double* __restrict__ angle_rows, const double* __restrict__ feats,
     const double* __restrict__ gates, const double* __restrict__ grad_out, double* __restrict__ grad_rows,
@@ -478,7 +560,7 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
     for (int oi = 0; oi < m.n_ops; ++oi) {
       const MixedOp op = prog[oi];
       C* snap = mixed_needs_snapshot(op.kind, oi) ? snaps + (size_t)(si++) * DD : nullptr;
-      mixed_apply_op<T>(op, rho, snap, angle_rows, feats, gates, s_red, m, sample);
+      mixed_apply_op<T, GENERAL>(op, rho, snap, angle_rows, feats, gates, s_red, m, sample);
       __syncthreads();
     }
 
@@ -603,6 +685,27 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
             rho[base | cj] = sp[base | cj];
             rho[base | ci] = sp[base | ci];
             rho[base | ci | cj] = sp[base | ci | cj];
+          }
+          break;
+        }
+        case kMixChannel: {  // its four rows of grad_gates stay zero: channel operands get no gradient
+          if constexpr (GENERAL) {
+            const MixedSuper<T> su = mixed_super<T>(op, gates);
+            const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
+            for (uint32_t t = tid; t < DD / 4; t += 256) {
+              const uint32_t base = insert_two_bits(t, q, q + n);
+              const uint32_t cj = 1u << q, ci = 1u << (q + n);
+              C l00 = lam[base], l01 = lam[base | cj], l10 = lam[base | ci], l11 = lam[base | ci | cj];
+              mixed_block_super_adjoint<T>(su, l00, l01, l10, l11);
+              lam[base] = l00;
+              lam[base | cj] = l01;
+              lam[base | ci] = l10;
+              lam[base | ci | cj] = l11;
+              rho[base] = sp[base];
+              rho[base | cj] = sp[base | cj];
+              rho[base | ci] = sp[base | ci];
+              rho[base | ci | cj] = sp[base | ci | cj];
+            }
           }
           break;
         }

@@ -9,7 +9,7 @@
 // are the tile number.  A segment holds
 //   * ops that are diagonal on vec(rho) -- PHASE, CZ, PhaseDamping -- on any wires: the factor of an element depends
 //     on its global index only (tile bits + local bits);
-//   * GATE / RY / AmplitudeDamping / Depolarizing on a tile wire, CNOT with both wires in the tile;
+//   * GATE / RY / AmplitudeDamping / Depolarizing / the general channel on a tile wire, CNOT with both wires in the tile;
 //   * ZERO / AMP_EMBED as its first op: the tile is generated instead of read.
 // The host cuts the program into segments (plan_mixed_wide in qiddm_mixed.hip) and uploads it sorted by segment.
 // Wires n-1 and n-2 (q = 0, 1) belong to every tile: the two lowest column bits are local, so a lane moves two
@@ -71,7 +71,8 @@ __global__ __launch_bounds__(256) void mixed_wide_norms(const double* __restrict
   if (threadIdx.x == 0) norms[blockIdx.x] = v;
 }
 
-template <typename T>
+// GENERAL: the instantiation that carries the general channel's case (qsim_mixed.h), launched for segments that hold one
+template <typename T, bool GENERAL>
 __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restrict__ prog,
                                                         const double* __restrict__ angle_rows,
                                                         const double* __restrict__ feats,
@@ -190,6 +191,24 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
           tile[l | cj] = m01;
           tile[l | ci] = m10;
           tile[l | ci | cj] = m11;
+        }
+        break;
+      }
+      case kMixChannel: {
+        if constexpr (GENERAL) {
+          const int a = wide_local_rank(sg, q), b = wide_local_rank(sg, q + n);
+          const uint32_t cj = 1u << a, ci = 1u << b;
+          const MixedSuper<T> su = mixed_super<T>(op, gates);
+#pragma unroll
+          for (int i = 0; i < kWideBlocks; ++i) {
+            const uint32_t l = insert_two_bits(tid + 256u * i, a, b);
+            C m00 = tile[l], m01 = tile[l | cj], m10 = tile[l | ci], m11 = tile[l | ci | cj];
+            mixed_block_super<T>(su, m00, m01, m10, m11);
+            tile[l] = m00;
+            tile[l | cj] = m01;
+            tile[l | ci] = m10;
+            tile[l | ci | cj] = m11;
+          }
         }
         break;
       }

@@ -236,9 +236,11 @@ __global__ __launch_bounds__(256) void mixed_wide_reverse_sweep(
   }
 }
 
-// One channel segment backwards: E^dagger on the Lambda tile of (tile, sample), ops in reverse
-template <typename T>
+// One channel segment backwards: E^dagger on the Lambda tile of (tile, sample), ops in reverse.  GENERAL: as in
+// mixed_wide_sweep
+template <typename T, bool GENERAL>
 __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp* __restrict__ prog,
+                                                                   const double* __restrict__ gates,
                                                                    const double* __restrict__ grad_out,
                                                                    V2<T>* __restrict__ lam_slabs, const MixedScalars m,
                                                                    const WideSegment sg, const WideBwdScalars b,
@@ -260,6 +262,22 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp
     const bool diag = op.kind == kMixPhaseDamp;
     if (!(diag && owned)) __syncthreads();
     owned = diag;
+    if (GENERAL && op.kind == kMixChannel) {  // S^H on vec of each block
+      const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
+      const uint32_t cj = 1u << a, ci = 1u << bb;
+      const MixedSuper<T> su = mixed_super<T>(op, gates);
+#pragma unroll
+      for (int i = 0; i < kWideBlocks; ++i) {
+        const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
+        C l00 = lt[l], l01 = lt[l | cj], l10 = lt[l | ci], l11 = lt[l | ci | cj];
+        mixed_block_super_adjoint<T>(su, l00, l01, l10, l11);
+        lt[l] = l00;
+        lt[l | cj] = l01;
+        lt[l | ci] = l10;
+        lt[l | ci | cj] = l11;
+      }
+      continue;
+    }
     const MixedChannel<T> ch = mixed_channel<T>(op);
     if (diag) {
 #pragma unroll

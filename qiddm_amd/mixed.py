@@ -15,6 +15,11 @@ angle rows, the SEL rotation matrices and the amplitude-embedding features (Penn
 or parameter-shift; both give this gradient).  Autograd carries it on through the stacked rows, ``rot_matrices`` and
 whatever weight map the circuit applied.  Channel strengths get no gradient.
 
+PhaseDamping, AmplitudeDamping and DepolarizingChannel are native ops of the kernels.  Every other one-wire channel of
+``qiddm_amd.qml`` (BitFlip, PhaseFlip, PauliError, GeneralizedAmplitudeDamping, ResetError, ThermalRelaxationError,
+QubitChannel) is lowered to ``QIDDM_MIX_CHANNEL``: its 4 x 4 superoperator S = sum_k K_k (x) conj(K_k), worked out here
+on the host in float64 (``channel_kraus``, ``channel_rows``, ``superoperator``), travels as four rows of ``gates``.
+
 Beyond 8 wires gradients are a second opt-in, ``set_max_grad_wires(10)`` or ``with max_grad_wires(10):`` -- the reverse
 sweep of the tile-fused engine (``qiddm_mixed_wide_backward``) keeps rho, its adjoint and one snapshot per group of
 channels per sample, several slabs where the forward keeps one.  With both limits raised a 9- or 10-wire launch is the
@@ -24,7 +29,9 @@ tile-fused reverse sweep.
 from __future__ import annotations
 
 import contextlib
+import math
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -32,6 +39,141 @@ from . import circuit as _c
 
 CHANNELS = {"PhaseDamping": _capi.MIX_PHASE_DAMP, "AmplitudeDamping": _capi.MIX_AMP_DAMP,
             "DepolarizingChannel": _capi.MIX_DEPOL}
+
+
+# lower the three native channels through MIX_CHANNEL as well (tests and A/B runs only; the default routing is native)
+general_channels = False
+
+
+# ---- one-wire channels on the host (float64, no GPU) -------------------------------------------------------------------
+_PAULI = {"X": np.array([[0, 1], [1, 0]], dtype=complex), "Y": np.array([[0, -1j], [1j, 0]], dtype=complex),
+          "Z": np.array([[1, 0], [0, -1]], dtype=complex)}
+
+
+def _prob(name, value):
+    v = float(value)
+    if not 0.0 <= v <= 1.0:  # NaN fails too
+        raise ValueError(f"{name} must be in the interval [0, 1] (got {v})")
+    return v
+
+
+def _thermal(pe, t1, t2, tg):
+    """-> (pr0, pr1, e1, e2) of ThermalRelaxationError, arguments checked."""
+    pe = _prob("pe", pe)
+    t1, t2, tg = float(t1), float(t2), float(tg)
+    if not t1 > 0.0:
+        raise ValueError(f"t1 must be positive (got {t1})")
+    if not t2 > 0.0:
+        raise ValueError(f"t2 must be positive (got {t2})")
+    if not t2 <= 2.0 * t1:
+        raise ValueError(f"t2 must not exceed 2 * t1 (got t2 = {t2}, t1 = {t1})")
+    if not tg >= 0.0:
+        raise ValueError(f"tg must not be negative (got {tg})")
+    e1, e2 = math.exp(-tg / t1), math.exp(-tg / t2)
+    return (1.0 - pe) * (1.0 - e1), pe * (1.0 - e1), e1, e2
+
+
+def _thermal_super(pe, t1, t2, tg):
+    pr0, pr1, _, e2 = _thermal(pe, t1, t2, tg)
+    s = np.zeros((4, 4), dtype=complex)
+    s[0, 0], s[0, 3], s[3, 0], s[3, 3], s[1, 1], s[2, 2] = 1.0 - pr1, pr0, pr1, 1.0 - pr0, e2, e2
+    return s
+
+
+def _kraus_of_super(s):
+    """A Kraus set of the superoperator `s` from the eigen-decomposition of its Choi matrix."""
+    choi = s.reshape(2, 2, 2, 2).transpose(0, 2, 1, 3).reshape(4, 4)  # [(a, c), (b, d)] = S[(a, b), (c, d)]
+    lam, vec = np.linalg.eigh(choi)
+    if lam.min() < -1e-12:
+        raise ValueError(f"the map is not completely positive (Choi eigenvalue {lam.min():.3e})")
+    return [math.sqrt(max(l, 0.0)) * vec[:, k].reshape(2, 2) for k, l in enumerate(lam) if l > 1e-15]
+
+
+def channel_kraus(name, *params):
+    """The Kraus operators (a list of 2 x 2 complex128 arrays) of a named one-wire channel, PennyLane's definitions:
+    PhaseDamping(g), AmplitudeDamping(g), DepolarizingChannel(p), BitFlip(p), PhaseFlip(p), PauliError(P, p),
+    GeneralizedAmplitudeDamping(g, p), ResetError(p0, p1), ThermalRelaxationError(pe, t1, t2, tg).
+    Arguments out of range raise ``ValueError`` naming the parameter."""
+    eye = np.eye(2, dtype=complex)
+    e = lambda r, c: np.array([[float((r, c) == (i, j)) for j in range(2)] for i in range(2)], dtype=complex)  # |r><c|
+    if len(params) != {"PauliError": 2, "GeneralizedAmplitudeDamping": 2, "ResetError": 2,
+                       "ThermalRelaxationError": 4}.get(name, 1):
+        raise TypeError(f"{name}: wrong number of parameters ({len(params)})")
+    if name == "PhaseDamping":
+        g = _prob("gamma", params[0])
+        return [np.diag([1, math.sqrt(1 - g)]).astype(complex), np.diag([0, math.sqrt(g)]).astype(complex)]
+    if name == "AmplitudeDamping":
+        g = _prob("gamma", params[0])
+        return [np.diag([1, math.sqrt(1 - g)]).astype(complex), math.sqrt(g) * e(0, 1)]
+    if name == "DepolarizingChannel":
+        p = _prob("p", params[0])
+        return [math.sqrt(1 - p) * eye] + [math.sqrt(p / 3) * _PAULI[k] for k in "XYZ"]
+    if name in ("BitFlip", "PhaseFlip"):
+        p = _prob("p", params[0])
+        return [math.sqrt(1 - p) * eye, math.sqrt(p) * _PAULI["X" if name == "BitFlip" else "Z"]]
+    if name == "PauliError":
+        op, p = params[0], _prob("p", params[1])
+        if op not in _PAULI:
+            raise ValueError(f"operators must be 'X', 'Y' or 'Z' on one wire (got {op!r})")
+        return [math.sqrt(1 - p) * eye, math.sqrt(p) * _PAULI[op]]
+    if name == "GeneralizedAmplitudeDamping":
+        g, p = _prob("gamma", params[0]), _prob("p", params[1])
+        return [math.sqrt(p) * np.diag([1, math.sqrt(1 - g)]).astype(complex), math.sqrt(p * g) * e(0, 1),
+                math.sqrt(1 - p) * np.diag([math.sqrt(1 - g), 1]).astype(complex), math.sqrt((1 - p) * g) * e(1, 0)]
+    if name == "ResetError":
+        p0, p1 = float(params[0]), float(params[1])
+        if not p0 >= 0.0:
+            raise ValueError(f"p0 must not be negative (got {p0})")
+        if not p1 >= 0.0:
+            raise ValueError(f"p1 must not be negative (got {p1})")
+        if not p0 + p1 <= 1.0:
+            raise ValueError(f"p0 + p1 must not exceed 1 (got p0 = {p0}, p1 = {p1})")
+        return [math.sqrt(max(1 - p0 - p1, 0.0)) * eye, math.sqrt(p0) * e(0, 0), math.sqrt(p0) * e(0, 1),
+                math.sqrt(p1) * e(1, 0), math.sqrt(p1) * e(1, 1)]
+    if name == "ThermalRelaxationError":
+        pr0, pr1, e1, e2 = _thermal(*params)
+        if e2 > e1:  # t2 > t1: no Pauli / reset mixture; any Kraus set of the same map
+            return _kraus_of_super(_thermal_super(*params))
+        pz = 0.5 * e1 * (1.0 - e2 / e1)
+        return [math.sqrt(max(1 - pz - pr0 - pr1, 0.0)) * eye, math.sqrt(pz) * _PAULI["Z"], math.sqrt(pr0) * e(0, 0),
+                math.sqrt(pr0) * e(0, 1), math.sqrt(pr1) * e(1, 0), math.sqrt(pr1) * e(1, 1)]
+    raise ValueError(f"unknown channel {name}")
+
+
+def _rows(s):
+    """4 x 4 complex -> (4, 8) float64 rows, (re, im) interleaved: the layout of QIDDM_MIX_CHANNEL's gate rows."""
+    out = np.empty((4, 8), dtype=np.float64)
+    out[:, 0::2], out[:, 1::2] = s.real, s.imag
+    return torch.from_numpy(out)
+
+
+def _matrices(kraus):
+    ks = [np.asarray(k.detach().cpu().numpy() if torch.is_tensor(k) else k, dtype=complex) for k in kraus]
+    if not ks or any(k.shape != (2, 2) for k in ks):
+        raise ValueError("Kraus operators must be a non-empty list of 2 x 2 matrices")
+    return ks
+
+
+def superoperator(kraus):
+    """``(4, 8)`` float64 (CPU) rows of S = sum_k K_k (x) conj(K_k) for a list of 2 x 2 complex matrices: S acts on
+    vec(M) = (M00, M01, M10, M11) as M -> sum_k K_k M K_k^dagger."""
+    return _rows(sum(np.kron(k, k.conj()) for k in _matrices(kraus)))
+
+
+def channel_rows(name, *params):
+    """``(4, 8)`` float64 (CPU) superoperator rows of a named channel (see ``channel_kraus``).  ThermalRelaxationError is
+    written down directly (it needs no Kraus set, and t1 < t2 <= 2 t1 has no Pauli / reset one)."""
+    if name == "ThermalRelaxationError":
+        return _rows(_thermal_super(*params))
+    return superoperator(channel_kraus(name, *params))
+
+
+def qubit_channel_rows(kraus):
+    """``superoperator`` for ``qml.QubitChannel``: refuses a set that is not trace preserving (sum K^dagger K = I to 1e-10)."""
+    dev = np.abs(sum(k.conj().T @ k for k in _matrices(kraus)) - np.eye(2)).max()
+    if not dev <= 1e-10:
+        raise ValueError(f"K_list is not trace preserving: sum K^dagger K differs from the identity by {dev:.3e}")
+    return superoperator(kraus)
 
 
 # wires up to which ``execute`` runs a circuit (8: the one-workgroup kernel only; 9, 10: the tile-fused engine as well)
@@ -133,6 +275,12 @@ class _Lowering:
     def op(self, kind, wire=0, a=-1, p=0.0, scale=1.0):
         self.ops.append((kind, wire, a, p, scale))
 
+    def channel(self, rows, wire):
+        """A general one-wire channel: its four superoperator rows join the gates, `a` is the first of them."""
+        base = sum(g.shape[0] for g in self.gates)
+        self.gates.append(rows)
+        self.op(_capi.MIX_CHANNEL, wire, base)
+
     def sel(self, weights, wires, imprimitive):
         n = len(wires)
         self._see(weights)
@@ -190,7 +338,12 @@ def lower(tape, ret, n):
                 low.op(_capi.MIX_CZ if t.name == "CZ" else _capi.MIX_CNOT, t.wires[0], t.wires[1])
             elif t.name in CHANNELS:
                 p = t.params[0]
-                low.op(CHANNELS[t.name], t.wires[0], -1, float(p))
+                if general_channels:
+                    low.channel(channel_rows(t.name, float(p)), t.wires[0])
+                else:
+                    low.op(CHANNELS[t.name], t.wires[0], -1, float(p))
+            elif "superoperator" in t.hyper:
+                low.channel(t.hyper["superoperator"], t.wires[0])
             else:
                 raise NotImplementedError(f"operation {t.name} is not supported on default.mixed")
         first = False
@@ -293,6 +446,15 @@ class _MixedFunction(torch.autograd.Function):
 backward_max_blocks = 0
 
 
+def _gates_on(device, parts):
+    """The gate rows in program order on `device`: SEL matrices are there already, channel rows cross in one copy."""
+    host = [g for g in parts if not g.is_cuda]
+    if host:
+        moved = iter(torch.cat(host).to(device).split([g.shape[0] for g in host]))
+        parts = [g if g.is_cuda else next(moved) for g in parts]
+    return torch.cat(parts).contiguous()
+
+
 def execute(tape, ret, n, precision=None, _engine=None):
     """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)``
     (or the unbatched row), as ``default.mixed`` does.  Up to 8 wires: differentiable when grad mode is on and an input
@@ -319,7 +481,7 @@ def execute(tape, ret, n, precision=None, _engine=None):
     launch = _Launch(low, measure, n, prec, device, batch)
     f64 = dict(dtype=torch.float64, device=device)
     rows = torch.stack([r.to(**f64).expand(batch) for r in low.rows]).contiguous() if low.rows else None
-    gates = torch.cat(low.gates).to(device).contiguous() if low.gates else None
+    gates = _gates_on(device, low.gates) if low.gates else None
     feats = low.features.to(**f64).contiguous() if low.features is not None else None
     if feats is not None and feats.shape[0] != batch:
         feats = feats.expand(batch, -1).contiguous()

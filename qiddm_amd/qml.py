@@ -132,6 +132,52 @@ AmplitudeDamping = _channel("AmplitudeDamping")
 DepolarizingChannel = _channel("DepolarizingChannel")
 
 
+# PennyLane's other one-wire channels: default.mixed runs them as one general op whose 4 x 4 superoperator is worked
+# out here on the host (qiddm_amd.mixed.channel_rows).  Strengths are Python floats or host arrays; arguments out of
+# range raise ValueError when the op is constructed.
+def _general_channel(name, wires, params, rows_of):
+    """`rows_of(mixed)`: the op's (4, 8) superoperator rows; it checks the parameters."""
+    from . import mixed as _mixed
+    w = _wires(wires)
+    if len(w) != 1:
+        raise NotImplementedError(f"{name} on {len(w)} wires: only one-wire channels are supported (the density-matrix "
+                                  "kernels apply a channel to the 2 x 2 blocks of a single wire)")
+    return _Op(name, w, params, channel=True, superoperator=rows_of(_mixed))
+
+
+def _named_channel(name, wires, *params):
+    return _general_channel(name, wires, params, lambda mixed: mixed.channel_rows(name, *params))
+
+
+def BitFlip(p, wires):
+    return _named_channel("BitFlip", wires, p)
+
+
+def PhaseFlip(p, wires):
+    return _named_channel("PhaseFlip", wires, p)
+
+
+def GeneralizedAmplitudeDamping(gamma, p, wires):
+    return _named_channel("GeneralizedAmplitudeDamping", wires, gamma, p)
+
+
+def ResetError(p0, p1, wires):
+    return _named_channel("ResetError", wires, p0, p1)
+
+
+def PauliError(operators, p, wires):
+    return _named_channel("PauliError", wires, operators, p)
+
+
+def ThermalRelaxationError(pe, t1, t2, tg, wires):
+    return _named_channel("ThermalRelaxationError", wires, pe, t1, t2, tg)
+
+
+def QubitChannel(K_list, wires):
+    """``qml.QubitChannel(K_list, wires)``: Kraus operators as 2 x 2 complex host matrices, sum K^dagger K = I."""
+    return _general_channel("QubitChannel", wires, (), lambda mixed: mixed.qubit_channel_rows(K_list))
+
+
 # --- measurements -------------------------------------------------------------
 class PauliZ:
     def __init__(self, wires):
