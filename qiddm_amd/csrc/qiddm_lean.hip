@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "qsim_lean.h"
+#include "qsim_lean_solo.h"
 
 namespace {
 
@@ -55,9 +55,52 @@ qiddm::KScalars params_of(const qiddm_circuit_t* c) {
   return p;
 }
 
+// When the instance that carries both bodies (qsim_lean.h: lean_has_solo) runs the one-wavefront-per-item body: from
+// kLeanSoloMinSteps steps per launch on at every batch, below that from kLeanSoloMinItems items (batch x n_steps) on.
+// A solo workgroup stages linear_up's weights and every wavefront the whole phase table before its first item (~9 us
+// for a launch of one item against ~5 us), and then runs one item in ~3 us, whatever the launch holds up to 2 048 items;
+// the four-wave body pays ~2.7 us per step of a sample.  Measured by tools/ab_lean_solo_threshold.py, float32, P = 784
+// (profiles/lean_solo/threshold.txt; us per launch, four-wave / solo):
+//   1 step:   256 items 5.8 / 12.3    1 024 items 13.4 / 13.1    2 048 items 24.1 / 14.5
+//   4 steps:   64 items 13.2 / 12.0   1 024 items 14.9 / 13.1
+//   15 steps: 240 items 42.9 / 12.3   3 840 items 46.3 / 21.7
+constexpr int kLeanSoloMinSteps = 4;
+constexpr int64_t kLeanSoloMinItems = 2048;
+
+int lean_cu_count() {
+  static int cus[qiddm_capi::DeviceFlags::kMaxDevices] = {};
+  const int dev = qiddm_capi::DeviceFlags::current();
+  if (dev >= 0 && cus[dev] > 0) return cus[dev];
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev < 0 ? 0 : dev) != hipSuccess || n < 1) n = 256;
+  if (dev >= 0) cus[dev] = n;
+  return n;
+}
+
+// QIDDM_LEAN_SOLO_MIN_ITEMS replaces the rule by a bare item count (kernel experiments: A/B in one process; 0 = always
+// the solo body, -1 = never)
+bool lean_solo_wanted(int64_t items, int n_steps) {
+  const char* e = std::getenv("QIDDM_LEAN_SOLO_MIN_ITEMS");
+  if (e == nullptr || *e == 0) return n_steps >= kLeanSoloMinSteps || items >= kLeanSoloMinItems;
+  const long long v = std::atoll(e);
+  return v >= 0 && items >= (int64_t)v;
+}
+
 template <typename T, int N, int PPT, bool REUP, int LPR, bool POST>
 int launch_lean(const double* x, const double* wd, const double* bd, const double* wu, const double* bu, double* y,
                 const void* tables, const qiddm::QuadScalars& d, const qiddm::KScalars& p, int layers, hipStream_t st) {
+  if constexpr (qiddm::lean_has_solo<T, N, PPT, REUP, LPR, POST>()) {
+    const int64_t items = p.batch * d.n_steps;
+    // (the body counts items and waves in 32 bits)
+    if (lean_solo_wanted(items, d.n_steps) && items < ((int64_t)1 << 31) && d.out_features <= 1024) {
+      const size_t smem = qiddm::LeanSoloLds::bytes(d.out_features, LPR);
+      const int64_t want = (items + qiddm::kSoloWaves - 1) / qiddm::kSoloWaves;   // one item per wavefront
+      const int64_t cus = lean_cu_count();                                         // one workgroup per CU at most
+      return qiddm_capi::launch<qiddm::dense_lean_kernel<T, N, PPT, REUP, LPR, POST>>(
+          kMaxLds, dim3((unsigned)(want < cus ? want : cus)), dim3(qiddm::kSoloThreads), smem, st, "dense_lean_kernel",
+          x, wd, bd, wu, bu, y, static_cast<const unsigned char*>(tables), d, p);
+    }
+  }
   const size_t smem = qiddm::LeanTables<T, N>::lds_bytes(layers, p.n_rounds,
                                                          !qiddm::lean_tables_in_registers<REUP, LPR>());
   const unsigned blocks = (unsigned)(p.batch < 2048 ? p.batch : 2048);

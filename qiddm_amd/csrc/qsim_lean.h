@@ -1,12 +1,22 @@
 // qsim_lean.h -- the sampling loop of the 8- and 6-qubit dense nets with the layer's dependent chain cut to the bone.
 //
-// Same decomposition as qsim_quad.h (8 qubits: four wavefronts per sample, amplitude k = (wave << 6) | lane, one LDS
-// exchange per layer for the two wave-bit gates; 6 qubits: the state fits one wavefront, every wave runs the circuit on
-// its own copy and there is no exchange and no barrier in a round), but built around what the microbenchmarks of
-// tools/ubench/ say a
-// LONE wavefront on a SIMD pays: ~11 cycles per DEPENDENT vector instruction whatever it is, ~155 cycles for the LDS
-// round trip + barrier.  A layer is a dependent chain (every gate acts on the same amplitudes), so its time is
-// (chain depth) x 11 + 155 and the only lever is depth:
+// Which instance runs which decomposition:
+//   * float32, 8 qubits, no re-upload, compiled-in layer count, goal "data", P <= 1024 (the flagship QNN_noise(784, 8, 14)),
+//     launches of at least 4 steps or 2 048 (sample, step) items: ONE wavefront per item, four amplitudes per lane, no
+//     exchange and no barrier in a layer, the items of a launch dealt to all wavefronts -- qsim_lean_solo.h, which says
+//     why.  The kernel keeps its name and template arguments; the host picks the body by the workgroup size
+//     (qiddm_lean.hip: launch_lean, with the measured threshold).
+//   * the same instance at smaller launches, and every other instance (complex128, re-upload, POST, 6 qubits, runtime
+//     layer count, P > 1024): the body below.  A one-step launch of a few hundred samples cannot fill the solo body's
+//     wavefronts and still pays its per-workgroup setup; the others read the image or the previous step (their steps
+//     depend on each other), or do not fit a wavefront's registers (complex128: not measured, kept here).
+//
+// The body below has the decomposition of qsim_quad.h (8 qubits: four wavefronts per sample, amplitude k = (wave << 6) |
+// lane, one LDS exchange per layer for the two wave-bit gates; 6 qubits: the state fits one wavefront, every wave runs the
+// circuit on its own copy and there is no exchange and no barrier in a round), built around what the microbenchmarks of
+// tools/ubench/ say a LONE wavefront on a SIMD pays: ~11 cycles per DEPENDENT vector instruction whatever it is, ~155
+// cycles for the LDS round trip + barrier.  A layer is a dependent chain (every gate acts on the same amplitudes), so its
+// time is (chain depth) x 11 + 155 and the only lever is depth:
 //
 //   * RY in tangent form.  RY = c [[1, -t], [t, 1]], t = tan(theta / 2): own' = own +- t * partner is ONE instruction
 //     whose partner operand is fetched by DPP inside it (`v_fmac_f32_dpp`, accumulator = own value, in place) --
@@ -24,13 +34,15 @@
 //     this step -- an n x n product built once per weights (lean_tables_kernel).  Where the angles cannot reach the
 //     state at all (one block per round: RZ on |0..0> is a global phase, finding F2) they are not computed.
 //
-// Tried on top and dropped (round 3): the tail of a step (|amplitude|^2, signed sums, linear_up, stores: ~1 250 of ~6 900
-// cycles, and independent of the next step's circuit when there is no re-upload) overlapped with the next step's layers
+// Tried on top of the four-wave body and dropped (round 3): the tail of a step (|amplitude|^2, signed sums, linear_up,
+// stores: ~1 250 of ~6 900 cycles, and independent of the next step's circuit when there is no re-upload) overlapped with
+// the next step's layers
 // (a) as pieces placed in the two exchange windows of the first five layers -- behind in-order issue a wave that waits for
 // its side chain waits with its main chain too: the layers grew by what the tail had cost (6 924 -> 6 492 cycles per step);
 // (b) on a fifth, helper wavefront sharing SIMD 0 with wave 0, applying the last layer's 4 x 4 itself and owning all 256
 // probabilities -- correct, but every barrier now waits for five waves and wave 0 shares its issue: 3.35 -> 3.51 us per
 // step in float32 (4.28 -> 4.11 in complex128).
+// What did pay was changing the decomposition itself (qsim_lean_solo.h): 3.10 -> 1.56 us per step on the flagship.
 //
 // The tangent form needs cos(theta / 2) away from zero: the table builder records max |t|; the host routes weights with
 // max |t| > kLeanMaxTan to dense_quad_kernel (qiddm_dense_sample_lean_check).  Shipped checkpoints have |theta / 2| < 0.9.
@@ -234,6 +246,20 @@ struct LeanLayer {
   T k1, k2, k3;  // wave-bit exchange: partners wave^1, wave^2, wave^3
 };
 
+// The instance that also carries the one-wavefront-per-item body of qsim_lean_solo.h (float32, 8 qubits, no re-upload,
+// compiled-in layer count, "data" goal, at most 1024 pixels): launched with kSoloThreads threads it runs that body, with
+// 256 threads the four-wave body below.
+constexpr int kSoloWaves = 8;                     // wavefronts per workgroup: two per SIMD, <= 256 VGPRs each
+constexpr int kSoloThreads = kSoloWaves * kWave;
+template <typename T, int N, int PPT, bool REUP, int LPR, bool POST>
+constexpr bool lean_has_solo() {
+  return std::is_same<T, float>::value && N == 8 && PPT == 4 && !REUP && LPR > 1 && !POST;
+}
+template <int LPR>
+__device__ void dense_lean_solo_body(const double* __restrict__ wu, const double* __restrict__ bu,
+                                     double* __restrict__ y, const unsigned char* __restrict__ tables,
+                                     const QuadScalars& d, const KScalars& p);
+
 // REUP: the circuit re-uploads its data angles (n_blocks > 1); without it the angles never reach the state and no
 //       angle code is compiled at all (no branch in the layer either: a taken branch costs a lone wavefront ~50 cycles).
 // LPR:  layers per round as a compile-time constant (fully unrolled layer sequence; 14 = the flagship QNN_noise(784, 8,
@@ -243,7 +269,7 @@ struct LeanLayer {
 //       (reference src/models.py:130-134).  The clamp breaks the composite map, so the image stays in registers
 //       (PPT pixels per thread) and a re-uploading net runs its whole linear_down every step, weights in registers too.
 template <typename T, int N, int PPT, bool REUP, int LPR, bool POST>
-__global__ __launch_bounds__(256) void dense_lean_kernel(
+__global__ __launch_bounds__((lean_has_solo<T, N, PPT, REUP, LPR, POST>() ? kSoloThreads : 256)) void dense_lean_kernel(
     const double* __restrict__ x, const double* __restrict__ wd, const double* __restrict__ bd,
     const double* __restrict__ wu, const double* __restrict__ bu, double* __restrict__ y,
     const unsigned char* __restrict__ tables, const QuadScalars d, const KScalars p) {
@@ -251,6 +277,13 @@ __global__ __launch_bounds__(256) void dense_lean_kernel(
   using QT = LeanTables<T, N>;
   constexpr int TL = QT::TL;
   using V4 = T __attribute__((ext_vector_type(4)));
+  if constexpr (lean_has_solo<T, N, PPT, REUP, LPR, POST>()) {
+    // the host picks the decomposition by the workgroup size (qiddm_lean.hip: launch_lean)
+    if (blockDim.x == kSoloThreads) {
+      dense_lean_solo_body<LPR>(wu, bu, y, tables, d, p);
+      return;
+    }
+  }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr bool kRegTables = lean_tables_in_registers<REUP, LPR>();
   const int n_rounds = kRegTables ? 1 : p.n_rounds;

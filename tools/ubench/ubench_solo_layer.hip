@@ -1,0 +1,116 @@
+// ubench_solo_layer.hip -- the layer of the one-wavefront-per-item body (qsim_lean_solo.h: solo_layer, the shipped code)
+// next to ubench_layer.hip's four-wave layer: 13 layers per "step", s_memtime around `iters` steps, one workgroup of
+// W = 1, 2, 4, 8 wavefronts per CU on all 256 CUs (96 KiB of LDS per workgroup keep a second one off the CU), every
+// wavefront on an item of its own.  Phases in registers, tangents read from LDS one layer ahead, as the kernel does.
+// The four-wave layer costs 400 ticks for ONE item per CU (ubench_layer, "full layer as shipped"); W solo wavefronts
+// finish W items in the time printed here.
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../qiddm_amd/csrc -o ubench_solo_layer ubench_solo_layer.hip
+#include "qsim_lean_solo.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+using namespace qiddm;
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+#define CHECK(x)                                                                  \
+  do {                                                                            \
+    hipError_t e_ = (x);                                                          \
+    if (e_ != hipSuccess) {                                                       \
+      fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); \
+      exit(1);                                                                    \
+    }                                                                             \
+  } while (0)
+
+constexpr int kLayers = 13;
+constexpr int kBlocks = 256;
+constexpr int kMaxWaves = 8;
+constexpr size_t kLds = 96 * 1024;
+
+__global__ __launch_bounds__(kMaxWaves * 64) void solo_layer_loop(float* out, unsigned long long* ticks, int iters,
+                                                                 const float* tab) {
+  using T = float;
+  using C = V2<T>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  T* s_un = reinterpret_cast<T*>(smem_raw);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int i = tid; i < (kLayers + 1) * 8; i += blockDim.x) s_un[i] = tab[i % 509] * 0.4f;
+  C ph[kLayers][4];
+#pragma unroll
+  for (int l = 0; l < kLayers; ++l) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = (l * 4 + r) * 64 + lane;
+      ph[l][r] = C{tab[(i * 2) % 509] * 0.9f + 0.05f, tab[(i * 2 + 1) % 509] * 0.3f};
+    }
+  }
+  T pm[4];
+  const int llane = logical_lane(lane);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) pm[q] = ((llane >> q) & 1) ? (T)1 : (T)-1;
+  C a[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) a[r] = C{0.01f * (float)(lane + 64 * r + 1), 0.02f};
+  __syncthreads();
+  const v4f* un4 = reinterpret_cast<const v4f*>(s_un);
+  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+  for (int it = 0; it < iters; ++it) {
+    asm volatile("" ::: "memory");
+    v4f lo = un4[0], hi = un4[1];
+#pragma unroll
+    for (int l = 0; l < kLayers; ++l) {
+      const v4f nlo = un4[2 * (l + 1)], nhi = un4[2 * (l + 1) + 1];
+      __builtin_amdgcn_sched_barrier(0);
+      const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
+      solo_layer(a, ph[l], ts, hi.x, hi.y, hi.z, hi.w);
+      lo = nlo;
+      hi = nhi;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a[r] = a[r] * C{0.05f, 0.05f};   // keep the values bounded
+  }
+  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+  if (lane == 0) ticks[blockIdx.x * kMaxWaves + wv] = t1 - t0;
+  out[(size_t)blockIdx.x * (kMaxWaves * 64) + tid] = (a[0].x + a[1].y) + (a[2].x + a[3].y);
+}
+
+static double run(float* out, unsigned long long* ticks, const float* tab, int iters, int waves) {
+  for (int rep = 0; rep < 2; ++rep) {
+    hipLaunchKernelGGL(solo_layer_loop, dim3(kBlocks), dim3(waves * 64), kLds, 0, out, ticks, iters, tab);
+    CHECK(hipGetLastError());
+    CHECK(hipDeviceSynchronize());
+  }
+  std::vector<unsigned long long> h(kBlocks * kMaxWaves);
+  CHECK(hipMemcpy(h.data(), ticks, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  double sum = 0, mx = 0;
+  for (int b = 0; b < kBlocks; ++b)
+    for (int w = 0; w < waves; ++w) {
+      const double v = (double)h[b * kMaxWaves + w];
+      sum += v;
+      mx = v > mx ? v : mx;
+    }
+  const double per = sum / (kBlocks * waves) / ((double)iters * kLayers);
+  printf("  %d solo wavefront(s) per CU: %7.1f ticks/layer (slowest wavefront %7.1f), %7.1f ticks per item-layer\n", waves,
+         per, mx / ((double)iters * kLayers), per / waves);
+  return per;
+}
+
+int main() {
+  float *out, *tab;
+  unsigned long long* ticks;
+  CHECK(hipMalloc(&out, (size_t)kBlocks * kMaxWaves * 64 * sizeof(float)));
+  CHECK(hipMalloc(&ticks, kBlocks * kMaxWaves * sizeof(unsigned long long)));
+  CHECK(hipMalloc(&tab, 512 * sizeof(float)));
+  std::vector<float> h(512);
+  for (int i = 0; i < 512; ++i) h[i] = (float)((i * 2654435761u) % 1000) / 1000.0f;
+  CHECK(hipMemcpy(tab, h.data(), 512 * sizeof(float), hipMemcpyHostToDevice));
+  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kLds));
+  const int iters = 400;
+  for (int rep = 0; rep < 3; ++rep) {
+    printf("run %d\n", rep);
+    for (int waves : {1, 2, 4, 8}) run(out, ticks, tab, iters, waves);
+  }
+  return 0;
+}
