@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define QIDDM_ABI_VERSION 1
+#define QIDDM_ABI_VERSION 2
 #define QIDDM_MAX_QUBITS_FUSED 10 /* one wavefront owns the whole slab in registers */
 #define QIDDM_MAX_QUBITS 16       /* 11..16: one workgroup per sample, tiled passes over a workspace slab */
 
@@ -421,7 +421,7 @@ int qiddm_batchnorm_train_forward(const double *x, int64_t batch, int64_t channe
                                   double *save_invstd, void *workspace, int64_t workspace_bytes, void *stream);
 /* the statistics half of the backward only: grad_weight / grad_bias (each may be NULL) and coef (3, channels) with
  * dL/dx = coef[0][c] grad_y + coef[1][c] x + coef[2][c] -- for a producer that applies it itself
- * (qiddm_qconv_train_backward_bn).  Same workspace as qiddm_batchnorm_backward.                               */
+ * (qiddm_qconv_train_backward, conv_y / bn_coef).  Same workspace as qiddm_batchnorm_backward.               */
 int qiddm_batchnorm_backward_stats(const double *x, const double *grad_y, int64_t batch, int64_t channels, int64_t hw,
                                    const double *weight, const double *save_mean, const double *save_invstd,
                                    double *grad_weight, double *grad_bias, double *coef, void *workspace,
@@ -466,18 +466,68 @@ int qiddm_maxpool2_backward(const double *x, const double *grad_y, int64_t plane
  * per-pixel circuit sweep:  with t_mc = dL/dy_mc D/2 where the clamp passes,
  *     dL/dv^_mj = 2 Re sum_c t_mc conj(a_mc) U[2c,j]   -> through the normalisation and the fold -> grad_x
  *     dL/dangle = 2 Re sum_c <e_2c| dU/dangle |h_c>,   h_c[j] = sum_m t_mc conj(a_mc) v^_mj
- * qiddm_qconv_train_backward computes a, dL/dv (stored transposed, (C kh kw, M) float32, then folded into grad_x
- * unless NULL) and partial sums of h:  h_partials (qiddm_qconv_train_partials(..., C kh kw), 2 row_channels,
+ * qiddm_qconv_train_backward computes a, dL/dv and partial sums of h:  h_partials (plan.n_partials, 2 row_channels,
  * C kh kw + 1) float32 with  h_c[j] = sum_p hp[p][c][j] - i sum_p hp[p][row_channels + c][j];  column C kh kw is the
  * value every pad column j >= C kh kw shares.
  *   rows: (C kh kw + 1, 2 row_channels) float32 -- rows[j][c] = Re U[2c,j], rows[j][row_channels + c] = Im U[2c,j],
- *         last row 0.5 sum_{j >= C kh kw} U[2c,j]; zero for c >= out_channels.  row_channels in {8, 16, 32}
- *         (C kh kw <= 510): wider layers return QIDDM_ERR_UNSUPPORTED (use qiddm_qconv_backward or library GEMMs).
- *         From 32 patch features on the three products run on the f32 matrix cores (v_mfma_f32_16x16x4_f32 /
- *         32x32x2_f32); numel(x) and numel(grad_y) must then be below 2^32 (32-bit element offsets).
+ *         last row 0.5 sum_{j >= C kh kw} U[2c,j]; zero for c >= out_channels.
  * qiddm_matrix_adjoint: K slabs (-> qiddm_adjoint_finalize) of 2 Re <lambda_s| dU/dangle |psi0_s> summed over
  * `count` (psi0, lambda) pairs of complex128 vectors (count, 2^n, interleaved); circ->dtype QIDDM_F64, gate table
- * of that dtype, 2 <= n_qubits <= 16.                                                                        */
+ * of that dtype, 2 <= n_qubits <= 16.
+ *
+ * One descriptor names the layer, qiddm_qconv_train_plan (host only) says what the library does with it, and
+ * qiddm_qconv_train_backward launches exactly that:
+ *   route         THIN: the hand-written thin-product kernels (<= 32 output channels, kernel extent <= 15, LDS tiles
+ *                 that fit); GEMM: the unitary route holds (2 <= n_qubits <= 12, C kh kw <= 2^n, 2 out_channels <= 2^n)
+ *                 but the layer is too wide for them -- the caller forms the products with library GEMMs and uses
+ *                 qiddm_qconv_fold_features; NONE: no unitary route.  route and row_channels depend on (n_qubits,
+ *                 in_channels, kh, kw, out_channels) only (one exception: a THIN layer whose C H W reaches 2^24 has no
+ *                 plan at all, see below); on GEMM and NONE every other field is 0.
+ *   row_channels  8, 16 or 32: the narrowest that holds out_channels (0 beyond 32); the width of `rows` / h_partials
+ *   matrix_core   the three products run on the f32 matrix cores (v_mfma_f32_16x16x4_f32 / 32x32x2_f32: from 32 patch
+ *                 features on, numel(x) and numel(grad_y) below 2^32), otherwise on the VALU kernel
+ *   bn_fold       the kernel can apply a following training-mode BatchNorm2d's backward transform to dL/dy while it
+ *                 loads it (0: the matrix-core kernel with 32 row channels has no registers left for it)
+ *   pixel_rows_elems  > 0: dL/dx can come from 2 row_channels + 1 floats per output pixel and a transposed convolution
+ *                 on the matrix cores (qsim_qconv_dx.h; same-size convolutions on the matrix-core kernel with at most
+ *                 32 input channels) -- C kh kw / (2 row_channels + 1) times less memory traffic than the (C kh kw, M)
+ *                 feature gradients + fold, and equal to them to float32 rounding (the taps are summed in float32)
+ * A descriptor with an extent below 1, negative padding, a kernel larger than the padded image or 2^40 output pixels is
+ * QIDDM_ERR_INVALID, and a THIN layer whose C H W reaches 2^24 QIDDM_ERR_UNSUPPORTED, from both functions alike.
+ * The entry takes a THIN layer (anything else: QIDDM_ERR_UNSUPPORTED); x, grad_y, rows and h_partials are required.
+ *   argument              means                                             needs
+ *   x_is_f32              x is a float32 copy of the activations (same      plan.matrix_core; neither conv_y / bn_coef
+ *                         results: every patch element is converted anyway) nor pixel_rows (QIDDM_ERR_UNSUPPORTED)
+ *   grad_y_batch_stride   elements between two images of grad_y, 0 = dense  >= out_channels Ho Wo, batch * stride < 2^32
+ *                         (a channel slice of a wider tensor read in place) (every route)
+ *   conv_y, bn_coef       grad_y is dL/d(BatchNorm output): dL/dy = coef[0] both or neither; plan.bn_fold
+ *                         grad_y + coef[1] conv_y + coef[2] per channel
+ *                         (bn_coef: qiddm_batchnorm_backward_stats; conv_y is always the dense (batch, out_channels,
+ *                         Ho, Wo) tensor: grad_y_batch_stride applies to grad_y alone)
+ *   pixel_rows            (plan.pixel_rows_elems floats) dL/dx from the     grad_x, plan.pixel_rows_elems > 0, float64 x;
+ *                         per-pixel rows; grad_features_t is not touched    otherwise grad_features_t is required
+ *   grad_features_t       (C kh kw, M) float32 feature gradients, folded    --
+ *                         into grad_x unless grad_x is NULL                                                        */
+#define QIDDM_QCONV_ROUTE_NONE 0
+#define QIDDM_QCONV_ROUTE_THIN 1
+#define QIDDM_QCONV_ROUTE_GEMM 2
+typedef struct {
+  int32_t n_qubits, reserved;
+  int64_t batch, in_channels, height, width, kh, kw, pad_h, pad_w, out_channels;
+} qiddm_qconv_layer_t;
+typedef struct {
+  int32_t route;            /* QIDDM_QCONV_ROUTE_NONE / _THIN / _GEMM                                 */
+  int32_t row_channels;     /* 8, 16, 32 (0: more than 32 output channels)                            */
+  int32_t matrix_core;      /* thin-product kernel on the MFMA units; float32 x is accepted iff 1     */
+  int32_t bn_fold;          /* the entry accepts conv_y / bn_coef                                     */
+  int64_t n_partials;       /* slabs of h_partials                                                    */
+  int64_t pixel_rows_elems; /* > 0: dL/dx from per-pixel rows; 0: feature gradients + fold            */
+} qiddm_qconv_train_plan_t;
+int qiddm_qconv_train_plan(const qiddm_qconv_layer_t *layer, qiddm_qconv_train_plan_t *plan);
+int qiddm_qconv_train_backward(const qiddm_qconv_layer_t *layer, const void *x, int32_t x_is_f32, const double *grad_y,
+                               int64_t grad_y_batch_stride, const double *conv_y, const double *bn_coef,
+                               const float *rows, float *grad_features_t, float *pixel_rows, float *h_partials,
+                               double *grad_x, void *stream);
 /* the two small steps either side: `rows` from the unitary (qiddm_circuit_unitary[_wide]; u_transposed as there),
  * and h_partials -> the (out_channels, 2^n) complex128 start vectors psi0 = h_c and lambda = e_2c of
  * qiddm_matrix_adjoint                                                                                        */
@@ -491,54 +541,6 @@ int qiddm_qconv_train_vectors(int32_t n_qubits, const float *h_partials, int64_t
 int qiddm_qconv_fold_features(const float *grad_features_t, int64_t batch, int64_t in_channels, int64_t height,
                               int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w, double *grad_x,
                               void *stream);
-int64_t qiddm_qconv_train_partials(int64_t batch, int64_t height_out, int64_t width_out, int64_t features);
-int qiddm_qconv_train_backward(int32_t n_qubits, const double *x, int64_t batch, int64_t in_channels,
-                               int64_t height, int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w,
-                               const double *grad_y, int64_t out_channels, const float *rows, int32_t row_channels,
-                               float *grad_features_t, float *h_partials, double *grad_x, void *stream);
-/* the same with x as a float32 copy of the activations (every patch element is converted to float32 before the products
- * anyway, so the results are identical; half the bytes and registers of the gather).  Taken where the matrix-core kernel
- * runs the layer -- qiddm_qconv_train_x32_ok() returns 1 -- and QIDDM_ERR_UNSUPPORTED otherwise.                  */
-int32_t qiddm_qconv_train_x32_ok(int64_t batch, int64_t in_channels, int64_t height, int64_t width, int64_t kh,
-                                 int64_t kw, int64_t pad_h, int64_t pad_w, int64_t out_channels, int32_t row_channels);
-int qiddm_qconv_train_backward_x32(int32_t n_qubits, const float *x, int64_t batch, int64_t in_channels,
-                                   int64_t height, int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w,
-                                   const double *grad_y, int64_t out_channels, const float *rows,
-                                   int32_t row_channels, float *grad_features_t, float *h_partials, double *grad_x,
-                                   void *stream);
-/* dL/dx without the feature-gradient matrix (qsim_qconv_dx.h): the fold commutes with the second product, so the thin-
- * product kernel only leaves 2 row_channels + 1 floats per output pixel (`pixel_rows`: qiddm_qconv_train_dx_elems()
- * floats) and a second kernel makes grad_x from them as a transposed convolution on the matrix cores -- C kh kw / (2
- * row_channels + 1) times less memory traffic than grad_features_t + fold.  Same-size convolutions (Ho = H, Wo = W) on the
- * matrix-core kernel with at most 32 input channels: qiddm_qconv_train_dx_elems() returns 0 for anything else, and
- * qiddm_qconv_train_backward_dx then QIDDM_ERR_UNSUPPORTED (use qiddm_qconv_train_backward).  Same h_partials; grad_x
- * agrees with the fold route to float32 rounding (the nine taps are summed in float32 instead of float64).
- * grad_y_batch_stride: elements between two images of grad_y, 0 = dense (out_channels Ho Wo); a channel slice of a wider
- * contiguous tensor -- one half of a concatenation's gradient -- is read in place.                                   */
-int64_t qiddm_qconv_train_dx_elems(int32_t n_qubits, int64_t batch, int64_t in_channels, int64_t height, int64_t width,
-                                   int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w, int64_t out_channels,
-                                   int32_t row_channels);
-int qiddm_qconv_train_backward_dx(int32_t n_qubits, const double *x, int64_t batch, int64_t in_channels,
-                                  int64_t height, int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w,
-                                  const double *grad_y, int64_t grad_y_batch_stride, int64_t out_channels,
-                                  const float *rows, int32_t row_channels, float *pixel_rows, float *h_partials,
-                                  double *grad_x, void *stream);
-/* The same backward for a convolution that is followed by a training-mode BatchNorm2d (every `net` of unet_simple,
- * reference nn/unet_simple.py:9-18): grad_out is dL/d(BatchNorm output), conv_y the convolution's own output and
- * bn_coef the (3, out_channels) coefficients of qiddm_batchnorm_backward_stats; the kernels form
- * dL/dy = coef[0] grad_out + coef[1] conv_y + coef[2] per channel while they load it, so the BatchNorm backward's
- * transform pass never runs.  With pixel_rows (qiddm_qconv_train_dx_elems() floats) dL/dx comes from the per-pixel
- * rows and grad_features_t may be NULL; otherwise as qiddm_qconv_train_backward.  qiddm_qconv_train_bn_ok() says whether
- * a layer has this form (1) or keeps the separate BatchNorm backward (0: the matrix-core kernel with 32 row channels has no
- * registers left for it; qiddm_qconv_train_backward_bn then returns QIDDM_ERR_UNSUPPORTED).                       */
-int32_t qiddm_qconv_train_bn_ok(int64_t batch, int64_t in_channels, int64_t height, int64_t width, int64_t kh,
-                                int64_t kw, int64_t pad_h, int64_t pad_w, int64_t out_channels, int32_t row_channels);
-int qiddm_qconv_train_backward_bn(int32_t n_qubits, const double *x, int64_t batch, int64_t in_channels,
-                                  int64_t height, int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w,
-                                  const double *grad_out, const double *conv_y, const double *bn_coef,
-                                  int64_t out_channels, const float *rows, int32_t row_channels,
-                                  float *grad_features_t, float *pixel_rows, float *h_partials, double *grad_x,
-                                  void *stream);
 int64_t qiddm_matrix_adjoint_partials(int64_t count);
 int64_t qiddm_matrix_adjoint_workspace_bytes(const qiddm_circuit_t *circ, int64_t count);
 int qiddm_matrix_adjoint(const qiddm_circuit_t *circ, const double *psi0, const double *lambda, int64_t count,

@@ -95,6 +95,21 @@ class AdamTensor(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class QConvLayer(ctypes.Structure):
+    """``qiddm_qconv_layer_t``."""
+
+    _fields_ = [("n_qubits", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
+        (name, ctypes.c_int64) for name in ("batch", "in_channels", "height", "width", "kh", "kw", "pad_h", "pad_w",
+                                            "out_channels")]
+
+
+class QConvTrainPlan(ctypes.Structure):
+    """``qiddm_qconv_train_plan_t``."""
+
+    _fields_ = [("route", ctypes.c_int32), ("row_channels", ctypes.c_int32), ("matrix_core", ctypes.c_int32),
+                ("bn_fold", ctypes.c_int32), ("n_partials", ctypes.c_int64), ("pixel_rows_elems", ctypes.c_int64)]
+
+
 _P = ctypes.POINTER(CircuitStruct)
 _int, _i32, _i64, _dbl, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
 _ops, _i32p = ctypes.POINTER(MixedOp), ctypes.POINTER(ctypes.c_int32)
@@ -105,8 +120,7 @@ _image = [_i64] * 8                                        # batch, in_channels,
 _table_of = [_P, _vp, _vp] + _stream                       # circ, angles -> one device table
 _dense = [_P, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _dbl]     # circ, x .. noise_factor
 _adjoint = [_P, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64]                    # circ, inputs .. gin_ld
-_thin = [_i32, _vp] + _image + [_vp, _i64, _vp, _i32, _vp, _vp, _vp] + _stream      # qiddm_qconv_train_backward[_x32]
-_layer_ok = _image + [_i64, _i32]                          # the geometry, out_channels, row_channels
+_layer = ctypes.POINTER(QConvLayer)
 _norm_back = [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp] + _ws + _stream
 _planes = [_vp, _i64, _i64, _i64]                          # x, planes, height, width
 # what the four compute entry points of the density-matrix executor share: n_qubits .. batch
@@ -163,18 +177,11 @@ SIGNATURES = {
     "qiddm_prob_post": (_int, [_vp, _i64, _i64, _dbl, _vp] + _stream),
     "qiddm_maxpool2_forward": (_int, _planes + [_vp] + _stream),
     "qiddm_maxpool2_backward": (_int, [_vp] + _planes + [_vp] + _stream),
+    "qiddm_qconv_train_plan": (_int, [_layer, ctypes.POINTER(QConvTrainPlan)]),
+    "qiddm_qconv_train_backward": (_int, [_layer, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp] + _stream),
     "qiddm_qconv_train_rows": (_int, [_i32, _vp, _i32, _i64, _i64, _i32, _vp] + _stream),
     "qiddm_qconv_train_vectors": (_int, [_i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp] + _stream),
     "qiddm_qconv_fold_features": (_int, [_vp] + _image + [_vp] + _stream),
-    "qiddm_qconv_train_partials": (_i64, [_i64, _i64, _i64, _i64]),
-    "qiddm_qconv_train_backward": (_int, _thin),
-    "qiddm_qconv_train_x32_ok": (_i32, _layer_ok),
-    "qiddm_qconv_train_backward_x32": (_int, _thin),
-    "qiddm_qconv_train_dx_elems": (_i64, [_i32] + _layer_ok),
-    "qiddm_qconv_train_backward_dx": (_int, [_i32, _vp] + _image + [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp] + _stream),
-    "qiddm_qconv_train_bn_ok": (_i32, _layer_ok),
-    "qiddm_qconv_train_backward_bn": (_int, [_i32, _vp] + _image + [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]
-                                      + _stream),
     "qiddm_matrix_adjoint_partials": (_i64, [_i64]),
     "qiddm_matrix_adjoint_workspace_bytes": (_i64, [_P, _i64]),
     "qiddm_matrix_adjoint": (_int, [_P, _vp, _vp, _i64, _vp, _vp] + _ws + _stream),
@@ -211,7 +218,7 @@ def _declare(handle):
         fn.restype, fn.argtypes = SIGNATURES[name]
         return fn
 
-    if bind("qiddm_abi_version")() != 1:
+    if bind("qiddm_abi_version")() != 2:
         raise RuntimeError("libqiddm_hip.so ABI version mismatch; rebuild it")
     for name in SIGNATURES:
         bind(name)

@@ -10,6 +10,7 @@ be built, otherwise the call raises.
 """
 from __future__ import annotations
 
+import functools
 import os
 from dataclasses import dataclass, replace
 
@@ -708,27 +709,28 @@ def qconv_execute(x: torch.Tensor, angles: torch.Tensor, n_qubits: int, out_chan
                                 precision or _default_precision)
 
 
-def _row_channels(out_channels: int):
-    for co in (8, 16, 32):
-        if out_channels <= co:
-            return co
-    return None
+@functools.lru_cache(maxsize=256)
+def _qconv_train_plan(n_qubits, batch, in_channels, height, width, kh, kw, pad_h, pad_w, out_channels):
+    """(descriptor, plan) of a QConv2d trained through its circuit unitary (``qiddm_qconv_train_plan``): everything the
+    library decides about the layer's backward, asked once per layer shape.  The pair is shared by every caller: read
+    it, do not write to it.  A geometry the library refuses (kernel larger than the padded image, a thin layer whose
+    C H W reaches 2^24) raises ``QiddmError`` here, so from the callers below as well."""
+    layer = _capi.QConvLayer(n_qubits, 0, batch, in_channels, height, width, kh, kw, pad_h, pad_w, out_channels)
+    plan = _capi.QConvTrainPlan()
+    _capi.launch("qiddm_qconv_train_plan", None, layer, plan)
+    return layer, plan
+
+
+_QCONV_ROUTES = (None, "thin", "gemm")      # QIDDM_QCONV_ROUTE_NONE, _THIN, _GEMM
 
 
 def qconv_unitary_route(n_qubits: int, in_channels: int, kernel_size, out_channels: int):
     """Which backward serves a QConv2d trained through its circuit unitary: ``"thin"`` (the hand-written
     thin-product kernel, ``qiddm_qconv_train_backward``: <= 32 output channels), ``"gemm"`` (wider layers, e.g. C4's
-    256 channels on 12 wires: the same three products as library GEMMs over batch chunks) or None."""
-    f = in_channels * kernel_size[0] * kernel_size[1]
-    if not 2 <= n_qubits <= 12 or 2 * out_channels > 2 ** n_qubits or f > 2 ** n_qubits:
-        return None
-    co = _row_channels(out_channels)
-    if co is not None and max(kernel_size) <= 15 and f + 1 <= 512:
-        v_stride = (f + 1) | 1
-        lds = ((f + 1) * 2 * co + 64 * v_stride + 64 * (2 * co + 1) + 8 * 64 * (co + 1) + 16 * 64) * 4 + f * 4
-        if lds <= 160 * 1024:
-            return "thin"
-    return "gemm"
+    256 channels on 12 wires: the same three products as library GEMMs over batch chunks) or None.  The route does not
+    depend on the image: the plan of one image of the kernel's own extent says it."""
+    kh, kw = kernel_size
+    return _QCONV_ROUTES[_qconv_train_plan(n_qubits, 1, in_channels, kh, kw, kh, kw, 0, 0, out_channels)[1].route]
 
 
 def qconv_unitary_trainable(n_qubits: int, in_channels: int, kernel_size, out_channels: int) -> bool:
@@ -816,12 +818,12 @@ def _angle_grads_from_h(hpart, n_part, angles, n_qubits, f, c_out, co, device):
     return _adjoint_finalize(cs, ang, kp, device).reshape(angles.shape)
 
 
-# QIDDM_QCONV_X32=1: hand the thin-product backward a float32 copy of the activations (qiddm_qconv_train_backward_x32).
+# QIDDM_QCONV_X32=1: hand the thin-product backward a float32 copy of the activations (its ``x_is_f32``).
 # Measured at the unet_simple layer shapes (tools/stamp_qconv_train.py) the copy pass costs what the lighter gather gains
 # (1.35 vs 1.26 ms, 0.95 vs 0.93 ms, 0.34 vs 0.36 ms per layer backward), so float64 activations go in as they are
 _QCONV_X32 = os.environ.get("QIDDM_QCONV_X32", "0") == "1"
 # QIDDM_QCONV_FOLD=1: keep the (F, M) feature gradients + fold for dL/dx instead of the per-pixel rows + transposed
-# convolution (qiddm_qconv_train_backward_dx); the library reads the same variable
+# convolution (``pixel_rows``); the library reads the same variable
 _QCONV_DX = os.environ.get("QIDDM_QCONV_FOLD") is None
 # QIDDM_QCONV_BN_SPLIT=1: keep [QConv2d, BatchNorm2d] as two autograd nodes in training (no folding of the BatchNorm
 # backward into the convolution's)
@@ -890,13 +892,14 @@ class _QConvUnitaryFunction(torch.autograd.Function):
 def _qconv_unitary_backward(x, angles, u, cfg, grad_y, need_gx, need_ga, bn=None):
     """Backward of the unitary-route QConv2d: (dL/dx or None, dL/dangles or None).  ``bn = (conv_y, coef)``: grad_y is the
     gradient BEHIND the training-mode BatchNorm2d that follows the layer, and dL/dy is formed per channel as
-    ``coef[0] * grad_y + coef[1] * conv_y + coef[2]`` inside the thin-product kernel (``qiddm_qconv_train_backward_bn``)."""
+    ``coef[0] * grad_y + coef[1] * conv_y + coef[2]`` inside the thin-product kernel."""
     n_qubits, c_out, (kh, kw), (ph, pw) = cfg
     device = x.device
     b, c, h, w = x.shape
     f = c * kh * kw
     ho, wo = _conv_out(h, w, (kh, kw), (ph, pw))
-    if qconv_unitary_route(n_qubits, c, (kh, kw), c_out) == "gemm":
+    layer, plan = _qconv_train_plan(n_qubits, b, c, h, w, kh, kw, ph, pw, c_out)
+    if _QCONV_ROUTES[plan.route] == "gemm":
         if bn is not None:      # library-GEMM route: apply the BatchNorm coefficients with torch
             conv_y, coef = bn
             shape = (1, c_out, 1, 1)
@@ -904,31 +907,22 @@ def _qconv_unitary_backward(x, angles, u, cfg, grad_y, need_gx, need_ga, bn=None
         hpart, gx = _qconv_unitary_backward_gemm(x, grad_y, u, n_qubits, c_out, (kh, kw), (ph, pw), need_gx)
         ga = _angle_grads_off_stream(hpart, 1, angles, n_qubits, f, c_out, c_out, device) if need_ga else None
         return (None if gx is None else gx.to(x.dtype)), ga
-    co = _row_channels(c_out)
+    co, n_part = plan.row_channels, plan.n_partials
     rt = _unitary_rows(u, n_qubits, f, c_out, co, device)
     # the matrix-core kernel converts every patch element to float32 anyway: hand it a float32 copy (one elementwise
     # pass; its gather then holds half the bytes in flight)
-    x32 = bn is None and _QCONV_X32 and bool(_capi.query("qiddm_qconv_train_x32_ok", b, c, h, w, kh, kw, ph, pw, c_out, co))
+    x32 = bn is None and _QCONV_X32 and bool(plan.matrix_core)
     xx = x.detach().to(device=device, dtype=torch.float32).contiguous() if x32 else _as_f64(x, device).contiguous()
-    n_part = _capi.query("qiddm_qconv_train_partials", b, ho, wo, f)
     hpart = torch.empty(n_part, 2 * co, f + 1, dtype=torch.float32, device=device)
     gx = torch.empty(b, c, h, w, dtype=torch.float64, device=device) if need_gx else None
     # dL/dx from 2 co + 1 floats per pixel where the layer allows it (same-size convolution on the matrix-core
     # kernel), instead of the (F, M) feature gradients and their fold
-    dx_elems = 0 if (gx is None or x32 or not _QCONV_DX) else \
-        _capi.query("qiddm_qconv_train_dx_elems", n_qubits, b, c, h, w, kh, kw, ph, pw, c_out, co)
+    dx_elems = 0 if (gx is None or x32 or not _QCONV_DX) else plan.pixel_rows_elems
     wpix = torch.empty(dx_elems, dtype=torch.float32, device=device) if dx_elems > 0 else None
     gfeat_t = torch.empty(f, b * ho * wo, dtype=torch.float32, device=device) if wpix is None else None
     gy = _as_f64(grad_y, device)            # dense: grad_y_batch_stride below is always 0
-    geom = (n_qubits, xx, b, c, h, w, kh, kw, ph, pw)
-    if bn is not None:
-        conv_y, coef = bn
-        _capi.launch("qiddm_qconv_train_backward_bn", device, *geom, gy, conv_y, coef, c_out, rt, co, gfeat_t, wpix, hpart, gx)
-    elif wpix is not None:
-        _capi.launch("qiddm_qconv_train_backward_dx", device, *geom, gy, 0, c_out, rt, co, wpix, hpart, gx)
-    else:
-        _capi.launch("qiddm_qconv_train_backward_x32" if x32 else "qiddm_qconv_train_backward", device, *geom, gy, c_out,
-                     rt, co, gfeat_t, hpart, gx)
+    conv_y, coef = (None, None) if bn is None else bn
+    _capi.launch("qiddm_qconv_train_backward", device, layer, xx, int(x32), gy, 0, conv_y, coef, rt, gfeat_t, wpix, hpart, gx)
     ga = _angle_grads_off_stream(hpart, n_part, angles, n_qubits, f, c_out, co, device) if need_ga else None
     return (None if gx is None else gx.to(x.dtype)), ga
 
@@ -1048,13 +1042,10 @@ class _QConvBNTrainFunction(torch.autograd.Function):
 
 def qconv_bn_foldable(x_shape, n_qubits: int, out_channels: int, kernel_size, padding) -> bool:
     """Whether the unitary-route backward of this layer can apply a following BatchNorm's backward transform itself
-    (``qiddm_qconv_train_bn_ok``; the library-GEMM route of the widest layers does it with torch)."""
-    b, c, h, w = x_shape
-    (kh, kw), (ph, pw) = kernel_size, padding
-    route = qconv_unitary_route(n_qubits, c, (kh, kw), out_channels)
-    if route != "thin":
-        return route == "gemm"
-    return bool(_capi.query("qiddm_qconv_train_bn_ok", b, c, h, w, kh, kw, ph, pw, out_channels, _row_channels(out_channels)))
+    (the plan's ``bn_fold``; the library-GEMM route of the widest layers does it with torch)."""
+    plan = _qconv_train_plan(n_qubits, *x_shape, *kernel_size, *padding, out_channels)[1]
+    route = _QCONV_ROUTES[plan.route]
+    return bool(plan.bn_fold) if route == "thin" else route == "gemm"
 
 
 def batch_norm_eligible(bn: torch.nn.BatchNorm2d, channels: int) -> bool:

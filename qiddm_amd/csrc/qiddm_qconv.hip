@@ -1,5 +1,6 @@
-// qiddm_qconv.hip -- extern "C" entry points of the eval-mode quantum convolution (circuit unitary + MFMA GEMM);
-// device code in qsim_unitary.h.
+// qiddm_qconv.hip -- extern "C" entry points of the quantum convolution through its circuit unitary: the unitary itself,
+// the eval-mode forward (unitary + MFMA GEMM) and the training backward (one layer descriptor -> one plan -> one entry);
+// device code in the qsim_qconv_*.h / qsim_unitary.h headers.
 #include "capi_common.h"
 
 #include <hip/hip_runtime.h>
@@ -261,6 +262,9 @@ int qiddm_qconv_unitary_forward(int32_t n_qubits, const double* u, const double*
   return launched("qconv_gemm_kernel");
 }
 
+// ---- training backward through the circuit unitary: one layer descriptor -> one plan, read by qiddm_qconv_train_plan and
+// launched by qiddm_qconv_train_backward --------------------------------------------------------------------------------
+extern "C++" {
 namespace {
 // resident workgroups of the thin-product backward (= per-workgroup h slabs).  The kernel's tiles wait on gathered
 // global loads, so it wants every workgroup the LDS admits: up to four per CU for narrow layers (<= 160 patch
@@ -275,18 +279,12 @@ int train_groups(int64_t features) {
   const int64_t g = qiddm::kTcThreads / (features + 1);
   return g < 1 ? 1 : (g > 8 ? 8 : (int)g);
 }
-}  // namespace
 
-int64_t qiddm_qconv_train_partials(int64_t batch, int64_t height_out, int64_t width_out, int64_t features) {
-  if (batch < 0 || height_out < 1 || width_out < 1 || features < 1) return -1;
-  return train_grid(batch * height_out * width_out, features);
-}
-
-extern "C++" {
-namespace {
-// the matrix-core variant of the thin-product backward for this layer (nullptr: the VALU kernel keeps it)
+// the matrix-core variants of the thin-product backward for this layer (all nullptr: the VALU kernel keeps it)
 struct TmChoice {
-  const void* kern = nullptr;
+  const void* f32 = nullptr;  // float32 copy of the activations
+  const void* bn = nullptr;   // float64 x, BatchNorm coefficients applied to dL/dy (nullptr at 32 row channels)
+  const void* f64 = nullptr;
   size_t smem = 0;
 };
 // the BatchNorm-folding variant of a shape (8 / 16 row channels only: see the kernel's BN parameter); nullptr otherwise
@@ -297,8 +295,7 @@ const void* tm_bn_kernel() {
   else
     return nullptr;
 }
-TmChoice train_mfma_choice(int64_t f, int32_t row_channels, bool fits32, bool x32, int64_t kh, int64_t kw, int64_t c_in,
-                           bool bn = false) {
+TmChoice train_mfma_choice(int64_t f, int32_t row_channels, bool fits32, int64_t kh, int64_t kw, int64_t c_in) {
   // from 32 patch features on and whenever its LDS tiles fit; the VALU kernel keeps the narrowest layers (9 / 16
   // features: the whole backward of the layer measured 0.37 / 0.55 ms against 0.53 / 0.67 on the MFMA kernel at
   // 2560 x 28 x 28 pixels, tools/stamp_qconv_train.py; from 32 features on the MFMA kernel wins) and the widest.
@@ -311,21 +308,21 @@ TmChoice train_mfma_choice(int64_t f, int32_t row_channels, bool fits32, bool x3
   if (env_valu || !fits32 || (f < 32 && !env_mfma && !narrow_ok)) return ch;
   const int jbm = (int)((qiddm::tm_fcols((int)f) / 16 + qiddm::kTmWaves - 1) / qiddm::kTmWaves);
 #define QIDDM_TM_CASE(CO, J)                                                                                       \
-  if (!ch.kern && row_channels == CO && jbm <= J && qiddm::tm_lds_bytes_bn<CO>((int)f) <= kMaxLds) {                   \
+  if (!ch.smem && row_channels == CO && jbm <= J && qiddm::tm_lds_bytes_bn<CO>((int)f) <= kMaxLds) {                  \
     ch.smem = qiddm::tm_lds_bytes_bn<CO>((int)f);                                                                     \
-    ch.kern = x32 ? reinterpret_cast<const void*>(qiddm::qconv_train_backward_mfma_kernel<CO, J, float>)           \
-                  : (bn ? tm_bn_kernel<CO, J, 0, 0>()                                                              \
-                        : reinterpret_cast<const void*>(qiddm::qconv_train_backward_mfma_kernel<CO, J, double>));  \
+    ch.f32 = reinterpret_cast<const void*>(qiddm::qconv_train_backward_mfma_kernel<CO, J, float>);                 \
+    ch.bn = tm_bn_kernel<CO, J, 0, 0>();                                                                           \
+    ch.f64 = reinterpret_cast<const void*>(qiddm::qconv_train_backward_mfma_kernel<CO, J, double>);                \
   }
   // the layer shapes of unet_simple with kernel extent and channel count compiled in (no control flow in the gather)
   static const bool env_generic = std::getenv("QIDDM_QCONV_GENERIC") != nullptr;
 #define QIDDM_TM_SCASE(CO, J, SK, SC)                                                                              \
-  if (!ch.kern && !env_generic && row_channels == CO && jbm <= J && kh == SK && kw == SK && c_in == SC &&          \
+  if (!ch.smem && !env_generic && row_channels == CO && jbm <= J && kh == SK && kw == SK && c_in == SC &&          \
       qiddm::tm_lds_bytes_bn<CO>((int)f) <= kMaxLds) {                                                                \
     ch.smem = qiddm::tm_lds_bytes_bn<CO>((int)f);                                                                     \
-    ch.kern = x32 ? reinterpret_cast<const void*>(qiddm::qconv_train_backward_mfma_kernel<CO, J, float, SK, SC>)   \
-                  : (bn ? tm_bn_kernel<CO, J, SK, SC>()                                                            \
-                        : reinterpret_cast<const void*>(qiddm::qconv_train_backward_mfma_kernel<CO, J, double, SK, SC>)); \
+    ch.f32 = reinterpret_cast<const void*>(qiddm::qconv_train_backward_mfma_kernel<CO, J, float, SK, SC>);         \
+    ch.bn = tm_bn_kernel<CO, J, SK, SC>();                                                                         \
+    ch.f64 = reinterpret_cast<const void*>(qiddm::qconv_train_backward_mfma_kernel<CO, J, double, SK, SC>);        \
   }
   QIDDM_TM_SCASE(8, 2, 1, 16)
   QIDDM_TM_SCASE(8, 4, 3, 16)
@@ -346,16 +343,6 @@ TmChoice train_mfma_choice(int64_t f, int32_t row_channels, bool fits32, bool x3
 #undef QIDDM_TM_CASE
   return ch;
 }
-bool train_fits32(int64_t batch, int64_t in_channels, int64_t height, int64_t width, int64_t out_channels, int64_t ho,
-                  int64_t wo) {
-  // the MFMA kernel addresses x and grad_y with 32-bit element offsets
-  return batch * in_channels * height * width < ((int64_t)1 << 32) && batch * out_channels * ho * wo < ((int64_t)1 << 32);
-}
-int train_backward(int32_t n_qubits, const void* x, bool x32, int64_t batch, int64_t in_channels, int64_t height,
-                   int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w, const double* grad_y,
-                   int64_t out_channels, const float* rows, int32_t row_channels, float* grad_features_t,
-                   float* pixel_rows, float* h_partials, double* grad_x, void* stream, const double* bn_y = nullptr,
-                   const double* bn_coef = nullptr, int64_t grad_y_batch_stride = 0);
 
 // dL/dx from per-pixel rows (qsim_qconv_dx.h) instead of feature gradients + fold: the matrix-core kernel, a same-size
 // convolution, at most 32 input channels, LDS of the dx kernel within the limit.  QIDDM_QCONV_FOLD=1 switches it off.
@@ -400,176 +387,147 @@ DxChoice train_dx_choice(const qiddm::TrainConv& tc, int32_t row_channels, bool 
   }
   return ch;
 }
-qiddm::TrainConv train_geometry(int32_t n_qubits, int64_t batch, int64_t in_channels, int64_t height, int64_t width,
-                                int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w, int64_t out_channels) {
-  const int64_t d = (int64_t)1 << n_qubits, f = in_channels * kh * kw;
-  const int64_t ho = height + 2 * pad_h - kh + 1, wo = width + 2 * pad_w - kw + 1;
+
+// what every descriptor has to satisfy, whichever route its layer takes
+int check_layer(const qiddm_qconv_layer_t* l) {
+  if (!l) return fail(QIDDM_ERR_INVALID, "layer is NULL");
+  if (l->batch < 1 || l->in_channels < 1 || l->height < 1 || l->width < 1 || l->kh < 1 || l->kw < 1 || l->pad_h < 0 ||
+      l->pad_w < 0 || l->out_channels < 1)
+    return fail(QIDDM_ERR_INVALID, "layer: bad convolution geometry");
+  const int64_t ho = l->height + 2 * l->pad_h - l->kh + 1, wo = l->width + 2 * l->pad_w - l->kw + 1;
+  if (ho < 1 || wo < 1) return fail(QIDDM_ERR_INVALID, "layer: kernel larger than the padded image");
+  if (l->batch * ho * wo >= ((int64_t)1 << 40)) return fail(QIDDM_ERR_INVALID, "layer: too many output pixels");
+  return QIDDM_OK;
+}
+
+qiddm::TrainConv train_geometry(const qiddm_qconv_layer_t& l) {
+  const int64_t d = (int64_t)1 << l.n_qubits, f = l.in_channels * l.kh * l.kw;
+  const int64_t ho = l.height + 2 * l.pad_h - l.kh + 1, wo = l.width + 2 * l.pad_w - l.kw + 1;
   qiddm::TrainConv tc;
   std::memset(&tc, 0, sizeof(tc));
-  tc.C = (int32_t)in_channels;
-  tc.H = (int32_t)height;
-  tc.W = (int32_t)width;
-  tc.kh = (int32_t)kh;
-  tc.kw = (int32_t)kw;
-  tc.ph = (int32_t)pad_h;
-  tc.pw = (int32_t)pad_w;
+  tc.C = (int32_t)l.in_channels;
+  tc.H = (int32_t)l.height;
+  tc.W = (int32_t)l.width;
+  tc.kh = (int32_t)l.kh;
+  tc.kw = (int32_t)l.kw;
+  tc.ph = (int32_t)l.pad_h;
+  tc.pw = (int32_t)l.pad_w;
   tc.Ho = (int32_t)ho;
   tc.Wo = (int32_t)wo;
-  tc.C_out = (int32_t)out_channels;
+  tc.C_out = (int32_t)l.out_channels;
   tc.F = (int32_t)f;
-  tc.M = batch * ho * wo;
-  tc.gy_bstride = out_channels * ho * wo;
+  tc.groups = train_groups(f);
+  tc.M = l.batch * ho * wo;
+  tc.gy_bstride = l.out_channels * ho * wo;
   tc.pad_norm2 = 0.25f * (float)(d - f);
   tc.post_scale = 0.5f * (float)d;
   return tc;
 }
+
+// everything the library decides about a layer: what the plan reports and what the entry launches
+struct TrainPlan {
+  int32_t route = QIDDM_QCONV_ROUTE_NONE, row_channels = 0;
+  qiddm::TrainConv tc;  // dense grad_y, no BatchNorm, no pixel rows: the entry fills those in
+  int64_t grid = 0;     // workgroups of the thin-product kernel = slabs of h_partials
+  TmChoice tm;          // matrix-core kernel (tm.f64 == nullptr: the VALU kernel)
+  DxChoice dx;          // per-pixel-row route (dx.kern == nullptr: feature gradients + fold)
+  bool bn_fold = false;
+};
+int train_plan(const qiddm_qconv_layer_t* l, TrainPlan* p) {
+  const int rc = check_layer(l);
+  if (rc != QIDDM_OK) return rc;
+  *p = TrainPlan{};
+  // the route and the row channels from (n_qubits, in_channels, kh, kw, out_channels) alone
+  const int32_t co = l->out_channels <= 8 ? 8 : l->out_channels <= 16 ? 16 : l->out_channels <= 32 ? 32 : 0;
+  p->row_channels = co;
+  if (l->n_qubits < 2 || l->n_qubits > 12) return QIDDM_OK;
+  const int64_t d = (int64_t)1 << l->n_qubits;
+  if (2 * l->out_channels > d || l->in_channels > d || l->kh > d || l->kw > d) return QIDDM_OK;
+  const int64_t f = l->in_channels * l->kh * l->kw;
+  if (f > d) return QIDDM_OK;
+  p->route = QIDDM_QCONV_ROUTE_GEMM;
+  // the thin-product kernels: 8 / 16 / 32 row channels, taps in four bits, one column chunk per thread, the VALU
+  // kernel's LDS within the limit (it is the kernel every thin layer can fall back to)
+  if (co == 0 || l->kh > 15 || l->kw > 15 || f + 1 > qiddm::kTcThreads) return QIDDM_OK;
+  const size_t valu_lds = co == 8 ? qiddm::tc_lds_bytes<8>((int)f)
+                                  : co == 16 ? qiddm::tc_lds_bytes<16>((int)f) : qiddm::tc_lds_bytes<32>((int)f);
+  if (valu_lds > kMaxLds) return QIDDM_OK;
+  if (l->in_channels * l->height * l->width >= (1 << 24))
+    return fail(QIDDM_ERR_UNSUPPORTED, "layer: image plane stack beyond 2^24 elements");
+  p->route = QIDDM_QCONV_ROUTE_THIN;
+  p->tc = train_geometry(*l);
+  p->grid = train_grid(p->tc.M, f);
+  // the MFMA kernel addresses x and grad_y with 32-bit element offsets
+  const bool fits32 = l->batch * l->in_channels * l->height * l->width < ((int64_t)1 << 32) &&
+                      l->batch * p->tc.gy_bstride < ((int64_t)1 << 32);
+  p->tm = train_mfma_choice(f, co, fits32, l->kh, l->kw, l->in_channels);
+  p->bn_fold = !p->tm.f64 || p->tm.bn;   // (the VALU kernel folds every layer)
+  p->dx = train_dx_choice(p->tc, co, p->tm.f64 != nullptr);
+  return QIDDM_OK;
+}
 }  // namespace
 }  // extern "C++"
 
-int64_t qiddm_qconv_train_dx_elems(int32_t n_qubits, int64_t batch, int64_t in_channels, int64_t height, int64_t width,
-                                   int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w, int64_t out_channels,
-                                   int32_t row_channels) {
-  if (n_qubits < 1 || n_qubits > 12 || batch < 1 || in_channels < 1 || height < 1 || width < 1 || kh < 1 || kw < 1 ||
-      pad_h < 0 || pad_w < 0 || out_channels < 1 || kh > 15 || kw > 15)
-    return 0;
-  const int64_t ho = height + 2 * pad_h - kh + 1, wo = width + 2 * pad_w - kw + 1;
-  if (ho < 1 || wo < 1) return 0;
-  const int64_t f = in_channels * kh * kw;
-  const qiddm::TrainConv tc = train_geometry(n_qubits, batch, in_channels, height, width, kh, kw, pad_h, pad_w, out_channels);
-  const bool mfma = train_mfma_choice(f, row_channels, train_fits32(batch, in_channels, height, width, out_channels, ho, wo),
-                                      false, kh, kw, in_channels).kern != nullptr;
-  if (!train_dx_choice(tc, row_channels, mfma).kern) return 0;
-  return tc.M * (2 * (int64_t)row_channels + 1);
+int qiddm_qconv_train_plan(const qiddm_qconv_layer_t* layer, qiddm_qconv_train_plan_t* plan) {
+  TrainPlan p;
+  const int rc = train_plan(layer, &p);
+  if (rc != QIDDM_OK) return rc;
+  if (!plan) return fail(QIDDM_ERR_INVALID, "plan is NULL");
+  std::memset(plan, 0, sizeof(*plan));
+  plan->route = p.route;
+  plan->row_channels = p.row_channels;
+  if (p.route != QIDDM_QCONV_ROUTE_THIN) return QIDDM_OK;
+  plan->matrix_core = p.tm.f64 != nullptr;
+  plan->bn_fold = p.bn_fold;
+  plan->n_partials = p.grid;
+  plan->pixel_rows_elems = p.dx.kern ? p.tc.M * (2 * (int64_t)p.row_channels + 1) : 0;
+  return QIDDM_OK;
 }
 
-int32_t qiddm_qconv_train_bn_ok(int64_t batch, int64_t in_channels, int64_t height, int64_t width, int64_t kh, int64_t kw,
-                                int64_t pad_h, int64_t pad_w, int64_t out_channels, int32_t row_channels) {
-  if (batch < 1 || in_channels < 1 || height < 1 || width < 1 || kh < 1 || kw < 1 || pad_h < 0 || pad_w < 0 ||
-      out_channels < 1)
-    return 0;
-  const int64_t ho = height + 2 * pad_h - kh + 1, wo = width + 2 * pad_w - kw + 1;
-  if (ho < 1 || wo < 1) return 0;
-  const int64_t f = in_channels * kh * kw;
-  const bool fits = train_fits32(batch, in_channels, height, width, out_channels, ho, wo);
-  if (!train_mfma_choice(f, row_channels, fits, false, kh, kw, in_channels).kern) return 1;   // the VALU kernel folds it
-  return train_mfma_choice(f, row_channels, fits, false, kh, kw, in_channels, true).kern != nullptr ? 1 : 0;
-}
-
-int qiddm_qconv_train_backward_bn(int32_t n_qubits, const double* x, int64_t batch, int64_t in_channels, int64_t height,
-                                  int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w,
-                                  const double* grad_out, const double* conv_y, const double* bn_coef,
-                                  int64_t out_channels, const float* rows, int32_t row_channels,
-                                  float* grad_features_t, float* pixel_rows, float* h_partials, double* grad_x,
-                                  void* stream) {
-  if (!conv_y || !bn_coef) return fail(QIDDM_ERR_INVALID, "conv_y/bn_coef is NULL");
-  if (pixel_rows && (!grad_x || qiddm_qconv_train_dx_elems(n_qubits, batch, in_channels, height, width, kh, kw, pad_h,
-                                                            pad_w, out_channels, row_channels) <= 0))
-    return fail(QIDDM_ERR_UNSUPPORTED, "pixel_rows: this layer keeps the feature-gradient route");
-  return train_backward(n_qubits, x, false, batch, in_channels, height, width, kh, kw, pad_h, pad_w, grad_out,
-                        out_channels, rows, row_channels, pixel_rows ? nullptr : grad_features_t, pixel_rows, h_partials,
-                        grad_x, stream, conv_y, bn_coef);
-}
-
-int qiddm_qconv_train_backward_dx(int32_t n_qubits, const double* x, int64_t batch, int64_t in_channels, int64_t height,
-                                  int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w,
-                                  const double* grad_y, int64_t grad_y_batch_stride, int64_t out_channels,
-                                  const float* rows, int32_t row_channels, float* pixel_rows, float* h_partials,
-                                  double* grad_x, void* stream) {
-  if (!pixel_rows || !grad_x) return fail(QIDDM_ERR_INVALID, "pixel_rows/grad_x is NULL");
-  if (qiddm_qconv_train_dx_elems(n_qubits, batch, in_channels, height, width, kh, kw, pad_h, pad_w, out_channels,
-                                 row_channels) <= 0)
-    return fail(QIDDM_ERR_UNSUPPORTED, "this layer keeps the feature-gradient route (qiddm_qconv_train_dx_elems() == 0)");
-  return train_backward(n_qubits, x, false, batch, in_channels, height, width, kh, kw, pad_h, pad_w, grad_y,
-                        out_channels, rows, row_channels, nullptr, pixel_rows, h_partials, grad_x, stream, nullptr, nullptr,
-                        grad_y_batch_stride);
-}
-
-int32_t qiddm_qconv_train_x32_ok(int64_t batch, int64_t in_channels, int64_t height, int64_t width, int64_t kh,
-                                 int64_t kw, int64_t pad_h, int64_t pad_w, int64_t out_channels, int32_t row_channels) {
-  if (batch < 1 || in_channels < 1 || height < 1 || width < 1 || kh < 1 || kw < 1 || pad_h < 0 || pad_w < 0 ||
-      out_channels < 1)
-    return 0;
-  const int64_t ho = height + 2 * pad_h - kh + 1, wo = width + 2 * pad_w - kw + 1;
-  if (ho < 1 || wo < 1) return 0;
-  const int64_t f = in_channels * kh * kw;
-  return train_mfma_choice(f, row_channels, train_fits32(batch, in_channels, height, width, out_channels, ho, wo), true,
-                           kh, kw, in_channels)
-                 .kern != nullptr
-             ? 1
-             : 0;
-}
-
-int qiddm_qconv_train_backward(int32_t n_qubits, const double* x, int64_t batch, int64_t in_channels, int64_t height,
-                               int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w,
-                               const double* grad_y, int64_t out_channels, const float* rows, int32_t row_channels,
-                               float* grad_features_t, float* h_partials, double* grad_x, void* stream) {
-  return train_backward(n_qubits, x, false, batch, in_channels, height, width, kh, kw, pad_h, pad_w, grad_y,
-                        out_channels, rows, row_channels, grad_features_t, nullptr, h_partials, grad_x, stream);
-}
-
-int qiddm_qconv_train_backward_x32(int32_t n_qubits, const float* x, int64_t batch, int64_t in_channels,
-                                   int64_t height, int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w,
-                                   const double* grad_y, int64_t out_channels, const float* rows,
-                                   int32_t row_channels, float* grad_features_t, float* h_partials, double* grad_x,
-                                   void* stream) {
-  return train_backward(n_qubits, x, true, batch, in_channels, height, width, kh, kw, pad_h, pad_w, grad_y,
-                        out_channels, rows, row_channels, grad_features_t, nullptr, h_partials, grad_x, stream);
-}
-
-namespace {
-int train_backward(int32_t n_qubits, const void* x, bool x32, int64_t batch, int64_t in_channels, int64_t height,
-                   int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w, const double* grad_y,
-                   int64_t out_channels, const float* rows, int32_t row_channels, float* grad_features_t,
-                   float* pixel_rows, float* h_partials, double* grad_x, void* stream, const double* bn_y,
-                   const double* bn_coef, int64_t grad_y_batch_stride) {
-  if ((bn_y == nullptr) != (bn_coef == nullptr)) return fail(QIDDM_ERR_INVALID, "bn_y and bn_coef go together");
-  if (n_qubits < 1 || n_qubits > 12) return fail(QIDDM_ERR_UNSUPPORTED, "n_qubits=%d outside 1..12", n_qubits);
-  if (batch < 1 || in_channels < 1 || height < 1 || width < 1 || kh < 1 || kw < 1 || pad_h < 0 || pad_w < 0 ||
-      out_channels < 1)
-    return fail(QIDDM_ERR_INVALID, "bad convolution geometry");
-  if (kh > 15 || kw > 15 || in_channels * height * width >= (1 << 24))
-    return fail(QIDDM_ERR_UNSUPPORTED, "kernel larger than 15 or image plane stack beyond 2^24 elements");
-  const int64_t d = (int64_t)1 << n_qubits, f = in_channels * kh * kw;
-  if (f > d) return fail(QIDDM_ERR_INVALID, "in_channels*kh*kw=%lld exceeds 2^n=%lld", (long long)f, (long long)d);
-  if (2 * out_channels > d) return fail(QIDDM_ERR_INVALID, "out_channels beyond the even-index probabilities");
-  if (out_channels > row_channels) return fail(QIDDM_ERR_INVALID, "out_channels > row_channels");
-  const int64_t ho = height + 2 * pad_h - kh + 1, wo = width + 2 * pad_w - kw + 1;
-  if (ho < 1 || wo < 1) return fail(QIDDM_ERR_INVALID, "kernel larger than the padded image");
-  if (batch * ho * wo >= ((int64_t)1 << 40)) return fail(QIDDM_ERR_INVALID, "too many output pixels");
-  if (!x || !grad_y || !rows || (!grad_features_t && !pixel_rows) || !h_partials)
-    return fail(QIDDM_ERR_INVALID, "x/grad_y/rows/grad_features_t/h_partials is NULL");
-  const int jch = (int)((f + 1 + qiddm::kTcThreads - 1) / qiddm::kTcThreads);
-  qiddm::TrainConv tc = train_geometry(n_qubits, batch, in_channels, height, width, kh, kw, pad_h, pad_w, out_channels);
-  tc.groups = train_groups(f);
-  tc.bn_y = bn_y;
-  tc.bn_coef = bn_coef;
+int qiddm_qconv_train_backward(const qiddm_qconv_layer_t* layer, const void* x, int32_t x_is_f32, const double* grad_y,
+                               int64_t grad_y_batch_stride, const double* conv_y, const double* bn_coef,
+                               const float* rows, float* grad_features_t, float* pixel_rows, float* h_partials,
+                               double* grad_x, void* stream) {
+  TrainPlan p;
+  int rc = train_plan(layer, &p);
+  if (rc != QIDDM_OK) return rc;
+  if (p.route != QIDDM_QCONV_ROUTE_THIN)
+    return fail(QIDDM_ERR_UNSUPPORTED, "layer: outside the thin-product backward (qiddm_qconv_train_plan: route %d)", p.route);
+  if (!x || !grad_y || !rows || !h_partials) return fail(QIDDM_ERR_INVALID, "x/grad_y/rows/h_partials is NULL");
+  if (!grad_features_t && !pixel_rows) return fail(QIDDM_ERR_INVALID, "grad_features_t/pixel_rows: one of them is required");
+  if ((conv_y == nullptr) != (bn_coef == nullptr)) return fail(QIDDM_ERR_INVALID, "conv_y and bn_coef go together");
+  if (conv_y && !p.bn_fold)
+    return fail(QIDDM_ERR_UNSUPPORTED, "conv_y/bn_coef: no BatchNorm-folding variant for this layer (plan.bn_fold == 0)");
+  if (x_is_f32 && !p.tm.f64)
+    return fail(QIDDM_ERR_UNSUPPORTED, "x_is_f32: float32 x is taken by the matrix-core kernel only (plan.matrix_core == 0)");
+  if (x_is_f32 && (conv_y || pixel_rows))
+    return fail(QIDDM_ERR_UNSUPPORTED, "x_is_f32: float32 x goes with neither conv_y/bn_coef nor pixel_rows");
+  if (pixel_rows && !grad_x) return fail(QIDDM_ERR_INVALID, "pixel_rows needs grad_x");
+  if (pixel_rows && !p.dx.kern)
+    return fail(QIDDM_ERR_UNSUPPORTED, "pixel_rows: this layer keeps the feature-gradient route (plan.pixel_rows_elems == 0)");
+  qiddm::TrainConv tc = p.tc;
+  const int64_t batch = layer->batch, f = tc.F;
   if (grad_y_batch_stride != 0) {
     if (grad_y_batch_stride < tc.gy_bstride) return fail(QIDDM_ERR_INVALID, "grad_y_batch_stride smaller than an image");
     if (batch * grad_y_batch_stride >= ((int64_t)1 << 32))
-      return fail(QIDDM_ERR_UNSUPPORTED, "strided grad_y beyond 2^32 elements");
+      return fail(QIDDM_ERR_UNSUPPORTED, "grad_y_batch_stride: strided grad_y beyond 2^32 elements");
     tc.gy_bstride = grad_y_batch_stride;
   }
+  tc.bn_y = conv_y;
+  tc.bn_coef = bn_coef;
   tc.stamps = qiddm_capi::stamp_buffer(8);
-  const unsigned grid = (unsigned)train_grid(batch * ho * wo, f);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  size_t smem = 0;
-  const void* kern = nullptr;
-  unsigned threads = qiddm::kTcThreads;
-  // the three products on the f32 matrix cores (qsim_qconv_train_mfma.h) where train_mfma_choice() says so
-  TmChoice tm = train_mfma_choice(f, row_channels,
-                                  train_fits32(batch, in_channels, height, width, out_channels, ho, wo), x32, kh, kw,
-                                  in_channels, bn_y != nullptr);
-  if (bn_y && tm.smem && !tm.kern)
-    return fail(QIDDM_ERR_UNSUPPORTED, "no BatchNorm-folding variant for this layer (qiddm_qconv_train_bn_ok() == 0)");
-  if (tm.kern) {
-    kern = tm.kern;
-    smem = tm.smem;
-    threads = qiddm::kTmThreads;
-  } else if (x32) {
-    return fail(QIDDM_ERR_UNSUPPORTED, "float32 x is taken by the matrix-core kernel only (qiddm_qconv_train_x32_ok)");
+  if (pixel_rows) {
+    tc.wpix = pixel_rows;
+    grad_features_t = nullptr;
   }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the three products on the f32 matrix cores (qsim_qconv_train_mfma.h) where train_mfma_choice() says so
+  const void* kern = x_is_f32 ? p.tm.f32 : (conv_y ? p.tm.bn : p.tm.f64);
+  size_t smem = p.tm.smem;
+  const unsigned threads = kern ? qiddm::kTmThreads : qiddm::kTcThreads;
+  const int jch = (int)((f + 1 + qiddm::kTcThreads - 1) / qiddm::kTcThreads);
 #define QIDDM_TC_CASE(CO, J)                                                                      \
-  if (!kern && row_channels == CO && jch == J) {                                                           \
+  if (!kern && p.row_channels == CO && jch == J) {                                                \
     smem = qiddm::tc_lds_bytes<CO>((int)f);                                                       \
     kern = reinterpret_cast<const void*>(qiddm::qconv_train_backward_kernel<CO, J>);              \
   }
@@ -577,68 +535,44 @@ int train_backward(int32_t n_qubits, const void* x, bool x32, int64_t batch, int
   QIDDM_TC_CASE(16, 1)
   QIDDM_TC_CASE(32, 1)
 #undef QIDDM_TC_CASE
-  if (!kern)
-    return fail(QIDDM_ERR_UNSUPPORTED, "unitary-route backward: row_channels=%d with %lld features is outside "
-                "{8,16,32} x 511", row_channels, (long long)f);
-  if (smem > kMaxLds) return fail(QIDDM_ERR_UNSUPPORTED, "unitary-route backward needs %zu B of LDS", smem);
   if (smem > 48 * 1024) {
     const hipError_t ea = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     if (ea != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
   }
-  DxChoice dx;
-  if (pixel_rows) {
-    dx = train_dx_choice(tc, row_channels, tm.kern != nullptr);
-    if (!dx.kern) return fail(QIDDM_ERR_UNSUPPORTED, "the per-pixel-row route does not take this layer");
-    tc.wpix = pixel_rows;
-  }
   void* args[] = {(void*)&x, (void*)&grad_y, (void*)&rows, (void*)&grad_features_t, (void*)&h_partials, (void*)&tc};
-  int rc = launch_status("qconv_train_backward_kernel", hipLaunchKernel(kern, dim3(grid), dim3(threads), args, smem, st));
+  rc = launch_status("qconv_train_backward_kernel",
+                     hipLaunchKernel(kern, dim3((unsigned)p.grid), dim3(threads), args, smem, st));
   if (rc != QIDDM_OK) return rc;
   if (pixel_rows) {
-    if (dx.smem > 48 * 1024) {
-      const hipError_t ea = hipFuncSetAttribute(dx.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    if (p.dx.smem > 48 * 1024) {
+      const hipError_t ea = hipFuncSetAttribute(p.dx.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
       if (ea != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "hipFuncSetAttribute(LDS) failed: %s", hipGetErrorString(ea));
     }
     // resident workgroups only (each stages the rows table once and walks its tiles): up to eight per CU by threads
     const int64_t dtiles = (tc.M + qiddm::kDxTile - 1) / qiddm::kDxTile;
-    const int64_t per_cu = std::min<int64_t>(8, (int64_t)(kMaxLds / (dx.smem + 1024)));
+    const int64_t per_cu = std::min<int64_t>(8, (int64_t)(kMaxLds / (p.dx.smem + 1024)));
     const int64_t resident = 256 * std::max<int64_t>(1, per_cu);
     const unsigned dgrid = (unsigned)(dtiles < resident ? dtiles : resident);
     const double* xd = static_cast<const double*>(x);
     const float* wp = pixel_rows;
     void* dargs[] = {(void*)&xd, (void*)&wp, (void*)&rows, (void*)&grad_x, (void*)&tc};
-    return launch_status("qconv_dx_kernel", hipLaunchKernel(dx.kern, dim3(dgrid), dim3(qiddm::kDxThreads), dargs, dx.smem, st));
+    return launch_status("qconv_dx_kernel", hipLaunchKernel(p.dx.kern, dim3(dgrid), dim3(qiddm::kDxThreads), dargs, p.dx.smem, st));
   }
   if (grad_x) return launch_status("qconv_fold_t_kernel", qiddm::launch_fold_t(grad_features_t, grad_x, batch, tc, st));
   return QIDDM_OK;
 }
-}  // namespace
 
 int qiddm_qconv_fold_features(const float* grad_features_t, int64_t batch, int64_t in_channels, int64_t height,
                               int64_t width, int64_t kh, int64_t kw, int64_t pad_h, int64_t pad_w, double* grad_x,
                               void* stream) {
-  if (batch < 1 || in_channels < 1 || height < 1 || width < 1 || kh < 1 || kw < 1 || pad_h < 0 || pad_w < 0)
-    return fail(QIDDM_ERR_INVALID, "bad convolution geometry");
-  const int64_t ho = height + 2 * pad_h - kh + 1, wo = width + 2 * pad_w - kw + 1;
-  if (ho < 1 || wo < 1) return fail(QIDDM_ERR_INVALID, "kernel larger than the padded image");
+  // (a fold knows neither wires nor output channels: the geometry fields of the descriptor are all it reads)
+  const qiddm_qconv_layer_t l{0, 0, batch, in_channels, height, width, kh, kw, pad_h, pad_w, 1};
+  const int rc = check_layer(&l);
+  if (rc != QIDDM_OK) return rc;
   if (!grad_features_t || !grad_x) return fail(QIDDM_ERR_INVALID, "grad_features_t/grad_x is NULL");
-  const int64_t total = batch * in_channels * height * width;
-  if (total >= ((int64_t)1 << 40)) return fail(QIDDM_ERR_INVALID, "image batch too large");
-  qiddm::TrainConv tc;
-  std::memset(&tc, 0, sizeof(tc));
-  tc.C = (int32_t)in_channels;
-  tc.H = (int32_t)height;
-  tc.W = (int32_t)width;
-  tc.kh = (int32_t)kh;
-  tc.kw = (int32_t)kw;
-  tc.ph = (int32_t)pad_h;
-  tc.pw = (int32_t)pad_w;
-  tc.Ho = (int32_t)ho;
-  tc.Wo = (int32_t)wo;
-  tc.F = (int32_t)(in_channels * kh * kw);
-  tc.M = batch * ho * wo;
-  return launch_status("qconv_fold_t_kernel",
-                       qiddm::launch_fold_t(grad_features_t, grad_x, batch, tc, static_cast<hipStream_t>(stream)));
+  if (batch * in_channels * height * width >= ((int64_t)1 << 40)) return fail(QIDDM_ERR_INVALID, "image batch too large");
+  return launch_status("qconv_fold_t_kernel", qiddm::launch_fold_t(grad_features_t, grad_x, batch, train_geometry(l),
+                                                                   static_cast<hipStream_t>(stream)));
 }
 
 int qiddm_qconv_train_rows(int32_t n_qubits, const double* u, int32_t u_transposed, int64_t features,

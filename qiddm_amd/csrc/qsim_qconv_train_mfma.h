@@ -55,7 +55,7 @@ __host__ __device__ inline size_t tm_lds_bytes_bn(int F) { return tm_coef_offset
 // BN: the layer is followed by a training-mode BatchNorm2d whose backward transform is applied to dL/dy here
 //     (TrainConv::bn_y / bn_coef; the convolution's own output rides in registers next to dL/dy, a tile ahead).  A
 //     template parameter, not a run-time test: the extra registers cost the CO = 32 variants their second wave per SIMD
-//     (spills), so those layers keep the separate BatchNorm pass (qiddm_qconv_train_bn_ok) and every other variant is
+//     (spills), so those layers keep the separate BatchNorm pass (the plan's bn_fold == 0) and every other variant is
 //     compiled without the code.
 template <int CO, int JBMAX, typename XT, int SK = 0, int SC = 0, bool BN = false>
 __global__ __launch_bounds__(kTmThreads, (JBMAX >= 8 ? 1 : 2)) void qconv_train_backward_mfma_kernel(const XT* __restrict__ x,

@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol(hip_lib):
 
 
 def test_introspection_calls_need_no_gpu(hip_lib):
-    assert hip_lib.qiddm_abi_version() == 1
+    assert hip_lib.qiddm_abi_version() == 2
     assert hip_lib.qiddm_max_qubits() == 16
     from qiddm_amd.circuit import Circuit
     # SURVEY section 8a gate counts

@@ -146,7 +146,7 @@ def test_fused_qconv_backward_vs_oracle_autograd(c_in, c_out, k, pad, hw, qdepth
     (40, 8, 1, 0, (6, 6)),       # 1 x 1, 40 features
 ])
 def test_thin_product_backward_float32_activations_and_generic_walk(c_in, c_out, k, pad, hw, monkeypatch):
-    """qiddm_qconv_train_backward_x32 (float32 copy of the activations) == qiddm_qconv_train_backward bit for bit:
+    """qiddm_qconv_train_backward with a float32 copy of the activations (x_is_f32) == with float64 x bit for bit:
     every patch element is converted to float32 before the products either way.  The last three shapes have no
     compiled-in variant and take the run-time walk of the gather; all of them against autograd through the oracle."""
     from qiddm_amd import nn, circuit
@@ -165,11 +165,9 @@ def test_thin_product_backward_float32_activations_and_generic_walk(c_in, c_out,
     gx64, gw64 = grads(False)
     gx32, gw32 = grads(True)
     assert torch.equal(gx64, gx32) and torch.equal(gw64, gw32)
-    # dL/dx from the per-pixel rows (qiddm_qconv_train_backward_dx: no feature-gradient matrix, the taps summed in float32
+    # dL/dx from the per-pixel rows (pixel_rows: no feature-gradient matrix, the taps summed in float32
     # on the matrix cores) against the fold route: same weight gradients bit for bit, dL/dx to float32 rounding
-    lib = circuit._capi.lib()
-    co = circuit._row_channels(c_out)
-    takes_dx = lib.qiddm_qconv_train_dx_elems(layer.wires, 3, c_in, hw[0], hw[1], k, k, pad, pad, c_out, co) > 0
+    takes_dx = circuit._qconv_train_plan(layer.wires, 3, c_in, hw[0], hw[1], k, k, pad, pad, c_out)[1].pixel_rows_elems > 0
     assert takes_dx == (c_in <= 32), "every same-size layer up to 32 input channels takes the per-pixel-row route"
     gxd, gwd = grads(False, dx=True)
     assert torch.equal(gwd, gw64)

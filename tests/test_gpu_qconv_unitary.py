@@ -248,3 +248,52 @@ def test_packed_operand_is_kept_per_layer_and_follows_weights_and_batchnorm(monk
         assert packs[n] is True and not torch.allclose(y3, y2)
         y4 = layer.eval_forward(x, batch_norm=bn)
         assert packs[-1] is False and torch.equal(y3, y4)
+
+
+@pytest.mark.parametrize("c_in,c_out,pad,matrix_core,pixel_rows", [
+    (1, 8, 1, False, False),        # 9 patch features: the VALU kernel, feature gradients + fold
+    (8, 16, 1, True, True),         # matrix-core kernel, same-size: per-pixel rows
+    (8, 16, 0, True, False),        # matrix-core kernel, 4 x 3 outputs: feature gradients + fold
+])
+def test_thin_product_backward_reads_a_strided_gradient_on_every_route(c_in, c_out, pad, matrix_core, pixel_rows):
+    """``grad_y_batch_stride`` of qiddm_qconv_train_backward through ctypes: dL/dy as channels [c0, c0 + c_out) of a
+    contiguous (3, 2 c_out + 1, Ho, Wo) tensor that is NaN everywhere else gives bit for bit the h partial sums and
+    dL/dx of the dense copy -- on the VALU kernel and on the matrix-core kernel with either way to dL/dx, each without
+    and with the BatchNorm coefficients (conv_y stays the dense tensor whatever the stride)."""
+    from qiddm_amd import _capi, nn
+    from qiddm_amd import circuit as qc
+    dev = torch.device(DEV)
+    b, h, w, k = 3, 6, 5, 3
+    ho, wo = h + 2 * pad - k + 1, w + 2 * pad - k + 1
+    n = nn.QConv2d(c_in, c_out, k, pad).wires
+    layer, plan = qc._qconv_train_plan(n, b, c_in, h, w, k, k, pad, pad, c_out)
+    assert (qc._QCONV_ROUTES[plan.route], bool(plan.matrix_core), plan.pixel_rows_elems > 0) == ("thin", matrix_core, pixel_rows)
+    f, co = c_in * k * k, plan.row_channels
+    torch.manual_seed(c_in + pad)
+    u = qc.circuit_unitary(torch.randn(2, n, 3, dtype=torch.float64, device=dev) * 0.8, n, "CNOT")
+    rt = qc._unitary_rows(u, n, f, c_out, co, dev)
+    x = torch.rand(b, c_in, h, w, dtype=torch.float64, device=dev)
+    c0 = c_out // 2 + 1
+    wide = torch.full((b, 2 * c_out + 1, ho, wo), float("nan"), dtype=torch.float64, device=dev)
+    wide[:, c0:c0 + c_out] = torch.randn(b, c_out, ho, wo, dtype=torch.float64, device=dev)
+    view = wide[:, c0:c0 + c_out]
+    assert not view.is_contiguous() and view.stride(0) == (2 * c_out + 1) * ho * wo and wide.isnan().sum() == b * (c_out + 1) * ho * wo
+
+    conv_y = torch.rand(b, c_out, ho, wo, dtype=torch.float64, device=dev)
+    coef = torch.randn(3, c_out, dtype=torch.float64, device=dev)
+    assert plan.bn_fold == 1
+
+    def run(gy, stride, bn):
+        hpart = torch.zeros(plan.n_partials, 2 * co, f + 1, dtype=torch.float32, device=dev)
+        gx = torch.zeros(b, c_in, h, w, dtype=torch.float64, device=dev)
+        wpix = torch.zeros(plan.pixel_rows_elems, dtype=torch.float32, device=dev) if pixel_rows else None
+        gft = None if pixel_rows else torch.zeros(f, b * ho * wo, dtype=torch.float32, device=dev)
+        _capi.launch("qiddm_qconv_train_backward", dev, layer, x, 0, gy, stride, conv_y if bn else None,
+                     coef if bn else None, rt, gft, wpix, hpart, gx)
+        return hpart, gx
+
+    for bn in (False, True):
+        hp_dense, gx_dense = run(view.contiguous(), 0, bn)
+        hp_view, gx_view = run(view, view.stride(0), bn)
+        assert hp_dense.isfinite().all() and gx_dense.isfinite().all() and hp_dense.abs().max() > 0 and gx_dense.abs().max() > 0
+        assert torch.equal(hp_view, hp_dense) and torch.equal(gx_view, gx_dense)

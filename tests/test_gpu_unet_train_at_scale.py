@@ -61,16 +61,15 @@ def test_unitary_route_qconv_training_past_the_caps_vs_oracle(c_in, c_out, k, pa
     Past 10^5 pixels some scaled probability lands within float32 rounding of the clamp at 1 (at 1004 images of the
     8 -> 16 layer one value of 3.1 M did: the two sides' gradients differ by 8.5 % of the largest dL/dx entry).  Within
     ``KINK`` of it the reference follows the kernel's clamp decision; everywhere else it is the exact function."""
-    from qiddm_amd import _capi, circuit, nn
+    from qiddm_amd import circuit, nn
     side_out = side + 2 * pad - k + 1
     batch = _smallest_batch(side_out)
     m = batch * side_out * side_out
-    f = c_in * k * k
-    parts = _capi.lib().qiddm_qconv_train_partials(batch, side_out, side_out, f)
-    assert 0 < parts < (m + 63) // 64, (parts, m)                  # thin-product grid capped: it grid-strides
-    assert m > PAST_EVERY_CAP
     torch.manual_seed(c_in * 100 + c_out)
     layer = nn.QConv2d(c_in, c_out, k, pad, 3).to(DEV).train()
+    parts = circuit._qconv_train_plan(layer.wires, batch, c_in, side, side, k, k, pad, pad, c_out)[1].n_partials
+    assert 0 < parts < (m + 63) // 64, (parts, m)                  # thin-product grid capped: it grid-strides
+    assert m > PAST_EVERY_CAP
     bn = torch.nn.BatchNorm2d(c_out, dtype=torch.double).to(DEV).train()
     _fill_bn(bn, c_in + c_out)
     assert circuit.qconv_unitary_route(layer.wires, c_in, (k, k), c_out) == "thin"
@@ -164,12 +163,12 @@ def test_unet_simple_training_step_vs_oracle():
     """``Diffusion(UNetUndirectedS(3, 8, 3))`` training step on 20 x tau 10 = 200 images of 28 x 28 (the 28 x 28
     layers and the n = 9 layer pass the thin-product cap): loss and every parameter's gradient against autograd
     through ``oracle.diffusion.training_loss`` over ``unet_simple_forward(training=True, unitary=True)``."""
-    from qiddm_amd import _capi, models, nn, noise
+    from qiddm_amd import circuit, models, nn, noise
     batch, tau = 20, 10
-    lib = _capi.lib()
-    for (c_in, side_out, f) in ((1, 28, 9), (16, 28, 144), (32, 14, 288)):
-        parts = lib.qiddm_qconv_train_partials(batch * tau, side_out, side_out, f)
-        assert parts < (batch * tau * side_out * side_out + 63) // 64, (c_in, parts)
+    for (c_in, c_out, side) in ((1, 8, 28), (16, 8, 28), (32, 16, 14)):       # 9, 144 and 288 patch features
+        n = nn.QConv2d(c_in, c_out, 3, 1).wires
+        parts = circuit._qconv_train_plan(n, batch * tau, c_in, side, side, 3, 3, 1, 1, c_out)[1].n_partials
+        assert 0 < parts < (batch * tau * side * side + 63) // 64, (c_in, parts)
     torch.manual_seed(41)
     net = nn.UNetUndirectedS(3, 8, 3)
     for mod in net.modules():
