@@ -10,7 +10,8 @@ runs here:
     unfold -> (+0.1) -> AmplitudeEmbedding(pad 0.5, normalize) ->
     StronglyEntanglingLayers(pi*tanh(W), CNOT) -> probs -> *D/2, clamp, [::2], [:C_out]
 
-one circuit per output pixel, one wavefront per circuit.
+one circuit per output pixel, one wavefront per circuit.  ``QConv2d._route`` is the one place that decides which of the
+five implementations a call takes; ``forward``, ``eval_forward`` and ``train_forward_bn`` dispatch on it.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ import torch
 
 from .. import circuit as _c
 from .. import qml
+from .derived import derived
 from .qdense import _qw_tanh
 from .utils import unfold_patches
 
@@ -47,6 +49,7 @@ class QConv2d(torch.nn.Module):
         self.sample_qnode = None
         self.sample_matrix = None
         self._own_qnode = self.qnode
+        self._packed_operand = {}
 
     def _circuit(self, features):
         qml.AmplitudeEmbedding(features=features.double(), wires=range(self.wires), pad_with=0.5,
@@ -58,39 +61,46 @@ class QConv2d(torch.nn.Module):
         p = torch.clamp(quantum_probs * quantum_probs.shape[-1] * 0.5, 0.0, 1.0)
         return p[:, ::2][:, : self.out_channels].double()
 
+    def _route(self, on_device: bool) -> str:
+        """Which of the five ways a call on a device / host input takes under the current grad mode, ``self.training``,
+        precision and the layer's shape: ``"unitary_eval"`` (the cached circuit unitary, then one GEMM on the matrix
+        cores; reference :92-126, up to C4's 12 wires), ``"circuit_inference"`` (unfold + embedding + circuit +
+        post-processing in one launch), ``"unitary_train"`` (training through the circuit unitary: GEMM forward,
+        thin-product backward, one adjoint sweep per output channel -- the circuit does not depend on the data),
+        ``"circuit_train"`` (the fused launch, differentiable: adjoint sweep per output pixel + fold) or ``"qnode"``."""
+        if self.qnode is not self._own_qnode or not on_device:
+            return "qnode"
+        f32 = _c._default_precision == "f32"      # the GEMMs multiply in float32; float64 keeps the float64 circuit kernels
+        fits = 2 * self.out_channels <= 2 ** self.wires
+        if not torch.is_grad_enabled() and fits:
+            if not self.training and f32 and self.wires <= 12:
+                return "unitary_eval"
+            if self.wires <= 10:
+                return "circuit_inference"
+        if f32 and _c.qconv_unitary_trainable(self.wires, self.in_channels, self.kernel_size, self.out_channels):
+            return "unitary_train"
+        return "circuit_train" if fits and self.wires <= 10 else "qnode"
+
+    def _train_angles(self):
+        # (the angle map runs on the weight-gradient stream: its backward, and the adjoint sweeps in front of it,
+        #  then overlap the rest of the network's backward -- circuit.on_weight_grad_stream)
+        return _c.on_weight_grad_stream(lambda w: _qw_tanh(w.double()), self.weights)
+
     def forward(self, x):
         b, c, h_in, w_in = x.shape
         assert c == self.in_channels, f"Expected {self.in_channels} channels, got {c}"
+        route = self._route(x.is_cuda)
+        shape = (self.wires, self.out_channels, self.kernel_size, self.padding)
+        if route == "unitary_eval":
+            return _c.qconv_unitary_forward(x, self._eval_unitary(), *shape, **self._packed_args())
+        if route == "circuit_inference":
+            return _c.qconv_forward(x, _qw_tanh(self.weights.detach().double()), *shape)
+        if route == "unitary_train":
+            return _c.qconv_unitary_execute(x.double(), self._train_angles(), *shape)
+        if route == "circuit_train":
+            return _c.qconv_execute(x.double(), _qw_tanh(self.weights.double()), *shape)
         h_out = h_in + 2 * self.padding[0] - self.kernel_size[0] + 1
         w_out = w_in + 2 * self.padding[1] - self.kernel_size[1] + 1
-        if (not torch.is_grad_enabled() and self.qnode is self._own_qnode and self.wires <= 12 and not self.training
-                and x.is_cuda and _c._default_precision == "f32" and 2 * self.out_channels <= 2 ** self.wires):
-            # eval mode (reference :92-126), up to C4's 12 wires: the cached circuit unitary, then one GEMM
-            return _c.qconv_unitary_forward(x, self._eval_unitary(), self.wires, self.out_channels,
-                                            self.kernel_size, self.padding, **self._packed_args())
-        if (not torch.is_grad_enabled() and self.qnode is self._own_qnode and self.wires <= 10
-                and 2 * self.out_channels <= 2 ** self.wires):
-            if not self.training and x.is_cuda and _c._default_precision == "f32":
-                # eval mode (reference :92-126): the cached circuit unitary, then one GEMM on the matrix cores
-                return _c.qconv_unitary_forward(x, self._eval_unitary(), self.wires, self.out_channels,
-                                                self.kernel_size, self.padding, **self._packed_args())
-            # inference: unfold + embedding + circuit + post-processing in one launch
-            return _c.qconv_forward(x, _qw_tanh(self.weights.detach().double()), self.wires,
-                                    self.out_channels, self.kernel_size, self.padding)
-        if (self.qnode is self._own_qnode and x.is_cuda and _c._default_precision == "f32"
-                and _c.qconv_unitary_trainable(self.wires, self.in_channels, self.kernel_size, self.out_channels)):
-            # training through the circuit unitary: GEMM forward, thin-product backward, one adjoint sweep per
-            # output channel (the circuit does not depend on the data)
-            # (the angle map runs on the weight-gradient stream: its backward, and the adjoint sweeps in front of it,
-            #  then overlap the rest of the network's backward -- circuit.on_weight_grad_stream)
-            angles = _c.on_weight_grad_stream(lambda w: _qw_tanh(w.double()), self.weights)
-            return _c.qconv_unitary_execute(x.double(), angles, self.wires, self.out_channels, self.kernel_size,
-                                            self.padding)
-        if (self.qnode is self._own_qnode and self.wires <= 10 and x.is_cuda
-                and 2 * self.out_channels <= 2 ** self.wires):
-            # training: the same fused launch, differentiable (adjoint sweep per output pixel + fold)
-            return _c.qconv_execute(x.double(), _qw_tanh(self.weights.double()), self.wires, self.out_channels,
-                                    self.kernel_size, self.padding)
         # self.unfold's columns, one row per output pixel (a strided view + one copy; nn/utils.unfold_patches)
         feats = unfold_patches(x.double(), self.kernel_size, self.padding) + 0.1
         y = self._post_process(self.qnode(feats))                        # ((b h w), C_out)
@@ -100,25 +110,20 @@ class QConv2d(torch.nn.Module):
         """``bn(self(x))`` as one autograd node when this layer trains through its circuit unitary and ``bn`` is a float64
         training-mode BatchNorm2d on the device (``circuit.qconv_bn_train``: the BatchNorm backward's transform pass is
         folded into the convolution's backward); None otherwise -- the caller then runs the two modules."""
-        if not (torch.is_grad_enabled() and self.qnode is self._own_qnode and x.is_cuda and x.dim() == 4
-                and x.numel() > 0 and x.shape[1] == self.in_channels and _c._default_precision == "f32"
-                and _c._QCONV_BN_FUSED
-                and _c.qconv_unitary_trainable(self.wires, self.in_channels, self.kernel_size, self.out_channels)
+        if not (torch.is_grad_enabled() and x.dim() == 4 and x.numel() > 0 and x.shape[1] == self.in_channels
+                and _c._QCONV_BN_FUSED and self._route(x.is_cuda) == "unitary_train"
                 and _c.batch_norm_eligible(bn, self.out_channels)
                 and _c.qconv_bn_foldable(tuple(x.shape), self.wires, self.out_channels, self.kernel_size, self.padding)):
             return None
-        angles = _c.on_weight_grad_stream(lambda w: _qw_tanh(w.double()), self.weights)
-        return _c.qconv_bn_train(x.double(), angles, bn, self.wires, self.out_channels, self.kernel_size, self.padding)
+        return _c.qconv_bn_train(x.double(), self._train_angles(), bn, self.wires, self.out_channels, self.kernel_size,
+                                 self.padding)
 
     def eval_forward(self, x, upsample2x=False, batch_norm=None):
         """Inference through the cached unitary + GEMM with the layer's ``unet_simple`` neighbours folded in
         (``upsample2x``: the bilinear x2 in front of an ``up_conv``; ``batch_norm``: the eval-mode BatchNorm2d behind
         a ``net`` convolution).  None when this layer or the call is outside that route."""
-        if torch.is_grad_enabled() or self.training or self.qnode is not self._own_qnode or not x.is_cuda \
-                or self.wires > 12 or 2 * self.out_channels > 2 ** self.wires or x.shape[1] != self.in_channels:
+        if self._route(x.is_cuda) != "unitary_eval" or x.shape[1] != self.in_channels:
             return None
-        if _c._default_precision != "f32":
-            return None      # the GEMM multiplies in float32; the float64 setting keeps the float64 circuit kernel
         if batch_norm is not None and (batch_norm.training or batch_norm.running_mean is None
                                        or batch_norm.num_features != self.out_channels):
             return None
@@ -126,20 +131,18 @@ class QConv2d(torch.nn.Module):
                                         self.padding, upsample2x=upsample2x, batch_norm=batch_norm, **self._packed_args())
 
     def _packed_args(self):
-        """The layer's own packed-operand cache for ``circuit.qconv_unitary_forward`` (valid while ``_sample_stamp``, the
-        stamp of the weights the cached unitary was built from, stands): call AFTER ``_eval_unitary()``."""
-        if not hasattr(self, "_packed_operand"):
-            self._packed_operand = {}
-        return {"packed": self._packed_operand, "packed_key": getattr(self, "_sample_stamp", None)}
+        """The layer's own packed-operand cache for ``circuit.qconv_unitary_forward``, keyed by the stamp of the weights
+        the cached unitary was built from: call AFTER ``_eval_unitary()``."""
+        return {"packed": self._packed_operand, "packed_key": self._derived["unitary"][0]}
 
     def _eval_unitary(self):
         """``sample_matrix`` of the reference (:96-103): the (D, D) complex128 matrix of
         ``StronglyEntanglingLayers(pi*tanh(weights))``, rebuilt when the weights changed since it was taken."""
-        stamp = (self.weights._version, self.weights.data_ptr(), self.weights.device)
-        if self.sample_matrix is None or getattr(self, "_sample_stamp", None) != stamp:
-            self.sample_matrix = _c.circuit_unitary(_qw_tanh(self.weights.detach().double()), self.wires, "CNOT")
-            self._sample_stamp = stamp
-        return self.sample_matrix
+        w = self.weights
+        u = derived(self, "unitary", (w,), (), lambda: _c.circuit_unitary(_qw_tanh(w.detach().double()), self.wires))
+        if u is not self.sample_matrix:
+            self.sample_matrix = u          # (nn.Module.__setattr__ is slow: only on a rebuild)
+        return u
 
     def train(self, mode=True):
         """Leaving eval mode drops the cached unitary, as the reference does (:123-125); entering it lets the
@@ -148,6 +151,7 @@ class QConv2d(torch.nn.Module):
         if mode:
             self.sample_qnode = None
             self.sample_matrix = None
+            self.__dict__.get("_derived", {}).pop("unitary", None)
         return self
 
     def __repr__(self):

@@ -16,6 +16,10 @@ deliberate (SURVEY.md "Findings"):
 
 There is no CPU execution path: ``forward`` raises unless the module lives on a
 HIP device and the in-tree extension is built.
+
+Routing: every family base states its circuit once (``_circuit_descriptor``); ``_QuantumNet._dense_family`` is the one
+answer to "is this the stock linear_down -> RZ/SEL(CZ) -> <Z> -> linear_up net" in front of the fused inference launch,
+``fused_sample_steps`` and ``fused_train_step``; tables built from the weights are kept by ``derived.derived``.
 """
 from __future__ import annotations
 
@@ -29,6 +33,7 @@ from .. import _capi
 from .. import circuit as _c
 from .. import pca as _pca
 from .. import qml
+from .derived import derived
 
 
 def _pair(shape):
@@ -71,76 +76,94 @@ class _QuantumNet(nn.Module):
         self.load_state_dict(checkpoint["model_state_dict"])
 
     _fusable_noise = (0,)   # add_noise settings that leave the circuit a pure-state no-op
+    _dense_angles = None    # set by the bases of the stock dense nets: the name of their angles parameter
+    _use_pca = False
+
+    def __init_subclass__(cls, **kwargs):
+        super().__init_subclass__(**kwargs)
+        if "_dense_angles" in vars(cls):
+            cls._dense_base = cls
+
+    def _fusable(self) -> bool:
+        """Own QNode and fusable noise: the fused launches compute what ``self.qnode`` would (grad on or off)."""
+        return self.qnode is self._own_qnode and getattr(self, "add_noise", 0) in self._fusable_noise
 
     def _fused_rounds_ok(self) -> bool:
-        return (not torch.is_grad_enabled()) and self.qnode is self._own_qnode and \
-            getattr(self, "add_noise", 0) in self._fusable_noise
+        """... and no autograd graph is wanted: the inference launches apply."""
+        return (not torch.is_grad_enabled()) and self._fusable()
 
-    def _sampler_tables(self, circ, angles):
-        """Per-layer tables of the fused sampler, rebuilt only when the weights (or the precision) changed."""
-        stamp = (angles._version, angles.data_ptr(), str(angles.device), _c._default_precision, circ.angles_shape)
-        cached = getattr(self, "_sampler_tables_cache", None)
-        if cached is None or cached[0] != stamp:
-            cached = (stamp, _c.dense_sample_tables(circ, angles.reshape(circ.angles_shape)))
-            self._sampler_tables_cache = cached
-        return cached[1]
+    def _dense_family(self):
+        """``(circuit, linear_down, angles parameter, linear_up)`` when this is the family's stock
+        linear_down -> angle-encoded circuit -> <Z> -> linear_up net, whatever the current settings; None otherwise.
+        The one gate in front of the fused inference launch, the fused sampler and the fused training step."""
+        if self._dense_angles is None:
+            return None
+        base, cls, mods = self._dense_base, type(self), self._modules      # (the dicts: no nn.Module.__getattr__ per call)
+        if self._use_pca or "linear_down" not in mods or cls._circuit is not base._circuit \
+                or cls.forward is not base.forward:
+            return None
+        return self._circuit_descriptor(), mods["linear_down"], self._parameters[self._dense_angles], mods["linear_up"]
 
     def _gate_table(self, circ, weights, angle_map=None):
-        """Gate table of ``circ`` for the current weights (``qiddm_prepare_gates``), rebuilt only when they (or the
-        precision) changed; ``angle_map`` is applied to the weights first (``qw_map.tanh`` / ``torch.tanh``)."""
-        stamp = (weights._version, weights.data_ptr(), str(weights.device), _c._default_precision, circ.angles_shape,
-                 circ.n_features)
-        cached = getattr(self, "_gate_table_cache", None)
-        if cached is None or cached[0] != stamp:
+        """``(angles, gate table)`` of ``circ`` for the current weights (``qiddm_prepare_gates``), rebuilt only when
+        they (or the precision) changed; ``angle_map`` (``qw_map.tanh`` / ``torch.tanh``) is applied to the weights first."""
+        def build():
             ang = weights.detach() if angle_map is None else angle_map(weights.detach())
             ang = ang.reshape(circ.angles_shape)
-            cached = (stamp, ang, _c.prepare_gates(circ, ang, _c._default_precision))
-            self._gate_table_cache = cached
-        return cached[1], cached[2]
+            return ang, _c.prepare_gates(circ, ang, _c._default_precision)
+        return derived(self, "gate_table", (weights,), (_c._default_precision, circ.angles_shape, circ.n_features), build)
 
-    def _lean_sampler_tables(self, circ, angles, lin_down, lin_up):
-        """Tables of the lean 8- / 6-qubit sampler, rebuilt only when the weights, the two linears or the
-        precision changed; None when that kernel does not apply (then the general sampler runs)."""
-        tensors = (angles, lin_down.weight, lin_down.bias, lin_up.weight, lin_up.bias)
-        stamp = tuple((t._version, t.data_ptr()) for t in tensors if t is not None) + \
-            (str(angles.device), _c._default_precision, circ.angles_shape)
-        cached = getattr(self, "_lean_tables_cache", None)
-        if cached is None or cached[0] != stamp:
-            if torch.cuda.is_current_stream_capturing():
-                return None                       # cannot validate inside a recording: not cached either
-            cached = (stamp, _c.dense_sample_lean_tables(circ, angles.reshape(circ.angles_shape), lin_down.weight,
-                                                         lin_down.bias, lin_up.weight, lin_up.bias))
-            self._lean_tables_cache = cached
-        return cached[1]
+    def _dense_inference(self, flat):
+        """linear_down + the circuit rounds + linear_up of the stock dense net in one launch, (b, features) in the
+        dtype of ``linear_up``; None outside inference or beyond 10 wires (the caller then runs the modules)."""
+        fam = self._dense_family() if self._fused_rounds_ok() else None
+        if fam is None or fam[0].n_qubits > 10:
+            return None
+        circ, lin_down, angles, lin_up = fam
+        out = _c.dense_forward(circ, flat, lin_down.weight, lin_down.bias, angles.reshape(circ.angles_shape),
+                               lin_up.weight, lin_up.bias)
+        return out if out.dtype == lin_up.weight.dtype else out.to(lin_up.weight.dtype)
 
-    def _fused_sampler_launch(self, circ, flat, angles, n_steps, goal, noise_factor):
-        """n_steps loop bodies in one launch: the lean 8- / 6-qubit kernel where it applies, else the general
-        four-wavefront sampler."""
-        ld, lu = self.linear_down, self.linear_up
-        post_mode = 0 if goal == "data" else 1
-        lean = self._lean_sampler_tables(circ, angles, ld, lu)
-        if lean is not None:
-            return _c.dense_sample_lean(circ, flat, ld.weight, ld.bias, lu.weight, lu.bias, n_steps, lean,
-                                        post_mode=post_mode, noise_factor=noise_factor)
-        return _c.dense_sample(circ, flat, ld.weight, ld.bias, angles.reshape(circ.angles_shape), lu.weight, lu.bias,
-                               n_steps, post_mode=post_mode, noise_factor=noise_factor,
-                               tables=self._sampler_tables(circ, angles))
+    def fused_sample_steps(self, x, n_steps, goal, noise_factor=1.0):
+        """n_steps bodies of Diffusion.sample in one launch -- the lean 8- / 6-qubit kernel where it applies, else the
+        general four-wavefront sampler; None when not applicable (the caller then samples step by step)."""
+        fam = self._dense_family() if self._fused_rounds_ok() else None
+        if fam is None:
+            return None
+        circ, ld, angles, lu = fam
+        b, c, w, h = x.shape
+        flat = x.reshape(b, -1).to(ld.weight.device)
+        if not 2 <= circ.n_qubits <= 10 or flat.shape[1] > 2048 or flat.shape[1] != lu.weight.shape[0]:
+            return None
+        lin = (ld.weight, ld.bias, lu.weight, lu.bias)
+        shape = circ.angles_shape
+        key = (_c._default_precision, shape)
+        kw = {"post_mode": 0 if goal == "data" else 1, "noise_factor": noise_factor}
+        try:
+            # (lean tables: None where that kernel does not apply; validated by a read-back, so never inside a recording)
+            lean = derived(self, "lean_tables", (angles,) + lin, key,
+                           lambda: _c.dense_sample_lean_tables(circ, angles.reshape(shape), *lin), capture="skip")
+            if lean is not None:
+                out = _c.dense_sample_lean(circ, flat, *lin, n_steps, lean, **kw)
+            else:
+                ang = angles.reshape(shape)
+                tables = derived(self, "sampler_tables", (angles,), key, lambda: _c.dense_sample_tables(circ, ang))
+                out = _c.dense_sample(circ, flat, ld.weight, ld.bias, ang, lu.weight, lu.bias, n_steps, tables=tables, **kw)
+        except _capi.QiddmError as e:
+            if e.code == -2:      # outside the fused sampler's range (e.g. tables beyond LDS): step by step
+                return None
+            raise
+        return (out if out.dtype == lu.weight.dtype else out.to(lu.weight.dtype)).view(n_steps, b, c, w, h)
 
     # -- fused training step (SURVEY.md section 8f rank 1) -------------------------------------------------
-    def _train_family(self):
-        """``(circuit, linear_down, angles parameter, linear_up)`` for nets of the
-        linear_down -> angle-encoded circuit -> <Z> -> linear_up shape; None otherwise."""
-        return None
-
     def fused_train_step(self, x, noise, schedule, goal, want_recon=False, want_elem_loss=False, rng_state=None):
         """What ``Diffusion.run_training_step_*`` does around this net -- noising, forward, MSE, backward --
         in three launches (``qiddm_train_step``).  Adds the gradients to ``.grad`` exactly where ``.backward()``
         would (with ``detach_quantum`` only ``linear_up`` receives one, finding F1) and returns the dict of
         ``circuit.train_step`` (``loss``, optional ``recon`` / ``elem_loss``); None when the net or its
         current settings are outside the fused step (the caller then runs the eager path)."""
-        fam = self._train_family()
-        if fam is None or self.qnode is not self._own_qnode or \
-                getattr(self, "add_noise", 0) not in self._fusable_noise:
+        fam = self._dense_family() if self._fusable() else None
+        if fam is None:
             return None
         circ, lin_down, angles, lin_up = fam
         if circ.n_qubits > 10 or not x.is_cuda or lin_up.weight.shape[0] != x.shape[1]:
@@ -193,6 +216,10 @@ class QDenseUndirected_old(_QuantumNet):
         qml.StronglyEntanglingLayers(weights=self._weight_map(self.weights), wires=range(self.wires))
         return qml.probs(wires=range(self.wires))
 
+    def _circuit_descriptor(self):
+        return _c.Circuit(n_qubits=self.wires, encoding="amplitude", imprimitive="CNOT", measure="probs",
+                          n_rounds=1, n_blocks=1, sel_layers=self.qdepth, n_features=self.pixels, pad_with=0.1)
+
     def _post_process(self, probs):
         return torch.clamp(probs[:, : self.pixels] * self.pixels, 0, 1)
 
@@ -200,16 +227,11 @@ class QDenseUndirected_old(_QuantumNet):
         """``[Re U^T | Im U^T]`` of the weight-only layers for the first ``pixels`` outcomes, float32, rebuilt when the
         weights changed (``circuit.dense_unitary_forward``).  ``build=False``: only what is cached for the current
         weights, else None."""
-        w = self.weights
-        stamp = (w._version, w.data_ptr(), str(w.device))
-        cached = getattr(self, "_unitary_operand_cache", None)
-        if cached is None or cached[0] != stamp:
-            if not build or torch.cuda.is_current_stream_capturing():
-                return None                   # (a recording computes nothing: warm the cache with one eager call first)
-            u = _c.circuit_unitary(self._weight_map(w.detach().double()), self.wires, "CNOT", precision="f64")
-            cached = (stamp, _c.dense_unitary_operand(u, self.pixels))
-            self._unitary_operand_cache = cached
-        return cached[1]
+        def operand():
+            u = _c.circuit_unitary(self._weight_map(self.weights.detach().double()), self.wires, "CNOT", precision="f64")
+            return _c.dense_unitary_operand(u, self.pixels)
+        # (a recording computes nothing: warm the cache with one eager call first)
+        return derived(self, "unitary_operand", (self.weights,), (), operand, capture="skip", build=build)
 
     def forward(self, x):
         b = x.shape[0]
@@ -218,8 +240,6 @@ class QDenseUndirected_old(_QuantumNet):
                 type(self)._circuit in (QDenseUndirected_old._circuit, QDenseUndirected_old_noise._circuit) and \
                 type(self)._post_process is QDenseUndirected_old._post_process:
             # inference: embedding, circuit and post-processing in one launch (no (B, 2^n) probability matrix)
-            circ = _c.Circuit(n_qubits=self.wires, encoding="amplitude", imprimitive="CNOT", measure="probs",
-                              n_rounds=1, n_blocks=1, sel_layers=self.qdepth, n_features=self.pixels, pad_with=0.1)
             # (building the unitary costs one 2^n-sample simulation: worth it from _UNITARY_ROUTE_MIN_BATCH samples on;
             #  once it is there for the current weights every batch size takes it)
             operand = self._unitary_operand(build=b >= _UNITARY_ROUTE_MIN_BATCH) \
@@ -228,11 +248,12 @@ class QDenseUndirected_old(_QuantumNet):
                 # the circuit does not depend on the data: one float32 product with the circuit unitary (cached per
                 # weights) instead of simulating every sample (C3's batch of 1024: 193 -> 45 us)
                 out = _c.dense_unitary_forward(flat, operand, self.wires, self.pixels, 0.1, float(self.pixels))
-                return out.reshape(b, 1, self.width, self.height)
-            angles, table = self._gate_table(circ, self.weights, self._weight_map)
-            out = _c.run_forward_post(circ, flat, angles, self.pixels, float(self.pixels), table=table)
-            return out.reshape(b, 1, self.width, self.height)
-        out = self._post_process(self.qnode(flat))
+            else:
+                circ = self._circuit_descriptor()
+                angles, table = self._gate_table(circ, self.weights, self._weight_map)
+                out = _c.run_forward_post(circ, flat, angles, self.pixels, float(self.pixels), table=table)
+        else:
+            out = self._post_process(self.qnode(flat))
         return out.reshape(b, 1, self.width, self.height)
 
     def __repr__(self):
@@ -334,6 +355,7 @@ class QNN_noise(_QuantumNet):
             torch.randn(weight_shape, dtype=torch.double, requires_grad=True).to(self.device) * 0.4)
         self._make_qnode("lightning.qubit", "parameter-shift")
 
+    _dense_angles = "weights"
     _noise_table = {1: (qml.PhaseDamping, 0.03), 2: (qml.AmplitudeDamping, 0.05),
                     3: (qml.DepolarizingChannel, 0.02)}
 
@@ -348,20 +370,11 @@ class QNN_noise(_QuantumNet):
         return _c.Circuit(n_qubits=self.hidden_features, encoding="rz", imprimitive="CZ", measure="expz",
                           n_rounds=1, n_blocks=1, sel_layers=self.qdepth)
 
-    def _train_family(self):
-        if type(self)._circuit is not QNN_noise._circuit:
-            return None
-        return self._circuit_descriptor(), self.linear_down, self.weights, self.linear_up
-
     def forward(self, x):
         b, c, w, h = x.shape
         flat = x.reshape(b, -1).to(self.linear_down.weight.device).to(torch.double)
-        if self._fused_rounds_ok() and self.hidden_features <= 10:
-            # inference: linear_down + circuit + linear_up in one launch
-            circ = self._circuit_descriptor()
-            out = _c.dense_forward(circ, flat, self.linear_down.weight, self.linear_down.bias,
-                                   self.weights.reshape(circ.angles_shape), self.linear_up.weight,
-                                   self.linear_up.bias)
+        out = self._dense_inference(flat)       # inference: linear_down + circuit + linear_up in one launch
+        if out is not None:
             return out.view(b, c, w, h)
         reduced = self.linear_down(flat)
         ev = self.qnode(reduced, self.weights)
@@ -369,23 +382,6 @@ class QNN_noise(_QuantumNet):
             ev = ev.detach()          # torch.tensor(qnode(...)) at reference :279 (finding F1)
         ev = ev.to(torch.double)
         return self.linear_up(ev).view(b, c, w, h)
-
-    def fused_sample_steps(self, x, n_steps, goal, noise_factor=1.0):
-        """n_steps bodies of Diffusion.sample in one launch; None when not applicable."""
-        if not (self._fused_rounds_ok() and 2 <= self.hidden_features <= 10):
-            return None
-        b, c, w, h = x.shape
-        circ = self._circuit_descriptor()
-        flat = x.reshape(b, -1).to(self.linear_down.weight.device).to(torch.double)
-        if flat.shape[1] > 2048 or flat.shape[1] != self.linear_up.weight.shape[0]:
-            return None
-        try:
-            out = self._fused_sampler_launch(circ, flat, self.weights, n_steps, goal, noise_factor)
-        except _capi.QiddmError as e:
-            if e.code == -2:      # outside the fused sampler's range (e.g. tables beyond LDS): step by step
-                return None
-            raise
-        return out.view(n_steps, b, c, w, h)
 
     def __repr__(self):
         return f"QNN(qdepth={self.qdepth}, features={self.hidden_features}, add_noise={self.add_noise})"
@@ -442,6 +438,10 @@ class differN_noise(_QuantumNet):
                                        3: (qml.DepolarizingChannel, 0.02)})
         return qml.probs(wires=range(self.wires))
 
+    def _circuit_descriptor(self):
+        return _c.Circuit(n_qubits=self.wires, encoding="rz", imprimitive="CZ", measure="probs",
+                          n_rounds=self.N, n_blocks=self.spectrum_layer, sel_layers=2)
+
     def _post_process(self, probs):
         return torch.clamp(probs[:, : self.pixels] * self.pixels, 0, 1)
 
@@ -454,8 +454,7 @@ class differN_noise(_QuantumNet):
     def forward_from_reduced(self, red):
         """Everything after the PCA (:464-472): the part that is parity-tested."""
         if self._fused_rounds_ok():
-            circ = _c.Circuit(n_qubits=self.wires, encoding="rz", imprimitive="CZ", measure="probs",
-                              n_rounds=self.N, n_blocks=self.spectrum_layer, sel_layers=2)
+            circ = self._circuit_descriptor()
             if self.wires <= 10 and type(self)._post_process is differN_noise._post_process:
                 # inference: all rounds AND the post-processing in one launch (the (B, 2^n) probabilities are never written)
                 ang, table = self._gate_table(circ, self.weights)
@@ -520,7 +519,7 @@ class differN_old_pca(differN_noise):
 # A2: [PCA | linear_down] -> N x [L x (RZ + SEL(CZ, 2 layers))] -> <Z> -> linear_up
 # ===========================================================================
 class _QIDDMBase(_QuantumNet):
-    _use_pca = False
+    _dense_angles = "weights1"
     _noise_table = {1: (qml.PhaseDamping, 0.03), 2: (qml.AmplitudeDamping, 0.05),
                     3: (qml.DepolarizingChannel, 0.9)}
 
@@ -550,6 +549,10 @@ class _QIDDMBase(_QuantumNet):
                                          imprimitive=qml.ops.CZ)
         return [qml.expval(qml.PauliZ(i)) for i in range(self.hidden_features)]
 
+    def _circuit_descriptor(self):
+        return _c.Circuit(n_qubits=self.hidden_features, encoding="rz", imprimitive="CZ", measure="expz",
+                          n_rounds=self.N, n_blocks=self.spectrum_layer, sel_layers=2)
+
     def reduce(self, flat):
         if self._use_pca:
             red = _pca.fit_transform(self.pca, flat)              # re-fit per call (F4)
@@ -559,52 +562,19 @@ class _QIDDMBase(_QuantumNet):
     def quantum_rounds(self, red):
         """The N chained QNode rounds (reference :1437-1441 / :1631-1635), one wavefront per
         sample instead of the per-sample Python loop."""
-        if self._fused_rounds_ok():
-            circ = _c.Circuit(n_qubits=self.hidden_features, encoding="rz", imprimitive="CZ",
-                              measure="expz", n_rounds=self.N, n_blocks=self.spectrum_layer, sel_layers=2)
-            return _c.execute(circ, red, self.weights1).to(torch.float64)
+        if self._fused_rounds_ok() and type(self)._circuit is _QIDDMBase._circuit:   # (the launch is this circuit's)
+            return _c.execute(self._circuit_descriptor(), red, self.weights1).to(torch.float64)
         x = red
         for n in range(self.N):
             x = self.qnode(x, self.weights1[n])
             x = (x.detach() if self.detach_quantum else x).to(torch.float64)   # finding F1
         return x
 
-    def _train_family(self):
-        if self._use_pca or not hasattr(self, "linear_down") or type(self)._circuit is not _QIDDMBase._circuit \
-                or type(self).forward is not _QIDDMBase.forward:
-            return None
-        circ = _c.Circuit(n_qubits=self.hidden_features, encoding="rz", imprimitive="CZ", measure="expz",
-                          n_rounds=self.N, n_blocks=self.spectrum_layer, sel_layers=2)
-        return circ, self.linear_down, self.weights1, self.linear_up
-
-    def fused_sample_steps(self, x, n_steps, goal, noise_factor=1.0):
-        """n_steps bodies of Diffusion.sample in one launch; None when not applicable."""
-        if not (self._fused_rounds_ok() and not self._use_pca and hasattr(self, "linear_down")
-                and 2 <= self.hidden_features <= 10 and type(self)._circuit is _QIDDMBase._circuit):
-            return None
-        b, c, w, h = x.shape
-        flat = x.reshape(b, -1)
-        if flat.shape[1] > 2048 or flat.shape[1] != self.linear_up.weight.shape[0]:
-            return None
-        circ = _c.Circuit(n_qubits=self.hidden_features, encoding="rz", imprimitive="CZ", measure="expz",
-                          n_rounds=self.N, n_blocks=self.spectrum_layer, sel_layers=2)
-        try:
-            out = self._fused_sampler_launch(circ, flat, self.weights1, n_steps, goal, noise_factor)
-        except _capi.QiddmError as e:
-            if e.code == -2:      # outside the fused sampler's range: step by step
-                return None
-            raise
-        return out.to(self.linear_up.weight.dtype).view(n_steps, b, c, w, h)
-
     def forward(self, x):
         b, c, w, h = x.shape
-        if self._fused_rounds_ok() and not self._use_pca and self.hidden_features <= 10:
-            # inference: linear_down + N chained rounds + linear_up in one launch
-            circ = _c.Circuit(n_qubits=self.hidden_features, encoding="rz", imprimitive="CZ",
-                              measure="expz", n_rounds=self.N, n_blocks=self.spectrum_layer, sel_layers=2)
-            out = _c.dense_forward(circ, x.reshape(b, -1), self.linear_down.weight, self.linear_down.bias,
-                                   self.weights1, self.linear_up.weight, self.linear_up.bias)
-            return out.to(self.linear_up.weight.dtype).view(b, c, w, h)
+        out = self._dense_inference(x.reshape(b, -1))   # inference: linear_down + N rounds + linear_up in one launch
+        if out is not None:
+            return out.view(b, c, w, h)
         red = self.reduce(x.reshape(b, -1))
         ev = self.quantum_rounds(red)
         ev = ev.to(self.linear_up.weight.device).to(self.linear_up.weight.dtype)

@@ -41,9 +41,6 @@ class QIDDM_PL_noise1(_QIDDMBase):
         _sel_cz_expz(self, inputs, weights1, enc=qml.RY)
         return [qml.expval(qml.PauliZ(i)) for i in range(self.hidden_features)]
 
-    def _fused_rounds_ok(self) -> bool:
-        return False        # the fused multi-round launch is specialised on the RZ encoding
-
     def __repr__(self):
         return (f"QIDDM_PL_noise(qlayer={self.spectrum_layer}, features={self.hidden_features}, "
                 f"N={self.N}, add_noise={self.add_noise})")
@@ -280,9 +277,6 @@ class differN_new_pca(differN_noise):
     def __init__(self, shape, spectrum_layer, N) -> None:
         super().__init__(shape, spectrum_layer, N, add_noise=0)
 
-    def _fused_rounds_ok(self) -> bool:
-        return False
-
     def forward_from_reduced(self, red):
         x = red
         for n in range(self.N):
@@ -323,7 +317,6 @@ class differN_old_conv(differN_noise, _ConvFront):
 class differN_new_conv(differN_old_conv):
     """Reference nn/qdense.py:838-936: conv front-end + the per-round post-processing of differN_new_pca."""
 
-    _fused_rounds_ok = differN_new_pca._fused_rounds_ok
     forward_from_reduced = differN_new_pca.forward_from_reduced
 
     def __repr__(self):
@@ -347,9 +340,6 @@ class QIDDM_A_sameN(differN_noise):
 
     def reduce(self, x):
         return x.reshape(x.shape[0], self.pixels)
-
-    def _fused_rounds_ok(self) -> bool:
-        return False
 
     def forward_from_reduced(self, red):
         p = red

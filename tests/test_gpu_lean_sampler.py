@@ -164,7 +164,7 @@ def test_nets_route_goal_data_through_the_lean_kernel_and_track_weight_updates(c
 
     with torch.no_grad():
         got = diff.denoise_steps(x, 3)
-        assert getattr(net, "_lean_tables_cache", (None, None))[1] is not None
+        assert getattr(net, "_derived", {}).get("lean_tables", (None, None))[1] is not None
         assert torch.allclose(got.cpu(), oracle(), atol=1e-4)
         net.linear_down.weight.mul_(1.5)                       # changes the composite map only
         net.linear_up.bias.add_(0.25)
