@@ -586,22 +586,41 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *                             operands get no gradient).  PennyLane's BitFlip, PhaseFlip, PauliError,
  *                             GeneralizedAmplitudeDamping, ResetError, ThermalRelaxationError and QubitChannel on one
  *                             wire are this op.
- * Kinds 10..15 and kinds above 16 are no ops: refused as `op %d: unknown kind %d` (16 leaves the next native kinds room).
+ *   QIDDM_MIX_CHANNEL2 (= 32) a general two-wire channel on w1 = `wire` and w2 = `reserved` -- the only kind that reads
+ *                             the struct's fourth field; w1 > w2 is allowed, w1 == w2 is not.  `a` is the first of 64
+ *                             consecutive rows of `gates` holding the superoperator S (16 x 16 complex, row-major): row t
+ *                             of S is gate rows a+4t .. a+4t+3, four (re, im) pairs a gate row.  With the other 2n-4
+ *                             index bits of rho fixed, the remaining 16 elements are a 4 x 4 block M[r][c],
+ *                             r = 2 (row bit of w1) + (row bit of w2), c likewise from the column bits; the op is
+ *                             vec(M') = S vec(M), vec(M)[4r + c] = M[r][c], on every block.  For Kraus operators K_k
+ *                             (4 x 4, index 2 b1 + b2, the first wire most significant: PennyLane's convention)
+ *                             S = sum_k K_k (x) conj(K_k), i.e. S[4r+c][4r'+c'] = sum_k K_k[r][r'] conj(K_k[c][c']).
+ *                             `p` and `scale` are not read; `gates` is not looked into (complete positivity and trace
+ *                             preservation are the caller's responsibility, and a channel that happens to be diagonal is
+ *                             still planned as a general one).  The planner gives it CNOT's wire set {w1, w2} and treats
+ *                             it as a channel that is not diagonal; every workspace size counts it as one channel.  In the
+ *                             reverse sweeps the adjoint takes S^H per block (out[c] = sum_r conj(S[r][c]) v[r]) and the
+ *                             op's 64 rows of grad_gates are zeros for every sample.  PennyLane's QubitChannel with 4 x 4
+ *                             operators and PauliError with a two-letter word are this op.  The rule for kinds is
+ *                             "general k-wire channel = 16 k".
+ * Kinds 10..15, 17..31 and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
  * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
  * batch / n_ops, measure (batch == 0 then returns QIDDM_OK with no pointer looked at), program (not empty, starts with a
- * state preparation), negative n_rows / n_gates, angle_rows / rows_ld, gates, the ops one by one (kind, wire, target wire,
+ * state preparation), negative n_rows / n_gates, angle_rows / rows_ld, gates, the ops one by one (kind, wire, target wire
+ * or second wire -- `op %d: bad second wire %d` when it is outside 0..n-1 or equal to `wire` --,
  * then the operand they index: features / feat_ld / n_features, angle row, gate, probability, channel rows), max_blocks (negative:
  * refused for an empty batch as well), the outputs
  * (out, out_ld | grad_out / gout_ld, grad_rows, grad_gates, grad_features), workspace.                   */
 enum {
   QIDDM_MIX_ZERO = 0, QIDDM_MIX_AMP_EMBED, QIDDM_MIX_PHASE, QIDDM_MIX_RY, QIDDM_MIX_GATE, QIDDM_MIX_CZ,
   QIDDM_MIX_CNOT, QIDDM_MIX_PHASE_DAMP, QIDDM_MIX_AMP_DAMP, QIDDM_MIX_DEPOL,
-  QIDDM_MIX_CHANNEL = 16
+  QIDDM_MIX_CHANNEL = 16,
+  QIDDM_MIX_CHANNEL2 = 32
 };
 typedef struct qiddm_mixed_op {
-  int32_t kind, wire, a, reserved;
+  int32_t kind, wire, a, reserved; /* reserved: the second wire of QIDDM_MIX_CHANNEL2; no other kind reads it */
   double p, scale;
 } qiddm_mixed_op_t;
 int64_t qiddm_mixed_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, int32_t n_ops);
@@ -636,7 +655,7 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
  * slab of `workspace`; the program is cut into SEGMENTS, each run by one sweep -- one launch over (tile, sample) in which
  * a workgroup holds the 2^12 elements spanned by the index-bit pairs of six wires in LDS and applies the whole segment.
  * A segment takes PHASE / CZ / PHASE_DAMP on any wires (diagonal on vec(rho)), GATE / RY / AMP_DAMP / DEPOL / CHANNEL on its six
- * wires, CNOT between two of them, and ZERO / AMP_EMBED as its first op.  Ops keep program order except where they
+ * wires, CNOT and CHANNEL2 between two of them, and ZERO / AMP_EMBED as its first op.  Ops keep program order except where they
  * commute (no shared wire, or both diagonal).  Same arguments and results as qiddm_mixed_forward; float64 read-out with
  * fixed-order sums, no atomics: reruns are bit-identical.
  *   qiddm_mixed_wide_plan             host only (no device is touched): the number of sweeps, the number of ops that are

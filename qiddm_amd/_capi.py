@@ -71,10 +71,11 @@ class TrainArgs(ctypes.Structure):
 
 MIX_ZERO, MIX_AMP_EMBED, MIX_PHASE, MIX_RY, MIX_GATE, MIX_CZ, MIX_CNOT, MIX_PHASE_DAMP, MIX_AMP_DAMP, MIX_DEPOL = range(10)
 MIX_CHANNEL = 16  # general one-wire channel: `a` = first of four gate rows holding the superoperator
+MIX_CHANNEL2 = 32  # general two-wire channel: `a` = first of 64 gate rows (16 x 16), `reserved` = the second wire
 
 
 class MixedOp(ctypes.Structure):
-    """``qiddm_mixed_op_t``."""
+    """``qiddm_mixed_op_t``.  ``reserved`` is 0 except for ``MIX_CHANNEL2``, which reads its second wire there."""
 
     _fields_ = [("kind", ctypes.c_int32), ("wire", ctypes.c_int32), ("a", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("p", ctypes.c_double), ("scale", ctypes.c_double)]

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <type_traits>
 #include <utility>
@@ -29,7 +30,9 @@ using qiddm_capi::launch;
 using qiddm_capi::launched;
 
 static_assert(sizeof(qiddm::MixedOp) == sizeof(qiddm_mixed_op_t), "program layout");
-static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixChannel == (int)QIDDM_MIX_CHANNEL, "op kinds");
+static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixChannel == (int)QIDDM_MIX_CHANNEL &&
+                  (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2, "op kinds");
+static_assert(offsetof(qiddm::MixedOp, wire2) == offsetof(qiddm_mixed_op_t, reserved), "the second wire travels in `reserved`");
 
 inline int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
 inline int64_t slab_bytes(int32_t n, int32_t dtype) { return ((int64_t)1 << (2 * n)) * (dtype == QIDDM_F32 ? 8 : 16); }
@@ -39,17 +42,22 @@ inline bool is_prep(int kind) { return kind == qiddm::kMixZero || kind == qiddm:
 inline bool is_diag(int kind) {
   return kind == qiddm::kMixPhase || kind == qiddm::kMixCZ || kind == qiddm::kMixPhaseDamp;
 }
-// the kernels' GENERAL instantiations carry the general channel's case; a program (segment) without one runs the lean ones
+// the kernels have an instantiation per qiddm::MixedLevel (which general-channel cases they carry); a program (segment)
+// runs the lowest one that holds its ops: calls f(std::integral_constant<int, level>{})
 template <typename F>
-int for_general(bool general, F&& f) {
-  return general ? f(std::true_type{}) : f(std::false_type{});
+int for_level(int level, F&& f) {
+  return level >= qiddm::kLevelChannel2 ? f(std::integral_constant<int, qiddm::kLevelChannel2>{})
+         : level == qiddm::kLevelChannel ? f(std::integral_constant<int, qiddm::kLevelChannel>{})
+                                          : f(std::integral_constant<int, qiddm::kLevelLean>{});
 }
-inline bool has_general_channel(const qiddm_mixed_op_t* program, int32_t n_ops) {
-  return std::any_of(program, program + n_ops, [](const qiddm_mixed_op_t& op) { return op.kind == qiddm::kMixChannel; });
+inline int program_level(const qiddm_mixed_op_t* program, int32_t n_ops) {
+  int level = qiddm::kLevelLean;
+  for (int i = 0; i < n_ops; ++i) level = std::max(level, qiddm::mixed_level_of(program[i].kind));
+  return level;
 }
 inline bool is_channel(int kind) {
   return kind == qiddm::kMixPhaseDamp || kind == qiddm::kMixAmpDamp || kind == qiddm::kMixDepol ||
-         kind == qiddm::kMixChannel;
+         kind == qiddm::kMixChannel || kind == qiddm::kMixChannel2;
 }
 
 // ---- argument checks ---------------------------------------------------------------------------------------------------
@@ -86,14 +94,18 @@ int check_program_start(const qiddm_mixed_op_t* program, int32_t n_ops) {
   return QIDDM_OK;
 }
 
-// kind, wire and target wire of op i: all the planner reads of an op, and the first thing the validator checks of it
+// kind, wire and target / second wire of op i: all the planner reads of an op, and the first thing the validator checks
+// of it
 int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i) {
-  if ((op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) && op.kind != qiddm::kMixChannel)
+  if ((op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) && op.kind != qiddm::kMixChannel &&
+      op.kind != qiddm::kMixChannel2)
     return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
   if (is_prep(op.kind)) return QIDDM_OK;
   if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
   if ((op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) && (op.a < 0 || op.a >= n || op.a == op.wire))
     return fail(QIDDM_ERR_INVALID, "op %d: bad target wire %d", i, op.a);
+  if (op.kind == qiddm::kMixChannel2 && (op.reserved < 0 || op.reserved >= n || op.reserved == op.wire))
+    return fail(QIDDM_ERR_INVALID, "op %d: bad second wire %d", i, op.reserved);  // n_qubits = 1 cannot hold the op
   return QIDDM_OK;
 }
 
@@ -156,6 +168,10 @@ int check_call(const MixedCall& c, const Engine& e, bool* embeds) {
       case qiddm::kMixChannel:  // four rows of gates; what they hold is device memory, out of the library's sight
         if (op.a < 0 || (int64_t)op.a + 3 >= c.n_gates)
           return fail(QIDDM_ERR_INVALID, "op %d: channel rows %d..%d out of range", i, op.a, (int)((int64_t)op.a + 3));
+        break;
+      case qiddm::kMixChannel2:  // 64 rows: the 16 x 16 superoperator
+        if (op.a < 0 || (int64_t)op.a + 63 >= c.n_gates)
+          return fail(QIDDM_ERR_INVALID, "op %d: channel rows %d..%d out of range", i, op.a, (int)((int64_t)op.a + 63));
         break;
       default:
         break;
@@ -290,7 +306,7 @@ struct WidePlan {
   std::vector<int32_t> op_segment;  // segment of every op
   std::vector<qiddm::WideSegment> segments;
   std::vector<char> seg_channel;    // split_channels: the segment holds channels only
-  std::vector<char> seg_general;    // the segment holds a general channel (QIDDM_MIX_CHANNEL)
+  std::vector<char> seg_level;      // the qiddm::MixedLevel the segment's ops need
   int32_t n_nondiag = 0;
 };
 
@@ -315,6 +331,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
     if ((rc = check_op_wires(n, op, i)) != QIDDM_OK) return rc;
     wires[i] = is_prep(op.kind) ? all : 1u << op.wire;
     if (op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) wires[i] |= 1u << op.a;
+    if (op.kind == qiddm::kMixChannel2) wires[i] |= 1u << op.reserved;  // both wires in the tile, as for CNOT
     plan->n_nondiag += is_diag(op.kind) ? 0 : 1;
   }
   plan->order.clear();
@@ -322,7 +339,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
   plan->op_segment.assign(n_ops, -1);
   plan->segments.clear();
   plan->seg_channel.clear();
-  plan->seg_general.clear();
+  plan->seg_level.clear();
   std::vector<char> placed(n_ops, 0);
   int first = 0;
   while (first < n_ops) {
@@ -331,7 +348,8 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
     uint32_t blocked_nondiag = 0, blocked_any = 0;  // wires with an earlier unplaced (non-diagonal / any) op
     qiddm::WideSegment sg{};
     sg.op_begin = (int32_t)plan->order.size();
-    bool empty = true, channels = false, general = false;
+    bool empty = true, channels = false;
+    int level = qiddm::kLevelLean;
     for (int i = first; i < n_ops && blocked_nondiag != all; ++i) {
       if (placed[i]) continue;
       const int kind = program[i].kind;
@@ -349,7 +367,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
       if (split_channels && !empty && is_channel(kind) != channels) ok = false;
       if (ok) {
         if (empty) channels = is_channel(kind);
-        general |= kind == qiddm::kMixChannel;
+        level = std::max(level, qiddm::mixed_level_of(kind));
         placed[i] = 1;
         plan->order.push_back(i);
         plan->op_segment[i] = (int32_t)plan->segments.size();
@@ -382,7 +400,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
       return fail(QIDDM_ERR_INVALID, "planner built a malformed tile (%d local, %d tile bits)", nl, ng);
     plan->segments.push_back(sg);
     plan->seg_channel.push_back(channels ? 1 : 0);
-    plan->seg_general.push_back(general ? 1 : 0);
+    plan->seg_level.push_back((char)level);
   }
   return QIDDM_OK;
 }
@@ -399,8 +417,8 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
     const unsigned chunk = (unsigned)(m.batch - s0 < resident ? m.batch - s0 : resident);
     if (embeds) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, c.features, norms, m, s0);
     for (size_t s = 0; s < plan.segments.size(); ++s) {   // (the sweeps ask for the LDS they use, no more)
-      const int rc = for_general(plan.seg_general[s] != 0, [&](auto general) {
-        return launch<qiddm::mixed_wide_sweep<T, decltype(general)::value>>(
+      const int rc = for_level(plan.seg_level[s], [&](auto level) {
+        return launch<qiddm::mixed_wide_sweep<T, decltype(level)::value>>(
             smem, dim3(tiles, chunk), dim3(256), smem, st, "mixed_wide_sweep", prog, c.angle_rows, c.features, c.gates, norms,
             slabs, m, plan.segments[s], s0, (int64_t)0);
       });
@@ -525,8 +543,8 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
     int cur = 0;
     for (int s = 0; s < bp.replay_end; ++s) {
       const bool ch = bp.plan.seg_channel[s] != 0;
-      rc = for_general(bp.plan.seg_general[s] != 0, [&](auto general) {
-        return launch<qiddm::mixed_wide_sweep<T, decltype(general)::value>>(
+      rc = for_level(bp.plan.seg_level[s], [&](auto level) {
+        return launch<qiddm::mixed_wide_sweep<T, decltype(level)::value>>(
             tile_bytes, dim3(tiles, chunk), block, tile_bytes, st, "mixed_wide_sweep", prog, c.angle_rows, c.features, c.gates,
             norms, slabs + (size_t)cur * set_stride, m, bp.plan.segments[s], s0, (int64_t)(ch ? set_stride : 0));
       });
@@ -542,8 +560,8 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
                                                         slabs + (size_t)cur * set_stride, lam, partials, m,
                                                         bp.plan.segments[s], bs, s0);
       } else {
-        rc = for_general(bp.plan.seg_general[s] != 0, [&](auto general) {
-          return launch<qiddm::mixed_wide_adjoint_channels<T, decltype(general)::value>>(
+        rc = for_level(bp.plan.seg_level[s], [&](auto level) {
+          return launch<qiddm::mixed_wide_adjoint_channels<T, decltype(level)::value>>(
               tile_bytes, dim3(tiles, chunk), block, tile_bytes, st, "mixed_wide_adjoint_channels", prog, c.gates, grad_out,
               lam, m, bp.plan.segments[s], bs, s0);
         });
@@ -594,10 +612,11 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
   const qiddm::MixedScalars m = make_scalars(c, n_ops, n_features, out_ld, g.in_lds);
   const size_t smem = g.in_lds ? (size_t)g.slab_bytes : 0;
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
+  const int level = program_level(program, n_ops);
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    return for_general(has_general_channel(program, n_ops), [&](auto general) {
-      return launch<qiddm::mixed_kernel<T, decltype(general)::value>>(
+    return for_level(level, [&](auto lv) {
+      return launch<qiddm::mixed_kernel<T, decltype(lv)::value>>(
           kMaxLds - 4096 /* the kernel also has 2 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
           "mixed_kernel", prog, angle_rows, features, gates, out, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m);
     });
@@ -643,10 +662,11 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   b.n_snaps = n_snaps;
   const size_t smem = g.in_lds ? 2 * (size_t)g.slab_bytes : 0;
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
+  const int level = program_level(program, n_ops);
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    return for_general(has_general_channel(program, n_ops), [&](auto general) {
-      return launch<qiddm::mixed_backward_kernel<T, decltype(general)::value>>(
+    return for_level(level, [&](auto lv) {
+      return launch<qiddm::mixed_backward_kernel<T, decltype(lv)::value>>(
           kMaxLds - 8192 /* the kernel also has 4.5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
           "mixed_backward_kernel", prog, angle_rows, features, gates, grad_out, grad_rows, grad_gates,
           embeds ? grad_features : nullptr, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m, b);

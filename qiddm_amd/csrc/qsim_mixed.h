@@ -16,7 +16,11 @@
 //     Depolarizing(p):      M00, M11 <- (1-2p/3) own + (2p/3) other;  M01, M10 *= 1-4p/3
 //     general channel S:    vec(M) <- S vec(M), vec(M) = (M00, M01, M10, M11), S = sum_k K_k (x) conj(K_k) (4 x 4 complex)
 // (the Kraus sums of PennyLane's channel definitions, written out; the general one carries BitFlip, PhaseFlip,
-// PauliError, GeneralizedAmplitudeDamping, ResetError, ThermalRelaxationError and QubitChannel).  Diagonal gates multiply by u_i conj(u_j); CZ by
+// PauliError, GeneralizedAmplitudeDamping, ResetError, ThermalRelaxationError and QubitChannel).  The general TWO-wire
+// channel works on the 4 x 4 blocks M[r][c] of its wires (r = 2 b_w1 + b_w2 from the row bits, c from the column bits):
+// vec(M) <- S vec(M), vec(M)[4r + c] = M[r][c], S 16 x 16 complex (mixed_block_super2 below; two-qubit depolarizing
+// behind an entangler, correlated dephasing, a two-letter PauliError, a measured two-qubit process).
+// Diagonal gates multiply by u_i conj(u_j); CZ by
 // sign(i) sign(j); CNOT permutes rows and columns (an involution: swapped in place).  Read-out: the diagonal.
 // mixed_backward_kernel (below) differentiates the same programs: PennyLane trains QNodes on default.mixed with
 // backprop or parameter-shift.  n <= 8.
@@ -37,12 +41,24 @@ enum MixedKind : int32_t {
   kMixAmpDamp,      // p = gamma
   kMixDepol,        // p
   kMixChannel = 16, // general one-wire channel: gates[a .. a+3] are the rows of the 4 x 4 superoperator S (10..15: no kind)
+  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..31: no kind)
 };
 
 struct MixedOp {
-  int32_t kind, wire, a, pad_;
+  int32_t kind, wire, a, wire2;  // wire2: qiddm_mixed_op_t's `reserved`, read by kMixChannel2 only
   double p, scale;
 };
+
+// Which general-channel cases an instantiation carries: each costs vector registers, so a program (tile-fused engine: a
+// segment) runs the lowest level that holds its ops.  A level carries the cases below it.
+enum MixedLevel : int {
+  kLevelLean = 0,     // the five-scalar channels only
+  kLevelChannel = 1,  // + kMixChannel
+  kLevelChannel2 = 2, // + kMixChannel2 (where its S is staged: 256 V2<T> of static LDS)
+};
+__host__ __device__ constexpr int mixed_level_of(int kind) {
+  return kind == kMixChannel2 ? kLevelChannel2 : kind == kMixChannel ? kLevelChannel : kLevelLean;
+}
 
 struct MixedScalars {
   int32_t n, n_ops, measure, n_features;  // measure 0 probs, 1 <Z_w>
@@ -91,7 +107,7 @@ __device__ __forceinline__ double mixed_block_sum(double v, double* s_red) {
 
 __device__ __forceinline__ bool mixed_needs_snapshot(int kind, int oi) {
   return kind == kMixPhaseDamp || kind == kMixAmpDamp || kind == kMixDepol || kind == kMixChannel ||
-         (oi > 0 && (kind == kMixZero || kind == kMixAmpEmbed));
+         kind == kMixChannel2 || (oi > 0 && (kind == kMixZero || kind == kMixAmpEmbed));
 }
 
 // ---- per-element / per-block arithmetic, shared by mixed_apply_op and the tiled engine (qsim_mixed_wide.h) ----------
@@ -209,8 +225,8 @@ __device__ __forceinline__ void mixed_block_channel_adjoint(const MixedChannel<T
 // The coefficients are the same for every thread of the workgroup: mixed_uniform pins each one to scalar registers, so
 // the 16 complex numbers cost no vector registers in the block loops.  Its case still costs the kernels that carry it
 // vector registers (a resident wave per SIMD in mixed_kernel, mixed_wide_sweep<float> and mixed_wide_adjoint_channels),
-// so those kernels have a GENERAL instantiation with the case and a lean one without; the host launches GENERAL only
-// for a program (tile-fused engine: a segment) that holds such an op.
+// so those kernels have an instantiation per MixedLevel; the host launches the lowest level that holds the ops of the
+// program (tile-fused engine: of the segment).
 __device__ __forceinline__ float mixed_uniform(float v) {
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
@@ -261,6 +277,75 @@ __device__ __forceinline__ void mixed_block_super_adjoint(const MixedSuper<T>& s
   m10 = o[2];
   m11 = o[3];
 }
+// ---- the general two-wire channel ------------------------------------------------------------------------------------
+// S (16 x 16 complex, row-major in gates[a .. a+63]: 256 consecutive (re, im) pairs) is the same for every thread, but
+// 256 complex numbers do not fit scalar registers the way the one-wire op's 16 do.  Two ways to read it:
+//   uniform  every coefficient is a uniform load from `gates` (the compiler makes scalar loads of them), converted from
+//            float64 where it is used: no LDS, no barrier, no vector register for S.
+//   staged   the workgroup copies S once per op to LDS, rounded once to T (2 KiB in float32, 4 KiB in float64); every
+//            read in the block loops is a broadcast (all lanes one address).
+// Measured on whole programs (profiles/mixed_channel2/op_cost.json): uniform is 7-17 % faster in the forward
+// of both engines and 4-6 % in the one-workgroup backward, staged 5-8 % faster in the tile-fused backward only; a mix
+// by direction was slower than either there.  Uniform is what is built, in both directions.
+template <typename T>
+struct MixedSuper2 {
+  const double* __restrict__ g;  // S in `gates`
+  __device__ __forceinline__ V2<T> at(int i) const { return V2<T>{(T)g[2 * i], (T)g[2 * i + 1]}; }
+};
+template <typename T>
+__device__ __forceinline__ MixedSuper2<T> mixed_super2(const MixedOp& op, const double* __restrict__ gates) {
+  return MixedSuper2<T>{gates + (size_t)op.a * 8};
+}
+// where the 4 x 4 block's rows and columns sit: the bits of the first and second wire in the row half (r1, r2) and in
+// the column half (c1, c2) -- any bit numbering: global or tile-local -- and the four positions in ascending order
+struct MixedBlock2 {
+  int r1, r2, c1, c2;
+  int pos[4];  // the block number's bits go around these
+  // element e = 4 r + c of the block (r = 2 b_w1 + b_w2 from the row bits, c from the column bits) relative to its base
+  __device__ __forceinline__ uint32_t elem(int e) const {
+    return (((uint32_t)e >> 3 & 1u) << r1) | (((uint32_t)e >> 2 & 1u) << r2) | (((uint32_t)e >> 1 & 1u) << c1) |
+           (((uint32_t)e & 1u) << c2);
+  }
+};
+__device__ __forceinline__ MixedBlock2 mixed_block2(int c1, int c2, int r1, int r2) {
+  MixedBlock2 b;
+  b.r1 = r1; b.r2 = r2; b.c1 = c1; b.c2 = c2;
+  // both numberings keep every column bit below every row bit and the order of the wires the same in both halves
+  b.pos[0] = c1 < c2 ? c1 : c2;
+  b.pos[1] = c1 < c2 ? c2 : c1;
+  b.pos[2] = r1 < r2 ? r1 : r2;
+  b.pos[3] = r1 < r2 ? r2 : r1;
+  return b;
+}
+// block number t -> the index of its (0, 0) element: zero bits inserted at the four positions
+__device__ __forceinline__ uint32_t mixed_block2_base(uint32_t t, const MixedBlock2& b) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) t = (t & ((1u << b.pos[i]) - 1u)) | ((t >> b.pos[i]) << (b.pos[i] + 1));
+  return t;
+}
+// vec(M) <- S vec(M) (ADJOINT: S^H vec(M), out[c] = sum_r conj(S[r][c]) v[r]) on the block at `base` of `mem`, in place:
+// all 16 elements are read before the first is written, and the thread owns the block.  `snap`: the block as it was
+// goes there too.  The 16-term sums run in a fixed order.  The loop over the outputs stays rolled: unrolled, the
+// compiler fetches all 256 coefficients ahead of the arithmetic and spills (2.8 KB of scratch a lane in mixed_kernel).
+template <typename T, bool ADJOINT>
+__device__ __forceinline__ void mixed_block_super2(const MixedSuper2<T>& su, V2<T>* __restrict__ mem, V2<T>* __restrict__ snap,
+                                                   uint32_t base, const MixedBlock2& b) {
+  V2<T> v[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) v[e] = mem[base | b.elem(e)];
+  if (snap) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) snap[base | b.elem(e)] = v[e];
+  }
+#pragma unroll 1
+  for (int o = 0; o < 16; ++o) {
+    V2<T> acc = ADJOINT ? cmulc<T>(v[0], su.at(o)) : cmul<T>(su.at(o * 16), v[0]);
+#pragma unroll
+    for (int e = 1; e < 16; ++e) acc = acc + (ADJOINT ? cmulc<T>(v[e], su.at(e * 16 + o)) : cmul<T>(su.at(o * 16 + e), v[e]));
+    mem[base | b.elem(o)] = acc;
+  }
+}
+
 // acc += B_rho B_Lambda^dagger of one block: N_ab = sum_c rho_ac conj(Lambda_bc), (re, im) of N00, N01, N10, N11
 template <typename T>
 __device__ __forceinline__ void mixed_block_n_accumulate(double (&acc)[8], V2<T> r00, V2<T> r01, V2<T> r10, V2<T> r11,
@@ -351,7 +436,7 @@ __device__ __forceinline__ void mixed_read_out(const V2<T>* __restrict__ rho, do
 
 // Op `op` of the program on one sample's rho.  `snap` (NULL in the forward): where the backward's replay keeps rho as
 // it was before a channel or a state preparation.  The caller puts a barrier after every op.
-template <typename T, bool GENERAL>
+template <typename T, int LEVEL>
 __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restrict__ rho, V2<T>* __restrict__ snap,
                                                const double* __restrict__ angle_rows, const double* __restrict__ feats,
                                                const double* __restrict__ gates, double* s_red, const MixedScalars& m,
@@ -440,8 +525,18 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
       }
       break;
     }
+    case kMixChannel2: {
+      if constexpr (LEVEL >= kLevelChannel2) {
+        // 4^n / 16 blocks for 256 threads: fewer blocks than threads up to n = 5, one block (all of rho) at n = 2
+        const int q2 = n - 1 - op.wire2;
+        const MixedBlock2 b = mixed_block2(q, q2, q + n, q2 + n);
+        const auto su = mixed_super2<T>(op, gates);
+        for (uint32_t t = tid; t < DD / 16; t += 256) mixed_block_super2<T, false>(su, rho, snap, mixed_block2_base(t, b), b);
+      }
+      break;
+    }
     case kMixChannel: {
-      if constexpr (GENERAL) {
+      if constexpr (LEVEL >= kLevelChannel) {
         const MixedSuper<T> su = mixed_super<T>(op, gates);
         for (uint32_t t = tid; t < DD / 4; t += 256) {
           const uint32_t base = insert_two_bits(t, q, q + n);
@@ -466,7 +561,7 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
   }
 }
 
-template <typename T, bool GENERAL>
+template <typename T, int LEVEL>
 __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ prog,
                                                     const double* __restrict__ angle_rows,
                                                     const double* __restrict__ feats,
@@ -482,7 +577,7 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
   for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
     for (int oi = 0; oi < m.n_ops; ++oi) {
       const MixedOp op = prog[oi];
-      mixed_apply_op<T, GENERAL>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
+      mixed_apply_op<T, LEVEL>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
       __syncthreads();
     }
     mixed_read_out<T>(rho, out, s_red, m, sample);  // the diagonal
@@ -528,7 +623,7 @@ __device__ __forceinline__ void mixed_udag_b_u(V2<T>& b00, V2<T>& b01, V2<T>& b1
   b11 = cmul<T>(a10, u01) + cmul<T>(a11, u11);
 }
 
-template <typename T, bool GENERAL>
+template <typename T, int LEVEL>
 __global__ __launch_bounds__(256) void mixed_backward_kernel(
     const MixedOp* __restrict__ prog, const double* __restrict__ angle_rows, const double* __restrict__ feats,
     const double* __restrict__ gates, const double* __restrict__ grad_out, double* __restrict__ grad_rows,
@@ -560,7 +655,7 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
     for (int oi = 0; oi < m.n_ops; ++oi) {
       const MixedOp op = prog[oi];
       C* snap = mixed_needs_snapshot(op.kind, oi) ? snaps + (size_t)(si++) * DD : nullptr;
-      mixed_apply_op<T, GENERAL>(op, rho, snap, angle_rows, feats, gates, s_red, m, sample);
+      mixed_apply_op<T, LEVEL>(op, rho, snap, angle_rows, feats, gates, s_red, m, sample);
       __syncthreads();
     }
 
@@ -688,8 +783,19 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
           }
           break;
         }
+        case kMixChannel2: {  // S^H on vec of each 4 x 4 block of Lambda, rho from the snapshot; its 64 rows of grad_gates stay zero
+          if constexpr (LEVEL >= kLevelChannel2) {
+            const int q2 = n - 1 - op.wire2;
+            const MixedBlock2 bl = mixed_block2(q, q2, q + n, q2 + n);
+            const auto su = mixed_super2<T>(op, gates);
+            const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
+            for (uint32_t t = tid; t < DD / 16; t += 256) mixed_block_super2<T, true>(su, lam, nullptr, mixed_block2_base(t, bl), bl);
+            for (uint32_t k = tid; k < DD; k += 256) rho[k] = sp[k];
+          }
+          break;
+        }
         case kMixChannel: {  // its four rows of grad_gates stay zero: channel operands get no gradient
-          if constexpr (GENERAL) {
+          if constexpr (LEVEL >= kLevelChannel) {
             const MixedSuper<T> su = mixed_super<T>(op, gates);
             const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
             for (uint32_t t = tid; t < DD / 4; t += 256) {

@@ -9,7 +9,8 @@
 // are the tile number.  A segment holds
 //   * ops that are diagonal on vec(rho) -- PHASE, CZ, PhaseDamping -- on any wires: the factor of an element depends
 //     on its global index only (tile bits + local bits);
-//   * GATE / RY / AmplitudeDamping / Depolarizing / the general channel on a tile wire, CNOT with both wires in the tile;
+//   * GATE / RY / AmplitudeDamping / Depolarizing / the general channel on a tile wire, CNOT and the general two-wire
+//     channel with both wires in the tile (2^12 / 16 = 256 blocks of 4 x 4: one per thread);
 //   * ZERO / AMP_EMBED as its first op: the tile is generated instead of read.
 // The host cuts the program into segments (plan_mixed_wide in qiddm_mixed.hip) and uploads it sorted by segment.
 // Wires n-1 and n-2 (q = 0, 1) belong to every tile: the two lowest column bits are local, so a lane moves two
@@ -71,8 +72,9 @@ __global__ __launch_bounds__(256) void mixed_wide_norms(const double* __restrict
   if (threadIdx.x == 0) norms[blockIdx.x] = v;
 }
 
-// GENERAL: the instantiation that carries the general channel's case (qsim_mixed.h), launched for segments that hold one
-template <typename T, bool GENERAL>
+// LEVEL (MixedLevel, qsim_mixed.h): the general-channel cases the instantiation carries; a segment is launched at the
+// lowest level that holds its ops
+template <typename T, int LEVEL>
 __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restrict__ prog,
                                                         const double* __restrict__ angle_rows,
                                                         const double* __restrict__ feats,
@@ -194,8 +196,18 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         }
         break;
       }
+      case kMixChannel2: {
+        if constexpr (LEVEL >= kLevelChannel2) {
+          const int q2 = n - 1 - op.wire2;
+          const MixedBlock2 b = mixed_block2(wide_local_rank(sg, q), wide_local_rank(sg, q2), wide_local_rank(sg, q + n),
+                                             wide_local_rank(sg, q2 + n));
+          const auto su = mixed_super2<T>(op, gates);
+          for (uint32_t t = tid; t < kWideTile / 16; t += 256) mixed_block_super2<T, false>(su, tile, nullptr, mixed_block2_base(t, b), b);
+        }
+        break;
+      }
       case kMixChannel: {
-        if constexpr (GENERAL) {
+        if constexpr (LEVEL >= kLevelChannel) {
           const int a = wide_local_rank(sg, q), b = wide_local_rank(sg, q + n);
           const uint32_t cj = 1u << a, ci = 1u << b;
           const MixedSuper<T> su = mixed_super<T>(op, gates);

@@ -236,9 +236,9 @@ __global__ __launch_bounds__(256) void mixed_wide_reverse_sweep(
   }
 }
 
-// One channel segment backwards: E^dagger on the Lambda tile of (tile, sample), ops in reverse.  GENERAL: as in
+// One channel segment backwards: E^dagger on the Lambda tile of (tile, sample), ops in reverse.  LEVEL: as in
 // mixed_wide_sweep
-template <typename T, bool GENERAL>
+template <typename T, int LEVEL>
 __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp* __restrict__ prog,
                                                                    const double* __restrict__ gates,
                                                                    const double* __restrict__ grad_out,
@@ -262,7 +262,17 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp
     const bool diag = op.kind == kMixPhaseDamp;
     if (!(diag && owned)) __syncthreads();
     owned = diag;
-    if (GENERAL && op.kind == kMixChannel) {  // S^H on vec of each block
+    if constexpr (LEVEL >= kLevelChannel2) {
+      if (op.kind == kMixChannel2) {  // S^H on vec of each 4 x 4 block
+        const int q2 = n - 1 - op.wire2;
+        const MixedBlock2 bl = mixed_block2(wide_local_rank(sg, q), wide_local_rank(sg, q2), wide_local_rank(sg, q + n),
+                                            wide_local_rank(sg, q2 + n));
+        const auto su = mixed_super2<T>(op, gates);
+        for (uint32_t t = tid; t < kWideTile / 16; t += 256) mixed_block_super2<T, true>(su, lt, nullptr, mixed_block2_base(t, bl), bl);
+        continue;
+      }
+    }
+    if (LEVEL >= kLevelChannel && op.kind == kMixChannel) {  // S^H on vec of each block
       const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
       const uint32_t cj = 1u << a, ci = 1u << bb;
       const MixedSuper<T> su = mixed_super<T>(op, gates);

@@ -20,6 +20,12 @@ PhaseDamping, AmplitudeDamping and DepolarizingChannel are native ops of the ker
 QubitChannel) is lowered to ``QIDDM_MIX_CHANNEL``: its 4 x 4 superoperator S = sum_k K_k (x) conj(K_k), worked out here
 on the host in float64 (``channel_kraus``, ``channel_rows``, ``superoperator``), travels as four rows of ``gates``.
 
+Two-wire channels -- ``qml.QubitChannel`` with 4 x 4 operators on ``wires=[a, b]`` and ``qml.PauliError`` with a
+two-letter word: entangler error, correlated dephasing, a measured two-qubit process -- are ``QIDDM_MIX_CHANNEL2``: the
+16 x 16 superoperator of the same formula (operator index 2 b_a + b_b, the first listed wire most significant), worked
+out by the same helpers with ``wires=2``, travels as 64 rows of ``gates``, and the op's fourth field names the second
+wire.  Rows that one circuit records several times (one error model behind every entangler) are uploaded once.
+
 Beyond 8 wires gradients are a second opt-in, ``set_max_grad_wires(10)`` or ``with max_grad_wires(10):`` -- the reverse
 sweep of the tile-fused engine (``qiddm_mixed_wide_backward``) keeps rho, its adjoint and one snapshot per group of
 channels per sample, several slabs where the forward keeps one.  With both limits raised a 9- or 10-wire launch is the
@@ -29,6 +35,7 @@ tile-fused reverse sweep.
 from __future__ import annotations
 
 import contextlib
+import functools
 import math
 
 import numpy as np
@@ -93,6 +100,7 @@ def channel_kraus(name, *params):
     """The Kraus operators (a list of 2 x 2 complex128 arrays) of a named one-wire channel, PennyLane's definitions:
     PhaseDamping(g), AmplitudeDamping(g), DepolarizingChannel(p), BitFlip(p), PhaseFlip(p), PauliError(P, p),
     GeneralizedAmplitudeDamping(g, p), ResetError(p0, p1), ThermalRelaxationError(pe, t1, t2, tg).
+    PauliError with a two-letter word is the two-wire channel {sqrt(1-p) I, sqrt(p) P_a (x) P_b}: 4 x 4 operators.
     Arguments out of range raise ``ValueError`` naming the parameter."""
     eye = np.eye(2, dtype=complex)
     e = lambda r, c: np.array([[float((r, c) == (i, j)) for j in range(2)] for i in range(2)], dtype=complex)  # |r><c|
@@ -112,10 +120,11 @@ def channel_kraus(name, *params):
         p = _prob("p", params[0])
         return [math.sqrt(1 - p) * eye, math.sqrt(p) * _PAULI["X" if name == "BitFlip" else "Z"]]
     if name == "PauliError":
-        op, p = params[0], _prob("p", params[1])
-        if op not in _PAULI:
-            raise ValueError(f"operators must be 'X', 'Y' or 'Z' on one wire (got {op!r})")
-        return [math.sqrt(1 - p) * eye, math.sqrt(p) * _PAULI[op]]
+        word, p = params[0], _prob("p", params[1])
+        if not isinstance(word, str) or not 1 <= len(word) <= 2 or any(c not in _PAULI for c in word):
+            raise ValueError(f"operators must be a word of one or two letters 'X', 'Y', 'Z', one per wire (got {word!r})")
+        pauli = functools.reduce(np.kron, [_PAULI[c] for c in word])  # the first letter's wire is the most significant
+        return [math.sqrt(1 - p) * np.eye(pauli.shape[0], dtype=complex), math.sqrt(p) * pauli]
     if name == "GeneralizedAmplitudeDamping":
         g, p = _prob("gamma", params[0]), _prob("p", params[1])
         return [math.sqrt(p) * np.diag([1, math.sqrt(1 - g)]).astype(complex), math.sqrt(p * g) * e(0, 1),
@@ -141,39 +150,47 @@ def channel_kraus(name, *params):
 
 
 def _rows(s):
-    """4 x 4 complex -> (4, 8) float64 rows, (re, im) interleaved: the layout of QIDDM_MIX_CHANNEL's gate rows."""
-    out = np.empty((4, 8), dtype=np.float64)
+    """4 x 4 complex -> (4, 8) float64 rows, (re, im) interleaved: the layout of QIDDM_MIX_CHANNEL's gate rows.
+    16 x 16 -> (64, 8), QIDDM_MIX_CHANNEL2's: row t of S is gate rows 4t .. 4t+3, four entries each."""
+    s = s.reshape(-1, 4)
+    out = np.empty((s.shape[0], 8), dtype=np.float64)
     out[:, 0::2], out[:, 1::2] = s.real, s.imag
     return torch.from_numpy(out)
 
 
-def _matrices(kraus):
+def _matrices(kraus, wires=1):
+    if wires not in (1, 2):
+        raise NotImplementedError(f"channels on {wires} wires: one- and two-wire channels are supported")
+    d = 1 << wires
     ks = [np.asarray(k.detach().cpu().numpy() if torch.is_tensor(k) else k, dtype=complex) for k in kraus]
-    if not ks or any(k.shape != (2, 2) for k in ks):
-        raise ValueError("Kraus operators must be a non-empty list of 2 x 2 matrices")
+    if not ks or any(k.shape != (d, d) for k in ks):
+        raise ValueError(f"Kraus operators must be a non-empty list of {d} x {d} matrices")
     return ks
 
 
-def superoperator(kraus):
+def superoperator(kraus, wires=1):
     """``(4, 8)`` float64 (CPU) rows of S = sum_k K_k (x) conj(K_k) for a list of 2 x 2 complex matrices: S acts on
-    vec(M) = (M00, M01, M10, M11) as M -> sum_k K_k M K_k^dagger."""
-    return _rows(sum(np.kron(k, k.conj()) for k in _matrices(kraus)))
+    vec(M) = (M00, M01, M10, M11) as M -> sum_k K_k M K_k^dagger.  ``wires=2``: 4 x 4 matrices (index 2 b_1 + b_2, the
+    first wire most significant) -> the ``(64, 8)`` rows of the 16 x 16 S on vec(M)[4 r + c] = M[r][c]."""
+    return _rows(sum(np.kron(k, k.conj()) for k in _matrices(kraus, wires)))
 
 
 def channel_rows(name, *params):
     """``(4, 8)`` float64 (CPU) superoperator rows of a named channel (see ``channel_kraus``).  ThermalRelaxationError is
-    written down directly (it needs no Kraus set, and t1 < t2 <= 2 t1 has no Pauli / reset one)."""
+    written down directly (it needs no Kraus set, and t1 < t2 <= 2 t1 has no Pauli / reset one).  PauliError with a
+    two-letter word: ``(64, 8)``."""
     if name == "ThermalRelaxationError":
         return _rows(_thermal_super(*params))
-    return superoperator(channel_kraus(name, *params))
+    kraus = channel_kraus(name, *params)
+    return superoperator(kraus, wires=2 if kraus[0].shape[0] == 4 else 1)
 
 
-def qubit_channel_rows(kraus):
+def qubit_channel_rows(kraus, wires=1):
     """``superoperator`` for ``qml.QubitChannel``: refuses a set that is not trace preserving (sum K^dagger K = I to 1e-10)."""
-    dev = np.abs(sum(k.conj().T @ k for k in _matrices(kraus)) - np.eye(2)).max()
+    dev = np.abs(sum(k.conj().T @ k for k in _matrices(kraus, wires)) - np.eye(1 << wires)).max()
     if not dev <= 1e-10:
         raise ValueError(f"K_list is not trace preserving: sum K^dagger K differs from the identity by {dev:.3e}")
-    return superoperator(kraus)
+    return superoperator(kraus, wires)
 
 
 # wires up to which ``execute`` runs a circuit (8: the one-workgroup kernel only; 9, 10: the tile-fused engine as well)
@@ -241,6 +258,7 @@ def rot_matrices(weights: torch.Tensor) -> torch.Tensor:
 class _Lowering:
     def __init__(self, n):
         self.n, self.ops, self.rows, self.gates = n, [], [], []
+        self.n_gates, self.channel_base = 0, {}  # rows so far; bytes of a two-wire channel's rows -> their first row
         self.batch, self.batched = None, False
         self.features, self.pad_with = None, 0.0
         self.device = None
@@ -275,17 +293,30 @@ class _Lowering:
     def op(self, kind, wire=0, a=-1, p=0.0, scale=1.0):
         self.ops.append((kind, wire, a, p, scale))
 
+    def _add_gates(self, g):
+        base = self.n_gates
+        self.gates.append(g)
+        self.n_gates += g.shape[0]
+        return base
+
     def channel(self, rows, wire):
         """A general one-wire channel: its four superoperator rows join the gates, `a` is the first of them."""
-        base = sum(g.shape[0] for g in self.gates)
-        self.gates.append(rows)
-        self.op(_capi.MIX_CHANNEL, wire, base)
+        self.op(_capi.MIX_CHANNEL, wire, self._add_gates(rows))
+
+    def channel2(self, rows, wire, second):
+        """A general two-wire channel: 64 rows, the second wire in the op's fourth field.  Rows equal (bit for bit) to
+        those of an earlier two-wire channel of the circuit join the gates once: a noise model puts the same 4 KiB
+        behind every entangler."""
+        key = rows.contiguous().numpy().tobytes()
+        base = self.channel_base.get(key)
+        if base is None:
+            base = self.channel_base[key] = self._add_gates(rows)
+        self.ops.append((_capi.MIX_CHANNEL2, wire, base, 0.0, 1.0, second))  # the only six-field entry of `ops`
 
     def sel(self, weights, wires, imprimitive):
         n = len(wires)
         self._see(weights)
-        base = sum(g.shape[0] for g in self.gates)
-        self.gates.append(rot_matrices(weights))
+        base = self._add_gates(rot_matrices(weights))
         kind = _capi.MIX_CZ if imprimitive == "CZ" else _capi.MIX_CNOT
         for layer in range(weights.shape[0]):
             for i, w in enumerate(wires):
@@ -343,7 +374,10 @@ def lower(tape, ret, n):
                 else:
                     low.op(CHANNELS[t.name], t.wires[0], -1, float(p))
             elif "superoperator" in t.hyper:
-                low.channel(t.hyper["superoperator"], t.wires[0])
+                if len(t.wires) == 2:
+                    low.channel2(t.hyper["superoperator"], t.wires[0], t.wires[1])
+                else:
+                    low.channel(t.hyper["superoperator"], t.wires[0])
             else:
                 raise NotImplementedError(f"operation {t.name} is not supported on default.mixed")
         first = False
@@ -369,8 +403,8 @@ class _Launch:
         self.n, self.prec, self.measure, self.batch, self.device = n, prec, measure, batch, device
         self.pad_with, self.n_rows = low.pad_with, len(low.rows)
         self.prog = (_capi.MixedOp * len(low.ops))()
-        for dst, (kind, wire, a, p, scale) in zip(self.prog, low.ops):
-            dst.kind, dst.wire, dst.a, dst.reserved, dst.p, dst.scale = kind, wire, a, 0, p, scale
+        for dst, (kind, wire, a, p, scale, *second) in zip(self.prog, low.ops):  # second: MIX_CHANNEL2's other wire
+            dst.kind, dst.wire, dst.a, dst.reserved, dst.p, dst.scale = kind, wire, a, second[0] if second else 0, p, scale
 
     def _prefix(self, rows, gates, feats):
         """The arguments every compute entry point starts with: ``n_qubits`` .. ``batch``."""

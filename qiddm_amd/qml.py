@@ -19,6 +19,7 @@ from __future__ import annotations
 import threading
 from typing import Iterable
 
+import numpy as np
 import torch
 
 from . import circuit as _c
@@ -132,16 +133,23 @@ AmplitudeDamping = _channel("AmplitudeDamping")
 DepolarizingChannel = _channel("DepolarizingChannel")
 
 
-# PennyLane's other one-wire channels: default.mixed runs them as one general op whose 4 x 4 superoperator is worked
-# out here on the host (qiddm_amd.mixed.channel_rows).  Strengths are Python floats or host arrays; arguments out of
-# range raise ValueError when the op is constructed.
-def _general_channel(name, wires, params, rows_of):
-    """`rows_of(mixed)`: the op's (4, 8) superoperator rows; it checks the parameters."""
+# PennyLane's other channels: default.mixed runs them as one general op whose superoperator is worked out here on the
+# host (qiddm_amd.mixed.channel_rows): 4 x 4 on one wire, 16 x 16 on two (QubitChannel with 4 x 4 operators and
+# PauliError with a two-letter word).  Strengths are Python floats or host arrays; arguments out of range raise
+# ValueError when the op is constructed.
+def _general_channel(name, wires, params, rows_of, two_wires=False):
+    """`rows_of(mixed)`: the op's (4, 8) -- on two wires (64, 8) -- superoperator rows; it checks the parameters."""
     from . import mixed as _mixed
     w = _wires(wires)
-    if len(w) != 1:
+    if len(w) > 2:
+        raise NotImplementedError(f"{name} on {len(w)} wires: one- and two-wire channels are supported")
+    if len(w) == 2 and not two_wires:
         raise NotImplementedError(f"{name} on {len(w)} wires: only one-wire channels are supported (the density-matrix "
                                   "kernels apply a channel to the 2 x 2 blocks of a single wire)")
+    if len(w) == 2 and w[0] == w[1]:
+        raise ValueError(f"{name}: the two wires must differ (got {list(w)})")
+    if len(w) != 1 and len(w) != 2:
+        raise ValueError(f"{name}: bad wires {wires!r}")
     return _Op(name, w, params, channel=True, superoperator=rows_of(_mixed))
 
 
@@ -166,6 +174,14 @@ def ResetError(p0, p1, wires):
 
 
 def PauliError(operators, p, wires):
+    """``qml.PauliError(operators, p, wires)``: one letter of "XYZ" per wire, one or two wires."""
+    w = _wires(wires)
+    if isinstance(operators, str) and len(w) in (1, 2) and len(operators) != len(w):
+        raise ValueError(f"PauliError: operators {operators!r} has {len(operators)} letter(s) for {len(w)} wire(s); "
+                         "the word needs one letter per wire")
+    if len(w) == 2:
+        return _general_channel("PauliError", w, (operators, p),
+                                lambda mixed: mixed.channel_rows("PauliError", operators, p), two_wires=True)
     return _named_channel("PauliError", wires, operators, p)
 
 
@@ -174,8 +190,20 @@ def ThermalRelaxationError(pe, t1, t2, tg, wires):
 
 
 def QubitChannel(K_list, wires):
-    """``qml.QubitChannel(K_list, wires)``: Kraus operators as 2 x 2 complex host matrices, sum K^dagger K = I."""
+    """``qml.QubitChannel(K_list, wires)``: Kraus operators as complex host matrices, sum K^dagger K = I; 2 x 2 on one
+    wire, 4 x 4 on two (index 2 b_a + b_b for ``wires=[a, b]``)."""
+    w = _wires(wires)
+    if len(w) == 2 and not _all_2x2(K_list):
+        return _general_channel("QubitChannel", w, (), lambda mixed: mixed.qubit_channel_rows(K_list, 2), two_wires=True)
     return _general_channel("QubitChannel", wires, (), lambda mixed: mixed.qubit_channel_rows(K_list))
+
+
+def _all_2x2(K_list):
+    """One-wire operators (on two wires: the refusal that names one-wire channels)."""
+    def shape(k):
+        s = getattr(k, "shape", None)  # arrays and tensors; nested lists go through numpy, which names a ragged one
+        return tuple(np.shape(k) if s is None else s)
+    return len(K_list) > 0 and all(shape(k) == (2, 2) for k in K_list)
 
 
 # --- measurements -------------------------------------------------------------
