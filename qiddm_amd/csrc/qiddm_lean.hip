@@ -57,15 +57,17 @@ qiddm::KScalars params_of(const qiddm_circuit_t* c) {
 
 // When the instance that carries both bodies (qsim_lean.h: lean_has_solo) runs the one-wavefront-per-item body: from
 // kLeanSoloMinSteps steps per launch on at every batch, below that from kLeanSoloMinItems items (batch x n_steps) on.
-// A solo workgroup stages linear_up's weights and every wavefront the whole phase table before its first item (~9 us
-// for a launch of one item against ~5 us), and then runs one item in ~3 us, whatever the launch holds up to 2 048 items;
-// the four-wave body pays ~2.7 us per step of a sample.  Measured by tools/ab_lean_solo_threshold.py, float32, P = 784
-// (profiles/lean_solo/threshold.txt; us per launch, four-wave / solo):
-//   1 step:   256 items 5.8 / 12.3    1 024 items 13.4 / 13.1    2 048 items 24.1 / 14.5
-//   4 steps:   64 items 13.2 / 12.0   1 024 items 14.9 / 13.1
-//   15 steps: 240 items 42.9 / 12.3   3 840 items 46.3 / 21.7
+// A solo workgroup stages linear_up's weights and the phase table in LDS and every wavefront fills its registers from
+// there before its first item (~7 us for a launch of one item against ~5 us), and then runs one item in ~3 us, whatever
+// the launch holds up to 2 048 items; the four-wave body pays ~2.7 us per step of a sample.  Measured by
+// tools/ab_lean_solo_threshold.py, float32, P = 784 (profiles/lean_pipeline/threshold.txt; us per launch, four-wave /
+// solo):
+//   1 step:   256 items 5.7 / 9.6     512 items 7.8 / 9.9    1 024 items 13.4 / 10.5    2 048 items 24.0 / 11.8
+//   4 steps:   64 items 13.3 / 9.3    1 024 items 14.9 / 10.6
+//   15 steps: 240 items 42.8 / 9.5    3 840 items 45.8 / 18.3
+// (2 and 3 steps are not in the table: the step rule stays where it was measured.)
 constexpr int kLeanSoloMinSteps = 4;
-constexpr int64_t kLeanSoloMinItems = 2048;
+constexpr int64_t kLeanSoloMinItems = 1024;
 
 int lean_cu_count() {
   static int cus[qiddm_capi::DeviceFlags::kMaxDevices] = {};

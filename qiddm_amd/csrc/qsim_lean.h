@@ -2,7 +2,7 @@
 //
 // Which instance runs which decomposition:
 //   * float32, 8 qubits, no re-upload, compiled-in layer count, goal "data", P <= 1024 (the flagship QNN_noise(784, 8, 14)),
-//     launches of at least 4 steps or 2 048 (sample, step) items: ONE wavefront per item, four amplitudes per lane, no
+//     launches of at least 4 steps or 1 024 (sample, step) items: ONE wavefront per item, four amplitudes per lane, no
 //     exchange and no barrier in a layer, the items of a launch dealt to all wavefronts -- qsim_lean_solo.h, which says
 //     why.  The kernel keeps its name and template arguments; the host picks the body by the workgroup size
 //     (qiddm_lean.hip: launch_lean, with the measured threshold).

@@ -1,33 +1,45 @@
 // qsim_lean_solo.h -- the "solo" body of the lean sampling loop: ONE wavefront per (sample, step) item of the 8-qubit
 // net without re-upload and with a compiled-in layer count (float32; the flagship QNN_noise(784, 8, 14)).
 //
-// Layout: all 256 amplitudes in one wavefront, four per lane.  Amplitude k = (r << 6) | logical_lane(lane), r = 0..3:
-// the register bits are index bits 6 and 7 -- the WAVE bits of the four-wave decomposition (qsim_lean.h), so entry
-// r * 64 + lane of a LeanTables<T, 8> layer is this lane's entry for register r and the tables are read as they are.
+// Layout: all 256 amplitudes in one wavefront, four per lane, in one of TWO layouts that alternate from layer to layer
+// (solo_amp below).  Index bits 0..3 are lane bits 0..3 in both.  Layout A: amplitude k = (r << 6) | logical_lane(lane),
+// r = 0..3 -- the register bits are index bits 6 and 7, the WAVE bits of the four-wave decomposition (qsim_lean.h), so
+// entry r * 64 + lane of a LeanTables<T, 8> layer is this lane's entry for register r.  Layout B: the register bits are
+// index bits 5 and 4, lane bits 5 and 4 hold index bits 6 and 7.  Eight permlane swaps turn one into the other.
 // What that buys:
-//   * index bits 6 / 7 are plain FMAs on register pairs: no LDS exchange, no s_barrier in a layer;
+//   * the RYs of a layer commute: a layer applies the two bits that are register bits where it starts, swaps, and
+//     applies the two that are register bits where it ends -- every RY on index bits 4..7 is a packed FMA on register
+//     pairs, no LDS exchange, no s_barrier, and nothing is swapped back (the layer before this one swapped (re, im) of
+//     every amplitude there and back for bits 4 and 5: 16 swaps and 16 FMAs, 701 -> 571 ticks per layer with two
+//     wavefronts on a SIMD, profiles/lean_pipeline/ubench_solo_layer.txt);
 //   * every gate acts on 8 independent registers (4 amplitudes x re / im), so the wave issues back to back (~4 cycles
 //     per vector instruction) instead of waiting ~11 cycles on its own previous result;
 //   * the items of a launch (batch x n_steps: this instance's angles never reach the state, so its steps do not depend
 //     on each other) are spread over all wavefronts of all workgroups, kSoloWaves per CU.  Every item is still
 //     simulated in full.
-// After the per-workgroup setup (linear_up's weights and the tangents into LDS, one __syncthreads()) there is no
-// cross-wave synchronisation at all: every wave runs the same code and the only thing that depends on the wave number
-// is which items it takes.
+// The per-workgroup setup fetches the tables and linear_up's weights from global memory ONCE and hands them to the
+// eight wavefronts through LDS (one __syncthreads()); after it there is no cross-wave synchronisation at all: every wave
+// runs the same code -- one copy of it, so every row of a launch is the same bits -- and the only thing that depends on
+// the wave number is which items it takes.
 #pragma once
 #include "qsim_lean.h"
 
 namespace qiddm {
 
 // LDS of the solo body: linear_up's weights as [4][Qp] pairs (w[pix][2 jj], w[pix][2 jj + 1]) -- a lane's 16 bytes next
-// to its neighbour's: `ds_read_b128` without bank conflicts --, the bias [Qp], the tangents [layers][8].  Qp = Q rounded
-// up to whole wavefronts; the rows beyond Q hold copies of the last row and are never stored.
+// to its neighbour's: `ds_read_b128` without bank conflicts --, the bias [Qp], the tangents [layers][8], the phase
+// entries in the lanes' order.  Qp = Q rounded up to whole wavefronts; the rows beyond Q hold copies of the last row and
+// are never stored.
 struct LeanSoloLds {
   __host__ __device__ static constexpr int padded(int q) { return (q + kWave - 1) / kWave * kWave; }
   __host__ __device__ static constexpr size_t w_bytes(int q) { return (size_t)padded(q) * 8 * sizeof(double); }
   __host__ __device__ static constexpr size_t b_bytes(int q) { return (size_t)padded(q) * sizeof(double); }
+  __host__ __device__ static constexpr size_t un_bytes(int layers) { return (size_t)layers * 8 * sizeof(float); }
+  // the phase entries of the simulated layers 1 .. layers - 1 in the order the lanes take them: [layer][2][64] units of
+  // 16 bytes, unit (l, h, lane) = the lane's entries for registers 2 h and 2 h + 1 in the layout layer l starts in
+  __host__ __device__ static constexpr size_t ph_bytes(int layers) { return (size_t)(layers - 1) * 256 * 2 * sizeof(float); }
   __host__ __device__ static constexpr size_t bytes(int q, int layers) {
-    return w_bytes(q) + b_bytes(q) + (size_t)layers * 8 * sizeof(float);
+    return w_bytes(q) + b_bytes(q) + un_bytes(layers) + ph_bytes(layers);
   }
 };
 
@@ -70,10 +82,74 @@ __device__ __forceinline__ void solo_ry_reg(V2<float>& lo, V2<float>& hi, float 
   hi = nhi;
 }
 
-// One layer on the four amplitudes of a lane: phase table entry, then RY on every index bit (tangent form: the cosines
-// sit in the phase entry).  ts: tangents of index bits 0..3 signed by this lane's bit; t4..t7: plain tangents.
-__device__ __forceinline__ void solo_layer(V2<float> (&a)[4], const V2<float> (&ph)[4], const float (&ts)[4], float t4,
-                                           float t5, float t6, float t7) {
+// exchange a register bit with lane bit Q (4 / 5): the permlane swap of (register with the bit clear, register with it
+// set), on both components
+template <int Q>
+__device__ __forceinline__ void solo_swap_bit(V2<float>& lo, V2<float>& hi) {
+  float lx = lo.x, ly = lo.y, hx = hi.x, hy = hi.y;
+  swap_parts<Q>(lx, hx);
+  swap_parts<Q>(ly, hy);
+  lo = V2<float>{lx, ly};
+  hi = V2<float>{hx, hy};
+}
+
+// ---- the two layouts ------------------------------------------------------------------------------------------------------
+// Which amplitude register r (bit 0 = r0, bit 1 = r1) of the lane with logical number llane holds.  Index bits 0..3 are
+// lane bits 0..3 in both layouts (the DPP gates and their lane signs do not care which one the wave is in);
+//   layout A: index bits 4, 5 = lane bits 4, 5; index bits 6, 7 = r0, r1  -- k = (r << 6) | llane, the tables' own order;
+//   layout B: index bits 4, 5 = r1, r0;         index bits 6, 7 = lane bits 5, 4.
+// A `v_permlane32_swap` of (a[2 r1].c, a[2 r1 + 1].c) exchanges r0 with lane bit 5, a `v_permlane16_swap` of (a[r0].c,
+// a[2 + r0].c) exchanges r1 with lane bit 4 (c = re, im): eight swaps turn either layout into the other.
+constexpr int kSoloLayoutA = 0, kSoloLayoutB = 1;
+__host__ __device__ constexpr int solo_amp(int layout, int r, int llane) {
+  const int r0 = r & 1, r1 = (r >> 1) & 1, l4 = (llane >> 4) & 1, l5 = (llane >> 5) & 1, low = llane & 15;
+  return layout == kSoloLayoutA ? (low | (l4 << 4) | (l5 << 5) | (r0 << 6) | (r1 << 7))
+                                : (low | (r1 << 4) | (r0 << 5) | (l5 << 6) | (l4 << 7));
+}
+// entry of a LeanTables<float, 8> layer (thread order of the four-wave body: (wave << 6) | physical lane) that register r
+// of physical lane `lane` multiplies by in `layout`
+__host__ __device__ constexpr int solo_table_slot(int layout, int r, int lane) {
+  const int k = solo_amp(layout, r, lane ^ (((lane >> 2) & 1) * 3));   // (logical_lane, an involution)
+  return (k & ~63) | ((k & 63) ^ ((((k & 63) >> 2) & 1) * 3));
+}
+// where the eight swaps put the value of (r, llane): (r', llane') as (r' << 6) | llane'
+__host__ __device__ constexpr int solo_swapped(int r, int llane) {
+  const int r0 = r & 1, r1 = (r >> 1) & 1, l4 = (llane >> 4) & 1, l5 = (llane >> 5) & 1;
+  return ((l5 | (l4 << 1)) << 6) | (llane & 15) | (r1 << 4) | (r0 << 5);
+}
+__host__ __device__ constexpr bool solo_layout_is_bijection(int layout) {
+  bool seen[256] = {};
+  for (int r = 0; r < 4; ++r)
+    for (int l = 0; l < 64; ++l) {
+      const int k = solo_amp(layout, r, l);
+      if (k < 0 || k > 255 || seen[k]) return false;
+      seen[k] = true;
+    }
+  return true;
+}
+__host__ __device__ constexpr bool solo_swaps_map(int from, int to) {
+  for (int r = 0; r < 4; ++r)
+    for (int l = 0; l < 64; ++l) {
+      const int s = solo_swapped(r, l);
+      if (solo_amp(from, r, l) != solo_amp(to, s >> 6, s & 63)) return false;
+    }
+  return true;
+}
+static_assert(solo_layout_is_bijection(kSoloLayoutA) && solo_layout_is_bijection(kSoloLayoutB),
+              "each layout holds every amplitude 0..255 exactly once");
+static_assert(solo_swaps_map(kSoloLayoutA, kSoloLayoutB) && solo_swaps_map(kSoloLayoutB, kSoloLayoutA),
+              "the eight swaps turn layout A into layout B and back");
+static_assert(solo_amp(kSoloLayoutA, 2, 37) == ((2 << 6) | 37) && solo_table_slot(kSoloLayoutA, 3, 21) == 3 * 64 + 21,
+              "layout A reads the tables as they are");
+
+// One layer on the four amplitudes of a lane: phase table entry (gathered by the layout the layer starts in), then RY on
+// every index bit (tangent form: the cosines sit in the phase entry).  The RYs of a layer commute, so the two bits that
+// are register bits NOW go first, the eight swaps change the layout, and the two bits that are register bits THEN
+// follow: every RY on bits 4..7 is a packed FMA on register pairs and nothing is swapped back -- a layer that starts in A
+// ends in B and the other way round.  ts: tangents of index bits 0..3 signed by this lane's bit; t4..t7: plain tangents.
+// layout: the one the layer starts in (a constant once the layer sequence is unrolled).
+__device__ __forceinline__ void solo_layer(int layout, V2<float> (&a)[4], const V2<float> (&ph)[4], const float (&ts)[4],
+                                           float t4, float t5, float t6, float t7) {
   // (component by component, the products of cmul2: its packed form wants (ph.x, ph.x) and (ph.y, ph.y) as register
   //  pairs, which the compiler keeps across the loop for every layer -- twice the registers of the phase table)
 #pragma unroll
@@ -82,14 +158,21 @@ __device__ __forceinline__ void solo_layer(V2<float> (&a)[4], const V2<float> (&
     a[r] = V2<float>{re, im};
   }
   solo_ry_dpp4(a, ts[0], ts[1], ts[2], ts[3]);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) ry_t_swap<5, float>(a[r], t5);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) ry_t_swap<4, float>(a[r], t4);
-  solo_ry_reg(a[0], a[1], t6);
-  solo_ry_reg(a[2], a[3], t6);
-  solo_ry_reg(a[0], a[2], t7);
-  solo_ry_reg(a[1], a[3], t7);
+  const bool from_a = layout == kSoloLayoutA;
+  const float in0 = from_a ? t6 : t5, in1 = from_a ? t7 : t4;     // r0 / r1 of the layout the layer starts in
+  const float out0 = from_a ? t5 : t6, out1 = from_a ? t4 : t7;   // ... of the one it ends in
+  solo_ry_reg(a[0], a[1], in0);
+  solo_ry_reg(a[2], a[3], in0);
+  solo_ry_reg(a[0], a[2], in1);
+  solo_ry_reg(a[1], a[3], in1);
+  solo_swap_bit<5>(a[0], a[1]);
+  solo_swap_bit<5>(a[2], a[3]);
+  solo_swap_bit<4>(a[0], a[2]);
+  solo_swap_bit<4>(a[1], a[3]);
+  solo_ry_reg(a[0], a[1], out0);
+  solo_ry_reg(a[2], a[3], out0);
+  solo_ry_reg(a[0], a[2], out1);
+  solo_ry_reg(a[1], a[3], out1);
 }
 
 // The body of dense_lean_kernel<float, 8, PPT, false, LPR, false> at kSoloThreads threads per workgroup.
@@ -105,11 +188,16 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   using V4 = T __attribute__((ext_vector_type(4)));
   using D2 = double __attribute__((ext_vector_type(2)));
   static_assert(LPR > 1, "a compiled-in layer count with at least one simulated layer");
+  // the layout simulated layer l (1 .. LPR - 1) starts in: they alternate, and the last one ends in A, where the
+  // read-out expects the state
+  auto layout_of = [](int l) { return (LPR - 1 - l) % 2 == 0 ? kSoloLayoutB : kSoloLayoutA; };
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int Q = d.out_features, Qp = LeanSoloLds::padded(Q);
   D2* s_w = reinterpret_cast<D2*>(smem_raw);                                   // [4][Qp]
   double* s_b = reinterpret_cast<double*>(smem_raw + LeanSoloLds::w_bytes(Q));  // [Qp]
   T* s_un = reinterpret_cast<T*>(smem_raw + LeanSoloLds::w_bytes(Q) + LeanSoloLds::b_bytes(Q));   // [LPR][8]
+  C* s_ph = reinterpret_cast<C*>(smem_raw + LeanSoloLds::w_bytes(Q) + LeanSoloLds::b_bytes(Q) +
+                                 LeanSoloLds::un_bytes(LPR));                     // [LPR - 1][2][64][2]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int llane = logical_lane(lane);
@@ -117,17 +205,48 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   const C* g_ph = reinterpret_cast<const C*>(g_body);
   const T* g_un = g_body + QT::ph_elems(LPR);
   const T* g_a0 = g_un + QT::un_elems(LPR);
+  // diagnostics (tools/stamp_lean_solo.py): s_memtime of wavefront 0 of workgroup 0 -- [0] entry, [1] setup loads issued,
+  // [2] barrier passed, [3] / [4] end of the layers / of the tail of its first item, [5] / [6] of its second item.
+  // [7]: s_memrealtime (100 MHz) from entry to the last tail stamped, which gives the ticks their length.
+  // The test is wave-uniform (a scalar branch per stamp); lane 0 stores.
+  const bool stamp_wave = d.stamps != nullptr && blockIdx.x == 0 && wv == 0;
+  const unsigned long long stamp_rt0 = stamp_wave ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  auto stamp = [&](int word) {
+    if (stamp_wave) {
+      const unsigned long long t = __builtin_amdgcn_s_memtime();
+      const unsigned long long rt = __builtin_amdgcn_s_memrealtime() - stamp_rt0;
+      if (lane == 0) {
+        d.stamps[word] = t;
+        if (word == 4 || word == 6) d.stamps[7] = rt;
+      }
+    }
+  };
+  stamp(0);
 
-  // ---- per-launch setup: weights, bias and tangents into LDS; this lane's table entries into registers -----------------
-  // Every global load is issued before anything waits: the ones on their way to LDS first (loads return in order, so the
-  // LDS stores wait for those alone), the table entries behind them -- one memory latency for the whole setup.
+  // ---- per-launch setup ----------------------------------------------------------------------------------------------
+  // The workgroup fetches everything ONCE -- the phase entries of the 13 simulated layers (26 KiB, gathered into the
+  // lanes' own order), linear_up's weights and bias, the tangents -- and hands it over through LDS; behind the barrier
+  // every wavefront fills its phase registers from the LDS copy with 16-byte reads.  (Each wavefront used to read the
+  // whole phase table from global memory itself: eight times the bytes through the CU's vector L1, which took longer
+  // than an item's layers.)  Every global load is issued before anything waits.
+  constexpr int kPhEntries = (LPR - 1) * QT::TL;                                  // phase entries of layers 1 .. LPR - 1
+  constexpr int kPhTrips = (kPhEntries + kSoloThreads - 1) / kSoloThreads;
   constexpr int kWTrips = 4 * 1024 / kSoloThreads, kBTrips = 1024 / kSoloThreads;   // Q <= 1024 (the host checks)
+  C phstage[kPhTrips];
   D2 wreg[kWTrips];
   double breg[kBTrips];
 #pragma unroll
+  for (int k = 0; k < kPhTrips; ++k) {
+    // LDS entry e = ((l - 1) * 2 + h) * 128 + lane * 2 + j: register r = 2 h + j of `lane` in layer l
+    // (an entry beyond the table loads entry 0 and is not stored: no branch around a load, which would wait inside)
+    const int e = tid + k * kSoloThreads, ec = e < kPhEntries ? e : 0;
+    const int l = (ec >> 8) + 1, r = ((ec >> 6) & 2) | (ec & 1), ln = (ec >> 1) & 63;
+    phstage[k] = g_ph[l * QT::TL + solo_table_slot(layout_of(l), r, ln)];
+  }
+#pragma unroll
   for (int k = 0; k < kWTrips; ++k) {
-    // (a row's four pairs are 64 contiguous bytes of w_up.  An entry beyond the image loads the last one -- no branch
-    //  around a load, which would wait for the loads before it -- and its pixel is never stored)
+    // (a row's four pairs are 64 contiguous bytes of w_up.  An entry beyond the image loads the last one, and its pixel
+    //  is never stored)
     const int i = tid + k * kSoloThreads;
     wreg[k] = reinterpret_cast<const D2*>(wu)[i < 4 * Q ? i : 4 * Q - 1];
   }
@@ -137,16 +256,16 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
     breg[k] = bu != nullptr ? bu[i < Q ? i : Q - 1] : 0.0;
   }
   const T unreg = g_un[tid < LPR * 8 ? tid : 0];
-  C phr[LPR][4];   // (entry 0 unused: the first layer is generated)
   T a0r[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) a0r[r] = g_a0[r * kWave + lane];
-#pragma unroll
-  for (int l = 1; l < LPR; ++l) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) phr[l][r] = g_ph[l * QT::TL + r * kWave + lane];
-  }
+  for (int r = 0; r < 4; ++r) a0r[r] = g_a0[solo_table_slot(layout_of(1), r, lane)];
   __builtin_amdgcn_sched_barrier(0);   // (all loads are out)
+  stamp(1);
+#pragma unroll
+  for (int k = 0; k < kPhTrips; ++k) {
+    const int e = tid + k * kSoloThreads;
+    if (e < kPhEntries) s_ph[e] = phstage[k];
+  }
 #pragma unroll
   for (int k = 0; k < kWTrips; ++k) {
     const int i = tid + k * kSoloThreads;
@@ -163,6 +282,18 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
 #pragma unroll
   for (int q = 0; q < 4; ++q) pm[q] = ((llane >> q) & 1) ? (T)1 : (T)-1;
   __syncthreads();
+  stamp(2);
+  // this lane's phase entries into registers, for all items of the wave (entry 0 unused: the first layer is generated)
+  C phr[LPR][4];
+#pragma unroll
+  for (int l = 1; l < LPR; ++l) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const V4 v = reinterpret_cast<const V4*>(s_ph)[((l - 1) * 2 + h) * kWave + lane];
+      phr[l][2 * h] = C{v.x, v.y};
+      phr[l][2 * h + 1] = C{v.z, v.w};
+    }
+  }
 
   // ---- the items of this wave ---------------------------------------------------------------------------------------
   const uint32_t n_steps = (uint32_t)d.n_steps;
@@ -172,7 +303,7 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   int64_t sample = (int64_t)(g0 / n_steps);
   uint32_t step = g0 - (g0 / n_steps) * n_steps;
   const int groups = Qp / kWave;
-  for (; sample < p.batch; ) {
+  for (int item = 0; sample < p.batch; ++item) {
     asm volatile("" ::: "memory");   // (the LDS reads below stay inside the loop: hoisted, they would not fit registers)
     C a[4];
 #pragma unroll
@@ -186,10 +317,11 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
       const V4 nlo = un4[2 * ln], nhi = un4[2 * ln + 1];
       __builtin_amdgcn_sched_barrier(0);
       const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
-      solo_layer(a, phr[l], ts, hi.x, hi.y, hi.z, hi.w);
+      solo_layer(layout_of(l), a, phr[l], ts, hi.x, hi.y, hi.z, hi.w);
       lo = nlo;
       hi = nhi;
     }
+    if (item < 2) stamp(3 + 2 * item);
     // ---- <Z_w>: the register-bit wires are signed in-lane sums, the lane-bit wires signed copies of the lane's total ----
     T pw[4];
 #pragma unroll
@@ -223,6 +355,7 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
       o0 += o1;
       if (pix < Q) yrow[pix] = o0;
     }
+    if (item < 2) stamp(4 + 2 * item);
     // next item of this wave
     sample += stride_q;
     step += stride_r;

@@ -1,10 +1,10 @@
 #!/usr/bin/env python
 """Diagnostic: where workgroup 0 of the lean 8-qubit sampler (dense_quad8_kernel) spends the cycles of a step
 (s_memtime stamps of thread 0 in the launch's second step).  Not a timing of the product path.
-Stamps are taken by the four-wave body only.  The one-wavefront-per-item body that float32 QNN_noise(784, 8, 14) runs in
-launches of at least 4 steps or 2 048 items (qsim_lean_solo.h) takes none: its wavefronts run different items side by
-side and no single thread sees a step's phases one after the other.  QIDDM_LEAN_SOLO_MIN_ITEMS=-1 below keeps that instance on the four-wave body, so its
-float32 row describes that body, not the shipped route (tools/ubench/ubench_solo_layer.hip prices the solo layer)."""
+These are the four-wave body's stamps.  The one-wavefront-per-item body that float32 QNN_noise(784, 8, 14) runs in
+launches of at least 4 steps or 1 024 items (qsim_lean_solo.h) has its own, printed by tools/stamp_lean_solo.py.
+QIDDM_LEAN_SOLO_MIN_ITEMS=-1 below keeps that instance on the four-wave body, so its
+float32 row describes that body, not the shipped route."""
 import os, sys
 os.environ["QIDDM_LEAN_SOLO_MIN_ITEMS"] = "-1"
 import torch

@@ -1,4 +1,6 @@
-// ubench_solo_layer.hip -- the layer of the one-wavefront-per-item body (qsim_lean_solo.h: solo_layer, the shipped code)
+// ubench_solo_layer.hip -- the layer of the one-wavefront-per-item body (qsim_lean_solo.h: solo_layer, the shipped code:
+// bits 4..7 as register bits of two alternating layouts, eight swaps per layer) beside the layer it replaced (bits 4 / 5
+// by swap, 2 x 2, swap back per amplitude: solo_layer_swapback below),
 // next to ubench_layer.hip's four-wave layer: 13 layers per "step", s_memtime around `iters` steps, one workgroup of
 // W = 1, 2, 4, 8 wavefronts per CU on all 256 CUs (96 KiB of LDS per workgroup keep a second one off the CU), every
 // wavefront on an item of its own.  Phases in registers, tangents read from LDS one layer ahead, as the kernel does.
@@ -28,6 +30,26 @@ constexpr int kBlocks = 256;
 constexpr int kMaxWaves = 8;
 constexpr size_t kLds = 96 * 1024;
 
+// the layer before the transposing one: one layout (A) throughout, index bits 4 / 5 through ry_t_swap
+__device__ __forceinline__ void solo_layer_swapback(V2<float> (&a)[4], const V2<float> (&ph)[4], const float (&ts)[4],
+                                                    float t4, float t5, float t6, float t7) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float re = fmaf(-ph[r].y, a[r].y, ph[r].x * a[r].x), im = fmaf(ph[r].y, a[r].x, ph[r].x * a[r].y);
+    a[r] = V2<float>{re, im};
+  }
+  solo_ry_dpp4(a, ts[0], ts[1], ts[2], ts[3]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ry_t_swap<5, float>(a[r], t5);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ry_t_swap<4, float>(a[r], t4);
+  solo_ry_reg(a[0], a[1], t6);
+  solo_ry_reg(a[2], a[3], t6);
+  solo_ry_reg(a[0], a[2], t7);
+  solo_ry_reg(a[1], a[3], t7);
+}
+
+template <bool TRANSPOSING>
 __global__ __launch_bounds__(kMaxWaves * 64) void solo_layer_loop(float* out, unsigned long long* ticks, int iters,
                                                                  const float* tab) {
   using T = float;
@@ -63,7 +85,8 @@ __global__ __launch_bounds__(kMaxWaves * 64) void solo_layer_loop(float* out, un
       const v4f nlo = un4[2 * (l + 1)], nhi = un4[2 * (l + 1) + 1];
       __builtin_amdgcn_sched_barrier(0);
       const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
-      solo_layer(a, ph[l], ts, hi.x, hi.y, hi.z, hi.w);
+      if constexpr (TRANSPOSING) solo_layer(l % 2 == 0 ? kSoloLayoutB : kSoloLayoutA, a, ph[l], ts, hi.x, hi.y, hi.z, hi.w);
+      else solo_layer_swapback(a, ph[l], ts, hi.x, hi.y, hi.z, hi.w);
       lo = nlo;
       hi = nhi;
     }
@@ -75,9 +98,10 @@ __global__ __launch_bounds__(kMaxWaves * 64) void solo_layer_loop(float* out, un
   out[(size_t)blockIdx.x * (kMaxWaves * 64) + tid] = (a[0].x + a[1].y) + (a[2].x + a[3].y);
 }
 
+template <bool TRANSPOSING>
 static double run(float* out, unsigned long long* ticks, const float* tab, int iters, int waves) {
   for (int rep = 0; rep < 2; ++rep) {
-    hipLaunchKernelGGL(solo_layer_loop, dim3(kBlocks), dim3(waves * 64), kLds, 0, out, ticks, iters, tab);
+    hipLaunchKernelGGL(solo_layer_loop<TRANSPOSING>, dim3(kBlocks), dim3(waves * 64), kLds, 0, out, ticks, iters, tab);
     CHECK(hipGetLastError());
     CHECK(hipDeviceSynchronize());
   }
@@ -91,8 +115,8 @@ static double run(float* out, unsigned long long* ticks, const float* tab, int i
       mx = v > mx ? v : mx;
     }
   const double per = sum / (kBlocks * waves) / ((double)iters * kLayers);
-  printf("  %d solo wavefront(s) per CU: %7.1f ticks/layer (slowest wavefront %7.1f), %7.1f ticks per item-layer\n", waves,
-         per, mx / ((double)iters * kLayers), per / waves);
+  printf("  %s  %d solo wavefront(s) per CU: %7.1f ticks/layer (slowest wavefront %7.1f), %7.1f ticks per item-layer\n",
+         TRANSPOSING ? "transposing" : "swap-back  ", waves, per, mx / ((double)iters * kLayers), per / waves);
   return per;
 }
 
@@ -105,12 +129,15 @@ int main() {
   std::vector<float> h(512);
   for (int i = 0; i < 512; ++i) h[i] = (float)((i * 2654435761u) % 1000) / 1000.0f;
   CHECK(hipMemcpy(tab, h.data(), 512 * sizeof(float), hipMemcpyHostToDevice));
-  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kLds));
+  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop<false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop<true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
   const int iters = 400;
   for (int rep = 0; rep < 3; ++rep) {
     printf("run %d\n", rep);
-    for (int waves : {1, 2, 4, 8}) run(out, ticks, tab, iters, waves);
+    for (int waves : {1, 2, 4, 8}) run<false>(out, ticks, tab, iters, waves);
+    for (int waves : {1, 2, 4, 8}) run<true>(out, ticks, tab, iters, waves);
   }
   return 0;
 }
