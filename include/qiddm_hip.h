@@ -574,7 +574,19 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *   QIDDM_MIX_GATE            the 2x2 unitary gates[a] = (u00, u01, u10, u11) as (re, im) float64
  *   QIDDM_MIX_CZ / _CNOT      control `wire`, target `a`
  *   QIDDM_MIX_PHASE_DAMP / _AMP_DAMP / _DEPOL   PennyLane's PhaseDamping / AmplitudeDamping /
- *                             DepolarizingChannel with probability p on `wire`
+ *                             DepolarizingChannel on `wire`.  a < 0: the strength is `p`, checked to lie in [0, 1].
+ *                             a >= 0: the strength of sample s is p + scale * angle_rows[a][s], the rule of PHASE / RY
+ *                             (`op %d: angle row %d out of range` when a >= n_rows; p and scale must be finite, else
+ *                             QIDDM_ERR_INVALID "... not finite").  The row is device memory the library does not look
+ *                             into: strengths outside [0, 1] are the caller's responsibility, the kernels do not clamp.
+ *                             The reverse sweeps add scale * dL/dstrength into grad_rows[a][s].  With Lambda the adjoint
+ *                             behind the channel, rho the state in front of it and o = -1 / (2 sqrt(1 - gamma)),
+ *                             dL/dstrength = <Lambda, E'(rho)>, where on each 2 x 2 block M of the wire E'(M) is
+ *                               PHASE_DAMP  M00' = M11' = 0;                       M01' = o M01, M10' = o M10
+ *                               AMP_DAMP    M00' = +M11, M11' = -M11;              M01' = o M01, M10' = o M10
+ *                               DEPOL       M00' = (2/3)(M11 - M00), M11' = -M00'; M01' = -(4/3) M01, M10' = -(4/3) M10
+ *                             At gamma = 1 the derivative of the two damping channels is not finite (PennyLane's is not
+ *                             either); it is not special-cased.  Several channels may read one row: their gradients add.
  *   QIDDM_MIX_CHANNEL (= 16)  a general one-wire channel on `wire`: `a` is the first of FOUR consecutive rows of `gates`,
  *                             rows a .. a+3 hold the superoperator S (4 x 4 complex, row-major; row r = S[r][0..3] as
  *                             (re, im)).  On every 2 x 2 block M of the wire vec(M') = S vec(M), vec(M) = (M00, M01,
@@ -610,7 +622,8 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  * batch / n_ops, measure (batch == 0 then returns QIDDM_OK with no pointer looked at), program (not empty, starts with a
  * state preparation), negative n_rows / n_gates, angle_rows / rows_ld, gates, the ops one by one (kind, wire, target wire
  * or second wire -- `op %d: bad second wire %d` when it is outside 0..n-1 or equal to `wire` --,
- * then the operand they index: features / feat_ld / n_features, angle row, gate, probability, channel rows), max_blocks (negative:
+ * then the operand they index: features / feat_ld / n_features, angle row, gate, probability (a >= 0: angle row, then
+ * finite p / scale), channel rows), max_blocks (negative:
  * refused for an empty batch as well), the outputs
  * (out, out_ld | grad_out / gout_ld, grad_rows, grad_gates, grad_features), workspace.                   */
 enum {
@@ -677,16 +690,21 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
                              int64_t out_ld, void *workspace, int64_t workspace_bytes, void *stream);
 /* Reverse sweep of the tile-fused engine: the exact vector-Jacobian product of qiddm_mixed_wide_forward, with the
  * arguments and gradient layouts of qiddm_mixed_backward (no max_blocks) and its argument checks; 7 <= n_qubits <= 10
- * (else QIDDM_ERR_UNSUPPORTED).  Channel strengths get no gradient.  Ops in front of the last state preparation reach
+ * (else QIDDM_ERR_UNSUPPORTED).  A native channel with a >= 0 gives its row the gradient of its strength (see the kinds);
+ * constant strengths (a < 0) and the general channels' rows get none.  Ops in front of the last state preparation reach
  * no output: only the ops from there on (the LIVE ops) are planned and run, other parameters get a zero gradient.  The
  * live ops are cut into segments that hold either channels only or no channel.  The call
  *   replays     the forward sweeps; a channel segment writes rho to a further slab, so the state in front of it stays
  *               behind as a snapshot (a channel is not inverted).  Channel segments behind the last unitary one are
- *               not replayed.
+ *               not replayed -- except, in a program where such a trailing segment other than the first holds a native
+ *               channel with a >= 0, those in front of the last one that does (its gradient needs the state in front
+ *               of it; the snapshots they add are counted by qiddm_mixed_wide_backward_plan).
  *   walks back  one launch over (tile, sample) per segment, the rho tile and the adjoint's tile side by side in LDS;
  *               the first one generates the adjoint from grad_out.  A unitary un-computes both tiles and writes its
  *               tile partial per (op, tile, sample); a channel segment applies E^dagger to the adjoint and rho steps
- *               back to the snapshot.  AMP_EMBED: a matrix-vector pass over the adjoint's slab.
+ *               back to the snapshot; one that holds a native channel with a >= 0 keeps the rho tile in front of each
+ *               such channel beside the adjoint's (the snapshot's tile with the segment's earlier ops applied again)
+ *               and writes a tile partial of <Lambda, E'(rho)>.  AMP_EMBED: a matrix-vector pass over the adjoint's slab.
  *   finalizes   the tile partials, summed in a fixed order per parameter and sample.
  * No atomics: reruns are bit-identical and the gradients do not depend on the chunking.
  *   qiddm_mixed_wide_backward_plan             host only: sweeps of the replay, launches of the walk back, snapshots.
@@ -695,7 +713,7 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
  *                                              head = live ops * 32 + live ops * 4 + gradient ops * 24 + (parameter
  *                                              groups + 1) * 4; per_sample = 8 (1 + 2^n) + 8 * slots * 2^(2n-12) +
  *                                              (2 + snapshots) slabs, slots = 8 per live GATE + 1 per live PHASE / RY
- *                                              with a >= 0.  resident = min(batch, 1 GiB / per_sample), at least 1;
+ *                                              / native channel with a >= 0 (gradient ops: the same ops).  resident = min(batch, 1 GiB / per_sample), at least 1;
  *                                              larger batches run in chunks inside the call.  `program` is required.
  *   qiddm_mixed_wide_backward                  also accepts a smaller workspace, down to head + per_sample.          */
 int64_t qiddm_mixed_wide_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch,

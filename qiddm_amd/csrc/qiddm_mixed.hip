@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 #include <type_traits>
@@ -58,6 +59,10 @@ inline int program_level(const qiddm_mixed_op_t* program, int32_t n_ops) {
 inline bool is_channel(int kind) {
   return kind == qiddm::kMixPhaseDamp || kind == qiddm::kMixAmpDamp || kind == qiddm::kMixDepol ||
          kind == qiddm::kMixChannel || kind == qiddm::kMixChannel2;
+}
+// a native channel that reads its strength from an angle row: the reverse sweeps give that row a gradient
+inline bool is_graded(const qiddm_mixed_op_t& op) {
+  return (op.kind == qiddm::kMixPhaseDamp || op.kind == qiddm::kMixAmpDamp || op.kind == qiddm::kMixDepol) && op.a >= 0;
 }
 
 // ---- argument checks ---------------------------------------------------------------------------------------------------
@@ -162,8 +167,14 @@ int check_call(const MixedCall& c, const Engine& e, bool* embeds) {
       case qiddm::kMixPhaseDamp:
       case qiddm::kMixAmpDamp:
       case qiddm::kMixDepol:
-        if (!(op.p >= 0.0 && op.p <= 1.0))
-          return fail(QIDDM_ERR_INVALID, "op %d: channel probability %g outside [0, 1]", i, op.p);
+        if (op.a < 0) {
+          if (!(op.p >= 0.0 && op.p <= 1.0))
+            return fail(QIDDM_ERR_INVALID, "op %d: channel probability %g outside [0, 1]", i, op.p);
+        } else {  // the strength is p + scale * angle_rows[a][sample]: device memory, out of the library's sight
+          if (op.a >= c.n_rows) return fail(QIDDM_ERR_INVALID, "op %d: angle row %d out of range", i, op.a);
+          if (!std::isfinite(op.p) || !std::isfinite(op.scale))
+            return fail(QIDDM_ERR_INVALID, "op %d: channel strength p = %g, scale = %g not finite", i, op.p, op.scale);
+        }
         break;
       case qiddm::kMixChannel:  // four rows of gates; what they hold is device memory, out of the library's sight
         if (op.a < 0 || (int64_t)op.a + 3 >= c.n_gates)
@@ -440,6 +451,7 @@ struct WideBwdPlan {
   int32_t n_snaps = 0;                    // channel segments among them
   int32_t n_slots = 0;                    // tile partials per (tile, sample)
   bool embed_live = false;
+  std::vector<char> seg_graded;           // the (channel) segment holds a native channel with a >= 0
   std::vector<int32_t> slot;              // per sorted live op, -1: no gradient
   std::vector<qiddm::WideParam> params;   // grouped by the parameter they feed, program order within a group
   std::vector<int32_t> group_begin;       // n_groups + 1
@@ -457,6 +469,16 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
   const int n_seg = (int)bp->plan.segments.size();
   bp->replay_end = n_seg;
   while (bp->replay_end > 0 && bp->plan.seg_channel[bp->replay_end - 1]) --bp->replay_end;
+  // A segment with a graded channel needs the state in front of it.  A trailing segment reads the last replayed set, so
+  // the replay goes on up to the last trailing segment that holds one (programs without a graded channel: as before).
+  bp->seg_graded.assign(n_seg, 0);
+  for (int i = 0; i < bp->n_live; ++i)
+    if (is_graded(live[i])) bp->seg_graded[bp->plan.op_segment[i]] = 1;
+  for (int s = n_seg - 1; s > bp->replay_end; --s)
+    if (bp->seg_graded[s]) {
+      bp->replay_end = s;
+      break;
+    }
   bp->n_snaps = 0;
   for (int s = 0; s < bp->replay_end; ++s) bp->n_snaps += bp->plan.seg_channel[s];
   bp->embed_live = live[0].kind == qiddm::kMixAmpEmbed;
@@ -466,7 +488,7 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
   for (int i = 0; i < bp->n_live; ++i) {
     const qiddm_mixed_op_t& op = live[bp->plan.order[i]];
     const bool gate = op.kind == qiddm::kMixGate;
-    if (!gate && !((op.kind == qiddm::kMixPhase || op.kind == qiddm::kMixRY) && op.a >= 0)) continue;
+    if (!gate && !((op.kind == qiddm::kMixPhase || op.kind == qiddm::kMixRY) && op.a >= 0) && !is_graded(op)) continue;
     bp->slot[i] = bp->n_slots;
     bp->n_slots += gate ? 8 : 1;
     keyed.push_back({((int64_t)(gate ? 1 : 0) << 32) | (uint32_t)op.a, i});
@@ -559,6 +581,15 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
                                                         "mixed_wide_reverse_sweep", prog, slot, c.angle_rows, c.gates, grad_out,
                                                         slabs + (size_t)cur * set_stride, lam, partials, m,
                                                         bp.plan.segments[s], bs, s0);
+      } else if (bp.seg_graded[s]) {
+        // the state in front of the segment: the set below the one it wrote, or (not replayed) the last replayed set
+        const C* front = slabs + (size_t)(s < bp.replay_end ? cur - 1 : cur) * set_stride;
+        rc = for_level(bp.plan.seg_level[s], [&](auto level) {
+          return launch<qiddm::mixed_wide_adjoint_channels_graded<T, decltype(level)::value>>(
+              2 * tile_bytes, dim3(tiles, chunk), block, 2 * tile_bytes, st, "mixed_wide_adjoint_channels_graded", prog, slot,
+              c.angle_rows, c.gates, grad_out, front, lam, partials, m, bp.plan.segments[s], bs, s0);
+        });
+        if (s < bp.replay_end) --cur;
       } else {
         rc = for_level(bp.plan.seg_level[s], [&](auto level) {
           return launch<qiddm::mixed_wide_adjoint_channels<T, decltype(level)::value>>(

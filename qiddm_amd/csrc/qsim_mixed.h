@@ -37,9 +37,9 @@ enum MixedKind : int32_t {
   kMixGate,         // fixed unitary gates[a]
   kMixCZ,           // control wire, target a
   kMixCNOT,         // control wire, target a
-  kMixPhaseDamp,    // p = gamma
-  kMixAmpDamp,      // p = gamma
-  kMixDepol,        // p
+  kMixPhaseDamp,    // gamma = p, or with a >= 0 p + scale * angle_rows[a][sample] (not clamped; the row gets a gradient)
+  kMixAmpDamp,      // gamma likewise
+  kMixDepol,        // p likewise
   kMixChannel = 16, // general one-wire channel: gates[a .. a+3] are the rows of the 4 x 4 superoperator S (10..15: no kind)
   kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..31: no kind)
 };
@@ -185,18 +185,47 @@ template <typename T>
 struct MixedChannel {
   T off, d_own, d_other_to_0, d_other_to_1, d11;
 };
+// `p`: the strength of this sample, mixed_angle(op, ...) -- op.p, or with a >= 0 op.p + op.scale * angle_rows[a][sample]
 template <typename T>
-__device__ __forceinline__ MixedChannel<T> mixed_channel(const MixedOp& op) {
+__device__ __forceinline__ MixedChannel<T> mixed_channel(int kind, double p) {
   MixedChannel<T> c;
-  if (op.kind == kMixPhaseDamp) {
-    c.off = (T)sqrt(1.0 - op.p); c.d_own = 1; c.d11 = 1; c.d_other_to_0 = 0; c.d_other_to_1 = 0;
-  } else if (op.kind == kMixAmpDamp) {
-    c.off = (T)sqrt(1.0 - op.p); c.d_own = 1; c.d11 = (T)(1.0 - op.p); c.d_other_to_0 = (T)op.p; c.d_other_to_1 = 0;
+  if (kind == kMixPhaseDamp) {
+    c.off = (T)sqrt(1.0 - p); c.d_own = 1; c.d11 = 1; c.d_other_to_0 = 0; c.d_other_to_1 = 0;
+  } else if (kind == kMixAmpDamp) {
+    c.off = (T)sqrt(1.0 - p); c.d_own = 1; c.d11 = (T)(1.0 - p); c.d_other_to_0 = (T)p; c.d_other_to_1 = 0;
   } else {
-    c.off = (T)(1.0 - 4.0 * op.p / 3.0); c.d_own = (T)(1.0 - 2.0 * op.p / 3.0); c.d11 = c.d_own;
-    c.d_other_to_0 = (T)(2.0 * op.p / 3.0); c.d_other_to_1 = c.d_other_to_0;
+    c.off = (T)(1.0 - 4.0 * p / 3.0); c.d_own = (T)(1.0 - 2.0 * p / 3.0); c.d11 = c.d_own;
+    c.d_other_to_0 = (T)(2.0 * p / 3.0); c.d_other_to_1 = c.d_other_to_0;
   }
   return c;
+}
+// ---- dL/dstrength of a native channel with a >= 0 (the reverse sweeps) -------------------------------------------------
+// With Lambda the adjoint behind the channel and rho the state in front of it, dL/dstrength = <Lambda, E'(rho)> =
+// sum over the wire's blocks of Re sum_xy conj(L_xy) E'(M)_xy, and E'(M) is
+//     PhaseDamping(g):      M01, M10 -> o M01, o M10,  o = -1 / (2 sqrt(1-g));  M00, M11 -> 0
+//     AmplitudeDamping(g):  M00 -> +M11, M11 -> -M11;  off-diagonals as PhaseDamping (not finite at g = 1, as PennyLane's)
+//     Depolarizing(p):      M00 -> (2/3)(M11 - M00), M11 -> (2/3)(M00 - M11);  M01, M10 -> -(4/3) M01, -(4/3) M10
+// The products are taken in double whatever T is: one sum per (op, sample) feeds the gradient.
+__device__ __forceinline__ double mixed_channel_doff(int kind, double p) {  // d(off-diagonal factor)/dstrength
+  return kind == kMixDepol ? -4.0 / 3.0 : -0.5 / sqrt(1.0 - p);
+}
+template <typename T>
+__device__ __forceinline__ double mixed_re_dot(V2<T> l, V2<T> r) {  // Re(conj(l) r)
+  return (double)l.x * (double)r.x + (double)l.y * (double)r.y;
+}
+// the off-diagonal elements' share, still to be multiplied by mixed_channel_doff
+template <typename T>
+__device__ __forceinline__ double mixed_strength_grad_off(V2<T> r01, V2<T> r10, V2<T> l01, V2<T> l10) {
+  return mixed_re_dot<T>(l01, r01) + mixed_re_dot<T>(l10, r10);
+}
+// the diagonal elements' share (AmplitudeDamping, Depolarizing; PhaseDamping has none)
+template <typename T>
+__device__ __forceinline__ double mixed_strength_grad_diag(int kind, V2<T> r00, V2<T> r11, V2<T> l00, V2<T> l11) {
+  const double lx = (double)l00.x - (double)l11.x, ly = (double)l00.y - (double)l11.y;
+  if (kind == kMixAmpDamp) return lx * (double)r11.x + ly * (double)r11.y;
+  if (kind == kMixDepol)
+    return (2.0 / 3.0) * (lx * ((double)r11.x - (double)r00.x) + ly * ((double)r11.y - (double)r00.y));
+  return 0.0;
 }
 template <typename T>
 __device__ __forceinline__ void mixed_block_channel(const MixedChannel<T>& c, V2<T>& m00, V2<T>& m01, V2<T>& m10, V2<T>& m11) {
@@ -506,7 +535,7 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
     case kMixPhaseDamp:
     case kMixAmpDamp:
     case kMixDepol: {
-      const MixedChannel<T> ch = mixed_channel<T>(op);
+      const MixedChannel<T> ch = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample));
       for (uint32_t t = tid; t < DD / 4; t += 256) {
         const uint32_t base = insert_two_bits(t, q, q + n);
         const uint32_t cj = 1u << q, ci = 1u << (q + n);
@@ -595,7 +624,8 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
 //         rho, Lambda <- U^dagger B U  (one pass over both)
 //     CZ / CNOT: applied to both (involutions)
 //     channel E: Lambda <- E^dagger(Lambda) (the general channel: S^H on vec of each block), rho <- snapshot (a channel is not inverted: Depolarizing(0.9) has
-//         condition number 5 per wire)
+//         condition number 5 per wire).  A native channel with a >= 0 (strength from a row) first reduces
+//         dL/dstrength = <Lambda, E'(snapshot)> over the wire's blocks, like RY its Im Tr(G N)
 //     AMP_EMBED: rho_0 = v v^T / |v|^2, dL/dv = 2 (Re(Lambda) v - (v^T Re(Lambda) v / |v|^2) v) / |v|^2
 // Gradients go to per-sample double outputs (no atomics): every reduction runs in a fixed order, so reruns are
 // bit-identical.  Thread 0 adds each parameter's reduced value after the op's barrier.
@@ -679,7 +709,9 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
     for (int oi = m.n_ops - 1; oi >= 0; --oi) {
       const MixedOp op = prog[oi];
       const int q = n - 1 - op.wire;
-      const bool param = op.kind == kMixPhase || op.kind == kMixRY || op.kind == kMixGate;
+      // a native channel that reads its strength from a row feeds that row like an angle op
+      const bool graded = (op.kind == kMixPhaseDamp || op.kind == kMixAmpDamp || op.kind == kMixDepol) && op.a >= 0;
+      const bool param = op.kind == kMixPhase || op.kind == kMixRY || op.kind == kMixGate || graded;
       switch (op.kind) {
         case kMixPhase:
         case kMixRY:
@@ -765,21 +797,32 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
         case kMixPhaseDamp:
         case kMixAmpDamp:
         case kMixDepol: {
-          const MixedChannel<T> ch = mixed_channel<T>(op);
+          const double strength = mixed_angle(op, angle_rows, m, sample);
+          const MixedChannel<T> ch = mixed_channel<T>(op.kind, strength);
           const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
+          double acc_off = 0.0, acc_diag = 0.0;  // a >= 0: <Lambda behind the channel, E'(rho in front of it)>
           for (uint32_t t = tid; t < DD / 4; t += 256) {
             const uint32_t base = insert_two_bits(t, q, q + n);
             const uint32_t cj = 1u << q, ci = 1u << (q + n);
             C l00 = lam[base], l01 = lam[base | cj], l10 = lam[base | ci], l11 = lam[base | ci | cj];
+            const C r00 = sp[base], r01 = sp[base | cj], r10 = sp[base | ci], r11 = sp[base | ci | cj];
+            if (graded) {
+              acc_off += mixed_strength_grad_off<T>(r01, r10, l01, l10);
+              acc_diag += mixed_strength_grad_diag<T>(op.kind, r00, r11, l00, l11);
+            }
             mixed_block_channel_adjoint<T>(ch, l00, l01, l10, l11);
             lam[base] = l00;
             lam[base | ci | cj] = l11;
             lam[base | cj] = l01;
             lam[base | ci] = l10;
-            rho[base] = sp[base];
-            rho[base | cj] = sp[base | cj];
-            rho[base | ci] = sp[base | ci];
-            rho[base | ci | cj] = sp[base | ci | cj];
+            rho[base] = r00;
+            rho[base | cj] = r01;
+            rho[base | ci] = r10;
+            rho[base | ci | cj] = r11;
+          }
+          if (graded) {
+            const double s = mixed_wave_sum(mixed_channel_doff(op.kind, strength) * acc_off + acc_diag);
+            if (lane == 0) s_part[buf][wave][0] = s;
           }
           break;
         }

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         break;
       }
       case kMixPhaseDamp: {
-        const T off = mixed_channel<T>(op).off;
+        const T off = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample)).off;
 #pragma unroll
         for (int i = 0; i < kWidePairs; ++i) {
           const uint32_t l = 2u * (tid + 256u * i);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         MixedU<T> u{};
         MixedChannel<T> ch{};
         if (unitary) u = mixed_unitary<T>(op, angle_rows, gates, m, sample);
-        else ch = mixed_channel<T>(op);
+        else ch = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample));
 #pragma unroll
         for (int i = 0; i < kWideBlocks; ++i) {
           const uint32_t l = insert_two_bits(tid + 256u * i, a, b);

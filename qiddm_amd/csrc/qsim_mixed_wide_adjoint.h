@@ -13,6 +13,11 @@
 //               backwards: U^dagger . U on both, N = sum B_rho B_Lambda^dagger of the tile in double -> one partial per
 //               (slot, tile, sample).  PHASE is element-wise on any wire.
 //             channel segment: mixed_wide_adjoint_channels applies E^dagger to the Lambda tile; rho steps back one set.
+//               A segment with a native channel whose strength comes from a row (a >= 0) runs
+//               mixed_wide_adjoint_channels_graded instead: it also holds the rho tile in front of each such channel
+//               and writes the tile partial of dL/dstrength = <Lambda, E'(rho)> to the channel's slot.  A trailing
+//               segment reads the last replayed set as its snapshot, so the host replays up to the last trailing
+//               segment that holds such a channel (only programs with one are planned differently).
 //             The first reverse launch generates Lambda_N from grad_out instead of reading it.
 //   AMP_EMBED dL/dv from Re(Lambda_0) v: a matrix-vector pass over Lambda's slab, then one workgroup per sample.
 //   finalize  a wave per parameter (angle row / gate) and sample sums the tile partials in a fixed order: no atomics,
@@ -288,7 +293,7 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp
       }
       continue;
     }
-    const MixedChannel<T> ch = mixed_channel<T>(op);
+    const MixedChannel<T> ch = mixed_channel<T>(op.kind, op.p);  // a < 0 throughout: the host sends other segments below
     if (diag) {
 #pragma unroll
       for (int i = 0; i < kWidePairs; ++i) {
@@ -312,6 +317,146 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp
     }
   }
   if (!owned) __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i) {
+    const uint32_t l = 2u * (tid + 256u * i);
+    *reinterpret_cast<V4<T>*>(lam + kown[i]) = *reinterpret_cast<const V4<T>*>(lt + l);
+  }
+}
+
+// One op of a channel segment on a tile in LDS, with this sample's strength: E, or with ADJOINT E^dagger (the
+// arithmetic of mixed_wide_sweep and of mixed_wide_adjoint_channels).  The caller puts a barrier between two ops.
+template <typename T, int LEVEL, bool ADJOINT>
+__device__ __forceinline__ void wide_channel_op(const MixedOp& op, V2<T>* tile, const uint32_t (&kown)[kWidePairs],
+                                                const double* __restrict__ angle_rows, const double* __restrict__ gates,
+                                                const MixedScalars& m, const WideSegment& sg, int64_t sample) {
+  using C = V2<T>;
+  const int n = m.n, tid = threadIdx.x, q = n - 1 - op.wire;
+  if constexpr (LEVEL >= kLevelChannel2) {
+    if (op.kind == kMixChannel2) {
+      const int q2 = n - 1 - op.wire2;
+      const MixedBlock2 bl = mixed_block2(wide_local_rank(sg, q), wide_local_rank(sg, q2), wide_local_rank(sg, q + n),
+                                          wide_local_rank(sg, q2 + n));
+      const auto su = mixed_super2<T>(op, gates);
+      for (uint32_t t = tid; t < kWideTile / 16; t += 256) mixed_block_super2<T, ADJOINT>(su, tile, nullptr, mixed_block2_base(t, bl), bl);
+      return;
+    }
+  }
+  if (op.kind == kMixPhaseDamp) {  // element-wise on any wire; E^dagger = E
+    const T off = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample)).off;
+#pragma unroll
+    for (int i = 0; i < kWidePairs; ++i) {
+      const uint32_t l = 2u * (tid + 256u * i);
+      tile[l] = mixed_phase_damp_elem<T>(tile[l], kown[i], q, n, off);
+      tile[l + 1] = mixed_phase_damp_elem<T>(tile[l + 1], kown[i] + 1u, q, n, off);
+    }
+    return;
+  }
+  const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
+  const uint32_t cj = 1u << a, ci = 1u << bb;
+  const bool general = LEVEL >= kLevelChannel && op.kind == kMixChannel;
+  MixedSuper<T> su{};
+  MixedChannel<T> ch{};
+  if constexpr (LEVEL >= kLevelChannel) {
+    if (general) su = mixed_super<T>(op, gates);
+  }
+  if (!general) ch = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample));
+#pragma unroll
+  for (int i = 0; i < kWideBlocks; ++i) {
+    const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
+    C m00 = tile[l], m01 = tile[l | cj], m10 = tile[l | ci], m11 = tile[l | ci | cj];
+    if constexpr (LEVEL >= kLevelChannel) {
+      if (general) {
+        if (ADJOINT) mixed_block_super_adjoint<T>(su, m00, m01, m10, m11);
+        else mixed_block_super<T>(su, m00, m01, m10, m11);
+      }
+    }
+    if (!general) {
+      if (ADJOINT) mixed_block_channel_adjoint<T>(ch, m00, m01, m10, m11);
+      else mixed_block_channel<T>(ch, m00, m01, m10, m11);
+    }
+    tile[l] = m00;
+    tile[l | cj] = m01;
+    tile[l | ci] = m10;
+    tile[l | ci | cj] = m11;
+  }
+}
+
+// A channel segment that holds a native channel with a >= 0 (strength from a row), backwards: as
+// mixed_wide_adjoint_channels on the Lambda tile, with the rho tile beside it in LDS as in mixed_wide_reverse_sweep.
+// `rho_slabs` is the state in front of the SEGMENT (its snapshot; read only).  In front of each graded channel (slot[oi]
+// >= 0) the rho tile is loaded again and the segment's earlier ops applied to it -- quadratic in the segment's channels,
+// which are few, and all in LDS --, then <Lambda, E'(rho)> of the tile goes to partials[(resident * n_slots + slot) *
+// tiles + tile]: per thread in double in a fixed order, across the wave, then the four waves in order.
+template <typename T, int LEVEL>
+__global__ __launch_bounds__(256) void mixed_wide_adjoint_channels_graded(
+    const MixedOp* __restrict__ prog, const int32_t* __restrict__ slot, const double* __restrict__ angle_rows,
+    const double* __restrict__ gates, const double* __restrict__ grad_out, const V2<T>* __restrict__ rho_slabs,
+    V2<T>* __restrict__ lam_slabs, double* __restrict__ partials, const MixedScalars m, const WideSegment sg,
+    const WideBwdScalars b, int64_t sample0) {
+  using C = V2<T>;
+  extern __shared__ __attribute__((aligned(32))) unsigned char smem_raw[];
+  __shared__ uint32_t s_lo[64], s_hi[64];
+  __shared__ double s_part[2][4];
+  C* lt = reinterpret_cast<C*>(smem_raw);
+  C* rt = lt + kWideTile;
+  const int n = m.n, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t resident = blockIdx.y, sample = sample0 + resident;
+  const C* __restrict__ rho = rho_slabs + ((size_t)resident << (2 * n));
+  C* __restrict__ lam = lam_slabs + ((size_t)resident << (2 * n));
+  uint32_t kown[kWidePairs];
+  wide_owned_indices(sg, s_lo, s_hi, kown);
+  wide_load_lambda<T>(lt, lam, kown, grad_out + sample * b.gout_ld, m, b.seed != 0);
+  __syncthreads();
+
+  double* __restrict__ part = partials + (size_t)resident * b.n_slots * gridDim.x + blockIdx.x;
+  int buf = 0;
+  for (int oi = sg.op_end - 1; oi >= sg.op_begin; --oi) {
+    const MixedOp op = prog[oi];
+    const int sl = slot[oi];
+    if (sl >= 0) {  // uniform over the workgroup
+#pragma unroll
+      for (int i = 0; i < kWidePairs; ++i) {
+        const uint32_t l = 2u * (tid + 256u * i);
+        *reinterpret_cast<V4<T>*>(rt + l) = *reinterpret_cast<const V4<T>*>(rho + kown[i]);
+      }
+      for (int oj = sg.op_begin; oj < oi; ++oj) {
+        __syncthreads();
+        wide_channel_op<T, LEVEL, false>(prog[oj], rt, kown, angle_rows, gates, m, sg, sample);
+      }
+      __syncthreads();
+      const int q = n - 1 - op.wire;
+      const double strength = mixed_angle(op, angle_rows, m, sample);
+      double acc_off = 0.0, acc_diag = 0.0;
+      if (op.kind == kMixPhaseDamp) {  // any wire: the off-diagonal elements of its blocks among the owned ones
+#pragma unroll
+        for (int i = 0; i < kWidePairs; ++i) {
+          const uint32_t l = 2u * (tid + 256u * i);
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const uint32_t k = kown[i] + e;
+            if (((k >> (q + n)) ^ (k >> q)) & 1u) acc_off += mixed_re_dot<T>(lt[l + e], rt[l + e]);
+          }
+        }
+      } else {
+        const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
+        const uint32_t cj = 1u << a, ci = 1u << bb;
+#pragma unroll
+        for (int i = 0; i < kWideBlocks; ++i) {
+          const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
+          acc_off += mixed_strength_grad_off<T>(rt[l | cj], rt[l | ci], lt[l | cj], lt[l | ci]);
+          acc_diag += mixed_strength_grad_diag<T>(op.kind, rt[l], rt[l | ci | cj], lt[l], lt[l | ci | cj]);
+        }
+      }
+      const double s = mixed_wave_sum(mixed_channel_doff(op.kind, strength) * acc_off + acc_diag);
+      if (lane == 0) s_part[buf][wave] = s;
+      __syncthreads();
+      if (tid == 0) part[(size_t)sl * gridDim.x] = s_part[buf][0] + s_part[buf][1] + s_part[buf][2] + s_part[buf][3];
+      buf ^= 1;
+    }
+    wide_channel_op<T, LEVEL, true>(op, lt, kown, angle_rows, gates, m, sg, sample);
+    __syncthreads();
+  }
 #pragma unroll
   for (int i = 0; i < kWidePairs; ++i) {
     const uint32_t l = 2u * (tid + 256u * i);

@@ -13,9 +13,18 @@ With grad mode on and an input that requires grad, the launch is one ``torch.aut
 ``qiddm_mixed_backward``: a reverse sweep over the same program that gives the exact gradient with respect to the
 angle rows, the SEL rotation matrices and the amplitude-embedding features (PennyLane trains such QNodes with backprop
 or parameter-shift; both give this gradient).  Autograd carries it on through the stacked rows, ``rot_matrices`` and
-whatever weight map the circuit applied.  Channel strengths get no gradient.
+whatever weight map the circuit applied.
 
-PhaseDamping, AmplitudeDamping and DepolarizingChannel are native ops of the kernels.  Every other one-wire channel of
+PhaseDamping, AmplitudeDamping and DepolarizingChannel are native ops of the kernels.  Their strength is a Python float
+(baked into the program) or a tensor on the GPU, which travels as an angle row does: a 0-d tensor is one strength for the
+batch, a 1-D tensor one per sample (the study's ten intensities over the same inputs are one batch), and a strength
+that requires grad gets its gradient from the same reverse sweeps -- dL/dstrength = <Lambda, E'(rho)> where the
+adjoint and the snapshot meet at the channel -- so a noise model can be fitted to measured read-outs.  Tensor strengths
+are checked once per ``execute`` on the host (outside [0, 1] or NaN: ``ValueError``); at gamma = 1 the derivative of the
+two damping channels is not finite, as in PennyLane.  The general ops below get no gradient for their strengths or Kraus
+entries and take no per-sample strengths.
+
+Every other one-wire channel of
 ``qiddm_amd.qml`` (BitFlip, PhaseFlip, PauliError, GeneralizedAmplitudeDamping, ResetError, ThermalRelaxationError,
 QubitChannel) is lowered to ``QIDDM_MIX_CHANNEL``: its 4 x 4 superoperator S = sum_k K_k (x) conj(K_k), worked out here
 on the host in float64 (``channel_kraus``, ``channel_rows``, ``superoperator``), travels as four rows of ``gates``.
@@ -262,6 +271,7 @@ class _Lowering:
         self.batch, self.batched = None, False
         self.features, self.pad_with = None, 0.0
         self.device = None
+        self.strengths = []  # (row, parameter name) of every native channel whose strength is a tensor
 
     def _see(self, t):
         if torch.is_tensor(t):
@@ -275,13 +285,15 @@ class _Lowering:
         elif self.batch != b:
             raise ValueError(f"inconsistent batch sizes in one circuit: {self.batch} vs {b}")
 
-    def angle(self, value):
-        """-> (row index or -1, constant)"""
+    def angle(self, value, shared=False):
+        """-> (row index or -1, constant).  `shared` (channel strengths): a 0-d tensor is one value for the whole batch,
+        whatever the batch is, and says nothing about it."""
         if not torch.is_tensor(value):
             return -1, float(value)
         self._see(value)
         if value.dim() == 0:
-            self._note_batch(1, False)
+            if not shared:
+                self._note_batch(1, False)
             self.rows.append(value.reshape(1))
         elif value.dim() == 1:
             self._note_batch(value.shape[0], True)
@@ -369,7 +381,11 @@ def lower(tape, ret, n):
                 low.op(_capi.MIX_CZ if t.name == "CZ" else _capi.MIX_CNOT, t.wires[0], t.wires[1])
             elif t.name in CHANNELS:
                 p = t.params[0]
-                if general_channels:
+                if torch.is_tensor(p):  # a row like an angle: per sample, differentiable; native whatever general_channels is
+                    row, const = low.angle(p, shared=True)
+                    low.strengths.append((row, "p" if t.name == "DepolarizingChannel" else "gamma"))
+                    low.op(CHANNELS[t.name], t.wires[0], row, const)
+                elif general_channels:
                     low.channel(channel_rows(t.name, float(p)), t.wires[0])
                 else:
                     low.op(CHANNELS[t.name], t.wires[0], -1, float(p))
@@ -489,6 +505,16 @@ def _gates_on(device, parts):
     return torch.cat(parts).contiguous()
 
 
+def _check_strengths(rows, strengths):
+    """The kernels do not clamp a strength read from a row: one host-side look (one synchronisation) at all of them per
+    ``execute``; a value outside [0, 1] or NaN raises in the words of ``_prob``."""
+    s = rows.detach()[[row for row, _ in strengths]]
+    bad = ~((s >= 0.0) & (s <= 1.0))
+    if bool(bad.any()):
+        i, j = (int(v) for v in bad.nonzero()[0])
+        _prob(strengths[i][1], s[i, j])
+
+
 def execute(tape, ret, n, precision=None, _engine=None):
     """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)``
     (or the unbatched row), as ``default.mixed`` does.  Up to 8 wires: differentiable when grad mode is on and an input
@@ -515,7 +541,9 @@ def execute(tape, ret, n, precision=None, _engine=None):
     launch = _Launch(low, measure, n, prec, device, batch)
     f64 = dict(dtype=torch.float64, device=device)
     rows = torch.stack([r.to(**f64).expand(batch) for r in low.rows]).contiguous() if low.rows else None
-    gates = _gates_on(device, low.gates) if low.gates else None
+    if low.strengths:
+        _check_strengths(rows, low.strengths)
+    gates =_gates_on(device, low.gates) if low.gates else None
     feats = low.features.to(**f64).contiguous() if low.features is not None else None
     if feats is not None and feats.shape[0] != batch:
         feats = feats.expand(batch, -1).contiguous()

@@ -122,6 +122,8 @@ class StronglyEntanglingLayers:
 
 
 def _channel(name):
+    # `p`: a Python / NumPy float, or a tensor on the GPU -- 0-d: one strength for the batch, 1-D: one per sample; a tensor
+    # that requires grad gets its gradient (qiddm_amd.mixed)
     def make(p, wires):
         return _Op(name, wires, (p,), channel=True)
     make.__name__ = name
@@ -154,6 +156,11 @@ def _general_channel(name, wires, params, rows_of, two_wires=False):
 
 
 def _named_channel(name, wires, *params):
+    for p in params:
+        if getattr(p, "ndim", 0) >= 1:  # a 1-D tensor or array: one strength per sample
+            raise NotImplementedError(
+                f"{name}: per-sample (1-D) strengths exist for the three native channels only (PhaseDamping, "
+                "AmplitudeDamping, DepolarizingChannel); this channel takes floats and 0-d tensors")
     return _general_channel(name, wires, params, lambda mixed: mixed.channel_rows(name, *params))
 
 
@@ -250,7 +257,9 @@ def device(name, wires=1, **kwargs):
     """``qml.device(name, wires=n)``.  Every pure-state device name the reference uses maps
     to the HIP statevector engine; ``default.mixed`` (the noise scripts create it,
     src/mnist_noise.py:223) maps to the density-matrix kernels (``qiddm_amd.mixed``: n <= 8 differentiable by a reverse sweep;
-    n = 9, 10 after ``mixed.set_max_wires``, differentiable after ``mixed.set_max_grad_wires``)."""
+    n = 9, 10 after ``mixed.set_max_wires``, differentiable after ``mixed.set_max_grad_wires``).  There
+    ``PhaseDamping`` / ``AmplitudeDamping`` / ``DepolarizingChannel`` take a float or a GPU tensor as strength: 0-d for
+    the batch, 1-D per sample, differentiable when it requires grad."""
     return Device(name, wires, **kwargs)
 
 
