@@ -44,6 +44,13 @@
  *       StronglyEntanglingLayers(angles[round][block] : (sel_layers, n, 3), imprimitive)
  *     out <- probs (B, 2^n)  |  <Z_i> (B, n)
  *     x   <- out[:, 0:n]     (input of the next round)
+ *
+ * Amplitude embedding, edge rows.  Every engine divides the padded row by its L2 norm, always: a row that already
+ * has unit norm is divided by 1 and its grad_inputs carries the projection term of the normalisation (PennyLane
+ * skips the division within 1e-10 of unit norm, and its gradient then has no such term; the outputs agree).
+ * A row whose padded norm is zero (all features + enc_offset zero and nothing padded, or pad_with = 0; PennyLane
+ * raises for it) is not an error here: its output row and its grad_inputs row are NaN (0 * 1/sqrt(0)), no other
+ * sample's output or grad_inputs row is affected, and the weight gradients, being sums over the batch, are NaN too.
  */
 #ifndef QIDDM_HIP_H
 #define QIDDM_HIP_H

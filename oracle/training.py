@@ -12,21 +12,24 @@ from . import circuits as oc
 from . import diffusion as odf
 
 
-def dense_step(kind, sd, x, noise, T, shape, goal, detach):
+def dense_step(kind, sd, x, noise, T, shape, goal, detach, h_hook=None):
     """Loss, parameter gradients and reconstruction of one ``Diffusion`` training step of ``QNN_noise``
     (``kind == "qnn"``) or ``QIDDM_LL_noise`` (``"ll"``) by autograd through the oracle.  ``sd`` holds the net's
-    parameters under their module names; ``detach`` cuts the gradient through the circuit (``detach_quantum``)."""
+    parameters under their module names; ``detach`` cuts the gradient through the circuit (``detach_quantum``);
+    ``h_hook`` edits the circuit's data angles ``h = W_down x + b_down`` (margin checks of the reference itself)."""
     prm = {k: v.detach().cpu().double().clone().requires_grad_(True) for k, v in sd.items()}
 
     def net(t):
         if kind == "qnn":
             w = prm["weights"]
             xr = t.reshape(t.shape[0], -1) @ prm["linear_down.weight"].T + prm["linear_down.bias"]
+            xr = xr if h_hook is None else h_hook(xr)
             ev = oc.run_round(oc.Spec(n=w.shape[1], encoding="rz", imprimitive="CZ", measure="expz"), xr,
                               w.unsqueeze(0))
         else:
             w = prm["weights1"]
             xr = t.reshape(t.shape[0], -1) @ prm["linear_down.weight"].T + prm["linear_down.bias"]
+            xr = xr if h_hook is None else h_hook(xr)
             ev = oc.run_circuit(oc.Spec(n=w.shape[3], encoding="rz", imprimitive="CZ", measure="expz"), xr, w)
         if detach:
             ev = ev.detach()

@@ -157,6 +157,13 @@ def test_fused_noise_generation():
     allf = torch.cat([f.flatten() for f in fields]).double()
     assert abs(allf.mean().item() - 0.5) < 0.01 and abs(allf.std().item() - 0.2) < 0.01
     assert abs(((allf - 0.5) / 0.2).pow(3).mean().item()) < 0.1 and abs(((allf - 0.5) / 0.2).pow(4).mean().item() - 3.0) < 0.2
+    # element for element the Philox4x32-10 / Box-Muller field of this process's key: the recording leaves the offset at
+    # zero and every replay advances it by one (_value_domain.noise_field; 1e-5 as in test_gpu_value_domain.py)
+    import _value_domain as vd
+    key = torch.initial_seed() & ((1 << 63) - 1)
+    for offset, f in enumerate(fields):
+        err = (f.cpu().double() - vd.noise_field(key, offset, 64, 64)).abs().max().item()
+        assert err < vd.FIELD_TOL, (offset, err)
     # same numbers as the eager step on the recorded field
     diff.net.fused_train_step = None
     for f, want in zip(fields, losses):
