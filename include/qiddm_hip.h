@@ -622,20 +622,48 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *                             op's 64 rows of grad_gates are zeros for every sample.  PennyLane's QubitChannel with 4 x 4
  *                             operators and PauliError with a two-letter word are this op.  The rule for kinds is
  *                             "general k-wire channel = 16 k".
- * Kinds 10..15, 17..31 and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
+ *   QIDDM_MIX_SHOTS (= 12)    legal only as the LAST op (`op %d: a sampled read-out must be the last op`); not an operation on
+ *                             rho: it says that the read-out named by `measure` is estimated from a finite number of
+ *                             computational-basis shots, drawn on the device in the launch that holds rho.  `a` is the
+ *                             number of shots, 1 .. 2^31 - 1 (`op %d: shots %d out of range`); `p` is the seed and `scale`
+ *                             the stream offset, both integer-valued doubles in [0, 2^53) (a non-integer, negative, too
+ *                             large or non-finite value: `op %d: sampled read-out seed|offset %g is not an integer in
+ *                             [0, 2^53)`); `wire` and `reserved` must be 0.  Output layout and dtype do not change:
+ *                             QIDDM_MEAS_PROBS gives count[k] / shots, QIDDM_MEAS_EXPZ (n+ - n-) / shots per wire (wire w
+ *                             is bit n-1-w of the outcome, sign -1 when the bit is set), each one float64 division of
+ *                             exact integers.  The sampling rule, for D = 2^n outcomes of sample b (the ABSOLUTE row of
+ *                             the batch: neither the sample loop of qiddm_mixed_forward nor the chunks of
+ *                             qiddm_mixed_wide_forward move a stream):
+ *                               p_k = fmax((double)Re rho_kk, 0)   (a NaN counts as 0),
+ *                               c_k = p_0 + ... + p_k, float64, added sequentially in k (numpy.cumsum), T = c_{D-1};
+ *                               shot s takes word (s & 3) of Philox4x32-10 with counter (s >> 2, b mod 2^32, offset mod
+ *                               2^32, offset >> 32) and key (seed mod 2^32, seed >> 32);
+ *                               v = ((double)word * 2^-32) * T;  outcome = #{k : c_k <= v}, clamped to D - 1.
+ *                             T not positive or not finite: the sample's row is NaN.  Counts are accumulated with
+ *                             integer adds only (LDS integer atomics, integer wave reductions): reruns are bit-identical,
+ *                             no float atomics.  CDF and histogram live in LDS: no workspace size changes.  The reverse
+ *                             sweeps (qiddm_mixed_backward, qiddm_mixed_wide_backward), their *_workspace_bytes and
+ *                             qiddm_mixed_wide_backward_plan answer QIDDM_ERR_UNSUPPORTED for a program that ends in it
+ *                             (`... a sampled read-out has no gradient`).  qiddm_mixed_wide_plan accepts it, counts it in
+ *                             no sweep and not as a non-diagonal op; its op_segment entry is -1.  PennyLane's
+ *                             default.mixed with shots=... is a program that ends in this op; readout_prob is a BitFlip
+ *                             (QIDDM_MIX_CHANNEL) on every wire in front of it.
+ * Kinds 10, 11, 13..15, 17..31 and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
  * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
  * batch / n_ops, measure (batch == 0 then returns QIDDM_OK with no pointer looked at), program (not empty, starts with a
  * state preparation), negative n_rows / n_gates, angle_rows / rows_ld, gates, the ops one by one (kind, wire, target wire
- * or second wire -- `op %d: bad second wire %d` when it is outside 0..n-1 or equal to `wire` --,
+ * or second wire -- `op %d: bad second wire %d` when it is outside 0..n-1 or equal to `wire` --; QIDDM_MIX_SHOTS instead:
+ * its position, wire / reserved, shots, seed, offset --,
  * then the operand they index: features / feat_ld / n_features, angle row, gate, probability (a >= 0: angle row, then
  * finite p / scale), channel rows), max_blocks (negative:
- * refused for an empty batch as well), the outputs
+ * refused for an empty batch as well), in the reverse sweeps a program that ends in QIDDM_MIX_SHOTS, the outputs
  * (out, out_ld | grad_out / gout_ld, grad_rows, grad_gates, grad_features), workspace.                   */
 enum {
   QIDDM_MIX_ZERO = 0, QIDDM_MIX_AMP_EMBED, QIDDM_MIX_PHASE, QIDDM_MIX_RY, QIDDM_MIX_GATE, QIDDM_MIX_CZ,
   QIDDM_MIX_CNOT, QIDDM_MIX_PHASE_DAMP, QIDDM_MIX_AMP_DAMP, QIDDM_MIX_DEPOL,
+  QIDDM_MIX_SHOTS = 12,
   QIDDM_MIX_CHANNEL = 16,
   QIDDM_MIX_CHANNEL2 = 32
 };

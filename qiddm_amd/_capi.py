@@ -70,6 +70,7 @@ class TrainArgs(ctypes.Structure):
 
 
 MIX_ZERO, MIX_AMP_EMBED, MIX_PHASE, MIX_RY, MIX_GATE, MIX_CZ, MIX_CNOT, MIX_PHASE_DAMP, MIX_AMP_DAMP, MIX_DEPOL = range(10)
+MIX_SHOTS = 12  # last op only: the read-out is sampled; `a` = shots, `p` = seed, `scale` = stream offset
 MIX_CHANNEL = 16  # general one-wire channel: `a` = first of four gate rows holding the superoperator
 MIX_CHANNEL2 = 32  # general two-wire channel: `a` = first of 64 gate rows (16 x 16), `reserved` = the second wire
 

@@ -6,6 +6,8 @@
 // MixedCall, has check_call() validate them (one order for all four, stated in the header), and then reads as a list of
 // steps: outputs, geometry (and plan), workspace, upload(), make_scalars(), for_dtype launch.  The *_workspace_bytes
 // functions check sizes with check_sizes() and the two *_plan functions validate through the planner alone.
+// A program may end in QIDDM_MIX_SHOTS (the sampled read-out, qsim_mixed_shots.h): the forwards keep it out of the ops the
+// kernels walk and launch the sampling kernels with its fields (shots_of); everything reverse refuses it (refuse_sampled).
 #include "capi_common.h"
 
 #include <hip/hip_runtime.h>
@@ -32,7 +34,8 @@ using qiddm_capi::launched;
 
 static_assert(sizeof(qiddm::MixedOp) == sizeof(qiddm_mixed_op_t), "program layout");
 static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixChannel == (int)QIDDM_MIX_CHANNEL &&
-                  (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2, "op kinds");
+                  (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2 && (int)qiddm::kMixShots == (int)QIDDM_MIX_SHOTS,
+              "op kinds");
 static_assert(offsetof(qiddm::MixedOp, wire2) == offsetof(qiddm_mixed_op_t, reserved), "the second wire travels in `reserved`");
 
 inline int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
@@ -99,13 +102,58 @@ int check_program_start(const qiddm_mixed_op_t* program, int32_t n_ops) {
   return QIDDM_OK;
 }
 
+// a seed or stream offset of QIDDM_MIX_SHOTS: an integer-valued double in [0, 2^53)
+inline bool is_counter_word(double v) { return v >= 0.0 && v < 9007199254740992.0 && v == std::floor(v); }  // NaN fails
+
+// the sampled read-out a program ends in (all zeros: none; the ops have been checked)
+qiddm::MixedShots shots_of(const qiddm_mixed_op_t* program, int32_t n_ops) {
+  qiddm::MixedShots sh{};
+  if (n_ops < 1 || !program || program[n_ops - 1].kind != qiddm::kMixShots) return sh;
+  const qiddm_mixed_op_t& op = program[n_ops - 1];
+  const uint64_t seed = (uint64_t)op.p, offset = (uint64_t)op.scale;
+  sh.shots = (uint32_t)op.a;
+  sh.seed_lo = (uint32_t)seed;
+  sh.seed_hi = (uint32_t)(seed >> 32);
+  sh.off_lo = (uint32_t)offset;
+  sh.off_hi = (uint32_t)(offset >> 32);
+  return sh;
+}
+inline bool ends_in_shots(const qiddm_mixed_op_t* program, int32_t n_ops) {
+  return n_ops > 0 && program && program[n_ops - 1].kind == qiddm::kMixShots;
+}
+
+// the reverse sweeps, their workspace sizes and their plan: a program with a sampled read-out is refused (a SHOTS op
+// in front of the last op is the validator's fault, reported first)
+int refuse_sampled(const qiddm_mixed_op_t* program, int32_t n_ops) {
+  if (!program) return QIDDM_OK;
+  for (int i = 0; i + 1 < n_ops; ++i)
+    if (program[i].kind == qiddm::kMixShots)
+      return fail(QIDDM_ERR_INVALID, "op %d: a sampled read-out must be the last op", i);
+  if (ends_in_shots(program, n_ops))
+    return fail(QIDDM_ERR_UNSUPPORTED, "op %d: a sampled read-out has no gradient (finite shots have no reverse sweep)",
+                n_ops - 1);
+  return QIDDM_OK;
+}
+
 // kind, wire and target / second wire of op i: all the planner reads of an op, and the first thing the validator checks
-// of it
-int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i) {
+// of it.  QIDDM_MIX_SHOTS is checked here in full (position, wire / reserved, shots, seed, offset): it indexes no operand.
+int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops) {
   if ((op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) && op.kind != qiddm::kMixChannel &&
-      op.kind != qiddm::kMixChannel2)
+      op.kind != qiddm::kMixChannel2 && op.kind != qiddm::kMixShots)
     return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
   if (is_prep(op.kind)) return QIDDM_OK;
+  if (op.kind == qiddm::kMixShots) {
+    if (i != n_ops - 1) return fail(QIDDM_ERR_INVALID, "op %d: a sampled read-out must be the last op", i);
+    if (op.wire != 0 || op.reserved != 0)
+      return fail(QIDDM_ERR_INVALID, "op %d: a sampled read-out takes wire 0 and reserved 0 (got %d, %d)", i, op.wire,
+                  op.reserved);
+    if (op.a < 1) return fail(QIDDM_ERR_INVALID, "op %d: shots %d out of range", i, op.a);
+    if (!is_counter_word(op.p))
+      return fail(QIDDM_ERR_INVALID, "op %d: sampled read-out seed %g is not an integer in [0, 2^53)", i, op.p);
+    if (!is_counter_word(op.scale))
+      return fail(QIDDM_ERR_INVALID, "op %d: sampled read-out offset %g is not an integer in [0, 2^53)", i, op.scale);
+    return QIDDM_OK;
+  }
   if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
   if ((op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) && (op.a < 0 || op.a >= n || op.a == op.wire))
     return fail(QIDDM_ERR_INVALID, "op %d: bad target wire %d", i, op.a);
@@ -149,7 +197,7 @@ int check_call(const MixedCall& c, const Engine& e, bool* embeds) {
   *embeds = false;
   for (int i = 0; i < c.n_ops; ++i) {
     const qiddm_mixed_op_t& op = c.program[i];
-    if ((rc = check_op_wires(c.n_qubits, op, i)) != QIDDM_OK) return rc;
+    if ((rc = check_op_wires(c.n_qubits, op, i, c.n_ops)) != QIDDM_OK) return rc;
     switch (op.kind) {
       case qiddm::kMixAmpEmbed:
         if (!c.features || c.n_features < 1 || c.n_features > d)
@@ -335,11 +383,18 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
   int rc = check_plan_input(n, program, n_ops);
   if (rc != QIDDM_OK) return rc;
   const uint32_t all = (1u << n) - 1u;
+  // a sampled read-out (last op) is no op on rho: checked, then left out of every segment.  plan->order holds the
+  // n_ops - 1 ops in front of it and its op_segment stays -1.
+  const int32_t n_all = n_ops;
+  if (ends_in_shots(program, n_ops)) {
+    if ((rc = check_op_wires(n, program[n_ops - 1], n_ops - 1, n_all)) != QIDDM_OK) return rc;
+    --n_ops;
+  }
   std::vector<uint32_t> wires(n_ops);
   plan->n_nondiag = 0;
   for (int i = 0; i < n_ops; ++i) {
     const qiddm_mixed_op_t& op = program[i];
-    if ((rc = check_op_wires(n, op, i)) != QIDDM_OK) return rc;
+    if ((rc = check_op_wires(n, op, i, n_all)) != QIDDM_OK) return rc;
     wires[i] = is_prep(op.kind) ? all : 1u << op.wire;
     if (op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) wires[i] |= 1u << op.a;
     if (op.kind == qiddm::kMixChannel2) wires[i] |= 1u << op.reserved;  // both wires in the tile, as for CNOT
@@ -347,7 +402,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
   }
   plan->order.clear();
   plan->order.reserve(n_ops);
-  plan->op_segment.assign(n_ops, -1);
+  plan->op_segment.assign(n_all, -1);
   plan->segments.clear();
   plan->seg_channel.clear();
   plan->seg_level.clear();
@@ -418,7 +473,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
 
 template <typename T>
 int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resident, unsigned char* ws, const MixedCall& c,
-                      double* out, qiddm::MixedScalars m, bool embeds, hipStream_t st) {
+                      double* out, qiddm::MixedScalars m, bool embeds, const qiddm::MixedShots& sh, hipStream_t st) {
   const size_t smem = (size_t)qiddm::kWideTile * sizeof(qiddm::V2<T>);
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
   double* norms = reinterpret_cast<double*>(ws + g.off_norms);
@@ -435,7 +490,10 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
       });
       if (rc != QIDDM_OK) return rc;
     }
-    hipLaunchKernelGGL(qiddm::mixed_wide_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0);
+    if (sh.shots)  // the sampled read-out, keyed by the absolute row s0 + block
+      hipLaunchKernelGGL(qiddm::mixed_wide_sampled_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0, sh);
+    else
+      hipLaunchKernelGGL(qiddm::mixed_wide_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0);
     if (const int rc = launched("mixed_wide"); rc != QIDDM_OK) return rc;
   }
   return QIDDM_OK;
@@ -459,6 +517,7 @@ struct WideBwdPlan {
 
 int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WideBwdPlan* bp) {
   int rc = check_plan_input(n, program, n_ops);
+  if (rc == QIDDM_OK) rc = refuse_sampled(program, n_ops);
   if (rc != QIDDM_OK) return rc;
   bp->live_begin = 0;
   for (int i = 0; i < n_ops; ++i)
@@ -640,13 +699,20 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
-  const qiddm::MixedScalars m = make_scalars(c, n_ops, n_features, out_ld, g.in_lds);
+  const qiddm::MixedShots sh = shots_of(program, n_ops);
+  const int32_t n_body = n_ops - (sh.shots ? 1 : 0);  // the ops the kernel walks: a sampled read-out is none of them
+  const qiddm::MixedScalars m = make_scalars(c, n_body, n_features, out_ld, g.in_lds);
   const size_t smem = g.in_lds ? (size_t)g.slab_bytes : 0;
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
-  const int level = program_level(program, n_ops);
+  const int level = program_level(program, n_body);
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     return for_level(level, [&](auto lv) {
+      if (sh.shots)
+        return launch<qiddm::mixed_sampled_kernel<T, decltype(lv)::value>>(
+            kMaxLds - 8192 /* the kernel also has 5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
+            "mixed_sampled_kernel", prog, angle_rows, features, gates, out,
+            reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m, sh);
       return launch<qiddm::mixed_kernel<T, decltype(lv)::value>>(
           kMaxLds - 4096 /* the kernel also has 2 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
           "mixed_kernel", prog, angle_rows, features, gates, out, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m);
@@ -660,6 +726,7 @@ int64_t qiddm_mixed_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, in
   int32_t n_snaps = 0;
   int rc = check_sizes(n_qubits, dtype, batch, n_ops, kOneWorkgroup);
   if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc == QIDDM_OK) rc = refuse_sampled(program, n_ops);
   if (rc == QIDDM_OK) rc = mixed_backward_geometry(n_qubits, dtype, batch, program, n_ops, max_blocks, &g, &n_snaps);
   if (rc != QIDDM_OK) return rc;
   return g.total;
@@ -677,6 +744,7 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   int rc = check_call(c, kOneWorkgroup, &embeds);
   if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);  // refused for an empty batch as well
   if (rc != QIDDM_OK || batch == 0) return rc;
+  if ((rc = refuse_sampled(program, n_ops)) != QIDDM_OK) return rc;
   if ((rc = check_backward_outputs(c, embeds, grad_out, gout_ld, grad_rows, grad_gates, grad_features)) != QIDDM_OK) return rc;
   MixedGeometry g;
   int32_t n_snaps = 0;
@@ -743,14 +811,16 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
   rc = wide_resident(workspace, workspace_bytes, g.off_slabs, g.slab_bytes, g.resident, g.total,
                      "qiddm_mixed_wide_workspace_bytes", &resident);
   if (rc != QIDDM_OK) return rc;
-  std::vector<qiddm_mixed_op_t> sorted(n_ops);
-  for (int i = 0; i < n_ops; ++i) sorted[i] = program[plan.order[i]];
+  const qiddm::MixedShots sh = shots_of(program, n_ops);
+  const int32_t n_body = (int32_t)plan.order.size();  // n_ops, or n_ops - 1 in front of a sampled read-out
+  std::vector<qiddm_mixed_op_t> sorted(n_body);
+  for (int i = 0; i < n_body; ++i) sorted[i] = program[plan.order[i]];
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  if ((rc = upload(ws, sorted.data(), (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
-  const qiddm::MixedScalars m = make_scalars(c, n_ops, n_features, out_ld, false);
+  if ((rc = upload(ws, sorted.data(), (size_t)n_body * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  const qiddm::MixedScalars m = make_scalars(c, n_body, n_features, out_ld, false);
   return for_dtype(dtype, [&](auto t) {
-    return launch_mixed_wide<decltype(t)>(plan, g, resident, ws, c, out, m, embeds, st);
+    return launch_mixed_wide<decltype(t)>(plan, g, resident, ws, c, out, m, embeds, sh, st);
   });
 }
 
@@ -785,6 +855,7 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
   bool embeds = false;
   int rc = check_call(c, kTileFused, &embeds);
   if (rc != QIDDM_OK || batch == 0) return rc;
+  if ((rc = refuse_sampled(program, n_ops)) != QIDDM_OK) return rc;
   if ((rc = check_backward_outputs(c, embeds, grad_out, gout_ld, grad_rows, grad_gates, grad_features)) != QIDDM_OK) return rc;
   WideBwdPlan bp;
   if ((rc = plan_mixed_wide_backward(n_qubits, program, n_ops, &bp)) != QIDDM_OK) return rc;

@@ -21,11 +21,13 @@
 // vec(M) <- S vec(M), vec(M)[4r + c] = M[r][c], S 16 x 16 complex (mixed_block_super2 below; two-qubit depolarizing
 // behind an entangler, correlated dephasing, a two-letter PauliError, a measured two-qubit process).
 // Diagonal gates multiply by u_i conj(u_j); CZ by
-// sign(i) sign(j); CNOT permutes rows and columns (an involution: swapped in place).  Read-out: the diagonal.
+// sign(i) sign(j); CNOT permutes rows and columns (an involution: swapped in place).  Read-out: the diagonal -- or, for
+// a program that ends in kMixShots, estimates from that many shots drawn from it in the launch (qsim_mixed_shots.h).
 // mixed_backward_kernel (below) differentiates the same programs: PennyLane trains QNodes on default.mixed with
 // backprop or parameter-shift.  n <= 8.
 #pragma once
 #include "qsim_fused.h"
+#include "qsim_mixed_shots.h"
 
 namespace qiddm {
 
@@ -40,6 +42,8 @@ enum MixedKind : int32_t {
   kMixPhaseDamp,    // gamma = p, or with a >= 0 p + scale * angle_rows[a][sample] (not clamped; the row gets a gradient)
   kMixAmpDamp,      // gamma likewise
   kMixDepol,        // p likewise
+  kMixShots = 12,   // last op only, not an op on rho: the read-out is estimated from `a` shots (qsim_mixed_shots.h);
+                    // the host keeps it out of the ops the kernels walk and hands its fields over as a MixedShots
   kMixChannel = 16, // general one-wire channel: gates[a .. a+3] are the rows of the 4 x 4 superoperator S (10..15: no kind)
   kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..31: no kind)
 };
@@ -610,6 +614,34 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
       __syncthreads();
     }
     mixed_read_out<T>(rho, out, s_red, m, sample);  // the diagonal
+    __syncthreads();
+  }
+}
+
+// mixed_kernel with the sampled read-out (the program ended in kMixShots; m.n_ops counts the ops in front of it).  An
+// instantiation of its own: the analytic kernel carries none of this, neither registers nor LDS.
+template <typename T, int LEVEL>
+__global__ __launch_bounds__(256) void mixed_sampled_kernel(const MixedOp* __restrict__ prog,
+                                                            const double* __restrict__ angle_rows,
+                                                            const double* __restrict__ feats,
+                                                            const double* __restrict__ gates, double* __restrict__ out,
+                                                            V2<T>* __restrict__ workspace, const MixedScalars m,
+                                                            const MixedShots sh) {
+  using C = V2<T>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ double s_red[256];
+  __shared__ double s_cdf[256];    // n <= 8: 2^n prefix sums
+  __shared__ uint32_t s_cnt[256];  // and as many counts
+  const uint32_t DD = 1u << (2 * m.n);
+  C* rho = m.slab_in_lds ? reinterpret_cast<C*>(smem_raw) : workspace + (size_t)blockIdx.x * DD;
+
+  for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
+    for (int oi = 0; oi < m.n_ops; ++oi) {
+      const MixedOp op = prog[oi];
+      mixed_apply_op<T, LEVEL>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
+      __syncthreads();
+    }
+    mixed_sample_read_out<T>(rho, out + sample * m.out_ld, s_cdf, s_cnt, m.n, m.measure, sample, sh);
     __syncthreads();
   }
 }

@@ -260,4 +260,17 @@ __global__ __launch_bounds__(256) void mixed_wide_read_out(const V2<T>* __restri
   mixed_read_out<T>(slabs + ((size_t)blockIdx.x << (2 * m.n)), out, s_red, m, sample0 + blockIdx.x);
 }
 
+// the sampled read-out (qsim_mixed_shots.h) in its place when the program ends in kMixShots: one workgroup per resident
+// sample, keyed by the absolute row sample0 + blockIdx.x, so the chunking does not move a stream
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_sampled_read_out(const V2<T>* __restrict__ slabs,
+                                                                   double* __restrict__ out, const MixedScalars m,
+                                                                   int64_t sample0, const MixedShots sh) {
+  __shared__ double s_cdf[1024];    // n <= 10
+  __shared__ uint32_t s_cnt[1024];
+  const int64_t sample = sample0 + blockIdx.x;
+  mixed_sample_read_out<T>(slabs + ((size_t)blockIdx.x << (2 * m.n)), out + sample * m.out_ld, s_cdf, s_cnt, m.n, m.measure,
+                           sample, sh);
+}
+
 }  // namespace qiddm

@@ -27,6 +27,7 @@
 // All reductions have a fixed order: the step is bit-reproducible run to run.
 #pragma once
 #include "qsim_adjoint.h"
+#include "qsim_philox.h"
 
 #ifndef QIDDM_TRAIN_OCC
 #define QIDDM_TRAIN_OCC 2  // waves per SIMD the reverse-sweep kernel is compiled for (register budget 512 / OCC).
@@ -60,18 +61,7 @@ __device__ __forceinline__ double blend_noise(double xv, float nz, float w) {
 // every wavefront that needs the element) derives the same number.
 __device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t offset, uint64_t index) {
   uint32_t c0 = (uint32_t)index, c1 = (uint32_t)(index >> 32), c2 = (uint32_t)offset, c3 = (uint32_t)(offset >> 32);
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
+  philox4x32_10(c0, c1, c2, c3, (uint32_t)seed, (uint32_t)(seed >> 32));  // qsim_philox.h
   const float u1 = ((float)c0 + 1.0f) * 2.3283064365386963e-10f;  // (0, 1]
   const float u2 = (float)c1 * 2.3283064365386963e-10f;           // [0, 1): revolutions
   const float n = sqrtf(-2.0f * __logf(u1)) * __builtin_amdgcn_cosf(u2);

@@ -40,6 +40,15 @@ sweep of the tile-fused engine (``qiddm_mixed_wide_backward``) keeps rho, its ad
 channels per sample, several slabs where the forward keeps one.  With both limits raised a 9- or 10-wire launch is the
 same kind of autograd node: the forward is the tile-fused forward (bit-identical to the no-grad call), the backward the
 tile-fused reverse sweep.
+
+The read-out follows PennyLane's ``default.mixed`` as well.  ``qml.device("default.mixed", wires=n, readout_prob=q)``
+appends one ``BitFlip(q)`` per wire, in wire order, behind the tape (``QIDDM_MIX_CHANNEL``; the four rows are uploaded
+once): analytic and differentiable for everything in front of it.  ``shots=N`` appends ``QIDDM_MIX_SHOTS``: the launch
+that holds rho draws N computational-basis outcomes per sample (Philox4x32-10 keyed by the device's seed, the stream
+offset is the device's count of sampled executions; the rule is in include/qiddm_hip.h) and returns count / N or
+(n+ - n-) / N per wire, float64.  Nothing is copied to the host.  A sampled execution has no reverse sweep: with grad
+mode on and an input that requires grad it raises ``qml.QuantumFunctionError``; while the current stream is capturing it
+raises ``RuntimeError`` (a replay would repeat the same shots).
 """
 from __future__ import annotations
 
@@ -339,7 +348,9 @@ class _Lowering:
                     self.op(kind, wires[i], wires[(i + r) % n])
 
 
-def lower(tape, ret, n):
+def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
+    """Tape and measurement -> (_Lowering, measure).  `readout_prob`: one BitFlip per wire behind the tape; `shots`: the
+    program ends in MIX_SHOTS with this `seed` and stream `offset`."""
     from . import qml
     low = _Lowering(n)
     all_w = tuple(range(n))
@@ -399,6 +410,12 @@ def lower(tape, ret, n):
         first = False
     if first:
         low.op(_capi.MIX_ZERO)
+    if readout_prob is not None:  # PennyLane: BitFlip(readout_prob) on every measured wire in front of the measurement
+        base = low._add_gates(channel_rows("BitFlip", readout_prob))  # the same four rows for every wire
+        for w in all_w:
+            low.op(_capi.MIX_CHANNEL, w, base)
+    if shots is not None:
+        low.op(_capi.MIX_SHOTS, 0, int(shots), float(seed), float(offset))
     # measurement
     if isinstance(ret, qml._Measurement):
         if ret.kind != "probs" or (ret.wires is not None and ret.wires != all_w):
@@ -515,11 +532,23 @@ def _check_strengths(rows, strengths):
         _prob(strengths[i][1], s[i, j])
 
 
-def execute(tape, ret, n, precision=None, _engine=None):
+def execute(tape, ret, n, precision=None, _engine=None, device=None):
     """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)``
     (or the unbatched row), as ``default.mixed`` does.  Up to 8 wires: differentiable when grad mode is on and an input
     requires grad; otherwise a plain launch whose result has no ``grad_fn``.  9 and 10 wires (within the wire limit, see
-    ``set_max_wires``): forward only unless ``set_max_grad_wires`` admits them too."""
+    ``set_max_wires``): forward only unless ``set_max_grad_wires`` admits them too.  `device` (the QNode's ``qml.Device``):
+    its ``readout_prob`` and ``shots``; a sampled execution takes the device's next stream offset."""
+    qdev = device  # (`device` below: the torch device of the operands)
+    shots = getattr(qdev, "shots", None)
+    readout_prob = getattr(qdev, "readout_prob", None)
+    if shots is not None:
+        from . import qml
+        if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params):
+            raise qml.QuantumFunctionError("finite shots have no reverse sweep; sample under torch.no_grad() or use "
+                                           "shots=None")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a sampled default.mixed execution cannot be captured into a graph: every replay would "
+                               "repeat the same shots")
     # the engine follows the number of wires; `_engine="wide"` (tests, A/B tools) forces the tile-fused one at 7, 8 wires
     wide = _engine == "wide" or 8 < n <= _max_wires
     if wide and n > _max_grad_wires and torch.is_grad_enabled() and \
@@ -532,9 +561,11 @@ def execute(tape, ret, n, precision=None, _engine=None):
         raise NotImplementedError(
             f"default.mixed on {n} wires executes forward only: gradients stop at 8 wires (the tile-fused engine has no "
             "reverse sweep).  Sample under torch.no_grad(), or train on a pure-state device.")
-    low, measure = lower(tape, ret, n)
+    low, measure = lower(tape, ret, n, readout_prob, shots, getattr(qdev, "seed", 0), getattr(qdev, "calls", 0))
     if low.device is None:
         raise RuntimeError("default.mixed runs on the GPU only: no tensor argument lives on a HIP device (no CPU path)")
+    if shots is not None:  # the circuit has been accepted: this execution has taken a stream of its own
+        qdev.next_offset()
     device = low.device
     batch = low.batch or 1
     prec = _capi.F64 if (precision or _c.get_default_precision()) == "f64" else _capi.F32

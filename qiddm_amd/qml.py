@@ -237,8 +237,12 @@ def expval(obs):
 # ---------------------------------------------------------------------------
 # device / QNode
 # ---------------------------------------------------------------------------
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
 class Device:
-    def __init__(self, name, wires, **kwargs):
+    def __init__(self, name, wires, shots=None, readout_prob=None, seed=None, **kwargs):
         if isinstance(wires, int):
             self.num_wires = wires
         else:
@@ -247,20 +251,62 @@ class Device:
         self.mixed = name == "default.mixed"
         if name not in _PURE_STATE_DEVICES and not self.mixed:
             raise DeviceError(f"Device {name} does not exist. Make sure the required plugin is installed.")
+        self.shots, self.readout_prob, self.seed, self.calls = None, None, None, 0
+        if not self.mixed:
+            if readout_prob is not None:
+                raise TypeError(f"device {name!r} got an unexpected keyword argument 'readout_prob'")
+            if shots is not None:
+                raise NotImplementedError(
+                    f"shots={shots!r} on device {name!r}: the statevector engines are analytic only; finite shots (and "
+                    "readout_prob) are sampled on 'default.mixed'")
+            return
+        if shots is not None:
+            if not _is_int(shots) or not 1 <= shots < 2**31:
+                raise ValueError(f"shots must be None (analytic) or a positive int below 2**31 (got {shots!r})")
+            self.shots = int(shots)
+        if readout_prob is not None:
+            from . import mixed as _mixed
+            self.readout_prob = _mixed._prob("readout_prob", readout_prob)
+        if seed is not None and (not _is_int(seed) or not 0 <= seed < 2**53):
+            raise ValueError(f"seed must be None or a non-negative int below 2**53 (got {seed!r})")
+        if seed is not None:
+            self.seed = int(seed)
+        elif self.shots is not None:
+            # one draw from torch's default CPU generator: torch.manual_seed reproduces a sampled run.  (An analytic
+            # device draws nothing: creating it leaves the generator where it was.)
+            self.seed = int(torch.randint(0, 2**53, (1,), dtype=torch.int64).item())
+
+    def next_offset(self) -> int:
+        """The stream offset of the next sampled execution: the device's call counter, which it advances.  The steps of
+        a denoising loop draw disjoint streams; two devices with one seed replay each other."""
+        offset = self.calls
+        self.calls += 1
+        return offset
 
     def __repr__(self):
         kind = "density-matrix" if self.mixed else "statevector"
-        return f"<qiddm_amd HIP {kind} device standing in for {self.short_name!r}, wires={self.num_wires}>"
+        extra = "" if self.shots is None else f", shots={self.shots}, seed={self.seed}"
+        if self.readout_prob is not None:
+            extra += f", readout_prob={self.readout_prob}"
+        return f"<qiddm_amd HIP {kind} device standing in for {self.short_name!r}, wires={self.num_wires}{extra}>"
 
 
-def device(name, wires=1, **kwargs):
+def device(name, wires=1, shots=None, readout_prob=None, seed=None, **kwargs):
     """``qml.device(name, wires=n)``.  Every pure-state device name the reference uses maps
     to the HIP statevector engine; ``default.mixed`` (the noise scripts create it,
     src/mnist_noise.py:223) maps to the density-matrix kernels (``qiddm_amd.mixed``: n <= 8 differentiable by a reverse sweep;
     n = 9, 10 after ``mixed.set_max_wires``, differentiable after ``mixed.set_max_grad_wires``).  There
     ``PhaseDamping`` / ``AmplitudeDamping`` / ``DepolarizingChannel`` take a float or a GPU tensor as strength: 0-d for
-    the batch, 1-D per sample, differentiable when it requires grad."""
-    return Device(name, wires, **kwargs)
+    the batch, 1-D per sample, differentiable when it requires grad.
+
+    ``default.mixed`` also takes PennyLane's read-out model.  ``shots``: ``None`` (analytic) or a positive int -- every
+    execution then returns the estimate from that many computational-basis shots, drawn on the device inside the launch
+    (no gradient: sample under ``torch.no_grad()``).  ``readout_prob``: ``None`` or a float in [0, 1], a ``BitFlip`` of
+    that strength on every wire in front of the measurement, with or without shots.  ``seed``: ``None`` (one draw from
+    torch's default CPU generator when the device is created with shots) or a non-negative int; the device counts its
+    sampled executions and gives each a stream of its own.  On the pure-state names ``shots`` raises
+    ``NotImplementedError`` and ``readout_prob`` ``TypeError``; other keywords are ignored."""
+    return Device(name, wires, shots=shots, readout_prob=readout_prob, seed=seed, **kwargs)
 
 
 class QNode:
@@ -297,7 +343,7 @@ class QNode:
             # on and an input requires grad
             from . import mixed as _mixed
             self.circuit = None
-            return _mixed.execute(tape, ret, n, self.precision)
+            return _mixed.execute(tape, ret, n, self.precision, device=self.device)  # its shots, readout_prob, streams
         circ, x, angles, batched, as_list = _compile(tape, ret, n, self.device)
         self.circuit = circ
         out = _c.execute(circ, x, angles, self.precision, self.diff_method or "backprop")
