@@ -241,14 +241,21 @@ int qiddm_qconv_unitary_forward(int32_t n_qubits, const double* u, const double*
   }
   const int64_t mblocks = (g.m + qiddm::kGemmM - 1) / qiddm::kGemmM;
   if (mblocks > 0x7fffffff) return fail(QIDDM_ERR_UNSUPPORTED, "too many output pixels for one launch");
+  // (kernel extents beyond 16: the variants whose tap table holds whole coordinates)
+  const bool big = kh > 16 || kw > 16;
+#define QIDDM_GEMM_LAUNCH_AS(GRID_Y, ...)                                                                          \
+  hipLaunchKernelGGL((qiddm::__VA_ARGS__>), dim3((unsigned)mblocks, (unsigned)(GRID_Y)), dim3(4 * qiddm::kWave), 0, \
+                     st, x, w, padv, bnv, y, gc)
 #define QIDDM_GEMM_LAUNCH(GRID_Y, ...)                                                                             \
   do {                                                                                                            \
-    if (upsample2x)                                                                                               \
-      hipLaunchKernelGGL((qiddm::__VA_ARGS__ true>), dim3((unsigned)mblocks, (unsigned)(GRID_Y)),                  \
-                         dim3(4 * qiddm::kWave), 0, st, x, w, padv, bnv, y, gc);                                  \
+    if (upsample2x && big)                                                                                        \
+      QIDDM_GEMM_LAUNCH_AS(GRID_Y, __VA_ARGS__ true, true);                                                       \
+    else if (upsample2x)                                                                                          \
+      QIDDM_GEMM_LAUNCH_AS(GRID_Y, __VA_ARGS__ true);                                                             \
+    else if (big)                                                                                                 \
+      QIDDM_GEMM_LAUNCH_AS(GRID_Y, __VA_ARGS__ false, true);                                                      \
     else                                                                                                          \
-      hipLaunchKernelGGL((qiddm::__VA_ARGS__ false>), dim3((unsigned)mblocks, (unsigned)(GRID_Y)),                 \
-                         dim3(4 * qiddm::kWave), 0, st, x, w, padv, bnv, y, gc);                                  \
+      QIDDM_GEMM_LAUNCH_AS(GRID_Y, __VA_ARGS__ false);                                                            \
   } while (0)
   if (g.packed == 3)
     QIDDM_GEMM_LAUNCH(g.n_pad / 256, qconv_gemm_wide_kernel<);
@@ -259,6 +266,7 @@ int qiddm_qconv_unitary_forward(int32_t n_qubits, const double* u, const double*
   else
     QIDDM_GEMM_LAUNCH(g.n_pad / 64, qconv_gemm_kernel<0,);
 #undef QIDDM_GEMM_LAUNCH
+#undef QIDDM_GEMM_LAUNCH_AS
   return launched("qconv_gemm_kernel");
 }
 

@@ -151,7 +151,10 @@ constexpr int kGemmMaxK = 4096;  // F <= D <= 2^12 on this route
 // UP (compile time = g.upsample): the bilinear x2 in front of an up_conv folded into the gather.  As a run-time branch
 // its four-load taps shared registers with the plain path, and the wait-count pass then drained the plain path's gather
 // before the chunk's MFMAs (vmcnt waits between the B loads)
-template <int MODE, bool UP>
+// BIG (compile time = kh > 16 || kw > 16): the tap table's four bits per kernel coordinate do not hold the extent; the
+// table then carries di << 16 | dj and the gather derives channel and offset from the feature index (a division per
+// element: such kernels are rare, and the common variants stay as they are).
+template <int MODE, bool UP, bool BIG = false>
 __global__ __launch_bounds__(4 * kWave) void qconv_gemm_kernel(const double* __restrict__ x,
                                                                const float* __restrict__ w,
                                                                const float* __restrict__ padv,
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(4 * kWave) void qconv_gemm_kernel(const double* __r
     const int di = rem / g.kw, dj = rem - di * g.kw;
     // (upsample: the offset field carries the channel; the taps are interpolated)
     const uint32_t off = UP ? (uint32_t)c : (uint32_t)(c * plane) + (uint32_t)(di * g.W + dj);
-    s_tap[f] = off | ((uint32_t)di << 24) | ((uint32_t)dj << 28);
+    s_tap[f] = BIG ? ((uint32_t)di << 16) | (uint32_t)dj : off | ((uint32_t)di << 24) | ((uint32_t)dj << 28);
   }
   // ---- this thread's staging duty: row m_s, KT consecutive k of every chunk ------------------------------
   const int m_s = tid & (kGemmM - 1), kh_s = (tid >> 7) * KT;
@@ -212,8 +215,18 @@ __global__ __launch_bounds__(4 * kWave) void qconv_gemm_kernel(const double* __r
 #pragma unroll
     for (int u = 0; u < KT; ++u) {
       const int f = k0 + kh_s + u;
-      const int ii = oi + (int)((tap[u] >> 24) & 15u), jj = oj + (int)(tap[u] >> 28);
-      const uint32_t off = tap[u] & 0xFFFFFFu;
+      int ii, jj;
+      uint32_t off;
+      if constexpr (BIG) {
+        const int di = (int)(tap[u] >> 16), dj = (int)(tap[u] & 0xFFFFu), c = f / khw;
+        ii = oi + di;
+        jj = oj + dj;
+        off = UP ? (uint32_t)c : (uint32_t)(c * plane) + (uint32_t)(di * g.W + dj);
+      } else {
+        ii = oi + (int)((tap[u] >> 24) & 15u);
+        jj = oj + (int)(tap[u] >> 28);
+        off = tap[u] & 0xFFFFFFu;
+      }
       const bool in = m_ok && f < g.F && ii >= 0 && ii < g.H && jj >= 0 && jj < g.W;
       // the select on the loaded value is deferred to stage(): done here it put a wait for the gather in front of
       // the chunk's MFMAs (s_waitcnt vmcnt right after the issue), i.e. the load latency on the critical path
@@ -361,7 +374,7 @@ __global__ __launch_bounds__(4 * kWave) void qconv_gemm_kernel(const double* __r
 constexpr int kWideSub = 4;
 constexpr int kWideK = 16;
 
-template <bool UP>
+template <bool UP, bool BIG = false>
 __global__ __launch_bounds__(4 * kWave, UP ? 1 : 2) void qconv_gemm_wide_kernel(const double* __restrict__ x,
                                                                     const float* __restrict__ w,
                                                                     const float* __restrict__ padv,
@@ -386,7 +399,7 @@ __global__ __launch_bounds__(4 * kWave, UP ? 1 : 2) void qconv_gemm_wide_kernel(
     const int c = f / khw, rem = f - c * khw;
     const int di = rem / g.kw, dj = rem - di * g.kw;
     const uint32_t off = UP ? (uint32_t)c : (uint32_t)(c * plane) + (uint32_t)(di * g.W + dj);
-    s_tap[f] = off | ((uint32_t)di << 24) | ((uint32_t)dj << 28);
+    s_tap[f] = BIG ? ((uint32_t)di << 16) | (uint32_t)dj : off | ((uint32_t)di << 24) | ((uint32_t)dj << 28);
   }
   const int m_s = tid & (kGemmM - 1), kh_s = (tid >> 7) * KT;
   const int64_t mg = m0 + m_s;
@@ -420,8 +433,18 @@ __global__ __launch_bounds__(4 * kWave, UP ? 1 : 2) void qconv_gemm_wide_kernel(
 #pragma unroll
     for (int u = 0; u < KT; ++u) {
       const int f = k0 + kh_s + u;
-      const int ii = oi + (int)((tap[u] >> 24) & 15u), jj = oj + (int)(tap[u] >> 28);
-      const uint32_t off = tap[u] & 0xFFFFFFu;
+      int ii, jj;
+      uint32_t off;
+      if constexpr (BIG) {
+        const int di = (int)(tap[u] >> 16), dj = (int)(tap[u] & 0xFFFFu), c = f / khw;
+        ii = oi + di;
+        jj = oj + dj;
+        off = UP ? (uint32_t)c : (uint32_t)(c * plane) + (uint32_t)(di * g.W + dj);
+      } else {
+        ii = oi + (int)((tap[u] >> 24) & 15u);
+        jj = oj + (int)(tap[u] >> 28);
+        off = tap[u] & 0xFFFFFFu;
+      }
       const bool in = m_ok && f < g.F && ii >= 0 && ii < g.H && jj >= 0 && jj < g.W;
       // the select on the loaded value is deferred to stage(): done here it put a wait for the gather in front of
       // the chunk's MFMAs (s_waitcnt vmcnt right after the issue), i.e. the load latency on the critical path
