@@ -25,6 +25,15 @@
 // a program that ends in kMixShots, estimates from that many shots drawn from it in the launch (qsim_mixed_shots.h).
 // mixed_backward_kernel (below) differentiates the same programs: PennyLane trains QNodes on default.mixed with
 // backprop or parameter-shift.  n <= 8.
+//
+// How the code is laid out (this file and the tile-fused engine, qsim_mixed_wide*.h): three layers.
+//   arithmetic  what a kind does to one 2 x 2 block or one element, in registers: mixed_block_* and mixed_*_elem.
+//   walking     where a wire's blocks sit (MixedBlock1) and the load / call / store of one block
+//               (mixed_block_visit); mixed_walk_blocks loops over a thread's blocks of a slab, wide_walk_blocks over
+//               its blocks of a tile.
+//   kernels     mixed_apply_op (every op of the forward, and of the backward's replay) under mixed_replay in the two
+//               forward kernels.  mixed_backward_kernel and mixed_wide_reverse_sweep write their block loops out; the
+//               notes in front of them say why.
 #pragma once
 #include "qsim_fused.h"
 #include "qsim_mixed_shots.h"
@@ -90,6 +99,40 @@ __device__ __forceinline__ uint32_t insert_two_bits(uint32_t t, int qlo, int qhi
   return lo | (mid << (qlo + 1)) | (hi << (qhi + 1));
 }
 
+// Where the 2 x 2 blocks of a wire sit: its bit in the column half (lo) and in the row half (hi) -- any bit numbering:
+// the one-workgroup engine passes the global q, q + n, the tile-fused engine local ranks (MixedBlock2: the same for the
+// 4 x 4 blocks of two wires).  Every walk over 2 x 2 blocks takes its indices from here.
+struct MixedBlock1 {
+  int lo, hi;
+  __device__ __forceinline__ uint32_t base(uint32_t t) const { return insert_two_bits(t, lo, hi); }  // element (0, 0)
+  __device__ __forceinline__ uint32_t cj() const { return 1u << lo; }                                // column bit
+  __device__ __forceinline__ uint32_t ci() const { return 1u << hi; }                                // row bit
+};
+// Block number t of `mem`, owned by the thread: f(m00, m01, m10, m11) works on its four elements in registers and what
+// it leaves goes back.  `snap` (may be NULL): the block as it was goes there too (as in mixed_block_super2).
+template <typename T, typename F>
+__device__ __forceinline__ void mixed_block_visit(V2<T>* mem, V2<T>* snap, uint32_t t, const MixedBlock1& b, F&& f) {
+  const uint32_t base = b.base(t), cj = b.cj(), ci = b.ci();
+  V2<T> m00 = mem[base], m01 = mem[base | cj], m10 = mem[base | ci], m11 = mem[base | ci | cj];
+  if (snap) {
+    snap[base] = m00;
+    snap[base | cj] = m01;
+    snap[base | ci] = m10;
+    snap[base | ci | cj] = m11;
+  }
+  f(m00, m01, m10, m11);
+  mem[base] = m00;
+  mem[base | cj] = m01;
+  mem[base | ci] = m10;
+  mem[base | ci | cj] = m11;
+}
+// A thread's blocks among the n_blocks of a slab (run-time count: fewer blocks than threads below n = 5).  The
+// tile-fused engine's count is a constant and its loops are unrolled: wide_walk_blocks in qsim_mixed_wide.h.
+template <typename T, typename F>
+__device__ __forceinline__ void mixed_walk_blocks(V2<T>* mem, V2<T>* snap, const MixedBlock1& b, uint32_t n_blocks, F&& f) {
+  for (uint32_t t = threadIdx.x; t < n_blocks; t += 256) mixed_block_visit<T>(mem, snap, t, b, f);
+}
+
 __device__ __forceinline__ double mixed_angle(const MixedOp& op, const double* __restrict__ angle_rows,
                                               const MixedScalars& m, int64_t sample) {
   return op.p + (op.a >= 0 ? op.scale * angle_rows[(size_t)op.a * m.rows_ld + sample] : 0.0);
@@ -114,7 +157,7 @@ __device__ __forceinline__ bool mixed_needs_snapshot(int kind, int oi) {
          kind == kMixChannel2 || (oi > 0 && (kind == kMixZero || kind == kMixAmpEmbed));
 }
 
-// ---- per-element / per-block arithmetic, shared by mixed_apply_op and the tiled engine (qsim_mixed_wide.h) ----------
+// ---- per-element / per-block arithmetic, shared by both engines and both directions --------------------------------
 template <typename T>
 __device__ __forceinline__ void mixed_phase_factors(double phi, V2<T>& up, V2<T>& dn) {
   double sn, cs;
@@ -128,11 +171,15 @@ __device__ __forceinline__ V2<T> mixed_phase_elem(V2<T> v, uint32_t k, int q, in
   const int bi = (k >> (q + n)) & 1, bj = (k >> q) & 1;
   return bi != bj ? cmul<T>(v, bi ? up : dn) : v;
 }
-template <typename T>
-__device__ __forceinline__ V2<T> mixed_cz_elem(V2<T> v, uint32_t k, int q, int qt, int n) {
+// whether CZ(bits q, qt) flips the sign of element k: sign(i) sign(j) = -1
+__device__ __forceinline__ bool mixed_cz_flips(uint32_t k, int q, int qt, int n) {
   const uint32_t i = k >> n, j = k & ((1u << n) - 1u);
   const int si = ((i >> q) & (i >> qt) & 1), sj = ((j >> q) & (j >> qt) & 1);
-  return si != sj ? V2<T>{-v.x, -v.y} : v;
+  return si != sj;
+}
+template <typename T>
+__device__ __forceinline__ V2<T> mixed_cz_elem(V2<T> v, uint32_t k, int q, int qt, int n) {
+  return mixed_cz_flips(k, q, qt, n) ? V2<T>{-v.x, -v.y} : v;
 }
 // where CNOT(control bit q, target bit qt) sends element k (an involution)
 __device__ __forceinline__ uint32_t mixed_cnot_index(uint32_t k, int q, int qt, int n) {
@@ -423,13 +470,7 @@ __device__ __forceinline__ double mixed_embed_norm2(const double* __restrict__ r
     const double v = k < (uint32_t)m.n_features ? row[k] + m.enc_offset : m.pad_with;
     part += v * v;
   }
-  s_red[tid] = part;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) s_red[tid] += s_red[tid + s];
-    __syncthreads();
-  }
-  return s_red[0];
+  return mixed_block_sum(part, s_red);
 }
 // element k of v v^T / |v|^2
 template <typename T>
@@ -438,6 +479,21 @@ __device__ __forceinline__ V2<T> mixed_embed_elem(const double* __restrict__ row
   const double vi = i < (uint32_t)m.n_features ? row[i] + m.enc_offset : m.pad_with;
   const double vj = j < (uint32_t)m.n_features ? row[j] + m.enc_offset : m.pad_with;
   return V2<T>{(T)(vi * vj * inv), (T)0};
+}
+// element k of Lambda_N = dL/drho_N, the seed of a reverse sweep: diag(g) for probs, sum_w g_w (1 - 2 bit_w) for <Z>
+template <typename T>
+__device__ __forceinline__ V2<T> mixed_seed_elem(const double* __restrict__ g, uint32_t k, const MixedScalars& m) {
+  const int n = m.n;
+  const uint32_t i = k >> n, j = k & ((1u << n) - 1u);
+  double v = 0.0;
+  if (i == j) {
+    if (m.measure == 0) {
+      v = g[i];
+    } else {
+      for (int w = 0; w < n; ++w) v += ((i >> (n - 1 - w)) & 1u) ? -g[w] : g[w];
+    }
+  }
+  return V2<T>{(T)v, (T)0};
 }
 
 // the diagonal of one sample's rho -> probs / <Z_w>, float64, fixed-order sums
@@ -455,14 +511,8 @@ __device__ __forceinline__ void mixed_read_out(const V2<T>* __restrict__ rho, do
         const double pk = (double)rho[((size_t)k << n) | k].x;
         part += ((k >> (n - 1 - w)) & 1u) ? -pk : pk;
       }
-      s_red[tid] = part;
-      __syncthreads();
-      for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) s_red[tid] += s_red[tid + s];
-        __syncthreads();
-      }
-      if (tid == 0) out[sample * m.out_ld + w] = s_red[0];
-      __syncthreads();
+      const double total = mixed_block_sum(part, s_red);
+      if (tid == 0) out[sample * m.out_ld + w] = total;
     }
   }
 }
@@ -478,6 +528,7 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
   const int n = m.n, tid = threadIdx.x;
   const uint32_t D = 1u << n, DD = 1u << (2 * n);
   const int q = n - 1 - op.wire;  // bit of the column half; the row half's is q + n
+  const MixedBlock1 blk{q, q + n};
   if (snap && (op.kind == kMixZero || op.kind == kMixAmpEmbed))
     for (uint32_t k = tid; k < DD; k += 256) snap[k] = rho[k];  // the same thread then overwrites rho[k]
   switch (op.kind) {
@@ -503,25 +554,14 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
     case kMixRY:
     case kMixGate: {
       const MixedU<T> u = mixed_unitary<T>(op, angle_rows, gates, m, sample);
-      for (uint32_t t = tid; t < DD / 4; t += 256) {
-        const uint32_t base = insert_two_bits(t, q, q + n);
-        const uint32_t cj = 1u << q, ci = 1u << (q + n);
-        C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
-        mixed_block_unitary<T>(u, m00, m01, m10, m11);
-        rho[base] = m00;
-        rho[base | cj] = m01;
-        rho[base | ci] = m10;
-        rho[base | ci | cj] = m11;
-      }
+      mixed_walk_blocks<T>(rho, nullptr, blk, DD / 4,
+                           [&](C& m00, C& m01, C& m10, C& m11) { mixed_block_unitary<T>(u, m00, m01, m10, m11); });
       break;
     }
     case kMixCZ: {
       const int qt = n - 1 - op.a;
-      for (uint32_t k = tid; k < DD; k += 256) {
-        const uint32_t i = k >> n, j = k & (D - 1);
-        const int si = ((i >> q) & (i >> qt) & 1), sj = ((j >> q) & (j >> qt) & 1);
-        if (si != sj) rho[k] = C{-rho[k].x, -rho[k].y};
-      }
+      for (uint32_t k = tid; k < DD; k += 256)
+        if (mixed_cz_flips(k, q, qt, n)) rho[k] = C{-rho[k].x, -rho[k].y};  // only the elements that change are stored
       break;
     }
     case kMixCNOT: {
@@ -540,22 +580,8 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
     case kMixAmpDamp:
     case kMixDepol: {
       const MixedChannel<T> ch = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample));
-      for (uint32_t t = tid; t < DD / 4; t += 256) {
-        const uint32_t base = insert_two_bits(t, q, q + n);
-        const uint32_t cj = 1u << q, ci = 1u << (q + n);
-        C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
-        if (snap) {
-          snap[base] = m00;
-          snap[base | ci | cj] = m11;
-          snap[base | cj] = m01;
-          snap[base | ci] = m10;
-        }
-        mixed_block_channel<T>(ch, m00, m01, m10, m11);
-        rho[base] = m00;
-        rho[base | ci | cj] = m11;
-        rho[base | cj] = m01;
-        rho[base | ci] = m10;
-      }
+      mixed_walk_blocks<T>(rho, snap, blk, DD / 4,
+                           [&](C& m00, C& m01, C& m10, C& m11) { mixed_block_channel<T>(ch, m00, m01, m10, m11); });
       break;
     }
     case kMixChannel2: {
@@ -571,26 +597,25 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
     case kMixChannel: {
       if constexpr (LEVEL >= kLevelChannel) {
         const MixedSuper<T> su = mixed_super<T>(op, gates);
-        for (uint32_t t = tid; t < DD / 4; t += 256) {
-          const uint32_t base = insert_two_bits(t, q, q + n);
-          const uint32_t cj = 1u << q, ci = 1u << (q + n);
-          C m00 = rho[base], m01 = rho[base | cj], m10 = rho[base | ci], m11 = rho[base | ci | cj];
-          if (snap) {
-            snap[base] = m00;
-            snap[base | cj] = m01;
-            snap[base | ci] = m10;
-            snap[base | ci | cj] = m11;
-          }
-          mixed_block_super<T>(su, m00, m01, m10, m11);
-          rho[base] = m00;
-          rho[base | cj] = m01;
-          rho[base | ci] = m10;
-          rho[base | ci | cj] = m11;
-        }
+        mixed_walk_blocks<T>(rho, snap, blk, DD / 4,
+                             [&](C& m00, C& m01, C& m10, C& m11) { mixed_block_super<T>(su, m00, m01, m10, m11); });
       }
       break;
     }
     default: break;
+  }
+}
+
+// The program on one sample's rho, a barrier behind every op: the body of both forward kernels
+template <typename T, int LEVEL>
+__device__ __forceinline__ void mixed_replay(const MixedOp* __restrict__ prog, V2<T>* __restrict__ rho,
+                                             const double* __restrict__ angle_rows, const double* __restrict__ feats,
+                                             const double* __restrict__ gates, double* s_red, const MixedScalars& m,
+                                             int64_t sample) {
+  for (int oi = 0; oi < m.n_ops; ++oi) {
+    const MixedOp op = prog[oi];
+    mixed_apply_op<T, LEVEL>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
+    __syncthreads();
   }
 }
 
@@ -603,16 +628,10 @@ __global__ __launch_bounds__(256) void mixed_kernel(const MixedOp* __restrict__ 
   using C = V2<T>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ double s_red[256];
-  const int n = m.n, tid = threadIdx.x;
-  const uint32_t D = 1u << n, DD = 1u << (2 * n);
-  C* rho = m.slab_in_lds ? reinterpret_cast<C*>(smem_raw) : workspace + (size_t)blockIdx.x * DD;
+  C* rho = m.slab_in_lds ? reinterpret_cast<C*>(smem_raw) : workspace + ((size_t)blockIdx.x << (2 * m.n));
 
   for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
-    for (int oi = 0; oi < m.n_ops; ++oi) {
-      const MixedOp op = prog[oi];
-      mixed_apply_op<T, LEVEL>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
-      __syncthreads();
-    }
+    mixed_replay<T, LEVEL>(prog, rho, angle_rows, feats, gates, s_red, m, sample);
     mixed_read_out<T>(rho, out, s_red, m, sample);  // the diagonal
     __syncthreads();
   }
@@ -632,15 +651,10 @@ __global__ __launch_bounds__(256) void mixed_sampled_kernel(const MixedOp* __res
   __shared__ double s_red[256];
   __shared__ double s_cdf[256];    // n <= 8: 2^n prefix sums
   __shared__ uint32_t s_cnt[256];  // and as many counts
-  const uint32_t DD = 1u << (2 * m.n);
-  C* rho = m.slab_in_lds ? reinterpret_cast<C*>(smem_raw) : workspace + (size_t)blockIdx.x * DD;
+  C* rho = m.slab_in_lds ? reinterpret_cast<C*>(smem_raw) : workspace + ((size_t)blockIdx.x << (2 * m.n));
 
   for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
-    for (int oi = 0; oi < m.n_ops; ++oi) {
-      const MixedOp op = prog[oi];
-      mixed_apply_op<T, LEVEL>(op, rho, nullptr, angle_rows, feats, gates, s_red, m, sample);
-      __syncthreads();
-    }
+    mixed_replay<T, LEVEL>(prog, rho, angle_rows, feats, gates, s_red, m, sample);
     mixed_sample_read_out<T>(rho, out + sample * m.out_ld, s_cdf, s_cnt, m.n, m.measure, sample, sh);
     __syncthreads();
   }
@@ -685,6 +699,12 @@ __device__ __forceinline__ void mixed_udag_b_u(V2<T>& b00, V2<T>& b01, V2<T>& b1
   b11 = cmul<T>(a10, u01) + cmul<T>(a11, u11);
 }
 
+// The seed, the CZ sign and the CNOT partner are the forward's helpers.  The three block loops are written out, not
+// calls of the walkers: with the loops as walker calls (and nothing else changed) the state and every single
+// contribution stay the same, but gradients that sum two contributions move by one unit in the last place -- the
+// compiler then contracts thread 0's `+= scale * s` behind each op differently.  (Building RY / GATE with mixed_unitary
+// kept the bits on the n = 6 cases of tools/mixed_bits.py; it waits for a change that runs the whole list and the
+// timing.)
 template <typename T, int LEVEL>
 __global__ __launch_bounds__(256) void mixed_backward_kernel(
     const MixedOp* __restrict__ prog, const double* __restrict__ angle_rows, const double* __restrict__ feats,
@@ -723,18 +743,7 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
 
     // ---- seed Lambda_N --------------------------------------------------------------------------------------------
     const double* __restrict__ g = grad_out + sample * b.gout_ld;
-    for (uint32_t k = tid; k < DD; k += 256) {
-      const uint32_t i = k >> n, j = k & (D - 1);
-      double v = 0.0;
-      if (i == j) {
-        if (m.measure == 0) {
-          v = g[i];
-        } else {
-          for (int w = 0; w < n; ++w) v += ((i >> (n - 1 - w)) & 1u) ? -g[w] : g[w];
-        }
-      }
-      lam[k] = C{(T)v, (T)0};
-    }
+    for (uint32_t k = tid; k < DD; k += 256) lam[k] = mixed_seed_elem<T>(g, k, m);
     __syncthreads();
 
     // ---- reverse sweep --------------------------------------------------------------------------------------------
@@ -800,22 +809,17 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
         }
         case kMixCZ: {
           const int qt = n - 1 - op.a;
-          for (uint32_t k = tid; k < DD; k += 256) {
-            const uint32_t i = k >> n, j = k & (D - 1);
-            const int si_ = ((i >> q) & (i >> qt) & 1), sj = ((j >> q) & (j >> qt) & 1);
-            if (si_ != sj) {
+          for (uint32_t k = tid; k < DD; k += 256)
+            if (mixed_cz_flips(k, q, qt, n)) {
               rho[k] = C{-rho[k].x, -rho[k].y};
               lam[k] = C{-lam[k].x, -lam[k].y};
             }
-          }
           break;
         }
         case kMixCNOT: {
           const int qt = n - 1 - op.a;
           for (uint32_t k = tid; k < DD; k += 256) {
-            const uint32_t i = k >> n, j = k & (D - 1);
-            const uint32_t pi = i ^ (((i >> q) & 1u) << qt), pj = j ^ (((j >> q) & 1u) << qt);
-            const uint32_t pk = (pi << n) | pj;
+            const uint32_t pk = mixed_cnot_index(k, q, qt, n);
             if (k < pk) {
               const C tr = rho[k], tl = lam[k];
               rho[k] = rho[pk];

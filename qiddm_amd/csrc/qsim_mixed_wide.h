@@ -15,7 +15,10 @@
 // The host cuts the program into segments (plan_mixed_wide in qiddm_mixed.hip) and uploads it sorted by segment.
 // Wires n-1 and n-2 (q = 0, 1) belong to every tile: the two lowest column bits are local, so a lane moves two
 // consecutive elements (16 bytes in float32) and four lanes cover 64 contiguous bytes.
-// Per 2 x 2 block and per element the arithmetic is that of mixed_apply_op (shared helpers in qsim_mixed.h).
+// Per 2 x 2 block and per element the arithmetic is that of the one-workgroup engine, and so is the walk over a wire's
+// blocks, on local ranks instead of global bits (MixedBlock1 and the block visitors of qsim_mixed.h).  What is the tile
+// engine's own sits below in one place for all its kernels: the indices a thread owns, the copies between slab and
+// tile, the walkers over owned elements and over a thread's blocks, and wide_channel_op, the channel kinds on a tile.
 // `dst_delta` (elements; 0 in the forward) moves the write-back to another set of slabs: the reverse sweep's replay
 // (qsim_mixed_wide_adjoint.h) leaves the state in front of a channel segment behind as its snapshot.
 #pragma once
@@ -63,6 +66,118 @@ __device__ __forceinline__ int wide_local_rank(const WideSegment& sg, int g) {
   return r;
 }
 
+// ---- tile plumbing: every kernel of the engine (here and in qsim_mixed_wide_adjoint.h) moves and walks its tiles with these
+// The global indices of the element pairs a thread owns: l = 2 (tid + 256 i), l + 1 -> k, k + 1 (lpos[0] = 0).  Ends
+// in a barrier.
+__device__ __forceinline__ void wide_owned_indices(const WideSegment& sg, uint32_t* s_lo, uint32_t* s_hi,
+                                                   uint32_t (&kown)[kWidePairs]) {
+  const int tid = threadIdx.x;
+  const uint32_t base = wide_deposit<kWideMaxTileBits>(blockIdx.x, sg.gpos);  // the tile number has n_tile_bits bits
+  if (tid < 64) {
+    s_lo[tid] = wide_deposit<6>(tid, sg.lpos);
+    s_hi[tid] = wide_deposit<kWideHiBits>(tid, sg.lpos + 6);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i) {
+    const uint32_t l = 2u * (tid + 256u * i);
+    kown[i] = base | s_lo[l & 63u] | s_hi[l >> 6];
+  }
+}
+// slab -> tile and tile -> slab, a thread its own pairs (a pair: 16 bytes in float32)
+template <typename T>
+__device__ __forceinline__ void wide_load_pair(V2<T>* tile, const V2<T>* slab, const uint32_t (&kown)[kWidePairs], int i) {
+  *reinterpret_cast<V4<T>*>(tile + 2u * (threadIdx.x + 256u * i)) = *reinterpret_cast<const V4<T>*>(slab + kown[i]);
+}
+template <typename T>
+__device__ __forceinline__ void wide_load_tile(V2<T>* tile, const V2<T>* slab, const uint32_t (&kown)[kWidePairs]) {
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i) wide_load_pair<T>(tile, slab, kown, i);
+}
+template <typename T>
+__device__ __forceinline__ void wide_store_tile(V2<T>* slab, const V2<T>* tile, const uint32_t (&kown)[kWidePairs],
+                                                int64_t dst_delta) {
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i)
+    *reinterpret_cast<V4<T>*>(slab + dst_delta + kown[i]) = *reinterpret_cast<const V4<T>*>(tile + 2u * (threadIdx.x + 256u * i));
+}
+// every element the thread owns, for the element-wise kinds: f(l, k), l its index in the tile and k in rho
+template <typename F>
+__device__ __forceinline__ void wide_for_owned(const uint32_t (&kown)[kWidePairs], F&& f) {
+#pragma unroll
+  for (int i = 0; i < kWidePairs; ++i) {
+    const uint32_t l = 2u * (threadIdx.x + 256u * i);
+    f(l, kown[i]);
+    f(l + 1u, kown[i] + 1u);
+  }
+}
+// the 2 x 2 blocks of the tile wire with column bit q, by local ranks
+__device__ __forceinline__ MixedBlock1 wide_block(const WideSegment& sg, int q, int n) {
+  return MixedBlock1{wide_local_rank(sg, q), wide_local_rank(sg, q + n)};
+}
+// mixed_walk_blocks on a tile: kWideBlocks blocks a thread, a constant, so the loops unroll
+template <typename T, typename F>
+__device__ __forceinline__ void wide_walk_blocks(V2<T>* tile, const MixedBlock1& b, F&& f) {
+#pragma unroll
+  for (int i = 0; i < kWideBlocks; ++i) mixed_block_visit<T>(tile, nullptr, threadIdx.x + 256u * i, b, f);
+}
+// the general two-wire channel on a tile (ADJOINT: S^H): 2^12 / 16 = 256 blocks of 4 x 4, one per thread
+template <typename T, bool ADJOINT>
+__device__ __forceinline__ void wide_channel2(const MixedOp& op, V2<T>* tile, const double* __restrict__ gates,
+                                              const MixedScalars& m, const WideSegment& sg) {
+  const int n = m.n, q = n - 1 - op.wire, q2 = n - 1 - op.wire2;
+  const MixedBlock2 bl = mixed_block2(wide_local_rank(sg, q), wide_local_rank(sg, q2), wide_local_rank(sg, q + n),
+                                      wide_local_rank(sg, q2 + n));
+  const auto su = mixed_super2<T>(op, gates);
+  for (uint32_t t = threadIdx.x; t < kWideTile / 16; t += 256) mixed_block_super2<T, ADJOINT>(su, tile, nullptr, mixed_block2_base(t, bl), bl);
+}
+
+// One op of a channel kind on a tile in LDS with this sample's strength: E, or with ADJOINT E^dagger.  It is the
+// channel body of mixed_wide_adjoint_channels_graded in both directions.  mixed_wide_sweep and
+// mixed_wide_adjoint_channels list the same cases themselves, one walker call each: the compiler fuses the native
+// arithmetic differently here (the kind is tested inside the walk) than in a walk of its own, so in float32 the two
+// give different last bits, and the float64 adjoint kernel holds 8 waves with its own list and 5 through this function.
+// LEVEL (MixedLevel, qsim_mixed.h): the general-channel cases the instantiation carries.  PhaseDamping works on the
+// elements its thread owns (any wire; E^dagger = E).  The caller puts a barrier between ops.
+template <typename T, int LEVEL, bool ADJOINT>
+__device__ __forceinline__ void wide_channel_op(const MixedOp& op, V2<T>* tile, const uint32_t (&kown)[kWidePairs],
+                                                const double* __restrict__ angle_rows, const double* __restrict__ gates,
+                                                const MixedScalars& m, const WideSegment& sg, int64_t sample) {
+  using C = V2<T>;
+  const int n = m.n, q = n - 1 - op.wire;
+  if constexpr (LEVEL >= kLevelChannel2) {
+    if (op.kind == kMixChannel2) {
+      wide_channel2<T, ADJOINT>(op, tile, gates, m, sg);
+      return;
+    }
+  }
+  if (op.kind == kMixPhaseDamp) {
+    const T off = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample)).off;
+    wide_for_owned(kown, [&](uint32_t l, uint32_t k) { tile[l] = mixed_phase_damp_elem<T>(tile[l], k, q, n, off); });
+    return;
+  }
+  // one walk for the general and the native kinds, the kind tested inside it
+  const bool general = LEVEL >= kLevelChannel && op.kind == kMixChannel;
+  MixedSuper<T> su{};
+  MixedChannel<T> ch{};
+  if constexpr (LEVEL >= kLevelChannel) {
+    if (general) su = mixed_super<T>(op, gates);
+  }
+  if (!general) ch = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample));
+  wide_walk_blocks<T>(tile, wide_block(sg, q, n), [&](C& m00, C& m01, C& m10, C& m11) {
+    if constexpr (LEVEL >= kLevelChannel) {
+      if (general) {
+        if (ADJOINT) mixed_block_super_adjoint<T>(su, m00, m01, m10, m11);
+        else mixed_block_super<T>(su, m00, m01, m10, m11);
+      }
+    }
+    if (!general) {
+      if (ADJOINT) mixed_block_channel_adjoint<T>(ch, m00, m01, m10, m11);
+      else mixed_block_channel<T>(ch, m00, m01, m10, m11);
+    }
+  });
+}
+
 // |v|^2 of every resident sample's feature row (AMP_EMBED), in the order of the 8-wire kernel
 __global__ __launch_bounds__(256) void mixed_wide_norms(const double* __restrict__ feats, double* __restrict__ norms,
                                                         const MixedScalars m, int64_t sample0) {
@@ -89,47 +204,21 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
   const int n = m.n, tid = threadIdx.x;
   const int64_t resident = blockIdx.y, sample = sample0 + resident;
   C* __restrict__ rho = slabs + ((size_t)resident << (2 * n));
-  const uint32_t base = wide_deposit<kWideMaxTileBits>(blockIdx.x, sg.gpos);  // the tile number has n_tile_bits bits
-  if (tid < 64) {
-    s_lo[tid] = wide_deposit<6>(tid, sg.lpos);
-    s_hi[tid] = wide_deposit<kWideHiBits>(tid, sg.lpos + 6);
-  }
-  __syncthreads();
-  // a thread owns the element pairs l = 2 (tid + 256 i), l + 1: global k, k + 1 (lpos[0] = 0)
   uint32_t kown[kWidePairs];
-#pragma unroll
-  for (int i = 0; i < kWidePairs; ++i) {
-    const uint32_t l = 2u * (tid + 256u * i);
-    kown[i] = base | s_lo[l & 63u] | s_hi[l >> 6];
-  }
+  wide_owned_indices(sg, s_lo, s_hi, kown);
 
   int oi = sg.op_begin;
   const int first_kind = prog[oi].kind;
   if (first_kind == kMixZero) {
-#pragma unroll
-    for (int i = 0; i < kWidePairs; ++i) {
-      const uint32_t l = 2u * (tid + 256u * i);
-      tile[l] = C{kown[i] == 0 ? (T)1 : (T)0, (T)0};
-      tile[l + 1] = C{(T)0, (T)0};
-    }
+    wide_for_owned(kown, [&](uint32_t l, uint32_t k) { tile[l] = C{k == 0 ? (T)1 : (T)0, (T)0}; });
     ++oi;
   } else if (first_kind == kMixAmpEmbed) {
     const double* __restrict__ row = feats + sample * m.feat_ld;
     const double inv = 1.0 / norms[resident];
-#pragma unroll
-    for (int i = 0; i < kWidePairs; ++i) {
-      const uint32_t l = 2u * (tid + 256u * i);
-      tile[l] = mixed_embed_elem<T>(row, kown[i], inv, m);
-      tile[l + 1] = mixed_embed_elem<T>(row, kown[i] + 1u, inv, m);
-    }
+    wide_for_owned(kown, [&](uint32_t l, uint32_t k) { tile[l] = mixed_embed_elem<T>(row, k, inv, m); });
     ++oi;
   } else {
-#pragma unroll
-    for (int i = 0; i < kWidePairs; ++i) {
-      const uint32_t l = 2u * (tid + 256u * i);
-      const V4<T> v = *reinterpret_cast<const V4<T>*>(rho + kown[i]);
-      *reinterpret_cast<V4<T>*>(tile + l) = v;
-    }
+    wide_load_tile<T>(tile, rho, kown);
   }
 
   // Diagonal ops work on the elements their thread owns: no barrier between two of them.
@@ -144,84 +233,32 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
       case kMixPhase: {
         C up, dn;
         mixed_phase_factors<T>(mixed_angle(op, angle_rows, m, sample), up, dn);
-#pragma unroll
-        for (int i = 0; i < kWidePairs; ++i) {
-          const uint32_t l = 2u * (tid + 256u * i);
-          tile[l] = mixed_phase_elem<T>(tile[l], kown[i], q, n, up, dn);
-          tile[l + 1] = mixed_phase_elem<T>(tile[l + 1], kown[i] + 1u, q, n, up, dn);
-        }
+        wide_for_owned(kown, [&](uint32_t l, uint32_t k) { tile[l] = mixed_phase_elem<T>(tile[l], k, q, n, up, dn); });
         break;
       }
       case kMixCZ: {
         const int qt = n - 1 - op.a;
-#pragma unroll
-        for (int i = 0; i < kWidePairs; ++i) {
-          const uint32_t l = 2u * (tid + 256u * i);
-          tile[l] = mixed_cz_elem<T>(tile[l], kown[i], q, qt, n);
-          tile[l + 1] = mixed_cz_elem<T>(tile[l + 1], kown[i] + 1u, q, qt, n);
-        }
+        wide_for_owned(kown, [&](uint32_t l, uint32_t k) { tile[l] = mixed_cz_elem<T>(tile[l], k, q, qt, n); });
         break;
       }
       case kMixPhaseDamp: {
         const T off = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample)).off;
-#pragma unroll
-        for (int i = 0; i < kWidePairs; ++i) {
-          const uint32_t l = 2u * (tid + 256u * i);
-          tile[l] = mixed_phase_damp_elem<T>(tile[l], kown[i], q, n, off);
-          tile[l + 1] = mixed_phase_damp_elem<T>(tile[l + 1], kown[i] + 1u, q, n, off);
-        }
+        wide_for_owned(kown, [&](uint32_t l, uint32_t k) { tile[l] = mixed_phase_damp_elem<T>(tile[l], k, q, n, off); });
         break;
       }
       case kMixRY:
       case kMixGate:
       case kMixAmpDamp:
-      case kMixDepol: {
-        const int a = wide_local_rank(sg, q), b = wide_local_rank(sg, q + n);
-        const uint32_t cj = 1u << a, ci = 1u << b;
+      case kMixDepol: {  // one walk for the unitary and the native channel kinds: two cost a resident wave
         const bool unitary = op.kind == kMixRY || op.kind == kMixGate;
         MixedU<T> u{};
         MixedChannel<T> ch{};
         if (unitary) u = mixed_unitary<T>(op, angle_rows, gates, m, sample);
         else ch = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample));
-#pragma unroll
-        for (int i = 0; i < kWideBlocks; ++i) {
-          const uint32_t l = insert_two_bits(tid + 256u * i, a, b);
-          C m00 = tile[l], m01 = tile[l | cj], m10 = tile[l | ci], m11 = tile[l | ci | cj];
+        wide_walk_blocks<T>(tile, wide_block(sg, q, n), [&](C& m00, C& m01, C& m10, C& m11) {
           if (unitary) mixed_block_unitary<T>(u, m00, m01, m10, m11);
           else mixed_block_channel<T>(ch, m00, m01, m10, m11);
-          tile[l] = m00;
-          tile[l | cj] = m01;
-          tile[l | ci] = m10;
-          tile[l | ci | cj] = m11;
-        }
-        break;
-      }
-      case kMixChannel2: {
-        if constexpr (LEVEL >= kLevelChannel2) {
-          const int q2 = n - 1 - op.wire2;
-          const MixedBlock2 b = mixed_block2(wide_local_rank(sg, q), wide_local_rank(sg, q2), wide_local_rank(sg, q + n),
-                                             wide_local_rank(sg, q2 + n));
-          const auto su = mixed_super2<T>(op, gates);
-          for (uint32_t t = tid; t < kWideTile / 16; t += 256) mixed_block_super2<T, false>(su, tile, nullptr, mixed_block2_base(t, b), b);
-        }
-        break;
-      }
-      case kMixChannel: {
-        if constexpr (LEVEL >= kLevelChannel) {
-          const int a = wide_local_rank(sg, q), b = wide_local_rank(sg, q + n);
-          const uint32_t cj = 1u << a, ci = 1u << b;
-          const MixedSuper<T> su = mixed_super<T>(op, gates);
-#pragma unroll
-          for (int i = 0; i < kWideBlocks; ++i) {
-            const uint32_t l = insert_two_bits(tid + 256u * i, a, b);
-            C m00 = tile[l], m01 = tile[l | cj], m10 = tile[l | ci], m11 = tile[l | ci | cj];
-            mixed_block_super<T>(su, m00, m01, m10, m11);
-            tile[l] = m00;
-            tile[l | cj] = m01;
-            tile[l | ci] = m10;
-            tile[l | ci | cj] = m11;
-          }
-        }
+        });
         break;
       }
       case kMixCNOT: {
@@ -241,15 +278,23 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         }
         break;
       }
+      case kMixChannel: {
+        if constexpr (LEVEL >= kLevelChannel) {
+          const MixedSuper<T> su = mixed_super<T>(op, gates);
+          wide_walk_blocks<T>(tile, wide_block(sg, q, n),
+                              [&](C& m00, C& m01, C& m10, C& m11) { mixed_block_super<T>(su, m00, m01, m10, m11); });
+        }
+        break;
+      }
+      case kMixChannel2: {
+        if constexpr (LEVEL >= kLevelChannel2) wide_channel2<T, false>(op, tile, gates, m, sg);
+        break;
+      }
       default: break;
     }
   }
   if (!owned) __syncthreads();
-#pragma unroll
-  for (int i = 0; i < kWidePairs; ++i) {
-    const uint32_t l = 2u * (tid + 256u * i);
-    *reinterpret_cast<V4<T>*>(rho + dst_delta + kown[i]) = *reinterpret_cast<const V4<T>*>(tile + l);
-  }
+  wide_store_tile<T>(rho, tile, kown, dst_delta);
 }
 
 // the diagonal of every resident sample -> probs / <Z_w> (the read-out of mixed_kernel)

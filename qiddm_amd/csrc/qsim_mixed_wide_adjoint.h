@@ -38,56 +38,24 @@ struct WideParam {
   double scale;
 };
 
-// the global indices of the element pairs a thread owns: l = 2 (tid + 256 i) -> k, k + 1 (as in mixed_wide_sweep)
-__device__ __forceinline__ void wide_owned_indices(const WideSegment& sg, uint32_t* s_lo, uint32_t* s_hi,
-                                                   uint32_t (&kown)[kWidePairs]) {
-  const int tid = threadIdx.x;
-  const uint32_t base = wide_deposit<kWideMaxTileBits>(blockIdx.x, sg.gpos);
-  if (tid < 64) {
-    s_lo[tid] = wide_deposit<6>(tid, sg.lpos);
-    s_hi[tid] = wide_deposit<kWideHiBits>(tid, sg.lpos + 6);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < kWidePairs; ++i) {
-    const uint32_t l = 2u * (tid + 256u * i);
-    kown[i] = base | s_lo[l & 63u] | s_hi[l >> 6];
-  }
-}
-
-// element k of Lambda_N = dL/drho_N: diag(g) for probs, sum_w g_w (1 - 2 bit_w) for <Z> (the seed of
-// mixed_backward_kernel)
-template <typename T>
-__device__ __forceinline__ V2<T> wide_seed_elem(const double* __restrict__ g, uint32_t k, const MixedScalars& m) {
-  const int n = m.n;
-  const uint32_t i = k >> n, j = k & ((1u << n) - 1u);
-  double v = 0.0;
-  if (i == j) {
-    if (m.measure == 0) {
-      v = g[i];
-    } else {
-      for (int w = 0; w < n; ++w) v += ((i >> (n - 1 - w)) & 1u) ? -g[w] : g[w];
-    }
-  }
-  return V2<T>{(T)v, (T)0};
-}
-
+// the Lambda tile of a reverse launch: read from its slab, or with `seed` generated as Lambda_N from grad_out
 template <typename T>
 __device__ __forceinline__ void wide_load_lambda(V2<T>* tile, const V2<T>* __restrict__ lam, const uint32_t (&kown)[kWidePairs],
                                                  const double* __restrict__ g, const MixedScalars& m, bool seed) {
-  const int tid = threadIdx.x;
 #pragma unroll
-  for (int i = 0; i < kWidePairs; ++i) {
-    const uint32_t l = 2u * (tid + 256u * i);
+  for (int i = 0; i < kWidePairs; ++i) {  // the test inside: hoisted, all loads are issued at once and cost registers
     if (seed) {
-      tile[l] = wide_seed_elem<T>(g, kown[i], m);
-      tile[l + 1] = wide_seed_elem<T>(g, kown[i] + 1u, m);
+      const uint32_t l = 2u * (threadIdx.x + 256u * i);
+      tile[l] = mixed_seed_elem<T>(g, kown[i], m);
+      tile[l + 1] = mixed_seed_elem<T>(g, kown[i] + 1u, m);
     } else {
-      *reinterpret_cast<V4<T>*>(tile + l) = *reinterpret_cast<const V4<T>*>(lam + kown[i]);
+      wide_load_pair<T>(tile, lam, kown, i);
     }
   }
 }
 
+// The kernel writes its loops over the two tiles out (the shared tile copies apart): at 256 vector registers every
+// other form of them is scheduled differently, and the float64 round at 10 wires measured 1 % slower on the walkers.
 // One unitary segment backwards on the rho tile and the Lambda tile of (tile, sample).  slot[oi] >= 0: the op feeds a
 // parameter and writes its tile partial(s) to partials[(resident * n_slots + slot + c) * tiles + tile].
 template <typename T>
@@ -108,11 +76,7 @@ __global__ __launch_bounds__(256) void mixed_wide_reverse_sweep(
   C* __restrict__ lam = lam_slabs + ((size_t)resident << (2 * n));
   uint32_t kown[kWidePairs];
   wide_owned_indices(sg, s_lo, s_hi, kown);
-#pragma unroll
-  for (int i = 0; i < kWidePairs; ++i) {
-    const uint32_t l = 2u * (tid + 256u * i);
-    *reinterpret_cast<V4<T>*>(rt + l) = *reinterpret_cast<const V4<T>*>(rho + kown[i]);
-  }
+  wide_load_tile<T>(rt, rho, kown);
   wide_load_lambda<T>(lt, lam, kown, grad_out + sample * b.gout_ld, m, b.seed != 0);
   __syncthreads();
 
@@ -225,20 +189,8 @@ __global__ __launch_bounds__(256) void mixed_wide_reverse_sweep(
     }
   }
   // rho_0 is not read again, and Lambda_0 only by the AMP_EMBED gradient
-  if (prep < 0) {
-#pragma unroll
-    for (int i = 0; i < kWidePairs; ++i) {
-      const uint32_t l = 2u * (tid + 256u * i);
-      *reinterpret_cast<V4<T>*>(rho + kown[i]) = *reinterpret_cast<const V4<T>*>(rt + l);
-    }
-  }
-  if (prep != kMixZero) {
-#pragma unroll
-    for (int i = 0; i < kWidePairs; ++i) {
-      const uint32_t l = 2u * (tid + 256u * i);
-      *reinterpret_cast<V4<T>*>(lam + kown[i]) = *reinterpret_cast<const V4<T>*>(lt + l);
-    }
-  }
+  if (prep < 0) wide_store_tile<T>(rho, rt, kown, 0);
+  if (prep != kMixZero) wide_store_tile<T>(lam, lt, kown, 0);
 }
 
 // One channel segment backwards: E^dagger on the Lambda tile of (tile, sample), ops in reverse.  LEVEL: as in
@@ -263,123 +215,32 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp
   bool owned = true;  // PhaseDamping works on the elements its thread owns: no barrier between two of them
   for (int oi = sg.op_end - 1; oi >= sg.op_begin; --oi) {
     const MixedOp op = prog[oi];
-    const int q = n - 1 - op.wire;
     const bool diag = op.kind == kMixPhaseDamp;
     if (!(diag && owned)) __syncthreads();
     owned = diag;
+    const int q = n - 1 - op.wire;
     if constexpr (LEVEL >= kLevelChannel2) {
-      if (op.kind == kMixChannel2) {  // S^H on vec of each 4 x 4 block
-        const int q2 = n - 1 - op.wire2;
-        const MixedBlock2 bl = mixed_block2(wide_local_rank(sg, q), wide_local_rank(sg, q2), wide_local_rank(sg, q + n),
-                                            wide_local_rank(sg, q2 + n));
-        const auto su = mixed_super2<T>(op, gates);
-        for (uint32_t t = tid; t < kWideTile / 16; t += 256) mixed_block_super2<T, true>(su, lt, nullptr, mixed_block2_base(t, bl), bl);
+      if (op.kind == kMixChannel2) {
+        wide_channel2<T, true>(op, lt, gates, m, sg);
         continue;
       }
     }
     if (LEVEL >= kLevelChannel && op.kind == kMixChannel) {  // S^H on vec of each block
-      const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
-      const uint32_t cj = 1u << a, ci = 1u << bb;
       const MixedSuper<T> su = mixed_super<T>(op, gates);
-#pragma unroll
-      for (int i = 0; i < kWideBlocks; ++i) {
-        const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
-        C l00 = lt[l], l01 = lt[l | cj], l10 = lt[l | ci], l11 = lt[l | ci | cj];
-        mixed_block_super_adjoint<T>(su, l00, l01, l10, l11);
-        lt[l] = l00;
-        lt[l | cj] = l01;
-        lt[l | ci] = l10;
-        lt[l | ci | cj] = l11;
-      }
+      wide_walk_blocks<T>(lt, wide_block(sg, q, n),
+                          [&](C& l00, C& l01, C& l10, C& l11) { mixed_block_super_adjoint<T>(su, l00, l01, l10, l11); });
       continue;
     }
     const MixedChannel<T> ch = mixed_channel<T>(op.kind, op.p);  // a < 0 throughout: the host sends other segments below
     if (diag) {
-#pragma unroll
-      for (int i = 0; i < kWidePairs; ++i) {
-        const uint32_t l = 2u * (tid + 256u * i);
-        lt[l] = mixed_phase_damp_elem<T>(lt[l], kown[i], q, n, ch.off);
-        lt[l + 1] = mixed_phase_damp_elem<T>(lt[l + 1], kown[i] + 1u, q, n, ch.off);
-      }
+      wide_for_owned(kown, [&](uint32_t l, uint32_t k) { lt[l] = mixed_phase_damp_elem<T>(lt[l], k, q, n, ch.off); });
     } else {
-      const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
-      const uint32_t cj = 1u << a, ci = 1u << bb;
-#pragma unroll
-      for (int i = 0; i < kWideBlocks; ++i) {
-        const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
-        C l00 = lt[l], l01 = lt[l | cj], l10 = lt[l | ci], l11 = lt[l | ci | cj];
-        mixed_block_channel_adjoint<T>(ch, l00, l01, l10, l11);
-        lt[l] = l00;
-        lt[l | cj] = l01;
-        lt[l | ci] = l10;
-        lt[l | ci | cj] = l11;
-      }
+      wide_walk_blocks<T>(lt, wide_block(sg, q, n),
+                          [&](C& l00, C& l01, C& l10, C& l11) { mixed_block_channel_adjoint<T>(ch, l00, l01, l10, l11); });
     }
   }
   if (!owned) __syncthreads();
-#pragma unroll
-  for (int i = 0; i < kWidePairs; ++i) {
-    const uint32_t l = 2u * (tid + 256u * i);
-    *reinterpret_cast<V4<T>*>(lam + kown[i]) = *reinterpret_cast<const V4<T>*>(lt + l);
-  }
-}
-
-// One op of a channel segment on a tile in LDS, with this sample's strength: E, or with ADJOINT E^dagger (the
-// arithmetic of mixed_wide_sweep and of mixed_wide_adjoint_channels).  The caller puts a barrier between two ops.
-template <typename T, int LEVEL, bool ADJOINT>
-__device__ __forceinline__ void wide_channel_op(const MixedOp& op, V2<T>* tile, const uint32_t (&kown)[kWidePairs],
-                                                const double* __restrict__ angle_rows, const double* __restrict__ gates,
-                                                const MixedScalars& m, const WideSegment& sg, int64_t sample) {
-  using C = V2<T>;
-  const int n = m.n, tid = threadIdx.x, q = n - 1 - op.wire;
-  if constexpr (LEVEL >= kLevelChannel2) {
-    if (op.kind == kMixChannel2) {
-      const int q2 = n - 1 - op.wire2;
-      const MixedBlock2 bl = mixed_block2(wide_local_rank(sg, q), wide_local_rank(sg, q2), wide_local_rank(sg, q + n),
-                                          wide_local_rank(sg, q2 + n));
-      const auto su = mixed_super2<T>(op, gates);
-      for (uint32_t t = tid; t < kWideTile / 16; t += 256) mixed_block_super2<T, ADJOINT>(su, tile, nullptr, mixed_block2_base(t, bl), bl);
-      return;
-    }
-  }
-  if (op.kind == kMixPhaseDamp) {  // element-wise on any wire; E^dagger = E
-    const T off = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample)).off;
-#pragma unroll
-    for (int i = 0; i < kWidePairs; ++i) {
-      const uint32_t l = 2u * (tid + 256u * i);
-      tile[l] = mixed_phase_damp_elem<T>(tile[l], kown[i], q, n, off);
-      tile[l + 1] = mixed_phase_damp_elem<T>(tile[l + 1], kown[i] + 1u, q, n, off);
-    }
-    return;
-  }
-  const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
-  const uint32_t cj = 1u << a, ci = 1u << bb;
-  const bool general = LEVEL >= kLevelChannel && op.kind == kMixChannel;
-  MixedSuper<T> su{};
-  MixedChannel<T> ch{};
-  if constexpr (LEVEL >= kLevelChannel) {
-    if (general) su = mixed_super<T>(op, gates);
-  }
-  if (!general) ch = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample));
-#pragma unroll
-  for (int i = 0; i < kWideBlocks; ++i) {
-    const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
-    C m00 = tile[l], m01 = tile[l | cj], m10 = tile[l | ci], m11 = tile[l | ci | cj];
-    if constexpr (LEVEL >= kLevelChannel) {
-      if (general) {
-        if (ADJOINT) mixed_block_super_adjoint<T>(su, m00, m01, m10, m11);
-        else mixed_block_super<T>(su, m00, m01, m10, m11);
-      }
-    }
-    if (!general) {
-      if (ADJOINT) mixed_block_channel_adjoint<T>(ch, m00, m01, m10, m11);
-      else mixed_block_channel<T>(ch, m00, m01, m10, m11);
-    }
-    tile[l] = m00;
-    tile[l | cj] = m01;
-    tile[l | ci] = m10;
-    tile[l | ci | cj] = m11;
-  }
+  wide_store_tile<T>(lam, lt, kown, 0);
 }
 
 // A channel segment that holds a native channel with a >= 0 (strength from a row), backwards: as
@@ -415,11 +276,7 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels_graded(
     const MixedOp op = prog[oi];
     const int sl = slot[oi];
     if (sl >= 0) {  // uniform over the workgroup
-#pragma unroll
-      for (int i = 0; i < kWidePairs; ++i) {
-        const uint32_t l = 2u * (tid + 256u * i);
-        *reinterpret_cast<V4<T>*>(rt + l) = *reinterpret_cast<const V4<T>*>(rho + kown[i]);
-      }
+      wide_load_tile<T>(rt, rho, kown);
       for (int oj = sg.op_begin; oj < oi; ++oj) {
         __syncthreads();
         wide_channel_op<T, LEVEL, false>(prog[oj], rt, kown, angle_rows, gates, m, sg, sample);
@@ -429,21 +286,15 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels_graded(
       const double strength = mixed_angle(op, angle_rows, m, sample);
       double acc_off = 0.0, acc_diag = 0.0;
       if (op.kind == kMixPhaseDamp) {  // any wire: the off-diagonal elements of its blocks among the owned ones
-#pragma unroll
-        for (int i = 0; i < kWidePairs; ++i) {
-          const uint32_t l = 2u * (tid + 256u * i);
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const uint32_t k = kown[i] + e;
-            if (((k >> (q + n)) ^ (k >> q)) & 1u) acc_off += mixed_re_dot<T>(lt[l + e], rt[l + e]);
-          }
-        }
-      } else {
-        const int a = wide_local_rank(sg, q), bb = wide_local_rank(sg, q + n);
-        const uint32_t cj = 1u << a, ci = 1u << bb;
+        wide_for_owned(kown, [&](uint32_t l, uint32_t k) {
+          if (((k >> (q + n)) ^ (k >> q)) & 1u) acc_off += mixed_re_dot<T>(lt[l], rt[l]);
+        });
+      } else {  // read only: the one walk over blocks that stores nothing
+        const MixedBlock1 bl = wide_block(sg, q, n);
+        const uint32_t cj = bl.cj(), ci = bl.ci();
 #pragma unroll
         for (int i = 0; i < kWideBlocks; ++i) {
-          const uint32_t l = insert_two_bits(tid + 256u * i, a, bb);
+          const uint32_t l = bl.base(tid + 256u * i);
           acc_off += mixed_strength_grad_off<T>(rt[l | cj], rt[l | ci], lt[l | cj], lt[l | ci]);
           acc_diag += mixed_strength_grad_diag<T>(op.kind, rt[l], rt[l | ci | cj], lt[l], lt[l | ci | cj]);
         }
@@ -457,11 +308,7 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels_graded(
     wide_channel_op<T, LEVEL, true>(op, lt, kown, angle_rows, gates, m, sg, sample);
     __syncthreads();
   }
-#pragma unroll
-  for (int i = 0; i < kWidePairs; ++i) {
-    const uint32_t l = 2u * (tid + 256u * i);
-    *reinterpret_cast<V4<T>*>(lam + kown[i]) = *reinterpret_cast<const V4<T>*>(lt + l);
-  }
+  wide_store_tile<T>(lam, lt, kown, 0);
 }
 
 // (Re(Lambda_0) v)_i, one wave per row i of every resident sample's Lambda: lv[resident * 2^n + i]
