@@ -88,7 +88,8 @@ typedef enum qiddm_imprimitive {
 
 typedef enum qiddm_measure {
   QIDDM_MEAS_PROBS = 0, /* qml.probs(wires=range(n))                 (nn/qdense.py:47)       */
-  QIDDM_MEAS_EXPZ = 1   /* [qml.expval(qml.PauliZ(i)) for i in ...]  (nn/qdense.py:264)      */
+  QIDDM_MEAS_EXPZ = 1,  /* [qml.expval(qml.PauliZ(i)) for i in ...]  (nn/qdense.py:264)      */
+  QIDDM_MEAS_OBS = 2    /* density-matrix executor only: the Pauli-word table the program ends in (QIDDM_MIX_OBS) */
 } qiddm_measure;
 
 typedef enum qiddm_dtype {
@@ -648,12 +649,32 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *                             no sweep and not as a non-diagonal op; its op_segment entry is -1.  PennyLane's
  *                             default.mixed with shots=... is a program that ends in this op; readout_prob is a BitFlip
  *                             (QIDDM_MIX_CHANNEL) on every wire in front of it.
- * Kinds 10, 11, 13..15, 17..31 and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
+ *   QIDDM_MIX_OBS (= 20)      one term of the MEASUREMENT TABLE, not an operation on rho: coefficient `p` times a Pauli word.
+ *                             `wire` is the word's x-mask (the wires that carry X or Y), `a` its z-mask (Z or Y), wire w at
+ *                             bit n-1-w of each, both in [0, 2^n); `reserved` is the output column; `scale` is not read.
+ *                             The table is the tail of the program: from the first QIDDM_MIX_OBS on every op is one
+ *                             (`op %d: only measurement terms may follow the first one`), 1 .. QIDDM_MIX_MAX_OBS = 256 of
+ *                             them, `p` finite, the first term's column 0 and every later one equal to the previous
+ *                             term's or larger by 1.  Terms that share a column add up (a Hamiltonian).  measure =
+ *                             QIDDM_MEAS_OBS reads it: with ny = popcount(x & z),
+ *                               out[sample][c] = sum over the terms t of column c of
+ *                                                p_t Re( i^ny_t sum_k (-1)^popcount(k & z_t) rho[k][k ^ x_t] ),
+ *                             which is sum_t p_t Tr(rho P_t) with Y = [[0, -i], [i, 0]]; float64, fixed-order sums, no
+ *                             atomics (reruns are bit-identical).  out / grad_out are (batch, last column + 1).  The
+ *                             reverse sweeps start from Lambda_N = sum_t grad_out[sample][column_t] p_t P_t, a Hermitian
+ *                             matrix that is complex when a word holds Y and not diagonal when it holds X or Y.
+ *                             QIDDM_MEAS_OBS without a table, and a table under QIDDM_MEAS_PROBS / _EXPZ, are
+ *                             QIDDM_ERR_INVALID; a QIDDM_MIX_SHOTS anywhere in a program with a table is
+ *                             QIDDM_ERR_UNSUPPORTED (shots of a word with X or Y need a basis rotation).  The planners and
+ *                             the *_workspace_bytes functions that read a program check the table in full, count it in no
+ *                             sweep and no snapshot; its op_segment entries are -1.
+ * Kinds 10, 11, 13..15, 17..19, 21..31 and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
- * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n) float64 DEVICE arrays.
+ * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n | columns of the table) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
  * batch / n_ops, measure (batch == 0 then returns QIDDM_OK with no pointer looked at), program (not empty, starts with a
- * state preparation), negative n_rows / n_gates, angle_rows / rows_ld, gates, the ops one by one (kind, wire, target wire
+ * state preparation), the measurement table (all of it, then against `measure`), negative n_rows / n_gates,
+ * angle_rows / rows_ld, gates, the ops in front of the table one by one (kind, wire, target wire
  * or second wire -- `op %d: bad second wire %d` when it is outside 0..n-1 or equal to `wire` --; QIDDM_MIX_SHOTS instead:
  * its position, wire / reserved, shots, seed, offset --,
  * then the operand they index: features / feat_ld / n_features, angle row, gate, probability (a >= 0: angle row, then
@@ -665,10 +686,12 @@ enum {
   QIDDM_MIX_CNOT, QIDDM_MIX_PHASE_DAMP, QIDDM_MIX_AMP_DAMP, QIDDM_MIX_DEPOL,
   QIDDM_MIX_SHOTS = 12,
   QIDDM_MIX_CHANNEL = 16,
+  QIDDM_MIX_OBS = 20,
   QIDDM_MIX_CHANNEL2 = 32
 };
+#define QIDDM_MIX_MAX_OBS 256 /* terms of a measurement table */
 typedef struct qiddm_mixed_op {
-  int32_t kind, wire, a, reserved; /* reserved: the second wire of QIDDM_MIX_CHANNEL2; no other kind reads it */
+  int32_t kind, wire, a, reserved; /* reserved: the second wire of QIDDM_MIX_CHANNEL2, the column of QIDDM_MIX_OBS */
   double p, scale;
 } qiddm_mixed_op_t;
 int64_t qiddm_mixed_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, int32_t n_ops);

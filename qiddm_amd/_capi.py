@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("QIDDM_HIP_LIB") or os.path.join(LIB_DIR, "libqiddm_hi
 QIDDM_OK = 0
 ENC_NONE, ENC_AMPLITUDE, ENC_RZ, ENC_RY, ENC_RY_BLOCKS = 0, 1, 2, 3, 4
 IMP_CNOT, IMP_CZ = 0, 1
-MEAS_PROBS, MEAS_EXPZ = 0, 1
+MEAS_PROBS, MEAS_EXPZ, MEAS_OBS = 0, 1, 2  # MEAS_OBS (density-matrix executor): the MIX_OBS table the program ends in
 F32, F64 = 0, 1
 
 
@@ -72,11 +72,15 @@ class TrainArgs(ctypes.Structure):
 MIX_ZERO, MIX_AMP_EMBED, MIX_PHASE, MIX_RY, MIX_GATE, MIX_CZ, MIX_CNOT, MIX_PHASE_DAMP, MIX_AMP_DAMP, MIX_DEPOL = range(10)
 MIX_SHOTS = 12  # last op only: the read-out is sampled; `a` = shots, `p` = seed, `scale` = stream offset
 MIX_CHANNEL = 16  # general one-wire channel: `a` = first of four gate rows holding the superoperator
+# tail of the program: one term of the measurement table, `p` times the Pauli word with x-mask `wire` and z-mask `a`
+# (wire w at bit n-1-w), output column `reserved`; at most MIX_MAX_OBS terms
+MIX_OBS, MIX_MAX_OBS = 20, 256
 MIX_CHANNEL2 = 32  # general two-wire channel: `a` = first of 64 gate rows (16 x 16), `reserved` = the second wire
 
 
 class MixedOp(ctypes.Structure):
-    """``qiddm_mixed_op_t``.  ``reserved`` is 0 except for ``MIX_CHANNEL2``, which reads its second wire there."""
+    """``qiddm_mixed_op_t``.  ``reserved`` is 0 except for ``MIX_CHANNEL2``, which reads its second wire there, and ``MIX_OBS``, which reads
+    its output column there."""
 
     _fields_ = [("kind", ctypes.c_int32), ("wire", ctypes.c_int32), ("a", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("p", ctypes.c_double), ("scale", ctypes.c_double)]

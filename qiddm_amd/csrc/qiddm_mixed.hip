@@ -8,6 +8,9 @@
 // functions check sizes with check_sizes() and the two *_plan functions validate through the planner alone.
 // A program may end in QIDDM_MIX_SHOTS (the sampled read-out, qsim_mixed_shots.h): the forwards keep it out of the ops the
 // kernels walk and launch the sampling kernels with its fields (shots_of); everything reverse refuses it (refuse_sampled).
+// Or it ends in a table of QIDDM_MIX_OBS terms (QIDDM_MEAS_OBS: Pauli-word expectation values): check_obs_tail validates
+// it wherever a program is read, the planners leave it out of every sweep, and it is uploaded behind the ops so that the
+// read-out and the seed of the reverse sweeps find it at prog[n_body ..).
 #include "capi_common.h"
 
 #include <hip/hip_runtime.h>
@@ -34,7 +37,8 @@ using qiddm_capi::launched;
 
 static_assert(sizeof(qiddm::MixedOp) == sizeof(qiddm_mixed_op_t), "program layout");
 static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixChannel == (int)QIDDM_MIX_CHANNEL &&
-                  (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2 && (int)qiddm::kMixShots == (int)QIDDM_MIX_SHOTS,
+                  (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2 && (int)qiddm::kMixShots == (int)QIDDM_MIX_SHOTS &&
+                  (int)qiddm::kMixObs == (int)QIDDM_MIX_OBS,
               "op kinds");
 static_assert(offsetof(qiddm::MixedOp, wire2) == offsetof(qiddm_mixed_op_t, reserved), "the second wire travels in `reserved`");
 
@@ -135,6 +139,43 @@ int refuse_sampled(const qiddm_mixed_op_t* program, int32_t n_ops) {
   return QIDDM_OK;
 }
 
+// The measurement table a program may end in: QIDDM_MIX_OBS ops and nothing else from the first one on.  Checks all of it
+// (position, count, masks, coefficient, columns; no QIDDM_MIX_SHOTS beside it) and counts its terms and columns; a
+// program without one gives 0, 0.  `n_qubits` has been checked.
+int check_obs_tail(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, int32_t* n_obs, int32_t* n_cols) {
+  *n_obs = *n_cols = 0;
+  if (!program) return QIDDM_OK;
+  int first = -1, shots = -1;
+  for (int i = 0; i < n_ops; ++i) {
+    if (program[i].kind == qiddm::kMixObs && first < 0) first = i;
+    if (program[i].kind == qiddm::kMixShots && shots < 0) shots = i;
+  }
+  if (first < 0) return QIDDM_OK;
+  if (shots >= 0)
+    return fail(QIDDM_ERR_UNSUPPORTED,
+                "op %d: a sampled read-out beside a measurement table (shots of a Pauli word need a basis rotation)", shots);
+  for (int i = first; i < n_ops; ++i)
+    if (program[i].kind != qiddm::kMixObs)
+      return fail(QIDDM_ERR_INVALID, "op %d: only measurement terms may follow the first one (op %d)", i, first);
+  if (n_ops - first > QIDDM_MIX_MAX_OBS)
+    return fail(QIDDM_ERR_INVALID, "op %d: more than %d measurement terms", first + QIDDM_MIX_MAX_OBS, QIDDM_MIX_MAX_OBS);
+  const int64_t d = (int64_t)1 << n;
+  int32_t col = 0;
+  for (int i = first; i < n_ops; ++i) {
+    const qiddm_mixed_op_t& op = program[i];
+    if (op.wire < 0 || op.wire >= d) return fail(QIDDM_ERR_INVALID, "op %d: x-mask %d outside [0, 2^%d)", i, op.wire, n);
+    if (op.a < 0 || op.a >= d) return fail(QIDDM_ERR_INVALID, "op %d: z-mask %d outside [0, 2^%d)", i, op.a, n);
+    if (!std::isfinite(op.p)) return fail(QIDDM_ERR_INVALID, "op %d: measurement coefficient %g not finite", i, op.p);
+    if (i == first ? op.reserved != 0 : (op.reserved != col && op.reserved != col + 1))
+      return fail(QIDDM_ERR_INVALID, "op %d: output column %d (columns start at 0 and rise by at most 1; the last was %d)", i,
+                  op.reserved, i == first ? -1 : col);
+    col = op.reserved;
+  }
+  *n_obs = n_ops - first;
+  *n_cols = col + 1;
+  return QIDDM_OK;
+}
+
 // kind, wire and target / second wire of op i: all the planner reads of an op, and the first thing the validator checks
 // of it.  QIDDM_MIX_SHOTS is checked here in full (position, wire / reserved, shots, seed, offset): it indexes no operand.
 int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops) {
@@ -177,27 +218,37 @@ struct MixedCall {
   const double* gates;
   int32_t n_gates, measure;
   int64_t batch;
-  int64_t width() const { return measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits; }  // of out / grad_out
+  int32_t n_obs = 0, n_cols = 0;  // the measurement table the program ends in: set by check_call
+  int64_t width() const {  // of out / grad_out
+    return measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : measure == QIDDM_MEAS_OBS ? n_cols : n_qubits;
+  }
+  int32_t n_body() const { return n_ops - n_obs; }  // the ops in front of the measurement table
 };
 
 // Everything the compute entry points check about a MixedCall, in the order include/qiddm_hip.h states: wires, dtype,
 // negative batch / n_ops, measure; [an empty batch is QIDDM_OK here: nothing further is looked at, the caller returns];
-// program, n_rows / n_gates, angle_rows / rows_ld, gates, then op by op against the arguments it indexes.
-// *embeds: the program has an AMP_EMBED.
-int check_call(const MixedCall& c, const Engine& e, bool* embeds) {
+// program, its measurement table (against `measure` too), n_rows / n_gates, angle_rows / rows_ld, gates, then op by op
+// against the arguments it indexes.  *embeds: the program has an AMP_EMBED.  Fills in c.n_obs, c.n_cols.
+int check_call(MixedCall& c, const Engine& e, bool* embeds) {
   int rc = check_sizes(c.n_qubits, c.dtype, c.batch, c.n_ops, e);
   if (rc != QIDDM_OK) return rc;
-  if (c.measure != QIDDM_MEAS_PROBS && c.measure != QIDDM_MEAS_EXPZ) return fail(QIDDM_ERR_INVALID, "unknown measure %d", c.measure);
+  if (c.measure != QIDDM_MEAS_PROBS && c.measure != QIDDM_MEAS_EXPZ && c.measure != QIDDM_MEAS_OBS)
+    return fail(QIDDM_ERR_INVALID, "unknown measure %d", c.measure);
   if (c.batch == 0) return QIDDM_OK;
   if ((rc = check_program_start(c.program, c.n_ops)) != QIDDM_OK) return rc;
+  if ((rc = check_obs_tail(c.n_qubits, c.program, c.n_ops, &c.n_obs, &c.n_cols)) != QIDDM_OK) return rc;
+  if (c.measure == QIDDM_MEAS_OBS && c.n_obs == 0)
+    return fail(QIDDM_ERR_INVALID, "measure QIDDM_MEAS_OBS needs a measurement table: QIDDM_MIX_OBS ops at the end of the program");
+  if (c.measure != QIDDM_MEAS_OBS && c.n_obs > 0)
+    return fail(QIDDM_ERR_INVALID, "op %d: a measurement table needs measure QIDDM_MEAS_OBS (got %d)", c.n_body(), c.measure);
   if (c.n_rows < 0 || c.n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
   if (c.n_rows > 0 && (!c.angle_rows || c.rows_ld < c.batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
   if (c.n_gates > 0 && !c.gates) return fail(QIDDM_ERR_INVALID, "gates is NULL");
   const int64_t d = (int64_t)1 << c.n_qubits;
   *embeds = false;
-  for (int i = 0; i < c.n_ops; ++i) {
+  for (int i = 0; i < c.n_body(); ++i) {
     const qiddm_mixed_op_t& op = c.program[i];
-    if ((rc = check_op_wires(c.n_qubits, op, i, c.n_ops)) != QIDDM_OK) return rc;
+    if ((rc = check_op_wires(c.n_qubits, op, i, c.n_body())) != QIDDM_OK) return rc;
     switch (op.kind) {
       case qiddm::kMixAmpEmbed:
         if (!c.features || c.n_features < 1 || c.n_features > d)
@@ -262,6 +313,7 @@ qiddm::MixedScalars make_scalars(const MixedCall& c, int32_t n_ops, int32_t n_fe
   qiddm::MixedScalars m{};
   m.n = c.n_qubits;
   m.n_ops = n_ops;
+  m.n_obs = c.n_obs;  // the table sits behind the n_ops ops of the uploaded program
   m.measure = c.measure;
   m.n_features = n_features;
   m.batch = c.batch;
@@ -385,7 +437,11 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
   const uint32_t all = (1u << n) - 1u;
   // a sampled read-out (last op) is no op on rho: checked, then left out of every segment.  plan->order holds the
   // n_ops - 1 ops in front of it and its op_segment stays -1.
-  const int32_t n_all = n_ops;
+  // A measurement table (the tail of QIDDM_MIX_OBS terms) likewise: checked, in no sweep, op_segment -1.
+  int32_t n_obs = 0, n_cols = 0;
+  if ((rc = check_obs_tail(n, program, n_ops, &n_obs, &n_cols)) != QIDDM_OK) return rc;
+  n_ops -= n_obs;
+  const int32_t n_table = n_ops + n_obs, n_all = n_ops;  // n_all: the ops that a sampled read-out must be the last of
   if (ends_in_shots(program, n_ops)) {
     if ((rc = check_op_wires(n, program[n_ops - 1], n_ops - 1, n_all)) != QIDDM_OK) return rc;
     --n_ops;
@@ -402,7 +458,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
   }
   plan->order.clear();
   plan->order.reserve(n_ops);
-  plan->op_segment.assign(n_all, -1);
+  plan->op_segment.assign(n_table, -1);
   plan->segments.clear();
   plan->seg_channel.clear();
   plan->seg_level.clear();
@@ -492,6 +548,8 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
     }
     if (sh.shots)  // the sampled read-out, keyed by the absolute row s0 + block
       hipLaunchKernelGGL(qiddm::mixed_wide_sampled_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0, sh);
+    else if (m.measure == QIDDM_MEAS_OBS)
+      hipLaunchKernelGGL(qiddm::mixed_wide_obs_read_out<T>, dim3(chunk), dim3(256), 0, st, prog, slabs, out, m, s0);
     else
       hipLaunchKernelGGL(qiddm::mixed_wide_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0);
     if (const int rc = launched("mixed_wide"); rc != QIDDM_OK) return rc;
@@ -505,6 +563,7 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
 struct WideBwdPlan {
   WidePlan plan;                          // of the live ops, channels split off into segments of their own
   int32_t live_begin = 0, n_live = 0;
+  int32_t n_obs = 0;                      // terms of the measurement table behind the live ops (in no segment)
   int32_t replay_end = 0;                 // segments [0, replay_end) are replayed: up to the last unitary one
   int32_t n_snaps = 0;                    // channel segments among them
   int32_t n_slots = 0;                    // tile partials per (tile, sample)
@@ -517,8 +576,11 @@ struct WideBwdPlan {
 
 int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WideBwdPlan* bp) {
   int rc = check_plan_input(n, program, n_ops);
+  int32_t n_cols = 0;
+  if (rc == QIDDM_OK) rc = check_obs_tail(n, program, n_ops, &bp->n_obs, &n_cols);
   if (rc == QIDDM_OK) rc = refuse_sampled(program, n_ops);
   if (rc != QIDDM_OK) return rc;
+  n_ops -= bp->n_obs;  // the table has been checked; the plan is of the ops in front of it
   bp->live_begin = 0;
   for (int i = 0; i < n_ops; ++i)
     if (is_prep(program[i].kind)) bp->live_begin = i;
@@ -570,7 +632,7 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
   return QIDDM_OK;
 }
 
-// Workspace: [sorted live program | slot per op | params | group_begin] then, per resident sample, |v|^2 and
+// Workspace: [sorted live program, measurement table | slot per op | params | group_begin] then, per resident sample, |v|^2 and
 // Re(Lambda_0) v (AMP_EMBED), the tile partials, and 2 + n_snaps slabs.
 struct WideBwdGeometry {
   int64_t slab_bytes, aux_bytes, part_bytes, per_sample, resident;
@@ -586,7 +648,7 @@ WideBwdGeometry wide_backward_geometry(int32_t n, int32_t dtype, int64_t batch, 
   const int64_t cap = kWideSlabBudget / g.per_sample;
   g.resident = batch < cap ? batch : cap;
   if (g.resident < 1) g.resident = 1;
-  g.off_slot = program_bytes(bp.n_live);
+  g.off_slot = program_bytes(bp.n_live + bp.n_obs);
   g.off_params = g.off_slot + round256((int64_t)bp.n_live * 4);
   g.off_groups = g.off_params + round256((int64_t)bp.params.size() * (int64_t)sizeof(qiddm::WideParam));
   g.head = g.off_groups + round256((int64_t)bp.group_begin.size() * 4);
@@ -634,6 +696,11 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
     }
     qiddm::WideBwdScalars bs = b;
     bs.seed = 1;
+    if (m.measure == QIDDM_MEAS_OBS) {  // Lambda_N of the measurement table: a launch of its own, the sweeps read the slab
+      hipLaunchKernelGGL(qiddm::mixed_wide_obs_seed<T>, dim3((unsigned)(DD / 1024), chunk), block, 0, st, prog, grad_out, lam,
+                         m, bs, s0);
+      bs.seed = 0;
+    }
     for (int s = n_seg - 1; s >= 0; --s) {
       if (!bp.plan.seg_channel[s]) {
         rc = launch<qiddm::mixed_wide_reverse_sweep<T>>(2 * tile_bytes, dim3(tiles, chunk), block, 2 * tile_bytes, st,
@@ -688,8 +755,8 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
                         int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with, const double* gates,
                         int32_t n_gates, int32_t measure, int64_t batch, double* out, int64_t out_ld, void* workspace,
                         int64_t workspace_bytes, void* stream) {
-  const MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
-                    enc_offset, pad_with, gates, n_gates, measure, batch};
+  MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+              enc_offset, pad_with, gates, n_gates, measure, batch};
   bool embeds = false;
   int rc = check_call(c, kOneWorkgroup, &embeds);
   if (rc != QIDDM_OK || batch == 0) return rc;
@@ -700,7 +767,8 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
   const qiddm::MixedShots sh = shots_of(program, n_ops);
-  const int32_t n_body = n_ops - (sh.shots ? 1 : 0);  // the ops the kernel walks: a sampled read-out is none of them
+  // the ops the kernel walks: a sampled read-out is none of them, nor is the measurement table
+  const int32_t n_body = c.n_body() - (sh.shots ? 1 : 0);
   const qiddm::MixedScalars m = make_scalars(c, n_body, n_features, out_ld, g.in_lds);
   const size_t smem = g.in_lds ? (size_t)g.slab_bytes : 0;
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
@@ -713,6 +781,10 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
             kMaxLds - 8192 /* the kernel also has 5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
             "mixed_sampled_kernel", prog, angle_rows, features, gates, out,
             reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m, sh);
+      if (measure == QIDDM_MEAS_OBS)
+        return launch<qiddm::mixed_obs_kernel<T, decltype(lv)::value>>(
+            kMaxLds - 8192 /* the kernel also has 4 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
+            "mixed_obs_kernel", prog, angle_rows, features, gates, out, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m);
       return launch<qiddm::mixed_kernel<T, decltype(lv)::value>>(
           kMaxLds - 4096 /* the kernel also has 2 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
           "mixed_kernel", prog, angle_rows, features, gates, out, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m);
@@ -724,8 +796,10 @@ int64_t qiddm_mixed_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, in
                                              const qiddm_mixed_op_t* program, int32_t n_ops, int32_t max_blocks) {
   MixedGeometry g;
   int32_t n_snaps = 0;
+  int32_t n_obs = 0, n_cols = 0;  // a measurement table is checked and takes room in the program head only
   int rc = check_sizes(n_qubits, dtype, batch, n_ops, kOneWorkgroup);
   if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc == QIDDM_OK) rc = check_obs_tail(n_qubits, program, n_ops, &n_obs, &n_cols);
   if (rc == QIDDM_OK) rc = refuse_sampled(program, n_ops);
   if (rc == QIDDM_OK) rc = mixed_backward_geometry(n_qubits, dtype, batch, program, n_ops, max_blocks, &g, &n_snaps);
   if (rc != QIDDM_OK) return rc;
@@ -738,8 +812,8 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
                          int32_t n_gates, int32_t measure, int64_t batch, const double* grad_out, int64_t gout_ld,
                          double* grad_rows, double* grad_gates, double* grad_features, int32_t max_blocks,
                          void* workspace, int64_t workspace_bytes, void* stream) {
-  const MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
-                    enc_offset, pad_with, gates, n_gates, measure, batch};
+  MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+              enc_offset, pad_with, gates, n_gates, measure, batch};
   bool embeds = false;
   int rc = check_call(c, kOneWorkgroup, &embeds);
   if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);  // refused for an empty batch as well
@@ -753,7 +827,7 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
-  const qiddm::MixedScalars m = make_scalars(c, n_ops, embeds ? n_features : 0, 0, g.in_lds);
+  const qiddm::MixedScalars m = make_scalars(c, c.n_body(), embeds ? n_features : 0, 0, g.in_lds);
   qiddm::MixedBwdScalars b{};
   b.gout_ld = gout_ld;
   b.n_rows = n_rows;
@@ -765,10 +839,13 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     return for_level(level, [&](auto lv) {
-      return launch<qiddm::mixed_backward_kernel<T, decltype(lv)::value>>(
-          kMaxLds - 8192 /* the kernel also has 4.5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
-          "mixed_backward_kernel", prog, angle_rows, features, gates, grad_out, grad_rows, grad_gates,
-          embeds ? grad_features : nullptr, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m, b);
+      const auto run = [&](auto obs) {  // measure QIDDM_MEAS_OBS: the instantiation that seeds from the measurement table
+        return launch<qiddm::mixed_backward_kernel<T, decltype(lv)::value, decltype(obs)::value>>(
+            kMaxLds - 8192 /* the kernel also has 4.5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
+            "mixed_backward_kernel", prog, angle_rows, features, gates, grad_out, grad_rows, grad_gates,
+            embeds ? grad_features : nullptr, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m, b);
+      };
+      return measure == QIDDM_MEAS_OBS ? run(std::true_type{}) : run(std::false_type{});
     });
   });
 }
@@ -798,8 +875,8 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
                              int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with, const double* gates,
                              int32_t n_gates, int32_t measure, int64_t batch, double* out, int64_t out_ld, void* workspace,
                              int64_t workspace_bytes, void* stream) {
-  const MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
-                    enc_offset, pad_with, gates, n_gates, measure, batch};
+  MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+              enc_offset, pad_with, gates, n_gates, measure, batch};
   bool embeds = false;
   int rc = check_call(c, kTileFused, &embeds);
   if (rc != QIDDM_OK || batch == 0) return rc;
@@ -813,11 +890,12 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
   if (rc != QIDDM_OK) return rc;
   const qiddm::MixedShots sh = shots_of(program, n_ops);
   const int32_t n_body = (int32_t)plan.order.size();  // n_ops, or n_ops - 1 in front of a sampled read-out
-  std::vector<qiddm_mixed_op_t> sorted(n_body);
+  std::vector<qiddm_mixed_op_t> sorted(n_body + c.n_obs);  // the measurement table stays behind the sorted ops
   for (int i = 0; i < n_body; ++i) sorted[i] = program[plan.order[i]];
+  for (int i = 0; i < c.n_obs; ++i) sorted[n_body + i] = program[c.n_body() + i];
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  if ((rc = upload(ws, sorted.data(), (size_t)n_body * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  if ((rc = upload(ws, sorted.data(), sorted.size() * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
   const qiddm::MixedScalars m = make_scalars(c, n_body, n_features, out_ld, false);
   return for_dtype(dtype, [&](auto t) {
     return launch_mixed_wide<decltype(t)>(plan, g, resident, ws, c, out, m, embeds, sh, st);
@@ -850,8 +928,8 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
                               const double* gates, int32_t n_gates, int32_t measure, int64_t batch,
                               const double* grad_out, int64_t gout_ld, double* grad_rows, double* grad_gates,
                               double* grad_features, void* workspace, int64_t workspace_bytes, void* stream) {
-  const MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
-                    enc_offset, pad_with, gates, n_gates, measure, batch};
+  MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+              enc_offset, pad_with, gates, n_gates, measure, batch};
   bool embeds = false;
   int rc = check_call(c, kTileFused, &embeds);
   if (rc != QIDDM_OK || batch == 0) return rc;
@@ -868,6 +946,7 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
   std::vector<unsigned char> head((size_t)g.head, 0);
   qiddm_mixed_op_t* sorted = reinterpret_cast<qiddm_mixed_op_t*>(head.data());
   for (int i = 0; i < bp.n_live; ++i) sorted[i] = program[bp.live_begin + bp.plan.order[i]];
+  for (int i = 0; i < bp.n_obs; ++i) sorted[bp.n_live + i] = program[c.n_body() + i];  // the measurement table
   memcpy(head.data() + g.off_slot, bp.slot.data(), bp.slot.size() * 4);
   if (!bp.params.empty()) memcpy(head.data() + g.off_params, bp.params.data(), bp.params.size() * sizeof(qiddm::WideParam));
   memcpy(head.data() + g.off_groups, bp.group_begin.data(), bp.group_begin.size() * 4);

@@ -22,7 +22,8 @@
 // behind an entangler, correlated dephasing, a two-letter PauliError, a measured two-qubit process).
 // Diagonal gates multiply by u_i conj(u_j); CZ by
 // sign(i) sign(j); CNOT permutes rows and columns (an involution: swapped in place).  Read-out: the diagonal -- or, for
-// a program that ends in kMixShots, estimates from that many shots drawn from it in the launch (qsim_mixed_shots.h).
+// a program that ends in kMixShots, estimates from that many shots drawn from it in the launch (qsim_mixed_shots.h); for a
+// program that ends in a table of kMixObs terms, Pauli-word expectation values from the off-diagonals (mixed_obs_read_out).
 // mixed_backward_kernel (below) differentiates the same programs: PennyLane trains QNodes on default.mixed with
 // backprop or parameter-shift.  n <= 8.
 //
@@ -54,11 +55,13 @@ enum MixedKind : int32_t {
   kMixShots = 12,   // last op only, not an op on rho: the read-out is estimated from `a` shots (qsim_mixed_shots.h);
                     // the host keeps it out of the ops the kernels walk and hands its fields over as a MixedShots
   kMixChannel = 16, // general one-wire channel: gates[a .. a+3] are the rows of the 4 x 4 superoperator S (10..15: no kind)
-  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..31: no kind)
+  kMixObs = 20,     // tail of the program, not an op on rho: one term of the measurement table (coefficient p times the
+                    // Pauli word with x-mask `wire` and z-mask `a`, output column wire2); see mixed_obs_read_out
+  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..19, 21..31: no kind)
 };
 
 struct MixedOp {
-  int32_t kind, wire, a, wire2;  // wire2: qiddm_mixed_op_t's `reserved`, read by kMixChannel2 only
+  int32_t kind, wire, a, wire2;  // wire2: qiddm_mixed_op_t's `reserved`, read by kMixChannel2 (second wire) and kMixObs (column)
   double p, scale;
 };
 
@@ -74,10 +77,10 @@ __host__ __device__ constexpr int mixed_level_of(int kind) {
 }
 
 struct MixedScalars {
-  int32_t n, n_ops, measure, n_features;  // measure 0 probs, 1 <Z_w>
+  int32_t n, n_ops, measure, n_features;  // measure 0 probs, 1 <Z_w>, 2 the measurement table behind the n_ops ops
   int64_t batch, rows_ld, feat_ld, out_ld;
   double enc_offset, pad_with;
-  int32_t slab_in_lds, pad_;
+  int32_t slab_in_lds, n_obs;  // n_obs: terms of the measurement table, prog[n_ops .. n_ops + n_obs) (measure 2 only)
 };
 
 template <typename T>
@@ -150,6 +153,11 @@ __device__ __forceinline__ double mixed_block_sum(double v, double* s_red) {
   const double total = s_red[0];
   __syncthreads();
   return total;
+}
+
+__device__ __forceinline__ double mixed_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
 }
 
 __device__ __forceinline__ bool mixed_needs_snapshot(int kind, int oi) {
@@ -517,6 +525,80 @@ __device__ __forceinline__ void mixed_read_out(const V2<T>* __restrict__ rho, do
   }
 }
 
+// ---- the measurement table (measure 2): Pauli-word expectation values ---------------------------------------------------
+// The program's tail is a table of kMixObs terms, each coefficient p times a Pauli word: x-mask `wire` (wires carrying X
+// or Y), z-mask `a` (Z or Y), wire w at bit n-1-w; wire2 is the output column and several terms may share one (a
+// Hamiltonian).  With ny = popcount(x & z) the word is P[i][j] = i^ny (-1)^popcount(j & z) where i ^ j = x, so
+//     Tr(rho P) = Re( i^ny sum_k (-1)^popcount(k & z) rho[k][k ^ x] )
+// (rho and P are Hermitian).  The table is the same for every thread: a term's fields are read at an index that is
+// uniform over the wave (scalar loads); the seed keeps the per-sample weights of the terms in LDS.
+__device__ __forceinline__ int mixed_obs_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// |Re(i^ny v)|'s component of v: Re(i^ny (re + i im)) is re, -im, -re, im for ny = 0, 1, 2, 3 (the caller has the sign)
+template <typename T>
+__device__ __forceinline__ double mixed_obs_part(V2<T> v, int ny) {
+  return (ny & 1) ? (double)v.y : (double)v.x;
+}
+// One sample's rho -> out_row[column] = sum over the column's terms of p Tr(rho P), float64.  A wave owns every fourth
+// term: its lanes stride the 2^n elements rho[k][k ^ x], the wave sums them in a fixed order, and the thread of a
+// column's first term adds that column's terms in table order.  s_term: 256 doubles.  Ends in a barrier.
+template <typename T>
+__device__ __forceinline__ void mixed_obs_read_out(const V2<T>* __restrict__ rho, double* __restrict__ out_row,
+                                                   double* s_term, const MixedOp* __restrict__ terms, int n_terms, int n) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const uint32_t D = 1u << n;
+  for (int t = mixed_obs_wave(); t < n_terms; t += 4) {
+    const uint32_t x = (uint32_t)terms[t].wire, z = (uint32_t)terms[t].a;
+    const int ny = __popc(x & z) & 3;
+    const bool flip = ny == 1 || ny == 2;
+    double part = 0.0;
+    for (uint32_t k = lane; k < D; k += 64) {
+      const double c = mixed_obs_part<T>(rho[((size_t)k << n) | (k ^ x)], ny);
+      part += (((__popc(k & z) & 1) != 0) != flip) ? -c : c;
+    }
+    const double total = mixed_wave_sum(part);
+    if (lane == 0) s_term[t] = terms[t].p * total;
+  }
+  __syncthreads();
+  if (tid < n_terms) {
+    const int col = terms[tid].wire2;
+    if (tid == 0 || terms[tid - 1].wire2 != col) {
+      double s = 0.0;
+      for (int u = tid; u < n_terms && terms[u].wire2 == col; ++u) s += s_term[u];
+      out_row[col] = s;
+    }
+  }
+  __syncthreads();
+}
+// the weights of the seed, one per term: s_w[t] = g[column_t] p_t (g: this sample's row of grad_out).  The caller puts a
+// barrier behind it.
+__device__ __forceinline__ void mixed_obs_seed_weights(double* s_w, const double* __restrict__ g,
+                                                       const MixedOp* __restrict__ terms, int n_terms) {
+  for (int t = threadIdx.x; t < n_terms; t += 256) s_w[t] = g[terms[t].wire2] * terms[t].p;
+}
+// Element k = (i << n) | j of Lambda_N = sum_t g[column_t] p_t P_t, the seed of a reverse sweep under measure 2: the terms
+// with x_t = i ^ j, in table order.  Hermitian; not real when a word holds Y, not diagonal when it holds X or Y.  The
+// sweeps pair Lambda with rho as Re sum conj(Lambda_ij) rho_ij, so Lambda itself (not its transpose) is what they take:
+// d/drho_ij of Re(i^ny s rho[k][k ^ x]) is conj(i^ny) s at (i, j) = (k, k ^ x), which is P[i][j] by Hermiticity.
+template <typename T>
+__device__ __forceinline__ V2<T> mixed_obs_seed_elem(const MixedOp* __restrict__ terms, int n_terms, const double* s_w,
+                                                     uint32_t k, int n) {
+  const uint32_t i = k >> n, j = k & ((1u << n) - 1u), x = i ^ j;
+  double re = 0.0, im = 0.0;
+  for (int t = 0; t < n_terms; ++t) {
+    const uint32_t xt = (uint32_t)terms[t].wire, zt = (uint32_t)terms[t].a;  // uniform: scalar loads
+    if (xt == x) {
+      const int ny = __popc(xt & zt) & 3;
+      const double w = (__popc(j & zt) & 1) ? -s_w[t] : s_w[t];
+      if (ny == 0) re += w;
+      else if (ny == 1) im += w;
+      else if (ny == 2) re -= w;
+      else im -= w;
+    }
+  }
+  return V2<T>{(T)re, (T)im};
+}
+
 // Op `op` of the program on one sample's rho.  `snap` (NULL in the forward): where the backward's replay keeps rho as
 // it was before a channel or a state preparation.  The caller puts a barrier after every op.
 template <typename T, int LEVEL>
@@ -660,6 +742,26 @@ __global__ __launch_bounds__(256) void mixed_sampled_kernel(const MixedOp* __res
   }
 }
 
+// mixed_kernel with the measurement table's read-out (measure 2: m.n_obs terms behind the m.n_ops ops).  An instantiation
+// of its own, as the sampled read-out's: the probs / <Z> kernel carries none of it.
+template <typename T, int LEVEL>
+__global__ __launch_bounds__(256) void mixed_obs_kernel(const MixedOp* __restrict__ prog,
+                                                        const double* __restrict__ angle_rows,
+                                                        const double* __restrict__ feats,
+                                                        const double* __restrict__ gates, double* __restrict__ out,
+                                                        V2<T>* __restrict__ workspace, const MixedScalars m) {
+  using C = V2<T>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ double s_red[256];
+  __shared__ double s_term[256];
+  C* rho = m.slab_in_lds ? reinterpret_cast<C*>(smem_raw) : workspace + ((size_t)blockIdx.x << (2 * m.n));
+
+  for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
+    mixed_replay<T, LEVEL>(prog, rho, angle_rows, feats, gates, s_red, m, sample);
+    mixed_obs_read_out<T>(rho, out + sample * m.out_ld, s_term, prog + m.n_ops, m.n_obs, m.n);
+  }
+}
+
 // ---- reverse sweep ------------------------------------------------------------------------------------------------
 // Per sample: replay the forward to rho_N (copying rho to a snapshot in front of every channel and every later state
 // preparation), seed the adjoint Lambda_N = dL/drho_N (diagonal: diag(g) for probs, sum_w g_w (1 - 2 bit_w) for <Z>),
@@ -679,11 +781,6 @@ struct MixedBwdScalars {
   int64_t gout_ld;
   int32_t n_rows, n_gates, n_snaps, pad_;
 };
-
-__device__ __forceinline__ double mixed_wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // U^dagger B U for the 2 x 2 block (b00, b01, b10, b11), in place
 template <typename T>
@@ -705,7 +802,8 @@ __device__ __forceinline__ void mixed_udag_b_u(V2<T>& b00, V2<T>& b01, V2<T>& b1
 // compiler then contracts thread 0's `+= scale * s` behind each op differently.  (Building RY / GATE with mixed_unitary
 // kept the bits on the n = 6 cases of tools/mixed_bits.py; it waits for a change that runs the whole list and the
 // timing.)
-template <typename T, int LEVEL>
+// OBS: the seed is the measurement table's (measure 2); an instantiation of its own, the probs / <Z> one carries none of it.
+template <typename T, int LEVEL, bool OBS = false>
 __global__ __launch_bounds__(256) void mixed_backward_kernel(
     const MixedOp* __restrict__ prog, const double* __restrict__ angle_rows, const double* __restrict__ feats,
     const double* __restrict__ gates, const double* __restrict__ grad_out, double* __restrict__ grad_rows,
@@ -743,7 +841,14 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
 
     // ---- seed Lambda_N --------------------------------------------------------------------------------------------
     const double* __restrict__ g = grad_out + sample * b.gout_ld;
-    for (uint32_t k = tid; k < DD; k += 256) lam[k] = mixed_seed_elem<T>(g, k, m);
+    if constexpr (OBS) {  // s_v is free until AMP_EMBED, the last op backwards
+      const MixedOp* __restrict__ terms = prog + m.n_ops;
+      mixed_obs_seed_weights(s_v, g, terms, m.n_obs);
+      __syncthreads();
+      for (uint32_t k = tid; k < DD; k += 256) lam[k] = mixed_obs_seed_elem<T>(terms, m.n_obs, s_v, k, n);
+    } else {
+      for (uint32_t k = tid; k < DD; k += 256) lam[k] = mixed_seed_elem<T>(g, k, m);
+    }
     __syncthreads();
 
     // ---- reverse sweep --------------------------------------------------------------------------------------------

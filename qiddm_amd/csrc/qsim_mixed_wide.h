@@ -305,6 +305,17 @@ __global__ __launch_bounds__(256) void mixed_wide_read_out(const V2<T>* __restri
   mixed_read_out<T>(slabs + ((size_t)blockIdx.x << (2 * m.n)), out, s_red, m, sample0 + blockIdx.x);
 }
 
+// the measurement table's read-out (measure 2; mixed_obs_read_out of qsim_mixed.h) in its place: the m.n_obs terms sit
+// behind the m.n_ops sorted ops of the uploaded program
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_obs_read_out(const MixedOp* __restrict__ prog,
+                                                               const V2<T>* __restrict__ slabs, double* __restrict__ out,
+                                                               const MixedScalars m, int64_t sample0) {
+  __shared__ double s_term[256];
+  mixed_obs_read_out<T>(slabs + ((size_t)blockIdx.x << (2 * m.n)), out + (sample0 + blockIdx.x) * m.out_ld, s_term,
+                        prog + m.n_ops, m.n_obs, m.n);
+}
+
 // the sampled read-out (qsim_mixed_shots.h) in its place when the program ends in kMixShots: one workgroup per resident
 // sample, keyed by the absolute row sample0 + blockIdx.x, so the chunking does not move a stream
 template <typename T>

@@ -54,6 +54,26 @@ __device__ __forceinline__ void wide_load_lambda(V2<T>* tile, const V2<T>* __res
   }
 }
 
+// Lambda_N of the measurement table (measure 2), written to every resident sample's Lambda slab in a launch of its own:
+// the reverse launches behind it read the slab (seed = 0), so their tile walkers carry no loop over terms.  Grid
+// (4^n / 1024, resident samples): a workgroup writes 1024 consecutive elements, the weights of the terms in LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_obs_seed(const MixedOp* __restrict__ prog,
+                                                           const double* __restrict__ grad_out,
+                                                           V2<T>* __restrict__ lam_slabs, const MixedScalars m,
+                                                           const WideBwdScalars b, int64_t sample0) {
+  __shared__ double s_w[256];
+  const int n = m.n;
+  const int64_t resident = blockIdx.y, sample = sample0 + resident;
+  const MixedOp* __restrict__ terms = prog + m.n_ops;
+  V2<T>* __restrict__ lam = lam_slabs + ((size_t)resident << (2 * n));
+  mixed_obs_seed_weights(s_w, grad_out + sample * b.gout_ld, terms, m.n_obs);
+  __syncthreads();
+  const uint32_t k0 = blockIdx.x * 1024u + threadIdx.x;
+#pragma unroll 1
+  for (int i = 0; i < 4; ++i) lam[k0 + 256u * i] = mixed_obs_seed_elem<T>(terms, m.n_obs, s_w, k0 + 256u * i, n);
+}
+
 // The kernel writes its loops over the two tiles out (the shared tile copies apart): at 256 vector registers every
 // other form of them is scheduled differently, and the float64 round at 10 wires measured 1 % slower on the walkers.
 // One unitary segment backwards on the rho tile and the Lambda tile of (tile, sample).  slot[oi] >= 0: the op feeds a

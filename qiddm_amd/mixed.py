@@ -49,6 +49,17 @@ offset is the device's count of sampled executions; the rule is in include/qiddm
 (n+ - n-) / N per wire, float64.  Nothing is copied to the host.  A sampled execution has no reverse sweep: with grad
 mode on and an input that requires grad it raises ``qml.QuantumFunctionError``; while the current stream is capturing it
 raises ``RuntimeError`` (a replay would repeat the same shots).
+
+What is measured: ``qml.probs`` over all wires or over any subset in any order (the full-probs launch, then a reshape and
+sum in torch: differentiable through the same node, valid under ``shots`` and ``readout_prob``), and ``qml.expval`` of
+Pauli words and their real linear combinations -- ``PauliX / PauliY / PauliZ / Identity``, ``A @ B``, ``c * A``,
+``A + B``, ``qml.Hamiltonian`` -- alone (``(B,)``) or as a list of k (``(B, k)``), float64.  The words travel as a table
+of ``QIDDM_MIX_OBS`` terms at the end of the program (``QIDDM_MEAS_OBS``; x-mask, z-mask, coefficient and output column
+per term, at most 256 terms): both engines read the off-diagonal elements rho[k][k ^ x] they need, and both reverse
+sweeps start from the table's Hermitian, in general complex and non-diagonal, adjoint.  ``[expval(PauliZ(i)) for i in
+range(n)]`` is still ``QIDDM_MEAS_EXPZ`` with the program it always had.  ``readout_prob=q`` scales a word by
+(1 - 2q)^weight (no BitFlip ops); with ``shots``, words of I and Z are signed sums of the sampled full probs and a word
+with X or Y raises ``NotImplementedError`` before a stream offset is taken (it needs a basis rotation).
 """
 from __future__ import annotations
 
@@ -281,6 +292,12 @@ class _Lowering:
         self.features, self.pad_with = None, 0.0
         self.device = None
         self.strengths = []  # (row, parameter name) of every native channel whose strength is a tensor
+        self.n_cols = 0      # MEAS_OBS: the columns of the measurement table
+        # what `execute` does with the launch's (B, width) result (None: nothing)
+        #   ("marginal", wires)   probs of these wires, in this order, from the full probs
+        #   ("signed", signs)     (2^n, k) float64 host matrix: the columns' Z-word estimates from sampled full probs
+        self.post = None
+        self.single = False  # one expval, not a list: the result loses its last axis
 
     def _see(self, t):
         if torch.is_tensor(t):
@@ -348,10 +365,77 @@ class _Lowering:
                     self.op(kind, wires[i], wires[(i + r) % n])
 
 
-def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
-    """Tape and measurement -> (_Lowering, measure).  `readout_prob`: one BitFlip per wire behind the tape; `shots`: the
-    program ends in MIX_SHOTS with this `seed` and stream `offset`."""
+def word_masks(word, n):
+    """((wire, letter), ...) -> (x-mask, z-mask, weight): X and Y set the x-mask, Z and Y the z-mask, wire w is bit
+    n-1-w; weight counts the letters other than I."""
+    x = z = weight = 0
+    for wire, letter in word:
+        if not 0 <= wire < n:
+            raise ValueError(f"observable on wire {wire}: the device has wires 0..{n - 1}")
+        bit = 1 << (n - 1 - wire)
+        if letter in "XY":
+            x |= bit
+        if letter in "YZ":
+            z |= bit
+        weight += letter != "I"
+    return x, z, weight
+
+
+def z_signs(z, n):
+    """(2^n,) float64: (-1)^popcount(k & z), the eigenvalue of the Z-word with mask `z` on basis state k."""
+    k = np.arange(1 << n)
+    parity = np.zeros_like(k)
+    for b in range(n):
+        if z >> b & 1:
+            parity ^= (k >> b) & 1
+    return 1.0 - 2.0 * parity
+
+
+def _measurement_plan(ret, n, shots):
+    """What the return value asks for -> ("probs" | "expz" | "marginal" | "obs", payload, single).  payload: the listed
+    wires of marginal probs; for "obs" one list of (coefficient, word) per column.  Refuses what is not supported."""
     from . import qml
+    all_w = tuple(range(n))
+    if isinstance(ret, qml._Measurement):
+        ms, single = [ret], True
+    elif isinstance(ret, (list, tuple)) and ret and all(isinstance(m, qml._Measurement) for m in ret):
+        ms, single = list(ret), False
+    else:
+        raise NotImplementedError("measurements must be probs(wires), expval(observable) or a list of expvals")
+    kinds = {"probs" if m.kind == "probs" else "expval" for m in ms}
+    if len(kinds) > 1:
+        raise NotImplementedError("probs and expval in one return are not supported: use two QNodes")
+    if kinds == {"probs"}:
+        if not single:
+            raise NotImplementedError("a list of probs is not supported: return one qml.probs(wires=...)")
+        wires = ms[0].wires
+        if wires is None or wires == all_w:
+            return "probs", None, True
+        if len(set(wires)) != len(wires) or not wires or any(not 0 <= w < n for w in wires):
+            raise ValueError(f"probs(wires={list(wires)}): wires must be distinct and in 0..{n - 1}")
+        return "marginal", wires, True
+    if not single and [m.kind for m in ms] == ["expz"] * n and [m.wires for m in ms] == [(i,) for i in range(n)]:
+        return "expz", None, False
+    columns = [list(m.obs.terms) for m in ms]
+    n_terms = sum(len(c) for c in columns)
+    if n_terms > _capi.MIX_MAX_OBS:
+        raise ValueError(f"{n_terms} measurement terms after expansion; at most {_capi.MIX_MAX_OBS} are supported")
+    if any(not c for c in columns):
+        raise ValueError("expval of an observable without terms")
+    masks = [word_masks(word, n) for c in columns for _, word in c]  # checks the wires
+    if shots is not None and any(x for x, _, _ in masks):
+        raise NotImplementedError("shots with an observable that holds PauliX or PauliY: sampling it needs a basis "
+                                  "rotation per commuting group; use shots=None, or measure words of I and Z")
+    return "obs", columns, single
+
+
+def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
+    """Tape and measurement -> (_Lowering, measure).  `readout_prob`: one BitFlip per wire behind the tape -- for
+    analytic expectation values instead the factor (1 - 2q)^weight on every word's coefficient, which is what those flips
+    do to a word; `shots`: the program ends in MIX_SHOTS with this `seed` and stream `offset`.  Pauli-word expectation
+    values end the program in a table of MIX_OBS terms (MEAS_OBS); marginal probs and sampled Z-words are the full-probs
+    launch and a reduction in torch (`_Lowering.post`)."""
+    form, payload, single = _measurement_plan(ret, n, shots)
     low = _Lowering(n)
     all_w = tuple(range(n))
     first = True
@@ -410,23 +494,38 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
         first = False
     if first:
         low.op(_capi.MIX_ZERO)
-    if readout_prob is not None:  # PennyLane: BitFlip(readout_prob) on every measured wire in front of the measurement
+    analytic_obs = form == "obs" and shots is None
+    if readout_prob is not None and not analytic_obs:
+        # PennyLane: BitFlip(readout_prob) on every measured wire in front of the measurement
         base = low._add_gates(channel_rows("BitFlip", readout_prob))  # the same four rows for every wire
         for w in all_w:
             low.op(_capi.MIX_CHANNEL, w, base)
     if shots is not None:
         low.op(_capi.MIX_SHOTS, 0, int(shots), float(seed), float(offset))
     # measurement
-    if isinstance(ret, qml._Measurement):
-        if ret.kind != "probs" or (ret.wires is not None and ret.wires != all_w):
-            raise NotImplementedError("probs must cover wires 0..n-1")
-        measure, as_list = _capi.MEAS_PROBS, False
-    elif isinstance(ret, (list, tuple)) and all(isinstance(m, qml._Measurement) for m in ret) and \
-            [m.kind for m in ret] == ["expz"] * n and [m.wires for m in ret] == [(i,) for i in range(n)]:
-        measure, as_list = _capi.MEAS_EXPZ, True
-    else:
-        raise NotImplementedError("measurements must be probs(all wires) or [expval(PauliZ(i)) for i in range(n)]")
-    return low, measure
+    low.single = single and form == "obs"
+    if form == "expz":
+        return low, _capi.MEAS_EXPZ
+    if form == "probs":
+        return low, _capi.MEAS_PROBS
+    if form == "marginal":
+        low.post = ("marginal", payload)
+        return low, _capi.MEAS_PROBS
+    if not analytic_obs:  # words of I and Z from the sampled full probs: column c = sum_t p_t sum_k (-1)^popcount(k & z_t) probs[k]
+        signs = np.zeros((1 << n, len(payload)))
+        for c, column in enumerate(payload):
+            for coeff, word in column:
+                signs[:, c] += coeff * z_signs(word_masks(word, n)[1], n)
+        low.post = ("signed", signs)
+        return low, _capi.MEAS_PROBS
+    for c, column in enumerate(payload):
+        for coeff, word in column:
+            x, z, weight = word_masks(word, n)
+            if readout_prob is not None:  # a flip with probability q on a measured wire scales its letter by 1 - 2q
+                coeff = coeff * (1.0 - 2.0 * readout_prob) ** weight
+            low.ops.append((_capi.MIX_OBS, x, z, float(coeff), 1.0, c))  # six fields: the column travels in `reserved`
+    low.n_cols = len(payload)
+    return low, _capi.MEAS_OBS
 
 
 class _Launch:
@@ -435,6 +534,7 @@ class _Launch:
     def __init__(self, low, measure, n, prec, device, batch):
         self.n, self.prec, self.measure, self.batch, self.device = n, prec, measure, batch, device
         self.pad_with, self.n_rows = low.pad_with, len(low.rows)
+        self.n_cols = low.n_cols
         self.prog = (_capi.MixedOp * len(low.ops))()
         for dst, (kind, wire, a, p, scale, *second) in zip(self.prog, low.ops):  # second: MIX_CHANNEL2's other wire
             dst.kind, dst.wire, dst.a, dst.reserved, dst.p, dst.scale = kind, wire, a, second[0] if second else 0, p, scale
@@ -457,8 +557,8 @@ class _Launch:
 
     def forward(self, rows, gates, feats, wide=False):
         n, batch = self.n, self.batch
-        out = torch.empty(batch, (1 << n) if self.measure == _capi.MEAS_PROBS else n, dtype=torch.float64,
-                          device=self.device)
+        width = (1 << n) if self.measure == _capi.MEAS_PROBS else self.n_cols if self.measure == _capi.MEAS_OBS else n
+        out = torch.empty(batch, width, dtype=torch.float64, device=self.device)
         if wide:
             ws = self._fresh(_capi.query("qiddm_mixed_wide_workspace_bytes", n, self.prec, self._resident(), self.prog,
                                          len(self.prog)))
@@ -533,7 +633,8 @@ def _check_strengths(rows, strengths):
 
 
 def execute(tape, ret, n, precision=None, _engine=None, device=None):
-    """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)``
+    """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)`` -- marginal
+    probs of k wires ``(B, 2^k)``, one expval ``(B,)``, a list of k expvals ``(B, k)`` --
     (or the unbatched row), as ``default.mixed`` does.  Up to 8 wires: differentiable when grad mode is on and an input
     requires grad; otherwise a plain launch whose result has no ``grad_fn``.  9 and 10 wires (within the wire limit, see
     ``set_max_wires``): forward only unless ``set_max_grad_wires`` admits them too.  `device` (the QNode's ``qml.Device``):
@@ -582,4 +683,16 @@ def execute(tape, ret, n, precision=None, _engine=None, device=None):
         out = _MixedFunction.apply(launch, rows, gates, feats, wide)
     else:
         out = launch.forward(rows, gates, feats, wide=wide)
+    if low.post is not None and low.post[0] == "marginal":  # sum the other wires out, the listed ones in their order
+        wires = low.post[1]
+        out = out.reshape(batch, *([2] * n))
+        others = tuple(1 + w for w in range(n) if w not in wires)
+        if others:
+            out = out.sum(dim=others)
+        kept = sorted(wires)
+        out = out.permute(0, *[1 + kept.index(w) for w in wires]).reshape(batch, 1 << len(wires))
+    elif low.post is not None:  # ("signed", signs)
+        out = out @ torch.from_numpy(low.post[1]).to(out)
+    if low.single:
+        out = out[:, 0]
     return out if low.batched else out[0]

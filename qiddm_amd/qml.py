@@ -214,14 +214,116 @@ def _all_2x2(K_list):
 
 
 # --- measurements -------------------------------------------------------------
-class PauliZ:
+MAX_TERMS = 256  # QIDDM_MIX_MAX_OBS: the terms of one measurement table
+
+
+def _real(c, what):
+    """A coefficient as a Python float: Python and NumPy real numbers only."""
+    if torch.is_tensor(c):
+        raise NotImplementedError(f"{what}: tensor coefficients are not supported; measure the words one by one "
+                                  "(a list of expvals) and weight them in torch")
+    if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{what}: a coefficient must be a real Python or NumPy number (got {type(c).__name__})")
+    return float(c)
+
+
+class Observable:
+    """A real linear combination of Pauli words, ``terms = [(coefficient, ((wire, letter), ...)), ...]`` with letters of
+    "IXYZ".  ``A @ B`` is the tensor product (the factors must not share a wire), ``c * A``, ``-A``, ``A + B`` and
+    ``A - B`` the usual algebra.  Terms are kept as written: nothing is simplified or merged.  ``default.mixed``
+    measures it (``qml.expval``); the pure-state devices measure ``[expval(PauliZ(i)) for i in range(n)]`` only."""
+
+    def __init__(self, terms):
+        self.terms = list(terms)
+
+    @property
+    def obs_wires(self):
+        return tuple(sorted({w for _, word in self.terms for w, _ in word}))
+
+    def __matmul__(self, other):
+        if not isinstance(other, Observable):
+            return NotImplemented
+        out = []
+        for ca, wa in self.terms:
+            for cb, wb in other.terms:
+                shared = {w for w, _ in wa} & {w for w, _ in wb}
+                if shared:
+                    raise NotImplementedError(f"a tensor product with two factors on wire {min(shared)}: products of "
+                                              "operators on one wire are not simplified")
+                out.append((ca * cb, wa + wb))
+        return Observable(out)
+
+    def __mul__(self, c):
+        if isinstance(c, Observable):
+            raise NotImplementedError("A * B of two observables: use A @ B for the tensor product")
+        c = _real(c, "scalar product")
+        return Observable([(c * k, word) for k, word in self.terms])
+
+    __rmul__ = __mul__
+
+    def __neg__(self):
+        return Observable([(-k, word) for k, word in self.terms])
+
+    def __add__(self, other):
+        if not isinstance(other, Observable):
+            return NotImplemented
+        return Observable(self.terms + other.terms)
+
+    def __sub__(self, other):
+        if not isinstance(other, Observable):
+            return NotImplemented
+        return Observable(self.terms + (-other).terms)
+
+    def __repr__(self):
+        def word(w):
+            return " @ ".join(f"{letter}({wire})" for wire, letter in w) or "I"
+        return " + ".join(f"{k:g} * {word(w)}" for k, w in self.terms) or "0"
+
+
+class _Pauli(Observable):
+    letter = "I"
+
     def __init__(self, wires):
         self.wires = _wires(wires)
+        if len(self.wires) != 1:
+            raise ValueError(f"Pauli{self.letter} acts on one wire (got wires={list(self.wires)})")
+        super().__init__([(1.0, ((self.wires[0], self.letter),))])
+
+
+class PauliX(_Pauli):
+    letter = "X"
+
+
+class PauliY(_Pauli):
+    letter = "Y"
+
+
+class PauliZ(_Pauli):
+    letter = "Z"
+
+
+class Identity(_Pauli):
+    letter = "I"
+
+
+def Hamiltonian(coeffs, observables):
+    """``qml.Hamiltonian(coeffs, observables)``: sum_i coeffs[i] * observables[i], real Python / NumPy coefficients."""
+    coeffs, observables = list(coeffs), list(observables)
+    if len(coeffs) != len(observables):
+        raise ValueError(f"Hamiltonian: {len(coeffs)} coefficients for {len(observables)} observables")
+    terms = []
+    for c, o in zip(coeffs, observables):
+        if not isinstance(o, Observable):
+            raise TypeError(f"Hamiltonian: {o!r} is not an observable")
+        terms += (_real(c, "Hamiltonian") * o).terms
+    if len(terms) > MAX_TERMS:
+        raise ValueError(f"Hamiltonian: {len(terms)} terms after expansion; at most {MAX_TERMS} are supported")
+    return Observable(terms)
 
 
 class _Measurement:
-    def __init__(self, kind, wires):
-        self.kind, self.wires = kind, wires
+    def __init__(self, kind, wires, obs=None):
+        self.kind, self.wires, self.obs = kind, wires, obs
 
 
 def probs(wires=None):
@@ -229,9 +331,16 @@ def probs(wires=None):
 
 
 def expval(obs):
-    if not isinstance(obs, PauliZ):
-        raise NotImplementedError("only expval(PauliZ(i)) is supported")
-    return _Measurement("expz", obs.wires)
+    """``qml.expval(obs)``.  ``PauliZ(i)`` is what every device measures; any other ``Observable`` (PauliX / PauliY /
+    Identity, tensor products, sums, ``Hamiltonian``) is measured on ``default.mixed``."""
+    if isinstance(obs, PauliZ):
+        return _Measurement("expz", obs.wires, obs)
+    if not isinstance(obs, Observable):
+        raise NotImplementedError("only expval of Pauli words and their real linear combinations is supported "
+                                  "(PauliX, PauliY, PauliZ, Identity, A @ B, c * A, A + B, Hamiltonian)")
+    if len(obs.terms) > MAX_TERMS:
+        raise ValueError(f"expval: {len(obs.terms)} terms after expansion; at most {MAX_TERMS} are supported")
+    return _Measurement("expval", obs.obs_wires, obs)
 
 
 # ---------------------------------------------------------------------------
@@ -305,7 +414,11 @@ def device(name, wires=1, shots=None, readout_prob=None, seed=None, **kwargs):
     that strength on every wire in front of the measurement, with or without shots.  ``seed``: ``None`` (one draw from
     torch's default CPU generator when the device is created with shots) or a non-negative int; the device counts its
     sampled executions and gives each a stream of its own.  On the pure-state names ``shots`` raises
-    ``NotImplementedError`` and ``readout_prob`` ``TypeError``; other keywords are ignored."""
+    ``NotImplementedError`` and ``readout_prob`` ``TypeError``; other keywords are ignored.
+
+    ``default.mixed`` measures ``probs`` of all wires or of a subset, and ``expval`` of any ``Observable`` (Pauli words and
+    their real linear combinations), one or a list; the pure-state names measure ``probs`` of all wires or
+    ``[expval(PauliZ(i)) for i in range(n)]`` and refuse the rest with ``NotImplementedError``."""
     return Device(name, wires, shots=shots, readout_prob=readout_prob, seed=seed, **kwargs)
 
 
@@ -374,17 +487,22 @@ def _compile(tape, ret, n, dev):
             raise DeviceError(f"Gate {op.name} not supported on device {dev.short_name}")
 
     # measurement
+    elsewhere = "; Pauli-word expectation values and marginal probs are measured on 'default.mixed'"
+    for m in (ret if isinstance(ret, (list, tuple)) else [ret]):
+        if isinstance(m, _Measurement) and m.kind == "expval":
+            raise NotImplementedError(f"expval({m.obs!r}) on device {dev.short_name}: the statevector engines measure "
+                                      "probs(all wires) or [expval(PauliZ(i)) for i in range(n)]" + elsewhere)
     if isinstance(ret, _Measurement):
         meas, as_list = ret, False
         if meas.kind != "probs" or (meas.wires is not None and meas.wires != tuple(range(n))):
             if meas.kind == "expz" and n == 1 and meas.wires == (0,):
                 pass
             else:
-                raise NotImplementedError("probs must cover wires 0..n-1")
+                raise NotImplementedError("probs must cover wires 0..n-1" + elsewhere)
         measure = meas.kind
     elif isinstance(ret, (list, tuple)) and all(isinstance(m, _Measurement) for m in ret):
         if [m.kind for m in ret] != ["expz"] * n or [m.wires for m in ret] != [(i,) for i in range(n)]:
-            raise NotImplementedError("expectation values must be [expval(PauliZ(i)) for i in range(n)]")
+            raise NotImplementedError("expectation values must be [expval(PauliZ(i)) for i in range(n)]" + elsewhere)
         measure, as_list = "expz", True
     else:
         raise QuantumFunctionError("A quantum function must return measurements")
