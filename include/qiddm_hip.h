@@ -668,7 +668,28 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *                             QIDDM_ERR_UNSUPPORTED (shots of a word with X or Y need a basis rotation).  The planners and
  *                             the *_workspace_bytes functions that read a program check the table in full, count it in no
  *                             sweep and no snapshot; its op_segment entries are -1.
- * Kinds 10, 11, 13..15, 17..19, 21..31 and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
+ *   QIDDM_MIX_GATE2 (= 24)    a two-wire unitary on w1 = `wire` and w2 = `reserved` (checked like QIDDM_MIX_CHANNEL2's: `op %d:
+ *                             bad second wire %d`; w1 > w2 is allowed).  `a` is the first of FOUR consecutive rows of
+ *                             `gates`: row a + r holds U[r][0..3] as four (re, im) pairs, operator index 2 b1 + b2 with the
+ *                             first wire most significant (QIDDM_MIX_CHANNEL2's convention, PennyLane's).  On every 4 x 4
+ *                             block M of the two wires (as for QIDDM_MIX_CHANNEL2) M' = U M U^dagger, i.e. rho <- U rho
+ *                             U^dagger.  `p` and `scale` are not read.  As with QIDDM_MIX_GATE the rows are device memory
+ *                             and unitarity is the caller's responsibility.  a < 0 or a + 3 >= n_gates (summed in 64 bits):
+ *                             `op %d: gate rows %d..%d out of range`.  The planner gives it CNOT's wire set {w1, w2}: not
+ *                             diagonal, both wires in the segment's tile.  It is a unitary, not a channel: no snapshot, no
+ *                             segment of its own in the reverse plan; the reverse sweeps un-compute it with U^dagger on rho
+ *                             and on the adjoint and return, per sample, dL/dRe U and dL/dIm U in rows a .. a+3 of
+ *                             grad_gates, in the layout of the rows themselves (entries treated as independent reals): with
+ *                             N = sum over the 4 x 4 blocks of B_rho B_Lambda^dagger, both taken behind the gate, and
+ *                             R = U^dagger N, dL/dRe U_ab = 2 Re R_ba and dL/dIm U_ab = -2 Im R_ba -- the 4 x 4 form of
+ *                             QIDDM_MIX_GATE's.  Several ops may name the same four rows (one matrix behind every
+ *                             entangler): their gradients add, as for QIDDM_MIX_GATE.  Rows that PARTLY overlap those of
+ *                             another QIDDM_MIX_GATE / QIDDM_MIX_GATE2 op have no meaningful gradient: the two backward
+ *                             entry points refuse them with QIDDM_ERR_INVALID, `op %d: gate rows %d..%d overlap those of
+ *                             op %d` (checked behind the sampled read-out's refusal, in front of the outputs).  PennyLane's
+ *                             SWAP, ISWAP, CY, CRX / CRY / CRZ / CRot, ControlledPhaseShift, IsingXX / YY / ZZ and
+ *                             QubitUnitary on two wires are this op.
+ * Kinds 10, 11, 13..15, 17..19, 21..23, 25..31 and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
  * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n | columns of the table) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
@@ -678,7 +699,7 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  * or second wire -- `op %d: bad second wire %d` when it is outside 0..n-1 or equal to `wire` --; QIDDM_MIX_SHOTS instead:
  * its position, wire / reserved, shots, seed, offset --,
  * then the operand they index: features / feat_ld / n_features, angle row, gate, probability (a >= 0: angle row, then
- * finite p / scale), channel rows), max_blocks (negative:
+ * finite p / scale), channel rows, gate rows), max_blocks (negative:
  * refused for an empty batch as well), in the reverse sweeps a program that ends in QIDDM_MIX_SHOTS, the outputs
  * (out, out_ld | grad_out / gout_ld, grad_rows, grad_gates, grad_features), workspace.                   */
 enum {
@@ -687,11 +708,12 @@ enum {
   QIDDM_MIX_SHOTS = 12,
   QIDDM_MIX_CHANNEL = 16,
   QIDDM_MIX_OBS = 20,
+  QIDDM_MIX_GATE2 = 24,
   QIDDM_MIX_CHANNEL2 = 32
 };
 #define QIDDM_MIX_MAX_OBS 256 /* terms of a measurement table */
 typedef struct qiddm_mixed_op {
-  int32_t kind, wire, a, reserved; /* reserved: the second wire of QIDDM_MIX_CHANNEL2, the column of QIDDM_MIX_OBS */
+  int32_t kind, wire, a, reserved; /* reserved: the second wire of QIDDM_MIX_CHANNEL2 / _GATE2, the column of QIDDM_MIX_OBS */
   double p, scale;
 } qiddm_mixed_op_t;
 int64_t qiddm_mixed_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, int32_t n_ops);
@@ -726,7 +748,7 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
  * slab of `workspace`; the program is cut into SEGMENTS, each run by one sweep -- one launch over (tile, sample) in which
  * a workgroup holds the 2^12 elements spanned by the index-bit pairs of six wires in LDS and applies the whole segment.
  * A segment takes PHASE / CZ / PHASE_DAMP on any wires (diagonal on vec(rho)), GATE / RY / AMP_DAMP / DEPOL / CHANNEL on its six
- * wires, CNOT and CHANNEL2 between two of them, and ZERO / AMP_EMBED as its first op.  Ops keep program order except where they
+ * wires, CNOT, GATE2 and CHANNEL2 between two of them, and ZERO / AMP_EMBED as its first op.  Ops keep program order except where they
  * commute (no shared wire, or both diagonal).  Same arguments and results as qiddm_mixed_forward; float64 read-out with
  * fixed-order sums, no atomics: reruns are bit-identical.
  *   qiddm_mixed_wide_plan             host only (no device is touched): the number of sweeps, the number of ops that are
@@ -770,7 +792,7 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
  *   qiddm_mixed_wide_backward_workspace_bytes  head + resident * per_sample, every term rounded up to 256 B:
  *                                              head = live ops * 32 + live ops * 4 + gradient ops * 24 + (parameter
  *                                              groups + 1) * 4; per_sample = 8 (1 + 2^n) + 8 * slots * 2^(2n-12) +
- *                                              (2 + snapshots) slabs, slots = 8 per live GATE + 1 per live PHASE / RY
+ *                                              (2 + snapshots) slabs, slots = 8 per live GATE + 32 per live GATE2 + 1 per live PHASE / RY
  *                                              / native channel with a >= 0 (gradient ops: the same ops).  resident = min(batch, 1 GiB / per_sample), at least 1;
  *                                              larger batches run in chunks inside the call.  `program` is required.
  *   qiddm_mixed_wide_backward                  also accepts a smaller workspace, down to head + per_sample.          */

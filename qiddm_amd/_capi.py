@@ -75,11 +75,12 @@ MIX_CHANNEL = 16  # general one-wire channel: `a` = first of four gate rows hold
 # tail of the program: one term of the measurement table, `p` times the Pauli word with x-mask `wire` and z-mask `a`
 # (wire w at bit n-1-w), output column `reserved`; at most MIX_MAX_OBS terms
 MIX_OBS, MIX_MAX_OBS = 20, 256
+MIX_GATE2 = 24  # two-wire unitary: `a` = first of four gate rows (the 4 x 4 matrix), `reserved` = the second wire
 MIX_CHANNEL2 = 32  # general two-wire channel: `a` = first of 64 gate rows (16 x 16), `reserved` = the second wire
 
 
 class MixedOp(ctypes.Structure):
-    """``qiddm_mixed_op_t``.  ``reserved`` is 0 except for ``MIX_CHANNEL2``, which reads its second wire there, and ``MIX_OBS``, which reads
+    """``qiddm_mixed_op_t``.  ``reserved`` is 0 except for ``MIX_CHANNEL2`` and ``MIX_GATE2``, which read their second wire there, and ``MIX_OBS``, which reads
     its output column there."""
 
     _fields_ = [("kind", ctypes.c_int32), ("wire", ctypes.c_int32), ("a", ctypes.c_int32),

@@ -38,7 +38,7 @@ using qiddm_capi::launched;
 static_assert(sizeof(qiddm::MixedOp) == sizeof(qiddm_mixed_op_t), "program layout");
 static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixChannel == (int)QIDDM_MIX_CHANNEL &&
                   (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2 && (int)qiddm::kMixShots == (int)QIDDM_MIX_SHOTS &&
-                  (int)qiddm::kMixObs == (int)QIDDM_MIX_OBS,
+                  (int)qiddm::kMixObs == (int)QIDDM_MIX_OBS && (int)qiddm::kMixGate2 == (int)QIDDM_MIX_GATE2,
               "op kinds");
 static_assert(offsetof(qiddm::MixedOp, wire2) == offsetof(qiddm_mixed_op_t, reserved), "the second wire travels in `reserved`");
 
@@ -46,23 +46,38 @@ inline int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
 inline int64_t slab_bytes(int32_t n, int32_t dtype) { return ((int64_t)1 << (2 * n)) * (dtype == QIDDM_F32 ? 8 : 16); }
 inline int64_t program_bytes(int32_t n_ops) { return round256((int64_t)n_ops * (int64_t)sizeof(qiddm::MixedOp)); }
 
+// QIDDM_MIX_GATE2 (the two-wire unitary): validated like CHANNEL2's wires and GATE's rows, planned like CNOT, and in the
+// reverse sweeps a unitary -- no snapshot, 32 tile partials, a refusal of rows that partly overlap another gate's.
 inline bool is_prep(int kind) { return kind == qiddm::kMixZero || kind == qiddm::kMixAmpEmbed; }
 inline bool is_diag(int kind) {
   return kind == qiddm::kMixPhase || kind == qiddm::kMixCZ || kind == qiddm::kMixPhaseDamp;
 }
 // the kernels have an instantiation per qiddm::MixedLevel (which general-channel cases they carry); a program (segment)
 // runs the lowest one that holds its ops: calls f(std::integral_constant<int, level>{})
+// (the kernels that only ever see channel segments: a level without the two-wire unitary's flag)
 template <typename F>
 int for_level(int level, F&& f) {
   return level >= qiddm::kLevelChannel2 ? f(std::integral_constant<int, qiddm::kLevelChannel2>{})
          : level == qiddm::kLevelChannel ? f(std::integral_constant<int, qiddm::kLevelChannel>{})
                                           : f(std::integral_constant<int, qiddm::kLevelLean>{});
 }
+// the kernels that run whole programs or unitary segments.  With the flag of the two-wire unitary (qiddm::kLevelGate2)
+// two instantiations exist: beside no channel case at all, or beside all of them.
+template <typename F>
+int for_op_level(int level, F&& f) {
+  if (!qiddm::mixed_has_gate2(level)) return for_level(level, f);
+  return qiddm::mixed_channels_of(level) > qiddm::kLevelLean
+             ? f(std::integral_constant<int, qiddm::kLevelChannel2 | qiddm::kLevelGate2>{})
+             : f(std::integral_constant<int, qiddm::kLevelLean | qiddm::kLevelGate2>{});
+}
 inline int program_level(const qiddm_mixed_op_t* program, int32_t n_ops) {
   int level = qiddm::kLevelLean;
-  for (int i = 0; i < n_ops; ++i) level = std::max(level, qiddm::mixed_level_of(program[i].kind));
+  for (int i = 0; i < n_ops; ++i) level = qiddm::mixed_level_join(level, qiddm::mixed_level_of(program[i].kind));
   return level;
 }
+inline bool is_gate2(int kind) { return kind == qiddm::kMixGate2; }
+// the rows of `gates` a GATE / GATE2 op reads and gets its gradient in: [a, a + n), n = 0 for every other kind
+inline int gate_rows(int kind) { return kind == qiddm::kMixGate ? 1 : is_gate2(kind) ? 4 : 0; }
 inline bool is_channel(int kind) {
   return kind == qiddm::kMixPhaseDamp || kind == qiddm::kMixAmpDamp || kind == qiddm::kMixDepol ||
          kind == qiddm::kMixChannel || kind == qiddm::kMixChannel2;
@@ -139,6 +154,26 @@ int refuse_sampled(const qiddm_mixed_op_t* program, int32_t n_ops) {
   return QIDDM_OK;
 }
 
+// The reverse sweeps: the rows of two GATE / GATE2 ops are the same rows (their gradients add) or share none -- a
+// gradient for rows that partly overlap has no meaning.  Only a GATE2 op can overlap another's partly.
+int refuse_overlapping_gate_rows(const qiddm_mixed_op_t* program, int32_t n_ops) {
+  bool any = false;
+  for (int i = 0; i < n_ops; ++i) any = any || is_gate2(program[i].kind);
+  if (!any) return QIDDM_OK;
+  std::vector<int> gated;
+  for (int i = 0; i < n_ops; ++i) {
+    const int64_t ni = gate_rows(program[i].kind), ai = program[i].a;
+    if (!ni) continue;
+    for (int j : gated) {
+      const int64_t nj = gate_rows(program[j].kind), aj = program[j].a;
+      if (ai < aj + nj && aj < ai + ni && !(ai == aj && ni == nj))
+        return fail(QIDDM_ERR_INVALID, "op %d: gate rows %d..%d overlap those of op %d", i, (int)ai, (int)(ai + ni - 1), j);
+    }
+    gated.push_back(i);
+  }
+  return QIDDM_OK;
+}
+
 // The measurement table a program may end in: QIDDM_MIX_OBS ops and nothing else from the first one on.  Checks all of it
 // (position, count, masks, coefficient, columns; no QIDDM_MIX_SHOTS beside it) and counts its terms and columns; a
 // program without one gives 0, 0.  `n_qubits` has been checked.
@@ -180,7 +215,7 @@ int check_obs_tail(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, in
 // of it.  QIDDM_MIX_SHOTS is checked here in full (position, wire / reserved, shots, seed, offset): it indexes no operand.
 int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops) {
   if ((op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) && op.kind != qiddm::kMixChannel &&
-      op.kind != qiddm::kMixChannel2 && op.kind != qiddm::kMixShots)
+      op.kind != qiddm::kMixChannel2 && op.kind != qiddm::kMixShots && !is_gate2(op.kind))
     return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
   if (is_prep(op.kind)) return QIDDM_OK;
   if (op.kind == qiddm::kMixShots) {
@@ -198,7 +233,7 @@ int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops) 
   if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
   if ((op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) && (op.a < 0 || op.a >= n || op.a == op.wire))
     return fail(QIDDM_ERR_INVALID, "op %d: bad target wire %d", i, op.a);
-  if (op.kind == qiddm::kMixChannel2 && (op.reserved < 0 || op.reserved >= n || op.reserved == op.wire))
+  if ((op.kind == qiddm::kMixChannel2 || is_gate2(op.kind)) && (op.reserved < 0 || op.reserved >= n || op.reserved == op.wire))
     return fail(QIDDM_ERR_INVALID, "op %d: bad second wire %d", i, op.reserved);  // n_qubits = 1 cannot hold the op
   return QIDDM_OK;
 }
@@ -278,6 +313,10 @@ int check_call(MixedCall& c, const Engine& e, bool* embeds) {
       case qiddm::kMixChannel:  // four rows of gates; what they hold is device memory, out of the library's sight
         if (op.a < 0 || (int64_t)op.a + 3 >= c.n_gates)
           return fail(QIDDM_ERR_INVALID, "op %d: channel rows %d..%d out of range", i, op.a, (int)((int64_t)op.a + 3));
+        break;
+      case qiddm::kMixGate2:  // four rows: the 4 x 4 unitary (device memory: unitarity is the caller's business, as for GATE)
+        if (op.a < 0 || (int64_t)op.a + 3 >= c.n_gates)
+          return fail(QIDDM_ERR_INVALID, "op %d: gate rows %d..%d out of range", i, op.a, (int)((int64_t)op.a + 3));
         break;
       case qiddm::kMixChannel2:  // 64 rows: the 16 x 16 superoperator
         if (op.a < 0 || (int64_t)op.a + 63 >= c.n_gates)
@@ -453,7 +492,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
     if ((rc = check_op_wires(n, op, i, n_all)) != QIDDM_OK) return rc;
     wires[i] = is_prep(op.kind) ? all : 1u << op.wire;
     if (op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) wires[i] |= 1u << op.a;
-    if (op.kind == qiddm::kMixChannel2) wires[i] |= 1u << op.reserved;  // both wires in the tile, as for CNOT
+    if (op.kind == qiddm::kMixChannel2 || is_gate2(op.kind)) wires[i] |= 1u << op.reserved;  // both wires in the tile, as for CNOT
     plan->n_nondiag += is_diag(op.kind) ? 0 : 1;
   }
   plan->order.clear();
@@ -489,7 +528,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
       if (split_channels && !empty && is_channel(kind) != channels) ok = false;
       if (ok) {
         if (empty) channels = is_channel(kind);
-        level = std::max(level, qiddm::mixed_level_of(kind));
+        level = qiddm::mixed_level_join(level, qiddm::mixed_level_of(kind));
         placed[i] = 1;
         plan->order.push_back(i);
         plan->op_segment[i] = (int32_t)plan->segments.size();
@@ -539,7 +578,7 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
     const unsigned chunk = (unsigned)(m.batch - s0 < resident ? m.batch - s0 : resident);
     if (embeds) hipLaunchKernelGGL(qiddm::mixed_wide_norms, dim3(chunk), dim3(256), 0, st, c.features, norms, m, s0);
     for (size_t s = 0; s < plan.segments.size(); ++s) {   // (the sweeps ask for the LDS they use, no more)
-      const int rc = for_level(plan.seg_level[s], [&](auto level) {
+      const int rc = for_op_level(plan.seg_level[s], [&](auto level) {
         return launch<qiddm::mixed_wide_sweep<T, decltype(level)::value>>(
             smem, dim3(tiles, chunk), dim3(256), smem, st, "mixed_wide_sweep", prog, c.angle_rows, c.features, c.gates, norms,
             slabs, m, plan.segments[s], s0, (int64_t)0);
@@ -568,6 +607,7 @@ struct WideBwdPlan {
   int32_t n_snaps = 0;                    // channel segments among them
   int32_t n_slots = 0;                    // tile partials per (tile, sample)
   bool embed_live = false;
+  bool gate2 = false;                     // a live GATE2: the finalize that sums 32 partials an op
   std::vector<char> seg_graded;           // the (channel) segment holds a native channel with a >= 0
   std::vector<int32_t> slot;              // per sorted live op, -1: no gradient
   std::vector<qiddm::WideParam> params;   // grouped by the parameter they feed, program order within a group
@@ -605,14 +645,16 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
   bp->embed_live = live[0].kind == qiddm::kMixAmpEmbed;
   bp->slot.assign(bp->n_live, -1);
   bp->n_slots = 0;
+  bp->gate2 = false;
   std::vector<std::pair<int64_t, int32_t>> keyed;  // (parameter, sorted position)
   for (int i = 0; i < bp->n_live; ++i) {
     const qiddm_mixed_op_t& op = live[bp->plan.order[i]];
-    const bool gate = op.kind == qiddm::kMixGate;
+    const int gate = gate_rows(op.kind);  // 1: GATE (8 tile partials), 4: GATE2 (32)
     if (!gate && !((op.kind == qiddm::kMixPhase || op.kind == qiddm::kMixRY) && op.a >= 0) && !is_graded(op)) continue;
     bp->slot[i] = bp->n_slots;
-    bp->n_slots += gate ? 8 : 1;
-    keyed.push_back({((int64_t)(gate ? 1 : 0) << 32) | (uint32_t)op.a, i});
+    bp->n_slots += gate ? 8 * gate : 1;
+    bp->gate2 = bp->gate2 || is_gate2(op.kind);
+    keyed.push_back({((int64_t)gate << 32) | (uint32_t)op.a, i});
   }
   std::stable_sort(keyed.begin(), keyed.end(),
                    [](const std::pair<int64_t, int32_t>& x, const std::pair<int64_t, int32_t>& y) { return x.first < y.first; });
@@ -622,7 +664,7 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
     const qiddm_mixed_op_t& op = live[bp->plan.order[keyed[k].second]];
     if (k == 0 || keyed[k].first != keyed[k - 1].first) bp->group_begin.push_back((int32_t)k);
     qiddm::WideParam p{};
-    p.kind = op.kind == qiddm::kMixGate ? qiddm::kMixGate : qiddm::kMixPhase;  // the finalize tells gates from angles
+    p.kind = gate_rows(op.kind) ? op.kind : qiddm::kMixPhase;  // the finalize tells GATE and GATE2 from angles
     p.a = op.a;
     p.slot = bp->slot[keyed[k].second];
     p.scale = op.scale;
@@ -686,7 +728,7 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
     int cur = 0;
     for (int s = 0; s < bp.replay_end; ++s) {
       const bool ch = bp.plan.seg_channel[s] != 0;
-      rc = for_level(bp.plan.seg_level[s], [&](auto level) {
+      rc = for_op_level(bp.plan.seg_level[s], [&](auto level) {
         return launch<qiddm::mixed_wide_sweep<T, decltype(level)::value>>(
             tile_bytes, dim3(tiles, chunk), block, tile_bytes, st, "mixed_wide_sweep", prog, c.angle_rows, c.features, c.gates,
             norms, slabs + (size_t)cur * set_stride, m, bp.plan.segments[s], s0, (int64_t)(ch ? set_stride : 0));
@@ -703,10 +745,12 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
     }
     for (int s = n_seg - 1; s >= 0; --s) {
       if (!bp.plan.seg_channel[s]) {
-        rc = launch<qiddm::mixed_wide_reverse_sweep<T>>(2 * tile_bytes, dim3(tiles, chunk), block, 2 * tile_bytes, st,
-                                                        "mixed_wide_reverse_sweep", prog, slot, c.angle_rows, c.gates, grad_out,
-                                                        slabs + (size_t)cur * set_stride, lam, partials, m,
-                                                        bp.plan.segments[s], bs, s0);
+        const auto reverse = [&](auto gate2) {  // the segment holds a two-wire unitary: the instantiation that carries it
+          return launch<qiddm::mixed_wide_reverse_sweep<T, decltype(gate2)::value>>(
+              2 * tile_bytes, dim3(tiles, chunk), block, 2 * tile_bytes, st, "mixed_wide_reverse_sweep", prog, slot,
+              c.angle_rows, c.gates, grad_out, slabs + (size_t)cur * set_stride, lam, partials, m, bp.plan.segments[s], bs, s0);
+        };
+        rc = qiddm::mixed_has_gate2(bp.plan.seg_level[s]) ? reverse(std::true_type{}) : reverse(std::false_type{});
       } else if (bp.seg_graded[s]) {
         // the state in front of the segment: the set below the one it wrote, or (not replayed) the last replayed set
         const C* front = slabs + (size_t)(s < bp.replay_end ? cur - 1 : cur) * set_stride;
@@ -732,9 +776,9 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
       hipLaunchKernelGGL(qiddm::mixed_wide_embed_grad, dim3(chunk), dim3(256), 0, st, c.features, lv, grad_features, m, s0);
     }
     if (n_groups > 0)
-      hipLaunchKernelGGL(qiddm::mixed_wide_grad_finalize, dim3((n_groups + 3) / 4, chunk), dim3(256), 0, st, params,
-                         group_begin, n_groups, c.gates, partials, grad_rows, grad_gates, bp.n_slots, c.n_gates, tiles,
-                         m.batch, s0);
+      hipLaunchKernelGGL(bp.gate2 ? qiddm::mixed_wide_grad_finalize<true> : qiddm::mixed_wide_grad_finalize<false>,
+                         dim3((n_groups + 3) / 4, chunk), dim3(256), 0, st, params, group_begin, n_groups, c.gates, partials,
+                         grad_rows, grad_gates, bp.n_slots, c.n_gates, tiles, m.batch, s0);
     if (rc = launched("mixed_wide backward"); rc != QIDDM_OK) return rc;
   }
   return QIDDM_OK;
@@ -775,7 +819,7 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
   const int level = program_level(program, n_body);
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    return for_level(level, [&](auto lv) {
+    return for_op_level(level, [&](auto lv) {
       if (sh.shots)
         return launch<qiddm::mixed_sampled_kernel<T, decltype(lv)::value>>(
             kMaxLds - 8192 /* the kernel also has 5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
@@ -819,6 +863,7 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);  // refused for an empty batch as well
   if (rc != QIDDM_OK || batch == 0) return rc;
   if ((rc = refuse_sampled(program, n_ops)) != QIDDM_OK) return rc;
+  if ((rc = refuse_overlapping_gate_rows(program, c.n_body())) != QIDDM_OK) return rc;
   if ((rc = check_backward_outputs(c, embeds, grad_out, gout_ld, grad_rows, grad_gates, grad_features)) != QIDDM_OK) return rc;
   MixedGeometry g;
   int32_t n_snaps = 0;
@@ -838,7 +883,7 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   const int level = program_level(program, n_ops);
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    return for_level(level, [&](auto lv) {
+    return for_op_level(level, [&](auto lv) {
       const auto run = [&](auto obs) {  // measure QIDDM_MEAS_OBS: the instantiation that seeds from the measurement table
         return launch<qiddm::mixed_backward_kernel<T, decltype(lv)::value, decltype(obs)::value>>(
             kMaxLds - 8192 /* the kernel also has 4.5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
@@ -934,6 +979,7 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
   int rc = check_call(c, kTileFused, &embeds);
   if (rc != QIDDM_OK || batch == 0) return rc;
   if ((rc = refuse_sampled(program, n_ops)) != QIDDM_OK) return rc;
+  if ((rc = refuse_overlapping_gate_rows(program, c.n_body())) != QIDDM_OK) return rc;
   if ((rc = check_backward_outputs(c, embeds, grad_out, gout_ld, grad_rows, grad_gates, grad_features)) != QIDDM_OK) return rc;
   WideBwdPlan bp;
   if ((rc = plan_mixed_wide_backward(n_qubits, program, n_ops, &bp)) != QIDDM_OK) return rc;

@@ -20,6 +20,8 @@
 // channel works on the 4 x 4 blocks M[r][c] of its wires (r = 2 b_w1 + b_w2 from the row bits, c from the column bits):
 // vec(M) <- S vec(M), vec(M)[4r + c] = M[r][c], S 16 x 16 complex (mixed_block_super2 below; two-qubit depolarizing
 // behind an entangler, correlated dephasing, a two-letter PauliError, a measured two-qubit process).
+// The two-wire unitary works on the same 4 x 4 blocks: M <- U M U^dagger (mixed_block_gate2 below; SWAP, controlled
+// rotations, Ising gates, a learned two-qubit gate), and is un-computed in the reverse sweep like a one-wire gate.
 // Diagonal gates multiply by u_i conj(u_j); CZ by
 // sign(i) sign(j); CNOT permutes rows and columns (an involution: swapped in place).  Read-out: the diagonal -- or, for
 // a program that ends in kMixShots, estimates from that many shots drawn from it in the launch (qsim_mixed_shots.h); for a
@@ -57,23 +59,33 @@ enum MixedKind : int32_t {
   kMixChannel = 16, // general one-wire channel: gates[a .. a+3] are the rows of the 4 x 4 superoperator S (10..15: no kind)
   kMixObs = 20,     // tail of the program, not an op on rho: one term of the measurement table (coefficient p times the
                     // Pauli word with x-mask `wire` and z-mask `a`, output column wire2); see mixed_obs_read_out
-  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..19, 21..31: no kind)
+  kMixGate2 = 24,   // fixed two-wire unitary on (wire, wire2): gates[a .. a+3] are the rows of the 4 x 4 U (a unitary, not a
+                    // channel: un-computed in the reverse sweeps, and its rows get a gradient)
+  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..19, 21..23, 25..31: no kind)
 };
 
 struct MixedOp {
-  int32_t kind, wire, a, wire2;  // wire2: qiddm_mixed_op_t's `reserved`, read by kMixChannel2 (second wire) and kMixObs (column)
+  int32_t kind, wire, a, wire2;  // wire2: qiddm_mixed_op_t's `reserved`, read by kMixChannel2 / kMixGate2 (second wire) and kMixObs (column)
   double p, scale;
 };
 
 // Which general-channel cases an instantiation carries: each costs vector registers, so a program (tile-fused engine: a
-// segment) runs the lowest level that holds its ops.  A level carries the cases below it.
+// segment) runs the lowest level that holds its ops.  A level carries the cases below it.  kLevelGate2 is a flag beside
+// the level: the two-wire unitary is no channel, and a unitary-only program that holds one carries no channel case.
 enum MixedLevel : int {
   kLevelLean = 0,     // the five-scalar channels only
   kLevelChannel = 1,  // + kMixChannel
   kLevelChannel2 = 2, // + kMixChannel2 (where its S is staged: 256 V2<T> of static LDS)
+  kLevelGate2 = 4,    // flag: + kMixGate2
 };
 __host__ __device__ constexpr int mixed_level_of(int kind) {
-  return kind == kMixChannel2 ? kLevelChannel2 : kind == kMixChannel ? kLevelChannel : kLevelLean;
+  return kind == kMixGate2 ? kLevelGate2 : kind == kMixChannel2 ? kLevelChannel2 : kind == kMixChannel ? kLevelChannel : kLevelLean;
+}
+__host__ __device__ constexpr int mixed_channels_of(int level) { return level & 3; }  // the channel level without the flag
+__host__ __device__ constexpr bool mixed_has_gate2(int level) { return (level & kLevelGate2) != 0; }
+// the lowest level that holds the ops of both
+__host__ __device__ constexpr int mixed_level_join(int a, int b) {
+  return (mixed_channels_of(a) > mixed_channels_of(b) ? mixed_channels_of(a) : mixed_channels_of(b)) | ((a | b) & kLevelGate2);
 }
 
 struct MixedScalars {
@@ -434,6 +446,101 @@ __device__ __forceinline__ void mixed_block_super2(const MixedSuper2<T>& su, V2<
   }
 }
 
+// ---- the two-wire unitary ---------------------------------------------------------------------------------------------
+// U (4 x 4 complex, row-major in gates[a .. a+3], operator index 2 b_w1 + b_w2) is read like mixed_super's S: in float64,
+// rounded once to T, every coefficient pinned to scalar registers -- 16 complex numbers, as many as the one-wire
+// channel's.  The block geometry is the two-wire channel's (MixedBlock2).
+template <typename T>
+struct MixedU2 {
+  V2<T> u[4][4];
+};
+template <typename T>
+__device__ __forceinline__ MixedU2<T> mixed_unitary2(const MixedOp& op, const double* __restrict__ gates) {
+  const double* __restrict__ g = gates + (size_t)op.a * 8;
+  MixedU2<T> u;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      u.u[r][c] = V2<T>{mixed_uniform((T)g[(r * 4 + c) * 2]), mixed_uniform((T)g[(r * 4 + c) * 2 + 1])};
+  return u;
+}
+// M <- U M U^dagger (ADJOINT: U^dagger M U) on the 4 x 4 block v[4 r + c] in registers, written to the block at `base`
+// of `mem`: one output row at a time -- the row of U M (four temporaries), then the row of (U M) U^dagger, stored.  The
+// caller has loaded all 16 elements, so the block may be the one `v` came from.  Four-term sums in a fixed order.
+template <typename T, bool ADJOINT>
+__device__ __forceinline__ void mixed_block_gate2_store(const MixedU2<T>& u, const V2<T> (&v)[16], V2<T>* __restrict__ mem,
+                                                        uint32_t base, const MixedBlock2& b) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    V2<T> t[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      t[c] = ADJOINT ? cmulc<T>(v[c], u.u[0][r]) + cmulc<T>(v[4 + c], u.u[1][r]) + cmulc<T>(v[8 + c], u.u[2][r]) +
+                           cmulc<T>(v[12 + c], u.u[3][r])
+                     : cmul<T>(u.u[r][0], v[c]) + cmul<T>(u.u[r][1], v[4 + c]) + cmul<T>(u.u[r][2], v[8 + c]) +
+                           cmul<T>(u.u[r][3], v[12 + c]);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      mem[base | b.elem(4 * r + c)] =
+          ADJOINT ? cmul<T>(t[0], u.u[0][c]) + cmul<T>(t[1], u.u[1][c]) + cmul<T>(t[2], u.u[2][c]) + cmul<T>(t[3], u.u[3][c])
+                  : cmulc<T>(t[0], u.u[c][0]) + cmulc<T>(t[1], u.u[c][1]) + cmulc<T>(t[2], u.u[c][2]) + cmulc<T>(t[3], u.u[c][3]);
+  }
+}
+// the same on the block at `base` of `mem`, in place (the thread owns the block)
+template <typename T, bool ADJOINT>
+__device__ __forceinline__ void mixed_block_gate2(const MixedU2<T>& u, V2<T>* __restrict__ mem, uint32_t base,
+                                                  const MixedBlock2& b) {
+  V2<T> v[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) v[e] = mem[base | b.elem(e)];
+  mixed_block_gate2_store<T, ADJOINT>(u, v, mem, base, b);
+}
+// One 4 x 4 block of the reverse sweeps: acc += B_rho B_Lambda^dagger (N_ab = sum_c rho_ac conj(Lambda_bc), (re, im) of
+// N[a][b] at acc[2 (4 a + b)]), both blocks taken behind the gate, then rho and Lambda <- U^dagger B U in place.  Lambda
+// is read a row at a time beside the 16 elements of rho: the 32 sums are what fills the registers.
+template <typename T>
+__device__ __forceinline__ void mixed_block_gate2_reverse(const MixedU2<T>& u, double (&acc)[32], V2<T>* __restrict__ rho,
+                                                          V2<T>* __restrict__ lam, uint32_t base, const MixedBlock2& b) {
+  V2<T> r[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) r[e] = rho[base | b.elem(e)];
+#pragma unroll
+  for (int bb = 0; bb < 4; ++bb) {
+    V2<T> l[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) l[c] = lam[base | b.elem(4 * bb + c)];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const V2<T> nab = cmulc<T>(r[4 * a], l[0]) + cmulc<T>(r[4 * a + 1], l[1]) + cmulc<T>(r[4 * a + 2], l[2]) +
+                        cmulc<T>(r[4 * a + 3], l[3]);
+      acc[2 * (4 * a + bb)] += (double)nab.x;
+      acc[2 * (4 * a + bb) + 1] += (double)nab.y;
+    }
+  }
+  mixed_block_gate2_store<T, true>(u, r, rho, base, b);
+  mixed_block_gate2<T, true>(u, lam, base, b);
+}
+// GATE2: go += dL/dU from the reduced N `s` and the gate `gu` (both as (re, im) of the 16 entries, row-major): the 4 x 4
+// form of mixed_gate_grad_accumulate below
+__device__ __forceinline__ void mixed_gate2_grad_accumulate(const double* s, const double* __restrict__ gu, double* go) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) {
+      double re = 0.0, im = 0.0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const double ur = gu[(c * 4 + bb) * 2], ui = gu[(c * 4 + bb) * 2 + 1];
+        const double nr = s[(c * 4 + a) * 2], ni = s[(c * 4 + a) * 2 + 1];
+        re += ur * nr + ui * ni;
+        im += ur * ni - ui * nr;
+      }
+      go[(a * 4 + bb) * 2] += 2.0 * re;
+      go[(a * 4 + bb) * 2 + 1] += -2.0 * im;
+    }
+}
+
 // acc += B_rho B_Lambda^dagger of one block: N_ab = sum_c rho_ac conj(Lambda_bc), (re, im) of N00, N01, N10, N11
 template <typename T>
 __device__ __forceinline__ void mixed_block_n_accumulate(double (&acc)[8], V2<T> r00, V2<T> r01, V2<T> r10, V2<T> r11,
@@ -667,7 +774,7 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
       break;
     }
     case kMixChannel2: {
-      if constexpr (LEVEL >= kLevelChannel2) {
+      if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel2) {
         // 4^n / 16 blocks for 256 threads: fewer blocks than threads up to n = 5, one block (all of rho) at n = 2
         const int q2 = n - 1 - op.wire2;
         const MixedBlock2 b = mixed_block2(q, q2, q + n, q2 + n);
@@ -676,8 +783,18 @@ __device__ __forceinline__ void mixed_apply_op(const MixedOp& op, V2<T>* __restr
       }
       break;
     }
+    case kMixGate2: {
+      if constexpr (mixed_has_gate2(LEVEL)) {
+        // the two-wire channel's walk: fewer blocks than threads up to n = 5, one block at n = 2; no snapshot (a unitary)
+        const int q2 = n - 1 - op.wire2;
+        const MixedBlock2 b = mixed_block2(q, q2, q + n, q2 + n);
+        const MixedU2<T> u = mixed_unitary2<T>(op, gates);
+        for (uint32_t t = tid; t < DD / 16; t += 256) mixed_block_gate2<T, false>(u, rho, mixed_block2_base(t, b), b);
+      }
+      break;
+    }
     case kMixChannel: {
-      if constexpr (LEVEL >= kLevelChannel) {
+      if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel) {
         const MixedSuper<T> su = mixed_super<T>(op, gates);
         mixed_walk_blocks<T>(rho, snap, blk, DD / 4,
                              [&](C& m00, C& m01, C& m10, C& m11) { mixed_block_super<T>(su, m00, m01, m10, m11); });
@@ -770,6 +887,7 @@ __global__ __launch_bounds__(256) void mixed_obs_kernel(const MixedOp* __restric
 //         N = sum over the wire's 2 x 2 blocks of B_rho B_Lambda^dagger  (= Tr_other rho_k Lambda_k)
 //         dL/dtheta = Im Tr(G N);  GATE: R = U^dagger N, dL/dRe U_ab = 2 Re R_ba, dL/dIm U_ab = -2 Im R_ba
 //         rho, Lambda <- U^dagger B U  (one pass over both)
+//     two-wire unitary (GATE2): the same on the 4 x 4 blocks of its wires, N and R 4 x 4
 //     CZ / CNOT: applied to both (involutions)
 //     channel E: Lambda <- E^dagger(Lambda) (the general channel: S^H on vec of each block), rho <- snapshot (a channel is not inverted: Depolarizing(0.9) has
 //         condition number 5 per wire).  A native channel with a >= 0 (strength from a row) first reduces
@@ -813,7 +931,8 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ double s_red[256];
   __shared__ double s_v[256];
-  __shared__ double s_part[2][4][8];
+  constexpr bool kGate2 = mixed_has_gate2(LEVEL);
+  __shared__ double s_part[2][4][kGate2 ? 32 : 8];  // the four waves' partials of an op's sums, double-buffered
   const int n = m.n, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const uint32_t D = 1u << n, DD = 1u << (2 * n);
   // workspace per workgroup: [rho, Lambda unless in LDS] then n_snaps snapshots
@@ -857,7 +976,8 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
       const int q = n - 1 - op.wire;
       // a native channel that reads its strength from a row feeds that row like an angle op
       const bool graded = (op.kind == kMixPhaseDamp || op.kind == kMixAmpDamp || op.kind == kMixDepol) && op.a >= 0;
-      const bool param = op.kind == kMixPhase || op.kind == kMixRY || op.kind == kMixGate || graded;
+      const bool param = op.kind == kMixPhase || op.kind == kMixRY || op.kind == kMixGate || graded ||
+                         (kGate2 && op.kind == kMixGate2);
       switch (op.kind) {
         case kMixPhase:
         case kMixRY:
@@ -968,7 +1088,7 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
           break;
         }
         case kMixChannel2: {  // S^H on vec of each 4 x 4 block of Lambda, rho from the snapshot; its 64 rows of grad_gates stay zero
-          if constexpr (LEVEL >= kLevelChannel2) {
+          if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel2) {
             const int q2 = n - 1 - op.wire2;
             const MixedBlock2 bl = mixed_block2(q, q2, q + n, q2 + n);
             const auto su = mixed_super2<T>(op, gates);
@@ -978,8 +1098,25 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
           }
           break;
         }
+        case kMixGate2: {  // N of the 4 x 4 blocks in 32 doubles a thread; rho and Lambda un-computed in place
+          if constexpr (kGate2) {
+            const int q2 = n - 1 - op.wire2;
+            const MixedBlock2 bl = mixed_block2(q, q2, q + n, q2 + n);
+            const MixedU2<T> u = mixed_unitary2<T>(op, gates);
+            double acc[32];
+#pragma unroll
+            for (int k = 0; k < 32; ++k) acc[k] = 0.0;
+            for (uint32_t t = tid; t < DD / 16; t += 256) mixed_block_gate2_reverse<T>(u, acc, rho, lam, mixed_block2_base(t, bl), bl);
+#pragma unroll
+            for (int k = 0; k < 32; ++k) {
+              const double s = mixed_wave_sum(acc[k]);
+              if (lane == 0) s_part[buf][wave][k] = s;
+            }
+          }
+          break;
+        }
         case kMixChannel: {  // its four rows of grad_gates stay zero: channel operands get no gradient
-          if constexpr (LEVEL >= kLevelChannel) {
+          if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel) {
             const MixedSuper<T> su = mixed_super<T>(op, gates);
             const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
             for (uint32_t t = tid; t < DD / 4; t += 256) {
@@ -1028,7 +1165,13 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
       __syncthreads();
       if (param) {
         if (tid == 0) {
-          if (op.kind == kMixGate) {
+          if (kGate2 && op.kind == kMixGate2) {
+            if constexpr (kGate2) {
+              double s[32];
+              for (int k = 0; k < 32; ++k) s[k] = s_part[buf][0][k] + s_part[buf][1][k] + s_part[buf][2][k] + s_part[buf][3][k];
+              mixed_gate2_grad_accumulate(s, gates + (size_t)op.a * 8, grad_gates + ((size_t)sample * b.n_gates + op.a) * 8);
+            }
+          } else if (op.kind == kMixGate) {
             double s[8];
             for (int k = 0; k < 8; ++k) s[k] = s_part[buf][0][k] + s_part[buf][1][k] + s_part[buf][2][k] + s_part[buf][3][k];
             mixed_gate_grad_accumulate(s, gates + (size_t)op.a * 8, grad_gates + ((size_t)sample * b.n_gates + op.a) * 8);

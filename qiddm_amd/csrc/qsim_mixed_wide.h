@@ -9,8 +9,8 @@
 // are the tile number.  A segment holds
 //   * ops that are diagonal on vec(rho) -- PHASE, CZ, PhaseDamping -- on any wires: the factor of an element depends
 //     on its global index only (tile bits + local bits);
-//   * GATE / RY / AmplitudeDamping / Depolarizing / the general channel on a tile wire, CNOT and the general two-wire
-//     channel with both wires in the tile (2^12 / 16 = 256 blocks of 4 x 4: one per thread);
+//   * GATE / RY / AmplitudeDamping / Depolarizing / the general channel on a tile wire, CNOT, the two-wire unitary and
+//     the general two-wire channel with both wires in the tile (2^12 / 16 = 256 blocks of 4 x 4: one per thread);
 //   * ZERO / AMP_EMBED as its first op: the tile is generated instead of read.
 // The host cuts the program into segments (plan_mixed_wide in qiddm_mixed.hip) and uploads it sorted by segment.
 // Wires n-1 and n-2 (q = 0, 1) belong to every tile: the two lowest column bits are local, so a lane moves two
@@ -132,6 +132,20 @@ __device__ __forceinline__ void wide_channel2(const MixedOp& op, V2<T>* tile, co
   for (uint32_t t = threadIdx.x; t < kWideTile / 16; t += 256) mixed_block_super2<T, ADJOINT>(su, tile, nullptr, mixed_block2_base(t, bl), bl);
 }
 
+// the 4 x 4 blocks of the op's two tile wires, by local ranks (the geometry wide_channel2 above works out for itself)
+__device__ __forceinline__ MixedBlock2 wide_block2(const MixedOp& op, const MixedScalars& m, const WideSegment& sg) {
+  const int n = m.n, q = n - 1 - op.wire, q2 = n - 1 - op.wire2;
+  return mixed_block2(wide_local_rank(sg, q), wide_local_rank(sg, q2), wide_local_rank(sg, q + n), wide_local_rank(sg, q2 + n));
+}
+// the two-wire unitary on a tile: U M U^dagger on its 256 blocks of 4 x 4, one per thread
+template <typename T>
+__device__ __forceinline__ void wide_gate2(const MixedOp& op, V2<T>* tile, const double* __restrict__ gates,
+                                           const MixedScalars& m, const WideSegment& sg) {
+  const MixedBlock2 bl = wide_block2(op, m, sg);
+  const MixedU2<T> u = mixed_unitary2<T>(op, gates);
+  for (uint32_t t = threadIdx.x; t < kWideTile / 16; t += 256) mixed_block_gate2<T, false>(u, tile, mixed_block2_base(t, bl), bl);
+}
+
 // One op of a channel kind on a tile in LDS with this sample's strength: E, or with ADJOINT E^dagger.  It is the
 // channel body of mixed_wide_adjoint_channels_graded in both directions.  mixed_wide_sweep and
 // mixed_wide_adjoint_channels list the same cases themselves, one walker call each: the compiler fuses the native
@@ -145,7 +159,7 @@ __device__ __forceinline__ void wide_channel_op(const MixedOp& op, V2<T>* tile, 
                                                 const MixedScalars& m, const WideSegment& sg, int64_t sample) {
   using C = V2<T>;
   const int n = m.n, q = n - 1 - op.wire;
-  if constexpr (LEVEL >= kLevelChannel2) {
+  if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel2) {
     if (op.kind == kMixChannel2) {
       wide_channel2<T, ADJOINT>(op, tile, gates, m, sg);
       return;
@@ -157,15 +171,15 @@ __device__ __forceinline__ void wide_channel_op(const MixedOp& op, V2<T>* tile, 
     return;
   }
   // one walk for the general and the native kinds, the kind tested inside it
-  const bool general = LEVEL >= kLevelChannel && op.kind == kMixChannel;
+  const bool general = mixed_channels_of(LEVEL) >= kLevelChannel && op.kind == kMixChannel;
   MixedSuper<T> su{};
   MixedChannel<T> ch{};
-  if constexpr (LEVEL >= kLevelChannel) {
+  if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel) {
     if (general) su = mixed_super<T>(op, gates);
   }
   if (!general) ch = mixed_channel<T>(op.kind, mixed_angle(op, angle_rows, m, sample));
   wide_walk_blocks<T>(tile, wide_block(sg, q, n), [&](C& m00, C& m01, C& m10, C& m11) {
-    if constexpr (LEVEL >= kLevelChannel) {
+    if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel) {
       if (general) {
         if (ADJOINT) mixed_block_super_adjoint<T>(su, m00, m01, m10, m11);
         else mixed_block_super<T>(su, m00, m01, m10, m11);
@@ -279,7 +293,7 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         break;
       }
       case kMixChannel: {
-        if constexpr (LEVEL >= kLevelChannel) {
+        if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel) {
           const MixedSuper<T> su = mixed_super<T>(op, gates);
           wide_walk_blocks<T>(tile, wide_block(sg, q, n),
                               [&](C& m00, C& m01, C& m10, C& m11) { mixed_block_super<T>(su, m00, m01, m10, m11); });
@@ -287,7 +301,11 @@ __global__ __launch_bounds__(256) void mixed_wide_sweep(const MixedOp* __restric
         break;
       }
       case kMixChannel2: {
-        if constexpr (LEVEL >= kLevelChannel2) wide_channel2<T, false>(op, tile, gates, m, sg);
+        if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel2) wide_channel2<T, false>(op, tile, gates, m, sg);
+        break;
+      }
+      case kMixGate2: {
+        if constexpr (mixed_has_gate2(LEVEL)) wide_gate2<T>(op, tile, gates, m, sg);
         break;
       }
       default: break;

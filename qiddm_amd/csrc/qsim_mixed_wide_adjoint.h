@@ -11,7 +11,8 @@
 //   reverse   segments backwards, one launch over (tile, sample) each.
 //             unitary segment: mixed_wide_reverse_sweep holds the rho tile and the Lambda tile in LDS and walks the ops
 //               backwards: U^dagger . U on both, N = sum B_rho B_Lambda^dagger of the tile in double -> one partial per
-//               (slot, tile, sample).  PHASE is element-wise on any wire.
+//               (slot, tile, sample).  PHASE is element-wise on any wire.  The two-wire unitary (GATE2) is un-computed the
+//               same way on the 4 x 4 blocks of its wires: 32 partials, an instantiation of its own.
 //             channel segment: mixed_wide_adjoint_channels applies E^dagger to the Lambda tile; rho steps back one set.
 //               A segment with a native channel whose strength comes from a row (a >= 0) runs
 //               mixed_wide_adjoint_channels_graded instead: it also holds the rho tile in front of each such channel
@@ -78,7 +79,8 @@ __global__ __launch_bounds__(256) void mixed_wide_obs_seed(const MixedOp* __rest
 // other form of them is scheduled differently, and the float64 round at 10 wires measured 1 % slower on the walkers.
 // One unitary segment backwards on the rho tile and the Lambda tile of (tile, sample).  slot[oi] >= 0: the op feeds a
 // parameter and writes its tile partial(s) to partials[(resident * n_slots + slot + c) * tiles + tile].
-template <typename T>
+// GATE2: the instantiation that carries the two-wire unitary (32 tile partials; the segments without one run the other).
+template <typename T, bool GATE2 = false>
 __global__ __launch_bounds__(256) void mixed_wide_reverse_sweep(
     const MixedOp* __restrict__ prog, const int32_t* __restrict__ slot, const double* __restrict__ angle_rows,
     const double* __restrict__ gates, const double* __restrict__ grad_out, V2<T>* __restrict__ rho_slabs,
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256) void mixed_wide_reverse_sweep(
   using C = V2<T>;
   extern __shared__ __attribute__((aligned(32))) unsigned char smem_raw[];
   __shared__ uint32_t s_lo[64], s_hi[64];
-  __shared__ double s_part[2][4][8];
+  __shared__ double s_part[2][4][GATE2 ? 32 : 8];
   C* rt = reinterpret_cast<C*>(smem_raw);
   C* lt = rt + kWideTile;
   const int n = m.n, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -111,7 +113,25 @@ __global__ __launch_bounds__(256) void mixed_wide_reverse_sweep(
     const int q = n - 1 - op.wire;
     const int sl = slot[oi];
     int n_vals = 0;
-    switch (op.kind) {
+    bool gate2 = false;  // tested in front of the switch: a case label there changes the code of the other instantiation
+    if constexpr (GATE2) {
+      if (op.kind == kMixGate2) {  // one 4 x 4 block of each tile a thread: N in 32 doubles, both tiles un-computed in place
+        const MixedBlock2 bl = wide_block2(op, m, sg);
+        const MixedU2<T> u = mixed_unitary2<T>(op, gates);
+        double acc[32];
+#pragma unroll
+        for (int k = 0; k < 32; ++k) acc[k] = 0.0;
+        for (uint32_t t = tid; t < kWideTile / 16; t += 256) mixed_block_gate2_reverse<T>(u, acc, rt, lt, mixed_block2_base(t, bl), bl);
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+          const double s = mixed_wave_sum(acc[k]);
+          if (lane == 0) s_part[buf][wave][k] = s;
+        }
+        n_vals = 32;
+        gate2 = true;
+      }
+    }
+    if (!gate2) switch (op.kind) {
       case kMixPhase: {
         // Im Tr(Z N) = Im N00 - Im N11 = sum_k (1 - 2 rowbit_k) Im(rho_k conj(Lambda_k)); the same before and after
         C up, dn;
@@ -239,13 +259,13 @@ __global__ __launch_bounds__(256) void mixed_wide_adjoint_channels(const MixedOp
     if (!(diag && owned)) __syncthreads();
     owned = diag;
     const int q = n - 1 - op.wire;
-    if constexpr (LEVEL >= kLevelChannel2) {
+    if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel2) {
       if (op.kind == kMixChannel2) {
         wide_channel2<T, true>(op, lt, gates, m, sg);
         continue;
       }
     }
-    if (LEVEL >= kLevelChannel && op.kind == kMixChannel) {  // S^H on vec of each block
+    if (mixed_channels_of(LEVEL) >= kLevelChannel && op.kind == kMixChannel) {  // S^H on vec of each block
       const MixedSuper<T> su = mixed_super<T>(op, gates);
       wide_walk_blocks<T>(lt, wide_block(sg, q, n),
                           [&](C& l00, C& l01, C& l10, C& l11) { mixed_block_super_adjoint<T>(su, l00, l01, l10, l11); });
@@ -375,6 +395,8 @@ __global__ __launch_bounds__(256) void mixed_wide_embed_grad(const double* __res
 
 // One wave per (parameter group, sample): the tile partials of every op of the group, summed lane-strided and then
 // across the wave, in program order.  group_begin[g] .. group_begin[g + 1] index `params`; a group's ops share kind and a.
+// GATE2: the instantiation for programs with a two-wire unitary (32 values an op where GATE has 8).
+template <bool GATE2 = false>
 __global__ __launch_bounds__(256) void mixed_wide_grad_finalize(const WideParam* __restrict__ params,
                                                                 const int32_t* __restrict__ group_begin, int32_t n_groups,
                                                                 const double* __restrict__ gates,
@@ -382,6 +404,7 @@ __global__ __launch_bounds__(256) void mixed_wide_grad_finalize(const WideParam*
                                                                 double* __restrict__ grad_rows, double* __restrict__ grad_gates,
                                                                 int32_t n_slots, int32_t n_gates, uint32_t tiles,
                                                                 int64_t batch, int64_t sample0) {
+  constexpr int kMaxVals = GATE2 ? 32 : 8;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + wave;
   if (g >= n_groups) return;
@@ -389,22 +412,34 @@ __global__ __launch_bounds__(256) void mixed_wide_grad_finalize(const WideParam*
   const double* __restrict__ part = partials + (size_t)resident * n_slots * tiles;
   const int begin = group_begin[g], end = group_begin[g + 1];
   const WideParam head = params[begin];
-  double go[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double go[kMaxVals];
+  for (int k = 0; k < kMaxVals; ++k) go[k] = 0.0;
   for (int pi = begin; pi < end; ++pi) {
     const WideParam p = params[pi];
-    const int n_vals = p.kind == kMixGate ? 8 : 1;
-    double s[8];
-    for (int c = 0; c < n_vals; ++c) {
+    const int n_vals = GATE2 && p.kind == kMixGate2 ? 32 : p.kind == kMixGate ? 8 : 1;
+    double s[kMaxVals];
+    const auto tile_sum = [&](int c) {
       const double* __restrict__ src = part + (size_t)(p.slot + c) * tiles;
       double v = 0.0;
       for (uint32_t t = lane; t < tiles; t += 64) v += src[t];
-      s[c] = mixed_wave_sum(v);
+      return mixed_wave_sum(v);
+    };
+    if constexpr (GATE2) {  // unrolled with the count tested inside: 32 sums indexed by a variable would live in scratch
+#pragma unroll
+      for (int c = 0; c < kMaxVals; ++c)
+        if (c < n_vals) s[c] = tile_sum(c);
+    } else {
+      for (int c = 0; c < n_vals; ++c) s[c] = tile_sum(c);
     }
-    if (p.kind == kMixGate) mixed_gate_grad_accumulate(s, gates + (size_t)p.a * 8, go);
+    if (GATE2 && p.kind == kMixGate2) mixed_gate2_grad_accumulate(s, gates + (size_t)p.a * 8, go);
+    else if (p.kind == kMixGate) mixed_gate_grad_accumulate(s, gates + (size_t)p.a * 8, go);
     else go[0] += p.scale * s[0];
   }
   if (lane != 0) return;
-  if (head.kind == kMixGate) {
+  if (GATE2 && head.kind == kMixGate2) {
+    double* __restrict__ dst = grad_gates + ((size_t)sample * n_gates + head.a) * 8;  // rows a .. a+3
+    for (int k = 0; k < 32; ++k) dst[k] = go[k];
+  } else if (head.kind == kMixGate) {
     double* __restrict__ dst = grad_gates + ((size_t)sample * n_gates + head.a) * 8;
     for (int k = 0; k < 8; ++k) dst[k] = go[k];
   } else {

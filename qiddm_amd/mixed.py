@@ -35,6 +35,15 @@ two-letter word: entangler error, correlated dephasing, a measured two-qubit pro
 out by the same helpers with ``wires=2``, travels as 64 rows of ``gates``, and the op's fourth field names the second
 wire.  Rows that one circuit records several times (one error model behind every entangler) are uploaded once.
 
+Gates beyond the reference's circuit family -- ``qml.Hadamard / S / T / SX`` and one-wire ``QubitUnitary`` (a constant
+row of ``QIDDM_MIX_GATE``), ``RX`` and ``Rot`` (``PHASE, RY, PHASE``: angle ops, so per-sample and differentiable), and the
+two-wire unitaries ``SWAP / ISWAP / CY``, ``CRX / CRY / CRZ / CRot``, ``ControlledPhaseShift``, ``IsingXX / YY / ZZ`` and
+two-wire ``QubitUnitary`` -- ``QIDDM_MIX_GATE2``: the 4 x 4 matrix travels as four rows of ``gates`` (operator index
+2 b_a + b_b, the first listed wire most significant), built in torch float64 from the gate's angles
+(``two_wire_matrix``; floats or 0-d tensors: the rows are shared by the batch) or taken from the caller's tensor
+(``unitary_rows``).  It is a unitary, not a channel: the reverse sweeps un-compute it and return dL/dU, which autograd
+carries on to the angles or to the tensor's entries.  Constant matrices are uploaded once per distinct matrix.
+
 Beyond 8 wires gradients are a second opt-in, ``set_max_grad_wires(10)`` or ``with max_grad_wires(10):`` -- the reverse
 sweep of the tile-fused engine (``qiddm_mixed_wide_backward``) keeps rho, its adjoint and one snapshot per group of
 channels per sample, several slabs where the forward keeps one.  With both limits raised a 9- or 10-wire launch is the
@@ -284,10 +293,87 @@ def rot_matrices(weights: torch.Tensor) -> torch.Tensor:
                         torch.cos(b) * s, -torch.sin(b) * s, torch.cos(a) * c, torch.sin(a) * c], dim=1).contiguous()
 
 
+# ---- one- and two-wire unitaries beyond the reference's circuit family ---------------------------------------------------
+_SQ = math.sqrt(0.5)
+# constant matrices, PennyLane's definitions (two wires: index 2 b_first + b_second, the control is the first wire)
+GATE_MATRICES = {
+    "Hadamard": np.array([[_SQ, _SQ], [_SQ, -_SQ]], dtype=complex),
+    "S": np.diag([1, 1j]).astype(complex),
+    "T": np.diag([1, complex(_SQ, _SQ)]).astype(complex),
+    "SX": 0.5 * np.array([[1 + 1j, 1 - 1j], [1 - 1j, 1 + 1j]]),
+    "SWAP": np.eye(4, dtype=complex)[[0, 2, 1, 3]],
+    "ISWAP": np.array([[1, 0, 0, 0], [0, 0, 1j, 0], [0, 1j, 0, 0], [0, 0, 0, 1]], dtype=complex),
+    "CY": np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, -1j], [0, 0, 1j, 0]], dtype=complex),
+}
+# parametrised two-wire gates -> the number of their angles
+TWO_WIRE_GATES = {"CRX": 1, "CRY": 1, "CRZ": 1, "CRot": 3, "ControlledPhaseShift": 1, "IsingXX": 1, "IsingYY": 1,
+                  "IsingZZ": 1}
+
+
+def unitary_rows(matrix) -> torch.Tensor:
+    """2 x 2 or 4 x 4 complex -> ``(1, 8)`` / ``(4, 8)`` float64 rows, (re, im) interleaved: the layout of QIDDM_MIX_GATE's
+    row and of QIDDM_MIX_GATE2's four.  A tensor stays on its device and in its graph (``torch.view_as_real``)."""
+    if torch.is_tensor(matrix):
+        return torch.view_as_real(matrix.to(torch.complex128).contiguous()).reshape(-1, 8)
+    m = np.ascontiguousarray(matrix, dtype=complex)
+    return torch.from_numpy(m.view(np.float64).reshape(-1, 8).copy())
+
+
+def check_unitary(matrix, wires):
+    """Host data of ``qml.QubitUnitary`` -> complex128 numpy (2^wires square), unitary to 1e-10 (the tolerance of
+    ``qubit_channel_rows``) or ``ValueError`` naming the deviation."""
+    d = 1 << wires
+    m = np.asarray(matrix.detach().numpy() if torch.is_tensor(matrix) else matrix, dtype=complex)
+    if m.shape != (d, d):
+        raise ValueError(f"QubitUnitary on {wires} wire(s) takes a {d} x {d} matrix (got shape {tuple(m.shape)})")
+    dev = np.abs(m.conj().T @ m - np.eye(d)).max()
+    if not dev <= 1e-10:
+        raise ValueError(f"QubitUnitary: the matrix is not unitary: U^dagger U differs from the identity by {dev:.3e}")
+    return m
+
+
+def two_wire_matrix(name, *angles) -> torch.Tensor:
+    """The 4 x 4 complex128 matrix of a parametrised two-wire gate (``TWO_WIRE_GATES``), PennyLane's definitions, built in
+    torch float64 on the device of its angles (floats: the CPU) and differentiable with respect to them.  Controlled
+    gates: diag(I, U) with the control the first wire; Ising gates: exp(-i theta/2 P (x) P)."""
+    if len(angles) != TWO_WIRE_GATES[name]:
+        raise TypeError(f"{name}: wrong number of angles ({len(angles)})")
+    device = next((a.device for a in angles if torch.is_tensor(a)), torch.device("cpu"))
+    th = [a.to(device=device, dtype=torch.float64) if torch.is_tensor(a) else torch.tensor(float(a), dtype=torch.float64,
+                                                                                            device=device) for a in angles]
+    cplx = lambda re, im=None: torch.complex(re, torch.zeros_like(re) if im is None else im)
+    if name.startswith("Ising"):
+        p = _PAULI[name[-1]]
+        pp = torch.from_numpy(np.kron(p, p)).to(device)
+        c, s = torch.cos(th[0] / 2), torch.sin(th[0] / 2)
+        return cplx(c) * torch.eye(4, dtype=torch.complex128, device=device) + cplx(torch.zeros_like(s), -s) * pp
+    zero, one = torch.zeros_like(th[0]), torch.ones_like(th[0])
+    if name == "ControlledPhaseShift":
+        u = [cplx(one), cplx(zero), cplx(zero), cplx(torch.cos(th[0]), torch.sin(th[0]))]
+    elif name == "CRZ":
+        c, s = torch.cos(th[0] / 2), torch.sin(th[0] / 2)
+        u = [cplx(c, -s), cplx(zero), cplx(zero), cplx(c, s)]
+    elif name == "CRY":
+        c, s = torch.cos(th[0] / 2), torch.sin(th[0] / 2)
+        u = [cplx(c), cplx(-s), cplx(s), cplx(c)]
+    elif name == "CRX":
+        c, s = torch.cos(th[0] / 2), torch.sin(th[0] / 2)
+        u = [cplx(c), cplx(zero, -s), cplx(zero, -s), cplx(c)]
+    else:  # CRot(phi, theta, omega): Rot = RZ(omega) RY(theta) RZ(phi), the matrix of rot_matrices
+        phi, theta, omega = th
+        c, s = torch.cos(theta / 2), torch.sin(theta / 2)
+        a, b = (phi + omega) / 2, (phi - omega) / 2
+        u = [cplx(torch.cos(a) * c, -torch.sin(a) * c), cplx(-torch.cos(b) * s, -torch.sin(b) * s),
+             cplx(torch.cos(b) * s, -torch.sin(b) * s), cplx(torch.cos(a) * c, torch.sin(a) * c)]
+    z, o = cplx(zero), cplx(one)
+    return torch.stack([o, z, z, z, z, o, z, z, z, z, u[0], u[1], z, z, u[2], u[3]]).reshape(4, 4)
+
+
 class _Lowering:
     def __init__(self, n):
         self.n, self.ops, self.rows, self.gates = n, [], [], []
         self.n_gates, self.channel_base = 0, {}  # rows so far; bytes of a two-wire channel's rows -> their first row
+        self.gate_base = {}  # (rows, bytes) of a constant one- or two-wire unitary -> its first row
         self.batch, self.batched = None, False
         self.features, self.pad_with = None, 0.0
         self.device = None
@@ -349,7 +435,32 @@ class _Lowering:
         base = self.channel_base.get(key)
         if base is None:
             base = self.channel_base[key] = self._add_gates(rows)
-        self.ops.append((_capi.MIX_CHANNEL2, wire, base, 0.0, 1.0, second))  # the only six-field entry of `ops`
+        self.ops.append((_capi.MIX_CHANNEL2, wire, base, 0.0, 1.0, second))  # a six-field entry of `ops`, as gate2's and MIX_OBS's
+
+    def _gate_rows(self, rows):
+        """The first row of a unitary's `rows` among the gates.  Constant (host) rows join once per distinct matrix, found
+        by content as `channel2` finds its rows; rows on the GPU (a matrix built from a tensor angle, a trainable
+        QubitUnitary) stay in their graph and join as they are."""
+        if rows.is_cuda:
+            self._see(rows)
+            return self._add_gates(rows)
+        if rows.requires_grad:
+            raise RuntimeError("default.mixed runs on the GPU only: tensors must live on a HIP device (no CPU path)")
+        rows = rows.detach().contiguous()
+        key = (rows.shape[0], rows.numpy().tobytes())
+        base = self.gate_base.get(key)
+        if base is None:
+            base = self.gate_base[key] = self._add_gates(rows)
+        return base
+
+    def gate1(self, rows, wire):
+        """A one-wire unitary given as its ``(1, 8)`` row: MIX_GATE."""
+        self.op(_capi.MIX_GATE, wire, self._gate_rows(rows))
+
+    def gate2(self, rows, wire, second):
+        """A two-wire unitary given as its ``(4, 8)`` rows (operator index 2 b_wire + b_second): MIX_GATE2, a six-field
+        entry like `channel2`'s with the second wire in the fourth field of the op."""
+        self.ops.append((_capi.MIX_GATE2, wire, self._gate_rows(rows), 0.0, 1.0, second))
 
     def sel(self, weights, wires, imprimitive):
         n = len(wires)
@@ -484,6 +595,26 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
                     low.channel(channel_rows(t.name, float(p)), t.wires[0])
                 else:
                     low.op(CHANNELS[t.name], t.wires[0], -1, float(p))
+            elif t.name in ("RX", "Rot"):  # angle ops: floats, 0-d and per-sample tensors, differentiable like RZ / RY
+                # RX(theta) = RZ(-pi/2) RY(theta) RZ(pi/2) up to a global phase; Rot = RZ(omega) RY(theta) RZ(phi)
+                first_, theta, last_ = (math.pi / 2, t.params[0], -math.pi / 2) if t.name == "RX" else t.params
+                for kind, value in ((_capi.MIX_PHASE, first_), (_capi.MIX_RY, theta), (_capi.MIX_PHASE, last_)):
+                    row, const = low.angle(value)
+                    low.op(kind, t.wires[0], row, const)
+            elif "matrix" in t.hyper:  # a constant unitary: Hadamard, S, T, SX, SWAP, ISWAP, CY, host QubitUnitary, adjoints
+                rows = unitary_rows(t.hyper["matrix"])
+                if len(t.wires) == 2:
+                    low.gate2(rows, t.wires[0], t.wires[1])
+                else:
+                    low.gate1(rows, t.wires[0])
+            elif t.name in TWO_WIRE_GATES:
+                low.gate2(unitary_rows(two_wire_matrix(t.name, *t.params)), t.wires[0], t.wires[1])
+            elif t.name == "QubitUnitary":  # a GPU tensor: not looked into, differentiable through view_as_real
+                rows = unitary_rows(t.params[0])
+                if len(t.wires) == 2:
+                    low.gate2(rows, t.wires[0], t.wires[1])
+                else:
+                    low.gate1(rows, t.wires[0])
             elif "superoperator" in t.hyper:
                 if len(t.wires) == 2:
                     low.channel2(t.hyper["superoperator"], t.wires[0], t.wires[1])
@@ -536,7 +667,7 @@ class _Launch:
         self.pad_with, self.n_rows = low.pad_with, len(low.rows)
         self.n_cols = low.n_cols
         self.prog = (_capi.MixedOp * len(low.ops))()
-        for dst, (kind, wire, a, p, scale, *second) in zip(self.prog, low.ops):  # second: MIX_CHANNEL2's other wire
+        for dst, (kind, wire, a, p, scale, *second) in zip(self.prog, low.ops):  # second: MIX_CHANNEL2's / MIX_GATE2's other wire
             dst.kind, dst.wire, dst.a, dst.reserved, dst.p, dst.scale = kind, wire, a, second[0] if second else 0, p, scale
 
     def _prefix(self, rows, gates, feats):

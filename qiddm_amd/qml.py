@@ -104,6 +104,138 @@ class ops:  # ``qml.ops.CZ`` as spelled at reference nn/qdense.py:263
     CZ = CZ
 
 
+# --- one- and two-wire gates beyond the reference's circuits: `default.mixed` only -----------------------------------------
+# They record an _Op like everything else; `qiddm_amd.mixed.lower` turns them into ops of the density-matrix program
+# (constant matrices and two-wire unitaries as rows of `gates`, RX and Rot as PHASE / RY / PHASE).  The pure-state devices
+# refuse them as they refuse every op outside their circuit family.
+def _gate_wires(name, wires, count):
+    w = _wires(wires)
+    if len(w) != count:
+        raise ValueError(f"{name} acts on {count} wire(s) (got wires={list(w)})")
+    if count == 2 and w[0] == w[1]:
+        raise ValueError(f"{name}: the two wires must differ (got {list(w)})")
+    return w
+
+
+def _constant_gate(name, count, self_adjoint=False):
+    """A gate with a fixed matrix (qiddm_amd.mixed.GATE_MATRICES); its adjoint records the conjugate transpose."""
+    def make(wires):
+        from . import mixed as _mixed
+        return _Op(name, _gate_wires(name, wires, count), matrix=_mixed.GATE_MATRICES[name])
+
+    def inverse(wires):
+        from . import mixed as _mixed
+        if self_adjoint:
+            return make(wires)
+        return _Op(f"Adjoint({name})", _gate_wires(name, wires, count), matrix=_mixed.GATE_MATRICES[name].conj().T.copy())
+
+    make.__name__ = name
+    make._adjoint = inverse
+    return make
+
+
+Hadamard = _constant_gate("Hadamard", 1, self_adjoint=True)
+S = _constant_gate("S", 1)
+T = _constant_gate("T", 1)
+SX = _constant_gate("SX", 1)
+SWAP = _constant_gate("SWAP", 2, self_adjoint=True)
+ISWAP = _constant_gate("ISWAP", 2)
+CY = _constant_gate("CY", 2, self_adjoint=True)
+
+
+def _neg(angle):
+    return -angle
+
+
+def RX(phi, wires):
+    """``qml.RX``: lowered to PHASE(pi/2), RY(phi), PHASE(-pi/2) -- RX up to a global phase --, so `phi` is a float, a 0-d
+    tensor or a 1-D tensor with one angle per sample, and differentiable."""
+    return _Op("RX", _gate_wires("RX", wires, 1), (phi,))
+
+
+def Rot(phi, theta, omega, wires):
+    """``qml.Rot`` = RZ(omega) RY(theta) RZ(phi): PHASE(phi), RY(theta), PHASE(omega); angles as for ``RX``."""
+    return _Op("Rot", _gate_wires("Rot", wires, 1), (phi, theta, omega))
+
+
+def _two_wire_gate(name):
+    """A parametrised two-wire gate (qiddm_amd.mixed.two_wire_matrix): one 4 x 4 matrix for the whole batch, built from
+    floats or 0-d tensors and differentiable with respect to them."""
+    def make(*args, wires=None):
+        from . import mixed as _mixed
+        count = _mixed.TWO_WIRE_GATES[name]
+        if wires is None and len(args) == count + 1:
+            args, wires = args[:-1], args[-1]
+        if wires is None or len(args) != count:
+            raise TypeError(f"{name} takes {count} angle(s) and wires")
+        for a in args:
+            if getattr(a, "ndim", 0) >= 1:
+                raise NotImplementedError(
+                    f"{name}: a per-sample (1-D) angle is not supported: the gate's rows are shared by the batch; use "
+                    "a float or a 0-d tensor (RX, RY, RZ, PhaseShift and Rot take per-sample angles)")
+        return _Op(name, _gate_wires(name, wires, 2), args)
+
+    def inverse(*args, wires=None):
+        # every angle negated, their order reversed (CRot(phi, theta, omega)^-1 = CRot(-omega, -theta, -phi))
+        if wires is None and args:
+            args, wires = args[:-1], args[-1]
+        return make(*[_neg(a) for a in reversed(args)], wires=wires)
+
+    make.__name__ = name
+    make._adjoint = inverse
+    return make
+
+
+CRX = _two_wire_gate("CRX")
+CRY = _two_wire_gate("CRY")
+CRZ = _two_wire_gate("CRZ")
+CRot = _two_wire_gate("CRot")
+ControlledPhaseShift = _two_wire_gate("ControlledPhaseShift")
+IsingXX = _two_wire_gate("IsingXX")
+IsingYY = _two_wire_gate("IsingYY")
+IsingZZ = _two_wire_gate("IsingZZ")
+
+
+def QubitUnitary(U, wires, _inverse=False):
+    """``qml.QubitUnitary(U, wires)`` on one wire (2 x 2) or two (4 x 4, index 2 b_a + b_b for ``wires=[a, b]``).  Data the
+    host can see (nested lists, NumPy, a CPU tensor) is checked for unitarity to 1e-10 (``ValueError``).  A complex tensor
+    on the GPU is not looked into -- that would synchronise -- and may require grad: the gradient reaches its entries."""
+    from . import mixed as _mixed
+    w = _wires(wires)
+    if len(w) > 2:
+        raise NotImplementedError(f"QubitUnitary on {len(w)} wires: one- and two-wire unitaries are supported")
+    w = _gate_wires("QubitUnitary", w, len(w) or 1)
+    d = 1 << len(w)
+    if torch.is_tensor(U) and U.is_cuda:
+        if tuple(U.shape) != (d, d) or not U.is_complex():
+            raise ValueError(f"QubitUnitary on {len(w)} wire(s) takes a complex {d} x {d} matrix (got {U.dtype}, shape "
+                             f"{tuple(U.shape)})")
+        return _Op("QubitUnitary", w, (U.mH if _inverse else U,))
+    m = _mixed.check_unitary(U, len(w))
+    return _Op("QubitUnitary", w, matrix=m.conj().T.copy() if _inverse else m)
+
+
+QubitUnitary._adjoint = lambda U, wires: QubitUnitary(U, wires, _inverse=True)
+RX._adjoint = lambda phi, wires: RX(_neg(phi), wires)
+Rot._adjoint = lambda phi, theta, omega, wires: Rot(_neg(omega), _neg(theta), _neg(phi), wires)
+RZ._adjoint = lambda phi, wires: RZ(_neg(phi), wires)
+RY._adjoint = lambda phi, wires: RY(_neg(phi), wires)
+PhaseShift._adjoint = lambda phi, wires: PhaseShift(_neg(phi), wires)
+CNOT._adjoint = CNOT
+CZ._adjoint = CZ
+
+
+def adjoint(gate):
+    """``qml.adjoint(gate)(*params, wires=...)`` for the gates above and RZ, RY, PhaseShift, CNOT, CZ: negated angles, the
+    conjugate-transposed matrix, or the gate itself."""
+    inverse = getattr(gate, "_adjoint", None)
+    if inverse is None:
+        raise NotImplementedError(f"adjoint of {getattr(gate, '__name__', gate)!r} is not supported: adjoint takes RZ, RY, "
+                                  "PhaseShift, RX, Rot, Hadamard, S, T, SX, CNOT, CZ, CY, SWAP, ISWAP, the controlled "
+                                  "rotations, ControlledPhaseShift, the Ising gates and QubitUnitary")
+    return inverse
+
+
 class StronglyEntanglingLayers:
     """``qml.StronglyEntanglingLayers(weights[S, n, 3], wires, ranges=None, imprimitive=CNOT)``."""
 
