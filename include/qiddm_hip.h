@@ -89,7 +89,10 @@ typedef enum qiddm_imprimitive {
 typedef enum qiddm_measure {
   QIDDM_MEAS_PROBS = 0, /* qml.probs(wires=range(n))                 (nn/qdense.py:47)       */
   QIDDM_MEAS_EXPZ = 1,  /* [qml.expval(qml.PauliZ(i)) for i in ...]  (nn/qdense.py:264)      */
-  QIDDM_MEAS_OBS = 2    /* density-matrix executor only: the Pauli-word table the program ends in (QIDDM_MIX_OBS) */
+  QIDDM_MEAS_OBS = 2,   /* density-matrix executor only: the Pauli-word table the program ends in (QIDDM_MIX_OBS) */
+  QIDDM_MEAS_RHO = 8    /* density-matrix executor only: the reduced density matrix of the wires the program's last op keeps
+                         * (QIDDM_MIX_RHO).  3 and 4 are deliberately no measures: they stay "unknown measure"; the pure-state
+                         * entry points refuse 8 as they refuse QIDDM_MEAS_OBS */
 } qiddm_measure;
 
 typedef enum qiddm_dtype {
@@ -689,12 +692,43 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *                             op %d` (checked behind the sampled read-out's refusal, in front of the outputs).  PennyLane's
  *                             SWAP, ISWAP, CY, CRX / CRY / CRZ / CRot, ControlledPhaseShift, IsingXX / YY / ZZ and
  *                             QubitUnitary on two wires are this op.
- * Kinds 10, 11, 13..15, 17..19, 21..23, 25..31 and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
+ *   QIDDM_MIX_RHO (= 28)      legal only as the LAST op and only once (`op %d: a density-matrix read-out must be the last op`);
+ *                             not an operation on rho: it says which wires the read-out of measure = QIDDM_MEAS_RHO keeps.
+ *                             `wire` is the keep-mask, wire w at bit n-1-w, in [1, 2^n) (`op %d: keep mask %d out of range`);
+ *                             `a` and `reserved` must be 0 (`op %d: a density-matrix read-out takes a 0 and reserved 0`); `p`
+ *                             and `scale` are not read.  With k = popcount(mask) and K = 2^k, out / grad_out are
+ *                             (batch, ld >= 2 K^2) float64: element (r, c) of the reduced matrix at columns 2 (r K + c) (real
+ *                             part) and 2 (r K + c) + 1 (imaginary part).  r and c number the bit strings of the kept wires in
+ *                             ascending wire order, the lowest wire most significant (the bit order of probs); with e running
+ *                             over the 2^(n-k) bit strings of the traced-out wires and dep(r, e) the n-bit index that holds r's
+ *                             bits at the mask's positions and e's at the others,
+ *                               out[sample][r][c] = sum_e rho[dep(r, e)][dep(c, e)],
+ *                             float64, added in a fixed order (64 or more traced values: 64 strided partial sums in ascending
+ *                             e, then a butterfly over them; fewer: ascending e), no atomics: reruns are bit-identical and
+ *                             the chunking of the tile-fused engine does not show.  k = n is rho itself, converted to float64.
+ *                             The reverse sweeps pair their adjoint Lambda with rho as Re sum_ij conj(Lambda_ij) rho_ij, and
+ *                             every state they meet is Hermitian; they have only ever been seeded with Hermitian matrices.
+ *                             With g_re[r][c] = grad_out[2 (r K + c)] and g_im[r][c] = grad_out[2 (r K + c) + 1] the loss's
+ *                             differential is sum g_re Re(d rho_A) + g_im Im(d rho_A) = Re sum_ij conj(G_ij) d rho_ij for
+ *                             G_ij = g_re[r][c] + i g_im[r][c] where ((i ^ j) & ~mask) == 0 (r, c: the kept bits of i, j) and
+ *                             G_ij = 0 elsewhere.  G's anti-Hermitian part pairs to zero with every Hermitian matrix, so it
+ *                             contributes to no gradient, and the sweeps start from the Hermitian part:
+ *                               Lambda_N[i][j] = (g_re[r][c] + g_re[c][r]) / 2 + i (g_im[r][c] - g_im[c][r]) / 2.
+ *                             Under any other measure the op is QIDDM_ERR_INVALID (`op %d: a density-matrix read-out needs
+ *                             measure QIDDM_MEAS_RHO`), QIDDM_MEAS_RHO without it likewise (`measure QIDDM_MEAS_RHO needs a
+ *                             density-matrix read-out as the last op`), as is a QIDDM_MIX_OBS table in the same program
+ *                             (`op %d: a density-matrix read-out beside a measurement table`); a QIDDM_MIX_SHOTS in the same
+ *                             program is QIDDM_ERR_UNSUPPORTED (`op %d: a sampled read-out beside a density-matrix read-out`).
+ *                             All of this is checked where the measurement table is, by everything that reads a program.  The
+ *                             planners count the op in no sweep, no snapshot and no slot; its op_segment entry is -1; no
+ *                             workspace size changes.  PennyLane's qml.state() (k = n), qml.density_matrix(wires) and what
+ *                             follows from them (purity, the expectation value of a Hermitian matrix) are this read-out.
+ * Kinds 10, 11, 13..15, 17..19, 21..23, 25..31 other than 28, and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
- * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n | columns of the table) float64 DEVICE arrays.
+ * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n | columns of the table | 2 * 4^k) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
  * batch / n_ops, measure (batch == 0 then returns QIDDM_OK with no pointer looked at), program (not empty, starts with a
- * state preparation), the measurement table (all of it, then against `measure`), negative n_rows / n_gates,
+ * state preparation), the density-matrix read-out or the measurement table (all of it, then against `measure`), negative n_rows / n_gates,
  * angle_rows / rows_ld, gates, the ops in front of the table one by one (kind, wire, target wire
  * or second wire -- `op %d: bad second wire %d` when it is outside 0..n-1 or equal to `wire` --; QIDDM_MIX_SHOTS instead:
  * its position, wire / reserved, shots, seed, offset --,
@@ -709,6 +743,7 @@ enum {
   QIDDM_MIX_CHANNEL = 16,
   QIDDM_MIX_OBS = 20,
   QIDDM_MIX_GATE2 = 24,
+  QIDDM_MIX_RHO = 28,
   QIDDM_MIX_CHANNEL2 = 32
 };
 #define QIDDM_MIX_MAX_OBS 256 /* terms of a measurement table */
@@ -723,7 +758,7 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t 
                         const double *gates, int32_t n_gates, int32_t measure, int64_t batch, double *out,
                         int64_t out_ld, void *workspace, int64_t workspace_bytes, void *stream);
 /* Reverse sweep (vector-Jacobian product) of qiddm_mixed_forward: the same program and inputs, plus
- *   grad_out       (batch, gout_ld >= 2^n | n) float64 DEVICE: dL/d out
+ *   grad_out       (batch, gout_ld >= 2^n | n | columns of the table | 2 * 4^k) float64 DEVICE: dL/d out
  *   grad_rows      (n_rows, batch) float64 DEVICE: dL/d angle_rows (required when n_rows > 0)
  *   grad_gates     (batch, n_gates, 8) float64 DEVICE: per-sample dL/d gates (the caller sums over the batch;
  *                  required when n_gates > 0)

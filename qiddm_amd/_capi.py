@@ -23,6 +23,7 @@ QIDDM_OK = 0
 ENC_NONE, ENC_AMPLITUDE, ENC_RZ, ENC_RY, ENC_RY_BLOCKS = 0, 1, 2, 3, 4
 IMP_CNOT, IMP_CZ = 0, 1
 MEAS_PROBS, MEAS_EXPZ, MEAS_OBS = 0, 1, 2  # MEAS_OBS (density-matrix executor): the MIX_OBS table the program ends in
+MEAS_RHO = 8  # density-matrix executor: the reduced density matrix of the wires the MIX_RHO op keeps (3, 4: no measures)
 F32, F64 = 0, 1
 
 
@@ -76,6 +77,7 @@ MIX_CHANNEL = 16  # general one-wire channel: `a` = first of four gate rows hold
 # (wire w at bit n-1-w), output column `reserved`; at most MIX_MAX_OBS terms
 MIX_OBS, MIX_MAX_OBS = 20, 256
 MIX_GATE2 = 24  # two-wire unitary: `a` = first of four gate rows (the 4 x 4 matrix), `reserved` = the second wire
+MIX_RHO = 28  # last op only: the read-out keeps the wires of the mask `wire` (wire w at bit n-1-w); `a`, `reserved` = 0
 MIX_CHANNEL2 = 32  # general two-wire channel: `a` = first of 64 gate rows (16 x 16), `reserved` = the second wire
 
 

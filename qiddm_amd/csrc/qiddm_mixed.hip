@@ -11,6 +11,9 @@
 // Or it ends in a table of QIDDM_MIX_OBS terms (QIDDM_MEAS_OBS: Pauli-word expectation values): check_obs_tail validates
 // it wherever a program is read, the planners leave it out of every sweep, and it is uploaded behind the ops so that the
 // read-out and the seed of the reverse sweeps find it at prog[n_body ..).
+// Or it ends in one QIDDM_MIX_RHO op (QIDDM_MEAS_RHO: the reduced density matrix of the wires in its keep-mask): the same
+// tail check validates it, it is a tail of one op to everything that plans or uploads, and the read-out kernels and the
+// seed of the reverse sweeps take its mask.
 #include "capi_common.h"
 
 #include <hip/hip_runtime.h>
@@ -38,7 +41,8 @@ using qiddm_capi::launched;
 static_assert(sizeof(qiddm::MixedOp) == sizeof(qiddm_mixed_op_t), "program layout");
 static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixChannel == (int)QIDDM_MIX_CHANNEL &&
                   (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2 && (int)qiddm::kMixShots == (int)QIDDM_MIX_SHOTS &&
-                  (int)qiddm::kMixObs == (int)QIDDM_MIX_OBS && (int)qiddm::kMixGate2 == (int)QIDDM_MIX_GATE2,
+                  (int)qiddm::kMixObs == (int)QIDDM_MIX_OBS && (int)qiddm::kMixGate2 == (int)QIDDM_MIX_GATE2 &&
+                  (int)qiddm::kMixRho == (int)QIDDM_MIX_RHO,
               "op kinds");
 static_assert(offsetof(qiddm::MixedOp, wire2) == offsetof(qiddm_mixed_op_t, reserved), "the second wire travels in `reserved`");
 
@@ -177,13 +181,36 @@ int refuse_overlapping_gate_rows(const qiddm_mixed_op_t* program, int32_t n_ops)
 // The measurement table a program may end in: QIDDM_MIX_OBS ops and nothing else from the first one on.  Checks all of it
 // (position, count, masks, coefficient, columns; no QIDDM_MIX_SHOTS beside it) and counts its terms and columns; a
 // program without one gives 0, 0.  `n_qubits` has been checked.
-int check_obs_tail(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, int32_t* n_obs, int32_t* n_cols) {
-  *n_obs = *n_cols = 0;
+// The density-matrix read-out (one QIDDM_MIX_RHO op, the last) is checked here as well, in front of the table: position,
+// keep-mask, a / reserved, no table and no QIDDM_MIX_SHOTS beside it.  It counts as a tail of one op whose columns are the
+// 2 * 4^k doubles of the reduced matrix; *rho_mask is its keep-mask (0: the program has none).
+int check_obs_tail(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, int32_t* n_obs, int32_t* n_cols,
+                   int32_t* rho_mask) {
+  *n_obs = *n_cols = *rho_mask = 0;
   if (!program) return QIDDM_OK;
-  int first = -1, shots = -1;
+  int first = -1, shots = -1, rho = -1;
   for (int i = 0; i < n_ops; ++i) {
     if (program[i].kind == qiddm::kMixObs && first < 0) first = i;
     if (program[i].kind == qiddm::kMixShots && shots < 0) shots = i;
+    if (program[i].kind == qiddm::kMixRho && rho < 0) rho = i;
+  }
+  if (rho >= 0) {
+    const qiddm_mixed_op_t& op = program[rho];
+    if (rho != n_ops - 1) return fail(QIDDM_ERR_INVALID, "op %d: a density-matrix read-out must be the last op", rho);
+    if (op.wire < 1 || op.wire >= ((int64_t)1 << n))
+      return fail(QIDDM_ERR_INVALID, "op %d: keep mask %d out of range [1, 2^%d)", rho, op.wire, n);
+    if (op.a != 0 || op.reserved != 0)
+      return fail(QIDDM_ERR_INVALID, "op %d: a density-matrix read-out takes a 0 and reserved 0 (got %d, %d)", rho, op.a,
+                  op.reserved);
+    if (first >= 0)
+      return fail(QIDDM_ERR_INVALID, "op %d: a density-matrix read-out beside a measurement table (op %d)", rho, first);
+    if (shots >= 0)
+      return fail(QIDDM_ERR_UNSUPPORTED,
+                  "op %d: a sampled read-out beside a density-matrix read-out (shots estimate the diagonal only)", shots);
+    *n_obs = 1;
+    *n_cols = 2 << (2 * __builtin_popcount((unsigned)op.wire));
+    *rho_mask = op.wire;
+    return QIDDM_OK;
   }
   if (first < 0) return QIDDM_OK;
   if (shots >= 0)
@@ -253,11 +280,13 @@ struct MixedCall {
   const double* gates;
   int32_t n_gates, measure;
   int64_t batch;
-  int32_t n_obs = 0, n_cols = 0;  // the measurement table the program ends in: set by check_call
+  int32_t n_obs = 0, n_cols = 0;  // the measurement table (or the one density-matrix read-out) the program ends in: set by check_call
+  int32_t rho_mask = 0;           // the keep-mask of that read-out (0: none)
   int64_t width() const {  // of out / grad_out
-    return measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : measure == QIDDM_MEAS_OBS ? n_cols : n_qubits;
+    return measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits)
+           : measure == QIDDM_MEAS_OBS || measure == QIDDM_MEAS_RHO ? n_cols : n_qubits;
   }
-  int32_t n_body() const { return n_ops - n_obs; }  // the ops in front of the measurement table
+  int32_t n_body() const { return n_ops - n_obs; }  // the ops in front of the measurement table / the density-matrix read-out
 };
 
 // Everything the compute entry points check about a MixedCall, in the order include/qiddm_hip.h states: wires, dtype,
@@ -267,14 +296,19 @@ struct MixedCall {
 int check_call(MixedCall& c, const Engine& e, bool* embeds) {
   int rc = check_sizes(c.n_qubits, c.dtype, c.batch, c.n_ops, e);
   if (rc != QIDDM_OK) return rc;
-  if (c.measure != QIDDM_MEAS_PROBS && c.measure != QIDDM_MEAS_EXPZ && c.measure != QIDDM_MEAS_OBS)
+  if (c.measure != QIDDM_MEAS_PROBS && c.measure != QIDDM_MEAS_EXPZ && c.measure != QIDDM_MEAS_OBS &&
+      c.measure != QIDDM_MEAS_RHO)
     return fail(QIDDM_ERR_INVALID, "unknown measure %d", c.measure);
   if (c.batch == 0) return QIDDM_OK;
   if ((rc = check_program_start(c.program, c.n_ops)) != QIDDM_OK) return rc;
-  if ((rc = check_obs_tail(c.n_qubits, c.program, c.n_ops, &c.n_obs, &c.n_cols)) != QIDDM_OK) return rc;
+  if ((rc = check_obs_tail(c.n_qubits, c.program, c.n_ops, &c.n_obs, &c.n_cols, &c.rho_mask)) != QIDDM_OK) return rc;
+  if (c.measure == QIDDM_MEAS_RHO && !c.rho_mask)
+    return fail(QIDDM_ERR_INVALID, "measure QIDDM_MEAS_RHO needs a density-matrix read-out as the last op (QIDDM_MIX_RHO)");
+  if (c.measure != QIDDM_MEAS_RHO && c.rho_mask)
+    return fail(QIDDM_ERR_INVALID, "op %d: a density-matrix read-out needs measure QIDDM_MEAS_RHO (got %d)", c.n_body(), c.measure);
   if (c.measure == QIDDM_MEAS_OBS && c.n_obs == 0)
     return fail(QIDDM_ERR_INVALID, "measure QIDDM_MEAS_OBS needs a measurement table: QIDDM_MIX_OBS ops at the end of the program");
-  if (c.measure != QIDDM_MEAS_OBS && c.n_obs > 0)
+  if (c.measure != QIDDM_MEAS_OBS && c.n_obs > 0 && !c.rho_mask)
     return fail(QIDDM_ERR_INVALID, "op %d: a measurement table needs measure QIDDM_MEAS_OBS (got %d)", c.n_body(), c.measure);
   if (c.n_rows < 0 || c.n_gates < 0) return fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
   if (c.n_rows > 0 && (!c.angle_rows || c.rows_ld < c.batch)) return fail(QIDDM_ERR_INVALID, "angle_rows missing or rows_ld < batch");
@@ -477,8 +511,9 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
   // a sampled read-out (last op) is no op on rho: checked, then left out of every segment.  plan->order holds the
   // n_ops - 1 ops in front of it and its op_segment stays -1.
   // A measurement table (the tail of QIDDM_MIX_OBS terms) likewise: checked, in no sweep, op_segment -1.
-  int32_t n_obs = 0, n_cols = 0;
-  if ((rc = check_obs_tail(n, program, n_ops, &n_obs, &n_cols)) != QIDDM_OK) return rc;
+  // The density-matrix read-out (QIDDM_MIX_RHO, last op) is a tail of one op to the same effect.
+  int32_t n_obs = 0, n_cols = 0, rho_mask = 0;
+  if ((rc = check_obs_tail(n, program, n_ops, &n_obs, &n_cols, &rho_mask)) != QIDDM_OK) return rc;
   n_ops -= n_obs;
   const int32_t n_table = n_ops + n_obs, n_all = n_ops;  // n_all: the ops that a sampled read-out must be the last of
   if (ends_in_shots(program, n_ops)) {
@@ -569,6 +604,10 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
 template <typename T>
 int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resident, unsigned char* ws, const MixedCall& c,
                       double* out, qiddm::MixedScalars m, bool embeds, const qiddm::MixedShots& sh, hipStream_t st) {
+  // the workgroups that share a sample's reduced density matrix (4^k elements, 256 or -- a wave an element -- 4 a round)
+  const int rho_bits = 2 * __builtin_popcount((unsigned)c.rho_mask);
+  const int64_t rho_elems = (int64_t)1 << rho_bits, rho_round = (m.n - rho_bits / 2) >= 6 ? 4 : 256;
+  const unsigned rho_parts = (unsigned)std::min<int64_t>((rho_elems + rho_round - 1) / rho_round, 256);
   const size_t smem = (size_t)qiddm::kWideTile * sizeof(qiddm::V2<T>);
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
   double* norms = reinterpret_cast<double*>(ws + g.off_norms);
@@ -589,6 +628,9 @@ int launch_mixed_wide(const WidePlan& plan, const WideGeometry& g, int64_t resid
       hipLaunchKernelGGL(qiddm::mixed_wide_sampled_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0, sh);
     else if (m.measure == QIDDM_MEAS_OBS)
       hipLaunchKernelGGL(qiddm::mixed_wide_obs_read_out<T>, dim3(chunk), dim3(256), 0, st, prog, slabs, out, m, s0);
+    else if (m.measure == QIDDM_MEAS_RHO)
+      hipLaunchKernelGGL(qiddm::mixed_wide_rho_read_out<T>, dim3(rho_parts, chunk), dim3(256), 0, st, slabs, out, m, s0,
+                         (uint32_t)c.rho_mask);
     else
       hipLaunchKernelGGL(qiddm::mixed_wide_read_out<T>, dim3(chunk), dim3(256), 0, st, slabs, out, m, s0);
     if (const int rc = launched("mixed_wide"); rc != QIDDM_OK) return rc;
@@ -603,6 +645,7 @@ struct WideBwdPlan {
   WidePlan plan;                          // of the live ops, channels split off into segments of their own
   int32_t live_begin = 0, n_live = 0;
   int32_t n_obs = 0;                      // terms of the measurement table behind the live ops (in no segment)
+  int32_t rho_mask = 0;                   // or the keep-mask of the density-matrix read-out there (n_obs = 1)
   int32_t replay_end = 0;                 // segments [0, replay_end) are replayed: up to the last unitary one
   int32_t n_snaps = 0;                    // channel segments among them
   int32_t n_slots = 0;                    // tile partials per (tile, sample)
@@ -617,7 +660,7 @@ struct WideBwdPlan {
 int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, WideBwdPlan* bp) {
   int rc = check_plan_input(n, program, n_ops);
   int32_t n_cols = 0;
-  if (rc == QIDDM_OK) rc = check_obs_tail(n, program, n_ops, &bp->n_obs, &n_cols);
+  if (rc == QIDDM_OK) rc = check_obs_tail(n, program, n_ops, &bp->n_obs, &n_cols, &bp->rho_mask);
   if (rc == QIDDM_OK) rc = refuse_sampled(program, n_ops);
   if (rc != QIDDM_OK) return rc;
   n_ops -= bp->n_obs;  // the table has been checked; the plan is of the ops in front of it
@@ -742,6 +785,10 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
       hipLaunchKernelGGL(qiddm::mixed_wide_obs_seed<T>, dim3((unsigned)(DD / 1024), chunk), block, 0, st, prog, grad_out, lam,
                          m, bs, s0);
       bs.seed = 0;
+    } else if (m.measure == QIDDM_MEAS_RHO) {  // Lambda_N of the density-matrix read-out: likewise
+      hipLaunchKernelGGL(qiddm::mixed_wide_rho_seed<T>, dim3((unsigned)(DD / 1024), chunk), block, 0, st, grad_out, lam, m, bs,
+                         s0, (uint32_t)bp.rho_mask);
+      bs.seed = 0;
     }
     for (int s = n_seg - 1; s >= 0; --s) {
       if (!bp.plan.seg_channel[s]) {
@@ -829,6 +876,11 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
         return launch<qiddm::mixed_obs_kernel<T, decltype(lv)::value>>(
             kMaxLds - 8192 /* the kernel also has 4 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
             "mixed_obs_kernel", prog, angle_rows, features, gates, out, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m);
+      if (measure == QIDDM_MEAS_RHO)
+        return launch<qiddm::mixed_rho_kernel<T, decltype(lv)::value>>(
+            kMaxLds - 4096 /* the kernel also has 2 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
+            "mixed_rho_kernel", prog, angle_rows, features, gates, out, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m,
+            (uint32_t)c.rho_mask);
       return launch<qiddm::mixed_kernel<T, decltype(lv)::value>>(
           kMaxLds - 4096 /* the kernel also has 2 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
           "mixed_kernel", prog, angle_rows, features, gates, out, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m);
@@ -840,10 +892,10 @@ int64_t qiddm_mixed_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, in
                                              const qiddm_mixed_op_t* program, int32_t n_ops, int32_t max_blocks) {
   MixedGeometry g;
   int32_t n_snaps = 0;
-  int32_t n_obs = 0, n_cols = 0;  // a measurement table is checked and takes room in the program head only
+  int32_t n_obs = 0, n_cols = 0, rho_mask = 0;  // a measurement table (a density-matrix read-out) is checked and takes room in the program head only
   int rc = check_sizes(n_qubits, dtype, batch, n_ops, kOneWorkgroup);
   if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
-  if (rc == QIDDM_OK) rc = check_obs_tail(n_qubits, program, n_ops, &n_obs, &n_cols);
+  if (rc == QIDDM_OK) rc = check_obs_tail(n_qubits, program, n_ops, &n_obs, &n_cols, &rho_mask);
   if (rc == QIDDM_OK) rc = refuse_sampled(program, n_ops);
   if (rc == QIDDM_OK) rc = mixed_backward_geometry(n_qubits, dtype, batch, program, n_ops, max_blocks, &g, &n_snaps);
   if (rc != QIDDM_OK) return rc;
@@ -884,13 +936,17 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     return for_op_level(level, [&](auto lv) {
-      const auto run = [&](auto obs) {  // measure QIDDM_MEAS_OBS: the instantiation that seeds from the measurement table
-        return launch<qiddm::mixed_backward_kernel<T, decltype(lv)::value, decltype(obs)::value>>(
+      // measure QIDDM_MEAS_OBS: the instantiation that seeds from the measurement table; QIDDM_MEAS_RHO: from the
+      // density-matrix read-out's cotangent
+      const auto run = [&](auto obs, auto rho) {
+        return launch<qiddm::mixed_backward_kernel<T, decltype(lv)::value, decltype(obs)::value, decltype(rho)::value>>(
             kMaxLds - 8192 /* the kernel also has 4.5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
             "mixed_backward_kernel", prog, angle_rows, features, gates, grad_out, grad_rows, grad_gates,
             embeds ? grad_features : nullptr, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), m, b);
       };
-      return measure == QIDDM_MEAS_OBS ? run(std::true_type{}) : run(std::false_type{});
+      return measure == QIDDM_MEAS_OBS   ? run(std::true_type{}, std::false_type{})
+             : measure == QIDDM_MEAS_RHO ? run(std::false_type{}, std::true_type{})
+                                         : run(std::false_type{}, std::false_type{});
     });
   });
 }

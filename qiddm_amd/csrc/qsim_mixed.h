@@ -25,7 +25,8 @@
 // Diagonal gates multiply by u_i conj(u_j); CZ by
 // sign(i) sign(j); CNOT permutes rows and columns (an involution: swapped in place).  Read-out: the diagonal -- or, for
 // a program that ends in kMixShots, estimates from that many shots drawn from it in the launch (qsim_mixed_shots.h); for a
-// program that ends in a table of kMixObs terms, Pauli-word expectation values from the off-diagonals (mixed_obs_read_out).
+// program that ends in a table of kMixObs terms, Pauli-word expectation values from the off-diagonals (mixed_obs_read_out);
+// for a program that ends in kMixRho, the reduced density matrix of the kept wires (mixed_rho_read_out).
 // mixed_backward_kernel (below) differentiates the same programs: PennyLane trains QNodes on default.mixed with
 // backprop or parameter-shift.  n <= 8.
 //
@@ -61,7 +62,9 @@ enum MixedKind : int32_t {
                     // Pauli word with x-mask `wire` and z-mask `a`, output column wire2); see mixed_obs_read_out
   kMixGate2 = 24,   // fixed two-wire unitary on (wire, wire2): gates[a .. a+3] are the rows of the 4 x 4 U (a unitary, not a
                     // channel: un-computed in the reverse sweeps, and its rows get a gradient)
-  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..19, 21..23, 25..31: no kind)
+  kMixRho = 28,     // last op only, not an op on rho: the read-out is the reduced density matrix of the wires in the keep-mask
+                    // `wire` (wire w at bit n-1-w); see mixed_rho_read_out
+  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..19, 21..23, 25..27, 29..31: no kind)
 };
 
 struct MixedOp {
@@ -89,10 +92,10 @@ __host__ __device__ constexpr int mixed_level_join(int a, int b) {
 }
 
 struct MixedScalars {
-  int32_t n, n_ops, measure, n_features;  // measure 0 probs, 1 <Z_w>, 2 the measurement table behind the n_ops ops
+  int32_t n, n_ops, measure, n_features;  // measure 0 probs, 1 <Z_w>, 2 the measurement table behind the n_ops ops, 8 the reduced density matrix
   int64_t batch, rows_ld, feat_ld, out_ld;
   double enc_offset, pad_with;
-  int32_t slab_in_lds, n_obs;  // n_obs: terms of the measurement table, prog[n_ops .. n_ops + n_obs) (measure 2 only)
+  int32_t slab_in_lds, n_obs;  // n_obs: terms of the measurement table, prog[n_ops .. n_ops + n_obs) (measure 2; measure 8: the one kMixRho op)
 };
 
 template <typename T>
@@ -706,6 +709,94 @@ __device__ __forceinline__ V2<T> mixed_obs_seed_elem(const MixedOp* __restrict__
   return V2<T>{(T)re, (T)im};
 }
 
+// ---- the reduced density matrix (measure 8): partial trace over the wires outside a keep-mask ------------------------------
+// The program's last op is kMixRho; its `wire` is the keep-mask (wire w at bit n-1-w, k = popcount(mask) wires, K = 2^k).
+// r and c number the kept wires' bit strings, the lowest wire most significant (the order of probs); e numbers the
+// 2^(n-k) strings of the traced-out wires.  dep(r, e) puts r's bits at the mask's positions and e's at the others:
+//     rho_A[r][c] = sum_e rho[dep(r, e)][dep(c, e)]        out_row[2 (r K + c)] = Re, out_row[2 (r K + c) + 1] = Im
+// float64 sums in a fixed order whatever T is; k = n is rho itself, converted.
+// the low bits of v, in order, to the set positions of `mask` (n <= 10 positions; the mask is uniform over the launch)
+__device__ __forceinline__ uint32_t mixed_deposit(uint32_t v, uint32_t mask) {
+  uint32_t out = 0;
+#pragma unroll
+  for (int b = 0; b < 10; ++b)
+    if (mask >> b & 1u) {
+      out |= (v & 1u) << b;
+      v >>= 1;
+    }
+  return out;
+}
+// its inverse: the bits of v at the set positions of `mask`, packed
+__device__ __forceinline__ uint32_t mixed_extract(uint32_t v, uint32_t mask) {
+  uint32_t out = 0;
+  int at = 0;
+#pragma unroll
+  for (int b = 0; b < 10; ++b)
+    if (mask >> b & 1u) {
+      out |= (v >> b & 1u) << at;
+      ++at;
+    }
+  return out;
+}
+// One sample's rho -> its reduced matrix in out_row.  `part` of `n_parts` workgroups of 256 threads share the K^2 output
+// elements (the one-workgroup engine: 0 of 1).  With 64 or more traced values a wave owns an element: its lanes stride
+// e, mixed_wave_sum adds the 64 partials in a fixed order, waves stride the elements.  Below that a thread owns an
+// element and adds its <= 32 terms in ascending e.  No LDS, no barrier; every element is written once, by one thread.
+template <typename T>
+__device__ __forceinline__ void mixed_rho_read_out(const V2<T>* __restrict__ rho, double* __restrict__ out_row,
+                                                   uint32_t mask, int n, uint32_t part, uint32_t n_parts) {
+  const uint32_t D = 1u << n, rest = (D - 1u) & ~mask;
+  const int k = __popc(mask);
+  const uint32_t K = 1u << k, KK = 1u << (2 * k), E = 1u << (n - k);
+  if (E >= 64u) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t idx = part * 4u + (uint32_t)mixed_obs_wave(); idx < KK; idx += 4u * n_parts) {
+      const uint32_t row = mixed_deposit(idx >> k, mask), col = mixed_deposit(idx & (K - 1u), mask);
+      double re = 0.0, im = 0.0;
+      for (uint32_t e = lane; e < E; e += 64u) {
+        const uint32_t t = mixed_deposit(e, rest);
+        const V2<T> v = rho[((size_t)(row | t) << n) | (col | t)];
+        re += (double)v.x;
+        im += (double)v.y;
+      }
+      re = mixed_wave_sum(re);
+      im = mixed_wave_sum(im);
+      if (lane == 0) {  // (two 8-byte stores: a row of `out` is 8-byte aligned, no more, when out_ld is odd)
+        out_row[2 * (size_t)idx] = re;
+        out_row[2 * (size_t)idx + 1] = im;
+      }
+    }
+  } else {
+    for (uint32_t idx = part * 256u + threadIdx.x; idx < KK; idx += 256u * n_parts) {
+      const uint32_t row = mixed_deposit(idx >> k, mask), col = mixed_deposit(idx & (K - 1u), mask);
+      double re = 0.0, im = 0.0;
+      for (uint32_t e = 0; e < E; ++e) {
+        const uint32_t t = mixed_deposit(e, rest);
+        const V2<T> v = rho[((size_t)(row | t) << n) | (col | t)];
+        re += (double)v.x;
+        im += (double)v.y;
+      }
+      out_row[2 * (size_t)idx] = re;
+      out_row[2 * (size_t)idx + 1] = im;
+    }
+  }
+}
+// Element k = (i << n) | j of Lambda_N, the seed of a reverse sweep under measure 8 (g: this sample's row of grad_out, laid
+// out like out_row).  L = sum g_re[r][c] Re rho_A[r][c] + g_im[r][c] Im rho_A[r][c] pairs with rho as Re sum conj(G_ij)
+// rho_ij for G_ij = g_re[r][c] + i g_im[r][c] where i and j agree outside the mask (r, c: their kept bits) and 0
+// elsewhere.  G need not be Hermitian; the sweeps have only ever met Hermitian matrices, and the anti-Hermitian part of G
+// pairs to zero with every Hermitian rho, so the seed is G's Hermitian part (G + G^dagger) / 2.
+template <typename T>
+__device__ __forceinline__ V2<T> mixed_rho_seed_elem(const double* __restrict__ g, uint32_t k, uint32_t mask, int n) {
+  const uint32_t i = k >> n, j = k & ((1u << n) - 1u);
+  if ((i ^ j) & ~mask) return V2<T>{(T)0, (T)0};
+  const int kk = __popc(mask);
+  const uint32_t r = mixed_extract(i, mask), c = mixed_extract(j, mask);
+  const double* __restrict__ a = g + 2 * (((size_t)r << kk) | c);
+  const double* __restrict__ b = g + 2 * (((size_t)c << kk) | r);
+  return V2<T>{(T)(0.5 * (a[0] + b[0])), (T)(0.5 * (a[1] - b[1]))};
+}
+
 // Op `op` of the program on one sample's rho.  `snap` (NULL in the forward): where the backward's replay keeps rho as
 // it was before a channel or a state preparation.  The caller puts a barrier after every op.
 template <typename T, int LEVEL>
@@ -879,6 +970,27 @@ __global__ __launch_bounds__(256) void mixed_obs_kernel(const MixedOp* __restric
   }
 }
 
+// mixed_kernel with the reduced density matrix's read-out (measure 8: the program ended in kMixRho, `mask` is its keep-mask;
+// m.n_ops counts the ops in front of it).  An instantiation of its own, as the measurement table's.
+template <typename T, int LEVEL>
+__global__ __launch_bounds__(256) void mixed_rho_kernel(const MixedOp* __restrict__ prog,
+                                                        const double* __restrict__ angle_rows,
+                                                        const double* __restrict__ feats,
+                                                        const double* __restrict__ gates, double* __restrict__ out,
+                                                        V2<T>* __restrict__ workspace, const MixedScalars m,
+                                                        const uint32_t mask) {
+  using C = V2<T>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ double s_red[256];
+  C* rho = m.slab_in_lds ? reinterpret_cast<C*>(smem_raw) : workspace + ((size_t)blockIdx.x << (2 * m.n));
+
+  for (int64_t sample = blockIdx.x; sample < m.batch; sample += gridDim.x) {
+    mixed_replay<T, LEVEL>(prog, rho, angle_rows, feats, gates, s_red, m, sample);
+    mixed_rho_read_out<T>(rho, out + sample * m.out_ld, mask, m.n, 0u, 1u);
+    __syncthreads();
+  }
+}
+
 // ---- reverse sweep ------------------------------------------------------------------------------------------------
 // Per sample: replay the forward to rho_N (copying rho to a snapshot in front of every channel and every later state
 // preparation), seed the adjoint Lambda_N = dL/drho_N (diagonal: diag(g) for probs, sum_w g_w (1 - 2 bit_w) for <Z>),
@@ -921,7 +1033,8 @@ __device__ __forceinline__ void mixed_udag_b_u(V2<T>& b00, V2<T>& b01, V2<T>& b1
 // kept the bits on the n = 6 cases of tools/mixed_bits.py; it waits for a change that runs the whole list and the
 // timing.)
 // OBS: the seed is the measurement table's (measure 2); an instantiation of its own, the probs / <Z> one carries none of it.
-template <typename T, int LEVEL, bool OBS = false>
+// RHO: the seed is the reduced density matrix's (measure 8, the keep-mask in the kMixRho op behind the m.n_ops ops); likewise.
+template <typename T, int LEVEL, bool OBS = false, bool RHO = false>
 __global__ __launch_bounds__(256) void mixed_backward_kernel(
     const MixedOp* __restrict__ prog, const double* __restrict__ angle_rows, const double* __restrict__ feats,
     const double* __restrict__ gates, const double* __restrict__ grad_out, double* __restrict__ grad_rows,
@@ -965,6 +1078,9 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
       mixed_obs_seed_weights(s_v, g, terms, m.n_obs);
       __syncthreads();
       for (uint32_t k = tid; k < DD; k += 256) lam[k] = mixed_obs_seed_elem<T>(terms, m.n_obs, s_v, k, n);
+    } else if constexpr (RHO) {
+      const uint32_t mask = (uint32_t)prog[m.n_ops].wire;  // uniform: a scalar load
+      for (uint32_t k = tid; k < DD; k += 256) lam[k] = mixed_rho_seed_elem<T>(g, k, mask, n);
     } else {
       for (uint32_t k = tid; k < DD; k += 256) lam[k] = mixed_seed_elem<T>(g, k, m);
     }

@@ -334,6 +334,16 @@ __global__ __launch_bounds__(256) void mixed_wide_obs_read_out(const MixedOp* __
                         prog + m.n_ops, m.n_obs, m.n);
 }
 
+// the reduced density matrix's read-out (measure 8; mixed_rho_read_out of qsim_mixed.h) in its place: `mask` is the keep-mask
+// of the kMixRho op the program ended in.  Grid (parts, resident samples): the workgroups of a sample share its 4^k
+// output elements, each written once by one thread, so the result does not depend on `parts` or on the chunking.
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_rho_read_out(const V2<T>* __restrict__ slabs, double* __restrict__ out,
+                                                               const MixedScalars m, int64_t sample0, const uint32_t mask) {
+  mixed_rho_read_out<T>(slabs + ((size_t)blockIdx.y << (2 * m.n)), out + (sample0 + blockIdx.y) * m.out_ld, mask, m.n,
+                        blockIdx.x, gridDim.x);
+}
+
 // the sampled read-out (qsim_mixed_shots.h) in its place when the program ends in kMixShots: one workgroup per resident
 // sample, keyed by the absolute row sample0 + blockIdx.x, so the chunking does not move a stream
 template <typename T>

@@ -19,7 +19,8 @@
 //               and writes the tile partial of dL/dstrength = <Lambda, E'(rho)> to the channel's slot.  A trailing
 //               segment reads the last replayed set as its snapshot, so the host replays up to the last trailing
 //               segment that holds such a channel (only programs with one are planned differently).
-//             The first reverse launch generates Lambda_N from grad_out instead of reading it.
+//             The first reverse launch generates Lambda_N from grad_out instead of reading it (a measurement table and
+//             the reduced density matrix's read-out: a seed launch of their own writes Lambda's slab first).
 //   AMP_EMBED dL/dv from Re(Lambda_0) v: a matrix-vector pass over Lambda's slab, then one workgroup per sample.
 //   finalize  a wave per parameter (angle row / gate) and sample sums the tile partials in a fixed order: no atomics,
 //             reruns are bit-identical and the result does not depend on how the batch is chunked.
@@ -73,6 +74,22 @@ __global__ __launch_bounds__(256) void mixed_wide_obs_seed(const MixedOp* __rest
   const uint32_t k0 = blockIdx.x * 1024u + threadIdx.x;
 #pragma unroll 1
   for (int i = 0; i < 4; ++i) lam[k0 + 256u * i] = mixed_obs_seed_elem<T>(terms, m.n_obs, s_w, k0 + 256u * i, n);
+}
+
+// Lambda_N of the reduced density matrix's read-out (measure 8; mixed_rho_seed_elem of qsim_mixed.h: the Hermitian part of
+// the cotangent, zero where row and column differ outside the keep-mask), written to every resident sample's Lambda slab in
+// a launch of its own beside mixed_wide_obs_seed; the same grid, and the reverse launches behind it read the slab.
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_rho_seed(const double* __restrict__ grad_out,
+                                                           V2<T>* __restrict__ lam_slabs, const MixedScalars m,
+                                                           const WideBwdScalars b, int64_t sample0, const uint32_t mask) {
+  const int n = m.n;
+  const int64_t resident = blockIdx.y, sample = sample0 + resident;
+  const double* __restrict__ g = grad_out + sample * b.gout_ld;
+  V2<T>* __restrict__ lam = lam_slabs + ((size_t)resident << (2 * n));
+  const uint32_t k0 = blockIdx.x * 1024u + threadIdx.x;
+#pragma unroll 1
+  for (int i = 0; i < 4; ++i) lam[k0 + 256u * i] = mixed_rho_seed_elem<T>(g, k0 + 256u * i, mask, n);
 }
 
 // The kernel writes its loops over the two tiles out (the shared tile copies apart): at 256 vector registers every

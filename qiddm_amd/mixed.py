@@ -69,6 +69,17 @@ sweeps start from the table's Hermitian, in general complex and non-diagonal, ad
 range(n)]`` is still ``QIDDM_MEAS_EXPZ`` with the program it always had.  ``readout_prob=q`` scales a word by
 (1 - 2q)^weight (no BitFlip ops); with ``shots``, words of I and Z are signed sums of the sampled full probs and a word
 with X or Y raises ``NotImplementedError`` before a stream offset is taken (it needs a basis rotation).
+
+The state itself is a read-out too: ``qml.state()`` (on this device the full density matrix), ``qml.density_matrix(wires)``,
+``qml.purity(wires)`` and ``qml.expval(qml.Hermitian(A, wires))``, one or a list.  The program then ends in one
+``QIDDM_MIX_RHO`` op whose mask names the wires to keep (``QIDDM_MEAS_RHO``): the launch that holds rho traces the other
+wires out in float64 and returns the reduced matrix as ``(B, 2 * 4^k)`` reals, kept wires in ascending order.  Everything
+else is torch on that result behind ``torch.view_as_complex`` -- the listed wire order (a reshape and permute), the
+further trace down to one observable's wires when a list of ``Hermitian`` keeps the union of theirs, ``sum |rho_A|^2``,
+``Re Tr(rho_A A)`` -- so torch's complex autograd delivers the real cotangent the reverse sweeps are seeded with (its
+Hermitian part: see include/qiddm_hip.h) and carries dL/dA to a matrix that requires grad.  These forms are analytic
+only: a device with ``shots`` or ``readout_prob`` raises ``NotImplementedError`` (a read-out error acts on bit strings,
+not on rho), as does a return that mixes them with Pauli words or probs.
 """
 from __future__ import annotations
 
@@ -378,10 +389,11 @@ class _Lowering:
         self.features, self.pad_with = None, 0.0
         self.device = None
         self.strengths = []  # (row, parameter name) of every native channel whose strength is a tensor
-        self.n_cols = 0      # MEAS_OBS: the columns of the measurement table
+        self.n_cols = 0      # MEAS_OBS: the columns of the measurement table; MEAS_RHO: 2 * 4^k, the reduced matrix as reals
         # what `execute` does with the launch's (B, width) result (None: nothing)
         #   ("marginal", wires)   probs of these wires, in this order, from the full probs
         #   ("signed", signs)     (2^n, k) float64 host matrix: the columns' Z-word estimates from sampled full probs
+        #   ("rho", kept, items)  MEAS_RHO: the kept wires (ascending) and what to make of their reduced matrix, see `_rho_plan`
         self.post = None
         self.single = False  # one expval, not a list: the result loses its last axis
 
@@ -502,9 +514,76 @@ def z_signs(z, n):
     return 1.0 - 2.0 * parity
 
 
-def _measurement_plan(ret, n, shots):
-    """What the return value asks for -> ("probs" | "expz" | "marginal" | "obs", payload, single).  payload: the listed
-    wires of marginal probs; for "obs" one list of (coefficient, word) per column.  Refuses what is not supported."""
+def keep_mask(wires, n):
+    """The keep-mask of QIDDM_MIX_RHO: wire w at bit n-1-w."""
+    mask = 0
+    for w in wires:
+        mask |= 1 << (n - 1 - w)
+    return mask
+
+
+def _rho_plan(ms, single, n, shots, readout_prob):
+    """The measurements that read the density matrix itself -> ("rho", (kept, items), single): `kept` the wires the
+    launch keeps (ascending: the union of the observables' wires), `items` one (kind, wires, matrix) per measurement."""
+    from . import qml
+    if any(m.kind not in qml.RHO_KINDS for m in ms):
+        raise NotImplementedError("state / density_matrix / purity / expval(Hermitian) together with probs or Pauli-word "
+                                  "expectation values in one return are not supported: use two QNodes")
+    what = "expval(Hermitian)" if ms[0].kind == "hermitian" else ms[0].kind
+    if shots is not None:
+        raise NotImplementedError(f"{what} with shots: the density matrix is not estimated from computational-basis "
+                                  "shots; use shots=None")
+    if readout_prob is not None:
+        raise NotImplementedError(f"{what} on a device with readout_prob: a read-out error acts on measured bit strings, "
+                                  "not on rho; use a device without it")
+    if not single and any(m.kind != "hermitian" for m in ms):
+        raise NotImplementedError("a list of state / density_matrix / purity is not supported: return one of them, or a "
+                                  "list of expval(Hermitian)")
+    items = []
+    for m in ms:
+        wires = tuple(range(n)) if m.kind == "state" else m.wires
+        if len(set(wires)) != len(wires) or not wires or any(not 0 <= w < n for w in wires):
+            name = "Hermitian" if m.kind == "hermitian" else m.kind
+            raise ValueError(f"{name}(wires={list(wires)}): wires must be distinct and in 0..{n - 1}")
+        items.append((m.kind, wires, m.obs.matrix if m.kind == "hermitian" else None))
+    kept = tuple(sorted({w for _, wires, _ in items for w in wires}))
+    return "rho", (kept, items), single
+
+
+def reduce_to(rho, kept, wires):
+    """(B, 2^k, 2^k) complex, index bits the wires `kept` (ascending, the first most significant) -> the reduced matrix
+    of the listed `wires` (a subset, any order), index bits in the listed order: the other wires are traced out."""
+    k = len(kept)
+    if tuple(wires) == tuple(kept):
+        return rho
+    row, col = "abcdefghij"[:k], "klmnopqrst"[:k]
+    src = "".join(row) + "".join(col[i] if w in wires else row[i] for i, w in enumerate(kept))
+    dst = "".join(row[kept.index(w)] for w in wires) + "".join(col[kept.index(w)] for w in wires)
+    d = 1 << len(wires)
+    return torch.einsum(f"z{src}->z{dst}", rho.reshape(rho.shape[0], *([2] * (2 * k)))).reshape(rho.shape[0], d, d)
+
+
+def _rho_results(out, kept, items, single, device):
+    """The launch's (B, 2 * 4^k) reals -> what the measurements asked for; torch expressions, differentiable."""
+    batch, d = out.shape[0], 1 << len(kept)
+    rho = torch.view_as_complex(out.reshape(batch, d, d, 2))
+    results = []
+    for kind, wires, matrix in items:
+        if kind == "purity":  # sum |rho_A[r][c]|^2 = Tr rho_A^2 (rho_A is Hermitian); kept == sorted(wires), the order does not matter
+            results.append(out.square().sum(dim=1))
+        elif kind == "hermitian":
+            a = matrix if torch.is_tensor(matrix) else torch.from_numpy(np.asarray(matrix, dtype=complex))
+            a = a.to(device=device, dtype=torch.complex128)
+            results.append(torch.einsum("brc,cr->b", reduce_to(rho, kept, wires), a).real)
+        else:  # state, density_matrix
+            results.append(reduce_to(rho, kept, wires))
+    return results[0] if single else torch.stack(results, dim=1)
+
+
+def _measurement_plan(ret, n, shots, readout_prob=None):
+    """What the return value asks for -> ("probs" | "expz" | "marginal" | "obs" | "rho", payload, single).  payload: the
+    listed wires of marginal probs; for "obs" one list of (coefficient, word) per column; for "rho" see `_rho_plan`.
+    Refuses what is not supported."""
     from . import qml
     all_w = tuple(range(n))
     if isinstance(ret, qml._Measurement):
@@ -513,6 +592,8 @@ def _measurement_plan(ret, n, shots):
         ms, single = list(ret), False
     else:
         raise NotImplementedError("measurements must be probs(wires), expval(observable) or a list of expvals")
+    if any(m.kind in qml.RHO_KINDS for m in ms):
+        return _rho_plan(ms, single, n, shots, readout_prob)
     kinds = {"probs" if m.kind == "probs" else "expval" for m in ms}
     if len(kinds) > 1:
         raise NotImplementedError("probs and expval in one return are not supported: use two QNodes")
@@ -546,7 +627,7 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
     do to a word; `shots`: the program ends in MIX_SHOTS with this `seed` and stream `offset`.  Pauli-word expectation
     values end the program in a table of MIX_OBS terms (MEAS_OBS); marginal probs and sampled Z-words are the full-probs
     launch and a reduction in torch (`_Lowering.post`)."""
-    form, payload, single = _measurement_plan(ret, n, shots)
+    form, payload, single = _measurement_plan(ret, n, shots, readout_prob)
     low = _Lowering(n)
     all_w = tuple(range(n))
     first = True
@@ -642,6 +723,15 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
     if form == "marginal":
         low.post = ("marginal", payload)
         return low, _capi.MEAS_PROBS
+    if form == "rho":  # the program ends in the op that names the wires to keep; the rest is torch on the reduced matrix
+        kept, items = payload
+        for _, _, matrix in items:
+            if torch.is_tensor(matrix) and matrix.is_cuda:
+                low._see(matrix)
+        low.op(_capi.MIX_RHO, keep_mask(kept, n), 0)
+        low.n_cols = 2 << (2 * len(kept))
+        low.post = ("rho", kept, items, single)
+        return low, _capi.MEAS_RHO
     if not analytic_obs:  # words of I and Z from the sampled full probs: column c = sum_t p_t sum_k (-1)^popcount(k & z_t) probs[k]
         signs = np.zeros((1 << n, len(payload)))
         for c, column in enumerate(payload):
@@ -688,7 +778,8 @@ class _Launch:
 
     def forward(self, rows, gates, feats, wide=False):
         n, batch = self.n, self.batch
-        width = (1 << n) if self.measure == _capi.MEAS_PROBS else self.n_cols if self.measure == _capi.MEAS_OBS else n
+        width = (1 << n) if self.measure == _capi.MEAS_PROBS else \
+            self.n_cols if self.measure in (_capi.MEAS_OBS, _capi.MEAS_RHO) else n
         out = torch.empty(batch, width, dtype=torch.float64, device=self.device)
         if wide:
             ws = self._fresh(_capi.query("qiddm_mixed_wide_workspace_bytes", n, self.prec, self._resident(), self.prog,
@@ -765,7 +856,8 @@ def _check_strengths(rows, strengths):
 
 def execute(tape, ret, n, precision=None, _engine=None, device=None):
     """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)`` -- marginal
-    probs of k wires ``(B, 2^k)``, one expval ``(B,)``, a list of k expvals ``(B, k)`` --
+    probs of k wires ``(B, 2^k)``, one expval ``(B,)``, a list of k expvals ``(B, k)``; complex128 ``(B, 2^k, 2^k)`` for
+    ``state`` / ``density_matrix``, float64 ``(B,)`` for ``purity`` --
     (or the unbatched row), as ``default.mixed`` does.  Up to 8 wires: differentiable when grad mode is on and an input
     requires grad; otherwise a plain launch whose result has no ``grad_fn``.  9 and 10 wires (within the wire limit, see
     ``set_max_wires``): forward only unless ``set_max_grad_wires`` admits them too.  `device` (the QNode's ``qml.Device``):
@@ -822,6 +914,8 @@ def execute(tape, ret, n, precision=None, _engine=None, device=None):
             out = out.sum(dim=others)
         kept = sorted(wires)
         out = out.permute(0, *[1 + kept.index(w) for w in wires]).reshape(batch, 1 << len(wires))
+    elif low.post is not None and low.post[0] == "rho":
+        out = _rho_results(out, *low.post[1:], device)
     elif low.post is not None:  # ("signed", signs)
         out = out @ torch.from_numpy(low.post[1]).to(out)
     if low.single:

@@ -453,9 +453,59 @@ def Hamiltonian(coeffs, observables):
     return Observable(terms)
 
 
+class Hermitian:
+    """``qml.Hermitian(A, wires)``: the observable given by a 2^k x 2^k Hermitian matrix on k wires, index bits in the
+    listed wire order (the first wire most significant).  ``A`` is a NumPy array, a CPU tensor or a GPU tensor, and may
+    require grad.  Host data is checked to be Hermitian to 1e-10; a GPU tensor is not looked into.  Measured by
+    ``qml.expval`` on ``default.mixed`` (``Re Tr(rho_A A)`` from the reduced density matrix); it is no ``Observable``:
+    it has no Pauli expansion here, so ``@``, ``+``, ``-`` and ``c *`` refuse it."""
+
+    def __init__(self, A, wires):
+        self.wires = _wires(wires)
+        d = 1 << len(self.wires)
+        shape = tuple(A.shape) if hasattr(A, "shape") else tuple(np.shape(A))
+        if not self.wires or shape != (d, d):
+            raise ValueError(f"Hermitian on {len(self.wires)} wire(s) takes a {d} x {d} matrix (got shape {shape})")
+        if not (torch.is_tensor(A) and A.is_cuda):
+            host = np.asarray(A.detach().numpy() if torch.is_tensor(A) else A, dtype=complex)
+            dev = np.abs(host - host.conj().T).max()
+            if not dev <= 1e-10:
+                raise ValueError(f"Hermitian: the matrix is not Hermitian: A differs from A^dagger by {dev:.3e}")
+        self.matrix = A
+
+    def _refuse(self, *_):
+        raise NotImplementedError("Hermitian inside @, + or c *: a matrix observable has no Pauli expansion here; measure "
+                                  "it on its own (a list of expvals) and combine the values in torch")
+
+    __matmul__ = __rmatmul__ = __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __neg__ = _refuse
+
+    def __repr__(self):
+        return f"Hermitian(wires={list(self.wires)})"
+
+
 class _Measurement:
     def __init__(self, kind, wires, obs=None):
         self.kind, self.wires, self.obs = kind, wires, obs
+
+
+# the measurements that read the (reduced) density matrix itself: default.mixed only
+RHO_KINDS = ("state", "density_matrix", "purity", "hermitian")
+
+
+def state():
+    """``qml.state()``: on ``default.mixed`` the full density matrix, complex128 ``(B, 2^n, 2^n)``."""
+    return _Measurement("state", None)
+
+
+def density_matrix(wires):
+    """``qml.density_matrix(wires)``: the reduced density matrix of the listed wires, in the listed order (the first
+    most significant), complex128 ``(B, 2^k, 2^k)``; differentiable."""
+    return _Measurement("density_matrix", _wires(wires))
+
+
+def purity(wires):
+    """``qml.purity(wires)``: Tr rho_A^2 of the listed wires' reduced density matrix, float64 ``(B,)``."""
+    return _Measurement("purity", _wires(wires))
 
 
 def probs(wires=None):
@@ -464,9 +514,11 @@ def probs(wires=None):
 
 def expval(obs):
     """``qml.expval(obs)``.  ``PauliZ(i)`` is what every device measures; any other ``Observable`` (PauliX / PauliY /
-    Identity, tensor products, sums, ``Hamiltonian``) is measured on ``default.mixed``."""
+    Identity, tensor products, sums, ``Hamiltonian``) and ``Hermitian(A, wires)`` are measured on ``default.mixed``."""
     if isinstance(obs, PauliZ):
         return _Measurement("expz", obs.wires, obs)
+    if isinstance(obs, Hermitian):  # default.mixed: Re Tr(rho_A A) from the reduced density matrix
+        return _Measurement("hermitian", obs.wires, obs)
     if not isinstance(obs, Observable):
         raise NotImplementedError("only expval of Pauli words and their real linear combinations is supported "
                                   "(PauliX, PauliY, PauliZ, Identity, A @ B, c * A, A + B, Hamiltonian)")
@@ -549,7 +601,9 @@ def device(name, wires=1, shots=None, readout_prob=None, seed=None, **kwargs):
     ``NotImplementedError`` and ``readout_prob`` ``TypeError``; other keywords are ignored.
 
     ``default.mixed`` measures ``probs`` of all wires or of a subset, and ``expval`` of any ``Observable`` (Pauli words and
-    their real linear combinations), one or a list; the pure-state names measure ``probs`` of all wires or
+    their real linear combinations), one or a list; and, analytic only (no ``shots``, no ``readout_prob``), the state
+    itself: ``state()`` (the full density matrix), ``density_matrix(wires)``, ``purity(wires)`` and
+    ``expval(Hermitian(A, wires))``, one or a list, all differentiable; the pure-state names measure ``probs`` of all wires or
     ``[expval(PauliZ(i)) for i in range(n)]`` and refuse the rest with ``NotImplementedError``."""
     return Device(name, wires, shots=shots, readout_prob=readout_prob, seed=seed, **kwargs)
 
@@ -621,6 +675,11 @@ def _compile(tape, ret, n, dev):
     # measurement
     elsewhere = "; Pauli-word expectation values and marginal probs are measured on 'default.mixed'"
     for m in (ret if isinstance(ret, (list, tuple)) else [ret]):
+        if isinstance(m, _Measurement) and m.kind in RHO_KINDS:
+            what = "expval(Hermitian)" if m.kind == "hermitian" else m.kind
+            raise NotImplementedError(f"{what} on device {dev.short_name}: the statevector engines measure probs(all "
+                                      "wires) or [expval(PauliZ(i)) for i in range(n)]; state, density_matrix, purity and "
+                                      "expval(Hermitian) are measured on 'default.mixed'")
         if isinstance(m, _Measurement) and m.kind == "expval":
             raise NotImplementedError(f"expval({m.obs!r}) on device {dev.short_name}: the statevector engines measure "
                                       "probs(all wires) or [expval(PauliZ(i)) for i in range(n)]" + elsewhere)
