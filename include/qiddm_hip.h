@@ -723,7 +723,30 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *                             planners count the op in no sweep, no snapshot and no slot; its op_segment entry is -1; no
  *                             workspace size changes.  PennyLane's qml.state() (k = n), qml.density_matrix(wires) and what
  *                             follows from them (purity, the expectation value of a Hermitian matrix) are this read-out.
- * Kinds 10, 11, 13..15, 17..19, 21..23, 25..31 other than 28, and kinds above 32 are no ops: refused as `op %d: unknown kind %d`.
+ *   QIDDM_MIX_CHANNEL_FIT (= 18), QIDDM_MIX_CHANNEL2_FIT (= 34)
+ *                             QIDDM_MIX_CHANNEL and QIDDM_MIX_CHANNEL2 with rows that get a gradient ("16 k + 2 is the k-wire
+ *                             channel whose rows get a gradient").  Operands, checks, messages, their place in the check
+ *                             order, planning and every workspace size of the forwards are those of 16 and 32, and a
+ *                             forward gives, bit for bit, what the same program with the constant kinds gives.  In the
+ *                             reverse sweeps they do to the adjoint and to rho what 16 and 32 do (S^H per block; rho from
+ *                             the snapshot) and return, per sample, the gradient of the rows in the layout of the rows,
+ *                             entries treated as independent reals as for QIDDM_MIX_GATE / _GATE2: the sweeps pair the
+ *                             adjoint with rho as dL = Re sum conj(Lambda) d rho (which gives dL/dstrength = <Lambda,
+ *                             E'(rho)> for the native channels and 2 Re R_ba for QIDDM_MIX_GATE), so with Lambda' the
+ *                             adjoint behind the channel, M the block of rho in front of it (the snapshot) and
+ *                               W[r][c] = sum over the blocks of conj(vec(Lambda')[r]) vec(M)[c],
+ *                             dL/dRe S[r][c] = Re W[r][c] and dL/dIm S[r][c] = -Im W[r][c]: 16 complex sums for one wire,
+ *                             256 for two.  The gradient is with respect to unconstrained entries: staying completely
+ *                             positive and trace preserving is the caller's parametrisation.  Several ops may name the
+ *                             same rows: their gradients add.  Rows that PARTLY overlap those of another QIDDM_MIX_GATE /
+ *                             _GATE2 / _FIT op are refused by the two backward entry points like QIDDM_MIX_GATE2's (`op %d:
+ *                             gate rows %d..%d overlap those of op %d`).  Every sum runs in a fixed order, without atomics:
+ *                             reruns, a lowered max_blocks and a smaller tile-fused workspace give the same bits.  The
+ *                             tile-fused backward keeps 32 (one wire) or 512 (two wires) tile partials per such op, and,
+ *                             like a native channel with a >= 0, replays up to a trailing channel segment that holds
+ *                             one; qiddm_mixed_wide_backward_workspace_bytes and _backward_plan count both, for these
+ *                             kinds only.  A program without them runs the device code it ran before they existed.
+ * Kinds 10, 11, 13..15, 17, 19, 21..23, 25..31 other than 28, 33, and kinds above 34 are no ops: refused as `op %d: unknown kind %d`.
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
  * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n | columns of the table | 2 * 4^k) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
@@ -741,10 +764,12 @@ enum {
   QIDDM_MIX_CNOT, QIDDM_MIX_PHASE_DAMP, QIDDM_MIX_AMP_DAMP, QIDDM_MIX_DEPOL,
   QIDDM_MIX_SHOTS = 12,
   QIDDM_MIX_CHANNEL = 16,
+  QIDDM_MIX_CHANNEL_FIT = 18,
   QIDDM_MIX_OBS = 20,
   QIDDM_MIX_GATE2 = 24,
   QIDDM_MIX_RHO = 28,
-  QIDDM_MIX_CHANNEL2 = 32
+  QIDDM_MIX_CHANNEL2 = 32,
+  QIDDM_MIX_CHANNEL2_FIT = 34
 };
 #define QIDDM_MIX_MAX_OBS 256 /* terms of a measurement table */
 typedef struct qiddm_mixed_op {

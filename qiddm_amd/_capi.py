@@ -79,6 +79,8 @@ MIX_OBS, MIX_MAX_OBS = 20, 256
 MIX_GATE2 = 24  # two-wire unitary: `a` = first of four gate rows (the 4 x 4 matrix), `reserved` = the second wire
 MIX_RHO = 28  # last op only: the read-out keeps the wires of the mask `wire` (wire w at bit n-1-w); `a`, `reserved` = 0
 MIX_CHANNEL2 = 32  # general two-wire channel: `a` = first of 64 gate rows (16 x 16), `reserved` = the second wire
+# 16 k + 2: the k-wire channel whose rows get a gradient from the reverse sweeps (operands and forward as 16 / 32)
+MIX_CHANNEL_FIT, MIX_CHANNEL2_FIT = 18, 34
 
 
 class MixedOp(ctypes.Structure):

@@ -14,6 +14,10 @@
 // Or it ends in one QIDDM_MIX_RHO op (QIDDM_MEAS_RHO: the reduced density matrix of the wires in its keep-mask): the same
 // tail check validates it, it is a tail of one op to everything that plans or uploads, and the read-out kernels and the
 // seed of the reverse sweeps take its mask.
+// QIDDM_MIX_CHANNEL_FIT / _CHANNEL2_FIT are QIDDM_MIX_CHANNEL / _CHANNEL2 to every check, plan and forward (base_kind);
+// the reverse sweeps return the gradient of their rows from kernels of their own (qiddm::kLevelFit in the one-workgroup
+// engine; mixed_wide_adjoint_channels_fit and mixed_wide_fit_finalize in the tile-fused one), which a program without
+// these kinds never launches.
 #include "capi_common.h"
 
 #include <hip/hip_runtime.h>
@@ -42,7 +46,8 @@ static_assert(sizeof(qiddm::MixedOp) == sizeof(qiddm_mixed_op_t), "program layou
 static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixChannel == (int)QIDDM_MIX_CHANNEL &&
                   (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2 && (int)qiddm::kMixShots == (int)QIDDM_MIX_SHOTS &&
                   (int)qiddm::kMixObs == (int)QIDDM_MIX_OBS && (int)qiddm::kMixGate2 == (int)QIDDM_MIX_GATE2 &&
-                  (int)qiddm::kMixRho == (int)QIDDM_MIX_RHO,
+                  (int)qiddm::kMixRho == (int)QIDDM_MIX_RHO && (int)qiddm::kMixChannelFit == (int)QIDDM_MIX_CHANNEL_FIT &&
+                  (int)qiddm::kMixChannel2Fit == (int)QIDDM_MIX_CHANNEL2_FIT,
               "op kinds");
 static_assert(offsetof(qiddm::MixedOp, wire2) == offsetof(qiddm_mixed_op_t, reserved), "the second wire travels in `reserved`");
 
@@ -52,13 +57,20 @@ inline int64_t program_bytes(int32_t n_ops) { return round256((int64_t)n_ops * (
 
 // QIDDM_MIX_GATE2 (the two-wire unitary): validated like CHANNEL2's wires and GATE's rows, planned like CNOT, and in the
 // reverse sweeps a unitary -- no snapshot, 32 tile partials, a refusal of rows that partly overlap another gate's.
+// QIDDM_MIX_CHANNEL_FIT / _CHANNEL2_FIT (16 k + 2: the k-wire channel whose rows get a gradient): everything that
+// validates, plans or sizes reads them as the constant kinds (base_kind); the forwards and the tile-fused engine upload
+// them as such, so their kernels never meet the new kinds; the reverse sweeps give their rows a gradient.
+inline bool is_fit(int kind) { return kind == qiddm::kMixChannelFit || kind == qiddm::kMixChannel2Fit; }
+inline int base_kind(int kind) { return is_fit(kind) ? kind - 2 : kind; }
+inline bool is_channel2(int kind) { return base_kind(kind) == qiddm::kMixChannel2; }
 inline bool is_prep(int kind) { return kind == qiddm::kMixZero || kind == qiddm::kMixAmpEmbed; }
 inline bool is_diag(int kind) {
   return kind == qiddm::kMixPhase || kind == qiddm::kMixCZ || kind == qiddm::kMixPhaseDamp;
 }
 // the kernels have an instantiation per qiddm::MixedLevel (which general-channel cases they carry); a program (segment)
 // runs the lowest one that holds its ops: calls f(std::integral_constant<int, level>{})
-// (the kernels that only ever see channel segments: a level without the two-wire unitary's flag)
+// (the kernels that only ever see channel segments: a level without the two-wire unitary's flag).  None of these
+// dispatchers looks at qiddm::kLevelFit: that flag selects kernels of its own where a reverse sweep is launched.
 template <typename F>
 int for_level(int level, F&& f) {
   return level >= qiddm::kLevelChannel2 ? f(std::integral_constant<int, qiddm::kLevelChannel2>{})
@@ -76,20 +88,33 @@ int for_op_level(int level, F&& f) {
 }
 inline int program_level(const qiddm_mixed_op_t* program, int32_t n_ops) {
   int level = qiddm::kLevelLean;
-  for (int i = 0; i < n_ops; ++i) level = qiddm::mixed_level_join(level, qiddm::mixed_level_of(program[i].kind));
+  for (int i = 0; i < n_ops; ++i) {
+    level = qiddm::mixed_level_join(level, qiddm::mixed_level_of(base_kind(program[i].kind)));
+    if (is_fit(program[i].kind)) level |= qiddm::kLevelFit;
+  }
   return level;
+}
+// the program as the forward kernels (and every kernel of the tile-fused engine) read it: the constant kinds
+inline qiddm_mixed_op_t constant_op(qiddm_mixed_op_t op) {
+  op.kind = base_kind(op.kind);
+  return op;
 }
 inline bool is_gate2(int kind) { return kind == qiddm::kMixGate2; }
 // the rows of `gates` a GATE / GATE2 op reads and gets its gradient in: [a, a + n), n = 0 for every other kind
-inline int gate_rows(int kind) { return kind == qiddm::kMixGate ? 1 : is_gate2(kind) ? 4 : 0; }
+// (a trainable channel: the 4 or 64 rows of its superoperator)
+inline int gate_rows(int kind) {
+  return kind == qiddm::kMixGate ? 1 : is_gate2(kind) ? 4 : kind == qiddm::kMixChannelFit ? 4 : kind == qiddm::kMixChannel2Fit ? 64 : 0;
+}
 inline bool is_channel(int kind) {
   return kind == qiddm::kMixPhaseDamp || kind == qiddm::kMixAmpDamp || kind == qiddm::kMixDepol ||
-         kind == qiddm::kMixChannel || kind == qiddm::kMixChannel2;
+         base_kind(kind) == qiddm::kMixChannel || base_kind(kind) == qiddm::kMixChannel2;
 }
 // a native channel that reads its strength from an angle row: the reverse sweeps give that row a gradient
 inline bool is_graded(const qiddm_mixed_op_t& op) {
   return (op.kind == qiddm::kMixPhaseDamp || op.kind == qiddm::kMixAmpDamp || op.kind == qiddm::kMixDepol) && op.a >= 0;
 }
+// a channel whose gradient needs the state in front of it
+inline bool needs_front(const qiddm_mixed_op_t& op) { return is_graded(op) || is_fit(op.kind); }
 
 // ---- argument checks ---------------------------------------------------------------------------------------------------
 struct Engine {
@@ -159,10 +184,11 @@ int refuse_sampled(const qiddm_mixed_op_t* program, int32_t n_ops) {
 }
 
 // The reverse sweeps: the rows of two GATE / GATE2 ops are the same rows (their gradients add) or share none -- a
-// gradient for rows that partly overlap has no meaning.  Only a GATE2 op can overlap another's partly.
+// gradient for rows that partly overlap has no meaning.  Only a GATE2 op or a trainable channel (CHANNEL_FIT: 4 rows,
+// CHANNEL2_FIT: 64) can overlap another's partly.
 int refuse_overlapping_gate_rows(const qiddm_mixed_op_t* program, int32_t n_ops) {
   bool any = false;
-  for (int i = 0; i < n_ops; ++i) any = any || is_gate2(program[i].kind);
+  for (int i = 0; i < n_ops; ++i) any = any || is_gate2(program[i].kind) || is_fit(program[i].kind);
   if (!any) return QIDDM_OK;
   std::vector<int> gated;
   for (int i = 0; i < n_ops; ++i) {
@@ -241,8 +267,8 @@ int check_obs_tail(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, in
 // kind, wire and target / second wire of op i: all the planner reads of an op, and the first thing the validator checks
 // of it.  QIDDM_MIX_SHOTS is checked here in full (position, wire / reserved, shots, seed, offset): it indexes no operand.
 int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops) {
-  if ((op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) && op.kind != qiddm::kMixChannel &&
-      op.kind != qiddm::kMixChannel2 && op.kind != qiddm::kMixShots && !is_gate2(op.kind))
+  if ((op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) && base_kind(op.kind) != qiddm::kMixChannel &&
+      base_kind(op.kind) != qiddm::kMixChannel2 && op.kind != qiddm::kMixShots && !is_gate2(op.kind))
     return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
   if (is_prep(op.kind)) return QIDDM_OK;
   if (op.kind == qiddm::kMixShots) {
@@ -260,7 +286,7 @@ int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops) 
   if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
   if ((op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) && (op.a < 0 || op.a >= n || op.a == op.wire))
     return fail(QIDDM_ERR_INVALID, "op %d: bad target wire %d", i, op.a);
-  if ((op.kind == qiddm::kMixChannel2 || is_gate2(op.kind)) && (op.reserved < 0 || op.reserved >= n || op.reserved == op.wire))
+  if ((is_channel2(op.kind) || is_gate2(op.kind)) && (op.reserved < 0 || op.reserved >= n || op.reserved == op.wire))
     return fail(QIDDM_ERR_INVALID, "op %d: bad second wire %d", i, op.reserved);  // n_qubits = 1 cannot hold the op
   return QIDDM_OK;
 }
@@ -318,7 +344,7 @@ int check_call(MixedCall& c, const Engine& e, bool* embeds) {
   for (int i = 0; i < c.n_body(); ++i) {
     const qiddm_mixed_op_t& op = c.program[i];
     if ((rc = check_op_wires(c.n_qubits, op, i, c.n_body())) != QIDDM_OK) return rc;
-    switch (op.kind) {
+    switch (base_kind(op.kind)) {
       case qiddm::kMixAmpEmbed:
         if (!c.features || c.n_features < 1 || c.n_features > d)
           return fail(QIDDM_ERR_INVALID, "Features must be of length %lld or smaller; got length %d.", (long long)d, c.n_features);
@@ -527,7 +553,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
     if ((rc = check_op_wires(n, op, i, n_all)) != QIDDM_OK) return rc;
     wires[i] = is_prep(op.kind) ? all : 1u << op.wire;
     if (op.kind == qiddm::kMixCZ || op.kind == qiddm::kMixCNOT) wires[i] |= 1u << op.a;
-    if (op.kind == qiddm::kMixChannel2 || is_gate2(op.kind)) wires[i] |= 1u << op.reserved;  // both wires in the tile, as for CNOT
+    if (is_channel2(op.kind) || is_gate2(op.kind)) wires[i] |= 1u << op.reserved;  // both wires in the tile, as for CNOT
     plan->n_nondiag += is_diag(op.kind) ? 0 : 1;
   }
   plan->order.clear();
@@ -563,7 +589,7 @@ int plan_mixed_wide(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, W
       if (split_channels && !empty && is_channel(kind) != channels) ok = false;
       if (ok) {
         if (empty) channels = is_channel(kind);
-        level = qiddm::mixed_level_join(level, qiddm::mixed_level_of(kind));
+        level = qiddm::mixed_level_join(level, qiddm::mixed_level_of(base_kind(kind)));
         placed[i] = 1;
         plan->order.push_back(i);
         plan->op_segment[i] = (int32_t)plan->segments.size();
@@ -651,7 +677,10 @@ struct WideBwdPlan {
   int32_t n_slots = 0;                    // tile partials per (tile, sample)
   bool embed_live = false;
   bool gate2 = false;                     // a live GATE2: the finalize that sums 32 partials an op
-  std::vector<char> seg_graded;           // the (channel) segment holds a native channel with a >= 0
+  std::vector<char> seg_graded;           // the (channel) segment holds a native channel with a >= 0 or a trainable channel
+  std::vector<char> seg_fit;              // ... a trainable channel: mixed_wide_adjoint_channels_fit
+  std::vector<qiddm::WideParam> fit_params;  // the trainable channels, grouped by their rows, program order within a group
+  std::vector<int32_t> fit_group_begin;      // n_fit_groups + 1; empty: the program has none
   std::vector<int32_t> slot;              // per sorted live op, -1: no gradient
   std::vector<qiddm::WideParam> params;   // grouped by the parameter they feed, program order within a group
   std::vector<int32_t> group_begin;       // n_groups + 1
@@ -676,8 +705,11 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
   // A segment with a graded channel needs the state in front of it.  A trailing segment reads the last replayed set, so
   // the replay goes on up to the last trailing segment that holds one (programs without a graded channel: as before).
   bp->seg_graded.assign(n_seg, 0);
-  for (int i = 0; i < bp->n_live; ++i)
-    if (is_graded(live[i])) bp->seg_graded[bp->plan.op_segment[i]] = 1;
+  bp->seg_fit.assign(n_seg, 0);
+  for (int i = 0; i < bp->n_live; ++i) {
+    if (needs_front(live[i])) bp->seg_graded[bp->plan.op_segment[i]] = 1;
+    if (is_fit(live[i].kind)) bp->seg_fit[bp->plan.op_segment[i]] = 1;
+  }
   for (int s = n_seg - 1; s > bp->replay_end; --s)
     if (bp->seg_graded[s]) {
       bp->replay_end = s;
@@ -690,12 +722,17 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
   bp->n_slots = 0;
   bp->gate2 = false;
   std::vector<std::pair<int64_t, int32_t>> keyed;  // (parameter, sorted position)
+  std::vector<std::pair<int64_t, int32_t>> fit_keyed;  // the same for the trainable channels: a finalize of their own
   for (int i = 0; i < bp->n_live; ++i) {
     const qiddm_mixed_op_t& op = live[bp->plan.order[i]];
-    const int gate = gate_rows(op.kind);  // 1: GATE (8 tile partials), 4: GATE2 (32)
+    const int gate = gate_rows(op.kind);  // 1: GATE (8 tile partials), 4: GATE2, CHANNEL_FIT (32), 64: CHANNEL2_FIT (512)
     if (!gate && !((op.kind == qiddm::kMixPhase || op.kind == qiddm::kMixRY) && op.a >= 0) && !is_graded(op)) continue;
     bp->slot[i] = bp->n_slots;
     bp->n_slots += gate ? 8 * gate : 1;
+    if (is_fit(op.kind)) {
+      fit_keyed.push_back({((int64_t)gate << 32) | (uint32_t)op.a, i});
+      continue;
+    }
     bp->gate2 = bp->gate2 || is_gate2(op.kind);
     keyed.push_back({((int64_t)gate << 32) | (uint32_t)op.a, i});
   }
@@ -714,14 +751,30 @@ int plan_mixed_wide_backward(int32_t n, const qiddm_mixed_op_t* program, int32_t
     bp->params.push_back(p);
   }
   bp->group_begin.push_back((int32_t)keyed.size());
+  bp->fit_params.clear();
+  bp->fit_group_begin.clear();
+  if (fit_keyed.empty()) return QIDDM_OK;
+  std::stable_sort(fit_keyed.begin(), fit_keyed.end(),
+                   [](const std::pair<int64_t, int32_t>& x, const std::pair<int64_t, int32_t>& y) { return x.first < y.first; });
+  for (size_t k = 0; k < fit_keyed.size(); ++k) {
+    const qiddm_mixed_op_t& op = live[bp->plan.order[fit_keyed[k].second]];
+    if (k == 0 || fit_keyed[k].first != fit_keyed[k - 1].first) bp->fit_group_begin.push_back((int32_t)k);
+    qiddm::WideParam p{};
+    p.kind = base_kind(op.kind);
+    p.a = op.a;
+    p.slot = bp->slot[fit_keyed[k].second];
+    bp->fit_params.push_back(p);
+  }
+  bp->fit_group_begin.push_back((int32_t)fit_keyed.size());
   return QIDDM_OK;
 }
 
-// Workspace: [sorted live program, measurement table | slot per op | params | group_begin] then, per resident sample, |v|^2 and
+// Workspace: [sorted live program, measurement table | slot per op | params | group_begin | with trainable channels only:
+// their params | their group_begin] then, per resident sample, |v|^2 and
 // Re(Lambda_0) v (AMP_EMBED), the tile partials, and 2 + n_snaps slabs.
 struct WideBwdGeometry {
   int64_t slab_bytes, aux_bytes, part_bytes, per_sample, resident;
-  int64_t off_slot, off_params, off_groups, head, total;
+  int64_t off_slot, off_params, off_groups, off_fit_params, off_fit_groups, head, total;
 };
 
 WideBwdGeometry wide_backward_geometry(int32_t n, int32_t dtype, int64_t batch, const WideBwdPlan& bp) {
@@ -736,7 +789,9 @@ WideBwdGeometry wide_backward_geometry(int32_t n, int32_t dtype, int64_t batch, 
   g.off_slot = program_bytes(bp.n_live + bp.n_obs);
   g.off_params = g.off_slot + round256((int64_t)bp.n_live * 4);
   g.off_groups = g.off_params + round256((int64_t)bp.params.size() * (int64_t)sizeof(qiddm::WideParam));
-  g.head = g.off_groups + round256((int64_t)bp.group_begin.size() * 4);
+  g.off_fit_params = g.off_groups + round256((int64_t)bp.group_begin.size() * 4);
+  g.off_fit_groups = g.off_fit_params + round256((int64_t)bp.fit_params.size() * (int64_t)sizeof(qiddm::WideParam));
+  g.head = g.off_fit_groups + round256((int64_t)bp.fit_group_begin.size() * 4);  // both empty: the head as it was
   g.total = g.head + g.resident * g.per_sample;
   return g;
 }
@@ -798,6 +853,12 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
               c.angle_rows, c.gates, grad_out, slabs + (size_t)cur * set_stride, lam, partials, m, bp.plan.segments[s], bs, s0);
         };
         rc = qiddm::mixed_has_gate2(bp.plan.seg_level[s]) ? reverse(std::true_type{}) : reverse(std::false_type{});
+      } else if (bp.seg_fit[s]) {  // a trainable channel: the state in front of the segment as below
+        const C* front = slabs + (size_t)(s < bp.replay_end ? cur - 1 : cur) * set_stride;
+        rc = launch<qiddm::mixed_wide_adjoint_channels_fit<T>>(
+            2 * tile_bytes, dim3(tiles, chunk), block, 2 * tile_bytes, st, "mixed_wide_adjoint_channels_fit", prog, slot,
+            c.angle_rows, c.gates, grad_out, front, lam, partials, m, bp.plan.segments[s], bs, s0);
+        if (s < bp.replay_end) --cur;
       } else if (bp.seg_graded[s]) {
         // the state in front of the segment: the set below the one it wrote, or (not replayed) the last replayed set
         const C* front = slabs + (size_t)(s < bp.replay_end ? cur - 1 : cur) * set_stride;
@@ -826,6 +887,12 @@ int launch_mixed_wide_backward(const WideBwdPlan& bp, const WideBwdGeometry& g, 
       hipLaunchKernelGGL(bp.gate2 ? qiddm::mixed_wide_grad_finalize<true> : qiddm::mixed_wide_grad_finalize<false>,
                          dim3((n_groups + 3) / 4, chunk), dim3(256), 0, st, params, group_begin, n_groups, c.gates, partials,
                          grad_rows, grad_gates, bp.n_slots, c.n_gates, tiles, m.batch, s0);
+    if (!bp.fit_params.empty())  // behind the finalize above: it adds to the rows
+      hipLaunchKernelGGL(qiddm::mixed_wide_fit_finalize,
+                         dim3(((unsigned)bp.fit_group_begin.size() - 1) * qiddm::kWideFitChunks, chunk), dim3(256), 0, st,
+                         reinterpret_cast<const qiddm::WideParam*>(ws + g.off_fit_params),
+                         reinterpret_cast<const int32_t*>(ws + g.off_fit_groups), partials, grad_gates, bp.n_slots, c.n_gates,
+                         tiles, s0);
     if (rc = launched("mixed_wide backward"); rc != QIDDM_OK) return rc;
   }
   return QIDDM_OK;
@@ -856,14 +923,16 @@ int qiddm_mixed_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t*
   if ((rc = check_workspace(workspace, workspace_bytes, g.total, "qiddm_mixed_workspace_bytes")) != QIDDM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  std::vector<qiddm_mixed_op_t> constant(program, program + n_ops);  // the forward knows the constant kinds only
+  for (qiddm_mixed_op_t& op : constant) op = constant_op(op);
+  if ((rc = upload(ws, constant.data(), (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
   const qiddm::MixedShots sh = shots_of(program, n_ops);
   // the ops the kernel walks: a sampled read-out is none of them, nor is the measurement table
   const int32_t n_body = c.n_body() - (sh.shots ? 1 : 0);
   const qiddm::MixedScalars m = make_scalars(c, n_body, n_features, out_ld, g.in_lds);
   const size_t smem = g.in_lds ? (size_t)g.slab_bytes : 0;
   const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
-  const int level = program_level(program, n_body);
+  const int level = program_level(program, n_body) & ~qiddm::kLevelFit;
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     return for_op_level(level, [&](auto lv) {
@@ -935,7 +1004,12 @@ int qiddm_mixed_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t
   const int level = program_level(program, n_ops);
   return for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    return for_op_level(level, [&](auto lv) {
+    // a program with a trainable channel: the instantiation that carries every case and the rows' gradient beside them
+    const auto for_backward_level = [&](auto&& f) {
+      constexpr int kAll = qiddm::kLevelChannel2 | qiddm::kLevelGate2 | qiddm::kLevelFit;
+      return qiddm::mixed_has_fit(level) ? f(std::integral_constant<int, kAll>{}) : for_op_level(level, f);
+    };
+    return for_backward_level([&](auto lv) {
       // measure QIDDM_MEAS_OBS: the instantiation that seeds from the measurement table; QIDDM_MEAS_RHO: from the
       // density-matrix read-out's cotangent
       const auto run = [&](auto obs, auto rho) {
@@ -992,7 +1066,7 @@ int qiddm_mixed_wide_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
   const qiddm::MixedShots sh = shots_of(program, n_ops);
   const int32_t n_body = (int32_t)plan.order.size();  // n_ops, or n_ops - 1 in front of a sampled read-out
   std::vector<qiddm_mixed_op_t> sorted(n_body + c.n_obs);  // the measurement table stays behind the sorted ops
-  for (int i = 0; i < n_body; ++i) sorted[i] = program[plan.order[i]];
+  for (int i = 0; i < n_body; ++i) sorted[i] = constant_op(program[plan.order[i]]);
   for (int i = 0; i < c.n_obs; ++i) sorted[n_body + i] = program[c.n_body() + i];
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
@@ -1047,11 +1121,15 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
   // the head in one upload: sorted live program, slots, params, groups
   std::vector<unsigned char> head((size_t)g.head, 0);
   qiddm_mixed_op_t* sorted = reinterpret_cast<qiddm_mixed_op_t*>(head.data());
-  for (int i = 0; i < bp.n_live; ++i) sorted[i] = program[bp.live_begin + bp.plan.order[i]];
+  for (int i = 0; i < bp.n_live; ++i) sorted[i] = constant_op(program[bp.live_begin + bp.plan.order[i]]);  // trainable channels: marked by their slot
   for (int i = 0; i < bp.n_obs; ++i) sorted[bp.n_live + i] = program[c.n_body() + i];  // the measurement table
   memcpy(head.data() + g.off_slot, bp.slot.data(), bp.slot.size() * 4);
   if (!bp.params.empty()) memcpy(head.data() + g.off_params, bp.params.data(), bp.params.size() * sizeof(qiddm::WideParam));
   memcpy(head.data() + g.off_groups, bp.group_begin.data(), bp.group_begin.size() * 4);
+  if (!bp.fit_params.empty()) {
+    memcpy(head.data() + g.off_fit_params, bp.fit_params.data(), bp.fit_params.size() * sizeof(qiddm::WideParam));
+    memcpy(head.data() + g.off_fit_groups, bp.fit_group_begin.data(), bp.fit_group_begin.size() * 4);
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   if ((rc = upload(ws, head.data(), head.size(), st)) != QIDDM_OK) return rc;

@@ -64,7 +64,12 @@ enum MixedKind : int32_t {
                     // channel: un-computed in the reverse sweeps, and its rows get a gradient)
   kMixRho = 28,     // last op only, not an op on rho: the read-out is the reduced density matrix of the wires in the keep-mask
                     // `wire` (wire w at bit n-1-w); see mixed_rho_read_out
-  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17..19, 21..23, 25..27, 29..31: no kind)
+  kMixChannel2 = 32,  // general two-wire channel on (wire, wire2): gates[a .. a+63] hold the 16 x 16 S (17, 19, 21..23, 25..27, 29..31: no kind)
+  // 16 k + 2: the k-wire channel whose rows get a gradient.  The forwards and the tile-fused engine never see these two:
+  // the host uploads them as kMixChannel / kMixChannel2 (and marks them by their slot); mixed_backward_kernel's kLevelFit
+  // instantiations read them and take them for the constant kinds wherever rho and Lambda are concerned.
+  kMixChannelFit = 18,
+  kMixChannel2Fit = 34,
 };
 
 struct MixedOp {
@@ -80,15 +85,17 @@ enum MixedLevel : int {
   kLevelChannel = 1,  // + kMixChannel
   kLevelChannel2 = 2, // + kMixChannel2 (where its S is staged: 256 V2<T> of static LDS)
   kLevelGate2 = 4,    // flag: + kMixGate2
+  kLevelFit = 8,      // flag: + the gradient of the general channels' rows (kMixChannelFit, kMixChannel2Fit): reverse sweeps only
 };
 __host__ __device__ constexpr int mixed_level_of(int kind) {
   return kind == kMixGate2 ? kLevelGate2 : kind == kMixChannel2 ? kLevelChannel2 : kind == kMixChannel ? kLevelChannel : kLevelLean;
 }
 __host__ __device__ constexpr int mixed_channels_of(int level) { return level & 3; }  // the channel level without the flag
 __host__ __device__ constexpr bool mixed_has_gate2(int level) { return (level & kLevelGate2) != 0; }
+__host__ __device__ constexpr bool mixed_has_fit(int level) { return (level & kLevelFit) != 0; }
 // the lowest level that holds the ops of both
 __host__ __device__ constexpr int mixed_level_join(int a, int b) {
-  return (mixed_channels_of(a) > mixed_channels_of(b) ? mixed_channels_of(a) : mixed_channels_of(b)) | ((a | b) & kLevelGate2);
+  return (mixed_channels_of(a) > mixed_channels_of(b) ? mixed_channels_of(a) : mixed_channels_of(b)) | ((a | b) & (kLevelGate2 | kLevelFit));
 }
 
 struct MixedScalars {
@@ -542,6 +549,47 @@ __device__ __forceinline__ void mixed_gate2_grad_accumulate(const double* s, con
       go[(a * 4 + bb) * 2] += 2.0 * re;
       go[(a * 4 + bb) * 2 + 1] += -2.0 * im;
     }
+}
+
+// ---- dL/dS of a general channel whose rows get a gradient (kMixChannelFit, kMixChannel2Fit; the reverse sweeps) ----------
+// With Lambda' the adjoint behind the channel and M the block of rho in front of it, dL = Re sum conj(Lambda') d rho' and
+// vec(M') = S vec(M) give W[r][c] = sum over blocks of conj(vec(Lambda')[r]) vec(M)[c], dL/dRe S[r][c] = Re W[r][c] and
+// dL/dIm S[r][c] = -Im W[r][c].  The products are taken in double whatever T is.
+// One wire: acc += (re, im) of the 16 W[r][c] of one block, at acc[2 (4 r + c)]
+template <typename T>
+__device__ __forceinline__ void mixed_super_grad_accumulate(double (&acc)[32], const V2<T> (&l)[4], const V2<T> (&r)[4]) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      acc[2 * (4 * a + c)] += (double)l[a].x * (double)r[c].x + (double)l[a].y * (double)r[c].y;
+      acc[2 * (4 * a + c) + 1] += (double)l[a].x * (double)r[c].y - (double)l[a].y * (double)r[c].x;
+    }
+}
+// Two wires: 256 entries do not fit a thread's registers as sums, so thread t = 16 r + c owns W[r][c] and walks all
+// `n_blocks` blocks in index order -- no reduction across threads, the order is fixed by construction.  `lam` is read
+// before any thread applies S^H to it: the caller puts a barrier behind this.
+template <typename T>
+__device__ __forceinline__ void mixed_super2_grad(const V2<T>* __restrict__ lam, const V2<T>* __restrict__ rho,
+                                                  uint32_t n_blocks, const MixedBlock2& b, double& re, double& im) {
+  const uint32_t er = b.elem((int)(threadIdx.x >> 4)), ec = b.elem((int)(threadIdx.x & 15u));
+  re = 0.0;
+  im = 0.0;
+#pragma unroll 16
+  for (uint32_t t = 0; t < n_blocks; ++t) {
+    const uint32_t base = mixed_block2_base(t, b);
+    const V2<T> l = lam[base | er], r = rho[base | ec];
+    re += (double)l.x * (double)r.x + (double)l.y * (double)r.y;
+    im += (double)l.x * (double)r.y - (double)l.y * (double)r.x;
+  }
+}
+// what the constant kinds do to rho and Lambda is what the trainable ones do: FIT instantiations take 18 for 16, 34 for 32
+template <bool FIT>
+__device__ __forceinline__ MixedOp mixed_constant_kind(MixedOp op) {
+  if constexpr (FIT) {
+    if (op.kind == kMixChannelFit || op.kind == kMixChannel2Fit) op.kind -= 2;
+  }
+  return op;
 }
 
 // acc += B_rho B_Lambda^dagger of one block: N_ab = sum_c rho_ac conj(Lambda_bc), (re, im) of N00, N01, N10, N11
@@ -1003,7 +1051,9 @@ __global__ __launch_bounds__(256) void mixed_rho_kernel(const MixedOp* __restric
 //     CZ / CNOT: applied to both (involutions)
 //     channel E: Lambda <- E^dagger(Lambda) (the general channel: S^H on vec of each block), rho <- snapshot (a channel is not inverted: Depolarizing(0.9) has
 //         condition number 5 per wire).  A native channel with a >= 0 (strength from a row) first reduces
-//         dL/dstrength = <Lambda, E'(snapshot)> over the wire's blocks, like RY its Im Tr(G N)
+//         dL/dstrength = <Lambda, E'(snapshot)> over the wire's blocks, like RY its Im Tr(G N).  A general channel whose
+//         rows get a gradient (kMixChannelFit, kMixChannel2Fit; the kLevelFit instantiations) first reduces
+//         W[r][c] = sum over blocks of conj(vec(Lambda)[r]) vec(snapshot)[c]: dL/dRe S = Re W, dL/dIm S = -Im W
 //     AMP_EMBED: rho_0 = v v^T / |v|^2, dL/dv = 2 (Re(Lambda) v - (v^T Re(Lambda) v / |v|^2) v) / |v|^2
 // Gradients go to per-sample double outputs (no atomics): every reduction runs in a fixed order, so reruns are
 // bit-identical.  Thread 0 adds each parameter's reduced value after the op's barrier.
@@ -1045,6 +1095,8 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
   __shared__ double s_red[256];
   __shared__ double s_v[256];
   constexpr bool kGate2 = mixed_has_gate2(LEVEL);
+  constexpr bool kFit = mixed_has_fit(LEVEL);  // the gradient of kMixChannelFit / kMixChannel2Fit rows: instantiations of their own
+  static_assert(!kFit || (kGate2 && mixed_channels_of(LEVEL) >= kLevelChannel2), "kLevelFit rides on the full level");
   __shared__ double s_part[2][4][kGate2 ? 32 : 8];  // the four waves' partials of an op's sums, double-buffered
   const int n = m.n, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const uint32_t D = 1u << n, DD = 1u << (2 * n);
@@ -1065,7 +1117,7 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
     // ---- replay -------------------------------------------------------------------------------------------------
     int si = 0;
     for (int oi = 0; oi < m.n_ops; ++oi) {
-      const MixedOp op = prog[oi];
+      const MixedOp op = mixed_constant_kind<kFit>(prog[oi]);
       C* snap = mixed_needs_snapshot(op.kind, oi) ? snaps + (size_t)(si++) * DD : nullptr;
       mixed_apply_op<T, LEVEL>(op, rho, snap, angle_rows, feats, gates, s_red, m, sample);
       __syncthreads();
@@ -1088,12 +1140,14 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
 
     // ---- reverse sweep --------------------------------------------------------------------------------------------
     for (int oi = m.n_ops - 1; oi >= 0; --oi) {
-      const MixedOp op = prog[oi];
+      const MixedOp op = mixed_constant_kind<kFit>(prog[oi]);
+      bool fit = false;  // the op's rows get a gradient
+      if constexpr (kFit) fit = prog[oi].kind != op.kind;
       const int q = n - 1 - op.wire;
       // a native channel that reads its strength from a row feeds that row like an angle op
       const bool graded = (op.kind == kMixPhaseDamp || op.kind == kMixAmpDamp || op.kind == kMixDepol) && op.a >= 0;
       const bool param = op.kind == kMixPhase || op.kind == kMixRY || op.kind == kMixGate || graded ||
-                         (kGate2 && op.kind == kMixGate2);
+                         (kGate2 && op.kind == kMixGate2) || (kFit && fit && op.kind == kMixChannel);
       switch (op.kind) {
         case kMixPhase:
         case kMixRY:
@@ -1203,12 +1257,22 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
           }
           break;
         }
-        case kMixChannel2: {  // S^H on vec of each 4 x 4 block of Lambda, rho from the snapshot; its 64 rows of grad_gates stay zero
+        case kMixChannel2: {  // S^H on vec of each 4 x 4 block of Lambda, rho from the snapshot; its 64 rows of grad_gates stay zero (kMixChannel2Fit: dL/dS)
           if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel2) {
             const int q2 = n - 1 - op.wire2;
             const MixedBlock2 bl = mixed_block2(q, q2, q + n, q2 + n);
             const auto su = mixed_super2<T>(op, gates);
             const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
+            if constexpr (kFit) {
+              if (fit) {  // uniform over the workgroup.  Thread 16 r + c adds its own entry: no other thread touches it
+                double re, im;
+                mixed_super2_grad<T>(lam, sp, DD / 16, bl, re, im);
+                double* __restrict__ go = grad_gates + ((size_t)sample * b.n_gates + op.a) * 8 + 2 * tid;
+                go[0] += re;
+                go[1] -= im;
+                __syncthreads();
+              }
+            }
             for (uint32_t t = tid; t < DD / 16; t += 256) mixed_block_super2<T, true>(su, lam, nullptr, mixed_block2_base(t, bl), bl);
             for (uint32_t k = tid; k < DD; k += 256) rho[k] = sp[k];
           }
@@ -1231,10 +1295,29 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
           }
           break;
         }
-        case kMixChannel: {  // its four rows of grad_gates stay zero: channel operands get no gradient
+        case kMixChannel: {  // its four rows of grad_gates stay zero: channel operands get no gradient (kMixChannelFit: dL/dS)
           if constexpr (mixed_channels_of(LEVEL) >= kLevelChannel) {
             const MixedSuper<T> su = mixed_super<T>(op, gates);
             const C* __restrict__ sp = snaps + (size_t)(--si) * DD;
+            if constexpr (kFit) {
+              if (fit) {  // W of the thread's blocks (the blocks it owns below), then across the workgroup like GATE2's N
+                double acc[32];
+#pragma unroll
+                for (int k = 0; k < 32; ++k) acc[k] = 0.0;
+                for (uint32_t t = tid; t < DD / 4; t += 256) {
+                  const uint32_t base = insert_two_bits(t, q, q + n);
+                  const uint32_t cj = 1u << q, ci = 1u << (q + n);
+                  const C l[4] = {lam[base], lam[base | cj], lam[base | ci], lam[base | ci | cj]};
+                  const C r[4] = {sp[base], sp[base | cj], sp[base | ci], sp[base | ci | cj]};
+                  mixed_super_grad_accumulate<T>(acc, l, r);
+                }
+#pragma unroll
+                for (int k = 0; k < 32; ++k) {
+                  const double s = mixed_wave_sum(acc[k]);
+                  if (lane == 0) s_part[buf][wave][k] = s;
+                }
+              }
+            }
             for (uint32_t t = tid; t < DD / 4; t += 256) {
               const uint32_t base = insert_two_bits(t, q, q + n);
               const uint32_t cj = 1u << q, ci = 1u << (q + n);
@@ -1281,7 +1364,15 @@ __global__ __launch_bounds__(256) void mixed_backward_kernel(
       __syncthreads();
       if (param) {
         if (tid == 0) {
-          if (kGate2 && op.kind == kMixGate2) {
+          if (kFit && op.kind == kMixChannel) {
+            if constexpr (kFit) {  // dL/dRe S = Re W, dL/dIm S = -Im W, in the layout of the rows
+              double* __restrict__ go = grad_gates + ((size_t)sample * b.n_gates + op.a) * 8;
+              for (int k = 0; k < 32; ++k) {
+                const double s = s_part[buf][0][k] + s_part[buf][1][k] + s_part[buf][2][k] + s_part[buf][3][k];
+                go[k] += (k & 1) ? -s : s;
+              }
+            }
+          } else if (kGate2 && op.kind == kMixGate2) {
             if constexpr (kGate2) {
               double s[32];
               for (int k = 0; k < 32; ++k) s[k] = s_part[buf][0][k] + s_part[buf][1][k] + s_part[buf][2][k] + s_part[buf][3][k];

@@ -19,6 +19,9 @@
 //               and writes the tile partial of dL/dstrength = <Lambda, E'(rho)> to the channel's slot.  A trailing
 //               segment reads the last replayed set as its snapshot, so the host replays up to the last trailing
 //               segment that holds such a channel (only programs with one are planned differently).
+//               A segment with a general channel whose rows get a gradient (QIDDM_MIX_CHANNEL_FIT / _CHANNEL2_FIT) runs
+//               mixed_wide_adjoint_channels_fit (the end of this file): the same with dL/dS of the tile in the op's 32
+//               or 512 slots, summed over tiles by mixed_wide_fit_finalize.
 //             The first reverse launch generates Lambda_N from grad_out instead of reading it (a measurement table and
 //             the reduced density matrix's read-out: a seed launch of their own writes Lambda's slab first).
 //   AMP_EMBED dL/dv from Re(Lambda_0) v: a matrix-vector pass over Lambda's slab, then one workgroup per sample.
@@ -461,6 +464,144 @@ __global__ __launch_bounds__(256) void mixed_wide_grad_finalize(const WideParam*
     for (int k = 0; k < 8; ++k) dst[k] = go[k];
   } else {
     grad_rows[(size_t)head.a * batch + sample] = go[0];
+  }
+}
+
+// ---- general channels whose rows get a gradient (QIDDM_MIX_CHANNEL_FIT / _CHANNEL2_FIT) ---------------------------------
+// The host uploads them as kMixChannel / kMixChannel2, so the replay and every kernel above run them as the constant
+// kinds; what marks them is slot[oi] >= 0 on a general channel.  Segments that hold one run the kernel below, programs
+// without one launch nothing of this section.
+//
+// mixed_wide_adjoint_channels_graded with the general channels' dL/dS beside the native channels' dL/dstrength (it carries
+// every channel case: one instantiation per precision).  In front of each op with a slot the rho tile is rebuilt as
+// there; then, with W[r][c] = sum over the tile's blocks of conj(vec(Lambda)[r]) vec(rho)[c] (mixed_super_grad_accumulate,
+// mixed_super2_grad of qsim_mixed.h), the tile partials Re W, -Im W go to the op's 32 (one wire) or 512 (two wires) slots
+// in the layout of the rows.  One wire: a thread's blocks, the wave, the four waves.  Two wires: thread 16 r + c owns
+// W[r][c] and walks the tile's 256 blocks in order.
+template <typename T>
+__global__ __launch_bounds__(256) void mixed_wide_adjoint_channels_fit(
+    const MixedOp* __restrict__ prog, const int32_t* __restrict__ slot, const double* __restrict__ angle_rows,
+    const double* __restrict__ gates, const double* __restrict__ grad_out, const V2<T>* __restrict__ rho_slabs,
+    V2<T>* __restrict__ lam_slabs, double* __restrict__ partials, const MixedScalars m, const WideSegment sg,
+    const WideBwdScalars b, int64_t sample0) {
+  using C = V2<T>;
+  constexpr int LEVEL = kLevelChannel2;
+  extern __shared__ __attribute__((aligned(32))) unsigned char smem_raw[];
+  __shared__ uint32_t s_lo[64], s_hi[64];
+  __shared__ double s_part[2][4][32];
+  C* lt = reinterpret_cast<C*>(smem_raw);
+  C* rt = lt + kWideTile;
+  const int n = m.n, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t resident = blockIdx.y, sample = sample0 + resident;
+  const C* __restrict__ rho = rho_slabs + ((size_t)resident << (2 * n));
+  C* __restrict__ lam = lam_slabs + ((size_t)resident << (2 * n));
+  uint32_t kown[kWidePairs];
+  wide_owned_indices(sg, s_lo, s_hi, kown);
+  wide_load_lambda<T>(lt, lam, kown, grad_out + sample * b.gout_ld, m, b.seed != 0);
+  __syncthreads();
+
+  double* __restrict__ part = partials + (size_t)resident * b.n_slots * gridDim.x + blockIdx.x;
+  int buf = 0;
+  for (int oi = sg.op_end - 1; oi >= sg.op_begin; --oi) {
+    const MixedOp op = prog[oi];
+    const int sl = slot[oi];
+    if (sl >= 0) {  // uniform over the workgroup
+      wide_load_tile<T>(rt, rho, kown);
+      for (int oj = sg.op_begin; oj < oi; ++oj) {
+        __syncthreads();
+        wide_channel_op<T, LEVEL, false>(prog[oj], rt, kown, angle_rows, gates, m, sg, sample);
+      }
+      __syncthreads();
+      const int q = n - 1 - op.wire;
+      if (op.kind == kMixChannel2) {
+        double re, im;
+        mixed_super2_grad<T>(lt, rt, kWideTile / 16, wide_block2(op, m, sg), re, im);
+        part[(size_t)(sl + 2 * tid) * gridDim.x] = re;
+        part[(size_t)(sl + 2 * tid + 1) * gridDim.x] = -im;
+        __syncthreads();  // every thread has read all of the Lambda tile
+      } else if (op.kind == kMixChannel) {
+        const MixedBlock1 bl = wide_block(sg, q, n);
+        const uint32_t cj = bl.cj(), ci = bl.ci();
+        double acc[32];
+#pragma unroll
+        for (int k = 0; k < 32; ++k) acc[k] = 0.0;
+#pragma unroll
+        for (int i = 0; i < kWideBlocks; ++i) {
+          const uint32_t l = bl.base(tid + 256u * i);
+          const C lv[4] = {lt[l], lt[l | cj], lt[l | ci], lt[l | ci | cj]};
+          const C rv[4] = {rt[l], rt[l | cj], rt[l | ci], rt[l | ci | cj]};
+          mixed_super_grad_accumulate<T>(acc, lv, rv);
+        }
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+          const double s = mixed_wave_sum(acc[k]);
+          if (lane == 0) s_part[buf][wave][k] = s;
+        }
+        __syncthreads();
+        if (tid < 32) {
+          const double s = s_part[buf][0][tid] + s_part[buf][1][tid] + s_part[buf][2][tid] + s_part[buf][3][tid];
+          part[(size_t)(sl + tid) * gridDim.x] = (tid & 1) ? -s : s;
+        }
+        buf ^= 1;
+      } else {  // a native channel with a >= 0: as in mixed_wide_adjoint_channels_graded
+        const double strength = mixed_angle(op, angle_rows, m, sample);
+        double acc_off = 0.0, acc_diag = 0.0;
+        if (op.kind == kMixPhaseDamp) {
+          wide_for_owned(kown, [&](uint32_t l, uint32_t k) {
+            if (((k >> (q + n)) ^ (k >> q)) & 1u) acc_off += mixed_re_dot<T>(lt[l], rt[l]);
+          });
+        } else {
+          const MixedBlock1 bl = wide_block(sg, q, n);
+          const uint32_t cj = bl.cj(), ci = bl.ci();
+#pragma unroll
+          for (int i = 0; i < kWideBlocks; ++i) {
+            const uint32_t l = bl.base(tid + 256u * i);
+            acc_off += mixed_strength_grad_off<T>(rt[l | cj], rt[l | ci], lt[l | cj], lt[l | ci]);
+            acc_diag += mixed_strength_grad_diag<T>(op.kind, rt[l], rt[l | ci | cj], lt[l], lt[l | ci | cj]);
+          }
+        }
+        const double s = mixed_wave_sum(mixed_channel_doff(op.kind, strength) * acc_off + acc_diag);
+        if (lane == 0) s_part[buf][wave][0] = s;
+        __syncthreads();
+        if (tid == 0) part[(size_t)sl * gridDim.x] = s_part[buf][0][0] + s_part[buf][1][0] + s_part[buf][2][0] + s_part[buf][3][0];
+        buf ^= 1;
+      }
+    }
+    wide_channel_op<T, LEVEL, true>(op, lt, kown, angle_rows, gates, m, sg, sample);
+    __syncthreads();
+  }
+  wide_store_tile<T>(lam, lt, kown, 0);
+}
+
+// kWideFitChunks workgroups per (group of trainable channels that name the same rows, sample), 32 values each (a one-wire
+// group uses the first): a wave per value sums the tile partials of every op of the group, lane-strided and then across
+// the wave, in program order, and ADDS the result to the rows of grad_gates (the host has zeroed them;
+// mixed_wide_grad_finalize, launched in front, may have written a GATE2 of the same four rows).  params[..].kind is
+// kMixChannel (32 values) or kMixChannel2 (512).
+constexpr int kWideFitChunks = 16;
+__global__ __launch_bounds__(256) void mixed_wide_fit_finalize(const WideParam* __restrict__ params,
+                                                               const int32_t* __restrict__ group_begin,
+                                                               const double* __restrict__ partials,
+                                                               double* __restrict__ grad_gates, int32_t n_slots,
+                                                               int32_t n_gates, uint32_t tiles, int64_t sample0) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t resident = blockIdx.y, sample = sample0 + resident;
+  const double* __restrict__ part = partials + (size_t)resident * n_slots * tiles;
+  const int group = blockIdx.x / kWideFitChunks, first = 32 * (blockIdx.x % kWideFitChunks);
+  const int begin = group_begin[group], end = group_begin[group + 1];
+  const WideParam head = params[begin];
+  const int n_vals = head.kind == kMixChannel2 ? 512 : 32;
+  if (first >= n_vals) return;
+  double* __restrict__ dst = grad_gates + ((size_t)sample * n_gates + head.a) * 8;
+  for (int c = first + wave; c < first + 32; c += 4) {
+    double go = 0.0;
+    for (int pi = begin; pi < end; ++pi) {
+      const double* __restrict__ src = part + (size_t)(params[pi].slot + c) * tiles;
+      double v = 0.0;
+      for (uint32_t t = lane; t < tiles; t += 64) v += src[t];
+      go += mixed_wave_sum(v);
+    }
+    if (lane == 0) dst[c] += go;
   }
 }
 

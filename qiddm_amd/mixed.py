@@ -21,8 +21,8 @@ batch, a 1-D tensor one per sample (the study's ten intensities over the same in
 that requires grad gets its gradient from the same reverse sweeps -- dL/dstrength = <Lambda, E'(rho)> where the
 adjoint and the snapshot meet at the channel -- so a noise model can be fitted to measured read-outs.  Tensor strengths
 are checked once per ``execute`` on the host (outside [0, 1] or NaN: ``ValueError``); at gamma = 1 the derivative of the
-two damping channels is not finite, as in PennyLane.  The general ops below get no gradient for their strengths or Kraus
-entries and take no per-sample strengths.
+two damping channels is not finite, as in PennyLane.  The general ops below take no per-sample strengths; their
+parameters and Kraus entries train as the last paragraph but one of this section says.
 
 Every other one-wire channel of
 ``qiddm_amd.qml`` (BitFlip, PhaseFlip, PauliError, GeneralizedAmplitudeDamping, ResetError, ThermalRelaxationError,
@@ -34,6 +34,22 @@ two-letter word: entangler error, correlated dephasing, a measured two-qubit pro
 16 x 16 superoperator of the same formula (operator index 2 b_a + b_b, the first listed wire most significant), worked
 out by the same helpers with ``wires=2``, travels as 64 rows of ``gates``, and the op's fourth field names the second
 wire.  Rows that one circuit records several times (one error model behind every entangler) are uploaded once.
+
+These general channels TRAIN as well.  With grad mode on, a named channel one of whose parameters is a 0-d tensor on the
+GPU that requires grad -- ``BitFlip(p)``, ``PhaseFlip``, ``PauliError`` on one or two wires, ``GeneralizedAmplitudeDamping``,
+``ResetError``, ``ThermalRelaxationError(pe, t1, t2, tg)`` -- and a ``QubitChannel`` whose ``K_list`` is, or holds, a complex
+GPU tensor that requires grad take another path: the superoperator rows are built in torch on the device
+(``channel_rows_torch``, ``superoperator_torch``: the numpy definitions' values, inside the autograd graph), join ``gates``
+as the rows of a trainable unitary do, and the op is ``QIDDM_MIX_CHANNEL_FIT`` / ``QIDDM_MIX_CHANNEL2_FIT`` (18, 34): the
+forward of 16 / 32, bit for bit, and in the reverse sweeps dL/dS per sample -- W[r][c] = sum over blocks of conj(Lambda')[r]
+M[c] where the adjoint behind the channel meets the snapshot in front of it, dL/dRe S = Re W, dL/dIm S = -Im W -- which
+autograd carries on to p, t1, t2, the Kraus entries.  The gradient is with respect to unconstrained entries: keeping a
+``QubitChannel`` trace preserving is the caller's parametrisation (the values given are still checked to 1e-10).  Ranges are
+conditions on the device, read back with the native channels' strengths in one synchronisation per ``execute`` and
+reported in the words of the host checks (``p must be in the interval [0, 1] (got ...)``, ``t1 must be positive``).  Everything
+else is lowered as before, to the same kinds, rows and bits: floats, host arrays, tensors that do not require grad or are
+used under ``no_grad``.  Per-sample (1-D) parameters of these channels stay refused, and a CPU tensor that requires grad
+raises the "no CPU path" error.
 
 Gates beyond the reference's circuit family -- ``qml.Hadamard / S / T / SX`` and one-wire ``QubitUnitary`` (a constant
 row of ``QIDDM_MIX_GATE``), ``RX`` and ``Rot`` (``PHASE, RY, PHASE``: angle ops, so per-sample and differentiable), and the
@@ -52,7 +68,11 @@ tile-fused reverse sweep.
 
 The read-out follows PennyLane's ``default.mixed`` as well.  ``qml.device("default.mixed", wires=n, readout_prob=q)``
 appends one ``BitFlip(q)`` per wire, in wire order, behind the tape (``QIDDM_MIX_CHANNEL``; the four rows are uploaded
-once): analytic and differentiable for everything in front of it.  ``shots=N`` appends ``QIDDM_MIX_SHOTS``: the launch
+once): analytic and differentiable for everything in front of it.  ``readout_prob`` may itself be a 0-d GPU tensor that
+requires grad: in grad mode every analytic read-out then gets one trainable flip per wire (``QIDDM_MIX_CHANNEL_FIT``, one set
+of rows) -- ``BitFlip(q)`` in front of probs and <Z>; in front of a table of Pauli words the flip in each letter's own basis
+(``readout_rows_torch``: every letter scaled by 1 - 2q, the value of the (1 - 2q)^weight shortcut that floats keep) -- and
+dL/dq comes back through the rows; with ``shots`` it raises the ``QuantumFunctionError`` of sampled executions.  ``shots=N`` appends ``QIDDM_MIX_SHOTS``: the launch
 that holds rho draws N computational-basis outcomes per sample (Philox4x32-10 keyed by the device's seed, the stream
 offset is the device's count of sampled executions; the rule is in include/qiddm_hip.h) and returns count / N or
 (n+ - n-) / N per wire, float64.  Nothing is copied to the host.  A sampled execution has no reverse sweep: with grad
@@ -242,6 +262,119 @@ def qubit_channel_rows(kraus, wires=1):
     return superoperator(kraus, wires)
 
 
+# ---- the same superoperators in torch: differentiable, on the parameters' device ----------------------------------------
+# A general channel whose parameter requires grad is lowered to QIDDM_MIX_CHANNEL_FIT / _CHANNEL2_FIT: its rows stay in
+# the autograd graph, the reverse sweeps return dL/drows, and autograd carries that on to p, t1, t2, the Kraus entries.
+# The named channels are written as S = sum_k w_k(parameters) A_k (x) conj(A_k) with constant A_k and the weights the
+# numpy definitions above square their roots to (p, 1 - p, ...): the same values, and no sqrt whose derivative is not
+# finite at a parameter of 0.  Nothing here looks at a value: range checks are conditions on the device that `execute`
+# reads in one synchronisation.
+def trainable(values) -> bool:
+    """Whether a channel with these parameters (or Kraus operators) takes the trainable path: grad mode is on and one of
+    them is a tensor that requires grad.  (On the CPU: the lowering then raises the "no CPU path" error.)"""
+    return torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in values)
+
+
+def _rows_torch(s):
+    """`_rows` for a complex128 tensor, inside its graph."""
+    return torch.view_as_real(s.reshape(-1, 4).contiguous()).reshape(-1, 8)
+
+
+def _weighted(weights, matrices, device):
+    """sum_k w_k A_k (x) conj(A_k): real 0-d tensors `weights`, constant numpy `matrices`."""
+    consts = [torch.from_numpy(np.kron(a, a.conj())).to(device) for a in matrices]
+    return sum(w * c for w, c in zip(weights, consts))
+
+
+def _unit(e, device):
+    """A real matrix unit E_rc as the 4 x 4 S whose only entry is 1 at vec index (r, c)."""
+    m = np.zeros((4, 4), dtype=complex)
+    m[e] = 1.0
+    return torch.from_numpy(m).to(device)
+
+
+def channel_rows_torch(name, *params):
+    """``channel_rows`` in torch: -> (rows, ok).  `rows`: the ``(4, 8)`` (two-letter PauliError: ``(64, 8)``) float64
+    superoperator rows on the device of the tensor parameters, differentiable with respect to them; for equal values they
+    are the numpy rows.  `ok`: a 0-d bool tensor there, whether every parameter is in the range ``channel_kraus`` /
+    ``_thermal`` demand (nothing is read back here).  Parameters are floats or 0-d tensors."""
+    if len(params) != {"PauliError": 2, "GeneralizedAmplitudeDamping": 2, "ResetError": 2,
+                       "ThermalRelaxationError": 4}.get(name, 1):
+        raise TypeError(f"{name}: wrong number of parameters ({len(params)})")
+    device = next((p.device for p in params if torch.is_tensor(p)), torch.device("cpu"))
+    word = None
+    if name == "PauliError":
+        word, params = params[0], params[1:]
+        channel_kraus("PauliError", word, 0.0)  # checks the word
+    f64 = dict(dtype=torch.float64, device=device)
+    v = [p.to(**f64) if torch.is_tensor(p) else torch.tensor(float(p), **f64) for p in params]
+    if any(p.dim() != 0 for p in v):
+        raise NotImplementedError(f"{name}: parameters must be floats or 0-d tensors")
+    prob = lambda x: (x >= 0.0) & (x <= 1.0)
+    eye = np.eye(2, dtype=complex)
+    e = lambda r, c: np.array([[float((r, c) == (i, j)) for j in range(2)] for i in range(2)], dtype=complex)
+    if name in ("BitFlip", "PhaseFlip"):
+        p, = v
+        s, ok = _weighted([1.0 - p, p], [eye, _PAULI["X" if name == "BitFlip" else "Z"]], device), prob(p)
+    elif name == "PauliError":
+        p, = v
+        pauli = functools.reduce(np.kron, [_PAULI[c] for c in word])
+        s, ok = _weighted([1.0 - p, p], [np.eye(pauli.shape[0], dtype=complex), pauli], device), prob(p)
+    elif name == "GeneralizedAmplitudeDamping":
+        g, p = v
+        off = torch.sqrt(1.0 - g)  # p sqrt(1-g) + (1-p) sqrt(1-g); not differentiable at gamma = 1, as AmplitudeDamping
+        s = (p + (1.0 - p) * (1.0 - g)) * _unit((0, 0), device) + (p * (1.0 - g) + (1.0 - p)) * _unit((3, 3), device) \
+            + off * (_unit((1, 1), device) + _unit((2, 2), device)) + p * g * _unit((0, 3), device) \
+            + (1.0 - p) * g * _unit((3, 0), device)
+        ok = prob(g) & prob(p)
+    elif name == "ResetError":
+        p0, p1 = v
+        s = _weighted([1.0 - p0 - p1, p0, p0, p1, p1], [eye, e(0, 0), e(0, 1), e(1, 0), e(1, 1)], device)
+        ok = (p0 >= 0.0) & (p1 >= 0.0) & (p0 + p1 <= 1.0)
+    elif name == "ThermalRelaxationError":
+        pe, t1, t2, tg = v
+        e1, e2 = torch.exp(-tg / t1), torch.exp(-tg / t2)
+        pr0, pr1 = (1.0 - pe) * (1.0 - e1), pe * (1.0 - e1)
+        s = (1.0 - pr1) * _unit((0, 0), device) + pr0 * _unit((0, 3), device) + pr1 * _unit((3, 0), device) \
+            + (1.0 - pr0) * _unit((3, 3), device) + e2 * (_unit((1, 1), device) + _unit((2, 2), device))
+        ok = prob(pe) & (t1 > 0.0) & (t2 > 0.0) & (t2 <= 2.0 * t1) & (tg >= 0.0)
+    else:
+        raise ValueError(f"unknown channel {name}")
+    return _rows_torch(s), ok
+
+
+def readout_rows_torch(q):
+    """-> (rows, ok) of a read-out flip with probability `q` (a 0-d tensor) as a Pauli word sees it.  PennyLane flips the
+    measured bit of a wire in the basis its letter is measured in, so every letter X, Y, Z is scaled by 1 - 2q -- the
+    (1 - 2q)^weight that floats put on a word's coefficient.  On rho that is M00' = (1-q) M00 + q M11, M11' likewise, M01'
+    = (1-2q) M01, M10' = (1-2q) M10: BitFlip(q) on the diagonal (the same probs), and on the off-diagonals the factor that
+    BitFlip gives to Y and Z but not to X."""
+    device = q.device
+    q = q.to(torch.float64)
+    s = (1.0 - q) * (_unit((0, 0), device) + _unit((3, 3), device)) + q * (_unit((0, 3), device) + _unit((3, 0), device)) \
+        + (1.0 - 2.0 * q) * (_unit((1, 1), device) + _unit((2, 2), device))
+    return _rows_torch(s), (q >= 0.0) & (q <= 1.0)
+
+
+def superoperator_torch(kraus, wires=1):
+    """``superoperator`` in torch: the rows of S = sum_k K_k (x) conj(K_k) for Kraus operators given as one complex tensor
+    ``(k, d, d)`` or a sequence of d x d tensors / arrays, on the device of the tensors among them and inside their graph.
+    -> (rows, dev): `dev` is the 0-d deviation max |sum K^dagger K - I| there (``qubit_channel_rows`` bounds it by 1e-10)."""
+    if wires not in (1, 2):
+        raise NotImplementedError(f"channels on {wires} wires: one- and two-wire channels are supported")
+    d = 1 << wires
+    ks = list(kraus.unbind(0)) if torch.is_tensor(kraus) else list(kraus)
+    device = next((k.device for k in ks if torch.is_tensor(k)), torch.device("cpu"))
+    ks = [(k if torch.is_tensor(k) else torch.from_numpy(np.asarray(k, dtype=complex))).to(device=device, dtype=torch.complex128)
+          for k in ks]
+    if not ks or any(tuple(k.shape) != (d, d) for k in ks):
+        raise ValueError(f"Kraus operators must be a non-empty list of {d} x {d} matrices")
+    s = sum(torch.kron(k, k.conj()) for k in ks)
+    with torch.no_grad():
+        dev = (sum(k.mH @ k for k in ks) - torch.eye(d, dtype=torch.complex128, device=device)).abs().max()
+    return _rows_torch(s), dev
+
+
 # wires up to which ``execute`` runs a circuit (8: the one-workgroup kernel only; 9, 10: the tile-fused engine as well)
 _max_wires = 8
 # resident samples per chunk of the tile-fused engine (0: the library's cap of 1 GiB of slabs); tests lower it to force
@@ -389,6 +522,8 @@ class _Lowering:
         self.features, self.pad_with = None, 0.0
         self.device = None
         self.strengths = []  # (row, parameter name) of every native channel whose strength is a tensor
+        self.checks = []     # (0-d bool on the GPU, explain) of every trainable general channel: its parameters' ranges
+        self.fit_base = {}   # (name, parameters) of a trainable named channel -> (first row, rows): built once per circuit
         self.n_cols = 0      # MEAS_OBS: the columns of the measurement table; MEAS_RHO: 2 * 4^k, the reduced matrix as reals
         # what `execute` does with the launch's (B, width) result (None: nothing)
         #   ("marginal", wires)   probs of these wires, in this order, from the full probs
@@ -448,6 +583,30 @@ class _Lowering:
         if base is None:
             base = self.channel_base[key] = self._add_gates(rows)
         self.ops.append((_capi.MIX_CHANNEL2, wire, base, 0.0, 1.0, second))  # a six-field entry of `ops`, as gate2's and MIX_OBS's
+
+    def channel_fit(self, op, wires):
+        """A general channel whose rows get a gradient, on each of `wires` (one wire, or one pair).  `op`: the recorded op,
+        whose `trainable` builds (rows in their autograd graph on the GPU, 0-d bool `ok` there, explain) -- or that
+        triple itself.  The rows join the gates as GPU rows of a unitary do, and the op is MIX_CHANNEL_FIT /
+        MIX_CHANNEL2_FIT.  A named channel recorded again with the same parameters (the same tensors, equal floats: one
+        error model on every wire) is built once: one graph, one set of rows, and the gradients of its ops add."""
+        key = None
+        if not isinstance(op, tuple) and op.name != "QubitChannel":
+            key = (op.name, len(op.wires)) + tuple(("t", id(p)) if torch.is_tensor(p) else ("v", p) for p in op.params)
+        base = self.fit_base.get(key)
+        if base is None:
+            rows, ok, explain = op if isinstance(op, tuple) else op.hyper["trainable"]()
+            self._see(rows)  # on the CPU: no CPU path
+            self.checks.append((ok, explain))
+            base = (self._add_gates(rows), rows.shape[0])
+            if key is not None:
+                self.fit_base[key] = base
+        base, n_rows = base
+        for w in wires:
+            if n_rows == 64:
+                self.ops.append((_capi.MIX_CHANNEL2_FIT, w[0], base, 0.0, 1.0, w[1]))
+            else:
+                self.op(_capi.MIX_CHANNEL_FIT, w, base)
 
     def _gate_rows(self, rows):
         """The first row of a unitary's `rows` among the gates.  Constant (host) rows join once per distinct matrix, found
@@ -696,6 +855,8 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
                     low.gate2(rows, t.wires[0], t.wires[1])
                 else:
                     low.gate1(rows, t.wires[0])
+            elif "trainable" in t.hyper:  # a general channel with a parameter that requires grad, in grad mode
+                low.channel_fit(t, [t.wires] if len(t.wires) == 2 else [t.wires[0]])
             elif "superoperator" in t.hyper:
                 if len(t.wires) == 2:
                     low.channel2(t.hyper["superoperator"], t.wires[0], t.wires[1])
@@ -707,6 +868,17 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
     if first:
         low.op(_capi.MIX_ZERO)
     analytic_obs = form == "obs" and shots is None
+    if torch.is_tensor(readout_prob):  # it requires grad (qml.Device keeps no other tensor)
+        if trainable([readout_prob]):
+            # one trainable flip per wire in front of every analytic read-out (no (1 - 2q)^weight shortcut: the channels
+            # themselves carry the gradient); the same four rows for every wire.  BitFlip for the read-outs of the
+            # diagonal; for a table of Pauli words the flip in each letter's own basis, which is what the shortcut stands
+            # for (a BitFlip on rho would leave the letter X unscaled)
+            rows, ok = readout_rows_torch(readout_prob) if analytic_obs else channel_rows_torch("BitFlip", readout_prob)
+            low.channel_fit((rows, ok, lambda q=readout_prob.detach(): _prob("readout_prob", q)), all_w)
+            readout_prob = None
+        else:  # under no_grad: a float like any other
+            readout_prob = _prob("readout_prob", readout_prob)
     if readout_prob is not None and not analytic_obs:
         # PennyLane: BitFlip(readout_prob) on every measured wire in front of the measurement
         base = low._add_gates(channel_rows("BitFlip", readout_prob))  # the same four rows for every wire
@@ -854,6 +1026,24 @@ def _check_strengths(rows, strengths):
         _prob(strengths[i][1], s[i, j])
 
 
+def _check_parameters(rows, strengths, checks):
+    """`_check_strengths` and the range conditions of the trainable general channels (`_Lowering.checks`) in ONE
+    synchronisation per ``execute``; what fails raises in the words of the host checks (``_prob``, ``_thermal``, ...)."""
+    flags = [ok.reshape(()) for ok, _ in checks]
+    if strengths:
+        s = rows.detach()[[row for row, _ in strengths]]
+        flags.append(((s >= 0.0) & (s <= 1.0)).all())
+    flags = torch.stack(flags).cpu()  # the one look
+    if bool(flags.all()):
+        return
+    if strengths and not bool(flags[-1]):
+        _check_strengths(rows, strengths)
+    for good, (_, explain) in zip(flags, checks):
+        if not bool(good):
+            explain()
+            raise ValueError("a channel parameter is out of range")  # (the host check found nothing to name)
+
+
 def execute(tape, ret, n, precision=None, _engine=None, device=None):
     """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)`` -- marginal
     probs of k wires ``(B, 2^k)``, one expval ``(B,)``, a list of k expvals ``(B, k)``; complex128 ``(B, 2^k, 2^k)`` for
@@ -867,7 +1057,8 @@ def execute(tape, ret, n, precision=None, _engine=None, device=None):
     readout_prob = getattr(qdev, "readout_prob", None)
     if shots is not None:
         from . import qml
-        if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params):
+        if torch.is_grad_enabled() and (any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params)
+                                        or (torch.is_tensor(readout_prob) and readout_prob.requires_grad)):
             raise qml.QuantumFunctionError("finite shots have no reverse sweep; sample under torch.no_grad() or use "
                                            "shots=None")
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
@@ -876,7 +1067,8 @@ def execute(tape, ret, n, precision=None, _engine=None, device=None):
     # the engine follows the number of wires; `_engine="wide"` (tests, A/B tools) forces the tile-fused one at 7, 8 wires
     wide = _engine == "wide" or 8 < n <= _max_wires
     if wide and n > _max_grad_wires and torch.is_grad_enabled() and \
-            any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params):
+            (any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params)
+             or (torch.is_tensor(readout_prob) and readout_prob.requires_grad)):
         if _max_grad_wires > 8:
             raise NotImplementedError(
                 f"default.mixed on {n} wires executes forward only: gradients stop at {_max_grad_wires} wires (the "
@@ -896,7 +1088,9 @@ def execute(tape, ret, n, precision=None, _engine=None, device=None):
     launch = _Launch(low, measure, n, prec, device, batch)
     f64 = dict(dtype=torch.float64, device=device)
     rows = torch.stack([r.to(**f64).expand(batch) for r in low.rows]).contiguous() if low.rows else None
-    if low.strengths:
+    if low.checks:
+        _check_parameters(rows, low.strengths, low.checks)
+    elif low.strengths:
         _check_strengths(rows, low.strengths)
     gates =_gates_on(device, low.gates) if low.gates else None
     feats = low.features.to(**f64).contiguous() if low.features is not None else None

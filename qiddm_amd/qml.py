@@ -271,8 +271,14 @@ DepolarizingChannel = _channel("DepolarizingChannel")
 # host (qiddm_amd.mixed.channel_rows): 4 x 4 on one wire, 16 x 16 on two (QubitChannel with 4 x 4 operators and
 # PauliError with a two-letter word).  Strengths are Python floats or host arrays; arguments out of range raise
 # ValueError when the op is constructed.
-def _general_channel(name, wires, params, rows_of, two_wires=False):
-    """`rows_of(mixed)`: the op's (4, 8) -- on two wires (64, 8) -- superoperator rows; it checks the parameters."""
+# With grad mode on and a parameter (a Kraus operator) that is a tensor requiring grad, the op is TRAINABLE instead: no
+# value is read here, `trainable(mixed)` builds the rows in torch on the tensor's device when the circuit is lowered
+# (qiddm_amd.mixed.channel_rows_torch / superoperator_torch), the op becomes QIDDM_MIX_CHANNEL_FIT / _CHANNEL2_FIT, and
+# the range checks are read back once per execution.
+def _general_channel(name, wires, params, rows_of, two_wires=False, trainable=None):
+    """`rows_of(mixed)`: the op's (4, 8) -- on two wires (64, 8) -- superoperator rows; it checks the parameters.
+    `trainable(mixed)` instead: -> (rows in their graph, 0-d bool `ok` on the device, `explain()` that raises in the words
+    of the host check once `ok` has been read as False)."""
     from . import mixed as _mixed
     w = _wires(wires)
     if len(w) > 2:
@@ -284,7 +290,23 @@ def _general_channel(name, wires, params, rows_of, two_wires=False):
         raise ValueError(f"{name}: the two wires must differ (got {list(w)})")
     if len(w) != 1 and len(w) != 2:
         raise ValueError(f"{name}: bad wires {wires!r}")
+    if trainable is not None:
+        return _Op(name, w, params, channel=True, trainable=lambda: trainable(_mixed))
     return _Op(name, w, params, channel=True, superoperator=rows_of(_mixed))
+
+
+def _named_rows(name, params):
+    """(rows_of, trainable) of a named channel for `_general_channel`."""
+    from . import mixed as _mixed
+    rows_of = lambda mixed: mixed.channel_rows(name, *params)
+    if not _mixed.trainable(params):
+        return rows_of, None
+
+    def trainable(mixed):
+        rows, ok = mixed.channel_rows_torch(name, *params)
+        values = [p.detach() if torch.is_tensor(p) else p for p in params]
+        return rows, ok, lambda: mixed.channel_rows(name, *values)  # the host check on the values: it raises in its own words
+    return rows_of, trainable
 
 
 def _named_channel(name, wires, *params):
@@ -293,7 +315,8 @@ def _named_channel(name, wires, *params):
             raise NotImplementedError(
                 f"{name}: per-sample (1-D) strengths exist for the three native channels only (PhaseDamping, "
                 "AmplitudeDamping, DepolarizingChannel); this channel takes floats and 0-d tensors")
-    return _general_channel(name, wires, params, lambda mixed: mixed.channel_rows(name, *params))
+    rows_of, trainable = _named_rows(name, params)
+    return _general_channel(name, wires, params, rows_of, trainable=trainable)
 
 
 def BitFlip(p, wires):
@@ -319,8 +342,8 @@ def PauliError(operators, p, wires):
         raise ValueError(f"PauliError: operators {operators!r} has {len(operators)} letter(s) for {len(w)} wire(s); "
                          "the word needs one letter per wire")
     if len(w) == 2:
-        return _general_channel("PauliError", w, (operators, p),
-                                lambda mixed: mixed.channel_rows("PauliError", operators, p), two_wires=True)
+        rows_of, trainable = _named_rows("PauliError", (operators, p))
+        return _general_channel("PauliError", w, (operators, p), rows_of, two_wires=True, trainable=trainable)
     return _named_channel("PauliError", wires, operators, p)
 
 
@@ -330,11 +353,27 @@ def ThermalRelaxationError(pe, t1, t2, tg, wires):
 
 def QubitChannel(K_list, wires):
     """``qml.QubitChannel(K_list, wires)``: Kraus operators as complex host matrices, sum K^dagger K = I; 2 x 2 on one
-    wire, 4 x 4 on two (index 2 b_a + b_b for ``wires=[a, b]``)."""
+    wire, 4 x 4 on two (index 2 b_a + b_b for ``wires=[a, b]``).  `K_list` may be, or hold, a complex GPU tensor that
+    requires grad: in grad mode the gradient reaches its entries (unconstrained: staying trace preserving is the caller's
+    parametrisation; the values given are checked as host matrices are)."""
+    from . import mixed as _mixed
     w = _wires(wires)
-    if len(w) == 2 and not _all_2x2(K_list):
-        return _general_channel("QubitChannel", w, (), lambda mixed: mixed.qubit_channel_rows(K_list, 2), two_wires=True)
-    return _general_channel("QubitChannel", wires, (), lambda mixed: mixed.qubit_channel_rows(K_list))
+    two = len(w) == 2 and not _all_2x2(K_list)
+    params, trainable = (), None
+    held = [K_list] if torch.is_tensor(K_list) else [k for k in K_list if torch.is_tensor(k)]
+    if _mixed.trainable(held):  # a complex tensor that requires grad: the gradient reaches the (unconstrained) entries
+        params = tuple(held)    # seen by what asks whether the tape requires grad
+
+        def trainable(mixed):
+            rows, dev = mixed.superoperator_torch(K_list, 2 if two else 1)
+
+            def explain():
+                raise ValueError(f"K_list is not trace preserving: sum K^dagger K differs from the identity by {float(dev):.3e}")
+            return rows, dev <= 1e-10, explain
+    if two:
+        return _general_channel("QubitChannel", w, params, lambda mixed: mixed.qubit_channel_rows(K_list, 2), two_wires=True,
+                                trainable=trainable)
+    return _general_channel("QubitChannel", wires, params, lambda mixed: mixed.qubit_channel_rows(K_list), trainable=trainable)
 
 
 def _all_2x2(K_list):
@@ -559,7 +598,15 @@ class Device:
             self.shots = int(shots)
         if readout_prob is not None:
             from . import mixed as _mixed
-            self.readout_prob = _mixed._prob("readout_prob", readout_prob)
+            if torch.is_tensor(readout_prob) and readout_prob.requires_grad:
+                # kept as it is: in grad mode every execution lowers one trainable BitFlip per wire from it and reads
+                # its range back with the other tensor parameters; under no_grad it is read as a float there
+                if readout_prob.dim() != 0:
+                    raise NotImplementedError("readout_prob: a tensor that requires grad must be 0-d (one probability for "
+                                              "every wire and sample)")
+                self.readout_prob = readout_prob
+            else:
+                self.readout_prob = _mixed._prob("readout_prob", readout_prob)
         if seed is not None and (not _is_int(seed) or not 0 <= seed < 2**53):
             raise ValueError(f"seed must be None or a non-negative int below 2**53 (got {seed!r})")
         if seed is not None:
@@ -595,7 +642,8 @@ def device(name, wires=1, shots=None, readout_prob=None, seed=None, **kwargs):
     ``default.mixed`` also takes PennyLane's read-out model.  ``shots``: ``None`` (analytic) or a positive int -- every
     execution then returns the estimate from that many computational-basis shots, drawn on the device inside the launch
     (no gradient: sample under ``torch.no_grad()``).  ``readout_prob``: ``None`` or a float in [0, 1], a ``BitFlip`` of
-    that strength on every wire in front of the measurement, with or without shots.  ``seed``: ``None`` (one draw from
+    that strength on every wire in front of the measurement, with or without shots; or a 0-d GPU tensor that requires
+    grad, which analytic read-outs differentiate in grad mode (``shots`` then raise ``QuantumFunctionError``).  ``seed``: ``None`` (one draw from
     torch's default CPU generator when the device is created with shots) or a non-negative int; the device counts its
     sampled executions and gives each a stream of its own.  On the pure-state names ``shots`` raises
     ``NotImplementedError`` and ``readout_prob`` ``TypeError``; other keywords are ignored.
