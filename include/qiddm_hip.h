@@ -746,7 +746,8 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *                             like a native channel with a >= 0, replays up to a trailing channel segment that holds
  *                             one; qiddm_mixed_wide_backward_workspace_bytes and _backward_plan count both, for these
  *                             kinds only.  A program without them runs the device code it ran before they existed.
- * Kinds 10, 11, 13..15, 17, 19, 21..23, 25..31 other than 28, 33, and kinds above 34 are no ops: refused as `op %d: unknown kind %d`.
+ * Kinds 10, 11, 13..15, 17, 19, 21..23, 25..31 other than 28, 33, and kinds above 34 are no ops: refused as `op %d: unknown kind %d`
+ * (40, QIDDM_MIX_KRAUS, is an op of the trajectory entry point alone, qiddm_hip_traj.h: these entry points refuse it in the same words).
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
  * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n | columns of the table | 2 * 4^k) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
@@ -769,7 +770,8 @@ enum {
   QIDDM_MIX_GATE2 = 24,
   QIDDM_MIX_RHO = 28,
   QIDDM_MIX_CHANNEL2 = 32,
-  QIDDM_MIX_CHANNEL2_FIT = 34
+  QIDDM_MIX_CHANNEL2_FIT = 34,
+  QIDDM_MIX_KRAUS = 40 /* the trajectory entry point only (qiddm_hip_traj.h) */
 };
 #define QIDDM_MIX_MAX_OBS 256 /* terms of a measurement table */
 typedef struct qiddm_mixed_op {
@@ -866,6 +868,10 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
                               const double *gates, int32_t n_gates, int32_t measure, int64_t batch,
                               const double *grad_out, int64_t gout_ld, double *grad_rows, double *grad_gates,
                               double *grad_features, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Quantum trajectories (the same programs on a pure state, 1 <= n_qubits <= 16, with the op QIDDM_MIX_KRAUS): the two
+ * entry points, their arguments and the trajectory rule are in the extension header include/qiddm_hip_traj.h.  This
+ * header declares what it declared before they existed.                                                            */
 
 #ifdef __cplusplus
 }

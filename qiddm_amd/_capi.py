@@ -81,6 +81,10 @@ MIX_RHO = 28  # last op only: the read-out keeps the wires of the mask `wire` (w
 MIX_CHANNEL2 = 32  # general two-wire channel: `a` = first of 64 gate rows (16 x 16), `reserved` = the second wire
 # 16 k + 2: the k-wire channel whose rows get a gradient from the reverse sweeps (operands and forward as 16 / 32)
 MIX_CHANNEL_FIT, MIX_CHANNEL2_FIT = 18, 34
+# trajectory engine only: a one-wire channel by its Kraus operators, `reserved` = m <= MIX_MAX_KRAUS of them in the gate
+# rows `a` .. `a` + m - 1
+MIX_KRAUS, MIX_MAX_KRAUS = 40, 8
+TRAJ_MAX, TRAJ_SLOTS = 1 << 20, 64  # most trajectories per sample; the slots of the mean are min(n_traj, TRAJ_SLOTS)
 
 
 class MixedOp(ctypes.Structure):
@@ -212,6 +216,12 @@ SIGNATURES = {
 }
 # every symbol include/qiddm_hip.h declares
 EXPORTS = tuple(SIGNATURES)
+# The extension header include/qiddm_hip_traj.h (the trajectory engine): the same kind of table, kept apart as the
+# header is, so that SIGNATURES stays the copy of qiddm_hip.h.  tests/test_mixed_traj_capi.py checks it against its header.
+TRAJ_SIGNATURES = {
+    "qiddm_mixed_traj_workspace_bytes": (_i64, [_i32, _i32, _i64, _i32, _i32, _i64, _i32]),
+    "qiddm_mixed_traj_forward": (_int, _mixed + [_i32, _dbl, _dbl, _i32, _vp, _i64, _vp, _vp] + _ws + _stream),
+}
 
 
 _lock = threading.Lock()
@@ -233,6 +243,17 @@ def _declare(handle):
         raise RuntimeError("libqiddm_hip.so ABI version mismatch; rebuild it")
     for name in SIGNATURES:
         bind(name)
+
+
+def _declare_extensions(handle):
+    """``restype`` / ``argtypes`` of every entry of ``TRAJ_SIGNATURES`` (after ``_declare`` has accepted the library's
+    version); a library without one of them is a stale build."""
+    for name, (restype, argtypes) in TRAJ_SIGNATURES.items():
+        try:
+            fn = getattr(handle, name)
+        except AttributeError:
+            raise RuntimeError(f"libqiddm_hip.so has no symbol {name}: ABI mismatch; rebuild it") from None
+        fn.restype, fn.argtypes = restype, argtypes
 
 
 def _preload_torch_hip_runtime():
@@ -258,6 +279,7 @@ def lib():
             _preload_torch_hip_runtime()
             handle = ctypes.CDLL(LIB_PATH)
             _declare(handle)
+            _declare_extensions(handle)
             _lib = handle
     return _lib
 

@@ -18,7 +18,12 @@
 // the reverse sweeps return the gradient of their rows from kernels of their own (qiddm::kLevelFit in the one-workgroup
 // engine; mixed_wide_adjoint_channels_fit and mixed_wide_fit_finalize in the tile-fused one), which a program without
 // these kinds never launches.
+// The trajectory engine (qsim_traj.h; the two qiddm_mixed_traj_* entry points at the end of this file) runs the same
+// programs on a pure state up to 16 wires.  It validates through check_call with an Engine whose `traj` flag admits
+// QIDDM_MIX_KRAUS and refuses what a trajectory cannot do (superoperator kinds, SHOTS, RHO); without the flag nothing
+// above reads differently.
 #include "capi_common.h"
+#include "../../include/qiddm_hip_traj.h"
 
 #include <hip/hip_runtime.h>
 
@@ -33,6 +38,7 @@
 #include "qsim_mixed.h"
 #include "qsim_mixed_wide.h"
 #include "qsim_mixed_wide_adjoint.h"
+#include "qsim_traj.h"
 
 namespace {
 
@@ -47,7 +53,7 @@ static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixC
                   (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2 && (int)qiddm::kMixShots == (int)QIDDM_MIX_SHOTS &&
                   (int)qiddm::kMixObs == (int)QIDDM_MIX_OBS && (int)qiddm::kMixGate2 == (int)QIDDM_MIX_GATE2 &&
                   (int)qiddm::kMixRho == (int)QIDDM_MIX_RHO && (int)qiddm::kMixChannelFit == (int)QIDDM_MIX_CHANNEL_FIT &&
-                  (int)qiddm::kMixChannel2Fit == (int)QIDDM_MIX_CHANNEL2_FIT,
+                  (int)qiddm::kMixChannel2Fit == (int)QIDDM_MIX_CHANNEL2_FIT && (int)qiddm::kMixKraus == (int)QIDDM_MIX_KRAUS,
               "op kinds");
 static_assert(offsetof(qiddm::MixedOp, wire2) == offsetof(qiddm_mixed_op_t, reserved), "the second wire travels in `reserved`");
 
@@ -120,10 +126,16 @@ inline bool needs_front(const qiddm_mixed_op_t& op) { return is_graded(op) || is
 struct Engine {
   const char* name;
   int min_qubits, max_qubits;
+  bool traj = false;  // the trajectory engine (qsim_traj.h): a pure state, QIDDM_MIX_KRAUS, no superoperators / SHOTS / RHO
 };
-constexpr Engine kOneWorkgroup{"", 1, 8}, kTileFused{"tile-fused ", 7, 10};
+constexpr Engine kOneWorkgroup{"", 1, 8}, kTileFused{"tile-fused ", 7, 10}, kTrajectories{"trajectory ", 1, 16, true};
 
 int check_wires(int32_t n, const Engine& e) {
+  if (e.traj && (n < e.min_qubits || n > e.max_qubits))
+    return fail(QIDDM_ERR_UNSUPPORTED,
+                "trajectory execution needs %d <= n_qubits <= %d (got %d): a pure state of 2^%d elements is the widest "
+                "the one-workgroup engine holds; split the register or use a state-vector device",
+                e.min_qubits, e.max_qubits, n, e.max_qubits);
   if (n < e.min_qubits || n > e.max_qubits)
     return fail(QIDDM_ERR_UNSUPPORTED, "%sdensity-matrix execution needs %d <= n_qubits <= %d (got %d)", e.name,
                 e.min_qubits, e.max_qubits, n);
@@ -266,7 +278,23 @@ int check_obs_tail(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, in
 
 // kind, wire and target / second wire of op i: all the planner reads of an op, and the first thing the validator checks
 // of it.  QIDDM_MIX_SHOTS is checked here in full (position, wire / reserved, shots, seed, offset): it indexes no operand.
-int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops) {
+// `traj`: the trajectory engine's kinds -- QIDDM_MIX_KRAUS is an op, the superoperator kinds and SHOTS are refused.
+int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops, bool traj = false) {
+  if (traj) {
+    if (base_kind(op.kind) == qiddm::kMixChannel || base_kind(op.kind) == qiddm::kMixChannel2)
+      return fail(QIDDM_ERR_UNSUPPORTED,
+                  "op %d: kind %d is a channel given by its superoperator; a trajectory draws Kraus operators: hand a "
+                  "one-wire channel over as QIDDM_MIX_KRAUS, or run the program on qiddm_mixed_forward / "
+                  "qiddm_mixed_wide_forward", i, op.kind);
+    if (op.kind == qiddm::kMixShots)
+      return fail(QIDDM_ERR_UNSUPPORTED,
+                  "op %d: a sampled read-out on trajectories; draw shots from rho with qiddm_mixed_forward / "
+                  "qiddm_mixed_wide_forward", i);
+  }
+  if (traj && op.kind == qiddm::kMixKraus) {
+    if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
+    return QIDDM_OK;
+  }
   if ((op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) && base_kind(op.kind) != qiddm::kMixChannel &&
       base_kind(op.kind) != qiddm::kMixChannel2 && op.kind != qiddm::kMixShots && !is_gate2(op.kind))
     return fail(QIDDM_ERR_INVALID, "op %d: unknown kind %d", i, op.kind);
@@ -328,6 +356,10 @@ int check_call(MixedCall& c, const Engine& e, bool* embeds) {
   if (c.batch == 0) return QIDDM_OK;
   if ((rc = check_program_start(c.program, c.n_ops)) != QIDDM_OK) return rc;
   if ((rc = check_obs_tail(c.n_qubits, c.program, c.n_ops, &c.n_obs, &c.n_cols, &c.rho_mask)) != QIDDM_OK) return rc;
+  if (e.traj && (c.measure == QIDDM_MEAS_RHO || c.rho_mask))
+    return fail(QIDDM_ERR_UNSUPPORTED,
+                "a density-matrix read-out on trajectories: a trajectory holds a pure state; use qiddm_mixed_forward / "
+                "qiddm_mixed_wide_forward (measure QIDDM_MEAS_RHO, QIDDM_MIX_RHO)");
   if (c.measure == QIDDM_MEAS_RHO && !c.rho_mask)
     return fail(QIDDM_ERR_INVALID, "measure QIDDM_MEAS_RHO needs a density-matrix read-out as the last op (QIDDM_MIX_RHO)");
   if (c.measure != QIDDM_MEAS_RHO && c.rho_mask)
@@ -343,8 +375,14 @@ int check_call(MixedCall& c, const Engine& e, bool* embeds) {
   *embeds = false;
   for (int i = 0; i < c.n_body(); ++i) {
     const qiddm_mixed_op_t& op = c.program[i];
-    if ((rc = check_op_wires(c.n_qubits, op, i, c.n_body())) != QIDDM_OK) return rc;
+    if ((rc = check_op_wires(c.n_qubits, op, i, c.n_body(), e.traj)) != QIDDM_OK) return rc;
     switch (base_kind(op.kind)) {
+      case qiddm::kMixKraus:  // (the trajectory engine only: refused above elsewhere) `reserved` rows of gates, one operator each
+        if (op.reserved < 1 || op.reserved > qiddm::kTrajMaxKraus)
+          return fail(QIDDM_ERR_INVALID, "op %d: %d Kraus operators (1 .. %d are taken)", i, op.reserved, qiddm::kTrajMaxKraus);
+        if (op.a < 0 || (int64_t)op.a + op.reserved > c.n_gates)
+          return fail(QIDDM_ERR_INVALID, "op %d: Kraus rows %d..%d out of range", i, op.a, (int)((int64_t)op.a + op.reserved - 1));
+        break;
       case qiddm::kMixAmpEmbed:
         if (!c.features || c.n_features < 1 || c.n_features > d)
           return fail(QIDDM_ERR_INVALID, "Features must be of length %lld or smaller; got length %d.", (long long)d, c.n_features);
@@ -1148,6 +1186,108 @@ int qiddm_mixed_wide_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
     return launch_mixed_wide_backward<decltype(t)>(bp, g, resident, ws, c, grad_out, grad_rows, grad_gates, grad_features,
                                                    m, b, st);
   });
+}
+
+}  // extern "C"
+
+// ---- trajectories (qsim_traj.h) ----------------------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t kTrajLdsBlocks = 2048, kTrajSlabBlocks = 256;  // default grid caps: psi in LDS / in a slab of the workspace
+
+struct TrajGeometry {
+  int64_t slots, blocks, psi_bytes, off_acc, off_slabs, total;
+  bool in_lds;
+};
+
+// S = min(n_traj, 64): a function of n_traj alone, so that the order of every sum is too
+inline int64_t traj_slots(int64_t n_traj) { return n_traj < qiddm::kTrajMaxSlots ? n_traj : qiddm::kTrajMaxSlots; }
+
+TrajGeometry traj_geometry(int32_t n, int32_t dtype, int64_t batch, int64_t n_traj, int32_t n_ops, int64_t width,
+                           int32_t max_blocks) {
+  TrajGeometry g;
+  g.slots = traj_slots(n_traj);
+  g.psi_bytes = ((int64_t)1 << n) * (dtype == QIDDM_F32 ? 8 : 16);
+  g.in_lds = (size_t)g.psi_bytes <= kMixedLdsSlab;
+  const int64_t items = std::max<int64_t>(batch, 1) * g.slots;
+  g.blocks = std::min<int64_t>(items, g.in_lds ? kTrajLdsBlocks : kTrajSlabBlocks);
+  if (max_blocks > 0 && g.blocks > max_blocks) g.blocks = max_blocks;
+  g.off_acc = program_bytes(n_ops);
+  g.off_slabs = g.off_acc + round256(items * width * 8);
+  g.total = g.off_slabs + (g.in_lds ? 0 : g.blocks * g.psi_bytes);
+  return g;
+}
+
+int check_traj_count(int32_t n_traj) {
+  if (n_traj < 1 || n_traj > qiddm::kTrajMaxTraj)
+    return fail(QIDDM_ERR_INVALID, "n_traj %d outside 1 .. 2^20", n_traj);
+  return QIDDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t qiddm_mixed_traj_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, int32_t n_traj, int32_t n_ops,
+                                         int64_t measure_width, int32_t max_blocks) {
+  int rc = check_sizes(n_qubits, dtype, batch, n_ops, kTrajectories);
+  if (rc == QIDDM_OK) rc = check_traj_count(n_traj);
+  if (rc == QIDDM_OK && (measure_width < 1 || measure_width > ((int64_t)1 << n_qubits) + QIDDM_MIX_MAX_OBS))
+    rc = fail(QIDDM_ERR_INVALID, "measure_width %lld out of range", (long long)measure_width);
+  if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc != QIDDM_OK) return rc;
+  return traj_geometry(n_qubits, dtype, batch, n_traj, n_ops, measure_width, max_blocks).total;
+}
+
+int qiddm_mixed_traj_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t* program, int32_t n_ops,
+                             const double* angle_rows, int64_t rows_ld, int32_t n_rows, const double* features,
+                             int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with, const double* gates,
+                             int32_t n_gates, int32_t measure, int64_t batch, int32_t n_traj, double seed, double offset,
+                             int32_t max_blocks, double* out, int64_t out_ld, double* per_traj, int32_t* branches,
+                             void* workspace, int64_t workspace_bytes, void* stream) {
+  MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+              enc_offset, pad_with, gates, n_gates, measure, batch};
+  bool embeds = false;
+  int rc = check_call(c, kTrajectories, &embeds);
+  if (rc == QIDDM_OK) rc = check_traj_count(n_traj);  // these four: refused for an empty batch as well
+  if (rc == QIDDM_OK && !is_counter_word(seed))
+    rc = fail(QIDDM_ERR_INVALID, "trajectory seed %g is not an integer in [0, 2^53)", seed);
+  if (rc == QIDDM_OK && !(is_counter_word(offset) && offset < 4294967296.0))
+    rc = fail(QIDDM_ERR_INVALID, "trajectory offset %g is not an integer in [0, 2^32)", offset);
+  if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc != QIDDM_OK || batch == 0) return rc;
+  if ((rc = check_forward_outputs(c, out, out_ld)) != QIDDM_OK) return rc;
+  const TrajGeometry g = traj_geometry(n_qubits, dtype, batch, n_traj, n_ops, c.width(), max_blocks);
+  if ((rc = check_workspace(workspace, workspace_bytes, g.total, "qiddm_mixed_traj_workspace_bytes")) != QIDDM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  const qiddm::MixedScalars m = make_scalars(c, c.n_body(), n_features, out_ld, g.in_lds);
+  qiddm::TrajScalars tr{};
+  tr.n_traj = n_traj;
+  tr.n_slots = (int32_t)g.slots;
+  tr.width = (int32_t)c.width();
+  for (int i = 0; i < c.n_body(); ++i) tr.n_channels += qiddm::traj_is_channel(program[i].kind) ? 1 : 0;
+  const uint64_t seed_word = (uint64_t)seed;
+  tr.seed_lo = (uint32_t)seed_word;
+  tr.seed_hi = (uint32_t)(seed_word >> 32);
+  tr.offset = (uint32_t)(uint64_t)offset;
+  tr.slab_in_lds = g.in_lds ? 1 : 0;
+  const size_t smem = g.in_lds ? (size_t)g.psi_bytes : 0;  // what this wire count needs, no more
+  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
+  double* acc = reinterpret_cast<double*>(ws + g.off_acc);
+  rc = for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch<qiddm::mixed_traj_kernel<T>>(kMaxLds - 4096 /* the kernel also has 2.5 KiB of static LDS */,
+                                               dim3((unsigned)g.blocks), dim3(256), smem, st, "mixed_traj_kernel", prog,
+                                               angle_rows, features, gates, acc,
+                                               reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), per_traj, branches, m, tr);
+  });
+  if (rc != QIDDM_OK) return rc;
+  const int64_t elems = batch * c.width();
+  hipLaunchKernelGGL(qiddm::mixed_traj_finalize, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, acc, out, out_ld,
+                     batch, tr);
+  return launched("mixed_traj_finalize");
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // qsim_philox.h -- Philox4x32-10 (Salmon et al., Random123) on the device: the one counter-based generator of the
-// library.  Users: the noise field of the training launch (qsim_train.h, philox_normal) and the sampled read-out of the
-// density-matrix engines (qsim_mixed_shots.h).  A value is a pure function of (counter, key): whichever thread, kernel
+// library.  Users: the noise field of the training launch (qsim_train.h, philox_normal), the sampled read-out of the
+// density-matrix engines (qsim_mixed_shots.h) and the decisions of the trajectory engine (qsim_traj.h).  A value is a pure function of (counter, key): whichever thread, kernel
 // or launch needs it derives the same bits.
 #pragma once
 #include <hip/hip_runtime.h>

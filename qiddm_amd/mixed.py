@@ -100,6 +100,22 @@ further trace down to one observable's wires when a list of ``Hermitian`` keeps 
 Hermitian part: see include/qiddm_hip.h) and carries dL/dA to a matrix that requires grad.  These forms are analytic
 only: a device with ``shots`` or ``readout_prob`` raises ``NotImplementedError`` (a read-out error acts on bit strings,
 not on rho), as does a return that mixes them with Pauli words or probs.
+
+Beyond 10 wires no density matrix fits (32 GiB a sample at 16), and the reference's colour-image noise nets are 16-wire
+circuits.  ``qml.device("default.mixed", wires=n, trajectories=T, seed=s)``, 1 <= n <= 16, runs them as QUANTUM
+TRAJECTORIES instead (``execute_trajectories``, ``qiddm_mixed_traj_forward``): T pure states per sample, at every channel
+one Kraus operator drawn with probability |K_k psi|^2 and psi renormalised, the read-outs averaged -- an unbiased
+estimate of the density-matrix result whose standard error is at most 1 / sqrt(T) per element.  The rule (weights, the
+Philox word of every decision, the fixed order of the mean) is in include/qiddm_hip_traj.h; tests/_mixed_traj_ref.py restates
+it.  Gates lower as above; the three native channels stay native (float, 0-d and per-sample strengths); every other
+one-wire channel becomes ``QIDDM_MIX_KRAUS`` -- its Kraus operators (``channel_kraus``; a ``QubitChannel``'s own, more
+than eight reduced to at most four through the Choi matrix, ``kraus_rows``) as rows of ``gates`` -- and a float
+``readout_prob`` one BitFlip ``KRAUS`` per wire (in front of a table of Pauli words still the (1 - 2q)^weight factor,
+which is exact).  Measured: probs (all wires or a subset), the PauliZ list, Pauli words and Hamiltonians.  Such a device
+does not consult ``set_max_wires`` (it guards the density-matrix workspaces), takes the device's next stream offset per
+execution as a sampled one does, and is forward only: a parameter that requires grad in grad mode raises
+``qml.QuantumFunctionError``, stream capture ``RuntimeError``, two-wire channels, ``shots`` on the same device and the
+read-outs of rho ``NotImplementedError``, each before an offset is taken.
 """
 from __future__ import annotations
 
@@ -252,6 +268,19 @@ def channel_rows(name, *params):
         return _rows(_thermal_super(*params))
     kraus = channel_kraus(name, *params)
     return superoperator(kraus, wires=2 if kraus[0].shape[0] == 4 else 1)
+
+
+def kraus_rows(operators):
+    """``(m, 8)`` float64 (CPU) rows of m one-wire Kraus operators, row k = K_k as (k00, k01, k10, k11) in (re, im): what
+    ``QIDDM_MIX_KRAUS`` reads.  More than ``MIX_MAX_KRAUS`` operators are replaced by a Kraus set of the same map (at
+    most four, from the Choi matrix)."""
+    ks = _matrices(operators)
+    if len(ks) > _capi.MIX_MAX_KRAUS:
+        ks = _kraus_of_super(sum(np.kron(k, k.conj()) for k in ks))
+    flat = np.stack(ks).reshape(len(ks), 4)
+    out = np.empty((len(ks), 8), dtype=np.float64)
+    out[:, 0::2], out[:, 1::2] = flat.real, flat.imag
+    return torch.from_numpy(out)
 
 
 def qubit_channel_rows(kraus, wires=1):
@@ -584,6 +613,17 @@ class _Lowering:
             base = self.channel_base[key] = self._add_gates(rows)
         self.ops.append((_capi.MIX_CHANNEL2, wire, base, 0.0, 1.0, second))  # a six-field entry of `ops`, as gate2's and MIX_OBS's
 
+    def kraus(self, operators, wire):
+        """A one-wire channel of a trajectories device: its m <= 8 Kraus operators join the gates, one row each (GATE's
+        layout), `a` is the first and the op's fourth field holds m.  Operators equal (bit for bit) to an earlier
+        channel's join once: a noise model puts the same set on every wire."""
+        rows = kraus_rows(operators)
+        key = rows.numpy().tobytes()
+        base = self.channel_base.get(key)
+        if base is None:
+            base = self.channel_base[key] = self._add_gates(rows)
+        self.ops.append((_capi.MIX_KRAUS, wire, base, 0.0, 1.0, rows.shape[0]))
+
     def channel_fit(self, op, wires):
         """A general channel whose rows get a gradient, on each of `wires` (one wire, or one pair).  `op`: the recorded op,
         whose `trainable` builds (rows in their autograd graph on the GPU, 0-d bool `ok` there, explain) -- or that
@@ -780,8 +820,18 @@ def _measurement_plan(ret, n, shots, readout_prob=None):
     return "obs", columns, single
 
 
-def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
-    """Tape and measurement -> (_Lowering, measure).  `readout_prob`: one BitFlip per wire behind the tape -- for
+def _traj_operators(t):
+    """The Kraus operators a trajectories device draws from for the recorded one-wire channel `t`: the named channels'
+    from ``channel_kraus`` (PennyLane's order), a ``QubitChannel``'s as given."""
+    if "kraus" in t.hyper:
+        return t.hyper["kraus"]
+    return channel_kraus(t.name, *t.params)
+
+
+def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0, traj=False):
+    """Tape and measurement -> (_Lowering, measure).  `traj` (a trajectories device): the general one-wire channels and
+    the read-out flips become MIX_KRAUS ops (their Kraus operators, not their superoperator), the native channels stay
+    native, two-wire channels are refused.  `readout_prob`: one BitFlip per wire behind the tape -- for
     analytic expectation values instead the factor (1 - 2q)^weight on every word's coefficient, which is what those flips
     do to a word; `shots`: the program ends in MIX_SHOTS with this `seed` and stream `offset`.  Pauli-word expectation
     values end the program in a table of MIX_OBS terms (MEAS_OBS); marginal probs and sampled Z-words are the full-probs
@@ -831,7 +881,7 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
                     row, const = low.angle(p, shared=True)
                     low.strengths.append((row, "p" if t.name == "DepolarizingChannel" else "gamma"))
                     low.op(CHANNELS[t.name], t.wires[0], row, const)
-                elif general_channels:
+                elif general_channels and not traj:
                     low.channel(channel_rows(t.name, float(p)), t.wires[0])
                 else:
                     low.op(CHANNELS[t.name], t.wires[0], -1, float(p))
@@ -855,6 +905,11 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
                     low.gate2(rows, t.wires[0], t.wires[1])
                 else:
                     low.gate1(rows, t.wires[0])
+            elif traj and t.hyper.get("channel"):
+                if len(t.wires) == 2:
+                    raise NotImplementedError(f"{t.name} on two wires on a trajectories device: only one-wire channels "
+                                              "are drawn; use default.mixed without trajectories (up to 10 wires)")
+                low.kraus(_traj_operators(t), t.wires[0])
             elif "trainable" in t.hyper:  # a general channel with a parameter that requires grad, in grad mode
                 low.channel_fit(t, [t.wires] if len(t.wires) == 2 else [t.wires[0]])
             elif "superoperator" in t.hyper:
@@ -881,9 +936,13 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0):
             readout_prob = _prob("readout_prob", readout_prob)
     if readout_prob is not None and not analytic_obs:
         # PennyLane: BitFlip(readout_prob) on every measured wire in front of the measurement
-        base = low._add_gates(channel_rows("BitFlip", readout_prob))  # the same four rows for every wire
-        for w in all_w:
-            low.op(_capi.MIX_CHANNEL, w, base)
+        if traj:
+            for w in all_w:
+                low.kraus(channel_kraus("BitFlip", readout_prob), w)  # the same two rows for every wire
+        else:
+            base = low._add_gates(channel_rows("BitFlip", readout_prob))  # the same four rows for every wire
+            for w in all_w:
+                low.op(_capi.MIX_CHANNEL, w, base)
     if shots is not None:
         low.op(_capi.MIX_SHOTS, 0, int(shots), float(seed), float(offset))
     # measurement
@@ -962,6 +1021,24 @@ class _Launch:
         _capi.launch("qiddm_mixed_wide_forward" if wide else "qiddm_mixed_forward", self.device,
                      *self._prefix(rows, gates, feats), out, out.stride(0), ws, ws.numel())
         return out
+
+    def traj_forward(self, rows, gates, feats, n_traj, seed, offset, max_blocks=0, diagnostics=False):
+        """The mean read-out over `n_traj` quantum trajectories per sample (``qiddm_mixed_traj_forward``).
+        `diagnostics`: -> (mean, per_traj (B, T, width) float64, branches (B, T, channel ops) int32)."""
+        n, batch = self.n, self.batch
+        width = (1 << n) if self.measure == _capi.MEAS_PROBS else self.n_cols if self.measure == _capi.MEAS_OBS else n
+        out = torch.empty(batch, width, dtype=torch.float64, device=self.device)
+        per_traj = branches = None
+        if diagnostics:
+            n_channels = sum(op.kind in (_capi.MIX_PHASE_DAMP, _capi.MIX_AMP_DAMP, _capi.MIX_DEPOL, _capi.MIX_KRAUS)
+                             for op in self.prog)
+            per_traj = torch.empty(batch, n_traj, width, dtype=torch.float64, device=self.device)
+            branches = torch.empty(batch, n_traj, n_channels, dtype=torch.int32, device=self.device)
+        ws = self._fresh(_capi.query("qiddm_mixed_traj_workspace_bytes", n, self.prec, batch, n_traj, len(self.prog),
+                                     width, max_blocks))
+        _capi.launch("qiddm_mixed_traj_forward", self.device, *self._prefix(rows, gates, feats), n_traj, float(seed),
+                     float(offset), max_blocks, out, out.stride(0), per_traj, branches, ws, ws.numel())
+        return (out, per_traj, branches) if diagnostics else out
 
     def backward(self, rows, gates, feats, grad_out, max_blocks=0, wide=False):
         """-> (dL/d rows, dL/d gates summed over the batch, dL/d feats); None where there is no operand."""
@@ -1044,6 +1121,63 @@ def _check_parameters(rows, strengths, checks):
             raise ValueError("a channel parameter is out of range")  # (the host check found nothing to name)
 
 
+def _marginal(out, wires, n, batch):
+    """Full probs (B, 2^n) -> the probs of `wires` in their listed order: the other wires summed out."""
+    out = out.reshape(batch, *([2] * n))
+    others = tuple(1 + w for w in range(n) if w not in wires)
+    if others:
+        out = out.sum(dim=others)
+    kept = sorted(wires)
+    return out.permute(0, *[1 + kept.index(w) for w in wires]).reshape(batch, 1 << len(wires))
+
+
+# grid cap of the trajectory launch (0: the library's default); tests lower it to show that the result does not move
+traj_max_blocks = 0
+
+
+def execute_trajectories(tape, ret, n, precision, qdev):
+    """Run the recorded function as ``qdev.trajectories`` quantum trajectories per sample (``qiddm_mixed_traj_forward``:
+    a pure state per trajectory, one Kraus operator drawn at every channel) and return their mean: an estimate of what
+    the density-matrix engines return whose error falls as 1 / sqrt(trajectories), up to 16 wires.  The wire limit of
+    ``set_max_wires`` is not consulted: it guards the density-matrix workspaces.  Forward only; every execution takes the
+    device's next stream offset once the circuit has been accepted."""
+    from . import qml
+    readout_prob = getattr(qdev, "readout_prob", None)
+    if torch.is_grad_enabled() and (any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params)
+                                    or (torch.is_tensor(readout_prob) and readout_prob.requires_grad)):
+        raise qml.QuantumFunctionError("quantum trajectories have no reverse sweep; run under torch.no_grad() or use "
+                                       "trajectories=None")
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("a default.mixed execution on trajectories cannot be captured into a graph: every replay would "
+                           "repeat the same trajectories")
+    ms = ret if isinstance(ret, (list, tuple)) else [ret]
+    if any(isinstance(m, qml._Measurement) and m.kind in qml.RHO_KINDS for m in ms):
+        raise NotImplementedError("state, density_matrix, purity and expval(Hermitian) on a trajectories device: a "
+                                  "trajectory holds a pure state, not rho; use default.mixed without trajectories (up to "
+                                  "10 wires)")
+    low, measure = lower(tape, ret, n, readout_prob, None, traj=True)
+    if low.device is None:
+        raise RuntimeError("default.mixed runs on the GPU only: no tensor argument lives on a HIP device (no CPU path)")
+    offset = qdev.next_offset()  # the circuit has been accepted: this execution has a stream of its own
+    device, batch = low.device, low.batch or 1
+    prec = _capi.F64 if (precision or _c.get_default_precision()) == "f64" else _capi.F32
+    launch = _Launch(low, measure, n, prec, device, batch)
+    f64 = dict(dtype=torch.float64, device=device)
+    rows = torch.stack([r.detach().to(**f64).expand(batch) for r in low.rows]).contiguous() if low.rows else None
+    if low.strengths:
+        _check_strengths(rows, low.strengths)
+    gates = _gates_on(device, low.gates).detach() if low.gates else None
+    feats = low.features.detach().to(**f64).contiguous() if low.features is not None else None
+    if feats is not None and feats.shape[0] != batch:
+        feats = feats.expand(batch, -1).contiguous()
+    out = launch.traj_forward(rows, gates, feats, qdev.trajectories, qdev.seed, offset % (1 << 32), traj_max_blocks)
+    if low.post is not None:  # ("marginal", wires): the only post-processing an analytic lowering asks for
+        out = _marginal(out, low.post[1], n, batch)
+    if low.single:
+        out = out[:, 0]
+    return out if low.batched else out[0]
+
+
 def execute(tape, ret, n, precision=None, _engine=None, device=None):
     """Run the recorded function on the density-matrix kernels.  Returns float64 ``(B, 2^n)`` / ``(B, n)`` -- marginal
     probs of k wires ``(B, 2^k)``, one expval ``(B,)``, a list of k expvals ``(B, k)``; complex128 ``(B, 2^k, 2^k)`` for
@@ -1053,6 +1187,8 @@ def execute(tape, ret, n, precision=None, _engine=None, device=None):
     ``set_max_wires``): forward only unless ``set_max_grad_wires`` admits them too.  `device` (the QNode's ``qml.Device``):
     its ``readout_prob`` and ``shots``; a sampled execution takes the device's next stream offset."""
     qdev = device  # (`device` below: the torch device of the operands)
+    if getattr(qdev, "trajectories", None) is not None:
+        return execute_trajectories(tape, ret, n, precision, qdev)
     shots = getattr(qdev, "shots", None)
     readout_prob = getattr(qdev, "readout_prob", None)
     if shots is not None:
@@ -1100,14 +1236,8 @@ def execute(tape, ret, n, precision=None, _engine=None, device=None):
         out = _MixedFunction.apply(launch, rows, gates, feats, wide)
     else:
         out = launch.forward(rows, gates, feats, wide=wide)
-    if low.post is not None and low.post[0] == "marginal":  # sum the other wires out, the listed ones in their order
-        wires = low.post[1]
-        out = out.reshape(batch, *([2] * n))
-        others = tuple(1 + w for w in range(n) if w not in wires)
-        if others:
-            out = out.sum(dim=others)
-        kept = sorted(wires)
-        out = out.permute(0, *[1 + kept.index(w) for w in wires]).reshape(batch, 1 << len(wires))
+    if low.post is not None and low.post[0] == "marginal":
+        out = _marginal(out, low.post[1], n, batch)
     elif low.post is not None and low.post[0] == "rho":
         out = _rho_results(out, *low.post[1:], device)
     elif low.post is not None:  # ("signed", signs)

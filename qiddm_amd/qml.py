@@ -373,7 +373,9 @@ def QubitChannel(K_list, wires):
     if two:
         return _general_channel("QubitChannel", w, params, lambda mixed: mixed.qubit_channel_rows(K_list, 2), two_wires=True,
                                 trainable=trainable)
-    return _general_channel("QubitChannel", wires, params, lambda mixed: mixed.qubit_channel_rows(K_list), trainable=trainable)
+    op = _general_channel("QubitChannel", wires, params, lambda mixed: mixed.qubit_channel_rows(K_list), trainable=trainable)
+    op.hyper["kraus"] = K_list  # a trajectories device draws from the operators themselves
+    return op
 
 
 def _all_2x2(K_list):
@@ -574,7 +576,7 @@ def _is_int(v):
 
 
 class Device:
-    def __init__(self, name, wires, shots=None, readout_prob=None, seed=None, **kwargs):
+    def __init__(self, name, wires, shots=None, readout_prob=None, seed=None, trajectories=None, **kwargs):
         if isinstance(wires, int):
             self.num_wires = wires
         else:
@@ -584,9 +586,12 @@ class Device:
         if name not in _PURE_STATE_DEVICES and not self.mixed:
             raise DeviceError(f"Device {name} does not exist. Make sure the required plugin is installed.")
         self.shots, self.readout_prob, self.seed, self.calls = None, None, None, 0
+        self.trajectories = None
         if not self.mixed:
             if readout_prob is not None:
                 raise TypeError(f"device {name!r} got an unexpected keyword argument 'readout_prob'")
+            if trajectories is not None:
+                raise TypeError(f"device {name!r} got an unexpected keyword argument 'trajectories'")
             if shots is not None:
                 raise NotImplementedError(
                     f"shots={shots!r} on device {name!r}: the statevector engines are analytic only; finite shots (and "
@@ -609,9 +614,20 @@ class Device:
                 self.readout_prob = _mixed._prob("readout_prob", readout_prob)
         if seed is not None and (not _is_int(seed) or not 0 <= seed < 2**53):
             raise ValueError(f"seed must be None or a non-negative int below 2**53 (got {seed!r})")
+        if trajectories is not None:
+            from . import _capi
+            if not _is_int(trajectories) or not 1 <= trajectories <= _capi.TRAJ_MAX:
+                raise ValueError(f"trajectories must be None (the density matrix) or a positive int up to 2**20 (got "
+                                 f"{trajectories!r})")
+            if not 1 <= self.num_wires <= 16:
+                raise ValueError(f"a trajectories device takes 1 to 16 wires (got {self.num_wires})")
+            if self.shots is not None:
+                raise NotImplementedError("shots together with trajectories: a trajectory's read-out is analytic; use "
+                                          "shots on default.mixed without trajectories, or trajectories alone")
+            self.trajectories = int(trajectories)
         if seed is not None:
             self.seed = int(seed)
-        elif self.shots is not None:
+        elif self.shots is not None or self.trajectories is not None:
             # one draw from torch's default CPU generator: torch.manual_seed reproduces a sampled run.  (An analytic
             # device draws nothing: creating it leaves the generator where it was.)
             self.seed = int(torch.randint(0, 2**53, (1,), dtype=torch.int64).item())
@@ -626,12 +642,14 @@ class Device:
     def __repr__(self):
         kind = "density-matrix" if self.mixed else "statevector"
         extra = "" if self.shots is None else f", shots={self.shots}, seed={self.seed}"
+        if self.trajectories is not None:
+            extra = f", trajectories={self.trajectories}, seed={self.seed}"
         if self.readout_prob is not None:
             extra += f", readout_prob={self.readout_prob}"
         return f"<qiddm_amd HIP {kind} device standing in for {self.short_name!r}, wires={self.num_wires}{extra}>"
 
 
-def device(name, wires=1, shots=None, readout_prob=None, seed=None, **kwargs):
+def device(name, wires=1, shots=None, readout_prob=None, seed=None, trajectories=None, **kwargs):
     """``qml.device(name, wires=n)``.  Every pure-state device name the reference uses maps
     to the HIP statevector engine; ``default.mixed`` (the noise scripts create it,
     src/mnist_noise.py:223) maps to the density-matrix kernels (``qiddm_amd.mixed``: n <= 8 differentiable by a reverse sweep;
@@ -652,8 +670,21 @@ def device(name, wires=1, shots=None, readout_prob=None, seed=None, **kwargs):
     their real linear combinations), one or a list; and, analytic only (no ``shots``, no ``readout_prob``), the state
     itself: ``state()`` (the full density matrix), ``density_matrix(wires)``, ``purity(wires)`` and
     ``expval(Hermitian(A, wires))``, one or a list, all differentiable; the pure-state names measure ``probs`` of all wires or
-    ``[expval(PauliZ(i)) for i in range(n)]`` and refuse the rest with ``NotImplementedError``."""
-    return Device(name, wires, shots=shots, readout_prob=readout_prob, seed=seed, **kwargs)
+    ``[expval(PauliZ(i)) for i in range(n)]`` and refuse the rest with ``NotImplementedError``.
+
+    ``trajectories=T`` (``default.mixed`` only; the pure-state names raise ``TypeError``) takes the device beyond the wires
+    at which a density matrix fits: 1 to 16 wires, whatever ``mixed.set_max_wires`` says.  Every execution then runs T
+    quantum trajectories per sample (T a positive int up to 2**20) -- a pure state each, one Kraus operator drawn at every
+    channel, Philox keyed by ``seed`` and the device's call counter as for ``shots`` -- and returns the mean of their
+    read-outs: an estimate of the density-matrix result with a standard error below 1 / sqrt(T) per element.  Gates and
+    the one-wire channels (the three native ones with float, 0-d or per-sample strengths; ``BitFlip``, ``PhaseFlip``,
+    one-letter ``PauliError``, ``GeneralizedAmplitudeDamping``, ``ResetError``, ``ThermalRelaxationError``, one-wire
+    ``QubitChannel``; a float ``readout_prob``) are accepted, and ``probs`` (all wires or a subset), the ``PauliZ`` list and
+    ``expval`` of Pauli words and Hamiltonians are measured.  Refused before a stream offset is taken: ``shots`` on the
+    same device and two-wire channels (``NotImplementedError``), ``state`` / ``density_matrix`` / ``purity`` /
+    ``Hermitian`` (``NotImplementedError``), a parameter that requires grad in grad mode (``QuantumFunctionError``:
+    trajectories have no gradient), stream capture (``RuntimeError``)."""
+    return Device(name, wires, shots=shots, readout_prob=readout_prob, seed=seed, trajectories=trajectories, **kwargs)
 
 
 class QNode:
