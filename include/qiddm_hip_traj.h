@@ -39,7 +39,7 @@ extern "C" {
  * (`op %d: kind %d is a channel given by its superoperator ...`), QIDDM_MIX_SHOTS (`op %d: a sampled read-out on
  * trajectories ...`), QIDDM_MEAS_RHO / QIDDM_MIX_RHO (`a density-matrix read-out on trajectories ...`).  Every other check
  * is qiddm_mixed_forward's, in its order; n_traj, seed, offset and max_blocks follow the ops and are refused for an empty
- * batch as well; then out / out_ld and the workspace.  batch == 0 returns QIDDM_OK.  There is no reverse sweep.
+ * batch as well; then out / out_ld and the workspace.  batch == 0 returns QIDDM_OK.  The reverse sweep: qiddm_hip_traj_grad.h.
  *
  * THE TRAJECTORY RULE.  Channel ops are numbered d = 0, 1, ... in program order (every PHASE_DAMP, AMP_DAMP, DEPOL and
  * KRAUS op; nothing else).  In trajectory t (0-based) of sample b (the ABSOLUTE row of the batch), channel op d on the

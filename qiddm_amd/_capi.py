@@ -222,6 +222,12 @@ TRAJ_SIGNATURES = {
     "qiddm_mixed_traj_workspace_bytes": (_i64, [_i32, _i32, _i64, _i32, _i32, _i64, _i32]),
     "qiddm_mixed_traj_forward": (_int, _mixed + [_i32, _dbl, _dbl, _i32, _vp, _i64, _vp, _vp] + _ws + _stream),
 }
+# include/qiddm_hip_traj_grad.h (the trajectory engine's reverse sweep): a header and a table of its own for the same
+# reason.  tests/test_mixed_traj_grad_capi.py checks it against its header.
+TRAJ_GRAD_SIGNATURES = {
+    "qiddm_mixed_traj_backward_workspace_bytes": (_i64, [_i32, _i32, _i64, _i32, _ops, _i32, _i32, _i32, _i32, _i32]),
+    "qiddm_mixed_traj_backward": (_int, _mixed + [_i32, _dbl, _dbl, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp] + _ws + _stream),
+}
 
 
 _lock = threading.Lock()
@@ -246,9 +252,9 @@ def _declare(handle):
 
 
 def _declare_extensions(handle):
-    """``restype`` / ``argtypes`` of every entry of ``TRAJ_SIGNATURES`` (after ``_declare`` has accepted the library's
-    version); a library without one of them is a stale build."""
-    for name, (restype, argtypes) in TRAJ_SIGNATURES.items():
+    """``restype`` / ``argtypes`` of every entry of ``TRAJ_SIGNATURES`` and ``TRAJ_GRAD_SIGNATURES`` (after ``_declare`` has
+    accepted the library's version); a library without one of them is a stale build."""
+    for name, (restype, argtypes) in {**TRAJ_SIGNATURES, **TRAJ_GRAD_SIGNATURES}.items():
         try:
             fn = getattr(handle, name)
         except AttributeError:

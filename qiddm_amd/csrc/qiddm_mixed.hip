@@ -21,9 +21,10 @@
 // The trajectory engine (qsim_traj.h; the two qiddm_mixed_traj_* entry points at the end of this file) runs the same
 // programs on a pure state up to 16 wires.  It validates through check_call with an Engine whose `traj` flag admits
 // QIDDM_MIX_KRAUS and refuses what a trajectory cannot do (superoperator kinds, SHOTS, RHO); without the flag nothing
-// above reads differently.
+// above reads differently.  Its reverse sweep (qsim_traj_adjoint.h; include/qiddm_hip_traj_grad.h) follows it: the same
+// checks, then the backward's own (no later state preparation, the gate-row overlap refusal, the gradient pointers).
 #include "capi_common.h"
-#include "../../include/qiddm_hip_traj.h"
+#include "../../include/qiddm_hip_traj_grad.h"
 
 #include <hip/hip_runtime.h>
 
@@ -39,6 +40,7 @@
 #include "qsim_mixed_wide.h"
 #include "qsim_mixed_wide_adjoint.h"
 #include "qsim_traj.h"
+#include "qsim_traj_adjoint.h"
 
 namespace {
 
@@ -197,17 +199,22 @@ int refuse_sampled(const qiddm_mixed_op_t* program, int32_t n_ops) {
 
 // The reverse sweeps: the rows of two GATE / GATE2 ops are the same rows (their gradients add) or share none -- a
 // gradient for rows that partly overlap has no meaning.  Only a GATE2 op or a trainable channel (CHANNEL_FIT: 4 rows,
-// CHANNEL2_FIT: 64) can overlap another's partly.
+// CHANNEL2_FIT: 64) can overlap another's partly -- or, in the trajectory engine's reverse sweep, a KRAUS op (its m rows,
+// which get a gradient there; the density-matrix entry points never see the kind).
 int refuse_overlapping_gate_rows(const qiddm_mixed_op_t* program, int32_t n_ops) {
+  const auto rows_of = [](const qiddm_mixed_op_t& op) -> int64_t {
+    return op.kind == qiddm::kMixKraus ? op.reserved : gate_rows(op.kind);
+  };
   bool any = false;
-  for (int i = 0; i < n_ops; ++i) any = any || is_gate2(program[i].kind) || is_fit(program[i].kind);
+  for (int i = 0; i < n_ops; ++i)
+    any = any || is_gate2(program[i].kind) || is_fit(program[i].kind) || (program[i].kind == qiddm::kMixKraus && program[i].reserved > 1);
   if (!any) return QIDDM_OK;
   std::vector<int> gated;
   for (int i = 0; i < n_ops; ++i) {
-    const int64_t ni = gate_rows(program[i].kind), ai = program[i].a;
+    const int64_t ni = rows_of(program[i]), ai = program[i].a;
     if (!ni) continue;
     for (int j : gated) {
-      const int64_t nj = gate_rows(program[j].kind), aj = program[j].a;
+      const int64_t nj = rows_of(program[j]), aj = program[j].a;
       if (ai < aj + nj && aj < ai + ni && !(ai == aj && ni == nj))
         return fail(QIDDM_ERR_INVALID, "op %d: gate rows %d..%d overlap those of op %d", i, (int)ai, (int)(ai + ni - 1), j);
     }
@@ -1288,6 +1295,133 @@ int qiddm_mixed_traj_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
   hipLaunchKernelGGL(qiddm::mixed_traj_finalize, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, acc, out, out_ld,
                      batch, tr);
   return launched("mixed_traj_finalize");
+}
+
+}  // extern "C"
+
+// ---- trajectories, the reverse sweep (qsim_traj_adjoint.h; include/qiddm_hip_traj_grad.h) ----------------------------------
+namespace {
+
+struct TrajBwdGeometry {
+  int64_t slots, blocks, psi_bytes, snap_stride, gwidth, off_acc, off_rows, off_snaps, off_slabs, total;
+  int32_t n_channels;
+  bool in_lds, embeds;
+};
+
+// `program` may be NULL with n_ops == 0 (an empty batch)
+TrajBwdGeometry traj_backward_geometry(int32_t n, int32_t dtype, int64_t batch, int64_t n_traj,
+                                       const qiddm_mixed_op_t* program, int32_t n_ops, int32_t n_rows, int32_t n_gates,
+                                       int32_t n_features, int32_t max_blocks) {
+  TrajBwdGeometry g;
+  g.slots = traj_slots(n_traj);
+  g.psi_bytes = ((int64_t)1 << n) * (dtype == QIDDM_F32 ? 8 : 16);
+  g.in_lds = (size_t)(2 * g.psi_bytes) <= kMixedLdsSlab;
+  g.n_channels = 0;
+  g.embeds = false;
+  for (int i = 0; program && i < n_ops; ++i) {
+    g.n_channels += qiddm::traj_is_channel(program[i].kind) ? 1 : 0;
+    g.embeds = g.embeds || program[i].kind == qiddm::kMixAmpEmbed;
+  }
+  g.gwidth = (int64_t)n_rows + 8 * (int64_t)n_gates + (g.embeds ? n_features : 0);
+  g.snap_stride = g.psi_bytes + qiddm::kTrajRecordBytes;
+  const int64_t items = std::max<int64_t>(batch, 1) * g.slots;
+  int64_t cap = g.in_lds ? kTrajLdsBlocks : kTrajSlabBlocks;  // never more than the forward's
+  if (g.n_channels > 0)  // the snapshots of a default launch stay within 1 GiB: the tile-fused engine's residency rule
+    cap = std::min<int64_t>(cap, std::max<int64_t>(1, kWideSlabBudget / (g.n_channels * g.snap_stride)));
+  g.blocks = std::min<int64_t>(items, cap);
+  if (max_blocks > 0 && g.blocks > max_blocks) g.blocks = max_blocks;
+  g.off_acc = program_bytes(n_ops);
+  g.off_rows = g.off_acc + round256(items * g.gwidth * 8);
+  g.off_snaps = g.off_rows + round256(g.blocks * g.gwidth * 8);
+  g.off_slabs = g.off_snaps + round256(g.blocks * g.n_channels * g.snap_stride);
+  g.total = g.off_slabs + (g.in_lds ? 0 : g.blocks * 2 * g.psi_bytes);
+  return g;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t qiddm_mixed_traj_backward_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, int32_t n_traj,
+                                                  const qiddm_mixed_op_t* program, int32_t n_ops, int32_t n_rows,
+                                                  int32_t n_gates, int32_t n_features, int32_t max_blocks) {
+  int rc = check_sizes(n_qubits, dtype, batch, n_ops, kTrajectories);
+  if (rc == QIDDM_OK) rc = check_traj_count(n_traj);
+  if (rc == QIDDM_OK && (n_rows < 0 || n_gates < 0)) rc = fail(QIDDM_ERR_INVALID, "negative n_rows / n_gates");
+  if (rc == QIDDM_OK && n_features < 0) rc = fail(QIDDM_ERR_INVALID, "negative n_features");
+  if (rc == QIDDM_OK && n_ops > 0 && !program) rc = fail(QIDDM_ERR_INVALID, "program is NULL");
+  if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc != QIDDM_OK) return rc;
+  return traj_backward_geometry(n_qubits, dtype, batch, n_traj, program, n_ops, n_rows, n_gates, n_features, max_blocks).total;
+}
+
+int qiddm_mixed_traj_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t* program, int32_t n_ops,
+                              const double* angle_rows, int64_t rows_ld, int32_t n_rows, const double* features,
+                              int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with, const double* gates,
+                              int32_t n_gates, int32_t measure, int64_t batch, int32_t n_traj, double seed, double offset,
+                              int32_t max_blocks, const double* grad_out, int64_t gout_ld, double* grad_rows,
+                              double* grad_gates, double* grad_features, double* per_traj_grad, int32_t* branches,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+  MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+              enc_offset, pad_with, gates, n_gates, measure, batch};
+  bool embeds = false;
+  int rc = check_call(c, kTrajectories, &embeds);
+  if (rc == QIDDM_OK) rc = check_traj_count(n_traj);  // these four: refused for an empty batch as well
+  if (rc == QIDDM_OK && !is_counter_word(seed))
+    rc = fail(QIDDM_ERR_INVALID, "trajectory seed %g is not an integer in [0, 2^53)", seed);
+  if (rc == QIDDM_OK && !(is_counter_word(offset) && offset < 4294967296.0))
+    rc = fail(QIDDM_ERR_INVALID, "trajectory offset %g is not an integer in [0, 2^32)", offset);
+  if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc != QIDDM_OK || batch == 0) return rc;
+  for (int i = 1; i < c.n_body(); ++i)
+    if (is_prep(program[i].kind))
+      return fail(QIDDM_ERR_UNSUPPORTED,
+                  "op %d: a state preparation after op 0 has no reverse sweep on trajectories (nothing in front of it "
+                  "reaches the read-out: drop those ops, or use qiddm_mixed_backward up to 8 wires)", i);
+  if ((rc = refuse_overlapping_gate_rows(program, c.n_body())) != QIDDM_OK) return rc;
+  if ((rc = check_backward_outputs(c, embeds, grad_out, gout_ld, grad_rows, grad_gates, grad_features)) != QIDDM_OK) return rc;
+  const TrajBwdGeometry g = traj_backward_geometry(n_qubits, dtype, batch, n_traj, program, n_ops, n_rows, n_gates,
+                                                   n_features, max_blocks);
+  if ((rc = check_workspace(workspace, workspace_bytes, g.total, "qiddm_mixed_traj_backward_workspace_bytes")) != QIDDM_OK) return rc;
+  // no parameter: no gradient to write; the replay still runs when a diagnostic asks for it (branches as the forward's)
+  if (g.gwidth == 0 && !branches) return QIDDM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  const qiddm::MixedScalars m = make_scalars(c, c.n_body(), embeds ? n_features : 0, 0, g.in_lds);
+  qiddm::TrajScalars tr{};
+  tr.n_traj = n_traj;
+  tr.n_slots = (int32_t)g.slots;
+  tr.width = (int32_t)c.width();
+  tr.n_channels = g.n_channels;
+  const uint64_t seed_word = (uint64_t)seed;
+  tr.seed_lo = (uint32_t)seed_word;
+  tr.seed_hi = (uint32_t)(seed_word >> 32);
+  tr.offset = (uint32_t)(uint64_t)offset;
+  tr.slab_in_lds = g.in_lds ? 1 : 0;
+  qiddm::TrajBwdScalars b{};
+  b.gout_ld = gout_ld;
+  b.snap_stride = g.snap_stride;
+  b.n_rows = n_rows;
+  b.n_gates = n_gates;
+  b.n_features = embeds ? n_features : 0;
+  b.gwidth = (int32_t)g.gwidth;
+  const size_t smem = g.in_lds ? 2 * (size_t)g.psi_bytes : 0;  // what this wire count needs, no more
+  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
+  double* acc = reinterpret_cast<double*>(ws + g.off_acc);
+  rc = for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch<qiddm::mixed_traj_backward_kernel<T>>(
+        kMaxLds - 4096 /* the kernel also has 3 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
+        "mixed_traj_backward_kernel", prog, angle_rows, features, gates, grad_out, acc,
+        reinterpret_cast<double*>(ws + g.off_rows), ws + g.off_snaps, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs),
+        per_traj_grad, branches, m, tr, b);
+  });
+  if (rc != QIDDM_OK || g.gwidth == 0) return rc;
+  const int64_t elems = batch * g.gwidth;
+  hipLaunchKernelGGL(qiddm::mixed_traj_grad_finalize, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, acc, grad_rows,
+                     grad_gates, grad_features, batch, tr, b);
+  return launched("mixed_traj_grad_finalize");
 }
 
 }  // extern "C"

@@ -103,12 +103,19 @@ __device__ __forceinline__ double traj_kraus_weight(const double* __restrict__ g
   return fmax(n0 * r[0] + n1 * r[1] + 2.0 * (cx * r[2] - cy * r[3]), 0.0);
 }
 
+struct TrajNoRecord {
+  template <typename U>
+  __device__ __forceinline__ void operator()(int, const U&, double, double) const {}
+};
+
 // One channel op of one trajectory: weights, the decision, psi <- K psi / sqrt(w).  Returns the operator chosen, or -1
 // when the total weight is not positive or not finite (psi is then left as it is).  The same value in every thread.
-template <typename T>
+// `record(chosen, u, w, strength)` is told the 2 x 2 matrix as applied (rounded to T), the chosen weight and the op's
+// strength before psi changes: the reverse sweep (qsim_traj_adjoint.h) keeps them; the forward passes nothing.
+template <typename T, typename R = TrajNoRecord>
 __device__ __forceinline__ int traj_channel(V2<T>* psi, const MixedOp& op, const double* __restrict__ angle_rows,
                                             const double* __restrict__ gates, const MixedScalars& m, const TrajScalars& tr,
-                                            int64_t sample, uint32_t t, uint32_t d, double* s_red) {
+                                            int64_t sample, uint32_t t, uint32_t d, double* s_red, R&& record = R{}) {
   using C = V2<T>;
   const int q = m.n - 1 - op.wire;
   const uint32_t half = 1u << (m.n - 1);
@@ -165,7 +172,12 @@ __device__ __forceinline__ int traj_channel(V2<T>* psi, const MixedOp& op, const
     u.u10 = C{(T)(g[4] * s), (T)(g[5] * s)};
     u.u11 = C{(T)(g[6] * s), (T)(g[7] * s)};
   } else if (op.kind == kMixDepol) {
-    if (chosen == 0) return 0;  // K_0 / sqrt(w_0) is the identity
+    if (chosen == 0) {  // K_0 / sqrt(w_0) is the identity
+      u.u00 = u.u11 = C{(T)1, (T)0};
+      u.u01 = u.u10 = zero;
+      record(0, u, wk, strength);
+      return 0;
+    }
     u.u00 = chosen == 3 ? C{(T)1, (T)0} : zero;
     u.u11 = chosen == 3 ? C{(T)-1, (T)0} : zero;
     u.u01 = chosen == 1 ? C{(T)1, (T)0} : chosen == 2 ? C{(T)0, (T)-1} : zero;
@@ -184,6 +196,7 @@ __device__ __forceinline__ int traj_channel(V2<T>* psi, const MixedOp& op, const
       u.u11 = zero;
     }
   }
+  record(chosen, u, wk, strength);
   traj_apply1<T>(psi, half, q, u);
   return chosen;
 }

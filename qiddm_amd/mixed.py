@@ -113,9 +113,17 @@ than eight reduced to at most four through the Choi matrix, ``kraus_rows``) as r
 ``readout_prob`` one BitFlip ``KRAUS`` per wire (in front of a table of Pauli words still the (1 - 2q)^weight factor,
 which is exact).  Measured: probs (all wires or a subset), the PauliZ list, Pauli words and Hamiltonians.  Such a device
 does not consult ``set_max_wires`` (it guards the density-matrix workspaces), takes the device's next stream offset per
-execution as a sampled one does, and is forward only: a parameter that requires grad in grad mode raises
+execution as a sampled one does, and is forward only by default: a parameter that requires grad in grad mode raises
 ``qml.QuantumFunctionError``, stream capture ``RuntimeError``, two-wire channels, ``shots`` on the same device and the
 read-outs of rho ``NotImplementedError``, each before an offset is taken.
+
+``set_trajectory_grad(True)`` / ``with trajectory_grad():`` turns its reverse sweep on (``_TrajFunction``,
+``qiddm_mixed_traj_backward``, include/qiddm_hip_traj_grad.h): the backward replays the forward's trajectories from the same
+(T, seed, offset), differentiates each one as a linear chain with its branches and normalisers frozen, and returns the
+mean -- an unbiased estimate of the density-matrix gradient.  Everything that reaches the program as angle rows, gate rows
+or features trains (embedding inputs, SEL weights, RX / Rot / RZ / RY angles, controlled rotations, Ising gates,
+``QubitUnitary`` tensors) and so do the strengths of the three native channels; a parameter that requires grad in a
+channel lowered to ``QIDDM_MIX_KRAUS`` (its rows are built on the host) is still refused, by name.
 """
 from __future__ import annotations
 
@@ -453,6 +461,31 @@ def max_grad_wires(k: int):
         yield
     finally:
         set_max_grad_wires(before)
+
+
+# whether a trajectories device differentiates (``qiddm_mixed_traj_backward``); off: the refusal it always gave
+_trajectory_grad = False
+
+
+def set_trajectory_grad(on: bool) -> None:
+    """Let ``qml.device("default.mixed", ..., trajectories=T)`` differentiate: the backward replays the forward's
+    trajectories and returns the mean of their frozen-branch gradients, an unbiased estimate of the density-matrix
+    gradient (include/qiddm_hip_traj_grad.h).  Off by default: a parameter that requires grad then raises as before."""
+    global _trajectory_grad
+    if not isinstance(on, bool):
+        raise ValueError(f"set_trajectory_grad takes True or False (got {on!r})")
+    _trajectory_grad = on
+
+
+@contextlib.contextmanager
+def trajectory_grad(on: bool = True):
+    """``with mixed.trajectory_grad(): ...`` -- ``set_trajectory_grad`` for the duration of a block."""
+    before = _trajectory_grad
+    set_trajectory_grad(on)
+    try:
+        yield
+    finally:
+        set_trajectory_grad(before)
 
 
 def rot_matrices(weights: torch.Tensor) -> torch.Tensor:
@@ -1040,6 +1073,34 @@ class _Launch:
                      float(offset), max_blocks, out, out.stride(0), per_traj, branches, ws, ws.numel())
         return (out, per_traj, branches) if diagnostics else out
 
+    def traj_backward(self, rows, gates, feats, grad_out, n_traj, seed, offset, max_blocks=0, diagnostics=False):
+        """The mean gradient over the `n_traj` trajectories that ``traj_forward`` ran for the same (seed, offset)
+        (``qiddm_mixed_traj_backward``) -> (dL/d rows, dL/d gates per sample (B, G, 8), dL/d feats); None where there is no
+        operand.  `diagnostics`: -> (those three, per_traj_grad (B, T, rows + 8 G + features) float64, branches)."""
+        n, batch = self.n, self.batch
+        grad_out = grad_out.to(torch.float64).contiguous()
+        f64 = dict(dtype=torch.float64, device=self.device)
+        n_gates = 0 if gates is None else gates.shape[0]
+        embeds = any(op.kind == _capi.MIX_AMP_EMBED for op in self.prog)
+        n_feats = feats.shape[1] if feats is not None else 0
+        g_rows = torch.empty(self.n_rows, batch, **f64) if rows is not None else None
+        g_gates = torch.empty(batch, n_gates, 8, **f64) if gates is not None else None
+        g_feats = torch.empty(batch, n_feats, **f64) if feats is not None else None
+        per_traj = branches = None
+        if diagnostics:
+            n_channels = sum(op.kind in (_capi.MIX_PHASE_DAMP, _capi.MIX_AMP_DAMP, _capi.MIX_DEPOL, _capi.MIX_KRAUS)
+                             for op in self.prog)
+            width = self.n_rows + 8 * n_gates + (n_feats if embeds else 0)
+            per_traj = torch.empty(batch, n_traj, width, **f64)
+            branches = torch.empty(batch, n_traj, n_channels, dtype=torch.int32, device=self.device)
+        ws = self._fresh(_capi.query("qiddm_mixed_traj_backward_workspace_bytes", n, self.prec, batch, n_traj, self.prog,
+                                     len(self.prog), self.n_rows, n_gates, n_feats, max_blocks))
+        _capi.launch("qiddm_mixed_traj_backward", self.device, *self._prefix(rows, gates, feats), n_traj, float(seed),
+                     float(offset), max_blocks, grad_out, grad_out.stride(0), g_rows, g_gates, g_feats, per_traj, branches,
+                     ws, ws.numel())
+        grads = (g_rows, g_gates, g_feats)
+        return (grads, per_traj, branches) if diagnostics else grads
+
     def backward(self, rows, gates, feats, grad_out, max_blocks=0, wide=False):
         """-> (dL/d rows, dL/d gates summed over the batch, dL/d feats); None where there is no operand."""
         n, batch = self.n, self.batch
@@ -1078,6 +1139,26 @@ class _MixedFunction(torch.autograd.Function):
         g_rows, g_gates, g_feats = ctx.launch.backward(rows, gates, feats, grad_out, backward_max_blocks, wide=ctx.wide)
         return (None, g_rows if ctx.needs_input_grad[1] else None, g_gates if ctx.needs_input_grad[2] else None,
                 g_feats if ctx.needs_input_grad[3] else None, None)
+
+
+class _TrajFunction(torch.autograd.Function):
+    """``qiddm_mixed_traj_forward`` as an autograd node; its backward is ``qiddm_mixed_traj_backward`` with the same
+    (trajectories, seed, offset), so it replays the trajectories the forward ran.  The forward is the no-grad call."""
+
+    @staticmethod
+    def forward(ctx, launch, rows, gates, feats, n_traj, seed, offset):
+        ctx.launch, ctx.stream = launch, (n_traj, seed, offset)
+        ctx.save_for_backward(rows, gates, feats)
+        return launch.traj_forward(rows, gates, feats, n_traj, seed, offset, traj_max_blocks)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        rows, gates, feats = ctx.saved_tensors
+        g_rows, g_gates, g_feats = ctx.launch.traj_backward(rows, gates, feats, grad_out, *ctx.stream, traj_max_blocks)
+        return (None, g_rows if ctx.needs_input_grad[1] else None,
+                g_gates.sum(dim=0) if ctx.needs_input_grad[2] else None,
+                g_feats if ctx.needs_input_grad[3] else None, None, None, None)
 
 
 # grid cap of the backward launch (0: the library's default); tests lower it to force the sample loop
@@ -1139,14 +1220,28 @@ def execute_trajectories(tape, ret, n, precision, qdev):
     """Run the recorded function as ``qdev.trajectories`` quantum trajectories per sample (``qiddm_mixed_traj_forward``:
     a pure state per trajectory, one Kraus operator drawn at every channel) and return their mean: an estimate of what
     the density-matrix engines return whose error falls as 1 / sqrt(trajectories), up to 16 wires.  The wire limit of
-    ``set_max_wires`` is not consulted: it guards the density-matrix workspaces.  Forward only; every execution takes the
-    device's next stream offset once the circuit has been accepted."""
+    ``set_max_wires`` is not consulted: it guards the density-matrix workspaces.  Forward only unless
+    ``set_trajectory_grad`` is on (then an autograd node, ``_TrajFunction``); every execution takes the device's next
+    stream offset once the circuit has been accepted."""
     from . import qml
     readout_prob = getattr(qdev, "readout_prob", None)
-    if torch.is_grad_enabled() and (any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params)
-                                    or (torch.is_tensor(readout_prob) and readout_prob.requires_grad)):
-        raise qml.QuantumFunctionError("quantum trajectories have no reverse sweep; run under torch.no_grad() or use "
-                                       "trajectories=None")
+    wants_grad = torch.is_grad_enabled() and (any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params)
+                                              or (torch.is_tensor(readout_prob) and readout_prob.requires_grad))
+    if wants_grad and not _trajectory_grad:
+        raise qml.QuantumFunctionError("quantum trajectories have no reverse sweep unless it is turned on "
+                                       "(mixed.set_trajectory_grad(True) or `with mixed.trajectory_grad():`); run under "
+                                       "torch.no_grad() or use trajectories=None")
+    if wants_grad:  # the reverse sweep returns the gradient of Kraus rows, but these rows are built on the host
+        if torch.is_tensor(readout_prob) and readout_prob.requires_grad:
+            raise qml.QuantumFunctionError("readout_prob requires grad on a trajectories device: the read-out flips are "
+                                           "drawn from Kraus operators built on the host, which carry no gradient; fit "
+                                           "it on default.mixed without trajectories (up to 10 wires)")
+        for t in tape:
+            if t.name not in CHANNELS and t.hyper.get("channel") and any(torch.is_tensor(p) and p.requires_grad for p in t.params):
+                raise qml.QuantumFunctionError(
+                    f"{t.name} has a parameter that requires grad on a trajectories device: its Kraus operators are built "
+                    "on the host and carry no gradient; PhaseDamping, AmplitudeDamping and DepolarizingChannel strengths "
+                    "train, or fit this channel on default.mixed without trajectories (up to 10 wires)")
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("a default.mixed execution on trajectories cannot be captured into a graph: every replay would "
                            "repeat the same trajectories")
@@ -1163,14 +1258,18 @@ def execute_trajectories(tape, ret, n, precision, qdev):
     prec = _capi.F64 if (precision or _c.get_default_precision()) == "f64" else _capi.F32
     launch = _Launch(low, measure, n, prec, device, batch)
     f64 = dict(dtype=torch.float64, device=device)
-    rows = torch.stack([r.detach().to(**f64).expand(batch) for r in low.rows]).contiguous() if low.rows else None
+    keep = (lambda v: v) if wants_grad else (lambda v: v.detach())
+    rows = torch.stack([keep(r).to(**f64).expand(batch) for r in low.rows]).contiguous() if low.rows else None
     if low.strengths:
         _check_strengths(rows, low.strengths)
-    gates = _gates_on(device, low.gates).detach() if low.gates else None
-    feats = low.features.detach().to(**f64).contiguous() if low.features is not None else None
+    gates = keep(_gates_on(device, low.gates)) if low.gates else None
+    feats = keep(low.features).to(**f64).contiguous() if low.features is not None else None
     if feats is not None and feats.shape[0] != batch:
         feats = feats.expand(batch, -1).contiguous()
-    out = launch.traj_forward(rows, gates, feats, qdev.trajectories, qdev.seed, offset % (1 << 32), traj_max_blocks)
+    if wants_grad and any(v is not None and v.requires_grad for v in (rows, gates, feats)):
+        out = _TrajFunction.apply(launch, rows, gates, feats, qdev.trajectories, qdev.seed, offset % (1 << 32))
+    else:
+        out = launch.traj_forward(rows, gates, feats, qdev.trajectories, qdev.seed, offset % (1 << 32), traj_max_blocks)
     if low.post is not None:  # ("marginal", wires): the only post-processing an analytic lowering asks for
         out = _marginal(out, low.post[1], n, batch)
     if low.single:

@@ -682,8 +682,10 @@ def device(name, wires=1, shots=None, readout_prob=None, seed=None, trajectories
     ``QubitChannel``; a float ``readout_prob``) are accepted, and ``probs`` (all wires or a subset), the ``PauliZ`` list and
     ``expval`` of Pauli words and Hamiltonians are measured.  Refused before a stream offset is taken: ``shots`` on the
     same device and two-wire channels (``NotImplementedError``), ``state`` / ``density_matrix`` / ``purity`` /
-    ``Hermitian`` (``NotImplementedError``), a parameter that requires grad in grad mode (``QuantumFunctionError``:
-    trajectories have no gradient), stream capture (``RuntimeError``)."""
+    ``Hermitian`` (``NotImplementedError``), a parameter that requires grad in grad mode (``QuantumFunctionError``;
+    ``mixed.set_trajectory_grad(True)`` or ``with mixed.trajectory_grad():`` turns the reverse sweep on, after which
+    gates, embeddings and the native channels' strengths train and only the parameters of the other channels are
+    refused), stream capture (``RuntimeError``)."""
     return Device(name, wires, shots=shots, readout_prob=readout_prob, seed=seed, trajectories=trajectories, **kwargs)
 
 
