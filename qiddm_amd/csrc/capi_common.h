@@ -18,8 +18,9 @@ constexpr size_t kMaxLds = 160 * 1024;  // per-workgroup LDS on gfx950
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int check_circuit(const qiddm_circuit_t* c);
 
-// the buffer registered with qiddm_set_stamp_buffer if it holds at least `need_words` words, else nullptr
-unsigned long long* stamp_buffer(int64_t need_words);
+// the buffer registered with qiddm_set_stamp_buffer if it holds at least `need_words` words, else nullptr; have_words:
+// how many words the returned buffer holds (0 with nullptr), from the same look at the registration
+unsigned long long* stamp_buffer(int64_t need_words, int64_t* have_words = nullptr);
 int set_stamp_buffer(void* device_ptr, int64_t n_words);
 
 // "done once" marker per HIP device: hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device,

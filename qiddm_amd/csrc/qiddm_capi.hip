@@ -33,9 +33,12 @@ int fail(int code, const char* fmt, ...) {
 static std::atomic<unsigned long long*> g_stamp_ptr{nullptr};
 static std::atomic<int64_t> g_stamp_words{0};
 
-unsigned long long* stamp_buffer(int64_t need_words) {
+unsigned long long* stamp_buffer(int64_t need_words, int64_t* have_words) {
   unsigned long long* p = g_stamp_ptr.load(std::memory_order_acquire);
-  return (p != nullptr && g_stamp_words.load(std::memory_order_acquire) >= need_words) ? p : nullptr;
+  const int64_t words = g_stamp_words.load(std::memory_order_acquire);
+  if (p == nullptr || words < need_words) p = nullptr;
+  if (have_words != nullptr) *have_words = p != nullptr ? words : 0;
+  return p;
 }
 
 int set_stamp_buffer(void* device_ptr, int64_t n_words) {

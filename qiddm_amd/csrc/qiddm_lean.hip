@@ -57,14 +57,15 @@ qiddm::KScalars params_of(const qiddm_circuit_t* c) {
 
 // When the instance that carries both bodies (qsim_lean.h: lean_has_solo) runs the one-wavefront-per-item body: from
 // kLeanSoloMinSteps steps per launch on at every batch, below that from kLeanSoloMinItems items (batch x n_steps) on.
-// A solo workgroup stages linear_up's weights and the phase table in LDS and every wavefront fills its registers from
-// there before its first item (~7 us for a launch of one item against ~5 us), and then runs one item in ~3 us, whatever
-// the launch holds up to 2 048 items; the four-wave body pays ~2.7 us per step of a sample.  Measured by
-// tools/ab_lean_solo_threshold.py, float32, P = 784 (profiles/lean_pipeline/threshold.txt; us per launch, four-wave /
+// A solo workgroup stages the phase table in LDS, every wavefront fills its registers from there and loads the weights
+// of the pixels it owns (~6 us for a launch of one item against ~5 us), then a round of eight items per workgroup costs
+// ~7 us whatever the launch holds up to 2 048 items; the four-wave body pays ~2.7 us per step of a sample.  Measured by
+// tools/ab_lean_solo_threshold.py, float32, P = 784 (profiles/lean_rows/threshold.txt; us per launch, four-wave /
 // solo):
-//   1 step:   256 items 5.7 / 9.6     512 items 7.8 / 9.9    1 024 items 13.4 / 10.5    2 048 items 24.0 / 11.8
-//   4 steps:   64 items 13.3 / 9.3    1 024 items 14.9 / 10.6
-//   15 steps: 240 items 42.8 / 9.5    3 840 items 45.8 / 18.3
+//   1 step:   256 items 5.8 / 9.8     512 items 7.8 / 9.9    1 024 items 13.3 / 10.2    2 048 items 24.0 / 10.6
+//   4 steps:   64 items 13.3 / 9.7    1 024 items 14.9 / 10.2
+//   15 steps: 240 items 42.8 / 9.8    3 840 items 46.4 / 16.7
+// The one-step crossover did not move when linear_up went from LDS to registers: between 512 and 1 024 items.
 // (2 and 3 steps are not in the table: the step rule stays where it was measured.)
 constexpr int kLeanSoloMinSteps = 4;
 constexpr int64_t kLeanSoloMinItems = 1024;
@@ -94,13 +95,14 @@ int launch_lean(const double* x, const double* wd, const double* bd, const doubl
   if constexpr (qiddm::lean_has_solo<T, N, PPT, REUP, LPR, POST>()) {
     const int64_t items = p.batch * d.n_steps;
     // (the body counts items and waves in 32 bits)
-    if (lean_solo_wanted(items, d.n_steps) && items < ((int64_t)1 << 31) && d.out_features <= 1024) {
-      const size_t smem = qiddm::LeanSoloLds::bytes(d.out_features, LPR);
+    if (lean_solo_wanted(items, d.n_steps) && items < ((int64_t)1 << 31) && d.out_features <= qiddm::kSoloMaxPixels) {
+      const size_t smem = qiddm::LeanSoloLds::bytes(LPR);
       const int64_t want = (items + qiddm::kSoloWaves - 1) / qiddm::kSoloWaves;   // one item per wavefront
       const int64_t cus = lean_cu_count();                                         // one workgroup per CU at most
+      const unsigned grid = (unsigned)(want < cus ? want : cus);
       return qiddm_capi::launch<qiddm::dense_lean_kernel<T, N, PPT, REUP, LPR, POST>>(
-          kMaxLds, dim3((unsigned)(want < cus ? want : cus)), dim3(qiddm::kSoloThreads), smem, st, "dense_lean_kernel",
-          x, wd, bd, wu, bu, y, static_cast<const unsigned char*>(tables), d, p);
+          kMaxLds, dim3(grid), dim3(qiddm::kSoloThreads), smem, st, "dense_lean_kernel", x, wd, bd, wu, bu, y,
+          static_cast<const unsigned char*>(tables), d, p);
     }
   }
   const size_t smem = qiddm::LeanTables<T, N>::lds_bytes(layers, p.n_rounds,
@@ -219,7 +221,10 @@ int qiddm_dense_sample_lean(const qiddm_circuit_t* c, const double* x, int64_t b
   d.post_mode = post_mode;
   d.n_steps = n_steps;
   d.noise_factor = noise_factor;
-  d.stamps = qiddm_capi::stamp_buffer(8);
+  // (pointer and size from ONE look at the registration: the solo body stamps 8 words per workgroup when they are there)
+  int64_t stamp_words = 0;
+  d.stamps = qiddm_capi::stamp_buffer(8, &stamp_words);
+  d.stamp_words = (int32_t)(stamp_words < INT32_MAX ? stamp_words : INT32_MAX);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return for_dtype(c->dtype, [&](auto t) {
     return dispatch_lean<decltype(t)>(c->n_qubits, x, w_down, b_down, w_up, b_up, y, tables, d, p, layers, st);

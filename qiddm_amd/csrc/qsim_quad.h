@@ -27,6 +27,9 @@ struct QuadScalars {
   int32_t post_mode, n_steps;
   double noise_factor;
   unsigned long long* stamps;  // diagnostics only (tools/stamp_dense.py)
+  // words `stamps` holds (0 with nullptr): with 8 per workgroup behind the first 8 the solo body (qsim_lean_solo.h)
+  // stamps every workgroup's timeline
+  int32_t stamp_words;
 };
 
 // Rot = RZ(omega) RY(theta) RZ(phi), and everything between two RY layers is diagonal:

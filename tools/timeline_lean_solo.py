@@ -1,0 +1,75 @@
+#!/usr/bin/env python
+"""Diagnostic: the timeline of one launch of the one-wavefront-per-item body (csrc/qsim_lean_solo.h) over ALL its
+workgroups.  With a stamp buffer of 8 + 8 x (workgroups) words registered, wavefront 0 of every workgroup writes
+s_memrealtime -- a 100 MHz clock that is the same on every CU -- at its entry, behind the setup's barrier, at the end of
+the layers and of the tail of its first two rounds, and as its last instruction.  Printed, in us (one tick = 0.01 us):
+dispatch skew (first entry -> last entry), the distribution of the workgroups' lifetimes and of their phases, first entry
+-> last exit, the kernel's duration from HIP events around the same launch replayed back to back in a graph, and the
+difference of the last two: the time of a launch that no stamped wavefront accounts for.  The stamped wavefront is one of
+eight of its workgroup; the other seven may leave later.  QNN_noise(784, 8, 14), float32, the solo body forced; the
+benchmark launch (batch 256, 15 steps) and a 240-item launch.
+    python tools/timeline_lean_solo.py"""
+import os, sys
+os.environ["QIDDM_LEAN_SOLO_MIN_ITEMS"] = "0"
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from qiddm_amd import _capi  # noqa: E402
+from qiddm_amd.circuit import Circuit, dense_sample_lean, dense_sample_lean_tables  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from microbench import timeit  # noqa: E402
+
+torch.manual_seed(0)
+P, n, WAVES = 784, 8, 8
+circ = Circuit(n_qubits=n, encoding="rz", imprimitive="CZ", measure="expz", n_rounds=1, n_blocks=1, sel_layers=14)
+wd = (torch.randn(n, P, dtype=torch.float64) / P ** 0.5 * 3).cuda()
+bd = torch.randn(n, dtype=torch.float64).cuda()
+wu = (torch.randn(P, n, dtype=torch.float64) * 0.3).cuda()
+bu = torch.rand(P, dtype=torch.float64).cuda()
+w = (torch.randn(1, 1, 14, n, 3, dtype=torch.float64) * 0.6).cuda()
+tables = dense_sample_lean_tables(circ, w, wd, bd, wu, bu, "f32")
+cus = torch.cuda.get_device_properties(0).multi_processor_count
+NAMES = ["entry -> barrier passed", "round 0 layers", "round 0 tail", "round 1 layers", "round 1 tail", "-> last instruction"]
+
+
+def dist(v):
+    v = sorted(v)
+    q = lambda f: v[min(len(v) - 1, int(f * len(v)))] / 100
+    return f"min {v[0] / 100:6.2f}  median {q(0.5):6.2f}  p90 {q(0.9):6.2f}  max {v[-1] / 100:6.2f}"
+
+
+for batch, steps in ((256, 15), (16, 15)):
+    x = torch.rand(batch, P, dtype=torch.float64).cuda()
+    call = lambda: dense_sample_lean(circ, x, wd, bd, wu, bu, steps, tables, "f32")
+    grid = min(-(-batch * steps // WAVES), cus)
+    _capi.lib().qiddm_set_stamp_buffer(None, 0)
+    kernel_us = timeit(call, launches=50, reps=5)
+    buf = torch.zeros(8 + 8 * grid, dtype=torch.int64, device="cuda")
+    _capi.check(_capi.lib().qiddm_set_stamp_buffer(buf.data_ptr(), buf.numel()))
+    stamped_us = timeit(call, launches=50, reps=5)
+    print(f"batch {batch}, {steps} steps, {batch * steps} items, {grid} workgroups; kernel (HIP events, graph of 50 launches): "
+          f"{kernel_us:.2f} us without stamps, {stamped_us:.2f} us with")
+    for rep in range(3):
+        torch.cuda.synchronize()
+        buf.zero_()
+        call()
+        torch.cuda.synchronize()
+        t = buf[8:].reshape(grid, 8).cpu()
+        assert (t[:, 0] > 0).all() and (t[:, 6] >= t[:, 0]).all(), "a workgroup did not stamp"
+        first, last_entry, last_exit = t[:, 0].min().item(), t[:, 0].max().item(), t[:, 6].max().item()
+        span = (last_exit - first) / 100
+        print(f"  launch {rep}: dispatch skew {(last_entry - first) / 100:5.2f}   first entry -> last exit {span:6.2f}   "
+              f"kernel - that {kernel_us - span:6.2f}   first entry -> first exit {(t[:, 6].min().item() - first) / 100:6.2f}")
+        print(f"    lifetime of a workgroup's wavefront 0   {dist((t[:, 6] - t[:, 0]).tolist())}")
+        for k, name in enumerate(NAMES[:-1]):
+            have = (t[:, k] > 0) & (t[:, k + 1] > 0)
+            if have.any():
+                print(f"    {name:38s}  {dist((t[have, k + 1] - t[have, k]).tolist())}   ({int(have.sum())} workgroups)")
+        # (behind the last stamp a workgroup took: its third and later rounds, if it has any, and the way out)
+        print(f"    {'last round stamped ' + NAMES[-1]:38s}  {dist((t[:, 6] - t[:, 1:6].max(dim=1).values).tolist())}")
+        # where on the chip the late ones sit: entry and exit by workgroup number, eighths of the grid
+        for lo in range(0, grid, max(grid // 8, 1)):
+            sl = t[lo:lo + max(grid // 8, 1)]
+            print(f"    workgroups {lo:3d}..{lo + len(sl) - 1:3d}: entry {(sl[:, 0].min().item() - first) / 100:5.2f}"
+                  f"..{(sl[:, 0].max().item() - first) / 100:5.2f}   exit {(sl[:, 6].min().item() - first) / 100:6.2f}"
+                  f"..{(sl[:, 6].max().item() - first) / 100:6.2f}")
+_capi.lib().qiddm_set_stamp_buffer(None, 0)
