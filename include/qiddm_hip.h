@@ -747,7 +747,8 @@ int qiddm_conv1x1_head_backward(const double *x, const double *weight, const dou
  *                             one; qiddm_mixed_wide_backward_workspace_bytes and _backward_plan count both, for these
  *                             kinds only.  A program without them runs the device code it ran before they existed.
  * Kinds 10, 11, 13..15, 17, 19, 21..23, 25..31 other than 28, 33, and kinds above 34 are no ops: refused as `op %d: unknown kind %d`
- * (40, QIDDM_MIX_KRAUS, is an op of the trajectory entry point alone, qiddm_hip_traj.h: these entry points refuse it in the same words).
+ * (40, QIDDM_MIX_KRAUS, and 48, QIDDM_MIX_KRAUS2, are ops of the trajectory entry points alone, qiddm_hip_traj.h: these entry
+ * points and the planners refuse them in the same words; 41 is no op anywhere).
  * program: HOST array (copied to the head of `workspace` on `stream`); angle_rows (n_rows, rows_ld >= batch),
  * features (batch, feat_ld), gates (n_gates, 8), out (batch, 2^n | n | columns of the table | 2 * 4^k) float64 DEVICE arrays.
  * The four compute entry points check their arguments in one order and report the first fault: n_qubits, dtype, negative
@@ -771,9 +772,11 @@ enum {
   QIDDM_MIX_RHO = 28,
   QIDDM_MIX_CHANNEL2 = 32,
   QIDDM_MIX_CHANNEL2_FIT = 34,
-  QIDDM_MIX_KRAUS = 40 /* the trajectory entry point only (qiddm_hip_traj.h) */
+  QIDDM_MIX_KRAUS = 40, /* the trajectory entry points only (qiddm_hip_traj.h) */
+  QIDDM_MIX_KRAUS2 = 48 /* the trajectory entry points only: a two-wire channel by its Kraus operators (qiddm_hip_traj.h) */
 };
 #define QIDDM_MIX_MAX_OBS 256 /* terms of a measurement table */
+#define QIDDM_MIX_MAX_KRAUS2 16 /* operators of a QIDDM_MIX_KRAUS2 op */
 typedef struct qiddm_mixed_op {
   int32_t kind, wire, a, reserved; /* reserved: the second wire of QIDDM_MIX_CHANNEL2 / _GATE2, the column of QIDDM_MIX_OBS */
   double p, scale;

@@ -35,14 +35,27 @@ extern "C" {
  *                             k10, k11) in (re, im): QIDDM_MIX_GATE's layout.  `p` and `scale` are not read; that
  *                             sum_k K_k^H K_k = 1 is the caller's responsibility.  Only this entry point takes the kind:
  *                             the four density-matrix entry points refuse it as `op %d: unknown kind 40`.
+ *   QIDDM_MIX_KRAUS2 (= 48)   a general two-wire channel on (`wire`, `reserved`) given by its Kraus operators; GATE2's
+ *                             convention: 4 x 4 index 2 b(wire) + b(reserved), the first wire most significant.  `p` = m
+ *                             of them, an integer-valued double in 1 .. QIDDM_MIX_MAX_KRAUS2 = 16 (`op %d: %g Kraus
+ *                             operators (1 .. 16 are taken)`; integers travel in `p` as the seed of QIDDM_MIX_SHOTS does),
+ *                             in the 4m consecutive rows a .. a+4m-1 of `gates` (`op %d: Kraus rows %d..%d out of range`,
+ *                             summed in 64 bits): operator k in rows a+4k .. a+4k+3, row r = K_k[r][0..3] as (re, im) --
+ *                             QIDDM_MIX_GATE2's layout, one matrix after another.  Checked in this order: `wire`
+ *                             (`op %d: wire %d out of range`), `reserved` (`op %d: bad second wire %d` outside 0..n-1 or
+ *                             equal to `wire`), m, the rows.  `scale` is not read; sum_k K_k^H K_k = 1 is the caller's
+ *                             responsibility.  The two trajectory entry points alone take the kind: the four
+ *                             density-matrix entry points and the planners refuse it as `op %d: unknown kind 48`.
+ *                             Kind 41 is no op anywhere.
  * Refused with QIDDM_ERR_UNSUPPORTED and a reason that names the alternative: the superoperator kinds 16 / 18 / 32 / 34
- * (`op %d: kind %d is a channel given by its superoperator ...`), QIDDM_MIX_SHOTS (`op %d: a sampled read-out on
+ * (`op %d: kind %d is a channel given by its superoperator ...`: hand a one-wire channel over as QIDDM_MIX_KRAUS and a
+ * two-wire channel as QIDDM_MIX_KRAUS2), QIDDM_MIX_SHOTS (`op %d: a sampled read-out on
  * trajectories ...`), QIDDM_MEAS_RHO / QIDDM_MIX_RHO (`a density-matrix read-out on trajectories ...`).  Every other check
  * is qiddm_mixed_forward's, in its order; n_traj, seed, offset and max_blocks follow the ops and are refused for an empty
  * batch as well; then out / out_ld and the workspace.  batch == 0 returns QIDDM_OK.  The reverse sweep: qiddm_hip_traj_grad.h.
  *
- * THE TRAJECTORY RULE.  Channel ops are numbered d = 0, 1, ... in program order (every PHASE_DAMP, AMP_DAMP, DEPOL and
- * KRAUS op; nothing else).  In trajectory t (0-based) of sample b (the ABSOLUTE row of the batch), channel op d on the
+ * THE TRAJECTORY RULE.  Channel ops are numbered d = 0, 1, ... in program order (every PHASE_DAMP, AMP_DAMP, DEPOL,
+ * KRAUS and KRAUS2 op; nothing else: a KRAUS2 op is one channel op in d, in n_channels and in `branches`).  In trajectory t (0-based) of sample b (the ABSOLUTE row of the batch), channel op d on the
  * wire at bit q = n-1-wire is applied as follows, everything in float64 whatever the state's dtype:
  *   1. the wire's reduced matrix, unnormalised, over the pairs (a0, a1) = (psi[k with bit q clear], psi[k | 1 << q]):
  *        r00 = sum |a0|^2,  r11 = sum |a1|^2,  r01 = sum a0 conj(a1)
@@ -62,6 +75,15 @@ extern "C" {
  *      operator of weight zero is never chosen.
  *   5. psi <- K_k psi / sqrt(w_k): the 2 x 2 matrix K_k / sqrt(w_k) is formed in float64, rounded once to the state's
  *      dtype, and applied like a GATE.  DEPOL applies 1, X, Y or Z exactly (k = 0 leaves psi untouched).
+ *   A KRAUS2 op on the bits q = n-1-wire and q2 = n-1-reserved follows the same five steps with the pair in the wire's place:
+ *   1. the pair's reduced matrix, unnormalised, over the quadruples a_0 .. a_3 of psi (a_j = psi[k with the bits set as in
+ *      j = 2 b(q) + b(q2)]):  R[r][c] = sum a_r conj(a_c) for r <= c -- 4 real and 6 complex sums, 16 doubles in one
+ *      reduction (per-thread partials in ascending quadruple index, a wave butterfly, four partials added in wave order).
+ *   2. w_k = max(0, Tr(K_k R K_k^H)),  Tr(K R K^H) = sum_r G[r][r] R[r][r] + 2 Re sum_{r<c} G[c][r] R[r][c],  G = K^H K.
+ *      No special case for unitary operator sets: two-qubit depolarizing goes through R like anything else.
+ *   3., 4. as above (sequential sums, the stop at W not positive or not finite, one Philox word, the clamp).
+ *   5. psi <- K_k psi / sqrt(w_k): the 4 x 4 matrix K_k / sqrt(w_k) is formed in float64, rounded once to the state's
+ *      dtype, and applied as GATE2 applies its matrix.  psi is swept twice per op: a read for R, a read and a write here.
  * Read-out of a trajectory, float64: QIDDM_MEAS_PROBS |psi_k|^2; QIDDM_MEAS_EXPZ sum_k (+-)|psi_k|^2 per wire;
  * QIDDM_MEAS_OBS the formula of QIDDM_MIX_OBS with rho[k][k ^ x] = psi_k conj(psi_{k ^ x}).
  * THE MEAN does not depend on the grid.  S = min(n_traj, 64) slots; trajectory t belongs to slot t mod S.  The read-outs

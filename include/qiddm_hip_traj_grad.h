@@ -46,7 +46,15 @@ extern "C" {
  *   grad_gates (batch, n_gates, 8)  GATE / GATE2 rows, entries as independent reals: dL/dRe A_ab = 2 Re sum conj(lambda_a)
  *                                   psi_b, dL/dIm A_ab = -2 Im sum conj(lambda_a) psi_b over the wire's pairs / quadruples
  *                                   (psi = psi_{i-1}).  KRAUS: row a + k_d gets that times 1 / sqrt(w_d), the op's other rows
- *                                   get zero in that trajectory.
+ *                                   get zero in that trajectory.  KRAUS2 (QIDDM_MIX_KRAUS2, qiddm_hip_traj.h): rows
+ *                                   a + 4 k_d .. a + 4 k_d + 3 get GATE2's entry gradients times 1 / sqrt(w_d) -- with W_rc =
+ *                                   sum over the quadruples of conj(lambda_r) psi_{i-1,c}, dL/dRe A_rc = 2 Re W_rc and
+ *                                   dL/dIm A_rc = -2 Im W_rc -- and the op's other operators zero in that trajectory.
+ *                                   The op is replayed with a snapshot in front of it like every channel op; its record
+ *                                   keeps the branch and w_d alone, and the walk back rebuilds the applied 4 x 4 matrix
+ *                                   K_k / sqrt(w_d) from them and the gate rows by the forward's code (the same rounding),
+ *                                   takes psi_{i-1} from the snapshot and sets lambda <- A^H lambda.  The record stays
+ *                                   256 B: both workspace sizes are what they are with a KRAUS op in its place.
  *   grad_features (batch, n_features)  AMP_EMBED as op 0: with g = 2 Re lambda_0 and psi_0 = v / |v|,
  *                                   dL/dv = (g - (g . psi_0) psi_0) / |v|.  Read only when the program embeds.
  * A trajectory whose forward stopped (W not positive or not finite) gives NaN in every gradient of its sample.
@@ -69,8 +77,8 @@ extern "C" {
  * Checks: those of qiddm_mixed_traj_forward, in its order and words, up to max_blocks (refused for an empty batch as well;
  * batch == 0 then returns QIDDM_OK); then QIDDM_ERR_UNSUPPORTED for a state preparation after op 0 (`op %d: a state
  * preparation after op 0 has no reverse sweep on trajectories`), the gate-row overlap refusal of qiddm_mixed_backward
- * (`op %d: gate rows %d..%d overlap those of op %d`; here a KRAUS op counts with its m rows a .. a+m-1: the rows of two ops
- * that get a gate-row gradient -- GATE, GATE2, KRAUS -- are the same rows, whose gradients add, or share none), grad_out / gout_ld and the gradient pointers in its words, then the
+ * (`op %d: gate rows %d..%d overlap those of op %d`; here a KRAUS op counts with its m rows a .. a+m-1 and a KRAUS2 op with
+ * its 4m rows a .. a+4m-1: the rows of two ops that get a gate-row gradient -- GATE, GATE2, KRAUS, KRAUS2 -- are the same rows, whose gradients add, or share none), grad_out / gout_ld and the gradient pointers in its words, then the
  * workspace (`workspace of %lld B needed (qiddm_mixed_traj_backward_workspace_bytes)`).
  *   qiddm_mixed_traj_backward_workspace_bytes  host only; reads the program to count its channel ops C and whether it
  *       embeds.  With W = n_rows + 8 n_gates + (embeds ? n_features : 0), E = 2^n elements of 8 B (float32) / 16 B (float64),

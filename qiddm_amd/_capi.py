@@ -84,11 +84,14 @@ MIX_CHANNEL_FIT, MIX_CHANNEL2_FIT = 18, 34
 # trajectory engine only: a one-wire channel by its Kraus operators, `reserved` = m <= MIX_MAX_KRAUS of them in the gate
 # rows `a` .. `a` + m - 1
 MIX_KRAUS, MIX_MAX_KRAUS = 40, 8
+# trajectory engine only: a two-wire channel by its Kraus operators on (`wire`, `reserved`), `p` = m <= MIX_MAX_KRAUS2 of
+# them, operator k in the gate rows `a` + 4k .. `a` + 4k + 3 (MIX_GATE2's layout)
+MIX_KRAUS2, MIX_MAX_KRAUS2 = 48, 16
 TRAJ_MAX, TRAJ_SLOTS = 1 << 20, 64  # most trajectories per sample; the slots of the mean are min(n_traj, TRAJ_SLOTS)
 
 
 class MixedOp(ctypes.Structure):
-    """``qiddm_mixed_op_t``.  ``reserved`` is 0 except for ``MIX_CHANNEL2`` and ``MIX_GATE2``, which read their second wire there, and ``MIX_OBS``, which reads
+    """``qiddm_mixed_op_t``.  ``reserved`` is 0 except for ``MIX_CHANNEL2``, ``MIX_GATE2`` and ``MIX_KRAUS2``, which read their second wire there, and ``MIX_OBS``, which reads
     its output column there."""
 
     _fields_ = [("kind", ctypes.c_int32), ("wire", ctypes.c_int32), ("a", ctypes.c_int32),

@@ -20,7 +20,7 @@
 // these kinds never launches.
 // The trajectory engine (qsim_traj.h; the two qiddm_mixed_traj_* entry points at the end of this file) runs the same
 // programs on a pure state up to 16 wires.  It validates through check_call with an Engine whose `traj` flag admits
-// QIDDM_MIX_KRAUS and refuses what a trajectory cannot do (superoperator kinds, SHOTS, RHO); without the flag nothing
+// QIDDM_MIX_KRAUS / QIDDM_MIX_KRAUS2 and refuses what a trajectory cannot do (superoperator kinds, SHOTS, RHO); without the flag nothing
 // above reads differently.  Its reverse sweep (qsim_traj_adjoint.h; include/qiddm_hip_traj_grad.h) follows it: the same
 // checks, then the backward's own (no later state preparation, the gate-row overlap refusal, the gradient pointers).
 #include "capi_common.h"
@@ -55,7 +55,8 @@ static_assert((int)qiddm::kMixDepol == (int)QIDDM_MIX_DEPOL && (int)qiddm::kMixC
                   (int)qiddm::kMixChannel2 == (int)QIDDM_MIX_CHANNEL2 && (int)qiddm::kMixShots == (int)QIDDM_MIX_SHOTS &&
                   (int)qiddm::kMixObs == (int)QIDDM_MIX_OBS && (int)qiddm::kMixGate2 == (int)QIDDM_MIX_GATE2 &&
                   (int)qiddm::kMixRho == (int)QIDDM_MIX_RHO && (int)qiddm::kMixChannelFit == (int)QIDDM_MIX_CHANNEL_FIT &&
-                  (int)qiddm::kMixChannel2Fit == (int)QIDDM_MIX_CHANNEL2_FIT && (int)qiddm::kMixKraus == (int)QIDDM_MIX_KRAUS,
+                  (int)qiddm::kMixChannel2Fit == (int)QIDDM_MIX_CHANNEL2_FIT && (int)qiddm::kMixKraus == (int)QIDDM_MIX_KRAUS &&
+                  (int)qiddm::kMixKraus2 == (int)QIDDM_MIX_KRAUS2 && qiddm::kTrajMaxKraus2 == QIDDM_MIX_MAX_KRAUS2,
               "op kinds");
 static_assert(offsetof(qiddm::MixedOp, wire2) == offsetof(qiddm_mixed_op_t, reserved), "the second wire travels in `reserved`");
 
@@ -200,14 +201,15 @@ int refuse_sampled(const qiddm_mixed_op_t* program, int32_t n_ops) {
 // The reverse sweeps: the rows of two GATE / GATE2 ops are the same rows (their gradients add) or share none -- a
 // gradient for rows that partly overlap has no meaning.  Only a GATE2 op or a trainable channel (CHANNEL_FIT: 4 rows,
 // CHANNEL2_FIT: 64) can overlap another's partly -- or, in the trajectory engine's reverse sweep, a KRAUS op (its m rows,
-// which get a gradient there; the density-matrix entry points never see the kind).
+// which get a gradient there; the density-matrix entry points never see the kind) or a KRAUS2 op (its 4 m rows).
 int refuse_overlapping_gate_rows(const qiddm_mixed_op_t* program, int32_t n_ops) {
   const auto rows_of = [](const qiddm_mixed_op_t& op) -> int64_t {
-    return op.kind == qiddm::kMixKraus ? op.reserved : gate_rows(op.kind);
+    return op.kind == qiddm::kMixKraus2 ? 4 * (int64_t)op.p : op.kind == qiddm::kMixKraus ? op.reserved : gate_rows(op.kind);
   };
   bool any = false;
   for (int i = 0; i < n_ops; ++i)
-    any = any || is_gate2(program[i].kind) || is_fit(program[i].kind) || (program[i].kind == qiddm::kMixKraus && program[i].reserved > 1);
+    any = any || is_gate2(program[i].kind) || is_fit(program[i].kind) || program[i].kind == qiddm::kMixKraus2 ||
+          (program[i].kind == qiddm::kMixKraus && program[i].reserved > 1);
   if (!any) return QIDDM_OK;
   std::vector<int> gated;
   for (int i = 0; i < n_ops; ++i) {
@@ -285,13 +287,13 @@ int check_obs_tail(int32_t n, const qiddm_mixed_op_t* program, int32_t n_ops, in
 
 // kind, wire and target / second wire of op i: all the planner reads of an op, and the first thing the validator checks
 // of it.  QIDDM_MIX_SHOTS is checked here in full (position, wire / reserved, shots, seed, offset): it indexes no operand.
-// `traj`: the trajectory engine's kinds -- QIDDM_MIX_KRAUS is an op, the superoperator kinds and SHOTS are refused.
+// `traj`: the trajectory engine's kinds -- QIDDM_MIX_KRAUS and QIDDM_MIX_KRAUS2 are ops, the superoperator kinds and SHOTS are refused.
 int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops, bool traj = false) {
   if (traj) {
     if (base_kind(op.kind) == qiddm::kMixChannel || base_kind(op.kind) == qiddm::kMixChannel2)
       return fail(QIDDM_ERR_UNSUPPORTED,
                   "op %d: kind %d is a channel given by its superoperator; a trajectory draws Kraus operators: hand a "
-                  "one-wire channel over as QIDDM_MIX_KRAUS, or run the program on qiddm_mixed_forward / "
+                  "one-wire channel over as QIDDM_MIX_KRAUS and a two-wire channel as QIDDM_MIX_KRAUS2, or run the program on qiddm_mixed_forward / "
                   "qiddm_mixed_wide_forward", i, op.kind);
     if (op.kind == qiddm::kMixShots)
       return fail(QIDDM_ERR_UNSUPPORTED,
@@ -300,6 +302,12 @@ int check_op_wires(int32_t n, const qiddm_mixed_op_t& op, int i, int32_t n_ops, 
   }
   if (traj && op.kind == qiddm::kMixKraus) {
     if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
+    return QIDDM_OK;
+  }
+  if (traj && op.kind == qiddm::kMixKraus2) {  // GATE2's wires
+    if (op.wire < 0 || op.wire >= n) return fail(QIDDM_ERR_INVALID, "op %d: wire %d out of range", i, op.wire);
+    if (op.reserved < 0 || op.reserved >= n || op.reserved == op.wire)
+      return fail(QIDDM_ERR_INVALID, "op %d: bad second wire %d", i, op.reserved);
     return QIDDM_OK;
   }
   if ((op.kind < qiddm::kMixZero || op.kind > qiddm::kMixDepol) && base_kind(op.kind) != qiddm::kMixChannel &&
@@ -390,6 +398,14 @@ int check_call(MixedCall& c, const Engine& e, bool* embeds) {
         if (op.a < 0 || (int64_t)op.a + op.reserved > c.n_gates)
           return fail(QIDDM_ERR_INVALID, "op %d: Kraus rows %d..%d out of range", i, op.a, (int)((int64_t)op.a + op.reserved - 1));
         break;
+      case qiddm::kMixKraus2: {  // (the trajectory engine only) `p` = m operators, four rows of gates each
+        if (!(op.p >= 1.0 && op.p <= (double)qiddm::kTrajMaxKraus2) || op.p != std::floor(op.p))  // NaN fails
+          return fail(QIDDM_ERR_INVALID, "op %d: %g Kraus operators (1 .. %d are taken)", i, op.p, qiddm::kTrajMaxKraus2);
+        const int64_t end = (int64_t)op.a + 4 * (int64_t)op.p;  // one past the last row
+        if (op.a < 0 || end > c.n_gates)
+          return fail(QIDDM_ERR_INVALID, "op %d: Kraus rows %d..%lld out of range", i, op.a, (long long)(end - 1));
+        break;
+      }
       case qiddm::kMixAmpEmbed:
         if (!c.features || c.n_features < 1 || c.n_features > d)
           return fail(QIDDM_ERR_INVALID, "Features must be of length %lld or smaller; got length %d.", (long long)d, c.n_features);
@@ -1225,6 +1241,12 @@ TrajGeometry traj_geometry(int32_t n, int32_t dtype, int64_t batch, int64_t n_tr
   return g;
 }
 
+inline bool has_kraus2(const qiddm_mixed_op_t* program, int32_t n_ops) {
+  for (int i = 0; i < n_ops; ++i)
+    if (program[i].kind == qiddm::kMixKraus2) return true;
+  return false;
+}
+
 int check_traj_count(int32_t n_traj) {
   if (n_traj < 1 || n_traj > qiddm::kTrajMaxTraj)
     return fail(QIDDM_ERR_INVALID, "n_traj %d outside 1 .. 2^20", n_traj);
@@ -1285,10 +1307,13 @@ int qiddm_mixed_traj_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_
   double* acc = reinterpret_cast<double*>(ws + g.off_acc);
   rc = for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    return launch<qiddm::mixed_traj_kernel<T>>(kMaxLds - 4096 /* the kernel also has 2.5 KiB of static LDS */,
-                                               dim3((unsigned)g.blocks), dim3(256), smem, st, "mixed_traj_kernel", prog,
-                                               angle_rows, features, gates, acc,
-                                               reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), per_traj, branches, m, tr);
+    const auto run = [&](auto k2) {  // the kernel with the two-wire Kraus op only for a program that holds one
+      return launch<qiddm::mixed_traj_kernel<T, decltype(k2)::value>>(
+          kMaxLds - 4096 /* the kernel also has 2.5 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
+          "mixed_traj_kernel", prog, angle_rows, features, gates, acc, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs),
+          per_traj, branches, m, tr);
+    };
+    return has_kraus2(program, c.n_body()) ? run(std::true_type{}) : run(std::false_type{});
   });
   if (rc != QIDDM_OK) return rc;
   const int64_t elems = batch * c.width();
@@ -1411,11 +1436,14 @@ int qiddm_mixed_traj_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
   double* acc = reinterpret_cast<double*>(ws + g.off_acc);
   rc = for_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    return launch<qiddm::mixed_traj_backward_kernel<T>>(
-        kMaxLds - 4096 /* the kernel also has 3 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
-        "mixed_traj_backward_kernel", prog, angle_rows, features, gates, grad_out, acc,
-        reinterpret_cast<double*>(ws + g.off_rows), ws + g.off_snaps, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs),
-        per_traj_grad, branches, m, tr, b);
+    const auto run = [&](auto k2) {  // as the forward: programs without the two-wire Kraus op run the kernel that knows none
+      return launch<qiddm::mixed_traj_backward_kernel<T, decltype(k2)::value>>(
+          kMaxLds - 4096 /* the kernel also has 3 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
+          "mixed_traj_backward_kernel", prog, angle_rows, features, gates, grad_out, acc,
+          reinterpret_cast<double*>(ws + g.off_rows), ws + g.off_snaps, reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs),
+          per_traj_grad, branches, m, tr, b);
+    };
+    return has_kraus2(program, c.n_body()) ? run(std::true_type{}) : run(std::false_type{});
   });
   if (rc != QIDDM_OK || g.gwidth == 0) return rc;
   const int64_t elems = batch * g.gwidth;

@@ -17,7 +17,10 @@
 //   n_traj.  No float atomics anywhere: reruns and any grid give the same bits.
 //   Every element of an accumulator row is owned by one thread for all trajectories of the item (element k by thread
 //   k mod 256, <Z_w> by thread w, a table column by the thread of its first term).
-// Sums over psi (the reduced matrix of a wire, the read-outs): float64 per-thread partials in ascending index, a wave
+// A two-wire channel given by its Kraus operators (kMixKraus2) is one channel op as well: traj_channel2 draws among up to
+// sixteen 4 x 4 operators from the reduced matrix of the pair (two sweeps over psi: a read for the matrix, a read and a
+// write for the apply).  The kernels are templates on K2, whether the program holds such an op: see traj_is_channel1.
+// Sums over psi (the reduced matrix of a wire or a pair, the read-outs): float64 per-thread partials in ascending index, a wave
 // butterfly, four partials in LDS added in wave order -- the shots kernel's reduction.
 #pragma once
 #include "qsim_mixed.h"
@@ -27,6 +30,9 @@ namespace qiddm {
 
 constexpr int kMixKraus = 40;       // general one-wire channel by its Kraus operators: gates[a .. a + wire2), wire2 = 1 .. 8
 constexpr int kTrajMaxKraus = 8;    // ThermalRelaxationError has six
+constexpr int kMixKraus2 = 48;      // general two-wire channel by its Kraus operators on (wire, wire2): p = m = 1 .. 16 of them,
+                                    // operator k in gates[a + 4k .. a + 4k + 3] (GATE2's layout, one matrix after another)
+constexpr int kTrajMaxKraus2 = 16;  // two-wire depolarizing has sixteen; a Choi matrix of 16 x 16 never needs more
 constexpr int kTrajMaxSlots = 64;   // S = min(n_traj, 64)
 constexpr int kTrajMaxTraj = 1 << 20;
 
@@ -36,9 +42,13 @@ struct TrajScalars {
   int32_t slab_in_lds;
 };
 
-__host__ __device__ constexpr bool traj_is_channel(int kind) {
+// the one-wire channel ops, and every channel op.  The kernels exist twice: K2 = false is the kernel that knows no two-wire
+// Kraus op -- the device code of every program without one, to the instruction what it was before the op existed -- and
+// K2 = true carries it; the host launches K2 = true only for a program that holds a kMixKraus2.
+__host__ __device__ constexpr bool traj_is_channel1(int kind) {
   return kind == kMixPhaseDamp || kind == kMixAmpDamp || kind == kMixDepol || kind == kMixKraus;
 }
+__host__ __device__ constexpr bool traj_is_channel(int kind) { return traj_is_channel1(kind) || kind == kMixKraus2; }
 
 __device__ __forceinline__ uint32_t traj_insert_bit(uint32_t t, int q) {
   return ((t >> q) << (q + 1)) | (t & ((1u << q) - 1u));
@@ -201,6 +211,132 @@ __device__ __forceinline__ int traj_channel(V2<T>* psi, const MixedOp& op, const
   return chosen;
 }
 
+// ---- the two-wire Kraus op (kMixKraus2) ----------------------------------------------------------------------------------
+// The reduced matrix of the pair at bits (q, q2), unnormalised, over the quadruples a_0 .. a_3 of psi (index 2 b(q) + b(q2)):
+// R[r][c] = sum a_r conj(a_c), r <= c.  r[0 .. 3] the diagonal; the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) follow as (re, im).
+template <typename T>
+__device__ __forceinline__ void traj_pair_rho(const V2<T>* psi, uint32_t quarter, int q, int q2, double* s_red, double (&r)[16]) {
+  const int qlo = q < q2 ? q : q2, qhi = q < q2 ? q2 : q;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) r[j] = 0.0;
+  for (uint32_t t = threadIdx.x; t < quarter; t += 256) {
+    const uint32_t base = insert_two_bits(t, qlo, qhi);
+    const V2<T> a[4] = {psi[base], psi[base | (1u << q2)], psi[base | (1u << q)], psi[base | (1u << q) | (1u << q2)]};
+    double x[4], y[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[j] = (double)a[j].x;
+      y[j] = (double)a[j].y;
+      r[j] += x[j] * x[j] + y[j] * y[j];
+    }
+    int at = 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int c = j + 1; c < 4; ++c) {
+        r[at] += x[j] * x[c] + y[j] * y[c];
+        r[at + 1] += y[j] * x[c] - x[j] * y[c];
+        at += 2;
+      }
+  }
+  traj_block_sum<16>(r, s_red);
+}
+
+// w = max(0, Tr(K R K^H)) = sum_r G[r][r] R[r][r] + 2 Re sum_{r<c} G[c][r] R[r][c], G = K^H K; g: the operator's four gate rows
+__device__ __forceinline__ double traj_kraus2_weight(const double* __restrict__ g, const double (&r)[16]) {
+  double w = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double d = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d += g[(4 * i + j) * 2] * g[(4 * i + j) * 2] + g[(4 * i + j) * 2 + 1] * g[(4 * i + j) * 2 + 1];
+    w += d * r[j];
+  }
+  int at = 4;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int c = j + 1; c < 4; ++c) {
+      double gre = 0.0, gim = 0.0;  // G[c][j] = sum_i conj(K[i][c]) K[i][j]
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const double cx = g[(4 * i + c) * 2], cy = g[(4 * i + c) * 2 + 1], jx = g[(4 * i + j) * 2], jy = g[(4 * i + j) * 2 + 1];
+        gre += cx * jx + cy * jy;
+        gim += cx * jy - cy * jx;
+      }
+      w += 2.0 * (gre * r[at] - gim * r[at + 1]);
+      at += 2;
+    }
+  return fmax(w, 0.0);
+}
+
+// A = K_chosen / sqrt(w): formed in float64, rounded once to T, uniform like mixed_unitary2's.  The forward applies it and
+// the reverse sweep rebuilds it from (gate rows, chosen, w) by this code: the same values.
+template <typename T>
+__device__ __forceinline__ MixedU2<T> traj_kraus2_matrix(const double* __restrict__ gates, int a, int chosen, double w) {
+  const double* __restrict__ g = gates + ((size_t)a + 4 * (size_t)chosen) * 8;
+  const double s = 1.0 / sqrt(w);
+  MixedU2<T> u;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      u.u[r][c] = V2<T>{mixed_uniform((T)(g[(r * 4 + c) * 2] * s)), mixed_uniform((T)(g[(r * 4 + c) * 2 + 1] * s))};
+  return u;
+}
+
+struct TrajNoRecord2 {
+  __device__ __forceinline__ void operator()(int, double) const {}
+};
+
+// One two-wire Kraus op of one trajectory; traj_channel's contract.  The weights do not stay in registers (sixteen of them
+// and their running sums would be 64): thread k < m computes w_k into LDS, every thread adds them from there in ascending
+// k.  psi is swept twice: a read for R, a read and a write for the apply.  `record(chosen, w)` is called before psi changes.
+template <typename T, typename R = TrajNoRecord2>
+__device__ __forceinline__ int traj_channel2(V2<T>* psi, const MixedOp& op, const double* __restrict__ gates,
+                                             const MixedScalars& m, const TrajScalars& tr, int64_t sample, uint32_t t,
+                                             uint32_t d, double* s_red, R&& record = R{}) {
+  using C = V2<T>;
+  __shared__ double s_weight[kTrajMaxKraus2];
+  const int tid = threadIdx.x;
+  const int q = m.n - 1 - op.wire, q2 = m.n - 1 - op.wire2;
+  const int qlo = q < q2 ? q : q2, qhi = q < q2 ? q2 : q;
+  const uint32_t quarter = 1u << (m.n - 2);
+  const int count = (int)op.p;
+  {
+    double r[16];
+    traj_pair_rho<T>(psi, quarter, q, q2, s_red, r);
+    if (tid < count) s_weight[tid] = traj_kraus2_weight(gates + ((size_t)op.a + 4 * (size_t)tid) * 8, r);
+  }
+  __syncthreads();
+  double total = 0.0;  // W = c_{count - 1}
+  for (int k = 0; k < count; ++k) total += s_weight[k];
+  if (!(total > 0.0) || !isfinite(total)) return -1;
+  uint32_t c0 = d >> 2, c1 = t, c2 = (uint32_t)sample, c3 = tr.offset;
+  philox4x32_10(c0, c1, c2, c3, tr.seed_lo, tr.seed_hi);
+  const uint32_t word = (d & 3u) == 0 ? c0 : (d & 3u) == 1 ? c1 : (d & 3u) == 2 ? c2 : c3;
+  const double v = ((double)word * 2.3283064365386963e-10) * total;  // 2^-32: the first product is exact
+  int chosen = 0;
+  double cum = 0.0;  // c_k, the same sequential sums as `total`
+  for (int k = 0; k < count; ++k) {
+    cum += s_weight[k];
+    chosen += cum <= v ? 1 : 0;
+  }
+  chosen = chosen < count - 1 ? chosen : count - 1;
+  const double wk = s_weight[chosen];
+  const MixedU2<T> u = traj_kraus2_matrix<T>(gates, op.a, chosen, wk);
+  record(chosen, wk);
+  for (uint32_t i = tid; i < quarter; i += 256) {  // GATE2's sweep
+    const uint32_t base = insert_two_bits(i, qlo, qhi);
+    const uint32_t at[4] = {base, base | (1u << q2), base | (1u << q), base | (1u << q) | (1u << q2)};
+    const C a[4] = {psi[at[0]], psi[at[1]], psi[at[2]], psi[at[3]]};
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      psi[at[r]] = (cmul<T>(u.u[r][0], a[0]) + cmul<T>(u.u[r][1], a[1])) + (cmul<T>(u.u[r][2], a[2]) + cmul<T>(u.u[r][3], a[3]));
+  }
+  return chosen;
+}
+
 // a unitary op or a state preparation on psi; the caller's barrier follows
 template <typename T>
 __device__ __forceinline__ void traj_apply_op(V2<T>* psi, const MixedOp& op, const double* __restrict__ angle_rows,
@@ -327,7 +463,7 @@ __device__ __forceinline__ void traj_read_out(const V2<T>* psi, const MixedOp* _
 
 // grid: any number of workgroups up to batch * n_slots; they stride the work items.  acc: (batch, n_slots, width) float64.
 // per_traj (batch, n_traj, width) float64 and branches (batch, n_traj, n_channels) int32 may be NULL.
-template <typename T>
+template <typename T, bool K2>
 __global__ __launch_bounds__(256) void mixed_traj_kernel(const MixedOp* __restrict__ prog,
                                                          const double* __restrict__ angle_rows,
                                                          const double* __restrict__ feats,
@@ -352,10 +488,14 @@ __global__ __launch_bounds__(256) void mixed_traj_kernel(const MixedOp* __restri
       bool bad = false;
       for (int oi = 0; oi < m.n_ops; ++oi) {
         const MixedOp op = prog[oi];
-        if (traj_is_channel(op.kind)) {
+        if (K2 ? traj_is_channel(op.kind) : traj_is_channel1(op.kind)) {
           int chosen = -1;
           if (!bad) {
-            chosen = traj_channel<T>(psi, op, angle_rows, gates, m, tr, sample, (uint32_t)t, d, s_red);
+            if (K2 && op.kind == kMixKraus2) {
+              if constexpr (K2) chosen = traj_channel2<T>(psi, op, gates, m, tr, sample, (uint32_t)t, d, s_red);
+            } else {
+              chosen = traj_channel<T>(psi, op, angle_rows, gates, m, tr, sample, (uint32_t)t, d, s_red);
+            }
             bad = chosen < 0;
           }
           if (branches && tid == 0) branches[traj * tr.n_channels + d] = chosen;

@@ -23,6 +23,9 @@
 //              unitary ops and the snapshot for channel ops (Kraus operators are singular in general).
 //              Every one-wire op reduces W_ab = sum over the wire's pairs of conj(lambda_a) psi_{i-1,b}; all its gradients
 //              are real-linear in W: dL/dRe A_ab = 2 Re W_ab, dL/dIm A_ab = -2 Im W_ab.
+//              A two-wire Kraus op (kMixKraus2) walks back in GATE2's case: 32 sums W_rc over the quadruples, psi_{i-1} from
+//              its snapshot, the applied 4 x 4 matrix rebuilt from (gate rows, branch, w_d) by the forward's traj_kraus2_matrix;
+//              rows a + 4 k_d .. a + 4 k_d + 3 get GATE2's entry gradients over sqrt(w_d).
 // psi and lambda live in dynamic LDS while 2 * 2^n elements fit in 128 KiB (n <= 13 in float32, n <= 12 in float64), else
 // in two slabs per workgroup in the workspace; snapshots are always in the workspace.
 // Sums: traj_block_sum (float64 partials in ascending index, a wave butterfly, four partials in wave order); no atomics.
@@ -97,10 +100,11 @@ __device__ __forceinline__ void traj_reverse1(V2<T>* psi, V2<T>* lam, const V2<T
   if (sums) traj_block_sum<8>(w, s_red);
 }
 
-// GATE2 backwards: w[2 (4 r + c)], +1 = Re, Im of W_rc = sum over the quadruples of conj(lambda_r) psi_{i-1,c}
+// A two-wire op backwards (GATE2, KRAUS2): w[2 (4 r + c)], +1 = Re, Im of W_rc = sum over the quadruples of
+// conj(lambda_r) psi_{i-1,c}.  `snap`: psi_{i-1} (KRAUS2: the operator is singular), else psi_{i-1} = U^H psi_i.
 template <typename T>
-__device__ __forceinline__ void traj_reverse2(V2<T>* psi, V2<T>* lam, uint32_t quarter, int q, int q2, const MixedU2<T>& u,
-                                              double (&w)[32], double* s_red) {
+__device__ __forceinline__ void traj_reverse2(V2<T>* psi, V2<T>* lam, const V2<T>* snap, uint32_t quarter, int q, int q2,
+                                              const MixedU2<T>& u, double (&w)[32], double* s_red) {
   using C = V2<T>;
   const int qlo = q < q2 ? q : q2, qhi = q < q2 ? q2 : q;
 #pragma unroll
@@ -113,7 +117,8 @@ __device__ __forceinline__ void traj_reverse2(V2<T>* psi, V2<T>* lam, uint32_t q
     C p[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      p[c] = (cmulc<T>(x[0], u.u[0][c]) + cmulc<T>(x[1], u.u[1][c])) + (cmulc<T>(x[2], u.u[2][c]) + cmulc<T>(x[3], u.u[3][c]));
+      p[c] = snap ? snap[at[c]]
+                  : (cmulc<T>(x[0], u.u[0][c]) + cmulc<T>(x[1], u.u[1][c])) + (cmulc<T>(x[2], u.u[2][c]) + cmulc<T>(x[3], u.u[3][c]));
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -175,7 +180,7 @@ __device__ __forceinline__ void traj_seed(const V2<T>* psi, V2<T>* lam, const do
 // workgroup; snaps: n_channels snapshots of snap_stride bytes per workgroup; slabs: 2 * 2^n elements per workgroup unless
 // psi and lambda are in LDS.  per_traj_grad (batch, n_traj, gwidth) float64 and branches (batch, n_traj, n_channels) int32
 // may be NULL.
-template <typename T>
+template <typename T, bool K2>
 __global__ __launch_bounds__(256) void mixed_traj_backward_kernel(
     const MixedOp* __restrict__ prog, const double* __restrict__ angle_rows, const double* __restrict__ feats,
     const double* __restrict__ gates, const double* __restrict__ grad_out, double* __restrict__ acc,
@@ -206,7 +211,7 @@ __global__ __launch_bounds__(256) void mixed_traj_backward_kernel(
       bool bad = false;
       for (int oi = 0; oi < m.n_ops; ++oi) {
         const MixedOp op = prog[oi];
-        if (traj_is_channel(op.kind)) {
+        if (K2 ? traj_is_channel(op.kind) : traj_is_channel1(op.kind)) {
           int chosen = -1;
           if (!bad) {
             unsigned char* const at = my_snaps + (size_t)d * (size_t)b.snap_stride;
@@ -217,18 +222,28 @@ __global__ __launch_bounds__(256) void mixed_traj_backward_kernel(
             // could apply X / Y / Z of a DEPOL decision (no reduction, so no barrier of its own) to elements another wave
             // has yet to copy
             __syncthreads();
-            chosen = traj_channel<T>(psi, op, angle_rows, gates, m, tr, sample, (uint32_t)t, d, s_red,
-                                     [&](int k, const MixedU<T>& u, double w, double strength) {
-                                       if (tid == 0) {
-                                         rec->u[0] = (double)u.u00.x; rec->u[1] = (double)u.u00.y;
-                                         rec->u[2] = (double)u.u01.x; rec->u[3] = (double)u.u01.y;
-                                         rec->u[4] = (double)u.u10.x; rec->u[5] = (double)u.u10.y;
-                                         rec->u[6] = (double)u.u11.x; rec->u[7] = (double)u.u11.y;
-                                         rec->w = w;
-                                         rec->strength = strength;
-                                         rec->chosen = k;
-                                       }
-                                     });
+            if (K2 && op.kind == kMixKraus2) {  // the record keeps (chosen, w): the walk back rebuilds the 4 x 4 matrix from them
+              if constexpr (K2)
+                chosen = traj_channel2<T>(psi, op, gates, m, tr, sample, (uint32_t)t, d, s_red, [&](int k, double w) {
+                  if (tid == 0) {
+                    rec->w = w;
+                    rec->strength = 0.0;
+                    rec->chosen = k;
+                  }
+                });
+            } else
+              chosen = traj_channel<T>(psi, op, angle_rows, gates, m, tr, sample, (uint32_t)t, d, s_red,
+                                       [&](int k, const MixedU<T>& u, double w, double strength) {
+                                         if (tid == 0) {
+                                           rec->u[0] = (double)u.u00.x; rec->u[1] = (double)u.u00.y;
+                                           rec->u[2] = (double)u.u01.x; rec->u[3] = (double)u.u01.y;
+                                           rec->u[4] = (double)u.u10.x; rec->u[5] = (double)u.u10.y;
+                                           rec->u[6] = (double)u.u11.x; rec->u[7] = (double)u.u11.y;
+                                           rec->w = w;
+                                           rec->strength = strength;
+                                           rec->chosen = k;
+                                         }
+                                       });
             bad = chosen < 0;
           }
           if (branches && tid == 0) branches[traj * tr.n_channels + d] = chosen;
@@ -246,7 +261,8 @@ __global__ __launch_bounds__(256) void mixed_traj_backward_kernel(
         for (int oi = m.n_ops - 1; oi >= 0; --oi) {
           const MixedOp op = prog[oi];
           const int q = n - 1 - op.wire;
-          switch (op.kind) {
+          const bool kraus2 = K2 && op.kind == kMixKraus2;  // walked back in GATE2's case
+          switch (kraus2 ? (int)kMixGate2 : op.kind) {
             case kMixPhase: {  // RZ: dA = diag(-i/2 dn, +i/2 up): 2 Re(dA_00 W_00 + dA_11 W_11) = Im(dn W_00) - Im(up W_11)
               double sn, cs;
               sincos(0.5 * mixed_angle(op, angle_rows, m, sample), &sn, &cs);
@@ -277,13 +293,30 @@ __global__ __launch_bounds__(256) void mixed_traj_backward_kernel(
               }
               break;
             }
-            case kMixGate2: {
+            case kMixGate2: {  // one sweep for both: KRAUS2 is GATE2 with A = K_k / sqrt(w_d) and psi_{i-1} from the snapshot
+              const C* snap = nullptr;
+              size_t row = (size_t)op.a;
+              double s = 2.0;
+              MixedU2<T> u;
+              if (kraus2) {
+                --d;
+                const unsigned char* const at = my_snaps + (size_t)d * (size_t)b.snap_stride;
+                const TrajDecision* const rec = reinterpret_cast<const TrajDecision*>(at + ((size_t)D * sizeof(C)));
+                const int chosen = rec->chosen;
+                const double wd = rec->w;
+                snap = reinterpret_cast<const C*>(at);
+                u = traj_kraus2_matrix<T>(gates, op.a, chosen, wd);
+                row += 4 * (size_t)chosen;  // the chosen operator's rows; the op's other rows keep their zeros
+                s = 2.0 / sqrt(wd);
+              } else {
+                u = mixed_unitary2<T>(op, gates);
+              }
               double w[32];
-              traj_reverse2<T>(psi, lam, D >> 2, q, n - 1 - op.wire2, mixed_unitary2<T>(op, gates), w, s_red);
+              traj_reverse2<T>(psi, lam, snap, D >> 2, q, n - 1 - op.wire2, u, w, s_red);
               if (tid == 0) {
-                double* __restrict__ go = tg + off_gates + (size_t)op.a * 8;
+                double* __restrict__ go = tg + off_gates + row * 8;
 #pragma unroll
-                for (int j = 0; j < 32; ++j) go[j] += (j & 1) ? -2.0 * w[j] : 2.0 * w[j];
+                for (int j = 0; j < 32; ++j) go[j] += (j & 1) ? -s * w[j] : s * w[j];
               }
               break;
             }

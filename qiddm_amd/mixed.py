@@ -117,13 +117,24 @@ execution as a sampled one does, and is forward only by default: a parameter tha
 ``qml.QuantumFunctionError``, stream capture ``RuntimeError``, two-wire channels, ``shots`` on the same device and the
 read-outs of rho ``NotImplementedError``, each before an offset is taken.
 
+``set_trajectory_channel2(True)`` / ``with trajectory_channel2():`` admits the two-wire channels of the density-matrix
+engines -- ``qml.QubitChannel`` with 4 x 4 operators, ``qml.PauliError("XZ", p, wires=[a, b])`` -- on a trajectories
+device: each lowers to one ``QIDDM_MIX_KRAUS2`` op (``_Lowering.kraus2``; ``kraus_rows(operators, wires=2)``: four gate
+rows per operator, at most sixteen operators, more reduced through the 16 x 16 Choi matrix; identical sets join the gates
+once), one decision among its operators from the pair's reduced 4 x 4 matrix.  Off by default, because the refusal is part
+of the tested surface; off, the ``NotImplementedError`` also says how to turn the op on.  Still refused with the switch on:
+three-wire channels, per-sample parameters of such a channel, a two-wire channel whose own parameter requires grad (by
+name, as for the one-wire ones: its rows are built on the host), ``shots``, the read-outs of rho and stream capture.  Not
+measured: the 16-wire nets with such a noise model end to end.
+
 ``set_trajectory_grad(True)`` / ``with trajectory_grad():`` turns its reverse sweep on (``_TrajFunction``,
 ``qiddm_mixed_traj_backward``, include/qiddm_hip_traj_grad.h): the backward replays the forward's trajectories from the same
 (T, seed, offset), differentiates each one as a linear chain with its branches and normalisers frozen, and returns the
 mean -- an unbiased estimate of the density-matrix gradient.  Everything that reaches the program as angle rows, gate rows
 or features trains (embedding inputs, SEL weights, RX / Rot / RZ / RY angles, controlled rotations, Ising gates,
 ``QubitUnitary`` tensors) and so do the strengths of the three native channels; a parameter that requires grad in a
-channel lowered to ``QIDDM_MIX_KRAUS`` (its rows are built on the host) is still refused, by name.
+channel lowered to ``QIDDM_MIX_KRAUS`` or ``QIDDM_MIX_KRAUS2`` (its rows are built on the host) is still refused, by
+name; gradients of everything else flow through a two-wire Kraus op as through a one-wire one.
 """
 from __future__ import annotations
 
@@ -181,12 +192,14 @@ def _thermal_super(pe, t1, t2, tg):
 
 
 def _kraus_of_super(s):
-    """A Kraus set of the superoperator `s` from the eigen-decomposition of its Choi matrix."""
-    choi = s.reshape(2, 2, 2, 2).transpose(0, 2, 1, 3).reshape(4, 4)  # [(a, c), (b, d)] = S[(a, b), (c, d)]
+    """A Kraus set of the superoperator `s` (4 x 4: one wire, 16 x 16: two) from the eigen-decomposition of its Choi
+    matrix: at most d^2 operators of d x d, d = 2 or 4."""
+    d = math.isqrt(s.shape[0])
+    choi = s.reshape(d, d, d, d).transpose(0, 2, 1, 3).reshape(d * d, d * d)  # [(a, c), (b, d)] = S[(a, b), (c, d)]
     lam, vec = np.linalg.eigh(choi)
     if lam.min() < -1e-12:
         raise ValueError(f"the map is not completely positive (Choi eigenvalue {lam.min():.3e})")
-    return [math.sqrt(max(l, 0.0)) * vec[:, k].reshape(2, 2) for k, l in enumerate(lam) if l > 1e-15]
+    return [math.sqrt(max(l, 0.0)) * vec[:, k].reshape(d, d) for k, l in enumerate(lam) if l > 1e-15]
 
 
 def channel_kraus(name, *params):
@@ -278,15 +291,18 @@ def channel_rows(name, *params):
     return superoperator(kraus, wires=2 if kraus[0].shape[0] == 4 else 1)
 
 
-def kraus_rows(operators):
+def kraus_rows(operators, wires=1):
     """``(m, 8)`` float64 (CPU) rows of m one-wire Kraus operators, row k = K_k as (k00, k01, k10, k11) in (re, im): what
     ``QIDDM_MIX_KRAUS`` reads.  More than ``MIX_MAX_KRAUS`` operators are replaced by a Kraus set of the same map (at
-    most four, from the Choi matrix)."""
-    ks = _matrices(operators)
-    if len(ks) > _capi.MIX_MAX_KRAUS:
+    most four, from the Choi matrix).  ``wires=2``: m operators of 4 x 4 (index 2 b_1 + b_2, the first wire most
+    significant) -> the ``(4m, 8)`` rows ``QIDDM_MIX_KRAUS2`` reads, operator k in rows 4k .. 4k+3, row r = K_k[r][0..3]
+    (``MIX_GATE2``'s layout, one matrix after another); more than ``MIX_MAX_KRAUS2`` operators are replaced by at most
+    sixteen of the same map, from the 16 x 16 Choi matrix."""
+    ks = _matrices(operators, wires)
+    if len(ks) > (_capi.MIX_MAX_KRAUS2 if wires == 2 else _capi.MIX_MAX_KRAUS):
         ks = _kraus_of_super(sum(np.kron(k, k.conj()) for k in ks))
-    flat = np.stack(ks).reshape(len(ks), 4)
-    out = np.empty((len(ks), 8), dtype=np.float64)
+    flat = np.stack(ks).reshape(-1, 4)
+    out = np.empty((flat.shape[0], 8), dtype=np.float64)
     out[:, 0::2], out[:, 1::2] = flat.real, flat.imag
     return torch.from_numpy(out)
 
@@ -488,6 +504,32 @@ def trajectory_grad(on: bool = True):
         set_trajectory_grad(before)
 
 
+# whether a trajectories device draws two-wire channels (``QIDDM_MIX_KRAUS2``); off: the refusal it always gave
+_trajectory_channel2 = False
+
+
+def set_trajectory_channel2(on: bool) -> None:
+    """Let ``qml.device("default.mixed", ..., trajectories=T)`` take two-wire channels (``QubitChannel`` with 4 x 4
+    operators, ``PauliError`` with a two-letter word): each becomes one ``QIDDM_MIX_KRAUS2`` op, one decision among its
+    at most sixteen Kraus operators from the pair's reduced matrix (include/qiddm_hip_traj.h).  Off by default: such a
+    channel then raises ``NotImplementedError`` as before."""
+    global _trajectory_channel2
+    if not isinstance(on, bool):
+        raise ValueError(f"set_trajectory_channel2 takes True or False (got {on!r})")
+    _trajectory_channel2 = on
+
+
+@contextlib.contextmanager
+def trajectory_channel2(on: bool = True):
+    """``with mixed.trajectory_channel2(): ...`` -- ``set_trajectory_channel2`` for the duration of a block."""
+    before = _trajectory_channel2
+    set_trajectory_channel2(on)
+    try:
+        yield
+    finally:
+        set_trajectory_channel2(before)
+
+
 def rot_matrices(weights: torch.Tensor) -> torch.Tensor:
     """(..., 3) Rot angles -> (G, 8) float64 rows (u00, u01, u10, u11) as (re, im); Rot = RZ(omega) RY(theta) RZ(phi).
     Differentiable."""
@@ -656,6 +698,17 @@ class _Lowering:
         if base is None:
             base = self.channel_base[key] = self._add_gates(rows)
         self.ops.append((_capi.MIX_KRAUS, wire, base, 0.0, 1.0, rows.shape[0]))
+
+    def kraus2(self, operators, wire, second):
+        """A two-wire channel of a trajectories device: its m <= 16 Kraus operators join the gates, four rows each
+        (GATE2's layout), `a` is the first row, `p` holds m and the op's fourth field the second wire.  Operators equal
+        (bit for bit) to an earlier channel's join once: a noise model puts the same set behind every entangler."""
+        rows = kraus_rows(operators, wires=2)
+        key = rows.numpy().tobytes()
+        base = self.channel_base.get(key)
+        if base is None:
+            base = self.channel_base[key] = self._add_gates(rows)
+        self.ops.append((_capi.MIX_KRAUS2, wire, base, float(rows.shape[0] // 4), 1.0, second))
 
     def channel_fit(self, op, wires):
         """A general channel whose rows get a gradient, on each of `wires` (one wire, or one pair).  `op`: the recorded op,
@@ -940,9 +993,14 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0, traj=Fa
                     low.gate1(rows, t.wires[0])
             elif traj and t.hyper.get("channel"):
                 if len(t.wires) == 2:
-                    raise NotImplementedError(f"{t.name} on two wires on a trajectories device: only one-wire channels "
-                                              "are drawn; use default.mixed without trajectories (up to 10 wires)")
-                low.kraus(_traj_operators(t), t.wires[0])
+                    if not _trajectory_channel2:
+                        raise NotImplementedError(
+                            f"{t.name} on two wires on a trajectories device: only one-wire channels "
+                            "are drawn; use default.mixed without trajectories (up to 10 wires), or turn the two-wire "
+                            "Kraus op on (mixed.set_trajectory_channel2(True) or `with mixed.trajectory_channel2():`)")
+                    low.kraus2(_traj_operators(t), t.wires[0], t.wires[1])
+                else:
+                    low.kraus(_traj_operators(t), t.wires[0])
             elif "trainable" in t.hyper:  # a general channel with a parameter that requires grad, in grad mode
                 low.channel_fit(t, [t.wires] if len(t.wires) == 2 else [t.wires[0]])
             elif "superoperator" in t.hyper:
@@ -1063,7 +1121,8 @@ class _Launch:
         out = torch.empty(batch, width, dtype=torch.float64, device=self.device)
         per_traj = branches = None
         if diagnostics:
-            n_channels = sum(op.kind in (_capi.MIX_PHASE_DAMP, _capi.MIX_AMP_DAMP, _capi.MIX_DEPOL, _capi.MIX_KRAUS)
+            n_channels = sum(op.kind in (_capi.MIX_PHASE_DAMP, _capi.MIX_AMP_DAMP, _capi.MIX_DEPOL, _capi.MIX_KRAUS,
+                                         _capi.MIX_KRAUS2)
                              for op in self.prog)
             per_traj = torch.empty(batch, n_traj, width, dtype=torch.float64, device=self.device)
             branches = torch.empty(batch, n_traj, n_channels, dtype=torch.int32, device=self.device)
@@ -1088,7 +1147,8 @@ class _Launch:
         g_feats = torch.empty(batch, n_feats, **f64) if feats is not None else None
         per_traj = branches = None
         if diagnostics:
-            n_channels = sum(op.kind in (_capi.MIX_PHASE_DAMP, _capi.MIX_AMP_DAMP, _capi.MIX_DEPOL, _capi.MIX_KRAUS)
+            n_channels = sum(op.kind in (_capi.MIX_PHASE_DAMP, _capi.MIX_AMP_DAMP, _capi.MIX_DEPOL, _capi.MIX_KRAUS,
+                                         _capi.MIX_KRAUS2)
                              for op in self.prog)
             width = self.n_rows + 8 * n_gates + (n_feats if embeds else 0)
             per_traj = torch.empty(batch, n_traj, width, **f64)

@@ -371,8 +371,10 @@ def QubitChannel(K_list, wires):
                 raise ValueError(f"K_list is not trace preserving: sum K^dagger K differs from the identity by {float(dev):.3e}")
             return rows, dev <= 1e-10, explain
     if two:
-        return _general_channel("QubitChannel", w, params, lambda mixed: mixed.qubit_channel_rows(K_list, 2), two_wires=True,
-                                trainable=trainable)
+        op = _general_channel("QubitChannel", w, params, lambda mixed: mixed.qubit_channel_rows(K_list, 2), two_wires=True,
+                              trainable=trainable)
+        op.hyper["kraus"] = K_list  # a trajectories device with the two-wire Kraus op on draws from these
+        return op
     op = _general_channel("QubitChannel", wires, params, lambda mixed: mixed.qubit_channel_rows(K_list), trainable=trainable)
     op.hyper["kraus"] = K_list  # a trajectories device draws from the operators themselves
     return op
@@ -681,7 +683,9 @@ def device(name, wires=1, shots=None, readout_prob=None, seed=None, trajectories
     one-letter ``PauliError``, ``GeneralizedAmplitudeDamping``, ``ResetError``, ``ThermalRelaxationError``, one-wire
     ``QubitChannel``; a float ``readout_prob``) are accepted, and ``probs`` (all wires or a subset), the ``PauliZ`` list and
     ``expval`` of Pauli words and Hamiltonians are measured.  Refused before a stream offset is taken: ``shots`` on the
-    same device and two-wire channels (``NotImplementedError``), ``state`` / ``density_matrix`` / ``purity`` /
+    same device and two-wire channels (``NotImplementedError``; ``mixed.set_trajectory_channel2(True)`` or ``with
+    mixed.trajectory_channel2():`` admits ``QubitChannel`` with 4 x 4 operators and two-letter ``PauliError`` as one
+    decision among at most sixteen Kraus operators), ``state`` / ``density_matrix`` / ``purity`` /
     ``Hermitian`` (``NotImplementedError``), a parameter that requires grad in grad mode (``QuantumFunctionError``;
     ``mixed.set_trajectory_grad(True)`` or ``with mixed.trajectory_grad():`` turns the reverse sweep on, after which
     gates, embeddings and the native channels' strengths train and only the parameters of the other channels are
