@@ -57,9 +57,10 @@ qiddm::KScalars params_of(const qiddm_circuit_t* c) {
 
 // When the instance that carries both bodies (qsim_lean.h: lean_has_solo) runs the one-wavefront-per-item body: from
 // kLeanSoloMinSteps steps per launch on at every batch, below that from kLeanSoloMinItems items (batch x n_steps) on.
-// A solo workgroup stages the phase table in LDS, every wavefront fills its registers from there and loads the weights
-// of the pixels it owns (~6 us for a launch of one item against ~5 us), then a round of eight items per workgroup costs
-// ~7 us whatever the launch holds up to 2 048 items; the four-wave body pays ~2.7 us per step of a sample.  Measured by
+// A solo workgroup stages the phase table in LDS (1 us), every wavefront fills its registers from there, simulates its
+// item (~3.5 us) while linear_up's weights arrive, hands its share of them to LDS and writes its item's row (~1.3 us
+// behind the one wait for the slowest wavefront): ~9 us whatever the launch holds up to 2 048 items, one item per
+// wavefront; the four-wave body pays ~2.7 us per step of a sample.  Measured by
 // tools/ab_lean_solo_threshold.py, float32, P = 784 (profiles/lean_rows/threshold.txt; us per launch, four-wave /
 // solo):
 //   1 step:   256 items 5.8 / 9.8     512 items 7.8 / 9.9    1 024 items 13.3 / 10.2    2 048 items 24.0 / 10.6
@@ -96,7 +97,8 @@ int launch_lean(const double* x, const double* wd, const double* bd, const doubl
     const int64_t items = p.batch * d.n_steps;
     // (the body counts items and waves in 32 bits)
     if (lean_solo_wanted(items, d.n_steps) && items < ((int64_t)1 << 31) && d.out_features <= qiddm::kSoloMaxPixels) {
-      const size_t smem = qiddm::LeanSoloLds::bytes(LPR);
+      static_assert(qiddm::LeanSoloLds::bytes(qiddm::kSoloMaxPixels, LPR) <= kMaxLds, "the largest image fits LDS");
+      const size_t smem = qiddm::LeanSoloLds::bytes(d.out_features, LPR);   // 90 KiB at 784 pixels, 99 KiB at 1 024
       const int64_t want = (items + qiddm::kSoloWaves - 1) / qiddm::kSoloWaves;   // one item per wavefront
       const int64_t cus = lean_cu_count();                                         // one workgroup per CU at most
       const unsigned grid = (unsigned)(want < cus ? want : cus);

@@ -18,86 +18,69 @@
 //     on each other) are spread over all wavefronts of all workgroups, kSoloWaves per CU.  Every item is still
 //     simulated in full.
 // The per-workgroup setup fetches the tables from global memory ONCE and hands them to the eight wavefronts through LDS
-// (one __syncthreads()).  linear_up is split by PIXELS, not by items: a lane owns two neighbouring pixels and keeps their
-// weights in registers for the whole launch; the eight wavefronts meet once per round of eight items (one s_barrier) to
-// exchange the read-outs, 64 bytes per item.  Every wave runs the same code -- one copy of it, and a pixel of every row
-// is computed by the same instructions on the same operands, so every row of a launch is the same bits --; what depends
-// on the wave number is which items it simulates and which pixels it writes.
+// (one __syncthreads()); linear_up's weights and bias follow under the first item's layers and reach LDS behind a second
+// barrier in front of the first tail.  These two are the body's only barriers: there is none per item.  A wavefront is on
+// its own: it simulates an item, broadcasts the eight <Z> from the lanes that hold them and writes that item's WHOLE row, a
+// lane two neighbouring pixels at a time (pair = lane + 64 g), 16 contiguous bytes per lane and store.  With two wavefronts
+// on a SIMD the one that is ahead runs its tail under its partner's layers.  Every wave runs the same code -- one copy of
+// it, and a pixel of every row is computed by the same instructions on the same operands, so every row of a launch is the
+// same bits --; what depends on the wave number is which items it takes.
 #pragma once
 #include "qsim_lean.h"
 
 namespace qiddm {
 
-// LDS of the solo body: the read-outs of a round's eight items [2 parities][kSoloWaves][8] as float64, the tangents
-// [layers][8], the phase entries in the lanes' order.  (linear_up's weights and bias were here too, 57 KiB that every
-// wavefront read in full for every item; they are in the registers of the lanes that own the pixels now, below.)
+// ---- which lane writes which pixels --------------------------------------------------------------------------------------
+// linear_up by pixel pairs: the Q <= 1024 pixels of a row are ceil(Q / 2) pairs (2 pr, 2 pr + 1); lane l of the wavefront
+// that simulated the item takes the pairs l, l + 64, .. -- group g of solo_groups(Q) the pair solo_pair_of(g, l) -- and
+// stores the solo_pair_pixels(Q, pr) pixels of a pair that exist: both (16 bytes), the first one of an odd Q's last pair,
+// or none beyond the row.
+constexpr int kSoloMaxPixels = 1024;
+__host__ __device__ constexpr int solo_pairs(int q) { return (q + 1) / 2; }
+__host__ __device__ constexpr int solo_pairs_padded(int q) { return (solo_pairs(q) + kWave - 1) / kWave * kWave; }
+__host__ __device__ constexpr int solo_groups(int q) { return solo_pairs_padded(q) / kWave; }
+__host__ __device__ constexpr int solo_pair_of(int group, int lane) { return lane + kWave * group; }
+__host__ __device__ constexpr int solo_pair_pixels(int q, int pr) { return q - 2 * pr >= 2 ? 2 : q - 2 * pr == 1 ? 1 : 0; }
+// Every pixel < Q is written by exactly one (group, lane) and no pixel >= Q is written, for every Q in 1 .. 1024: walking
+// the (group, lane) slots in order meets the pairs 0, 1, 2, .. once each (whatever Q is: the map does not depend on it), a
+// slot writes the pixels of its pair that are < Q and no others, and the groups a wavefront walks hold every pair of the
+// row -- the last of them at least one.
+__host__ __device__ constexpr bool solo_pairs_cover() {
+  int next = 0;
+  for (int g = 0; g < solo_groups(kSoloMaxPixels); ++g)
+    for (int l = 0; l < kWave; ++l)
+      if (solo_pair_of(g, l) != next++) return false;
+  for (int q = 1; q <= kSoloMaxPixels; ++q) {
+    const int pairs = solo_pairs(q), groups = solo_groups(q);
+    if (groups * kWave < pairs || (groups - 1) * kWave >= pairs || groups * kWave > next) return false;
+    for (int pr = (groups - 1) * kWave; pr < groups * kWave; ++pr) {   // (the groups before the last hold whole pairs)
+      const int n = solo_pair_pixels(q, pr);
+      if (n != (2 * pr + 1 < q ? 2 : 2 * pr < q ? 1 : 0)) return false;
+    }
+    if ((groups - 1) * kWave * 2 >= q || solo_pair_pixels(q, pairs - 1) != 2 - q % 2 || solo_pair_pixels(q, pairs) != 0) return false;
+  }
+  return true;
+}
+static_assert(solo_pairs_cover(), "pixel pairs: every pixel of every image size has exactly one writer");
+static_assert(solo_groups(784) == 7 && solo_groups(kSoloMaxPixels) == 8, "7 groups for the flagship, 8 at most");
+
+// LDS of the solo body: linear_up's weights as 16-byte units [8][stride] -- unit (u, pr) = the chunk (w[2 k], w[2 k + 1]),
+// k = u & 3, of row 2 pr + (u >> 2): consecutive lanes read consecutive 16 bytes --, its bias as [pairs padded][2], the
+// tangents [layers][8], the phase entries in the lanes' order.  The stride of a unit row is the padded pair count + 2: the
+// setup stores eight units of one pair from eight consecutive threads, and 2 units between rows spread them over all
+// banks.  Pad units and the missing second row of an odd Q's last pair hold finite values that are never stored.
 struct LeanSoloLds {
-  static constexpr size_t kEvBytes = (size_t)2 * kSoloWaves * 8 * sizeof(double);
+  __host__ __device__ static constexpr int w_stride(int q) { return solo_pairs_padded(q) + 2; }
+  __host__ __device__ static constexpr size_t w_bytes(int q) { return (size_t)8 * w_stride(q) * 2 * sizeof(double); }
+  __host__ __device__ static constexpr size_t b_bytes(int q) { return (size_t)solo_pairs_padded(q) * 2 * sizeof(double); }
   __host__ __device__ static constexpr size_t un_bytes(int layers) { return (size_t)layers * 8 * sizeof(float); }
   // the phase entries of the simulated layers 1 .. layers - 1 in the order the lanes take them: [layer][2][64] units of
   // 16 bytes, unit (l, h, lane) = the lane's entries for registers 2 h and 2 h + 1 in the layout layer l starts in
   __host__ __device__ static constexpr size_t ph_bytes(int layers) { return (size_t)(layers - 1) * 256 * 2 * sizeof(float); }
-  __host__ __device__ static constexpr size_t bytes(int layers) { return kEvBytes + un_bytes(layers) + ph_bytes(layers); }
-};
-
-// ---- who writes which pixels ---------------------------------------------------------------------------------------------
-// linear_up by ownership: the Q <= 1024 pixels of a row are ceil(Q / 2) pairs (2 p, 2 p + 1); wavefront w of the workgroup
-// owns solo_pairs_per_wave(Q) consecutive pairs (<= 64), its lane l < that the pair w * per_wave + l.  A lane keeps the
-// two rows of w_up and the two biases of its pair in registers for the whole launch and stores a pair as 16 bytes.
-// A wavefront's share is ceil(pairs / 8) rounded up to whole 64-byte lines (four pairs): with the bare quotient -- 49
-// pairs, 784 bytes at Q = 784 -- neighbouring wavefronts split a 32-byte sector at four of a row's seven seams, and the
-// write-through stores wrote those sectors twice (WRITE_SIZE 24 000 KiB per benchmark launch for 23 520 KiB of
-// images).  The instructions of a wavefront do not depend on how many of its lanes hold a pair, so the uneven split --
-// 7 x 52 + 28 at Q = 784 -- costs nothing.
-constexpr int kSoloMaxPixels = 1024;
-__host__ __device__ constexpr int solo_pairs(int q) { return (q + 1) / 2; }
-__host__ __device__ constexpr int solo_pairs_per_wave(int q) {
-  return ((solo_pairs(q) + kSoloWaves - 1) / kSoloWaves + 3) / 4 * 4;
-}
-// the pair of lane `lane` of wavefront `wave`, or -1: lanes beyond the wavefront's share and pairs beyond the row
-__host__ __device__ constexpr int solo_pair_of(int q, int wave, int lane) {
-  const int per = solo_pairs_per_wave(q), pr = wave * per + lane;
-  return lane < per && pr < solo_pairs(q) ? pr : -1;
-}
-// for every Q in [q_lo, q_hi]: walking the (wavefront, lane) slots in order meets the pairs 0, 1, .. ceil(Q / 2) - 1 once
-// each and nothing else -- every pixel has exactly one owner --, and no owned pixel is >= Q but the second half of an odd
-// Q's last pair
-__host__ __device__ constexpr bool solo_owners_cover(int q_lo, int q_hi) {
-  for (int q = q_lo; q <= q_hi; ++q) {
-    int next = 0;
-    for (int w = 0; w < kSoloWaves; ++w)
-      for (int l = 0; l < kWave; ++l) {
-        const int pr = solo_pair_of(q, w, l);
-        if (pr < 0) continue;
-        if (pr != next || 2 * pr >= q) return false;
-        if (2 * pr + 1 >= q && !(q % 2 == 1 && pr == solo_pairs(q) - 1)) return false;
-        ++next;
-      }
-    if (next != solo_pairs(q)) return false;
+  __host__ __device__ static constexpr size_t bytes(int q, int layers) {
+    return w_bytes(q) + b_bytes(q) + un_bytes(layers) + ph_bytes(layers);
   }
-  return true;
-}
-// (in slices of 64 image sizes: one constant expression has a step limit)
-#define QIDDM_SOLO_OWNERS(lo) static_assert(solo_owners_cover(lo, lo + 63), "pixel ownership, Q = " #lo " .. " #lo " + 63")
-QIDDM_SOLO_OWNERS(1);
-QIDDM_SOLO_OWNERS(65);
-QIDDM_SOLO_OWNERS(129);
-QIDDM_SOLO_OWNERS(193);
-QIDDM_SOLO_OWNERS(257);
-QIDDM_SOLO_OWNERS(321);
-QIDDM_SOLO_OWNERS(385);
-QIDDM_SOLO_OWNERS(449);
-QIDDM_SOLO_OWNERS(513);
-QIDDM_SOLO_OWNERS(577);
-QIDDM_SOLO_OWNERS(641);
-QIDDM_SOLO_OWNERS(705);
-QIDDM_SOLO_OWNERS(769);
-QIDDM_SOLO_OWNERS(833);
-QIDDM_SOLO_OWNERS(897);
-QIDDM_SOLO_OWNERS(961);
-#undef QIDDM_SOLO_OWNERS
-static_assert(961 + 63 == kSoloMaxPixels, "the slices end at the largest image");
-static_assert(solo_pairs_per_wave(kSoloMaxPixels) == kWave && solo_pairs_per_wave(784) == 52, "a wavefront's share fits its lanes");
+};
 
 // 1: a pair in a 16-byte aligned row leaves as one write-through store (`buffer_store_dwordx4 ... sc1`): the image goes
 // to memory while the launch runs instead of staying dirty in the L2s until the kernel boundary.  0 (A/B builds only):
@@ -240,11 +223,8 @@ __device__ __forceinline__ void solo_layer(int layout, V2<float> (&a)[4], const 
 
 // The body of dense_lean_kernel<float, 8, PPT, false, LPR, false> at kSoloThreads threads per workgroup.
 // Items: (sample, step) = item / n_steps, item % n_steps for item < batch * n_steps; wave g of the launch takes items
-// g, g + (waves of the launch), ...: every item is simulated exactly once, no wave idles while another has two to do.
-// Round r of workgroup b is the eight consecutive items (r * gridDim.x + b) * 8 + w of its wavefronts w: each simulates
-// its own and leaves the eight <Z> in LDS, one s_barrier, and every wavefront writes ITS pixels (above) of all eight
-// rows.  The read-outs alternate between two slots of LDS by the round's parity, so one barrier per round is enough: a
-// wavefront writes round r + 1's only behind the barrier of round r, and reads round r's only behind that barrier too.
+// g, g + (waves of the launch), ...: every item is simulated and written exactly once, by one wavefront, and no wave
+// idles while another has two to do.
 template <int LPR>
 __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double* __restrict__ bu,
                                                      double* __restrict__ y, const unsigned char* __restrict__ tables,
@@ -259,11 +239,14 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   // read-out expects the state
   auto layout_of = [](int l) { return (LPR - 1 - l) % 2 == 0 ? kSoloLayoutB : kSoloLayoutA; };
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int Q = d.out_features;
-  double* s_ev = reinterpret_cast<double*>(smem_raw);                             // [2][kSoloWaves][8]
-  T* s_un = reinterpret_cast<T*>(smem_raw + LeanSoloLds::kEvBytes);                // [LPR][8]
-  C* s_ph = reinterpret_cast<C*>(smem_raw + LeanSoloLds::kEvBytes + LeanSoloLds::un_bytes(LPR));   // [LPR - 1][2][64][2]
-  static_assert((LeanSoloLds::kEvBytes + LeanSoloLds::un_bytes(LPR)) % 16 == 0, "16-byte reads of the phase entries");
+  const int Q = d.out_features, PairsP = solo_pairs_padded(Q), WS = LeanSoloLds::w_stride(Q);
+  D2* s_w = reinterpret_cast<D2*>(smem_raw);                                    // [8][WS]
+  double* s_b = reinterpret_cast<double*>(smem_raw + LeanSoloLds::w_bytes(Q));   // [PairsP][2]
+  T* s_un = reinterpret_cast<T*>(smem_raw + LeanSoloLds::w_bytes(Q) + LeanSoloLds::b_bytes(Q));   // [LPR][8]
+  C* s_ph = reinterpret_cast<C*>(smem_raw + LeanSoloLds::w_bytes(Q) + LeanSoloLds::b_bytes(Q) +
+                                 LeanSoloLds::un_bytes(LPR));                     // [LPR - 1][2][64][2]
+  static_assert(LeanSoloLds::w_bytes(1) % 16 == 0 && LeanSoloLds::b_bytes(1) % 16 == 0 && LeanSoloLds::un_bytes(LPR) % 16 == 0,
+                "16-byte reads of the weights, the bias and the phase entries");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int llane = logical_lane(lane);
@@ -272,14 +255,13 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   const T* g_un = g_body + QT::ph_elems(LPR);
   const T* g_a0 = g_un + QT::un_elems(LPR);
   // diagnostics: wavefront 0 of workgroup 0 stamps s_memtime into words 0..7 (tools/stamp_lean_solo.py) -- [0] entry,
-  // [1] setup loads issued, [2] barrier passed, [3] / [4] end of the layers and read-out / of the tail of its first round
-  // (the tail starts at the round's barrier: it holds the wait for the slowest of the eight wavefronts, linear_up and
-  // the stores), [5] / [6] of its second round, [7]: s_memrealtime (100 MHz) from entry to the last tail stamped, which
-  // gives the ticks their length.
+  // [1] setup loads issued, [2] barrier passed, [3] / [4] end of the layers and read-out / of the tail (linear_up and the
+  // stores of the item's row) of its first item, [5] / [6] of its second item, [7]: s_memrealtime (100 MHz) from entry to
+  // the last tail stamped, which gives the ticks their length.
   // When the buffer holds 8 + 8 * gridDim.x words (d.stamp_words), wavefront 0 of EVERY workgroup b also stamps
   // s_memrealtime -- the same clock on every CU -- into words 8 + 8 b .. (tools/timeline_lean_solo.py): [0] entry,
-  // [1] barrier passed, [2] / [3] end of the layers / of the tail of its first round, [4] / [5] of its second, [6] its
-  // last instruction.
+  // [1] barrier passed, [2] / [3] end of the layers / of the tail of its first item, [4] / [5] of its second, [6] its
+  // last instruction; and the LAST wavefront of the workgroup, the younger one of its SIMD, [7] its last instruction.
   // The test is wave-uniform (a scalar branch per stamp); lane 0 stores.
   const bool stamp_timeline = d.stamps != nullptr && (int64_t)d.stamp_words >= 8 + 8 * (int64_t)gridDim.x;
   const bool stamp_wave = d.stamps != nullptr && wv == 0 && (blockIdx.x == 0 || stamp_timeline);
@@ -304,11 +286,44 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   // lanes' own order) and the tangents -- and hands it over through LDS; behind the barrier every wavefront fills its
   // phase registers from the LDS copy with 16-byte reads.  (Each wavefront used to read the whole phase table from
   // global memory itself: eight times the bytes through the CU's vector L1, which took longer than an item's layers.)
-  // Every global load of it is issued before anything waits.  linear_up's weights go straight to the registers of the
-  // lanes that own the pixels (the two rows of a pair are 128 contiguous bytes of w_up), behind the barrier.
+  // Every global load of it is issued before anything waits.  linear_up's weights and bias (56 KiB at 784 pixels) are
+  // NOT in front of that barrier, where they doubled the setup (2.0 against 1.0 us): they are loaded right behind it,
+  // fly under the first item's layers, and go to LDS behind a second workgroup barrier in front of the FIRST tail only.
   constexpr int kPhEntries = (LPR - 1) * QT::TL;                                  // phase entries of layers 1 .. LPR - 1
   constexpr int kPhTrips = (kPhEntries + kSoloThreads - 1) / kSoloThreads;
+  // (Q <= kSoloMaxPixels: the host checks)
+  constexpr int kWTrips = 8 * solo_pairs_padded(kSoloMaxPixels) / kSoloThreads, kBTrips = kSoloMaxPixels / kSoloThreads;
   C phstage[kPhTrips];
+  D2 wreg[kWTrips];
+  double breg[kBTrips];
+  auto load_weights = [&]() {
+#pragma unroll
+    for (int k = 0; k < kWTrips; ++k) {
+      // (w_up in its own order, 16-byte chunk i = the unit i & 7 of pair i >> 3: the two rows of a pair are 128 contiguous
+      //  bytes.  A chunk beyond the image loads the last one; its pixel is never stored)
+      const int i = tid + k * kSoloThreads;
+      wreg[k] = reinterpret_cast<const D2*>(wu)[i < 4 * Q ? i : 4 * Q - 1];
+    }
+#pragma unroll
+    for (int k = 0; k < kBTrips; ++k) {
+      const int i = tid + k * kSoloThreads;
+      breg[k] = bu != nullptr ? bu[i < Q ? i : Q - 1] : 0.0;
+    }
+  };
+  // (every thread of the workgroup has a share, a wavefront without an item too; then the barrier)
+  auto hand_over_weights = [&]() {
+#pragma unroll
+    for (int k = 0; k < kWTrips; ++k) {
+      const int i = tid + k * kSoloThreads;
+      if (i < 8 * PairsP) s_w[(i & 7) * WS + (i >> 3)] = wreg[k];
+    }
+#pragma unroll
+    for (int k = 0; k < kBTrips; ++k) {
+      const int i = tid + k * kSoloThreads;
+      if (i < 2 * PairsP) s_b[i] = breg[k];
+    }
+    __syncthreads();
+  };
 #pragma unroll
   for (int k = 0; k < kPhTrips; ++k) {
     // LDS entry e = ((l - 1) * 2 + h) * 128 + lane * 2 + j: register r = 2 h + j of `lane` in layer l
@@ -335,20 +350,7 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   for (int q = 0; q < 4; ++q) pm[q] = ((llane >> q) & 1) ? (T)1 : (T)-1;
   __syncthreads();
   stamp(2, 1);
-  // linear_up's weights, behind the barrier: the first tail is an item's layers away, and in front of the barrier
-  // these loads -- 16 bytes of up to 64 different lines each -- would stand in the queue before the phase entries.
-  // (a lane without a pair loads pair 0's rows and the missing second row of an odd Q's last pair the row before it:
-  //  no branch around a load, and neither is ever stored.  Q <= kSoloMaxPixels: the host checks)
-  const int pair = solo_pair_of(Q, wv, lane);
-  const int row_a = pair < 0 ? 0 : 2 * pair, row_b = row_a + 1 < Q ? row_a + 1 : Q - 1;
-  const bool has_b = pair >= 0 && 2 * pair + 1 < Q;
-  D2 wa[4], wb[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    wa[j] = reinterpret_cast<const D2*>(wu)[row_a * 4 + j];
-    wb[j] = reinterpret_cast<const D2*>(wu)[row_b * 4 + j];
-  }
-  const double bias_a = bu != nullptr ? bu[row_a] : 0.0, bias_b = bu != nullptr ? bu[row_b] : 0.0;
+  load_weights();
   // this lane's phase entries into registers, for all items of the wave (entry 0 unused: the first layer is generated)
   C phr[LPR][4];
 #pragma unroll
@@ -361,114 +363,101 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
     }
   }
 
-  // ---- the rounds of this workgroup ----------------------------------------------------------------------------------
+  // ---- the items of this wave ---------------------------------------------------------------------------------------
   const uint32_t n_steps = (uint32_t)d.n_steps;
-  const uint32_t n_items = (uint32_t)p.batch * n_steps;         // < 2^31 (the host checks)
   const uint32_t stride = (uint32_t)gridDim.x * kSoloWaves;     // waves of the launch
-  const uint32_t base0 = (uint32_t)blockIdx.x * kSoloWaves;     // the round's first item: wavefront w takes base + w
+  const uint32_t g0 = (uint32_t)blockIdx.x * kSoloWaves + (uint32_t)wv;
   const uint32_t stride_q = stride / n_steps, stride_r = stride - stride_q * n_steps;
-  int64_t sample = (int64_t)(base0 / n_steps);                  // (sample, step) of the round's first item
-  uint32_t step = base0 - (base0 / n_steps) * n_steps;
-  int round = 0;
-  // (the count of rounds is the same for the eight wavefronts: every one of them meets every barrier)
-  for (uint32_t base = base0; base < n_items; base += stride, ++round) {
+  int64_t sample = (int64_t)(g0 / n_steps);
+  uint32_t step = g0 - (g0 / n_steps) * n_steps;
+  const int groups = solo_groups(Q);
+  const D2* s_b2 = reinterpret_cast<const D2*>(s_b);
+  for (int item = 0; sample < p.batch; ++item) {
     asm volatile("" ::: "memory");   // (the LDS reads below stay inside the loop: hoisted, they would not fit registers)
-    double* s_round = s_ev + (round & 1) * (kSoloWaves * 8);
-    if (base + (uint32_t)wv < n_items) {   // (wave-uniform; a wavefront without an item in the last round skips to the barrier)
-      C a[4];
+    C a[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) a[r] = C{a0r[r], (T)0};
-      // a layer's tangents are read one layer ahead (the fence keeps the compiler from reading all layers' up front)
-      const V4* un4 = reinterpret_cast<const V4*>(s_un);
-      V4 lo = un4[2], hi = un4[3];
+    for (int r = 0; r < 4; ++r) a[r] = C{a0r[r], (T)0};
+    // a layer's tangents are read one layer ahead (the fence keeps the compiler from reading all layers' up front)
+    const V4* un4 = reinterpret_cast<const V4*>(s_un);
+    V4 lo = un4[2], hi = un4[3];
 #pragma unroll
-      for (int l = 1; l < LPR; ++l) {
-        const int ln = l + 1 < LPR ? l + 1 : l;
-        const V4 nlo = un4[2 * ln], nhi = un4[2 * ln + 1];
-        __builtin_amdgcn_sched_barrier(0);
-        const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
-        solo_layer(layout_of(l), a, phr[l], ts, hi.x, hi.y, hi.z, hi.w);
-        lo = nlo;
-        hi = nhi;
-      }
-      // ---- <Z_w>: the register-bit wires are signed in-lane sums, the lane-bit wires signed copies of the lane's total ----
-      T pw[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) pw[r] = a[r].x * a[r].x + a[r].y * a[r].y;
-      const T pt = (pw[0] + pw[1]) + (pw[2] + pw[3]);
-      T ez[8];
-      ez[0] = (pw[0] + pw[1]) - (pw[2] + pw[3]);   // wire 0 = index bit 7 = register bit 1
-      ez[1] = (pw[0] + pw[2]) - (pw[1] + pw[3]);   // wire 1 = index bit 6 = register bit 0
-#pragma unroll
-      for (int w = 2; w < 8; ++w) ez[w] = ((llane >> (7 - w)) & 1) ? -pt : pt;
-      const T tot = wave_reduce8<T>(ez, lane, llane);
-      // (the lane of logical number 4 b0 + 2 b1 + b2 -> wire b0 b1 b2 holds that wire's total: qsim_adjoint.h)
-      if (llane < 8) s_round[wv * 8 + (((llane & 1) << 2) | (llane & 2) | ((llane >> 2) & 1))] = (double)tot;
-      if (round < 2) stamp(3 + 2 * round, 2 + 2 * round);
+    for (int l = 1; l < LPR; ++l) {
+      const int ln = l + 1 < LPR ? l + 1 : l;
+      const V4 nlo = un4[2 * ln], nhi = un4[2 * ln + 1];
+      __builtin_amdgcn_sched_barrier(0);
+      const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
+      solo_layer(layout_of(l), a, phr[l], ts, hi.x, hi.y, hi.z, hi.w);
+      lo = nlo;
+      hi = nhi;
     }
-    // the round's only barrier.  It waits for this wavefront's LDS traffic alone -- the read-out just written, the
-    // reads of the round before --, not, as __syncthreads() may, for the image stores of the round before.
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    // ---- linear_up: this lane's two pixels of the round's rows, two partial sums each with explicit fma (as
-    // dense_lean_kernel); an item's eight <Z> are one address for all lanes, a broadcast read ------------------------------
-    const uint32_t left = n_items - base, n_rows = left < (uint32_t)kSoloWaves ? left : (uint32_t)kSoloWaves;
-    int64_t row_sample = sample;
-    uint32_t row_step = step;
-    const D2* ev2 = reinterpret_cast<const D2*>(s_round);
-    D2 e01 = ev2[0], e23 = ev2[1], e45 = ev2[2], e67 = ev2[3];
-    for (uint32_t k = 0; k < n_rows; ++k) {
-      // (the next row's values are read while this one is computed; behind the last row, the last again)
-      const uint32_t kn = k + 1 < (uint32_t)kSoloWaves ? k + 1 : k;
-      const D2 n01 = ev2[4 * kn], n23 = ev2[4 * kn + 1], n45 = ev2[4 * kn + 2], n67 = ev2[4 * kn + 3];
-      double a0 = bias_a, a1 = 0.0, b0 = bias_b, b1 = 0.0;
-      a0 = fma(e01.x, wa[0].x, a0);
-      a1 = fma(e01.y, wa[0].y, a1);
-      a0 = fma(e23.x, wa[1].x, a0);
-      a1 = fma(e23.y, wa[1].y, a1);
-      a0 = fma(e45.x, wa[2].x, a0);
-      a1 = fma(e45.y, wa[2].y, a1);
-      a0 = fma(e67.x, wa[3].x, a0);
-      a1 = fma(e67.y, wa[3].y, a1);
-      a0 += a1;
-      b0 = fma(e01.x, wb[0].x, b0);
-      b1 = fma(e01.y, wb[0].y, b1);
-      b0 = fma(e23.x, wb[1].x, b0);
-      b1 = fma(e23.y, wb[1].y, b1);
-      b0 = fma(e45.x, wb[2].x, b0);
-      b1 = fma(e45.y, wb[2].y, b1);
-      b0 = fma(e67.x, wb[3].x, b0);
-      b1 = fma(e67.y, wb[3].y, b1);
-      b0 += b1;
-      double* yrow = y + (size_t)row_step * d.y_step_stride + row_sample * d.y_ld;
-      // a whole pair of a 16-byte aligned row (a wave-uniform test) is one 16-byte store; a row that is not aligned
-      // and the lone last pixel of an odd Q take plain 8-byte stores (an 8-byte write-through store is the slow form)
-      const bool row_aligned = (reinterpret_cast<uintptr_t>(yrow) & 15) == 0;
-      if (pair >= 0) {
-        if (row_aligned && has_b) {
+    // ---- <Z_w>: the register-bit wires are signed in-lane sums, the lane-bit wires signed copies of the lane's total ----
+    T pw[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pw[r] = a[r].x * a[r].x + a[r].y * a[r].y;
+    const T pt = (pw[0] + pw[1]) + (pw[2] + pw[3]);
+    T ez[8];
+    ez[0] = (pw[0] + pw[1]) - (pw[2] + pw[3]);   // wire 0 = index bit 7 = register bit 1
+    ez[1] = (pw[0] + pw[2]) - (pw[1] + pw[3]);   // wire 1 = index bit 6 = register bit 0
+#pragma unroll
+    for (int w = 2; w < 8; ++w) ez[w] = ((llane >> (7 - w)) & 1) ? -pt : pt;
+    const T tot = wave_reduce8<T>(ez, lane, llane);
+    // (the lane of logical number 4 b0 + 2 b1 + b2 -> wire b0 b1 b2 holds that wire's total: qsim_adjoint.h)
+    double ev[8];
+#pragma unroll
+    for (int w = 0; w < 8; ++w)
+      ev[w] = (double)read_lane(tot, logical_lane(((w >> 2) & 1) | (w & 2) | ((w & 1) << 2)));
+    if (item < 2) stamp(3 + 2 * item, 2 + 2 * item);
+    if (item == 0) hand_over_weights();   // (the early wavefront of a SIMD waits here once for its partner)
+    // ---- linear_up: the item's row, pair = lane + 64 g; per pixel two partial sums with explicit fma (as
+    // dense_lean_kernel) and one add ------------------------------------------------------------------------------------
+    double* yrow = y + (size_t)step * d.y_step_stride + sample * d.y_ld;
+    // a whole pair of a 16-byte aligned row (a wave-uniform test) is one 16-byte store; a row that is not aligned and
+    // the lone last pixel of an odd Q take plain 8-byte stores (an 8-byte write-through store is the slow form)
+    const bool row_aligned = (reinterpret_cast<uintptr_t>(yrow) & 15) == 0;
 #if QIDDM_SOLO_WRITE_THROUGH
-          // (the resource spans this row alone, Q * 8 <= 8 192 bytes: the 32-bit offset never limits the output's size)
-          using U4 = unsigned __attribute__((ext_vector_type(4)));
-          const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(yrow, 0, Q * 8, 0x00020000);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, D2{a0, b0}), rsrc, pair * 16, 0, /*sc1*/ 16);
-#else
-          *reinterpret_cast<D2*>(yrow + 2 * pair) = D2{a0, b0};
+    // (the resource spans this row alone, Q * 8 <= 8 192 bytes: the 32-bit offset never limits the output's size)
+    using U4 = unsigned __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(yrow, 0, Q * 8, 0x00020000);
 #endif
-        } else {
-          yrow[2 * pair] = a0;
-          if (has_b) yrow[2 * pair + 1] = b0;
-        }
-      }
-      e01 = n01;
-      e23 = n23;
-      e45 = n45;
-      e67 = n67;
-      if (++row_step >= n_steps) {
-        row_step = 0;
-        ++row_sample;
+#pragma unroll 2
+    for (int g = 0; g < groups; ++g) {
+      const int pr = solo_pair_of(g, lane), n_pix = solo_pair_pixels(Q, pr);
+      const D2* wp = s_w + pr;
+      const D2 wa0 = wp[0], wa1 = wp[WS], wa2 = wp[2 * WS], wa3 = wp[3 * WS];
+      const D2 wb0 = wp[4 * WS], wb1 = wp[5 * WS], wb2 = wp[6 * WS], wb3 = wp[7 * WS];
+      const D2 bias = s_b2[pr];
+      double a0 = bias.x, a1 = 0.0, b0 = bias.y, b1 = 0.0;
+      a0 = fma(ev[0], wa0.x, a0);
+      a1 = fma(ev[1], wa0.y, a1);
+      a0 = fma(ev[2], wa1.x, a0);
+      a1 = fma(ev[3], wa1.y, a1);
+      a0 = fma(ev[4], wa2.x, a0);
+      a1 = fma(ev[5], wa2.y, a1);
+      a0 = fma(ev[6], wa3.x, a0);
+      a1 = fma(ev[7], wa3.y, a1);
+      a0 += a1;
+      b0 = fma(ev[0], wb0.x, b0);
+      b1 = fma(ev[1], wb0.y, b1);
+      b0 = fma(ev[2], wb1.x, b0);
+      b1 = fma(ev[3], wb1.y, b1);
+      b0 = fma(ev[4], wb2.x, b0);
+      b1 = fma(ev[5], wb2.y, b1);
+      b0 = fma(ev[6], wb3.x, b0);
+      b1 = fma(ev[7], wb3.y, b1);
+      b0 += b1;
+      if (row_aligned && n_pix == 2) {
+#if QIDDM_SOLO_WRITE_THROUGH
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, D2{a0, b0}), rsrc, pr * 16, 0, /*sc1*/ 16);
+#else
+        *reinterpret_cast<D2*>(yrow + 2 * pr) = D2{a0, b0};
+#endif
+      } else if (n_pix > 0) {
+        yrow[2 * pr] = a0;
+        if (n_pix == 2) yrow[2 * pr + 1] = b0;
       }
     }
-    if (round < 2) stamp(4 + 2 * round, 3 + 2 * round);
-    // the next round's first item
+    if (item < 2) stamp(4 + 2 * item, 3 + 2 * item);
+    // next item of this wave
     sample += stride_q;
     step += stride_r;
     if (step >= n_steps) {
@@ -476,7 +465,12 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
       ++sample;
     }
   }
+  if (g0 / n_steps >= (uint32_t)p.batch) hand_over_weights();   // (a wavefront without an item meets the barrier too)
   stamp(-1, 6);
+  if (stamp_timeline && wv == kSoloWaves - 1) {
+    const unsigned long long rt = __builtin_amdgcn_s_memrealtime();
+    if (lane == 0) d.stamps[8 + 8 * (size_t)blockIdx.x + 7] = rt;
+  }
 }
 
 }  // namespace qiddm

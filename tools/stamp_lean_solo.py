@@ -1,12 +1,11 @@
 #!/usr/bin/env python
 """Diagnostic: where wavefront 0 of workgroup 0 of the one-wavefront-per-item body (csrc/qsim_lean_solo.h) spends its
 ticks (s_memtime stamps taken by lane 0): the per-workgroup setup, then the layers and the tail of its first two
-rounds.  A round is the eight items of the workgroup's eight wavefronts: "layers" is the wavefront's own item up to its
-read-out in LDS; "tail" starts at the round's barrier, so it holds the wait for the slowest of the eight wavefronts, then
-linear_up for this wavefront's pixels of all eight rows and their stores.  QNN_noise(784, 8, 14), float32, the solo body
-forced; the benchmark launch (batch 256, 15 steps: 3 840 items, two rounds on 256 CUs) and a 240-item launch (one round
-on 30 workgroups).  A stamp is the issue time of the wavefront's instruction stream: work still in flight (stores above
-all) shows up in the next interval that waits for it; the first round's layers include the fill of the phase registers
+items.  "layers" is the item up to its read-out; "tail" is linear_up for the item's whole row, the weights read from LDS,
+and the row's stores.  QNN_noise(784, 8, 14), float32, the solo body forced; the benchmark launch (batch 256, 15 steps:
+3 840 items, two items per wavefront on 256 CUs, 1.875 in the mean) and a 240-item launch (one item per wavefront on 30
+workgroups).  A stamp is the issue time of the wavefront's instruction stream: work still in flight (stores above
+all) shows up in the next interval that waits for it; the first item's layers include the fill of the phase registers
 from LDS.  The last
 column is s_memrealtime (100 MHz) from entry to the last tail stamped, which gives the ticks their length.  Not a timing
 of the product path: compare with the kernel time of a profile.
@@ -49,7 +48,7 @@ for batch, steps in ((256, 15), (16, 15)):
         t = buf.cpu().tolist()
         last = max(t[:7])
         per = f"{(t[3] - t[2]) / LAYERS:.0f}" if t[3] else "-"
-        print(f"  loads issued {gap(t, 0, 1)}  to barrier passed {gap(t, 1, 2)}  round 0: layers {gap(t, 2, 3)} ({per} each)"
-              f"  tail {gap(t, 3, 4)}  round 1: layers {gap(t, 4, 5)}  tail {gap(t, 5, 6)}  entry to last stamp {last - t[0]:6d}"
+        print(f"  loads issued {gap(t, 0, 1)}  to barrier passed {gap(t, 1, 2)}  item 0: layers {gap(t, 2, 3)} ({per} each)"
+              f"  tail {gap(t, 3, 4)}  item 1: layers {gap(t, 4, 5)}  tail {gap(t, 5, 6)}  entry to last stamp {last - t[0]:6d}"
               f" = {t[7] / 100:.2f} us")
 _capi.lib().qiddm_set_stamp_buffer(None, 0)

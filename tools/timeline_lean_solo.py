@@ -2,11 +2,13 @@
 """Diagnostic: the timeline of one launch of the one-wavefront-per-item body (csrc/qsim_lean_solo.h) over ALL its
 workgroups.  With a stamp buffer of 8 + 8 x (workgroups) words registered, wavefront 0 of every workgroup writes
 s_memrealtime -- a 100 MHz clock that is the same on every CU -- at its entry, behind the setup's barrier, at the end of
-the layers and of the tail of its first two rounds, and as its last instruction.  Printed, in us (one tick = 0.01 us):
+the layers and of the tail (linear_up and the stores of the item's row) of its first two items, and as its last
+instruction; the workgroup's LAST wavefront, the younger one of its SIMD, stamps its last instruction too.  Printed, in
+us (one tick = 0.01 us):
 dispatch skew (first entry -> last entry), the distribution of the workgroups' lifetimes and of their phases, first entry
 -> last exit, the kernel's duration from HIP events around the same launch replayed back to back in a graph, and the
-difference of the last two: the time of a launch that no stamped wavefront accounts for.  The stamped wavefront is one of
-eight of its workgroup; the other seven may leave later.  QNN_noise(784, 8, 14), float32, the solo body forced; the
+difference of the last two: the time of a launch that no stamped wavefront accounts for.  Wavefronts 0 and 7 are two of
+eight of their workgroup; the other six may leave later than wavefront 0, hardly later than wavefront 7.  QNN_noise(784, 8, 14), float32, the solo body forced; the
 benchmark launch (batch 256, 15 steps) and a 240-item launch.
     python tools/timeline_lean_solo.py"""
 import os, sys
@@ -28,7 +30,7 @@ bu = torch.rand(P, dtype=torch.float64).cuda()
 w = (torch.randn(1, 1, 14, n, 3, dtype=torch.float64) * 0.6).cuda()
 tables = dense_sample_lean_tables(circ, w, wd, bd, wu, bu, "f32")
 cus = torch.cuda.get_device_properties(0).multi_processor_count
-NAMES = ["entry -> barrier passed", "round 0 layers", "round 0 tail", "round 1 layers", "round 1 tail", "-> last instruction"]
+NAMES = ["entry -> barrier passed", "item 0 layers", "item 0 tail", "item 1 layers", "item 1 tail", "-> last instruction"]
 
 
 def dist(v):
@@ -55,17 +57,20 @@ for batch, steps in ((256, 15), (16, 15)):
         torch.cuda.synchronize()
         t = buf[8:].reshape(grid, 8).cpu()
         assert (t[:, 0] > 0).all() and (t[:, 6] >= t[:, 0]).all(), "a workgroup did not stamp"
-        first, last_entry, last_exit = t[:, 0].min().item(), t[:, 0].max().item(), t[:, 6].max().item()
+        # (word 7: the last wavefront's exit; a body without that stamp leaves it 0)
+        first, last_entry, last_exit = t[:, 0].min().item(), t[:, 0].max().item(), t[:, 6:8].max().item()
         span = (last_exit - first) / 100
         print(f"  launch {rep}: dispatch skew {(last_entry - first) / 100:5.2f}   first entry -> last exit {span:6.2f}   "
               f"kernel - that {kernel_us - span:6.2f}   first entry -> first exit {(t[:, 6].min().item() - first) / 100:6.2f}")
         print(f"    lifetime of a workgroup's wavefront 0   {dist((t[:, 6] - t[:, 0]).tolist())}")
+        if (t[:, 7] > 0).all():
+            print(f"    wavefront 0's entry -> wavefront 7's exit {dist((t[:, 7] - t[:, 0]).tolist())}")
         for k, name in enumerate(NAMES[:-1]):
             have = (t[:, k] > 0) & (t[:, k + 1] > 0)
             if have.any():
                 print(f"    {name:38s}  {dist((t[have, k + 1] - t[have, k]).tolist())}   ({int(have.sum())} workgroups)")
-        # (behind the last stamp a workgroup took: its third and later rounds, if it has any, and the way out)
-        print(f"    {'last round stamped ' + NAMES[-1]:38s}  {dist((t[:, 6] - t[:, 1:6].max(dim=1).values).tolist())}")
+        # (behind the last stamp wavefront 0 took: its third and later items, if it has any, and the way out)
+        print(f"    {'last item stamped ' + NAMES[-1]:38s}  {dist((t[:, 6] - t[:, 1:6].max(dim=1).values).tolist())}")
         # where on the chip the late ones sit: entry and exit by workgroup number, eighths of the grid
         for lo in range(0, grid, max(grid // 8, 1)):
             sl = t[lo:lo + max(grid // 8, 1)]
