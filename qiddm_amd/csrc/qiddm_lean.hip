@@ -57,16 +57,16 @@ qiddm::KScalars params_of(const qiddm_circuit_t* c) {
 
 // When the instance that carries both bodies (qsim_lean.h: lean_has_solo) runs the one-wavefront-per-item body: from
 // kLeanSoloMinSteps steps per launch on at every batch, below that from kLeanSoloMinItems items (batch x n_steps) on.
-// A solo workgroup stages the phase table in LDS (1 us), every wavefront fills its registers from there, simulates its
-// item (~3.5 us) while linear_up's weights arrive, hands its share of them to LDS and writes its item's row (~1.3 us
-// behind the one wait for the slowest wavefront): ~9 us whatever the launch holds up to 2 048 items, one item per
-// wavefront; the four-wave body pays ~2.7 us per step of a sample.  Measured by
-// tools/ab_lean_solo_threshold.py, float32, P = 784 (profiles/lean_rows/threshold.txt; us per launch, four-wave /
-// solo):
-//   1 step:   256 items 5.8 / 9.8     512 items 7.8 / 9.9    1 024 items 13.3 / 10.2    2 048 items 24.0 / 10.6
-//   4 steps:   64 items 13.3 / 9.7    1 024 items 14.9 / 10.2
-//   15 steps: 240 items 42.8 / 9.8    3 840 items 46.4 / 16.7
-// The one-step crossover did not move when linear_up went from LDS to registers: between 512 and 1 024 items.
+// A solo workgroup stages the phase table in LDS (1.2 us), every wavefront simulates its item (~3.4 us alone on its
+// SIMD) while linear_up's weights arrive, hands its share of them to LDS and writes its item's row (~1.3 us behind the
+// one wait for the slowest wavefront): ~9 us whatever the launch holds up to 2 048 items, one item per wavefront; the
+// four-wave body pays ~2.7 us per step of a sample.  Measured by tools/ab_lean_solo_threshold.py, float32, P = 784
+// (profiles/lean_wide/threshold.txt; us per launch, four-wave / solo):
+//   1 step:   256 items 5.7 / 9.1     512 items 7.8 / 9.2    1 024 items 13.3 / 9.4     2 048 items 23.9 / 10.0
+//             4 096 items 37.3 / 15.9
+//   4 steps:   64 items 13.1 / 9.0    1 024 items 14.7 / 9.4
+//   15 steps: 240 items 42.3 / 9.1    3 840 items 45.2 / 14.9   15 360 items 99.8 / 46.3
+// The one-step crossover has not moved since linear_up went from LDS to registers: between 512 and 1 024 items.
 // (2 and 3 steps are not in the table: the step rule stays where it was measured.)
 constexpr int kLeanSoloMinSteps = 4;
 constexpr int64_t kLeanSoloMinItems = 1024;
@@ -90,6 +90,25 @@ bool lean_solo_wanted(int64_t items, int n_steps) {
   return v >= 0 && items >= (int64_t)v;
 }
 
+// Wavefronts per workgroup of the solo kernel: 8 (two per SIMD) while that gives every item a wavefront of its own on
+// as many CUs as the launch can use, 16 (four per SIMD) above that.  QIDDM_LEAN_SOLO_WAVES = 8 / 16 forces the width
+// (A/B runs only; read at every launch, as QIDDM_LEAN_SOLO_MIN_ITEMS is; anything else leaves the rule in place).
+int lean_solo_waves(int64_t items, int64_t cus) {
+  const char* e = std::getenv("QIDDM_LEAN_SOLO_WAVES");
+  if (e != nullptr && *e != 0) {
+    const long long v = std::atoll(e);
+    if (v == 8 || v == 16) return (int)v;
+  }
+  return items <= 8 * cus ? 8 : 16;
+}
+// One workgroup per CU at most, and at either width another CU for every 8 items while the CUs last: a launch that the
+// rule gives 16 wavefronts per workgroup (more than 8 items per CU) is on every CU, so the benchmark's 3 840 items are
+// 15 per CU on 256 CUs -- ceil(items / 16) workgroups would be 240 of 16 items, and 16 CUs idle.
+unsigned lean_solo_grid(int64_t items, int64_t cus) {
+  const int64_t want = (items + 7) / 8;
+  return (unsigned)(want < cus ? want : cus);
+}
+
 template <typename T, int N, int PPT, bool REUP, int LPR, bool POST>
 int launch_lean(const double* x, const double* wd, const double* bd, const double* wu, const double* bu, double* y,
                 const void* tables, const qiddm::QuadScalars& d, const qiddm::KScalars& p, int layers, hipStream_t st) {
@@ -99,12 +118,15 @@ int launch_lean(const double* x, const double* wd, const double* bd, const doubl
     if (lean_solo_wanted(items, d.n_steps) && items < ((int64_t)1 << 31) && d.out_features <= qiddm::kSoloMaxPixels) {
       static_assert(qiddm::LeanSoloLds::bytes(qiddm::kSoloMaxPixels, LPR) <= kMaxLds, "the largest image fits LDS");
       const size_t smem = qiddm::LeanSoloLds::bytes(d.out_features, LPR);   // 90 KiB at 784 pixels, 99 KiB at 1 024
-      const int64_t want = (items + qiddm::kSoloWaves - 1) / qiddm::kSoloWaves;   // one item per wavefront
-      const int64_t cus = lean_cu_count();                                         // one workgroup per CU at most
-      const unsigned grid = (unsigned)(want < cus ? want : cus);
-      return qiddm_capi::launch<qiddm::dense_lean_kernel<T, N, PPT, REUP, LPR, POST>>(
-          kMaxLds, dim3(grid), dim3(qiddm::kSoloThreads), smem, st, "dense_lean_kernel", x, wd, bd, wu, bu, y,
-          static_cast<const unsigned char*>(tables), d, p);
+      const int64_t cus = lean_cu_count();                                   // one workgroup per CU at most
+      const int waves = lean_solo_waves(items, cus);
+      const unsigned grid = lean_solo_grid(items, cus);
+      const unsigned char* tb = static_cast<const unsigned char*>(tables);
+      if (waves == 16)
+        return qiddm_capi::launch<qiddm::dense_lean_solo_kernel<LPR, 16>>(
+            kMaxLds, dim3(grid), dim3(qiddm::solo_threads(16)), smem, st, "dense_lean_solo_kernel", wu, bu, y, tb, d, p);
+      return qiddm_capi::launch<qiddm::dense_lean_solo_kernel<LPR, 8>>(
+          kMaxLds, dim3(grid), dim3(qiddm::solo_threads(8)), smem, st, "dense_lean_solo_kernel", wu, bu, y, tb, d, p);
     }
   }
   const size_t smem = qiddm::LeanTables<T, N>::lds_bytes(layers, p.n_rounds,

@@ -246,19 +246,13 @@ struct LeanLayer {
   T k1, k2, k3;  // wave-bit exchange: partners wave^1, wave^2, wave^3
 };
 
-// The instance that also carries the one-wavefront-per-item body of qsim_lean_solo.h (float32, 8 qubits, no re-upload,
-// compiled-in layer count, "data" goal, at most 1024 pixels): launched with kSoloThreads threads it runs that body, with
-// 256 threads the four-wave body below.
-constexpr int kSoloWaves = 8;                     // wavefronts per workgroup: two per SIMD, <= 256 VGPRs each
-constexpr int kSoloThreads = kSoloWaves * kWave;
+// The instance whose launches the one-wavefront-per-item kernel of qsim_lean_solo.h (dense_lean_solo_kernel) can take
+// over (float32, 8 qubits, no re-upload, compiled-in layer count, "data" goal, at most 1024 pixels): the host chooses
+// between that kernel and the four-wave kernel below (qiddm_lean.hip: launch_lean).
 template <typename T, int N, int PPT, bool REUP, int LPR, bool POST>
 constexpr bool lean_has_solo() {
   return std::is_same<T, float>::value && N == 8 && PPT == 4 && !REUP && LPR > 1 && !POST;
 }
-template <int LPR>
-__device__ void dense_lean_solo_body(const double* __restrict__ wu, const double* __restrict__ bu,
-                                     double* __restrict__ y, const unsigned char* __restrict__ tables,
-                                     const QuadScalars& d, const KScalars& p);
 
 // REUP: the circuit re-uploads its data angles (n_blocks > 1); without it the angles never reach the state and no
 //       angle code is compiled at all (no branch in the layer either: a taken branch costs a lone wavefront ~50 cycles).
@@ -269,7 +263,7 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
 //       (reference src/models.py:130-134).  The clamp breaks the composite map, so the image stays in registers
 //       (PPT pixels per thread) and a re-uploading net runs its whole linear_down every step, weights in registers too.
 template <typename T, int N, int PPT, bool REUP, int LPR, bool POST>
-__global__ __launch_bounds__((lean_has_solo<T, N, PPT, REUP, LPR, POST>() ? kSoloThreads : 256)) void dense_lean_kernel(
+__global__ __launch_bounds__(256) void dense_lean_kernel(
     const double* __restrict__ x, const double* __restrict__ wd, const double* __restrict__ bd,
     const double* __restrict__ wu, const double* __restrict__ bu, double* __restrict__ y,
     const unsigned char* __restrict__ tables, const QuadScalars d, const KScalars p) {
@@ -277,13 +271,6 @@ __global__ __launch_bounds__((lean_has_solo<T, N, PPT, REUP, LPR, POST>() ? kSol
   using QT = LeanTables<T, N>;
   constexpr int TL = QT::TL;
   using V4 = T __attribute__((ext_vector_type(4)));
-  if constexpr (lean_has_solo<T, N, PPT, REUP, LPR, POST>()) {
-    // the host picks the decomposition by the workgroup size (qiddm_lean.hip: launch_lean)
-    if (blockDim.x == kSoloThreads) {
-      dense_lean_solo_body<LPR>(wu, bu, y, tables, d, p);
-      return;
-    }
-  }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr bool kRegTables = lean_tables_in_registers<REUP, LPR>();
   const int n_rounds = kRegTables ? 1 : p.n_rounds;

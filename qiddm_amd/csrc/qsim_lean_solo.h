@@ -15,16 +15,17 @@
 //   * every gate acts on 8 independent registers (4 amplitudes x re / im), so the wave issues back to back (~4 cycles
 //     per vector instruction) instead of waiting ~11 cycles on its own previous result;
 //   * the items of a launch (batch x n_steps: this instance's angles never reach the state, so its steps do not depend
-//     on each other) are spread over all wavefronts of all workgroups, kSoloWaves per CU.  Every item is still
-//     simulated in full.
-// The per-workgroup setup fetches the tables from global memory ONCE and hands them to the eight wavefronts through LDS
+//     on each other) are spread over all wavefronts of all workgroups, WAVES = 8 or 16 per CU (two or four per SIMD;
+//     the host picks the width, qiddm_lean.hip: launch_lean).  Every item is still simulated in full.
+// The per-workgroup setup fetches the tables from global memory ONCE and hands them to the wavefronts through LDS
 // (one __syncthreads()); linear_up's weights and bias follow under the first item's layers and reach LDS behind a second
-// barrier in front of the first tail.  These two are the body's only barriers: there is none per item.  A wavefront is on
-// its own: it simulates an item, broadcasts the eight <Z> from the lanes that hold them and writes that item's WHOLE row, a
-// lane two neighbouring pixels at a time (pair = lane + 64 g), 16 contiguous bytes per lane and store.  With two wavefronts
-// on a SIMD the one that is ahead runs its tail under its partner's layers.  Every wave runs the same code -- one copy of
-// it, and a pixel of every row is computed by the same instructions on the same operands, so every row of a launch is the
-// same bits --; what depends on the wave number is which items it takes.
+// barrier in front of the first tail.  These two are the kernel's only barriers: there is none per item.  A wavefront is
+// on its own: it simulates an item -- the layer's phase entries and tangents read from LDS one layer ahead, which keeps
+// the kernel inside the 128 VGPRs of four wavefronts per SIMD --, broadcasts the eight <Z> from the lanes that hold them
+// and writes that item's WHOLE row, a lane two neighbouring pixels at a time (pair = lane + 64 g), 16 contiguous bytes per
+// lane and store.  A wavefront that is ahead runs its tail under its SIMD neighbours' layers.  Every wave of either width
+// runs the same code -- one copy of it, and a pixel of every row is computed by the same instructions on the same
+// operands, so every row of a launch is the same bits --; what depends on the wave number is which items it takes.
 #pragma once
 #include "qsim_lean.h"
 
@@ -120,6 +121,20 @@ __device__ __forceinline__ void solo_ry_dpp4(V2<float> (&a)[4], float t0, float 
 }
 #undef QIDDM_SOLO_DPP8
 
+// ph * a, the products of cmul2 component by component -- re = fma(-ph.y, a.y, ph.x * a.x), im = fma(ph.y, a.x, ph.x * a.y)
+// -- as two packed instructions: op_sel picks the half of a register pair that each component reads and neg_lo negates
+// ph.y for the real part, so neither (ph.x, ph.x), (-ph.y, ph.y) nor (a.y, a.x) is ever built in registers (written in
+// plain vector code the compiler builds two of them: a `v_xor` and a `v_mov` per amplitude).  Four scalar instructions
+// before: 16 -> 8 of a layer's ~80.
+__device__ __forceinline__ V2<float> solo_cmul(V2<float> ph, V2<float> a) {
+  V2<float> prod, out;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(prod) : "v"(ph), "v"(a));   // ph.x * (a.x, a.y)
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"           // (-ph.y a.y, ph.y a.x) + prod
+      : "=&v"(out)
+      : "v"(ph), "v"(a), "v"(prod));
+  return out;
+}
+
 // RY (tangent form) on a register bit: the 2 x 2 on (member with the bit clear, member with it set)
 __device__ __forceinline__ void solo_ry_reg(V2<float>& lo, V2<float>& hi, float t) {
   const V2<float> nlo = __builtin_elementwise_fma(bcast<float>(-t), hi, lo);
@@ -196,13 +211,8 @@ static_assert(solo_amp(kSoloLayoutA, 2, 37) == ((2 << 6) | 37) && solo_table_slo
 // layout: the one the layer starts in (a constant once the layer sequence is unrolled).
 __device__ __forceinline__ void solo_layer(int layout, V2<float> (&a)[4], const V2<float> (&ph)[4], const float (&ts)[4],
                                            float t4, float t5, float t6, float t7) {
-  // (component by component, the products of cmul2: its packed form wants (ph.x, ph.x) and (ph.y, ph.y) as register
-  //  pairs, which the compiler keeps across the loop for every layer -- twice the registers of the phase table)
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float re = fmaf(-ph[r].y, a[r].y, ph[r].x * a[r].x), im = fmaf(ph[r].y, a[r].x, ph[r].x * a[r].y);
-    a[r] = V2<float>{re, im};
-  }
+  for (int r = 0; r < 4; ++r) a[r] = solo_cmul(ph[r], a[r]);
   solo_ry_dpp4(a, ts[0], ts[1], ts[2], ts[3]);
   const bool from_a = layout == kSoloLayoutA;
   const float in0 = from_a ? t6 : t5, in1 = from_a ? t7 : t4;     // r0 / r1 of the layout the layer starts in
@@ -221,14 +231,19 @@ __device__ __forceinline__ void solo_layer(int layout, V2<float> (&a)[4], const 
   solo_ry_reg(a[1], a[3], out1);
 }
 
-// The body of dense_lean_kernel<float, 8, PPT, false, LPR, false> at kSoloThreads threads per workgroup.
-// Items: (sample, step) = item / n_steps, item % n_steps for item < batch * n_steps; wave g of the launch takes items
-// g, g + (waves of the launch), ...: every item is simulated and written exactly once, by one wavefront, and no wave
-// idles while another has two to do.
-template <int LPR>
-__device__ void dense_lean_solo_body(const double* __restrict__ wu, const double* __restrict__ bu,
-                                                     double* __restrict__ y, const unsigned char* __restrict__ tables,
-                                                     const QuadScalars& d, const KScalars& p) {
+// The launches of dense_lean_kernel<float, 8, 4, false, LPR, false> that the host routes here, WAVES wavefronts per
+// workgroup, one workgroup per CU.
+// Items: (sample, step) = item / n_steps, item % n_steps for item < batch * n_steps; wave wv of workgroup b takes items
+// wv * gridDim.x + b, + gridDim.x * WAVES, ...: consecutive items go to consecutive CUs, every item is simulated and
+// written exactly once, by one wavefront, and no CU holds two items more than another.
+constexpr int solo_threads(int waves) { return waves * kWave; }
+// (word 8 + 8 * workgroups + b of a stamp buffer that long: see the stamps below)
+__host__ __device__ constexpr int64_t solo_timeline_words(int64_t workgroups) { return 8 + 8 * workgroups; }
+template <int LPR, int WAVES>
+__global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
+    const double* __restrict__ wu, const double* __restrict__ bu, double* __restrict__ y,
+    const unsigned char* __restrict__ tables, const QuadScalars d, const KScalars p) {
+  constexpr int kThreads = solo_threads(WAVES);
   using T = float;
   using C = V2<T>;
   using QT = LeanTables<T, 8>;
@@ -261,9 +276,12 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   // When the buffer holds 8 + 8 * gridDim.x words (d.stamp_words), wavefront 0 of EVERY workgroup b also stamps
   // s_memrealtime -- the same clock on every CU -- into words 8 + 8 b .. (tools/timeline_lean_solo.py): [0] entry,
   // [1] barrier passed, [2] / [3] end of the layers / of the tail of its first item, [4] / [5] of its second, [6] its
-  // last instruction; and the LAST wavefront of the workgroup, the younger one of its SIMD, [7] its last instruction.
+  // last instruction; and the LAST wavefront of the workgroup (WAVES - 1, the youngest of its SIMD, which may have no
+  // item), [7] its last instruction.  With one more word per workgroup behind those (9 * gridDim.x in all) the last
+  // wavefront of workgroup b that HAD an item stamps its last instruction into word 8 + 8 * gridDim.x + b.
   // The test is wave-uniform (a scalar branch per stamp); lane 0 stores.
-  const bool stamp_timeline = d.stamps != nullptr && (int64_t)d.stamp_words >= 8 + 8 * (int64_t)gridDim.x;
+  const bool stamp_timeline = d.stamps != nullptr && (int64_t)d.stamp_words >= solo_timeline_words(gridDim.x);
+  const bool stamp_last_item = stamp_timeline && (int64_t)d.stamp_words >= solo_timeline_words(gridDim.x) + (int64_t)gridDim.x;
   const bool stamp_wave = d.stamps != nullptr && wv == 0 && (blockIdx.x == 0 || stamp_timeline);
   const unsigned long long stamp_rt0 = stamp_wave ? __builtin_amdgcn_s_memrealtime() : 0ull;
   auto stamp = [&](int word, int tword) {
@@ -283,16 +301,19 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
 
   // ---- per-launch setup ----------------------------------------------------------------------------------------------
   // The workgroup fetches everything ONCE -- the phase entries of the 13 simulated layers (26 KiB, gathered into the
-  // lanes' own order) and the tangents -- and hands it over through LDS; behind the barrier every wavefront fills its
-  // phase registers from the LDS copy with 16-byte reads.  (Each wavefront used to read the whole phase table from
-  // global memory itself: eight times the bytes through the CU's vector L1, which took longer than an item's layers.)
+  // lanes' own order) and the tangents -- and hands it over through LDS; behind the barrier every wavefront reads a
+  // layer's entries from the LDS copy with two 16-byte reads, one layer ahead.  (Each wavefront used to read the whole
+  // phase table from global memory itself: eight times the bytes through the CU's vector L1, which took longer than an
+  // item's layers; then it kept all 13 layers' entries in 104 registers, which held a SIMD to two wavefronts.)
   // Every global load of it is issued before anything waits.  linear_up's weights and bias (56 KiB at 784 pixels) are
   // NOT in front of that barrier, where they doubled the setup (2.0 against 1.0 us): they are loaded right behind it,
   // fly under the first item's layers, and go to LDS behind a second workgroup barrier in front of the FIRST tail only.
   constexpr int kPhEntries = (LPR - 1) * QT::TL;                                  // phase entries of layers 1 .. LPR - 1
-  constexpr int kPhTrips = (kPhEntries + kSoloThreads - 1) / kSoloThreads;
+  constexpr int kPhTrips = (kPhEntries + kThreads - 1) / kThreads;
   // (Q <= kSoloMaxPixels: the host checks)
-  constexpr int kWTrips = 8 * solo_pairs_padded(kSoloMaxPixels) / kSoloThreads, kBTrips = kSoloMaxPixels / kSoloThreads;
+  constexpr int kWTrips = 8 * solo_pairs_padded(kSoloMaxPixels) / kThreads, kBTrips = kSoloMaxPixels / kThreads;
+  static_assert(8 * solo_pairs_padded(kSoloMaxPixels) % kThreads == 0 && kSoloMaxPixels % kThreads == 0,
+                "whole trips over the weights and the bias");
   C phstage[kPhTrips];
   D2 wreg[kWTrips];
   double breg[kBTrips];
@@ -301,12 +322,12 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
     for (int k = 0; k < kWTrips; ++k) {
       // (w_up in its own order, 16-byte chunk i = the unit i & 7 of pair i >> 3: the two rows of a pair are 128 contiguous
       //  bytes.  A chunk beyond the image loads the last one; its pixel is never stored)
-      const int i = tid + k * kSoloThreads;
+      const int i = tid + k * kThreads;
       wreg[k] = reinterpret_cast<const D2*>(wu)[i < 4 * Q ? i : 4 * Q - 1];
     }
 #pragma unroll
     for (int k = 0; k < kBTrips; ++k) {
-      const int i = tid + k * kSoloThreads;
+      const int i = tid + k * kThreads;
       breg[k] = bu != nullptr ? bu[i < Q ? i : Q - 1] : 0.0;
     }
   };
@@ -314,12 +335,12 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   auto hand_over_weights = [&]() {
 #pragma unroll
     for (int k = 0; k < kWTrips; ++k) {
-      const int i = tid + k * kSoloThreads;
+      const int i = tid + k * kThreads;
       if (i < 8 * PairsP) s_w[(i & 7) * WS + (i >> 3)] = wreg[k];
     }
 #pragma unroll
     for (int k = 0; k < kBTrips; ++k) {
-      const int i = tid + k * kSoloThreads;
+      const int i = tid + k * kThreads;
       if (i < 2 * PairsP) s_b[i] = breg[k];
     }
     __syncthreads();
@@ -328,7 +349,7 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   for (int k = 0; k < kPhTrips; ++k) {
     // LDS entry e = ((l - 1) * 2 + h) * 128 + lane * 2 + j: register r = 2 h + j of `lane` in layer l
     // (an entry beyond the table loads entry 0 and is not stored: no branch around a load, which would wait inside)
-    const int e = tid + k * kSoloThreads, ec = e < kPhEntries ? e : 0;
+    const int e = tid + k * kThreads, ec = e < kPhEntries ? e : 0;
     const int l = (ec >> 8) + 1, r = ((ec >> 6) & 2) | (ec & 1), ln = (ec >> 1) & 63;
     phstage[k] = g_ph[l * QT::TL + solo_table_slot(layout_of(l), r, ln)];
   }
@@ -340,10 +361,10 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   stamp(1, -1);
 #pragma unroll
   for (int k = 0; k < kPhTrips; ++k) {
-    const int e = tid + k * kSoloThreads;
+    const int e = tid + k * kThreads;
     if (e < kPhEntries) s_ph[e] = phstage[k];
   }
-  static_assert(LPR * 8 <= kSoloThreads, "one tangent per thread");
+  static_assert(LPR * 8 <= kThreads, "one tangent per thread");
   if (tid < LPR * 8) s_un[tid] = unreg;
   T pm[4];   // +-1 by this lane's index bit
 #pragma unroll
@@ -351,22 +372,11 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   __syncthreads();
   stamp(2, 1);
   load_weights();
-  // this lane's phase entries into registers, for all items of the wave (entry 0 unused: the first layer is generated)
-  C phr[LPR][4];
-#pragma unroll
-  for (int l = 1; l < LPR; ++l) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const V4 v = reinterpret_cast<const V4*>(s_ph)[((l - 1) * 2 + h) * kWave + lane];
-      phr[l][2 * h] = C{v.x, v.y};
-      phr[l][2 * h + 1] = C{v.z, v.w};
-    }
-  }
 
   // ---- the items of this wave ---------------------------------------------------------------------------------------
   const uint32_t n_steps = (uint32_t)d.n_steps;
-  const uint32_t stride = (uint32_t)gridDim.x * kSoloWaves;     // waves of the launch
-  const uint32_t g0 = (uint32_t)blockIdx.x * kSoloWaves + (uint32_t)wv;
+  const uint32_t stride = (uint32_t)gridDim.x * WAVES;          // waves of the launch
+  const uint32_t g0 = (uint32_t)wv * gridDim.x + (uint32_t)blockIdx.x;
   const uint32_t stride_q = stride / n_steps, stride_r = stride - stride_q * n_steps;
   int64_t sample = (int64_t)(g0 / n_steps);
   uint32_t step = g0 - (g0 / n_steps) * n_steps;
@@ -377,18 +387,24 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
     C a[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) a[r] = C{a0r[r], (T)0};
-    // a layer's tangents are read one layer ahead (the fence keeps the compiler from reading all layers' up front)
+    // a layer's tangents and this lane's phase entries (two 16-byte units: registers 0, 1 and 2, 3) are read one layer
+    // ahead (the fence keeps the compiler from reading all layers' up front)
     const V4* un4 = reinterpret_cast<const V4*>(s_un);
-    V4 lo = un4[2], hi = un4[3];
+    const V4* ph4 = reinterpret_cast<const V4*>(s_ph) + lane;
+    V4 lo = un4[2], hi = un4[3], p01 = ph4[0], p23 = ph4[kWave];
 #pragma unroll
     for (int l = 1; l < LPR; ++l) {
       const int ln = l + 1 < LPR ? l + 1 : l;
       const V4 nlo = un4[2 * ln], nhi = un4[2 * ln + 1];
+      const V4 np01 = ph4[(ln - 1) * 2 * kWave], np23 = ph4[((ln - 1) * 2 + 1) * kWave];
       __builtin_amdgcn_sched_barrier(0);
       const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
-      solo_layer(layout_of(l), a, phr[l], ts, hi.x, hi.y, hi.z, hi.w);
+      const C ph[4] = {C{p01.x, p01.y}, C{p01.z, p01.w}, C{p23.x, p23.y}, C{p23.z, p23.w}};
+      solo_layer(layout_of(l), a, ph, ts, hi.x, hi.y, hi.z, hi.w);
       lo = nlo;
       hi = nhi;
+      p01 = np01;
+      p23 = np23;
     }
     // ---- <Z_w>: the register-bit wires are signed in-lane sums, the lane-bit wires signed copies of the lane's total ----
     T pw[4];
@@ -407,7 +423,7 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
     for (int w = 0; w < 8; ++w)
       ev[w] = (double)read_lane(tot, logical_lane(((w >> 2) & 1) | (w & 2) | ((w & 1) << 2)));
     if (item < 2) stamp(3 + 2 * item, 2 + 2 * item);
-    if (item == 0) hand_over_weights();   // (the early wavefront of a SIMD waits here once for its partner)
+    if (item == 0) hand_over_weights();   // (an early wavefront waits here once for the workgroup's slowest)
     // ---- linear_up: the item's row, pair = lane + 64 g; per pixel two partial sums with explicit fma (as
     // dense_lean_kernel) and one add ------------------------------------------------------------------------------------
     double* yrow = y + (size_t)step * d.y_step_stride + sample * d.y_ld;
@@ -467,9 +483,17 @@ __device__ void dense_lean_solo_body(const double* __restrict__ wu, const double
   }
   if (g0 / n_steps >= (uint32_t)p.batch) hand_over_weights();   // (a wavefront without an item meets the barrier too)
   stamp(-1, 6);
-  if (stamp_timeline && wv == kSoloWaves - 1) {
+  if (stamp_timeline && wv == WAVES - 1) {
     const unsigned long long rt = __builtin_amdgcn_s_memrealtime();
     if (lane == 0) d.stamps[8 + 8 * (size_t)blockIdx.x + 7] = rt;
+  }
+  // (the last wavefront of this workgroup with a first item: the next one's would lie beyond the launch's items)
+  if (stamp_last_item) {
+    const uint64_t n_items = (uint64_t)p.batch * n_steps;
+    if (g0 < n_items && (wv == WAVES - 1 || (uint64_t)g0 + gridDim.x >= n_items)) {
+      const unsigned long long rt = __builtin_amdgcn_s_memrealtime();
+      if (lane == 0) d.stamps[solo_timeline_words(gridDim.x) + blockIdx.x] = rt;
+    }
   }
 }
 

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
-"""Diagnostic: where wavefront 0 of workgroup 0 of the one-wavefront-per-item body (csrc/qsim_lean_solo.h) spends its
+"""Diagnostic: where wavefront 0 of workgroup 0 of the one-wavefront-per-item kernel (csrc/qsim_lean_solo.h) spends its
 ticks (s_memtime stamps taken by lane 0): the per-workgroup setup, then the layers and the tail of its first two
 items.  "layers" is the item up to its read-out; "tail" is linear_up for the item's whole row, the weights read from LDS,
-and the row's stores.  QNN_noise(784, 8, 14), float32, the solo body forced; the benchmark launch (batch 256, 15 steps:
-3 840 items, two items per wavefront on 256 CUs, 1.875 in the mean) and a 240-item launch (one item per wavefront on 30
-workgroups).  A stamp is the issue time of the wavefront's instruction stream: work still in flight (stores above
-all) shows up in the next interval that waits for it; the first item's layers include the fill of the phase registers
-from LDS.  The last
+and the row's stores.  QNN_noise(784, 8, 14), float32, the solo kernel forced; the benchmark launch (batch 256, 15 steps:
+3 840 items, at 16 wavefronts per workgroup one item per wavefront on 256 CUs and wavefront 15 idle) and a 240-item
+launch (one item per wavefront on 30 workgroups of 8).  QIDDM_LEAN_SOLO_WAVES=8 / 16 in the environment forces the
+width (at 8 wavefront 0 has a second item in the benchmark launch).  A stamp is the issue time of the wavefront's instruction stream: work still in flight (stores above
+all) shows up in the next interval that waits for it; a layer's phase entries are read from LDS one layer ahead.  The last
 column is s_memrealtime (100 MHz) from entry to the last tail stamped, which gives the ticks their length.  Not a timing
 of the product path: compare with the kernel time of a profile.
     python tools/stamp_lean_solo.py"""

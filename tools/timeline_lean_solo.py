@@ -1,18 +1,27 @@
 #!/usr/bin/env python
-"""Diagnostic: the timeline of one launch of the one-wavefront-per-item body (csrc/qsim_lean_solo.h) over ALL its
-workgroups.  With a stamp buffer of 8 + 8 x (workgroups) words registered, wavefront 0 of every workgroup writes
+"""Diagnostic: the timeline of one launch of the one-wavefront-per-item kernel (csrc/qsim_lean_solo.h) over ALL its
+workgroups.  With a stamp buffer of 8 + 9 x (workgroups) words registered, wavefront 0 of every workgroup writes
 s_memrealtime -- a 100 MHz clock that is the same on every CU -- at its entry, behind the setup's barrier, at the end of
 the layers and of the tail (linear_up and the stores of the item's row) of its first two items, and as its last
-instruction; the workgroup's LAST wavefront, the younger one of its SIMD, stamps its last instruction too.  Printed, in
+instruction; the workgroup's LAST wavefront (WAVES - 1, the youngest of its SIMD, which may have no item) stamps its last
+instruction too, and so does the last wavefront of the workgroup that had an item (the ninth word).  Printed, in
 us (one tick = 0.01 us):
 dispatch skew (first entry -> last entry), the distribution of the workgroups' lifetimes and of their phases, first entry
 -> last exit, the kernel's duration from HIP events around the same launch replayed back to back in a graph, and the
-difference of the last two: the time of a launch that no stamped wavefront accounts for.  Wavefronts 0 and 7 are two of
-eight of their workgroup; the other six may leave later than wavefront 0, hardly later than wavefront 7.  QNN_noise(784, 8, 14), float32, the solo body forced; the
-benchmark launch (batch 256, 15 steps) and a 240-item launch.
-    python tools/timeline_lean_solo.py"""
-import os, sys
+difference of the last two: the time of a launch that no stamped wavefront accounts for.  The stamped wavefronts are
+two or three of the 8 or 16 of their workgroup; the others may leave later than wavefront 0, hardly later than the last
+one.  QNN_noise(784, 8, 14), float32, the solo kernel forced; the benchmark launch (batch 256, 15 steps) and a 240-item
+launch.  --waves 8 / 16 forces the kernel's width (QIDDM_LEAN_SOLO_WAVES); without it the host's rule holds (8 while
+items <= 8 x CUs, 16 above).  A library from before the kernel had two widths runs 8 whatever is asked: give it
+--waves 8 so that the tool cuts the launch as that library does.
+    python tools/timeline_lean_solo.py [--waves 8|16]"""
+import argparse, os, sys
+ap = argparse.ArgumentParser()
+ap.add_argument("--waves", type=int, choices=(8, 16), default=None)
+args = ap.parse_args()
 os.environ["QIDDM_LEAN_SOLO_MIN_ITEMS"] = "0"
+if args.waves:
+    os.environ["QIDDM_LEAN_SOLO_WAVES"] = str(args.waves)
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from qiddm_amd import _capi  # noqa: E402
@@ -21,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from microbench import timeit  # noqa: E402
 
 torch.manual_seed(0)
-P, n, WAVES = 784, 8, 8
+P, n = 784, 8
 circ = Circuit(n_qubits=n, encoding="rz", imprimitive="CZ", measure="expz", n_rounds=1, n_blocks=1, sel_layers=14)
 wd = (torch.randn(n, P, dtype=torch.float64) / P ** 0.5 * 3).cuda()
 bd = torch.randn(n, dtype=torch.float64).cuda()
@@ -42,29 +51,34 @@ def dist(v):
 for batch, steps in ((256, 15), (16, 15)):
     x = torch.rand(batch, P, dtype=torch.float64).cuda()
     call = lambda: dense_sample_lean(circ, x, wd, bd, wu, bu, steps, tables, "f32")
-    grid = min(-(-batch * steps // WAVES), cus)
+    WAVES = args.waves or (8 if batch * steps <= 8 * cus else 16)
+    grid = min(-(-batch * steps // 8), cus)   # (csrc/qiddm_lean.hip: lean_solo_grid, the same at both widths)
     _capi.lib().qiddm_set_stamp_buffer(None, 0)
     kernel_us = timeit(call, launches=50, reps=5)
-    buf = torch.zeros(8 + 8 * grid, dtype=torch.int64, device="cuda")
+    buf = torch.zeros(8 + 9 * grid, dtype=torch.int64, device="cuda")
     _capi.check(_capi.lib().qiddm_set_stamp_buffer(buf.data_ptr(), buf.numel()))
     stamped_us = timeit(call, launches=50, reps=5)
-    print(f"batch {batch}, {steps} steps, {batch * steps} items, {grid} workgroups; kernel (HIP events, graph of 50 launches): "
+    print(f"batch {batch}, {steps} steps, {batch * steps} items, {grid} workgroups of {WAVES} wavefronts; kernel (HIP events, graph of 50 launches): "
           f"{kernel_us:.2f} us without stamps, {stamped_us:.2f} us with")
     for rep in range(3):
         torch.cuda.synchronize()
         buf.zero_()
         call()
         torch.cuda.synchronize()
-        t = buf[8:].reshape(grid, 8).cpu()
+        t = buf[8:8 + 8 * grid].reshape(grid, 8).cpu()
+        last_item = buf[8 + 8 * grid:].cpu()   # (a library without that stamp leaves it 0)
         assert (t[:, 0] > 0).all() and (t[:, 6] >= t[:, 0]).all(), "a workgroup did not stamp"
         # (word 7: the last wavefront's exit; a body without that stamp leaves it 0)
-        first, last_entry, last_exit = t[:, 0].min().item(), t[:, 0].max().item(), t[:, 6:8].max().item()
+        first, last_entry = t[:, 0].min().item(), t[:, 0].max().item()
+        last_exit = max(t[:, 6:8].max().item(), last_item.max().item())
         span = (last_exit - first) / 100
         print(f"  launch {rep}: dispatch skew {(last_entry - first) / 100:5.2f}   first entry -> last exit {span:6.2f}   "
               f"kernel - that {kernel_us - span:6.2f}   first entry -> first exit {(t[:, 6].min().item() - first) / 100:6.2f}")
         print(f"    lifetime of a workgroup's wavefront 0   {dist((t[:, 6] - t[:, 0]).tolist())}")
         if (t[:, 7] > 0).all():
-            print(f"    wavefront 0's entry -> wavefront 7's exit {dist((t[:, 7] - t[:, 0]).tolist())}")
+            print(f"    wavefront 0's entry -> wavefront {WAVES - 1}'s exit {dist((t[:, 7] - t[:, 0]).tolist())}")
+        if (last_item > 0).all():
+            print(f"    ... -> exit of the last one with an item {dist((last_item - t[:, 0]).tolist())}")
         for k, name in enumerate(NAMES[:-1]):
             have = (t[:, k] > 0) & (t[:, k + 1] > 0)
             if have.any():

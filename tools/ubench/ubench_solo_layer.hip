@@ -2,8 +2,11 @@
 // bits 4..7 as register bits of two alternating layouts, eight swaps per layer) beside the layer it replaced (bits 4 / 5
 // by swap, 2 x 2, swap back per amplitude: solo_layer_swapback below),
 // next to ubench_layer.hip's four-wave layer: 13 layers per "step", s_memtime around `iters` steps, one workgroup of
-// W = 1, 2, 4, 8 wavefronts per CU on all 256 CUs (96 KiB of LDS per workgroup keep a second one off the CU), every
-// wavefront on an item of its own.  Phases in registers, tangents read from LDS one layer ahead, as the kernel does.
+// W = 1, 2, 4, 8 (12, 16) wavefronts per CU on all 256 CUs (96 KiB of LDS per workgroup keep a second one off the CU), every
+// wavefront on an item of its own.  Tangents read from LDS one layer ahead, as the kernel does; the phase entries
+// either in registers (104 VGPRs, two wavefronts per SIMD at most: the kernel before it went wide) or in LDS as
+// [layer][2][64] 16-byte units (LeanSoloLds) and read one layer ahead too, under a 1 024-thread bound (the shipped
+// kernel: W up to 16, four wavefronts per SIMD).
 // The four-wave layer costs 400 ticks for ONE item per CU (ubench_layer, "full layer as shipped"); W solo wavefronts
 // finish W items in the time printed here.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../qiddm_amd/csrc -o ubench_solo_layer ubench_solo_layer.hip
@@ -27,7 +30,8 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kLayers = 13;
 constexpr int kBlocks = 256;
-constexpr int kMaxWaves = 8;
+constexpr int kMaxWaves = 16;      // ... of the LDS variant; the registers variants stop at kRegWaves
+constexpr int kRegWaves = 8;
 constexpr size_t kLds = 96 * 1024;
 
 // the layer before the transposing one: one layout (A) throughout, index bits 4 / 5 through ry_t_swap
@@ -49,8 +53,12 @@ __device__ __forceinline__ void solo_layer_swapback(V2<float> (&a)[4], const V2<
   solo_ry_reg(a[1], a[3], t7);
 }
 
-template <bool TRANSPOSING>
-__global__ __launch_bounds__(kMaxWaves * 64) void solo_layer_loop(float* out, unsigned long long* ticks, int iters,
+enum Variant { kSwapBack, kTransposing, kTransposingLds };
+constexpr const char* kNames[] = {"swap-back      ", "transposing    ", "transposing LDS"};
+constexpr size_t kPhOffset = 1024;   // the phase units behind the tangents in LDS
+
+template <int V>
+__global__ __launch_bounds__((V == kTransposingLds ? kMaxWaves : kRegWaves) * 64) void solo_layer_loop(float* out, unsigned long long* ticks, int iters,
                                                                  const float* tab) {
   using T = float;
   using C = V2<T>;
@@ -58,13 +66,21 @@ __global__ __launch_bounds__(kMaxWaves * 64) void solo_layer_loop(float* out, un
   T* s_un = reinterpret_cast<T*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   for (int i = tid; i < (kLayers + 1) * 8; i += blockDim.x) s_un[i] = tab[i % 509] * 0.4f;
-  C ph[kLayers][4];
+  constexpr bool kLdsPhases = V == kTransposingLds;
+  auto phase_of = [&](int l, int r, int ln) {
+    const int i = (l * 4 + r) * 64 + ln;
+    return C{tab[(i * 2) % 509] * 0.9f + 0.05f, tab[(i * 2 + 1) % 509] * 0.3f};
+  };
+  C ph[kLdsPhases ? 1 : kLayers][4];
+  C* s_ph = reinterpret_cast<C*>(smem_raw + kPhOffset);   // unit (l, h, lane) = registers 2 h, 2 h + 1 of the lane
+  if constexpr (kLdsPhases) {
+    for (int e = tid; e < kLayers * 256; e += blockDim.x)
+      s_ph[e] = phase_of(e >> 8, ((e >> 6) & 2) | (e & 1), (e >> 1) & 63);
+  } else {
 #pragma unroll
-  for (int l = 0; l < kLayers; ++l) {
+    for (int l = 0; l < kLayers; ++l) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = (l * 4 + r) * 64 + lane;
-      ph[l][r] = C{tab[(i * 2) % 509] * 0.9f + 0.05f, tab[(i * 2 + 1) % 509] * 0.3f};
+      for (int r = 0; r < 4; ++r) ph[l][r] = phase_of(l, r, lane);
     }
   }
   T pm[4];
@@ -76,19 +92,38 @@ __global__ __launch_bounds__(kMaxWaves * 64) void solo_layer_loop(float* out, un
   for (int r = 0; r < 4; ++r) a[r] = C{0.01f * (float)(lane + 64 * r + 1), 0.02f};
   __syncthreads();
   const v4f* un4 = reinterpret_cast<const v4f*>(s_un);
+  const v4f* ph4 = reinterpret_cast<const v4f*>(s_ph) + lane;
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
   for (int it = 0; it < iters; ++it) {
     asm volatile("" ::: "memory");
-    v4f lo = un4[0], hi = un4[1];
+    v4f lo = un4[0], hi = un4[1], p01 = {}, p23 = {};
+    if constexpr (kLdsPhases) {
+      p01 = ph4[0];
+      p23 = ph4[64];
+    }
 #pragma unroll
     for (int l = 0; l < kLayers; ++l) {
       const v4f nlo = un4[2 * (l + 1)], nhi = un4[2 * (l + 1) + 1];
+      v4f np01 = {}, np23 = {};
+      if constexpr (kLdsPhases) {
+        const int ln = l + 1 < kLayers ? l + 1 : l;
+        np01 = ph4[ln * 128];
+        np23 = ph4[ln * 128 + 64];
+      }
       __builtin_amdgcn_sched_barrier(0);
       const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
-      if constexpr (TRANSPOSING) solo_layer(l % 2 == 0 ? kSoloLayoutB : kSoloLayoutA, a, ph[l], ts, hi.x, hi.y, hi.z, hi.w);
-      else solo_layer_swapback(a, ph[l], ts, hi.x, hi.y, hi.z, hi.w);
+      if constexpr (kLdsPhases) {
+        const C pl[4] = {C{p01.x, p01.y}, C{p01.z, p01.w}, C{p23.x, p23.y}, C{p23.z, p23.w}};
+        solo_layer(l % 2 == 0 ? kSoloLayoutB : kSoloLayoutA, a, pl, ts, hi.x, hi.y, hi.z, hi.w);
+      } else if constexpr (V == kTransposing) {
+        solo_layer(l % 2 == 0 ? kSoloLayoutB : kSoloLayoutA, a, ph[l], ts, hi.x, hi.y, hi.z, hi.w);
+      } else {
+        solo_layer_swapback(a, ph[l], ts, hi.x, hi.y, hi.z, hi.w);
+      }
       lo = nlo;
       hi = nhi;
+      p01 = np01;
+      p23 = np23;
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) a[r] = a[r] * C{0.05f, 0.05f};   // keep the values bounded
@@ -98,10 +133,10 @@ __global__ __launch_bounds__(kMaxWaves * 64) void solo_layer_loop(float* out, un
   out[(size_t)blockIdx.x * (kMaxWaves * 64) + tid] = (a[0].x + a[1].y) + (a[2].x + a[3].y);
 }
 
-template <bool TRANSPOSING>
+template <int V>
 static double run(float* out, unsigned long long* ticks, const float* tab, int iters, int waves) {
   for (int rep = 0; rep < 2; ++rep) {
-    hipLaunchKernelGGL(solo_layer_loop<TRANSPOSING>, dim3(kBlocks), dim3(waves * 64), kLds, 0, out, ticks, iters, tab);
+    hipLaunchKernelGGL(solo_layer_loop<V>, dim3(kBlocks), dim3(waves * 64), kLds, 0, out, ticks, iters, tab);
     CHECK(hipGetLastError());
     CHECK(hipDeviceSynchronize());
   }
@@ -116,7 +151,7 @@ static double run(float* out, unsigned long long* ticks, const float* tab, int i
     }
   const double per = sum / (kBlocks * waves) / ((double)iters * kLayers);
   printf("  %s  %d solo wavefront(s) per CU: %7.1f ticks/layer (slowest wavefront %7.1f), %7.1f ticks per item-layer\n",
-         TRANSPOSING ? "transposing" : "swap-back  ", waves, per, mx / ((double)iters * kLayers), per / waves);
+         kNames[V], waves, per, mx / ((double)iters * kLayers), per / waves);
   return per;
 }
 
@@ -129,15 +164,18 @@ int main() {
   std::vector<float> h(512);
   for (int i = 0; i < 512; ++i) h[i] = (float)((i * 2654435761u) % 1000) / 1000.0f;
   CHECK(hipMemcpy(tab, h.data(), 512 * sizeof(float), hipMemcpyHostToDevice));
-  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop<false>),
+  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop<kSwapBack>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop<true>),
+  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop<kTransposing>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+  CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(solo_layer_loop<kTransposingLds>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
   const int iters = 400;
   for (int rep = 0; rep < 3; ++rep) {
     printf("run %d\n", rep);
-    for (int waves : {1, 2, 4, 8}) run<false>(out, ticks, tab, iters, waves);
-    for (int waves : {1, 2, 4, 8}) run<true>(out, ticks, tab, iters, waves);
+    for (int waves : {1, 2, 4, 8}) run<kSwapBack>(out, ticks, tab, iters, waves);
+    for (int waves : {1, 2, 4, 8}) run<kTransposing>(out, ticks, tab, iters, waves);
+    for (int waves : {1, 2, 4, 8, 12, 16}) run<kTransposingLds>(out, ticks, tab, iters, waves);
   }
   return 0;
 }
