@@ -231,6 +231,13 @@ TRAJ_GRAD_SIGNATURES = {
     "qiddm_mixed_traj_backward_workspace_bytes": (_i64, [_i32, _i32, _i64, _i32, _ops, _i32, _i32, _i32, _i32, _i32]),
     "qiddm_mixed_traj_backward": (_int, _mixed + [_i32, _dbl, _dbl, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp] + _ws + _stream),
 }
+# include/qiddm_hip_traj_shots.h (finite shots on the trajectory engine): again a header and a table of its own, so that
+# the three tables above hold what they held.  tests/test_mixed_traj_shots_capi.py checks it against its header.
+TRAJ_SHOTS_SIGNATURES = {
+    "qiddm_mixed_traj_shots_workspace_bytes": (_i64, [_i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32]),
+    "qiddm_mixed_traj_shots_forward": (_int, _mixed + [_i32, _i32, _dbl, _dbl, _i32, _vp, _i64, _vp, _vp, _vp] + _ws + _stream),
+}
+TRAJ_SHOTS_PER_TRAJ = 1 << 16  # most shots one trajectory draws: ceil(shots / trajectories) may not exceed it
 
 
 _lock = threading.Lock()
@@ -255,9 +262,10 @@ def _declare(handle):
 
 
 def _declare_extensions(handle):
-    """``restype`` / ``argtypes`` of every entry of ``TRAJ_SIGNATURES`` and ``TRAJ_GRAD_SIGNATURES`` (after ``_declare`` has
-    accepted the library's version); a library without one of them is a stale build."""
-    for name, (restype, argtypes) in {**TRAJ_SIGNATURES, **TRAJ_GRAD_SIGNATURES}.items():
+    """``restype`` / ``argtypes`` of every entry of ``TRAJ_SIGNATURES``, ``TRAJ_GRAD_SIGNATURES`` and
+    ``TRAJ_SHOTS_SIGNATURES`` (after ``_declare`` has accepted the library's version); a library without one of them is
+    a stale build."""
+    for name, (restype, argtypes) in {**TRAJ_SIGNATURES, **TRAJ_GRAD_SIGNATURES, **TRAJ_SHOTS_SIGNATURES}.items():
         try:
             fn = getattr(handle, name)
         except AttributeError:

@@ -23,8 +23,11 @@
 // QIDDM_MIX_KRAUS / QIDDM_MIX_KRAUS2 and refuses what a trajectory cannot do (superoperator kinds, SHOTS, RHO); without the flag nothing
 // above reads differently.  Its reverse sweep (qsim_traj_adjoint.h; include/qiddm_hip_traj_grad.h) follows it: the same
 // checks, then the backward's own (no later state preparation, the gate-row overlap refusal, the gradient pointers).
+// Its sampled read-out (qsim_traj_shots.h; include/qiddm_hip_traj_shots.h; the last two entry points of this file) shares
+// that validator too: the Engine's `sampled` flag refuses a measurement table beside the density-matrix read-out.
 #include "capi_common.h"
 #include "../../include/qiddm_hip_traj_grad.h"
+#include "../../include/qiddm_hip_traj_shots.h"
 
 #include <hip/hip_runtime.h>
 
@@ -41,6 +44,7 @@
 #include "qsim_mixed_wide_adjoint.h"
 #include "qsim_traj.h"
 #include "qsim_traj_adjoint.h"
+#include "qsim_traj_shots.h"
 
 namespace {
 
@@ -130,8 +134,17 @@ struct Engine {
   const char* name;
   int min_qubits, max_qubits;
   bool traj = false;  // the trajectory engine (qsim_traj.h): a pure state, QIDDM_MIX_KRAUS, no superoperators / SHOTS / RHO
+  bool sampled = false;  // its sampled read-out (qsim_traj_shots.h): PROBS and EXPZ only, no measurement table
 };
 constexpr Engine kOneWorkgroup{"", 1, 8}, kTileFused{"tile-fused ", 7, 10}, kTrajectories{"trajectory ", 1, 16, true};
+constexpr Engine kTrajectoryShots{"trajectory ", 1, 16, true, true};
+
+// shots count outcomes of the computational basis: a table of Pauli words has no sampled read-out on trajectories
+int refuse_sampled_table() {
+  return fail(QIDDM_ERR_UNSUPPORTED,
+              "a measurement table on sampled trajectories: words of I and Z are signed sums of the sampled probs "
+              "(QIDDM_MEAS_PROBS), words with X or Y need a basis rotation in front of the read-out");
+}
 
 int check_wires(int32_t n, const Engine& e) {
   if (e.traj && (n < e.min_qubits || n > e.max_qubits))
@@ -375,6 +388,7 @@ int check_call(MixedCall& c, const Engine& e, bool* embeds) {
     return fail(QIDDM_ERR_UNSUPPORTED,
                 "a density-matrix read-out on trajectories: a trajectory holds a pure state; use qiddm_mixed_forward / "
                 "qiddm_mixed_wide_forward (measure QIDDM_MEAS_RHO, QIDDM_MIX_RHO)");
+  if (e.sampled && (c.measure == QIDDM_MEAS_OBS || c.n_obs > 0)) return refuse_sampled_table();
   if (c.measure == QIDDM_MEAS_RHO && !c.rho_mask)
     return fail(QIDDM_ERR_INVALID, "measure QIDDM_MEAS_RHO needs a density-matrix read-out as the last op (QIDDM_MIX_RHO)");
   if (c.measure != QIDDM_MEAS_RHO && c.rho_mask)
@@ -1450,6 +1464,127 @@ int qiddm_mixed_traj_backward(int32_t n_qubits, int32_t dtype, const qiddm_mixed
   hipLaunchKernelGGL(qiddm::mixed_traj_grad_finalize, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, acc, grad_rows,
                      grad_gates, grad_features, batch, tr, b);
   return launched("mixed_traj_grad_finalize");
+}
+
+}  // extern "C"
+
+// ---- trajectories, finite shots (qsim_traj_shots.h; include/qiddm_hip_traj_shots.h) ---------------------------------------
+namespace {
+
+struct TrajShotsGeometry {
+  int64_t t_run, slots, blocks, psi_bytes, off_counts, off_flags, off_slabs, total;
+  bool in_lds;
+};
+
+// `width`: 2^n (PROBS) or n (EXPZ).  T_run = min(n_traj, shots) trajectories draw a shot; the slots are min(T_run, 64)
+TrajShotsGeometry traj_shots_geometry(int32_t n, int32_t dtype, int64_t batch, int64_t n_traj, int64_t shots, int32_t n_ops,
+                                      int64_t width, int32_t max_blocks) {
+  TrajShotsGeometry g;
+  g.t_run = std::min<int64_t>(n_traj, shots);
+  g.slots = traj_slots(g.t_run);
+  g.psi_bytes = ((int64_t)1 << n) * (dtype == QIDDM_F32 ? 8 : 16);
+  g.in_lds = (size_t)g.psi_bytes <= kMixedLdsSlab;
+  const int64_t rows = std::max<int64_t>(batch, 1), items = rows * g.slots;
+  g.blocks = std::min<int64_t>(items, g.in_lds ? kTrajLdsBlocks : kTrajSlabBlocks);
+  if (max_blocks > 0 && g.blocks > max_blocks) g.blocks = max_blocks;
+  g.off_counts = program_bytes(n_ops);
+  g.off_flags = g.off_counts + round256(rows * width * 4);
+  g.off_slabs = g.off_flags + round256(rows * 4);
+  g.total = g.off_slabs + (g.in_lds ? 0 : g.blocks * g.psi_bytes);
+  return g;
+}
+
+int check_traj_shots(int32_t n_traj, int32_t shots) {
+  if (shots < 1) return fail(QIDDM_ERR_INVALID, "shots %d out of range", shots);
+  const int64_t per = ((int64_t)shots + n_traj - 1) / n_traj;
+  if (per > qiddm::kTrajShotsPerTraj)
+    return fail(QIDDM_ERR_INVALID, "%d shots per trajectory: at most %d (raise n_traj)", (int)per, qiddm::kTrajShotsPerTraj);
+  return QIDDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t qiddm_mixed_traj_shots_workspace_bytes(int32_t n_qubits, int32_t dtype, int64_t batch, int32_t n_traj,
+                                               int32_t shots, int32_t n_ops, int32_t measure, int32_t max_blocks) {
+  int rc = check_sizes(n_qubits, dtype, batch, n_ops, kTrajectoryShots);
+  if (rc == QIDDM_OK) rc = check_traj_count(n_traj);
+  if (rc == QIDDM_OK && measure == QIDDM_MEAS_OBS) rc = refuse_sampled_table();
+  if (rc == QIDDM_OK && measure != QIDDM_MEAS_PROBS && measure != QIDDM_MEAS_EXPZ)
+    rc = measure == QIDDM_MEAS_RHO ? fail(QIDDM_ERR_UNSUPPORTED, "a density-matrix read-out on trajectories: a trajectory holds a pure state")
+                                   : fail(QIDDM_ERR_INVALID, "unknown measure %d", measure);
+  if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc == QIDDM_OK) rc = check_traj_shots(n_traj, shots);
+  if (rc != QIDDM_OK) return rc;
+  const int64_t width = measure == QIDDM_MEAS_PROBS ? ((int64_t)1 << n_qubits) : n_qubits;
+  return traj_shots_geometry(n_qubits, dtype, batch, n_traj, shots, n_ops, width, max_blocks).total;
+}
+
+int qiddm_mixed_traj_shots_forward(int32_t n_qubits, int32_t dtype, const qiddm_mixed_op_t* program, int32_t n_ops,
+                                   const double* angle_rows, int64_t rows_ld, int32_t n_rows, const double* features,
+                                   int64_t feat_ld, int32_t n_features, double enc_offset, double pad_with,
+                                   const double* gates, int32_t n_gates, int32_t measure, int64_t batch, int32_t n_traj,
+                                   int32_t shots, double seed, double offset, int32_t max_blocks, double* out,
+                                   int64_t out_ld, double* per_traj, int32_t* branches, int32_t* outcomes, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+  MixedCall c{n_qubits, dtype, program, n_ops, angle_rows, rows_ld, n_rows, features, feat_ld, n_features,
+              enc_offset, pad_with, gates, n_gates, measure, batch};
+  bool embeds = false;
+  int rc = check_call(c, kTrajectoryShots, &embeds);
+  if (rc == QIDDM_OK) rc = check_traj_count(n_traj);  // these six: refused for an empty batch as well
+  if (rc == QIDDM_OK && !is_counter_word(seed))
+    rc = fail(QIDDM_ERR_INVALID, "trajectory seed %g is not an integer in [0, 2^53)", seed);
+  if (rc == QIDDM_OK && !(is_counter_word(offset) && offset < 4294967296.0))
+    rc = fail(QIDDM_ERR_INVALID, "trajectory offset %g is not an integer in [0, 2^32)", offset);
+  if (rc == QIDDM_OK) rc = check_max_blocks(max_blocks);
+  if (rc == QIDDM_OK) rc = check_traj_shots(n_traj, shots);
+  if (rc != QIDDM_OK || batch == 0) return rc;
+  if ((rc = check_forward_outputs(c, out, out_ld)) != QIDDM_OK) return rc;
+  const TrajShotsGeometry g = traj_shots_geometry(n_qubits, dtype, batch, n_traj, shots, n_ops, c.width(), max_blocks);
+  if ((rc = check_workspace(workspace, workspace_bytes, g.total, "qiddm_mixed_traj_shots_workspace_bytes")) != QIDDM_OK)
+    return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  if ((rc = upload(ws, program, (size_t)n_ops * sizeof(qiddm_mixed_op_t), st)) != QIDDM_OK) return rc;
+  // the counts and the flags are one stretch of the workspace: one clear, on the stream, in front of the kernel
+  if (const hipError_t e = hipMemsetAsync(ws + g.off_counts, 0, (size_t)(g.off_slabs - g.off_counts), st); e != hipSuccess)
+    return fail(QIDDM_ERR_LAUNCH, "count reset failed: %s", hipGetErrorString(e));
+  const qiddm::MixedScalars m = make_scalars(c, c.n_body(), n_features, out_ld, g.in_lds);
+  qiddm::TrajScalars tr{};
+  tr.n_traj = n_traj;
+  tr.n_slots = (int32_t)g.slots;
+  tr.width = (int32_t)c.width();
+  for (int i = 0; i < c.n_body(); ++i) tr.n_channels += qiddm::traj_is_channel(program[i].kind) ? 1 : 0;
+  const uint64_t seed_word = (uint64_t)seed;
+  tr.seed_lo = (uint32_t)seed_word;
+  tr.seed_hi = (uint32_t)(seed_word >> 32);
+  tr.offset = (uint32_t)(uint64_t)offset;
+  tr.slab_in_lds = g.in_lds ? 1 : 0;
+  qiddm::TrajShotScalars sh{};
+  sh.shots = shots;
+  sh.t_run = (int32_t)g.t_run;
+  sh.per = shots / n_traj;
+  sh.extra = shots % n_traj;
+  const size_t smem = g.in_lds ? (size_t)g.psi_bytes : 0;
+  const qiddm::MixedOp* prog = reinterpret_cast<const qiddm::MixedOp*>(ws);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + g.off_counts);
+  uint32_t* flags = reinterpret_cast<uint32_t*>(ws + g.off_flags);
+  rc = for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const auto run = [&](auto k2) {  // as the analytic launch: the two-wire Kraus op only for a program that holds one
+      return launch<qiddm::mixed_traj_shots_kernel<T, decltype(k2)::value>>(
+          kMaxLds - 4096 /* the kernel also has 2.7 KiB of static LDS */, dim3((unsigned)g.blocks), dim3(256), smem, st,
+          "mixed_traj_shots_kernel", prog, angle_rows, features, gates, counts, flags,
+          reinterpret_cast<qiddm::V2<T>*>(ws + g.off_slabs), per_traj, branches, outcomes, m, tr, sh);
+    };
+    return has_kraus2(program, c.n_body()) ? run(std::true_type{}) : run(std::false_type{});
+  });
+  if (rc != QIDDM_OK) return rc;
+  const int64_t elems = batch * c.width();
+  hipLaunchKernelGGL(qiddm::mixed_traj_shots_finalize, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, counts, flags,
+                     out, out_ld, batch, (int32_t)c.width(), measure, shots);
+  return launched("mixed_traj_shots_finalize");
 }
 
 }  // extern "C"

@@ -114,8 +114,22 @@ than eight reduced to at most four through the Choi matrix, ``kraus_rows``) as r
 which is exact).  Measured: probs (all wires or a subset), the PauliZ list, Pauli words and Hamiltonians.  Such a device
 does not consult ``set_max_wires`` (it guards the density-matrix workspaces), takes the device's next stream offset per
 execution as a sampled one does, and is forward only by default: a parameter that requires grad in grad mode raises
-``qml.QuantumFunctionError``, stream capture ``RuntimeError``, two-wire channels, ``shots`` on the same device and the
-read-outs of rho ``NotImplementedError``, each before an offset is taken.
+``qml.QuantumFunctionError``, stream capture ``RuntimeError``, two-wire channels, ``shots`` on the same device (without
+``set_trajectory_shots``) and the read-outs of rho ``NotImplementedError``, each before an offset is taken.
+
+``set_trajectory_shots(True)`` / ``with trajectory_shots():`` (read when the device is constructed) admits
+``qml.device("default.mixed", wires=n, trajectories=T, shots=S, seed=s, readout_prob=q)``: a shot-limited read-out on the
+register sizes the trajectory engine exists for (``_Launch.traj_shots_forward``, ``qiddm_mixed_traj_shots_forward``,
+include/qiddm_hip_traj_shots.h; tests/_mixed_traj_shots_ref.py restates the rule).  The trajectories are the analytic ones,
+decision for decision; trajectory t draws S div T shots (the first S mod T one more; S < T runs only the first S) from
+its |psi_k|^2 inside the launch, through a two-level CDF (256 segment sums in LDS, then a walk over psi), and the counts
+are integers, so reruns and any grid give the same bits.  ``shots == trajectories`` is one noise realisation per shot, as
+hardware does it, and the recommended setting.  ``execute_trajectories`` then uses the measurement plan of sampled
+executions: probs of all wires, marginal probs, the PauliZ list, and words and Hamiltonians of I and Z as ``("signed",
+signs)`` sums of the sampled probs; a float ``readout_prob`` is a BitFlip decision per wire inside every trajectory.
+Refused before an offset is taken: words with X or Y (``NotImplementedError``), a parameter that requires grad in grad mode
+(``qml.QuantumFunctionError``, with ``trajectory_grad`` on as well), stream capture, the read-outs of rho; at construction
+more than 65536 shots per trajectory (``ValueError``).
 
 ``set_trajectory_channel2(True)`` / ``with trajectory_channel2():`` admits the two-wire channels of the density-matrix
 engines -- ``qml.QubitChannel`` with 4 x 4 operators, ``qml.PauliError("XZ", p, wires=[a, b])`` -- on a trajectories
@@ -124,7 +138,7 @@ rows per operator, at most sixteen operators, more reduced through the 16 x 16 C
 once), one decision among its operators from the pair's reduced 4 x 4 matrix.  Off by default, because the refusal is part
 of the tested surface; off, the ``NotImplementedError`` also says how to turn the op on.  Still refused with the switch on:
 three-wire channels, per-sample parameters of such a channel, a two-wire channel whose own parameter requires grad (by
-name, as for the one-wire ones: its rows are built on the host), ``shots``, the read-outs of rho and stream capture.  Not
+name, as for the one-wire ones: its rows are built on the host), ``shots`` (without ``set_trajectory_shots``), the read-outs of rho and stream capture.  Not
 measured: the 16-wire nets with such a noise model end to end.
 
 ``set_trajectory_grad(True)`` / ``with trajectory_grad():`` turns its reverse sweep on (``_TrajFunction``,
@@ -528,6 +542,32 @@ def trajectory_channel2(on: bool = True):
         yield
     finally:
         set_trajectory_channel2(before)
+
+
+# whether a trajectories device takes ``shots`` (``qiddm_mixed_traj_shots_forward``); off: the refusal it always gave
+_trajectory_shots = False
+
+
+def set_trajectory_shots(on: bool) -> None:
+    """Let ``qml.device("default.mixed", ..., trajectories=T, shots=S)`` be created: every execution then draws S
+    computational-basis shots per sample from its trajectories inside the launch, trajectory t its share of them
+    (include/qiddm_hip_traj_shots.h).  ``shots == trajectories`` is one noise realisation per shot, as hardware does it.
+    Read when the device is constructed.  Off by default: ``shots`` with ``trajectories`` then raises as before."""
+    global _trajectory_shots
+    if not isinstance(on, bool):
+        raise ValueError(f"set_trajectory_shots takes True or False (got {on!r})")
+    _trajectory_shots = on
+
+
+@contextlib.contextmanager
+def trajectory_shots(on: bool = True):
+    """``with mixed.trajectory_shots(): ...`` -- ``set_trajectory_shots`` for the duration of a block."""
+    before = _trajectory_shots
+    set_trajectory_shots(on)
+    try:
+        yield
+    finally:
+        set_trajectory_shots(before)
 
 
 def rot_matrices(weights: torch.Tensor) -> torch.Tensor:
@@ -1034,7 +1074,7 @@ def lower(tape, ret, n, readout_prob=None, shots=None, seed=0, offset=0, traj=Fa
             base = low._add_gates(channel_rows("BitFlip", readout_prob))  # the same four rows for every wire
             for w in all_w:
                 low.op(_capi.MIX_CHANNEL, w, base)
-    if shots is not None:
+    if shots is not None and not traj:  # (sampled trajectories: `shots` is an argument of their entry point, not an op)
         low.op(_capi.MIX_SHOTS, 0, int(shots), float(seed), float(offset))
     # measurement
     low.single = single and form == "obs"
@@ -1131,6 +1171,30 @@ class _Launch:
         _capi.launch("qiddm_mixed_traj_forward", self.device, *self._prefix(rows, gates, feats), n_traj, float(seed),
                      float(offset), max_blocks, out, out.stride(0), per_traj, branches, ws, ws.numel())
         return (out, per_traj, branches) if diagnostics else out
+
+    def traj_shots_forward(self, rows, gates, feats, n_traj, shots, seed, offset, max_blocks=0, diagnostics=False):
+        """The estimate from `shots` computational-basis shots per sample, drawn from `n_traj` quantum trajectories inside
+        the launch (``qiddm_mixed_traj_shots_forward``; PROBS or EXPZ).  `diagnostics`: -> (estimate, per_traj (B, T_run,
+        2^n) float64: the weights the sampler used, branches (B, T_run, channel ops) int32, outcomes (B, shots) int32),
+        T_run = min(n_traj, shots)."""
+        n, batch = self.n, self.batch
+        width = (1 << n) if self.measure == _capi.MEAS_PROBS else n
+        out = torch.empty(batch, width, dtype=torch.float64, device=self.device)
+        per_traj = branches = outcomes = None
+        if diagnostics:
+            n_channels = sum(op.kind in (_capi.MIX_PHASE_DAMP, _capi.MIX_AMP_DAMP, _capi.MIX_DEPOL, _capi.MIX_KRAUS,
+                                         _capi.MIX_KRAUS2)
+                             for op in self.prog)
+            t_run = min(n_traj, shots)
+            per_traj = torch.empty(batch, t_run, 1 << n, dtype=torch.float64, device=self.device)
+            branches = torch.empty(batch, t_run, n_channels, dtype=torch.int32, device=self.device)
+            outcomes = torch.empty(batch, shots, dtype=torch.int32, device=self.device)
+        ws = self._fresh(_capi.query("qiddm_mixed_traj_shots_workspace_bytes", n, self.prec, batch, n_traj, shots,
+                                     len(self.prog), self.measure, max_blocks))
+        _capi.launch("qiddm_mixed_traj_shots_forward", self.device, *self._prefix(rows, gates, feats), n_traj, shots,
+                     float(seed), float(offset), max_blocks, out, out.stride(0), per_traj, branches, outcomes, ws,
+                     ws.numel())
+        return (out, per_traj, branches, outcomes) if diagnostics else out
 
     def traj_backward(self, rows, gates, feats, grad_out, n_traj, seed, offset, max_blocks=0, diagnostics=False):
         """The mean gradient over the `n_traj` trajectories that ``traj_forward`` ran for the same (seed, offset)
@@ -1285,8 +1349,12 @@ def execute_trajectories(tape, ret, n, precision, qdev):
     stream offset once the circuit has been accepted."""
     from . import qml
     readout_prob = getattr(qdev, "readout_prob", None)
+    shots = getattr(qdev, "shots", None)  # sampled trajectories (``set_trajectory_shots``): forward only, whatever the switches
     wants_grad = torch.is_grad_enabled() and (any(torch.is_tensor(p) and p.requires_grad for t in tape for p in t.params)
                                               or (torch.is_tensor(readout_prob) and readout_prob.requires_grad))
+    if wants_grad and shots is not None:
+        raise qml.QuantumFunctionError("finite shots have no reverse sweep on trajectories either (with or without "
+                                       "mixed.set_trajectory_grad); sample under torch.no_grad() or use shots=None")
     if wants_grad and not _trajectory_grad:
         raise qml.QuantumFunctionError("quantum trajectories have no reverse sweep unless it is turned on "
                                        "(mixed.set_trajectory_grad(True) or `with mixed.trajectory_grad():`); run under "
@@ -1310,7 +1378,9 @@ def execute_trajectories(tape, ret, n, precision, qdev):
         raise NotImplementedError("state, density_matrix, purity and expval(Hermitian) on a trajectories device: a "
                                   "trajectory holds a pure state, not rho; use default.mixed without trajectories (up to "
                                   "10 wires)")
-    low, measure = lower(tape, ret, n, readout_prob, None, traj=True)
+    # with shots the plan of a sampled execution: words with X or Y are refused, words of I and Z are signed sums of the
+    # sampled probs, a float readout_prob is one BitFlip decision per wire inside every trajectory
+    low, measure = lower(tape, ret, n, readout_prob, shots, traj=True)
     if low.device is None:
         raise RuntimeError("default.mixed runs on the GPU only: no tensor argument lives on a HIP device (no CPU path)")
     offset = qdev.next_offset()  # the circuit has been accepted: this execution has a stream of its own
@@ -1326,12 +1396,17 @@ def execute_trajectories(tape, ret, n, precision, qdev):
     feats = keep(low.features).to(**f64).contiguous() if low.features is not None else None
     if feats is not None and feats.shape[0] != batch:
         feats = feats.expand(batch, -1).contiguous()
-    if wants_grad and any(v is not None and v.requires_grad for v in (rows, gates, feats)):
+    if shots is not None:
+        out = launch.traj_shots_forward(rows, gates, feats, qdev.trajectories, shots, qdev.seed, offset % (1 << 32),
+                                        traj_max_blocks)
+    elif wants_grad and any(v is not None and v.requires_grad for v in (rows, gates, feats)):
         out = _TrajFunction.apply(launch, rows, gates, feats, qdev.trajectories, qdev.seed, offset % (1 << 32))
     else:
         out = launch.traj_forward(rows, gates, feats, qdev.trajectories, qdev.seed, offset % (1 << 32), traj_max_blocks)
-    if low.post is not None:  # ("marginal", wires): the only post-processing an analytic lowering asks for
+    if low.post is not None and low.post[0] == "marginal":
         out = _marginal(out, low.post[1], n, batch)
+    elif low.post is not None:  # ("signed", signs): words of I and Z from the sampled full probs
+        out = out @ torch.from_numpy(low.post[1]).to(out)
     if low.single:
         out = out[:, 0]
     return out if low.batched else out[0]

@@ -624,8 +624,15 @@ class Device:
             if not 1 <= self.num_wires <= 16:
                 raise ValueError(f"a trajectories device takes 1 to 16 wires (got {self.num_wires})")
             if self.shots is not None:
-                raise NotImplementedError("shots together with trajectories: a trajectory's read-out is analytic; use "
-                                          "shots on default.mixed without trajectories, or trajectories alone")
+                from . import mixed as _mixed
+                if not _mixed._trajectory_shots:
+                    raise NotImplementedError("shots together with trajectories: a trajectory's read-out is analytic; use "
+                                              "shots on default.mixed without trajectories, or trajectories alone -- or "
+                                              "turn the sampled read-out of trajectories on "
+                                              "(mixed.set_trajectory_shots(True) or `with mixed.trajectory_shots():`)")
+                if -(-self.shots // int(trajectories)) > _capi.TRAJ_SHOTS_PER_TRAJ:
+                    raise ValueError(f"shots={self.shots} over trajectories={trajectories}: at most "
+                                     f"{_capi.TRAJ_SHOTS_PER_TRAJ} shots per trajectory (raise trajectories)")
             self.trajectories = int(trajectories)
         if seed is not None:
             self.seed = int(seed)
@@ -645,7 +652,8 @@ class Device:
         kind = "density-matrix" if self.mixed else "statevector"
         extra = "" if self.shots is None else f", shots={self.shots}, seed={self.seed}"
         if self.trajectories is not None:
-            extra = f", trajectories={self.trajectories}, seed={self.seed}"
+            shots = "" if self.shots is None else f", shots={self.shots}"
+            extra = f", trajectories={self.trajectories}{shots}, seed={self.seed}"
         if self.readout_prob is not None:
             extra += f", readout_prob={self.readout_prob}"
         return f"<qiddm_amd HIP {kind} device standing in for {self.short_name!r}, wires={self.num_wires}{extra}>"
@@ -682,8 +690,16 @@ def device(name, wires=1, shots=None, readout_prob=None, seed=None, trajectories
     the one-wire channels (the three native ones with float, 0-d or per-sample strengths; ``BitFlip``, ``PhaseFlip``,
     one-letter ``PauliError``, ``GeneralizedAmplitudeDamping``, ``ResetError``, ``ThermalRelaxationError``, one-wire
     ``QubitChannel``; a float ``readout_prob``) are accepted, and ``probs`` (all wires or a subset), the ``PauliZ`` list and
-    ``expval`` of Pauli words and Hamiltonians are measured.  Refused before a stream offset is taken: ``shots`` on the
-    same device and two-wire channels (``NotImplementedError``; ``mixed.set_trajectory_channel2(True)`` or ``with
+    ``expval`` of Pauli words and Hamiltonians are measured.  ``shots=S`` on the same device is taken once
+    ``mixed.set_trajectory_shots(True)`` (or ``with mixed.trajectory_shots():``) is on when the device is created: every
+    execution then draws S computational-basis shots per sample from its trajectories inside the launch -- trajectory t
+    draws S div T of them, the first S mod T one more, and with S < T only the first S trajectories run -- and returns
+    ``probs`` (all wires or a subset), the ``PauliZ`` list, or words and Hamiltonians of I and Z estimated from those
+    shots; a float ``readout_prob`` flips every wire inside each trajectory.  ``shots == trajectories`` is one noise
+    realisation per shot, as hardware does it, and the recommended setting.  Still refused under shots: words with X or Y
+    (``NotImplementedError``), a parameter that requires grad (``QuantumFunctionError``, also with the reverse sweep on)
+    and more than 65536 shots per trajectory (``ValueError``).  Refused before a stream offset is taken: ``shots`` without
+    that switch and two-wire channels (``NotImplementedError``; ``mixed.set_trajectory_channel2(True)`` or ``with
     mixed.trajectory_channel2():`` admits ``QubitChannel`` with 4 x 4 operators and two-letter ``PauliError`` as one
     decision among at most sixteen Kraus operators), ``state`` / ``density_matrix`` / ``purity`` /
     ``Hermitian`` (``NotImplementedError``), a parameter that requires grad in grad mode (``QuantumFunctionError``;
