@@ -57,16 +57,18 @@ qiddm::KScalars params_of(const qiddm_circuit_t* c) {
 
 // When the instance that carries both bodies (qsim_lean.h: lean_has_solo) runs the one-wavefront-per-item body: from
 // kLeanSoloMinSteps steps per launch on at every batch, below that from kLeanSoloMinItems items (batch x n_steps) on.
-// A solo workgroup stages the phase table in LDS (1.2 us), every wavefront simulates its item (~3.4 us alone on its
-// SIMD) while linear_up's weights arrive, hands its share of them to LDS and writes its item's row (~1.3 us behind the
-// one wait for the slowest wavefront): ~9 us whatever the launch holds up to 2 048 items, one item per wavefront; the
-// four-wave body pays ~2.7 us per step of a sample.  Measured by tools/ab_lean_solo_threshold.py, float32, P = 784
-// (profiles/lean_wide/threshold.txt; us per launch, four-wave / solo):
-//   1 step:   256 items 5.7 / 9.1     512 items 7.8 / 9.2    1 024 items 13.3 / 9.4     2 048 items 23.9 / 10.0
-//             4 096 items 37.3 / 15.9
-//   4 steps:   64 items 13.1 / 9.0    1 024 items 14.7 / 9.4
-//   15 steps: 240 items 42.3 / 9.1    3 840 items 45.2 / 14.9   15 360 items 99.8 / 46.3
-// The one-step crossover has not moved since linear_up went from LDS to registers: between 512 and 1 024 items.
+// A solo workgroup stages the phase table in LDS (1.2 us), its wavefront 0 simulates the circuit once (~2.8 us alone on
+// its SIMD) while the other wavefronts load linear_up's operands, the workgroup computes its one row (~0.3 us) and every
+// wavefront stores that row once per item it was dealt: ~6 us whatever the launch holds up to 1 024 items, and the
+// image stores beyond that; the four-wave body pays ~2.7 us per step of a sample.  Measured by
+// tools/ab_lean_solo_threshold.py, float32, P = 784 (profiles/lean_once/threshold.txt; us per launch, four-wave / solo):
+//   1 step:   256 items 5.7 / 6.1     512 items 7.8 / 6.2    1 024 items 13.3 / 6.3     2 048 items 24.0 / 7.1
+//             4 096 items 37.3 / 8.9
+//   4 steps:   64 items 13.2 / 6.0    1 024 items 14.6 / 6.3
+//   15 steps: 240 items 42.3 / 6.1    3 840 items 45.5 / 8.6    15 360 items 99.5 / 18.6
+// Since the solo body simulates once per workgroup the one-step crossover lies between 256 and 512 items, below
+// kLeanSoloMinItems.  The constants stay where they were: the four-wave body's row differs from the solo row in the last
+// bits, so moving a threshold changes results, and that is a change of its own.
 // (2 and 3 steps are not in the table: the step rule stays where it was measured.)
 constexpr int kLeanSoloMinSteps = 4;
 constexpr int64_t kLeanSoloMinItems = 1024;
@@ -117,7 +119,7 @@ int launch_lean(const double* x, const double* wd, const double* bd, const doubl
     // (the body counts items and waves in 32 bits)
     if (lean_solo_wanted(items, d.n_steps) && items < ((int64_t)1 << 31) && d.out_features <= qiddm::kSoloMaxPixels) {
       static_assert(qiddm::LeanSoloLds::bytes(qiddm::kSoloMaxPixels, LPR) <= kMaxLds, "the largest image fits LDS");
-      const size_t smem = qiddm::LeanSoloLds::bytes(d.out_features, LPR);   // 90 KiB at 784 pixels, 99 KiB at 1 024
+      const size_t smem = qiddm::LeanSoloLds::bytes(d.out_features, LPR);   // 33.5 KiB at 784 pixels, 34.5 KiB at 1 024
       const int64_t cus = lean_cu_count();                                   // one workgroup per CU at most
       const int waves = lean_solo_waves(items, cus);
       const unsigned grid = lean_solo_grid(items, cus);

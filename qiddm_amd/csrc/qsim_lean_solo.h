@@ -16,16 +16,21 @@
 //     per vector instruction) instead of waiting ~11 cycles on its own previous result;
 //   * the items of a launch (batch x n_steps: this instance's angles never reach the state, so its steps do not depend
 //     on each other) are spread over all wavefronts of all workgroups, WAVES = 8 or 16 per CU (two or four per SIMD;
-//     the host picks the width, qiddm_lean.hip: launch_lean).  Every item is still simulated in full.
-// The per-workgroup setup fetches the tables from global memory ONCE and hands them to the wavefronts through LDS
-// (one __syncthreads()); linear_up's weights and bias follow under the first item's layers and reach LDS behind a second
-// barrier in front of the first tail.  These two are the kernel's only barriers: there is none per item.  A wavefront is
-// on its own: it simulates an item -- the layer's phase entries and tangents read from LDS one layer ahead, which keeps
-// the kernel inside the 128 VGPRs of four wavefronts per SIMD --, broadcasts the eight <Z> from the lanes that hold them
-// and writes that item's WHOLE row, a lane two neighbouring pixels at a time (pair = lane + 64 g), 16 contiguous bytes per
-// lane and store.  A wavefront that is ahead runs its tail under its SIMD neighbours' layers.  Every wave of either width
-// runs the same code -- one copy of it, and a pixel of every row is computed by the same instructions on the same
-// operands, so every row of a launch is the same bits --; what depends on the wave number is which items it takes.
+//     the host picks the width, qiddm_lean.hip: launch_lean).
+// This instance never reads the image (no re-upload: the encoders are a global phase), so a row of the output is a
+// function of (tables, w_up, b_up) alone and every item of a launch has the same one.  A workgroup therefore simulates
+// the circuit ONCE and computes ONE row; what is per item is the row's stores.  Every workgroup does that for itself --
+// the simulations run side by side on all CUs, and nothing is carried from one launch to the next.
+// The per-workgroup setup fetches the tables from global memory once and hands them over through LDS (a first
+// __syncthreads()).  Then wavefront 0 simulates -- the layer's phase entries and tangents read from LDS one layer ahead,
+// which keeps the kernel inside the 128 VGPRs of four wavefronts per SIMD --, broadcasts the eight <Z> from the lanes that
+// hold them and leaves them in LDS, while the threads of wavefronts 1 .. WAVES - 1 load linear_up's weights and biases
+// straight from global memory into registers, a thread the two rows of a pixel pair.  Behind a second barrier those
+// threads compute their pair's two pixels and write them to an LDS row; behind a third every wavefront reads the row
+// into registers, a lane the pairs lane + 64 g, once.  From there on a wavefront only stores: per item the row, 16
+// contiguous bytes per lane and store.  These three are the kernel's only barriers: there is none per item.  A pixel is
+// computed once per workgroup, by the same instructions on the same operands in every workgroup of either width, so
+// every row of a launch is the same bits; what depends on the wave number is which items it takes.
 #pragma once
 #include "qsim_lean.h"
 
@@ -33,7 +38,7 @@ namespace qiddm {
 
 // ---- which lane writes which pixels --------------------------------------------------------------------------------------
 // linear_up by pixel pairs: the Q <= 1024 pixels of a row are ceil(Q / 2) pairs (2 pr, 2 pr + 1); lane l of the wavefront
-// that simulated the item takes the pairs l, l + 64, .. -- group g of solo_groups(Q) the pair solo_pair_of(g, l) -- and
+// that writes an item's row takes the pairs l, l + 64, .. -- group g of solo_groups(Q) the pair solo_pair_of(g, l) -- and
 // stores the solo_pair_pixels(Q, pr) pixels of a pair that exist: both (16 bytes), the first one of an odd Q's last pair,
 // or none beyond the row.
 constexpr int kSoloMaxPixels = 1024;
@@ -65,21 +70,20 @@ __host__ __device__ constexpr bool solo_pairs_cover() {
 static_assert(solo_pairs_cover(), "pixel pairs: every pixel of every image size has exactly one writer");
 static_assert(solo_groups(784) == 7 && solo_groups(kSoloMaxPixels) == 8, "7 groups for the flagship, 8 at most");
 
-// LDS of the solo body: linear_up's weights as 16-byte units [8][stride] -- unit (u, pr) = the chunk (w[2 k], w[2 k + 1]),
-// k = u & 3, of row 2 pr + (u >> 2): consecutive lanes read consecutive 16 bytes --, its bias as [pairs padded][2], the
-// tangents [layers][8], the phase entries in the lanes' order.  The stride of a unit row is the padded pair count + 2: the
-// setup stores eight units of one pair from eight consecutive threads, and 2 units between rows spread them over all
-// banks.  Pad units and the missing second row of an odd Q's last pair hold finite values that are never stored.
+// LDS of the solo body: the workgroup's one row as 16-byte units [pairs padded] -- unit pr = pixels (2 pr, 2 pr + 1):
+// consecutive lanes write and read consecutive 16 bytes --, the eight <Z> of the one simulation as doubles, the tangents
+// [layers][8], the phase entries in the lanes' order.  linear_up's weights and bias are not here: they go from global
+// memory to the registers of the thread that computes their pair.  Pad units and the missing second pixel of an odd Q's
+// last pair hold finite values that are never stored.
 struct LeanSoloLds {
-  __host__ __device__ static constexpr int w_stride(int q) { return solo_pairs_padded(q) + 2; }
-  __host__ __device__ static constexpr size_t w_bytes(int q) { return (size_t)8 * w_stride(q) * 2 * sizeof(double); }
-  __host__ __device__ static constexpr size_t b_bytes(int q) { return (size_t)solo_pairs_padded(q) * 2 * sizeof(double); }
+  __host__ __device__ static constexpr size_t row_bytes(int q) { return (size_t)solo_pairs_padded(q) * 2 * sizeof(double); }
+  __host__ __device__ static constexpr size_t ez_bytes() { return 8 * sizeof(double); }
   __host__ __device__ static constexpr size_t un_bytes(int layers) { return (size_t)layers * 8 * sizeof(float); }
   // the phase entries of the simulated layers 1 .. layers - 1 in the order the lanes take them: [layer][2][64] units of
   // 16 bytes, unit (l, h, lane) = the lane's entries for registers 2 h and 2 h + 1 in the layout layer l starts in
   __host__ __device__ static constexpr size_t ph_bytes(int layers) { return (size_t)(layers - 1) * 256 * 2 * sizeof(float); }
   __host__ __device__ static constexpr size_t bytes(int q, int layers) {
-    return w_bytes(q) + b_bytes(q) + un_bytes(layers) + ph_bytes(layers);
+    return row_bytes(q) + ez_bytes() + un_bytes(layers) + ph_bytes(layers);
   }
 };
 
@@ -234,9 +238,20 @@ __device__ __forceinline__ void solo_layer(int layout, V2<float> (&a)[4], const 
 // The launches of dense_lean_kernel<float, 8, 4, false, LPR, false> that the host routes here, WAVES wavefronts per
 // workgroup, one workgroup per CU.
 // Items: (sample, step) = item / n_steps, item % n_steps for item < batch * n_steps; wave wv of workgroup b takes items
-// wv * gridDim.x + b, + gridDim.x * WAVES, ...: consecutive items go to consecutive CUs, every item is simulated and
-// written exactly once, by one wavefront, and no CU holds two items more than another.
+// wv * gridDim.x + b, + gridDim.x * WAVES, ...: consecutive items go to consecutive CUs, every item is written exactly
+// once, by one wavefront, and no CU holds two items more than another.  Workgroup b exists only if item b does (the
+// host's grid is <= ceil(items / 8)): its wavefront 0 always has an item.
 constexpr int solo_threads(int waves) { return waves * kWave; }
+// linear_up's operands: the threads of wavefronts 1 .. WAVES - 1 take a pixel pair each, thread t of them the pairs
+// t, t + solo_loaders(WAVES), ..: one trip at 16 wavefronts, a second one at 8 for the images beyond 896 pixels
+constexpr int solo_loaders(int waves) { return (waves - 1) * kWave; }
+constexpr int solo_pair_trips(int waves) { return (solo_pairs(kSoloMaxPixels) + solo_loaders(waves) - 1) / solo_loaders(waves); }
+static_assert(solo_pair_trips(16) == 1 && solo_pair_trips(8) == 2, "the pairs of the largest image: one trip at 16, two at 8");
+static_assert(solo_pair_trips(16) * solo_loaders(16) >= solo_pairs_padded(kSoloMaxPixels) &&
+                  solo_pair_trips(8) * solo_loaders(8) >= solo_pairs_padded(kSoloMaxPixels),
+              "every pair of the largest image, pad pairs included, has a thread");
+static_assert(solo_loaders(8) % kWave == 0 && solo_pairs_padded(1) % kWave == 0,
+              "a wavefront's 64 pairs are all inside the padded row or all beyond it");
 // (word 8 + 8 * workgroups + b of a stamp buffer that long: see the stamps below)
 __host__ __device__ constexpr int64_t solo_timeline_words(int64_t workgroups) { return 8 + 8 * workgroups; }
 template <int LPR, int WAVES>
@@ -254,14 +269,14 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
   // read-out expects the state
   auto layout_of = [](int l) { return (LPR - 1 - l) % 2 == 0 ? kSoloLayoutB : kSoloLayoutA; };
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int Q = d.out_features, PairsP = solo_pairs_padded(Q), WS = LeanSoloLds::w_stride(Q);
-  D2* s_w = reinterpret_cast<D2*>(smem_raw);                                    // [8][WS]
-  double* s_b = reinterpret_cast<double*>(smem_raw + LeanSoloLds::w_bytes(Q));   // [PairsP][2]
-  T* s_un = reinterpret_cast<T*>(smem_raw + LeanSoloLds::w_bytes(Q) + LeanSoloLds::b_bytes(Q));   // [LPR][8]
-  C* s_ph = reinterpret_cast<C*>(smem_raw + LeanSoloLds::w_bytes(Q) + LeanSoloLds::b_bytes(Q) +
-                                 LeanSoloLds::un_bytes(LPR));                     // [LPR - 1][2][64][2]
-  static_assert(LeanSoloLds::w_bytes(1) % 16 == 0 && LeanSoloLds::b_bytes(1) % 16 == 0 && LeanSoloLds::un_bytes(LPR) % 16 == 0,
-                "16-byte reads of the weights, the bias and the phase entries");
+  const int Q = d.out_features, PairsP = solo_pairs_padded(Q);
+  D2* s_row = reinterpret_cast<D2*>(smem_raw);                                      // [PairsP]
+  double* s_ez = reinterpret_cast<double*>(smem_raw + LeanSoloLds::row_bytes(Q));    // [8]
+  T* s_un = reinterpret_cast<T*>(smem_raw + LeanSoloLds::row_bytes(Q) + LeanSoloLds::ez_bytes());   // [LPR][8]
+  C* s_ph = reinterpret_cast<C*>(smem_raw + LeanSoloLds::row_bytes(Q) + LeanSoloLds::ez_bytes() +
+                                 LeanSoloLds::un_bytes(LPR));                         // [LPR - 1][2][64][2]
+  static_assert(LeanSoloLds::row_bytes(1) % 16 == 0 && LeanSoloLds::ez_bytes() % 16 == 0 && LeanSoloLds::un_bytes(LPR) % 16 == 0,
+                "16-byte reads of the row, the read-out and the phase entries");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int llane = logical_lane(lane);
@@ -270,15 +285,17 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
   const T* g_un = g_body + QT::ph_elems(LPR);
   const T* g_a0 = g_un + QT::un_elems(LPR);
   // diagnostics: wavefront 0 of workgroup 0 stamps s_memtime into words 0..7 (tools/stamp_lean_solo.py) -- [0] entry,
-  // [1] setup loads issued, [2] barrier passed, [3] / [4] end of the layers and read-out / of the tail (linear_up and the
-  // stores of the item's row) of its first item, [5] / [6] of its second item, [7]: s_memrealtime (100 MHz) from entry to
-  // the last tail stamped, which gives the ticks their length.
+  // [1] setup loads issued, [2] setup barrier passed, [3] simulation and read-out done (the eight <Z> are on their way to
+  // LDS), [4] row barrier passed (the row is in LDS), [5] the stores of its first item issued, [6] its last instruction,
+  // [7]: s_memrealtime (100 MHz) from entry to [6], which gives the ticks their length.
   // When the buffer holds 8 + 8 * gridDim.x words (d.stamp_words), wavefront 0 of EVERY workgroup b also stamps
   // s_memrealtime -- the same clock on every CU -- into words 8 + 8 b .. (tools/timeline_lean_solo.py): [0] entry,
-  // [1] barrier passed, [2] / [3] end of the layers / of the tail of its first item, [4] / [5] of its second, [6] its
-  // last instruction; and the LAST wavefront of the workgroup (WAVES - 1, the youngest of its SIMD, which may have no
-  // item), [7] its last instruction.  With one more word per workgroup behind those (9 * gridDim.x in all) the last
-  // wavefront of workgroup b that HAD an item stamps its last instruction into word 8 + 8 * gridDim.x + b.
+  // [1] setup barrier passed, [2] simulation and read-out done, [3] row barrier passed, [4] the stores of its first item
+  // issued, ([5] is not written,) [6] its last instruction; and the LAST wavefront of the workgroup (WAVES - 1, the
+  // youngest of its SIMD, which may have no item), [7] its last instruction.  With one more word per workgroup behind
+  // those (9 * gridDim.x in all) the last wavefront of workgroup b that HAD an item stamps its last instruction into
+  // word 8 + 8 * gridDim.x + b.  (Words [0], [1], [6], [7] and the ninth are where the body that simulated every item
+  // had them, so the tools read either library.)
   // The test is wave-uniform (a scalar branch per stamp); lane 0 stores.
   const bool stamp_timeline = d.stamps != nullptr && (int64_t)d.stamp_words >= solo_timeline_words(gridDim.x);
   const bool stamp_last_item = stamp_timeline && (int64_t)d.stamp_words >= solo_timeline_words(gridDim.x) + (int64_t)gridDim.x;
@@ -291,7 +308,7 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
       if (lane == 0) {
         if (blockIdx.x == 0 && word >= 0) {
           d.stamps[word] = t;
-          if (word == 4 || word == 6) d.stamps[7] = rt - stamp_rt0;
+          if (word == 6) d.stamps[7] = rt - stamp_rt0;
         }
         if (stamp_timeline && tword >= 0) d.stamps[8 + 8 * (size_t)blockIdx.x + tword] = rt;
       }
@@ -306,45 +323,11 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
   // phase table from global memory itself: eight times the bytes through the CU's vector L1, which took longer than an
   // item's layers; then it kept all 13 layers' entries in 104 registers, which held a SIMD to two wavefronts.)
   // Every global load of it is issued before anything waits.  linear_up's weights and bias (56 KiB at 784 pixels) are
-  // NOT in front of that barrier, where they doubled the setup (2.0 against 1.0 us): they are loaded right behind it,
-  // fly under the first item's layers, and go to LDS behind a second workgroup barrier in front of the FIRST tail only.
+  // NOT in front of that barrier, where they doubled the setup (2.0 against 1.0 us): wavefronts 1 .. WAVES - 1 load them
+  // behind it, under wavefront 0's layers.
   constexpr int kPhEntries = (LPR - 1) * QT::TL;                                  // phase entries of layers 1 .. LPR - 1
   constexpr int kPhTrips = (kPhEntries + kThreads - 1) / kThreads;
-  // (Q <= kSoloMaxPixels: the host checks)
-  constexpr int kWTrips = 8 * solo_pairs_padded(kSoloMaxPixels) / kThreads, kBTrips = kSoloMaxPixels / kThreads;
-  static_assert(8 * solo_pairs_padded(kSoloMaxPixels) % kThreads == 0 && kSoloMaxPixels % kThreads == 0,
-                "whole trips over the weights and the bias");
   C phstage[kPhTrips];
-  D2 wreg[kWTrips];
-  double breg[kBTrips];
-  auto load_weights = [&]() {
-#pragma unroll
-    for (int k = 0; k < kWTrips; ++k) {
-      // (w_up in its own order, 16-byte chunk i = the unit i & 7 of pair i >> 3: the two rows of a pair are 128 contiguous
-      //  bytes.  A chunk beyond the image loads the last one; its pixel is never stored)
-      const int i = tid + k * kThreads;
-      wreg[k] = reinterpret_cast<const D2*>(wu)[i < 4 * Q ? i : 4 * Q - 1];
-    }
-#pragma unroll
-    for (int k = 0; k < kBTrips; ++k) {
-      const int i = tid + k * kThreads;
-      breg[k] = bu != nullptr ? bu[i < Q ? i : Q - 1] : 0.0;
-    }
-  };
-  // (every thread of the workgroup has a share, a wavefront without an item too; then the barrier)
-  auto hand_over_weights = [&]() {
-#pragma unroll
-    for (int k = 0; k < kWTrips; ++k) {
-      const int i = tid + k * kThreads;
-      if (i < 8 * PairsP) s_w[(i & 7) * WS + (i >> 3)] = wreg[k];
-    }
-#pragma unroll
-    for (int k = 0; k < kBTrips; ++k) {
-      const int i = tid + k * kThreads;
-      if (i < 2 * PairsP) s_b[i] = breg[k];
-    }
-    __syncthreads();
-  };
 #pragma unroll
   for (int k = 0; k < kPhTrips; ++k) {
     // LDS entry e = ((l - 1) * 2 + h) * 128 + lane * 2 + j: register r = 2 h + j of `lane` in layer l
@@ -371,19 +354,12 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
   for (int q = 0; q < 4; ++q) pm[q] = ((llane >> q) & 1) ? (T)1 : (T)-1;
   __syncthreads();
   stamp(2, 1);
-  load_weights();
 
-  // ---- the items of this wave ---------------------------------------------------------------------------------------
-  const uint32_t n_steps = (uint32_t)d.n_steps;
-  const uint32_t stride = (uint32_t)gridDim.x * WAVES;          // waves of the launch
-  const uint32_t g0 = (uint32_t)wv * gridDim.x + (uint32_t)blockIdx.x;
-  const uint32_t stride_q = stride / n_steps, stride_r = stride - stride_q * n_steps;
-  int64_t sample = (int64_t)(g0 / n_steps);
-  uint32_t step = g0 - (g0 / n_steps) * n_steps;
-  const int groups = solo_groups(Q);
-  const D2* s_b2 = reinterpret_cast<const D2*>(s_b);
-  for (int item = 0; sample < p.batch; ++item) {
-    asm volatile("" ::: "memory");   // (the LDS reads below stay inside the loop: hoisted, they would not fit registers)
+  // ---- one simulation (wavefront 0) beside the loads of linear_up's operands (the others), then one row --------------
+  // (the barriers inside the two branches are the same workgroup barrier: every wavefront meets it once, with or
+  //  without an item)
+  constexpr int kLoaders = solo_loaders(WAVES), kPairTrips = solo_pair_trips(WAVES);
+  if (wv == 0) {
     C a[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) a[r] = C{a0r[r], (T)0};
@@ -422,10 +398,86 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
 #pragma unroll
     for (int w = 0; w < 8; ++w)
       ev[w] = (double)read_lane(tot, logical_lane(((w >> 2) & 1) | (w & 2) | ((w & 1) << 2)));
-    if (item < 2) stamp(3 + 2 * item, 2 + 2 * item);
-    if (item == 0) hand_over_weights();   // (an early wavefront waits here once for the workgroup's slowest)
-    // ---- linear_up: the item's row, pair = lane + 64 g; per pixel two partial sums with explicit fma (as
-    // dense_lean_kernel) and one add ------------------------------------------------------------------------------------
+    if (lane == 0) {
+#pragma unroll
+      for (int w = 0; w < 8; ++w) s_ez[w] = ev[w];
+    }
+    stamp(3, 2);
+    __syncthreads();
+  } else {
+    // A thread takes a pair: the pair's two rows of w_up are 128 contiguous bytes, eight 16-byte chunks (chunk u = the
+    // weights (w[2 k], w[2 k + 1]), k = u & 3, of row 2 pr + (u >> 2)), and its two biases.  A chunk or a bias beyond
+    // the image loads the last one; its pixel is never stored.  The 64 pairs of a wavefront are all inside the padded
+    // row or all beyond it (a wave-uniform test): a wavefront beyond it loads nothing.  (Q <= kSoloMaxPixels: the host
+    // checks.)
+    const int t = tid - kWave;
+    const D2* wu2 = reinterpret_cast<const D2*>(wu);
+    D2 wreg[kPairTrips][8], breg[kPairTrips];
+#pragma unroll
+    for (int k = 0; k < kPairTrips; ++k) {
+      const int pr = t + k * kLoaders;
+      if (pr < PairsP) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = 8 * pr + u;
+          wreg[k][u] = wu2[i < 4 * Q ? i : 4 * Q - 1];
+        }
+        const int i0 = 2 * pr < Q ? 2 * pr : Q - 1, i1 = 2 * pr + 1 < Q ? 2 * pr + 1 : Q - 1;
+        breg[k] = bu != nullptr ? D2{bu[i0], bu[i1]} : D2{0.0, 0.0};
+      }
+    }
+    __syncthreads();   // (the eight <Z> are in LDS)
+    double ev[8];
+#pragma unroll
+    for (int w = 0; w < 8; ++w) ev[w] = s_ez[w];
+    // ---- linear_up: per pixel two partial sums with explicit fma (as dense_lean_kernel) and one add ------------------
+#pragma unroll
+    for (int k = 0; k < kPairTrips; ++k) {
+      const int pr = t + k * kLoaders;
+      if (pr < PairsP) {
+        const D2 wa0 = wreg[k][0], wa1 = wreg[k][1], wa2 = wreg[k][2], wa3 = wreg[k][3];
+        const D2 wb0 = wreg[k][4], wb1 = wreg[k][5], wb2 = wreg[k][6], wb3 = wreg[k][7];
+        const D2 bias = breg[k];
+        double a0 = bias.x, a1 = 0.0, b0 = bias.y, b1 = 0.0;
+        a0 = fma(ev[0], wa0.x, a0);
+        a1 = fma(ev[1], wa0.y, a1);
+        a0 = fma(ev[2], wa1.x, a0);
+        a1 = fma(ev[3], wa1.y, a1);
+        a0 = fma(ev[4], wa2.x, a0);
+        a1 = fma(ev[5], wa2.y, a1);
+        a0 = fma(ev[6], wa3.x, a0);
+        a1 = fma(ev[7], wa3.y, a1);
+        a0 += a1;
+        b0 = fma(ev[0], wb0.x, b0);
+        b1 = fma(ev[1], wb0.y, b1);
+        b0 = fma(ev[2], wb1.x, b0);
+        b1 = fma(ev[3], wb1.y, b1);
+        b0 = fma(ev[4], wb2.x, b0);
+        b1 = fma(ev[5], wb2.y, b1);
+        b0 = fma(ev[6], wb3.x, b0);
+        b1 = fma(ev[7], wb3.y, b1);
+        b0 += b1;
+        s_row[pr] = D2{a0, b0};
+      }
+    }
+  }
+  __syncthreads();   // (the row is in LDS)
+  stamp(4, 3);
+
+  // ---- the items of this wave: stores only ---------------------------------------------------------------------------
+  // (a lane's units of the row, pair = lane + 64 g, read once; a group beyond the image re-reads group 0 and is not stored)
+  const int groups = solo_groups(Q);
+  constexpr int kMaxGroups = solo_groups(kSoloMaxPixels);
+  D2 rowreg[kMaxGroups];
+#pragma unroll
+  for (int g = 0; g < kMaxGroups; ++g) rowreg[g] = s_row[solo_pair_of(g < groups ? g : 0, lane)];
+  const uint32_t n_steps = (uint32_t)d.n_steps;
+  const uint32_t stride = (uint32_t)gridDim.x * WAVES;          // waves of the launch
+  const uint32_t g0 = (uint32_t)wv * gridDim.x + (uint32_t)blockIdx.x;
+  const uint32_t stride_q = stride / n_steps, stride_r = stride - stride_q * n_steps;
+  int64_t sample = (int64_t)(g0 / n_steps);
+  uint32_t step = g0 - (g0 / n_steps) * n_steps;
+  for (int item = 0; sample < p.batch; ++item) {
     double* yrow = y + (size_t)step * d.y_step_stride + sample * d.y_ld;
     // a whole pair of a 16-byte aligned row (a wave-uniform test) is one 16-byte store; a row that is not aligned and
     // the lone last pixel of an odd Q take plain 8-byte stores (an 8-byte write-through store is the slow form)
@@ -435,44 +487,23 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
     using U4 = unsigned __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(yrow, 0, Q * 8, 0x00020000);
 #endif
-#pragma unroll 2
-    for (int g = 0; g < groups; ++g) {
-      const int pr = solo_pair_of(g, lane), n_pix = solo_pair_pixels(Q, pr);
-      const D2* wp = s_w + pr;
-      const D2 wa0 = wp[0], wa1 = wp[WS], wa2 = wp[2 * WS], wa3 = wp[3 * WS];
-      const D2 wb0 = wp[4 * WS], wb1 = wp[5 * WS], wb2 = wp[6 * WS], wb3 = wp[7 * WS];
-      const D2 bias = s_b2[pr];
-      double a0 = bias.x, a1 = 0.0, b0 = bias.y, b1 = 0.0;
-      a0 = fma(ev[0], wa0.x, a0);
-      a1 = fma(ev[1], wa0.y, a1);
-      a0 = fma(ev[2], wa1.x, a0);
-      a1 = fma(ev[3], wa1.y, a1);
-      a0 = fma(ev[4], wa2.x, a0);
-      a1 = fma(ev[5], wa2.y, a1);
-      a0 = fma(ev[6], wa3.x, a0);
-      a1 = fma(ev[7], wa3.y, a1);
-      a0 += a1;
-      b0 = fma(ev[0], wb0.x, b0);
-      b1 = fma(ev[1], wb0.y, b1);
-      b0 = fma(ev[2], wb1.x, b0);
-      b1 = fma(ev[3], wb1.y, b1);
-      b0 = fma(ev[4], wb2.x, b0);
-      b1 = fma(ev[5], wb2.y, b1);
-      b0 = fma(ev[6], wb3.x, b0);
-      b1 = fma(ev[7], wb3.y, b1);
-      b0 += b1;
-      if (row_aligned && n_pix == 2) {
+#pragma unroll
+    for (int g = 0; g < kMaxGroups; ++g) {
+      if (g < groups) {
+        const int pr = solo_pair_of(g, lane), n_pix = solo_pair_pixels(Q, pr);
+        if (row_aligned && n_pix == 2) {
 #if QIDDM_SOLO_WRITE_THROUGH
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, D2{a0, b0}), rsrc, pr * 16, 0, /*sc1*/ 16);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, rowreg[g]), rsrc, pr * 16, 0, /*sc1*/ 16);
 #else
-        *reinterpret_cast<D2*>(yrow + 2 * pr) = D2{a0, b0};
+          *reinterpret_cast<D2*>(yrow + 2 * pr) = rowreg[g];
 #endif
-      } else if (n_pix > 0) {
-        yrow[2 * pr] = a0;
-        if (n_pix == 2) yrow[2 * pr + 1] = b0;
+        } else if (n_pix > 0) {
+          yrow[2 * pr] = rowreg[g].x;
+          if (n_pix == 2) yrow[2 * pr + 1] = rowreg[g].y;
+        }
       }
     }
-    if (item < 2) stamp(4 + 2 * item, 3 + 2 * item);
+    if (item == 0) stamp(5, 4);
     // next item of this wave
     sample += stride_q;
     step += stride_r;
@@ -481,8 +512,7 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
       ++sample;
     }
   }
-  if (g0 / n_steps >= (uint32_t)p.batch) hand_over_weights();   // (a wavefront without an item meets the barrier too)
-  stamp(-1, 6);
+  stamp(6, 6);
   if (stamp_timeline && wv == WAVES - 1) {
     const unsigned long long rt = __builtin_amdgcn_s_memrealtime();
     if (lane == 0) d.stamps[8 + 8 * (size_t)blockIdx.x + 7] = rt;
