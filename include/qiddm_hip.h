@@ -278,7 +278,13 @@ int qiddm_dense_sample_prepare(const qiddm_circuit_t *circ, const double *angles
  * composition; the image and both linears' weights stay in registers across the steps.  Tables: qiddm_dense_sample_lean_tables_bytes(circ) bytes, written once per
  * weights by _prepare (angles AND the two linears); _check synchronises the stream and returns 1 when the tables are
  * usable -- max |tan(theta/2)| <= 16 over the simulated layers -- 0 when the caller must use qiddm_dense_sample, < 0
- * on error.  Results agree with qiddm_dense_sample to rounding (not bit for bit).                                  */
+ * on error.  Results agree with qiddm_dense_sample to rounding (not bit for bit).
+ * For the instance without re-upload that has a kernel of its own (float32, 8 qubits, one block of 14 layers, one round)
+ * the tables also carry the circuit's read-out, the eight <Z>: _prepare simulates the circuit once, on the same stream,
+ * and the sampler executes no gate.  The read-out depends on the angles alone, so the tables are valid exactly as long
+ * as the angles are -- the "once per weights" above, nothing new; _check returns 0 for such a circuit when the tables
+ * carry no finite read-out for it.  w_up / b_up remain operands of every qiddm_dense_sample_lean call: the row is
+ * computed from the pointers of that call.                                                                          */
 int64_t qiddm_dense_sample_lean_tables_bytes(const qiddm_circuit_t *circ);
 int qiddm_dense_sample_lean_prepare(const qiddm_circuit_t *circ, const double *angles, const double *w_down,
                                     const double *b_down, const double *w_up, const double *b_up, int64_t features,

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -39,6 +40,14 @@ int lean_layers(const qiddm_circuit_t* c) {
   return (int)layers;
 }
 
+// The circuits that dispatch_lean_n can route to the solo kernel (qsim_lean.h: lean_has_solo, with LPR = 14): their
+// tables carry the circuit's read-out (qsim_lean_solo.h: lean_solo_readout_kernel), and the solo kernel relies on it.
+constexpr int kLeanSoloLpr = 14;
+bool lean_solo_family(const qiddm_circuit_t* c) {
+  return c->dtype == QIDDM_F32 && c->n_qubits == 8 && c->n_blocks == 1 && c->n_blocks * c->sel_layers == kLeanSoloLpr &&
+         c->n_rounds == 1;
+}
+
 qiddm::KScalars params_of(const qiddm_circuit_t* c) {
   qiddm::KScalars p;
   std::memset(&p, 0, sizeof(p));
@@ -57,18 +66,18 @@ qiddm::KScalars params_of(const qiddm_circuit_t* c) {
 
 // When the instance that carries both bodies (qsim_lean.h: lean_has_solo) runs the one-wavefront-per-item body: from
 // kLeanSoloMinSteps steps per launch on at every batch, below that from kLeanSoloMinItems items (batch x n_steps) on.
-// A solo workgroup stages the phase table in LDS (1.2 us), its wavefront 0 simulates the circuit once (~2.8 us alone on
-// its SIMD) while the other wavefronts load linear_up's operands, the workgroup computes its one row (~0.3 us) and every
-// wavefront stores that row once per item it was dealt: ~6 us whatever the launch holds up to 1 024 items, and the
-// image stores beyond that; the four-wave body pays ~2.7 us per step of a sample.  Measured by
-// tools/ab_lean_solo_threshold.py, float32, P = 784 (profiles/lean_once/threshold.txt; us per launch, four-wave / solo):
-//   1 step:   256 items 5.7 / 6.1     512 items 7.8 / 6.2    1 024 items 13.3 / 6.3     2 048 items 24.0 / 7.1
-//             4 096 items 37.3 / 8.9
-//   4 steps:   64 items 13.2 / 6.0    1 024 items 14.6 / 6.3
-//   15 steps: 240 items 42.3 / 6.1    3 840 items 45.5 / 8.6    15 360 items 99.5 / 18.6
-// Since the solo body simulates once per workgroup the one-step crossover lies between 256 and 512 items, below
-// kLeanSoloMinItems.  The constants stay where they were: the four-wave body's row differs from the solo row in the last
-// bits, so moving a threshold changes results, and that is a change of its own.
+// A solo workgroup executes no gate (the circuit's read-out comes with the tables): its threads load linear_up's
+// operands and the read-out, compute the workgroup's one row, and behind one barrier every wavefront stores that row
+// once per item it was dealt: ~4.1 us whatever the launch holds up to 1 024 items, and the image stores beyond that;
+// the four-wave body pays ~2.7 us per step of a sample.  Measured by tools/ab_lean_solo_threshold.py, float32, P = 784
+// (profiles/lean_tabled/threshold.txt; us per launch, four-wave / solo):
+//   1 step:     1 item  5.0 / 3.6     256 items 5.7 / 4.1     512 items 7.8 / 4.2    1 024 items 13.2 / 4.4
+//             2 048 items 24.0 / 5.2   4 096 items 37.6 / 6.9
+//   4 steps:   64 items 13.2 / 4.1    1 024 items 14.5 / 4.3
+//   15 steps: 240 items 42.2 / 4.1    3 840 items 45.4 / 6.6    15 360 items 100.1 / 16.7
+// Since the solo body no longer simulates there is no crossover left: it is the faster one from a single item on.
+// The constants stay where they were: the four-wave body's row differs from the solo row in the last bits, so moving a
+// threshold changes results, and that is a change of its own.
 // (2 and 3 steps are not in the table: the step rule stays where it was measured.)
 constexpr int kLeanSoloMinSteps = 4;
 constexpr int64_t kLeanSoloMinItems = 1024;
@@ -118,8 +127,8 @@ int launch_lean(const double* x, const double* wd, const double* bd, const doubl
     const int64_t items = p.batch * d.n_steps;
     // (the body counts items and waves in 32 bits)
     if (lean_solo_wanted(items, d.n_steps) && items < ((int64_t)1 << 31) && d.out_features <= qiddm::kSoloMaxPixels) {
-      static_assert(qiddm::LeanSoloLds::bytes(qiddm::kSoloMaxPixels, LPR) <= kMaxLds, "the largest image fits LDS");
-      const size_t smem = qiddm::LeanSoloLds::bytes(d.out_features, LPR);   // 33.5 KiB at 784 pixels, 34.5 KiB at 1 024
+      static_assert(qiddm::LeanSoloLds::bytes(qiddm::kSoloMaxPixels) <= kMaxLds, "the largest image fits LDS");
+      const size_t smem = qiddm::LeanSoloLds::bytes(d.out_features);   // the row: 7 KiB at 784 pixels, 8 KiB at 1 024
       const int64_t cus = lean_cu_count();                                   // one workgroup per CU at most
       const int waves = lean_solo_waves(items, cus);
       const unsigned grid = lean_solo_grid(items, cus);
@@ -201,19 +210,34 @@ int qiddm_dense_sample_lean_prepare(const qiddm_circuit_t* c, const double* angl
       return qiddm_capi::launched("lean_tables_kernel");
     });
   };
-  return c->n_qubits == 8 ? prepare(std::integral_constant<int, 8>{}) : prepare(std::integral_constant<int, 6>{});
+  const int rc = c->n_qubits == 8 ? prepare(std::integral_constant<int, 8>{}) : prepare(std::integral_constant<int, 6>{});
+  if (rc != QIDDM_OK || !lean_solo_family(c)) return rc;
+  // (behind the builder on the same stream: it reads the body that kernel wrote and overwrites the header's zeros)
+  hipLaunchKernelGGL((qiddm::lean_solo_readout_kernel<kLeanSoloLpr>), dim3(1), dim3(qiddm::kWave), 0, st, tb);
+  return qiddm_capi::launched("lean_solo_readout_kernel");
 }
 
 int qiddm_dense_sample_lean_check(const qiddm_circuit_t* c, const void* tables, void* stream) {
   const int64_t need = qiddm_dense_sample_lean_tables_bytes(c);
   if (need < 0) return (int)need;
   if (!tables) return fail(QIDDM_ERR_INVALID, "tables is NULL");
-  double tmax = 0.0;
+  // the header through the read-out's tag: [0] max |tan|, [kLeanReadoutDouble ..] eight floats, [kLeanReadoutTagDouble]
+  double head[qiddm::kLeanReadoutTagDouble + 1] = {};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = hipMemcpyAsync(&tmax, tables, sizeof(double), hipMemcpyDeviceToHost, st);
+  hipError_t e = hipMemcpyAsync(head, tables, sizeof(head), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "reading the tables' max |tan| failed: %s", hipGetErrorString(e));
-  return (tmax == tmax && tmax <= qiddm::kLeanMaxTan) ? 1 : 0;
+  if (e != hipSuccess) return fail(QIDDM_ERR_LAUNCH, "reading the tables' header failed: %s", hipGetErrorString(e));
+  const double tmax = head[0];
+  if (!(tmax == tmax && tmax <= qiddm::kLeanMaxTan)) return 0;
+  if (lean_solo_family(c)) {
+    // the solo kernel computes nothing but linear_up: tables without this circuit's read-out are not usable
+    if (head[qiddm::kLeanReadoutTagDouble] != (double)kLeanSoloLpr) return 0;
+    float ez[8];
+    std::memcpy(ez, &head[qiddm::kLeanReadoutDouble], sizeof(ez));
+    for (float v : ez)
+      if (!std::isfinite(v)) return 0;
+  }
+  return 1;
 }
 
 int qiddm_dense_sample_lean(const qiddm_circuit_t* c, const double* x, int64_t batch, int64_t x_ld, int64_t features,

@@ -55,6 +55,7 @@ namespace qiddm {
 
 constexpr double kLeanMaxTan = 16.0;
 constexpr int kLeanHeaderDoubles = 80;   // [0] max |t|, [1 .. n n] M = W_down W_up (row-major [j][i]), then v [n], pad
+                                         // (zeros; 8 qubits: 73 .. 77 the read-out of qsim_lean_solo.h and its tag)
 
 // layout of the lean tables behind the header, in elements of T (built once per weights; per launch copied to LDS, or
 // read by each thread into registers: lean_tables_in_registers)
@@ -135,6 +136,10 @@ __global__ __launch_bounds__(256) void lean_tables_kernel(const double* __restri
     for (int i = 0; i < 256; ++i) m = fmax(m, s_max[i]);
     head[0] = m;
   }
+  // The header's pad is written too (callers hand in uninitialised buffers): zeros.  For the circuits of the solo
+  // kernel lean_solo_readout_kernel (qsim_lean_solo.h) then puts the circuit's read-out and its tag there; in every
+  // other circuit's tables the zeros say that they carry none.
+  if (tid >= 1 + N * N + N && tid < kLeanHeaderDoubles) head[tid] = 0.0;
   // this thread's amplitude index (8 qubits: one per thread; 6 qubits: the first wavefront writes, one per lane)
   const uint32_t k = (N == 8 ? ((uint32_t)wv << 6) : 0u) | (uint32_t)logical_lane(lane);
   const int slot = N == 8 ? tid : lane;

@@ -18,19 +18,20 @@
 //     on each other) are spread over all wavefronts of all workgroups, WAVES = 8 or 16 per CU (two or four per SIMD;
 //     the host picks the width, qiddm_lean.hip: launch_lean).
 // This instance never reads the image (no re-upload: the encoders are a global phase), so a row of the output is a
-// function of (tables, w_up, b_up) alone and every item of a launch has the same one.  A workgroup therefore simulates
-// the circuit ONCE and computes ONE row; what is per item is the row's stores.  Every workgroup does that for itself --
-// the simulations run side by side on all CUs, and nothing is carried from one launch to the next.
-// The per-workgroup setup fetches the tables from global memory once and hands them over through LDS (a first
-// __syncthreads()).  Then wavefront 0 simulates -- the layer's phase entries and tangents read from LDS one layer ahead,
-// which keeps the kernel inside the 128 VGPRs of four wavefronts per SIMD --, broadcasts the eight <Z> from the lanes that
-// hold them and leaves them in LDS, while the threads of wavefronts 1 .. WAVES - 1 load linear_up's weights and biases
-// straight from global memory into registers, a thread the two rows of a pixel pair.  Behind a second barrier those
-// threads compute their pair's two pixels and write them to an LDS row; behind a third every wavefront reads the row
-// into registers, a lane the pairs lane + 64 g, once.  From there on a wavefront only stores: per item the row, 16
-// contiguous bytes per lane and store.  These three are the kernel's only barriers: there is none per item.  A pixel is
-// computed once per workgroup, by the same instructions on the same operands in every workgroup of either width, so
-// every row of a launch is the same bits; what depends on the wave number is which items it takes.
+// function of (tables, w_up, b_up) alone and every item of a launch has the same one -- and the eight <Z> are a function
+// of the tables alone.  So the circuit is simulated when the tables are made, not when they are used:
+//   * lean_solo_readout_kernel<LPR>, one wavefront, runs behind lean_tables_kernel (qiddm_dense_sample_lean_prepare).
+//     It gathers the phase entries into LDS in the lanes' order, reads a layer's entries and tangents from there one
+//     layer ahead, applies the LPR - 1 simulated layers, reduces the eight <Z> and leaves them as floats in the pad of
+//     the tables' header (kLeanReadoutDouble ..) with the layer count as a tag behind them (kLeanReadoutTagDouble).
+//   * dense_lean_solo_kernel<LPR, WAVES> executes no gate.  Its threads load linear_up's weights and biases straight
+//     from global memory into registers, a thread the two rows of a pixel pair, and the read-out (32 bytes at a uniform
+//     address); they compute their pair's two pixels and write them to an LDS row; behind the kernel's ONE barrier every
+//     wavefront reads the row into registers, a lane the pairs lane + 64 g, once.  From there on a wavefront only
+//     stores: per item the row, 16 contiguous bytes per lane and store.  A pixel is computed once per workgroup, by the
+//     same instructions on the same operands in every workgroup of either width, so every row of a launch is the same
+//     bits; what depends on the wave number is which items it takes.
+// w_up and b_up stay operands of the launch: nothing but the tables is carried from one launch to the next.
 #pragma once
 #include "qsim_lean.h"
 
@@ -71,21 +72,29 @@ static_assert(solo_pairs_cover(), "pixel pairs: every pixel of every image size 
 static_assert(solo_groups(784) == 7 && solo_groups(kSoloMaxPixels) == 8, "7 groups for the flagship, 8 at most");
 
 // LDS of the solo body: the workgroup's one row as 16-byte units [pairs padded] -- unit pr = pixels (2 pr, 2 pr + 1):
-// consecutive lanes write and read consecutive 16 bytes --, the eight <Z> of the one simulation as doubles, the tangents
-// [layers][8], the phase entries in the lanes' order.  linear_up's weights and bias are not here: they go from global
+// consecutive lanes write and read consecutive 16 bytes.  linear_up's weights and bias are not here: they go from global
 // memory to the registers of the thread that computes their pair.  Pad units and the missing second pixel of an odd Q's
 // last pair hold finite values that are never stored.
 struct LeanSoloLds {
   __host__ __device__ static constexpr size_t row_bytes(int q) { return (size_t)solo_pairs_padded(q) * 2 * sizeof(double); }
-  __host__ __device__ static constexpr size_t ez_bytes() { return 8 * sizeof(double); }
+  __host__ __device__ static constexpr size_t bytes(int q) { return row_bytes(q); }
+};
+static_assert(LeanSoloLds::bytes(kSoloMaxPixels) == 8 * 1024, "the row of the largest image: 8 KiB");
+// LDS of the read-out kernel: the tangents [layers][8] and the phase entries in the lanes' order
+struct LeanReadoutLds {
   __host__ __device__ static constexpr size_t un_bytes(int layers) { return (size_t)layers * 8 * sizeof(float); }
   // the phase entries of the simulated layers 1 .. layers - 1 in the order the lanes take them: [layer][2][64] units of
   // 16 bytes, unit (l, h, lane) = the lane's entries for registers 2 h and 2 h + 1 in the layout layer l starts in
   __host__ __device__ static constexpr size_t ph_bytes(int layers) { return (size_t)(layers - 1) * 256 * 2 * sizeof(float); }
-  __host__ __device__ static constexpr size_t bytes(int q, int layers) {
-    return row_bytes(q) + ez_bytes() + un_bytes(layers) + ph_bytes(layers);
-  }
+  __host__ __device__ static constexpr size_t bytes(int layers) { return un_bytes(layers) + ph_bytes(layers); }
 };
+// Where the read-out sits in the tables' header (qsim_lean.h: kLeanHeaderDoubles; doubles 0 .. 72 are max |t|, M and v
+// of 8 qubits): eight floats <Z_0> .. <Z_7> in four doubles, and behind them the layer count they were made for as a
+// double -- 0.0 (with zeros in the four) in tables that carry none.
+constexpr int kLeanReadoutDouble = 73, kLeanReadoutTagDouble = 77;
+static_assert(kLeanReadoutDouble >= 1 + 8 * 8 + 8 && kLeanReadoutTagDouble == kLeanReadoutDouble + 4 &&
+                  kLeanReadoutTagDouble < kLeanHeaderDoubles && (kLeanReadoutDouble * sizeof(double)) % 4 == 0,
+              "the read-out lies in the header's pad");
 
 // 1: a pair in a 16-byte aligned row leaves as one write-through store (`buffer_store_dwordx4 ... sc1`): the image goes
 // to memory while the launch runs instead of staying dirty in the L2s until the kernel boundary.  0 (A/B builds only):
@@ -235,18 +244,119 @@ __device__ __forceinline__ void solo_layer(int layout, V2<float> (&a)[4], const 
   solo_ry_reg(a[1], a[3], out1);
 }
 
+// the layout simulated layer l (1 .. lpr - 1) starts in: they alternate, and the last one ends in A, where the read-out
+// expects the state
+__host__ __device__ constexpr int solo_layout_of(int lpr, int l) { return (lpr - 1 - l) % 2 == 0 ? kSoloLayoutB : kSoloLayoutA; }
+
+// ---- the read-out, once per tables --------------------------------------------------------------------------------------
+// One wavefront simulates the circuit of a LeanTables<float, 8> with LPR layers in one round (the layers, their order and
+// their operands are those of the kernel that simulated in every workgroup of every launch: the eight <Z> are its bits)
+// and writes them into the header of the tables it read (kLeanReadoutDouble ..).  It runs behind lean_tables_kernel on
+// the same stream.  No address depends on the data: tables whose tangents are out of range give non-finite values
+// there and nothing else (qiddm_dense_sample_lean_check turns such tables down).
+template <int LPR>
+__global__ __launch_bounds__(kWave) void lean_solo_readout_kernel(unsigned char* tables) {
+  using T = float;
+  using C = V2<T>;
+  using QT = LeanTables<T, 8>;
+  using V4 = T __attribute__((ext_vector_type(4)));
+  static_assert(LPR > 1, "a compiled-in layer count with at least one simulated layer");
+  __shared__ __attribute__((aligned(16))) unsigned char smem_raw[LeanReadoutLds::bytes(LPR)];
+  T* s_un = reinterpret_cast<T*>(smem_raw);                                    // [LPR][8]
+  C* s_ph = reinterpret_cast<C*>(smem_raw + LeanReadoutLds::un_bytes(LPR));    // [LPR - 1][2][64][2]
+  static_assert(LeanReadoutLds::un_bytes(LPR) % 16 == 0, "16-byte reads of the tangents and the phase entries");
+  const int lane = threadIdx.x;
+  const int llane = logical_lane(lane);
+  const T* g_body = reinterpret_cast<const T*>(tables + kLeanHeaderDoubles * sizeof(double));
+  const C* g_ph = reinterpret_cast<const C*>(g_body);
+  const T* g_un = g_body + QT::ph_elems(LPR);
+  const T* g_a0 = g_un + QT::un_elems(LPR);
+  // The phase entries of the LPR - 1 simulated layers (26 KiB at 14, gathered into the lanes' own order) and the
+  // tangents go to LDS; the wavefront then reads a layer's entries from there with two 16-byte reads, one layer ahead.
+  constexpr int kPhEntries = (LPR - 1) * QT::TL;                               // phase entries of layers 1 .. LPR - 1
+  static_assert(kPhEntries % kWave == 0, "whole trips of the wavefront");
+  constexpr int kPhTrips = kPhEntries / kWave, kUnTrips = (LPR * 8 + kWave - 1) / kWave;
+#pragma unroll 4
+  for (int k = 0; k < kPhTrips; ++k) {
+    // LDS entry e = ((l - 1) * 2 + h) * 128 + lane * 2 + j: register r = 2 h + j of `lane` in layer l
+    const int e = lane + k * kWave;
+    const int l = (e >> 8) + 1, r = ((e >> 6) & 2) | (e & 1), ln = (e >> 1) & 63;
+    s_ph[e] = g_ph[l * QT::TL + solo_table_slot(solo_layout_of(LPR, l), r, ln)];
+  }
+#pragma unroll
+  for (int k = 0; k < kUnTrips; ++k) {
+    const int e = lane + k * kWave;
+    if (e < LPR * 8) s_un[e] = g_un[e];
+  }
+  T a0r[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) a0r[r] = g_a0[solo_table_slot(solo_layout_of(LPR, 1), r, lane)];
+  T pm[4];   // +-1 by this lane's index bit
+#pragma unroll
+  for (int q = 0; q < 4; ++q) pm[q] = ((llane >> q) & 1) ? (T)1 : (T)-1;
+  __syncthreads();
+
+  C a[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) a[r] = C{a0r[r], (T)0};
+  // a layer's tangents and this lane's phase entries (two 16-byte units: registers 0, 1 and 2, 3) are read one layer
+  // ahead (the fence keeps the compiler from reading all layers' up front)
+  const V4* un4 = reinterpret_cast<const V4*>(s_un);
+  const V4* ph4 = reinterpret_cast<const V4*>(s_ph) + lane;
+  V4 lo = un4[2], hi = un4[3], p01 = ph4[0], p23 = ph4[kWave];
+#pragma unroll
+  for (int l = 1; l < LPR; ++l) {
+    const int ln = l + 1 < LPR ? l + 1 : l;
+    const V4 nlo = un4[2 * ln], nhi = un4[2 * ln + 1];
+    const V4 np01 = ph4[(ln - 1) * 2 * kWave], np23 = ph4[((ln - 1) * 2 + 1) * kWave];
+    __builtin_amdgcn_sched_barrier(0);
+    const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
+    const C ph[4] = {C{p01.x, p01.y}, C{p01.z, p01.w}, C{p23.x, p23.y}, C{p23.z, p23.w}};
+    solo_layer(solo_layout_of(LPR, l), a, ph, ts, hi.x, hi.y, hi.z, hi.w);
+    lo = nlo;
+    hi = nhi;
+    p01 = np01;
+    p23 = np23;
+  }
+  // ---- <Z_w>: the register-bit wires are signed in-lane sums, the lane-bit wires signed copies of the lane's total ----
+  T pw[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) pw[r] = a[r].x * a[r].x + a[r].y * a[r].y;
+  const T pt = (pw[0] + pw[1]) + (pw[2] + pw[3]);
+  T ez[8];
+  ez[0] = (pw[0] + pw[1]) - (pw[2] + pw[3]);   // wire 0 = index bit 7 = register bit 1
+  ez[1] = (pw[0] + pw[2]) - (pw[1] + pw[3]);   // wire 1 = index bit 6 = register bit 0
+#pragma unroll
+  for (int w = 2; w < 8; ++w) ez[w] = ((llane >> (7 - w)) & 1) ? -pt : pt;
+  const T tot = wave_reduce8<T>(ez, lane, llane);
+  // (the lane of logical number 4 b0 + 2 b1 + b2 -> wire b0 b1 b2 holds that wire's total: qsim_adjoint.h)
+  T ev[8];
+#pragma unroll
+  for (int w = 0; w < 8; ++w) ev[w] = read_lane(tot, logical_lane(((w >> 2) & 1) | (w & 2) | ((w & 1) << 2)));
+  // (plain vector stores from lane 0, as lean_tables_kernel writes its header; a float widens to the double that the
+  //  sampler's linear_up multiplies by without rounding)
+  if (lane == 0) {
+    double* head = reinterpret_cast<double*>(tables);
+    T* out = reinterpret_cast<T*>(head + kLeanReadoutDouble);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) out[w] = ev[w];
+    head[kLeanReadoutTagDouble] = (double)LPR;
+  }
+}
+
 // The launches of dense_lean_kernel<float, 8, 4, false, LPR, false> that the host routes here, WAVES wavefronts per
-// workgroup, one workgroup per CU.
+// workgroup, one workgroup per CU.  The tables carry the read-out of lean_solo_readout_kernel<LPR> (the host's check
+// has seen its tag).
 // Items: (sample, step) = item / n_steps, item % n_steps for item < batch * n_steps; wave wv of workgroup b takes items
 // wv * gridDim.x + b, + gridDim.x * WAVES, ...: consecutive items go to consecutive CUs, every item is written exactly
 // once, by one wavefront, and no CU holds two items more than another.  Workgroup b exists only if item b does (the
 // host's grid is <= ceil(items / 8)): its wavefront 0 always has an item.
 constexpr int solo_threads(int waves) { return waves * kWave; }
-// linear_up's operands: the threads of wavefronts 1 .. WAVES - 1 take a pixel pair each, thread t of them the pairs
-// t, t + solo_loaders(WAVES), ..: one trip at 16 wavefronts, a second one at 8 for the images beyond 896 pixels
-constexpr int solo_loaders(int waves) { return (waves - 1) * kWave; }
+// linear_up's operands: every thread of every wavefront takes a pixel pair, thread t the pair t: at either width the
+// workgroup has a thread for every pair of the largest image, so the pairs take one trip
+constexpr int solo_loaders(int waves) { return waves * kWave; }
 constexpr int solo_pair_trips(int waves) { return (solo_pairs(kSoloMaxPixels) + solo_loaders(waves) - 1) / solo_loaders(waves); }
-static_assert(solo_pair_trips(16) == 1 && solo_pair_trips(8) == 2, "the pairs of the largest image: one trip at 16, two at 8");
+static_assert(solo_pair_trips(16) == 1 && solo_pair_trips(8) == 1, "the pairs of the largest image: one trip at both widths");
 static_assert(solo_pair_trips(16) * solo_loaders(16) >= solo_pairs_padded(kSoloMaxPixels) &&
                   solo_pair_trips(8) * solo_loaders(8) >= solo_pairs_padded(kSoloMaxPixels),
               "every pair of the largest image, pad pairs included, has a thread");
@@ -258,44 +368,27 @@ template <int LPR, int WAVES>
 __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
     const double* __restrict__ wu, const double* __restrict__ bu, double* __restrict__ y,
     const unsigned char* __restrict__ tables, const QuadScalars d, const KScalars p) {
-  constexpr int kThreads = solo_threads(WAVES);
-  using T = float;
-  using C = V2<T>;
-  using QT = LeanTables<T, 8>;
-  using V4 = T __attribute__((ext_vector_type(4)));
   using D2 = double __attribute__((ext_vector_type(2)));
   static_assert(LPR > 1, "a compiled-in layer count with at least one simulated layer");
-  // the layout simulated layer l (1 .. LPR - 1) starts in: they alternate, and the last one ends in A, where the
-  // read-out expects the state
-  auto layout_of = [](int l) { return (LPR - 1 - l) % 2 == 0 ? kSoloLayoutB : kSoloLayoutA; };
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int Q = d.out_features, PairsP = solo_pairs_padded(Q);
   D2* s_row = reinterpret_cast<D2*>(smem_raw);                                      // [PairsP]
-  double* s_ez = reinterpret_cast<double*>(smem_raw + LeanSoloLds::row_bytes(Q));    // [8]
-  T* s_un = reinterpret_cast<T*>(smem_raw + LeanSoloLds::row_bytes(Q) + LeanSoloLds::ez_bytes());   // [LPR][8]
-  C* s_ph = reinterpret_cast<C*>(smem_raw + LeanSoloLds::row_bytes(Q) + LeanSoloLds::ez_bytes() +
-                                 LeanSoloLds::un_bytes(LPR));                         // [LPR - 1][2][64][2]
-  static_assert(LeanSoloLds::row_bytes(1) % 16 == 0 && LeanSoloLds::ez_bytes() % 16 == 0 && LeanSoloLds::un_bytes(LPR) % 16 == 0,
-                "16-byte reads of the row, the read-out and the phase entries");
+  static_assert(LeanSoloLds::row_bytes(1) % 16 == 0, "16-byte reads of the row");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int llane = logical_lane(lane);
-  const T* g_body = reinterpret_cast<const T*>(tables + kLeanHeaderDoubles * sizeof(double));
-  const C* g_ph = reinterpret_cast<const C*>(g_body);
-  const T* g_un = g_body + QT::ph_elems(LPR);
-  const T* g_a0 = g_un + QT::un_elems(LPR);
   // diagnostics: wavefront 0 of workgroup 0 stamps s_memtime into words 0..7 (tools/stamp_lean_solo.py) -- [0] entry,
-  // [1] setup loads issued, [2] setup barrier passed, [3] simulation and read-out done (the eight <Z> are on their way to
-  // LDS), [4] row barrier passed (the row is in LDS), [5] the stores of its first item issued, [6] its last instruction,
-  // [7]: s_memrealtime (100 MHz) from entry to [6], which gives the ticks their length.
+  // [1] the loads of linear_up's operands and of the read-out issued, [4] row barrier passed (the row is in LDS),
+  // [5] the stores of its first item issued, [6] its last instruction, [7]: s_memrealtime (100 MHz) from entry to [6],
+  // which gives the ticks their length.
   // When the buffer holds 8 + 8 * gridDim.x words (d.stamp_words), wavefront 0 of EVERY workgroup b also stamps
   // s_memrealtime -- the same clock on every CU -- into words 8 + 8 b .. (tools/timeline_lean_solo.py): [0] entry,
-  // [1] setup barrier passed, [2] simulation and read-out done, [3] row barrier passed, [4] the stores of its first item
-  // issued, ([5] is not written,) [6] its last instruction; and the LAST wavefront of the workgroup (WAVES - 1, the
-  // youngest of its SIMD, which may have no item), [7] its last instruction.  With one more word per workgroup behind
-  // those (9 * gridDim.x in all) the last wavefront of workgroup b that HAD an item stamps its last instruction into
-  // word 8 + 8 * gridDim.x + b.  (Words [0], [1], [6], [7] and the ninth are where the body that simulated every item
-  // had them, so the tools read either library.)
+  // [1] loads issued, [3] row barrier passed, [4] the stores of its first item issued, ([2] and [5] are not written,)
+  // [6] its last instruction; and the LAST wavefront of the workgroup (WAVES - 1, the youngest of its SIMD, which may
+  // have no item), [7] its last instruction.  With one more word per workgroup behind those (9 * gridDim.x in all) the
+  // last wavefront of workgroup b that HAD an item stamps its last instruction into word 8 + 8 * gridDim.x + b.
+  // (Against the kernel that simulated in every workgroup no word moved: words [1] took the place of that kernel's
+  // "setup loads issued" / "setup barrier passed", and its words [2], [3] (setup barrier, end of the simulation) and
+  // timeline word [2] (end of the simulation) are gone with what they marked -- the tools read either library.)
   // The test is wave-uniform (a scalar branch per stamp); lane 0 stores.
   const bool stamp_timeline = d.stamps != nullptr && (int64_t)d.stamp_words >= solo_timeline_words(gridDim.x);
   const bool stamp_last_item = stamp_timeline && (int64_t)d.stamp_words >= solo_timeline_words(gridDim.x) + (int64_t)gridDim.x;
@@ -316,152 +409,69 @@ __global__ __launch_bounds__(solo_threads(WAVES)) void dense_lean_solo_kernel(
   };
   stamp(0, 0);
 
-  // ---- per-launch setup ----------------------------------------------------------------------------------------------
-  // The workgroup fetches everything ONCE -- the phase entries of the 13 simulated layers (26 KiB, gathered into the
-  // lanes' own order) and the tangents -- and hands it over through LDS; behind the barrier every wavefront reads a
-  // layer's entries from the LDS copy with two 16-byte reads, one layer ahead.  (Each wavefront used to read the whole
-  // phase table from global memory itself: eight times the bytes through the CU's vector L1, which took longer than an
-  // item's layers; then it kept all 13 layers' entries in 104 registers, which held a SIMD to two wavefronts.)
-  // Every global load of it is issued before anything waits.  linear_up's weights and bias (56 KiB at 784 pixels) are
-  // NOT in front of that barrier, where they doubled the setup (2.0 against 1.0 us): wavefronts 1 .. WAVES - 1 load them
-  // behind it, under wavefront 0's layers.
-  constexpr int kPhEntries = (LPR - 1) * QT::TL;                                  // phase entries of layers 1 .. LPR - 1
-  constexpr int kPhTrips = (kPhEntries + kThreads - 1) / kThreads;
-  C phstage[kPhTrips];
-#pragma unroll
-  for (int k = 0; k < kPhTrips; ++k) {
-    // LDS entry e = ((l - 1) * 2 + h) * 128 + lane * 2 + j: register r = 2 h + j of `lane` in layer l
-    // (an entry beyond the table loads entry 0 and is not stored: no branch around a load, which would wait inside)
-    const int e = tid + k * kThreads, ec = e < kPhEntries ? e : 0;
-    const int l = (ec >> 8) + 1, r = ((ec >> 6) & 2) | (ec & 1), ln = (ec >> 1) & 63;
-    phstage[k] = g_ph[l * QT::TL + solo_table_slot(layout_of(l), r, ln)];
-  }
-  const T unreg = g_un[tid < LPR * 8 ? tid : 0];
-  T a0r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) a0r[r] = g_a0[solo_table_slot(layout_of(1), r, lane)];
-  __builtin_amdgcn_sched_barrier(0);   // (all loads are out)
-  stamp(1, -1);
-#pragma unroll
-  for (int k = 0; k < kPhTrips; ++k) {
-    const int e = tid + k * kThreads;
-    if (e < kPhEntries) s_ph[e] = phstage[k];
-  }
-  static_assert(LPR * 8 <= kThreads, "one tangent per thread");
-  if (tid < LPR * 8) s_un[tid] = unreg;
-  T pm[4];   // +-1 by this lane's index bit
-#pragma unroll
-  for (int q = 0; q < 4; ++q) pm[q] = ((llane >> q) & 1) ? (T)1 : (T)-1;
-  __syncthreads();
-  stamp(2, 1);
-
-  // ---- one simulation (wavefront 0) beside the loads of linear_up's operands (the others), then one row --------------
-  // (the barriers inside the two branches are the same workgroup barrier: every wavefront meets it once, with or
-  //  without an item)
+  // ---- the workgroup's one row ---------------------------------------------------------------------------------------
+  // A thread takes a pair: the pair's two rows of w_up are 128 contiguous bytes, eight 16-byte chunks (chunk u = the
+  // weights (w[2 k], w[2 k + 1]), k = u & 3, of row 2 pr + (u >> 2)), and its two biases.  A chunk or a bias beyond
+  // the image loads the last one; its pixel is never stored.  The 64 pairs of a wavefront are all inside the padded
+  // row or all beyond it (a wave-uniform test): a wavefront beyond it loads nothing.  (Q <= kSoloMaxPixels: the host
+  // checks.)  The eight <Z> come from the tables' header, the same 32 bytes for every thread.  Every load is issued
+  // before anything waits.
   constexpr int kLoaders = solo_loaders(WAVES), kPairTrips = solo_pair_trips(WAVES);
-  if (wv == 0) {
-    C a[4];
+  const D2* wu2 = reinterpret_cast<const D2*>(wu);
+  D2 wreg[kPairTrips][8], breg[kPairTrips];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) a[r] = C{a0r[r], (T)0};
-    // a layer's tangents and this lane's phase entries (two 16-byte units: registers 0, 1 and 2, 3) are read one layer
-    // ahead (the fence keeps the compiler from reading all layers' up front)
-    const V4* un4 = reinterpret_cast<const V4*>(s_un);
-    const V4* ph4 = reinterpret_cast<const V4*>(s_ph) + lane;
-    V4 lo = un4[2], hi = un4[3], p01 = ph4[0], p23 = ph4[kWave];
+  for (int k = 0; k < kPairTrips; ++k) {
+    const int pr = tid + k * kLoaders;
+    if (pr < PairsP) {
 #pragma unroll
-    for (int l = 1; l < LPR; ++l) {
-      const int ln = l + 1 < LPR ? l + 1 : l;
-      const V4 nlo = un4[2 * ln], nhi = un4[2 * ln + 1];
-      const V4 np01 = ph4[(ln - 1) * 2 * kWave], np23 = ph4[((ln - 1) * 2 + 1) * kWave];
-      __builtin_amdgcn_sched_barrier(0);
-      const T ts[4] = {lo.x * pm[0], lo.y * pm[1], lo.z * pm[2], lo.w * pm[3]};
-      const C ph[4] = {C{p01.x, p01.y}, C{p01.z, p01.w}, C{p23.x, p23.y}, C{p23.z, p23.w}};
-      solo_layer(layout_of(l), a, ph, ts, hi.x, hi.y, hi.z, hi.w);
-      lo = nlo;
-      hi = nhi;
-      p01 = np01;
-      p23 = np23;
-    }
-    // ---- <Z_w>: the register-bit wires are signed in-lane sums, the lane-bit wires signed copies of the lane's total ----
-    T pw[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) pw[r] = a[r].x * a[r].x + a[r].y * a[r].y;
-    const T pt = (pw[0] + pw[1]) + (pw[2] + pw[3]);
-    T ez[8];
-    ez[0] = (pw[0] + pw[1]) - (pw[2] + pw[3]);   // wire 0 = index bit 7 = register bit 1
-    ez[1] = (pw[0] + pw[2]) - (pw[1] + pw[3]);   // wire 1 = index bit 6 = register bit 0
-#pragma unroll
-    for (int w = 2; w < 8; ++w) ez[w] = ((llane >> (7 - w)) & 1) ? -pt : pt;
-    const T tot = wave_reduce8<T>(ez, lane, llane);
-    // (the lane of logical number 4 b0 + 2 b1 + b2 -> wire b0 b1 b2 holds that wire's total: qsim_adjoint.h)
-    double ev[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w)
-      ev[w] = (double)read_lane(tot, logical_lane(((w >> 2) & 1) | (w & 2) | ((w & 1) << 2)));
-    if (lane == 0) {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) s_ez[w] = ev[w];
-    }
-    stamp(3, 2);
-    __syncthreads();
-  } else {
-    // A thread takes a pair: the pair's two rows of w_up are 128 contiguous bytes, eight 16-byte chunks (chunk u = the
-    // weights (w[2 k], w[2 k + 1]), k = u & 3, of row 2 pr + (u >> 2)), and its two biases.  A chunk or a bias beyond
-    // the image loads the last one; its pixel is never stored.  The 64 pairs of a wavefront are all inside the padded
-    // row or all beyond it (a wave-uniform test): a wavefront beyond it loads nothing.  (Q <= kSoloMaxPixels: the host
-    // checks.)
-    const int t = tid - kWave;
-    const D2* wu2 = reinterpret_cast<const D2*>(wu);
-    D2 wreg[kPairTrips][8], breg[kPairTrips];
-#pragma unroll
-    for (int k = 0; k < kPairTrips; ++k) {
-      const int pr = t + k * kLoaders;
-      if (pr < PairsP) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int i = 8 * pr + u;
-          wreg[k][u] = wu2[i < 4 * Q ? i : 4 * Q - 1];
-        }
-        const int i0 = 2 * pr < Q ? 2 * pr : Q - 1, i1 = 2 * pr + 1 < Q ? 2 * pr + 1 : Q - 1;
-        breg[k] = bu != nullptr ? D2{bu[i0], bu[i1]} : D2{0.0, 0.0};
+      for (int u = 0; u < 8; ++u) {
+        const int i = 8 * pr + u;
+        wreg[k][u] = wu2[i < 4 * Q ? i : 4 * Q - 1];
       }
-    }
-    __syncthreads();   // (the eight <Z> are in LDS)
-    double ev[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) ev[w] = s_ez[w];
-    // ---- linear_up: per pixel two partial sums with explicit fma (as dense_lean_kernel) and one add ------------------
-#pragma unroll
-    for (int k = 0; k < kPairTrips; ++k) {
-      const int pr = t + k * kLoaders;
-      if (pr < PairsP) {
-        const D2 wa0 = wreg[k][0], wa1 = wreg[k][1], wa2 = wreg[k][2], wa3 = wreg[k][3];
-        const D2 wb0 = wreg[k][4], wb1 = wreg[k][5], wb2 = wreg[k][6], wb3 = wreg[k][7];
-        const D2 bias = breg[k];
-        double a0 = bias.x, a1 = 0.0, b0 = bias.y, b1 = 0.0;
-        a0 = fma(ev[0], wa0.x, a0);
-        a1 = fma(ev[1], wa0.y, a1);
-        a0 = fma(ev[2], wa1.x, a0);
-        a1 = fma(ev[3], wa1.y, a1);
-        a0 = fma(ev[4], wa2.x, a0);
-        a1 = fma(ev[5], wa2.y, a1);
-        a0 = fma(ev[6], wa3.x, a0);
-        a1 = fma(ev[7], wa3.y, a1);
-        a0 += a1;
-        b0 = fma(ev[0], wb0.x, b0);
-        b1 = fma(ev[1], wb0.y, b1);
-        b0 = fma(ev[2], wb1.x, b0);
-        b1 = fma(ev[3], wb1.y, b1);
-        b0 = fma(ev[4], wb2.x, b0);
-        b1 = fma(ev[5], wb2.y, b1);
-        b0 = fma(ev[6], wb3.x, b0);
-        b1 = fma(ev[7], wb3.y, b1);
-        b0 += b1;
-        s_row[pr] = D2{a0, b0};
-      }
+      const int i0 = 2 * pr < Q ? 2 * pr : Q - 1, i1 = 2 * pr + 1 < Q ? 2 * pr + 1 : Q - 1;
+      breg[k] = bu != nullptr ? D2{bu[i0], bu[i1]} : D2{0.0, 0.0};
     }
   }
-  __syncthreads();   // (the row is in LDS)
+  const float* g_ez = reinterpret_cast<const float*>(tables + kLeanReadoutDouble * sizeof(double));
+  float ezf[8];
+#pragma unroll
+  for (int w = 0; w < 8; ++w) ezf[w] = g_ez[w];
+  __builtin_amdgcn_sched_barrier(0);   // (all loads are out)
+  stamp(1, 1);
+  double ev[8];
+#pragma unroll
+  for (int w = 0; w < 8; ++w) ev[w] = (double)ezf[w];
+  // ---- linear_up: per pixel two partial sums with explicit fma (as dense_lean_kernel) and one add --------------------
+#pragma unroll
+  for (int k = 0; k < kPairTrips; ++k) {
+    const int pr = tid + k * kLoaders;
+    if (pr < PairsP) {
+      const D2 wa0 = wreg[k][0], wa1 = wreg[k][1], wa2 = wreg[k][2], wa3 = wreg[k][3];
+      const D2 wb0 = wreg[k][4], wb1 = wreg[k][5], wb2 = wreg[k][6], wb3 = wreg[k][7];
+      const D2 bias = breg[k];
+      double a0 = bias.x, a1 = 0.0, b0 = bias.y, b1 = 0.0;
+      a0 = fma(ev[0], wa0.x, a0);
+      a1 = fma(ev[1], wa0.y, a1);
+      a0 = fma(ev[2], wa1.x, a0);
+      a1 = fma(ev[3], wa1.y, a1);
+      a0 = fma(ev[4], wa2.x, a0);
+      a1 = fma(ev[5], wa2.y, a1);
+      a0 = fma(ev[6], wa3.x, a0);
+      a1 = fma(ev[7], wa3.y, a1);
+      a0 += a1;
+      b0 = fma(ev[0], wb0.x, b0);
+      b1 = fma(ev[1], wb0.y, b1);
+      b0 = fma(ev[2], wb1.x, b0);
+      b1 = fma(ev[3], wb1.y, b1);
+      b0 = fma(ev[4], wb2.x, b0);
+      b1 = fma(ev[5], wb2.y, b1);
+      b0 = fma(ev[6], wb3.x, b0);
+      b1 = fma(ev[7], wb3.y, b1);
+      b0 += b1;
+      s_row[pr] = D2{a0, b0};
+    }
+  }
+  __syncthreads();   // (the row is in LDS: the kernel's one barrier)
   stamp(4, 3);
 
   // ---- the items of this wave: stores only ---------------------------------------------------------------------------

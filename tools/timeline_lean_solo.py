@@ -1,28 +1,30 @@
 #!/usr/bin/env python
 """Diagnostic: the timeline of one launch of the one-wavefront-per-item kernel (csrc/qsim_lean_solo.h) over ALL its
 workgroups.  With a stamp buffer of 8 + 9 x (workgroups) words registered, wavefront 0 of every workgroup writes
-s_memrealtime -- a 100 MHz clock that is the same on every CU -- at its entry, behind the setup's barrier, when its
-simulation and read-out are done, behind the barrier that puts the workgroup's one row into LDS, when the stores of its
-first item are issued, and as its last instruction; the workgroup's LAST wavefront (WAVES - 1, the youngest of its SIMD,
-which may have no item) stamps its last instruction too, and so does the last wavefront of the workgroup that had an
-item (the ninth word).  Printed, in us (one tick = 0.01 us):
+s_memrealtime -- a 100 MHz clock that is the same on every CU -- at its entry, when the loads of linear_up's operands
+and of the tabulated read-out are issued, behind the barrier that puts the workgroup's one row into LDS, when the stores
+of its first item are issued, and as its last instruction; the workgroup's LAST wavefront (WAVES - 1, the youngest of
+its SIMD, which may have no item) stamps its last instruction too, and so does the last wavefront of the workgroup that
+had an item (the ninth word).  Printed, in us (one tick = 0.01 us):
 dispatch skew (first entry -> last entry), the distribution of the workgroups' lifetimes and of their phases -- the
-simulation, the row, the store stream (row barrier passed -> exit of the last wavefront with an item) --, first entry ->
-last exit, the kernel's duration from HIP events around the same launch replayed back to back in a graph, and the
-difference of the last two: the time of a launch that no stamped wavefront accounts for; and the store stream's rate:
-the launch's bytes over the time from the first workgroup's row barrier, and from the median workgroup's, to the last
-exit.  The stamped wavefronts are two or three of the 8 or 16 of their workgroup; the others may leave later than
-wavefront 0, hardly later than the last one.  QNN_noise(784, 8, 14), float32, the solo kernel forced; the benchmark
-launch (batch 256, 15 steps) and a 240-item launch.  --waves 8 / 16 forces the kernel's width (QIDDM_LEAN_SOLO_WAVES);
-without it the host's rule holds (8 while items <= 8 x CUs, 16 above).  --every-item: the library is one whose kernel
-simulated every item (words 2 .. 5 are then the ends of the layers and of the tail of wavefront 0's first two items;
-entry, setup barrier, exits and the ninth word are where they are now), for a timeline of such a library beside this
-one's.
-    python tools/timeline_lean_solo.py [--waves 8|16] [--every-item]"""
+loads' issue, the row, entry -> first item's stores issued, the store stream (row barrier passed -> exit of the last
+wavefront with an item) --, first entry -> last exit, the kernel's duration from HIP events around the same launch
+replayed back to back in a graph, and the difference of the last two: the time of a launch that no stamped wavefront
+accounts for; and the store stream's rate: the launch's bytes over the time from the first workgroup's row barrier, and
+from the median workgroup's, to the last exit.  The stamped wavefronts are two or three of the 8 or 16 of their
+workgroup; the others may leave later than wavefront 0, hardly later than the last one.  QNN_noise(784, 8, 14),
+float32, the solo kernel forced; the benchmark launch (batch 256, 15 steps) and a 240-item launch.  --waves 8 / 16
+forces the kernel's width (QIDDM_LEAN_SOLO_WAVES); without it the host's rule holds (8 while items <= 8 x CUs, 16
+above).  For a timeline of an earlier library (QIDDM_HIP_LIB) beside this one's: --simulating, its kernel simulated the
+circuit once per workgroup (word 1 is then the setup barrier, word 2 the end of the simulation; entry, row barrier,
+first stores, exits and the ninth word are where they are now); --every-item, its kernel simulated every item (words
+2 .. 5 are then the ends of the layers and of the tail of wavefront 0's first two items).
+    python tools/timeline_lean_solo.py [--waves 8|16] [--simulating | --every-item]"""
 import argparse, os, sys
 ap = argparse.ArgumentParser()
 ap.add_argument("--waves", type=int, choices=(8, 16), default=None)
 ap.add_argument("--every-item", action="store_true")
+ap.add_argument("--simulating", action="store_true")
 args = ap.parse_args()
 os.environ["QIDDM_LEAN_SOLO_MIN_ITEMS"] = "0"
 if args.waves:
@@ -44,11 +46,17 @@ bu = torch.rand(P, dtype=torch.float64).cuda()
 w = (torch.randn(1, 1, 14, n, 3, dtype=torch.float64) * 0.6).cuda()
 tables = dense_sample_lean_tables(circ, w, wd, bd, wu, bu, "f32")
 cus = torch.cuda.get_device_properties(0).multi_processor_count
+# (name, from word, to word) of wavefront 0's timeline words; the last one is what follows its last stamp
 if args.every_item:
-    NAMES = ["entry -> barrier passed", "item 0 layers", "item 0 tail", "item 1 layers", "item 1 tail", "-> last instruction"]
+    PHASES = [("entry -> barrier passed", 0, 1), ("item 0 layers", 1, 2), ("item 0 tail", 2, 3), ("item 1 layers", 3, 4),
+              ("item 1 tail", 4, 5)]
+elif args.simulating:
+    PHASES = [("entry -> setup barrier passed", 0, 1), ("simulation and read-out", 1, 2), ("row (two barriers around it)", 2, 3),
+              ("row read, first item's stores issued", 3, 4), ("entry -> first item's stores issued", 0, 4)]
 else:
-    NAMES = ["entry -> setup barrier passed", "simulation and read-out", "row (two barriers around it)",
-             "row read, first item's stores issued", "-> last instruction"]
+    PHASES = [("entry -> loads issued", 0, 1), ("loads, row, the one barrier", 1, 3),
+              ("row read, first item's stores issued", 3, 4), ("entry -> first item's stores issued", 0, 4)]
+LAST = "-> last instruction"
 
 
 def dist(v):
@@ -88,12 +96,12 @@ for batch, steps in ((256, 15), (16, 15)):
             print(f"    wavefront 0's entry -> wavefront {WAVES - 1}'s exit {dist((t[:, 7] - t[:, 0]).tolist())}")
         if (last_item > 0).all():
             print(f"    ... -> exit of the last one with an item {dist((last_item - t[:, 0]).tolist())}")
-        for k, name in enumerate(NAMES[:-1]):
-            have = (t[:, k] > 0) & (t[:, k + 1] > 0)
+        for name, a, b in PHASES:
+            have = (t[:, a] > 0) & (t[:, b] > 0)
             if have.any():
-                print(f"    {name:38s}  {dist((t[have, k + 1] - t[have, k]).tolist())}   ({int(have.sum())} workgroups)")
+                print(f"    {name:38s}  {dist((t[have, b] - t[have, a]).tolist())}   ({int(have.sum())} workgroups)")
         # (behind the last stamp wavefront 0 took: its later items, if it has any, and the way out)
-        print(f"    {'last stamp ' + NAMES[-1]:38s}  {dist((t[:, 6] - t[:, 1:6].max(dim=1).values).tolist())}")
+        print(f"    {'last stamp ' + LAST:38s}  {dist((t[:, 6] - t[:, 1:6].max(dim=1).values).tolist())}")
         if not args.every_item and (t[:, 3] > 0).all():
             out = torch.maximum(t[:, 6:8].max(dim=1).values, last_item if (last_item > 0).all() else t[:, 6])
             print(f"    {'store stream (row barrier -> exit)':38s}  {dist((out - t[:, 3]).tolist())}")
